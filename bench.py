@@ -17,6 +17,10 @@ standard-library socket group (victor_amd/rendezvous.py), the data path is libvi
 After the weak-scaling line's timed loop a multi-GPU run also times a fixed global batch (65536 points in total,
 `strong_scaling`) and every GPU's copy of the gathered lnL vector is checked against local recomputation of rows from every
 other shard.
+
+`--dump-outputs DIR` writes what the last timed step computed, as a caller of the path receives it: `DIR/lnl.npy` and
+`DIR/chi2.npy`, float64, one entry per point of the global batch in Halton order (a seeded sample of the points when the two
+arrays would exceed DUMP_LIMIT_BYTES).  The inputs depend on the arguments alone, so two builds can be compared output for output.
 """
 
 import argparse
@@ -45,6 +49,22 @@ EXIT_LEG_FAILED = 2
 EXIT_LEG_HUNG = 3
 LEG_TIMEOUT = 300.0              # seconds the N > 1 legs (configs 4 and 5) may take together before rank 0 prints its line without them
 REAL_STDOUT = os.dup(1)          # the stdout this program was started with
+DUMP_LIMIT_BYTES = 64 << 20      # --dump-outputs: at most this much in all
+DUMP_SEED = 0                    # --dump-outputs: the sample of points taken when the whole batch exceeds DUMP_LIMIT_BYTES
+
+
+def dump_outputs(out_dir, arrays):
+    """Write ``arrays`` ({name: 1-D array over the global batch}) as ``out_dir/<name>.npy`` in float64; above DUMP_LIMIT_BYTES
+    the same seeded sample of rows (sorted, fixed for a given batch size) is taken from every array."""
+    import numpy as np
+    n = len(next(iter(arrays.values())))
+    keep = DUMP_LIMIT_BYTES // (8 * len(arrays))
+    rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, keep, replace=False)) if n > keep else slice(None)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64)[rows])
+    print(f"outputs of the last timed step: {', '.join(arrays)} ({n} points{', sampled' if n > keep else ''}) in {out_dir}",
+          file=sys.stderr)
 
 
 def clock_pass(args):
@@ -110,7 +130,11 @@ def main():
     ap.add_argument("--simpson-even", default="simpson",
                     help="even-N Simpson convention of the velocity integral: 'simpson' (SciPy >= 1.11, default) or "
                          "'avg' (SciPy < 1.11); same cost, recorded in config.simpson_even")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write lnL and chi2 of the last timed step as DIR/lnl.npy and DIR/chi2.npy (float64, global batch order)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.clock_pass:
         return clock_pass(args)
 
@@ -253,6 +277,14 @@ def main():
             good = good and bool(np.max(np.abs(gathered[other * B + probe] - own_l)) <= 1e-9 * np.max(np.abs(own_l)))
     if gather != "none":
         gathered_ok = bool(dist.min_float(1.0 if good else 0.0))
+    if args.dump_outputs:
+        # every slot's lnL and chi2 from the last timed step, in global batch order (slot g holds points [g*B, (g+1)*B))
+        dumped = {"lnl": np.concatenate([s.eng.download(s.d_lnl, B) for s in slots]),
+                  "chi2": np.concatenate([s.eng.download(s.d_chi, B) for s in slots])}
+        if launched:
+            dumped = {k: dist.allgather_host(v, len(v)) for k, v in dumped.items()}
+        if rank == 0:
+            dump_outputs(args.dump_outputs, dumped)
     k_local = np.array([p[0] for p in per_slot])
     kernel_ms_ranks = (dist.allgather_host(k_local, len(k_local)) if launched else k_local).tolist() if total > 1 or launched else None
 

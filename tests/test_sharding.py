@@ -6,9 +6,11 @@ and the reassembly in batch order - the parts that differ between 1 and N ranks.
 """
 
 import os
+import shutil
 import socket
 import subprocess
 import sys
+import tempfile
 
 import numpy as np
 import pytest
@@ -16,6 +18,15 @@ import pytest
 from victor_amd.sharding import padded_chunk, shard_bounds, unpad
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture
+def sock_dir():
+    """A short directory for Unix socket files: a socket's path must fit sun_path (107 bytes), which pytest's ``tmp_path``
+    exceeds wherever the temporary root is deep."""
+    d = tempfile.mkdtemp(prefix="vk", dir="/tmp")
+    yield d
+    shutil.rmtree(d, ignore_errors=True)
 
 
 @pytest.mark.parametrize("n", [0, 1, 2, 7, 8, 9, 1024, 65536, 65537])
@@ -227,11 +238,11 @@ def test_every_rank_of_a_job_chooses_the_same_endpoint(monkeypatch):
     assert rz.endpoint({"MASTER_ADDR": "localhost", "MASTER_PORT": "1234"})[0] == "unix"
 
 
-def test_collectives_outlive_the_handshake_timeout(tmp_path):
+def test_collectives_outlive_the_handshake_timeout(sock_dir):
     """The handshake timeout must not govern the collectives after it: ranks may be far apart (one of them compiling the
     library) - here rank 1 arrives at the barrier later than the whole handshake timeout."""
     import multiprocessing as mp
-    where = ("unix", str(tmp_path / "late.sock"))
+    where = ("unix", os.path.join(sock_dir, "late.sock"))
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     procs = [ctx.Process(target=_late_rank, args=(r, where, q)) for r in range(2)]
@@ -257,12 +268,12 @@ def _late_rank(rank, where, q):
         q.put((rank, repr(exc)))
 
 
-def test_socket_group_collectives_with_three_ranks(tmp_path):
+def test_socket_group_collectives_with_three_ranks(sock_dir):
     """Three ranks as threads of one process over a Unix socket and over TCP: all-gather of bytes, broadcast, barrier,
     max / min, doubles of unequal lengths; a stray connection that does not speak the protocol is ignored."""
     import threading
     from victor_amd.rendezvous import SocketGroup
-    for where in (("unix", str(tmp_path / "g.sock")), ("tcp", ("127.0.0.1", _free_port()))):
+    for where in (("unix", os.path.join(sock_dir, "g.sock")), ("tcp", ("127.0.0.1", _free_port()))):
         results, errors = {}, []
 
         def run(rank):
@@ -296,12 +307,12 @@ def test_socket_group_collectives_with_three_ranks(tmp_path):
             assert (mx, mn) == (2.0, 0.0) and dbl == [1.0, 2.0, 2.0]
 
 
-def test_socket_group_reports_ranks_that_are_out_of_step(tmp_path):
+def test_socket_group_reports_ranks_that_are_out_of_step(sock_dir):
     """One rank calls a barrier where the other calls max_float (a branch only one of them took): both get a RuntimeError
     naming the two calls, instead of hanging or reading each other's payload as their own."""
     import threading
     from victor_amd.rendezvous import SocketGroup
-    where = ("unix", str(tmp_path / "oos.sock"))
+    where = ("unix", os.path.join(sock_dir, "oos.sock"))
     errors = {}
 
     def run(rank):
@@ -348,7 +359,7 @@ print("ok", dist.rank)
 """
 
 
-def test_eight_launched_ranks_meet_and_gather(tmp_path):
+def test_eight_launched_ranks_meet_and_gather(tmp_path, sock_dir):
     """The host side of `python -m torch.distributed.run --nproc-per-node 8 bench.py --gpus 8`, without the GPUs: eight
     processes with the launcher's environment (RANK, LOCAL_RANK, WORLD_SIZE, MASTER_ADDR, MASTER_PORT) find each other through
     Dist().connect() - the Unix socket derived from MASTER_PORT - and run bench.py's sequence of host collectives, including
@@ -361,7 +372,7 @@ def test_eight_launched_ranks_meet_and_gather(tmp_path):
     procs = []
     for r in range(8):
         env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE="8", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
-                   TORCHELASTIC_RUN_ID=f"t{port}", TMPDIR=str(tmp_path))
+                   TORCHELASTIC_RUN_ID=f"t{port}", TMPDIR=sock_dir)
         env.pop("VICTOR_RDZV", None)
         procs.append(subprocess.Popen([sys.executable, str(script), ROOT], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     try:
