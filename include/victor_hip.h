@@ -13,6 +13,8 @@
  *   vk_theory_batch      CCFModel.theory_multipoles   victor/ccf_model.py:791-827
  *                        (+ utils.multipoles_from_fn  victor/utils.py:9-58)
  *   vk_xi_smu_batch      CCFModel.theory_xi           victor/ccf_model.py:538-789
+ *   vk_eval_realisations CCFFit.log_likelihood against every simulation realisation of the
+ *                        data file (simulation_number, victor/ccf_fit.py:59-61,93-100)
  *   vk_create            CCFModel.__init__ / CCFFit.__init__ table set-up
  *                        victor/ccf_model.py:33-97, victor/ccf_fit.py:15-42
  *                        (the host has already turned every spline into explicit
@@ -36,7 +38,7 @@
 extern "C" {
 #endif
 
-#define VK_ABI_VERSION 18
+#define VK_ABI_VERSION 19
 
 /* error codes */
 #define VK_OK 0
@@ -360,6 +362,23 @@ void vk_walk_destroy(vk_walk* w);
  * evaluates them on Python floats (ccf_model.py:589-592): the one routine behind every row the package forms from an epsilon.
  * Pure host arithmetic: no context, no GPU. */
 void vk_epsilon_to_ap(const double* eps, int64_t n, double alpha, double* aperp, double* apar);
+
+/* ---- one parameter batch against many simulation realisations of the data vector ---------------------------------------
+ * The reference reads ONE realisation of a stacked data file, the one `simulation_number` names (victor/ccf_fit.py:59-61,
+ * 93-100); validating a model on mocks evaluates the same points against every realisation.  The theory vector of a point does
+ * not depend on the realisation: it is computed once, then compared with each data vector under the context's covariance
+ * (victor/ccf_fit.py:349-354 for chi2, :166-193 for the data vector at beta, :195-260 and :444-481 for the precision, the log
+ * determinant, the likelihood forms and the (-inf, inf) guards - the same arithmetic as vk_eval_batch, summed in another order).
+ * vk_set_realisations: n_real blocks back to back, each with exactly the layout of vk_tables.data ([N] for a fixed data vector,
+ *   the PCHIP pieces [n_beta_d-1][N][4] otherwise); copied to the device, resident until replaced or vk_destroy (n_real = 0
+ *   releases them).  The context must have been created with a data vector.
+ * vk_eval_realisations: which == NULL - every point against every realisation, lnl / chi2 [n][n_real]; otherwise which[i] is
+ *   the realisation (0 .. n_real-1) of point i and lnl / chi2 are [n].  Both modes return the same bits for the same (point,
+ *   realisation).  Either output may be NULL.  VK_E_ARG when no realisations are set or an index is out of range.  Synchronous;
+ *   large batches are cut into launches whose outputs stay below 256 MB. */
+int vk_set_realisations(vk_ctx* ctx, const double* data, int32_t n_real);
+int vk_eval_realisations(vk_ctx* ctx, const vk_eval_opts* opts, const double* params, int64_t n, const int32_t* which,
+                         double* lnl, double* chi2);
 
 /* Theory multipoles on a caller-supplied s grid: out[n][n_ell][n_s] with the caller's own
  * projection weights w_ell[n_ell][n_mu] on mu[n_mu] (host buffers). */

@@ -11,7 +11,7 @@ import os
 
 import numpy as np
 
-VK_ABI_VERSION = 18
+VK_ABI_VERSION = 19
 VK_NPAR = 12
 (P_FSIGMA8, P_SIGMAV, P_APERP, P_APAR, P_EPSILON, P_BETA, P_ASTAR, P_M, P_Q, P_BIAS, P_AV, P_SPARE) = range(12)
 MATTER = {"template": 0, "linear_bias": 1, "velocity_template": 2}
@@ -119,6 +119,8 @@ SYMBOLS = {
     "vk_epsilon_to_ap": (None, [_dp, C.c_int64, C.c_double, _dp, _dp]),
     "vk_theory_batch": (C.c_int, [_vp, _optp, _dp, C.c_int64, _dp, C.c_int32, _dp, C.c_int32, _dp, C.c_int32, _dp]),
     "vk_xi_smu_batch": (C.c_int, [_vp, _optp, _dp, C.c_int64, _dp, C.c_int32, _dp, C.c_int32, _dp]),
+    "vk_set_realisations": (C.c_int, [_vp, _dp, C.c_int32]),
+    "vk_eval_realisations": (C.c_int, [_vp, _optp, _dp, C.c_int64, C.POINTER(C.c_int32), _dp, _dp]),
     "vk_device_alloc": (_vp, [_vp, C.c_size_t]),
     "vk_device_free": (None, [_vp, _vp]),
     "vk_memcpy_h2d": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),

@@ -44,6 +44,7 @@ class CCFFit(CCFModel):
             if not os.path.isfile(fn):
                 raise InputError(f"Data file {fn} not found")
         self._load_redshiftspace_ccf(data["redshift_space_ccf"], data_fn)
+        self._data_source = (data_fn, dict(data["redshift_space_ccf"]))     # what realisations() reads the stack from
         self._load_covariance_matrix(data["covariance_matrix"], cov_fn)
         self.fit_options = {"beta_interpolation": data.get("beta_interpolation", "datavector"),
                             "likelihood": data.get("likelihood", {"form": "Gaussian"})}
@@ -297,6 +298,12 @@ class CCFFit(CCFModel):
             return lnl, chi2
         lnl, chi2, _ = self._run(params, kwargs)
         return lnl, chi2
+
+    def realisations(self, simulation_numbers=None):
+        """Every simulation realisation of this fit's data file (or the listed ``simulation_numbers``) against one model:
+        :class:`victor_amd.realisations.Realisations`.  The fit must have been built with an integer ``simulation_number``."""
+        from .realisations import Realisations
+        return Realisations(self, simulation_numbers)
 
     def theory_vector_batch(self, params, **kwargs):
         """Theory vectors (n, N) on the data's own s grid and multipoles."""

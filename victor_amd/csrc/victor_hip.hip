@@ -13,13 +13,15 @@
 //                        yardstick of tools/ and of the mapping tests, compiled into the DEVELOPMENT build only (VK_DEV_LANES)
 //   vk_kernel_cells.h    K1 cells (workgroup = point, lanes over (s, mu) cells, v loop innermost; per-point tables)
 //   vk_kernel_like.h     K2 residual . precision . residual, log det, likelihood form, NaN guard
+//   vk_kernel_real.h     K2 against many realisations of the data vector (vk_eval_realisations): f64 MFMA, one point per workgroup
 //
 // K1 restates CCFModel.theory_xi (streaming branch victor/ccf_model.py:589-690; the other branches :658-784),
 // theory_multipoles (:816-825) and utils.multipoles_from_fn (victor/utils.py:45-56); K2 restates CCFFit.chi_squared
 // (victor/ccf_fit.py:349-354), get_interpolated_{covariance,precision} (:195-260) and log_likelihood (:444-481).
 // All arithmetic is IEEE binary64 on the vector ALU: an evaluation is n_s*n_mu*n_x (= 200 000) integrand points of
 // ~80 FP64 instructions each against ~100 bytes of HBM traffic, so the kernels are laid out for VALU issue and LDS
-// gather bandwidth, not for HBM or MFMA.  launch_theory() picks the K1 variant per call.
+// gather bandwidth, not for HBM or MFMA - except the chi-square against many realisations, a batched
+// matrix product on the FP64 matrix cores.  launch_theory() picks the K1 variant per call.
 
 #include <hip/hip_runtime.h>
 #include <chrono>
@@ -48,6 +50,7 @@
 #include "vk_kernel_lanes.h"
 #endif
 #include "vk_kernel_like.h"
+#include "vk_kernel_real.h"
 
 // The theory kernels' instantiations are generated in translation units of their own (vk_instances.h names what lives where);
 // here they are declared only.
@@ -174,6 +177,7 @@ void load_knobs(vk_ctx* ctx) {
   if (const char* env = getenv("VICTOR_HIP_MAPPING"))
     k.mapping = !strcmp(env, "point") ? 1 : !strcmp(env, "cells") ? 2 : !strcmp(env, "lanes") ? 3 : -1;
   k.like_untiled = getenv("VICTOR_HIP_LIKE_UNTILED") != nullptr;
+  k.real_valu = getenv("VICTOR_HIP_REAL_VALU") != nullptr;
   k.no_graph = getenv("VICTOR_HIP_NO_GRAPH") != nullptr;
   k.no_fuse = getenv("VICTOR_HIP_NO_FUSE") != nullptr;
   k.no_inline_row = getenv("VICTOR_HIP_NO_INLINE_ROW") != nullptr;
@@ -1307,6 +1311,7 @@ void vk_destroy(vk_ctx* ctx) {
   if (ctx->ev_comm) (void)hipEventDestroy(ctx->ev_comm);
   for (auto& kv : ctx->images) (void)hipFree(kv.second);
   if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
+  if (ctx->d_real) (void)hipFree(ctx->d_real);
   for (auto& evt : ctx->ev)
     if (evt) (void)hipEventDestroy(evt);
   if (ctx->ev_joint) (void)hipEventDestroy(ctx->ev_joint);
@@ -1843,6 +1848,91 @@ int vk_theory_batch(vk_ctx* ctx, const vk_eval_opts* opts, const double* params,
 int vk_xi_smu_batch(vk_ctx* ctx, const vk_eval_opts* opts, const double* params, int64_t n, const double* s,
                     int32_t n_s, const double* mu, int32_t n_mu, double* out) {
   return general_grid(ctx, opts, params, n, s, n_s, mu, n_mu, nullptr, 0, out, false);
+}
+
+// ---- one parameter batch against many realisations of the data vector (include/victor_hip.h, vk_kernel_real.h) -----------
+int vk_set_realisations(vk_ctx* ctx, const double* data, int32_t n_real) {
+  if (!ctx) return VK_E_ARG;
+  if (n_real < 0 || (n_real > 0 && !data)) return fail(ctx, VK_E_ARG, "vk_set_realisations: bad arguments");
+  if (!ctx->d_data) return fail(ctx, VK_E_ARG, "context was created without a data vector");
+  VK_HIP(ctx, hipSetDevice(ctx->device));
+  VK_HIP(ctx, hipStreamSynchronize(ctx->stream));        // (nothing in flight may still read the old blocks)
+  if (ctx->d_real) (void)hipFree(ctx->d_real);
+  ctx->d_real = nullptr;
+  ctx->n_real = 0;
+  const long long block = ctx->n_beta_d > 0 ? (long long)(ctx->n_beta_d - 1) * ctx->N * 4 : ctx->N;
+  ctx->real_block = block;
+  if (n_real == 0) return VK_OK;
+  const size_t bytes = (size_t)n_real * block * sizeof(double);
+  VK_HIP(ctx, hipMalloc((void**)&ctx->d_real, bytes));
+  VK_HIP(ctx, hipMemcpy(ctx->d_real, data, bytes, hipMemcpyHostToDevice));
+  ctx->n_real = n_real;
+  return VK_OK;
+}
+
+int vk_eval_realisations(vk_ctx* ctx, const vk_eval_opts* opts, const double* params, int64_t n, const int32_t* which,
+                         double* lnl, double* chi2) {
+  if (!ctx) return VK_E_ARG;
+  sync_knobs(ctx);
+  int rc = check_opts(ctx, opts);
+  if (rc) return rc;
+  if (n < 0 || (n > 0 && !params)) return fail(ctx, VK_E_ARG, "params is NULL");
+  if (ctx->begun_n != 0) return fail(ctx, VK_E_ARG, "a batch begun with vk_eval_batch_begin is awaiting vk_eval_batch_finish on this context");
+  if (ctx->n_real <= 0 || !ctx->d_real) return fail(ctx, VK_E_ARG, "no realisations are set on this context (vk_set_realisations)");
+  if (which)
+    for (int64_t i = 0; i < n; ++i)
+      if (which[i] < 0 || which[i] >= ctx->n_real)
+        return fail(ctx, VK_E_ARG, "realisation index %d of point %lld is outside 0..%d", which[i], (long long)i, ctx->n_real - 1);
+  if (n == 0) return VK_OK;
+  const int N = ctx->N;
+  const size_t lds = real_lds_doubles(N) * sizeof(double);
+  if (lds > 160 * 1024) return fail(ctx, VK_E_ARG, "data vector of %d bins needs %zu bytes of LDS for the realisation kernel (> 160 KiB)", N, lds);
+  VK_HIP(ctx, hipSetDevice(ctx->device));
+  // Points go through in chunks whose two output arrays stay below 256 MB (65536 points x 1000 realisations would be 0.5 GB
+  // each); a chunk is one theory launch into the workspace and one realisation launch behind it.
+  const long long per_point = which ? 1 : ctx->n_real;
+  const long long chunk = std::max<long long>(1, std::min<long long>(65536, (256LL << 20) / (8 * per_point)));
+  const long long m_max = std::min<long long>(chunk, n);
+  const size_t doubles = (size_t)m_max * (VK_NPAR + N + 2 * per_point) + (size_t)m_max / 2 + 2;
+  rc = ensure_scratch(ctx, doubles * sizeof(double));
+  if (rc) return rc;
+  double* d_par = ctx->d_scratch;
+  double* d_th = d_par + (size_t)m_max * VK_NPAR;
+  double* d_lnl = d_th + (size_t)m_max * N;
+  double* d_chi = d_lnl + (size_t)m_max * per_point;
+  int32_t* d_which = reinterpret_cast<int32_t*>(d_chi + (size_t)m_max * per_point);
+  const bool timed = ctx->timing;
+  for (long long off = 0; off < n; off += m_max) {
+    const long long m = std::min<long long>(m_max, n - off);
+    VK_HIP(ctx, hipMemcpyAsync(d_par, params + off * VK_NPAR, (size_t)m * VK_NPAR * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (which) VK_HIP(ctx, hipMemcpyAsync(d_which, which + off, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    if (timed) {
+      harvest_timing(ctx);
+      VK_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    }
+    rc = vk_eval_batch_device_async(ctx, opts, d_par, m, nullptr, nullptr, d_th);     // theory vectors only, into the workspace
+    if (rc) return rc;
+    if (timed) VK_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+    RealArgs ra{};
+    fill_like_args(ctx, opts, d_par, d_th, m, lnl ? d_lnl : nullptr, chi2 ? d_chi : nullptr, &ra.like);
+    ra.real = ctx->d_real;
+    ra.block = ctx->real_block;
+    ra.n_real = ctx->n_real;
+    ra.which = which ? d_which : nullptr;
+    rc = ctx->knobs.real_valu ? launch_on_stream(ctx, vk_like_real_kernel<false>, (int)m, lds, ra)
+                              : launch_on_stream(ctx, vk_like_real_kernel<true>, (int)m, lds, ra);
+    if (rc) return rc;
+    if (timed) {
+      VK_HIP(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
+      ctx->pending = true;
+    }
+    const size_t nb = (size_t)m * per_point * sizeof(double);
+    if (lnl) VK_HIP(ctx, hipMemcpyAsync(lnl + off * per_point, d_lnl, nb, hipMemcpyDeviceToHost, ctx->stream));
+    if (chi2) VK_HIP(ctx, hipMemcpyAsync(chi2 + off * per_point, d_chi, nb, hipMemcpyDeviceToHost, ctx->stream));
+    rc = vk_sync(ctx);
+    if (rc) return rc;
+  }
+  return VK_OK;
 }
 
 }  // extern "C"

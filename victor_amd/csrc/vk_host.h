@@ -30,6 +30,7 @@ struct Knobs {
   long long point_cap = 0;             // VICTOR_HIP_POINT_CAP   (workgroups per CU, generic theory kernel; 0 = default)
   int mapping = 0;                     // VICTOR_HIP_MAPPING: 0 auto, 1 point, 2 cells, 3 lanes, -1 unknown name
   bool like_untiled = false;           // VICTOR_HIP_LIKE_UNTILED
+  bool real_valu = false;              // VICTOR_HIP_REAL_VALU: the realisation kernel on the vector ALU instead of the matrix cores (A/B)
   bool no_graph = false;               // VICTOR_HIP_NO_GRAPH
   bool no_fuse = false;                // VICTOR_HIP_NO_FUSE: keep chi2 in its own launch (A/B of the fused path)
   bool no_inline_row = false;          // VICTOR_HIP_NO_INLINE_ROW: single-point host calls read their row from the pinned buffer (A/B)
@@ -111,6 +112,10 @@ struct vk_ctx {
   // scratch for the host-buffer entry points
   double* d_scratch = nullptr;
   size_t scratch_bytes = 0;
+  // simulation realisations (vk_set_realisations): n_real blocks of real_block doubles, each laid out as vk_tables.data
+  double* d_real = nullptr;
+  int n_real = 0;
+  long long real_block = 0;
   // timing
   bool timing = false;
   hipEvent_t ev[3] = {nullptr, nullptr, nullptr};

@@ -207,14 +207,11 @@ def build_tables(model, fit=None, matter_model=None, simpson_even=None):
     if fit is not None:
         Nd = len(s) * len(poles)
         stack = np.array([fit.redshift_multipoles[f"{l}"] for l in poles])   # (n_ell, [n_beta,] n_s)
+        d = arr(data_table(stack, fit.fixed_data, fit.beta_ccf if not fit.fixed_data else None))
         if fit.fixed_data:
             t.n_beta_d = 0
-            d = arr(stack.reshape(Nd))
         else:
             bd = arr(fit.beta_ccf)
-            vals = np.transpose(stack, (1, 0, 2)).reshape(len(bd), Nd)     # (n_beta, N)
-            pc = T.pchip_coefficients(bd, vals)                            # (n_beta-1, 4, N)
-            d = arr(np.transpose(pc, (0, 2, 1)))                           # (n_beta-1, N, 4)
             t.n_beta_d = len(bd)
             t.beta_d = N.as_dp(bd)
         t.data = N.as_dp(d)
@@ -254,6 +251,19 @@ def build_tables(model, fit=None, matter_model=None, simpson_even=None):
             t.logdet = N.as_dp(logdet)
             t.eig = N.as_dp(eig)
     return t, keep
+
+
+def data_table(stack, fixed_data, beta=None):
+    """``vk_tables.data`` of one data vector: ``stack`` holds the multipoles, (n_ell, n_s) for fixed data, else
+    (n_ell, n_beta, n_s) on the grid ``beta``.  Fixed: the vector [N]; else its PCHIP pieces in beta, [n_beta-1][N][4]."""
+    stack = np.asarray(stack, dtype=float)
+    Nd = stack.shape[0] * stack.shape[-1]
+    if fixed_data:
+        return stack.reshape(Nd)
+    bd = N.f64(beta)
+    vals = np.transpose(stack, (1, 0, 2)).reshape(len(bd), Nd)     # (n_beta, N)
+    pc = T.pchip_coefficients(bd, vals)                            # (n_beta-1, 4, N)
+    return np.transpose(pc, (0, 2, 1))                             # (n_beta-1, N, 4)
 
 
 def table_array_lengths(t):
@@ -414,6 +424,28 @@ class Engine:
         if rc != 0:
             self._check(rc)
         return float(out[0]), float(out[1])
+
+    def set_realisations(self, blocks):
+        """Upload the data vectors of ``n_real`` simulation realisations, ``blocks[i]`` in the layout of ``vk_tables.data``
+        (:func:`data_table`); they stay on the device until replaced."""
+        blocks = N.f64(blocks)
+        self._check(self._lib.vk_set_realisations(self._ctx, N.as_dp(blocks), len(blocks)))
+
+    def eval_realisations(self, opts, rows, n_real, which=None):
+        """(lnl, chi2) of every row against every uploaded realisation, each ``(n, n_real)``; with ``which`` (one realisation
+        index per row) only those pairs, each ``(n,)``."""
+        rows = N.f64(rows).reshape(-1, N.VK_NPAR)
+        n = len(rows)
+        shape = (n,) if which is not None else (n, int(n_real))
+        lnl = np.empty(shape)
+        chi2 = np.empty(shape)
+        w = None
+        if which is not None:
+            which = np.ascontiguousarray(which, dtype=np.int32)
+            w = which.ctypes.data_as(C.POINTER(C.c_int32))
+        self._check(self._lib.vk_eval_realisations(self._ctx, C.byref(opts), N.as_dp(rows), n, w, N.as_dp(lnl),
+                                                   N.as_dp(chi2)))
+        return lnl, chi2
 
     def theory_vector_batch(self, opts, rows):
         rows = N.f64(rows).reshape(-1, N.VK_NPAR)
