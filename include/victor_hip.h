@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define VK_ABI_VERSION 19
+#define VK_ABI_VERSION 20
 
 /* error codes */
 #define VK_OK 0
@@ -295,6 +295,10 @@ void vk_destroy(vk_ctx* ctx);
 const char* vk_last_error(const vk_ctx* ctx);
 /* name of the theory-kernel variant the most recent evaluation launched (diagnostics / benchmarks) */
 const char* vk_last_kernel(const vk_ctx* ctx);
+/* the exact instantiation of that launch and the chi-square kernel that ran with it, "cells<3,2,1,dispersion,0>+fused",
+ * "fast<1,1,0,from_data,0>+like_tiled<8>", "generic<kaiser,2,3>+like", "cells<1,1,0,streaming,0>+none" (theory only),
+ * "xi<euclid,1>" (K1x); valid until the next call on ctx */
+const char* vk_last_instance(const vk_ctx* ctx);
 /* 1 when that launch also took the chi-square / log-likelihood (fused tail), 0 when K2 ran as its own launch */
 int vk_last_fused(const vk_ctx* ctx);
 /* 1 when that launch handed the partial sums of its split planes over by polling (vk_poll_rule below), 0 otherwise */

@@ -946,3 +946,61 @@ def test_every_kernel_is_generated_in_exactly_one_translation_unit(lib, tmp_path
     # the lists themselves: 18 + 45 + 45 cells, 45 + 36 point-major, 36 + 12 generic instantiations
     counts = {fam: sum(1 for k in where if fam in k) for fam in ("vk_theory_cells_kernel", "vk_theory_fast_kernel", "vk_theory_kernelI", "vk_xi_smu_kernel")}
     assert counts == {"vk_theory_cells_kernel": 108, "vk_theory_fast_kernel": 81, "vk_theory_kernelI": 36, "vk_xi_smu_kernel": 12}, counts
+
+
+def _shipped_instances(tmp_path):
+    """The theory-kernel and chi-square-kernel instantiations in the shipped library's gfx950 code objects, named as
+    vk_last_instance names them: {"cells<3,2,1,dispersion,0>", ..., "xi<euclid,1>"}, {"like", "like_tiled<8>", ...}."""
+    import re
+    import subprocess
+    from tests.kernel_matrix import MODES, RSD
+    rsd = list(RSD)
+    names = set()
+    for co in _gfx950_code_objects(tmp_path):
+        notes = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-readelf", "--notes", co], capture_output=True, text=True).stdout
+        names |= set(re.findall(r"\.name:\s+(\S+)", notes))
+    theory, like = set(), set()
+    for name in names:
+        m = re.match(r"_ZN2vk\d+vk_(\w+?)_kernel(?:I((?:L[ib]\d+E)+)E)?", name)
+        if not m:
+            continue
+        fam, args = m.group(1), [int(a) for a in re.findall(r"L[ib](\d+)E", m.group(2) or "")]
+        if fam in ("theory_cells", "theory_fast"):
+            nlr, nl, grid, mode, sva = args
+            theory.add(f"{fam[7:]}<{nlr},{nl},{grid},{MODES[mode]},{sva}>")
+        elif fam == "theory":
+            theory.add(f"generic<{rsd[args[0]]},{args[1]},{args[2]}>")
+        elif fam == "xi_smu":
+            theory.add(f"xi<{rsd[args[0]]},{args[1]}>")
+        elif fam == "like_real":
+            like.add(f"like_real<{'true' if args[0] else 'false'}>")
+        elif fam.startswith("like"):
+            like.add(fam + (f"<{args[0]}>" if args else ""))
+    return theory, like
+
+
+def test_every_shipped_instantiation_has_a_recipe(lib, tmp_path):
+    """tests/kernel_matrix.py names, for every theory-kernel instantiation in the shipped library (THEORY) and for every
+    chi-square kernel at one, two and three data poles (LIKE), the inputs that select it - or, in UNREACHABLE, why none can:
+    the GPU matrix (tests/test_gpu_kernel_matrix.py) then runs each one against the oracle.  Fails in both directions - an
+    instantiation without a recipe, a recipe that names no instantiation - and on a second recipe for the same one."""
+    from tests.kernel_matrix import LIKE, RECIPES, THEORY, UNREACHABLE, data_poles, parse
+    theory, like = _shipped_instances(tmp_path)
+    assert len(theory) == 237 and like == {"like", "like_tiled<8>", "like_wide", "like_real<true>", "like_real<false>"}, (len(theory), like)
+    assert len(RECIPES) == len(THEORY) + len(LIKE)
+    for key, why in UNREACHABLE.items():
+        assert key in theory | like and why, key
+    for key in RECIPES:
+        t, l = parse(key)
+        assert t in theory, f"recipe {key}: the library has no {t}"
+        assert l in like | {"fused", "none", None}, f"recipe {key}: the library has no chi-square kernel {l}"
+        assert (l is None) == t.startswith("xi<"), key
+        assert t not in UNREACHABLE and l not in UNREACHABLE, f"recipe {key} for an instance listed as unreachable"
+    got = sorted(parse(key)[0] for key in THEORY)
+    assert len(got) == len(set(got)), f"two recipes for one theory-kernel instantiation: {[t for t in got if got.count(t) > 1]}"
+    want = theory - set(UNREACHABLE)
+    assert set(got) == want, f"no recipe: {sorted(want - set(got))}; no instantiation: {sorted(set(got) - want)}"
+    got = sorted((parse(key)[1], data_poles(parse(key)[0])) for key in LIKE)
+    assert len(got) == len(set(got)), f"two recipes for one chi-square kernel: {got}"
+    want = {(l, nl) for l in like - set(UNREACHABLE) for nl in (1, 2, 3)}
+    assert set(got) == want, f"no recipe: {sorted(want - set(got))}; no kernel: {sorted(set(got) - want)}"

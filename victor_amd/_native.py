@@ -11,7 +11,7 @@ import os
 
 import numpy as np
 
-VK_ABI_VERSION = 19
+VK_ABI_VERSION = 20
 VK_NPAR = 12
 (P_FSIGMA8, P_SIGMAV, P_APERP, P_APAR, P_EPSILON, P_BETA, P_ASTAR, P_M, P_Q, P_BIAS, P_AV, P_SPARE) = range(12)
 MATTER = {"template": 0, "linear_bias": 1, "velocity_template": 2}
@@ -105,6 +105,7 @@ SYMBOLS = {
     "vk_destroy": (None, [_vp]),
     "vk_last_error": (C.c_char_p, [_vp]),
     "vk_last_kernel": (C.c_char_p, [_vp]),
+    "vk_last_instance": (C.c_char_p, [_vp]),
     "vk_last_fused": (C.c_int, [_vp]),
     "vk_last_polled": (C.c_int, [_vp]),
     "vk_default_opts": (None, [_optp]),

@@ -256,12 +256,61 @@ void choose_split(const vk_ctx* ctx, long long n, int n_s, int* spi, int* team, 
   *parts = (int)(q < 1 ? 1 : (q > 2 ? 2 : q));
 }
 
+// vk_last_instance: every leaf below names the instantiation it launches, with the names of its template arguments (kMode* of
+// vk_kernel_fast.h, VK_RSD_*).  The string is formed once per instantiation; a launch only stores its address.
+constexpr const char* kModeNames[] = {"streaming", "from_data", "dispersion", "dispersion_from_data", "kaiser"};
+constexpr const char* kRsdNames[] = {"streaming", "dispersion", "kaiser", "euclid"};
+
+template <int FAST, int NLR, int NL, int GRID, int MODE, int SVA>
+const char* owned_instance() {
+  static const std::string s = std::string(FAST ? "fast<" : "cells<") + std::to_string(NLR) + "," + std::to_string(NL) + "," +
+                               std::to_string(GRID) + "," + kModeNames[MODE] + "," + std::to_string(SVA) + ">";
+  return s.c_str();
+}
+
+template <int RSD, int NLR, int NL>
+const char* generic_instance() {
+  static const std::string s = std::string("generic<") + kRsdNames[RSD] + "," + std::to_string(NLR) + "," + std::to_string(NL) + ">";
+  return s.c_str();
+}
+
+template <int RSD, int NLR>
+const char* xi_instance() {
+  static const std::string s = std::string("xi<") + kRsdNames[RSD] + "," + std::to_string(NLR) + ">";
+  return s.c_str();
+}
+
+template <int NLR, int NL, int GRID, int MODE, int SVA = 0>
+int launch_cells(vk_ctx* ctx, const TheoryArgs& a, int grid, size_t lds) {
+  ctx->last_theory = owned_instance<0, NLR, NL, GRID, MODE, SVA>();
+  return launch_on_stream(ctx, vk_theory_cells_kernel<NLR, NL, GRID, MODE, SVA>, grid, lds, a);
+}
+
+template <int NLR, int NL, int GRID, int MODE, int SVA = 0>
+int launch_fast(vk_ctx* ctx, const TheoryArgs& a, int grid, size_t lds) {
+  ctx->last_theory = owned_instance<1, NLR, NL, GRID, MODE, SVA>();
+  return launch_on_stream(ctx, vk_theory_fast_kernel<NLR, NL, GRID, MODE, SVA>, grid, lds, a);
+}
+
+template <int RSD, int NLR, int NL>
+int launch_generic_one(vk_ctx* ctx, const TheoryArgs& a, int grid, size_t lds) {
+  ctx->last_theory = generic_instance<RSD, NLR, NL>();
+  return launch_on_stream(ctx, vk_theory_kernel<RSD, NLR, NL>, grid, lds, a);
+}
+
+template <int RSD, int NLR>
+int launch_xi_one(vk_ctx* ctx, const TheoryArgs& a, int grid, size_t lds) {
+  ctx->last_theory = xi_instance<RSD, NLR>();
+  ctx->last_like = nullptr;                    // K1x stores xi(s, mu): no chi-square pairs with it
+  return launch_on_stream(ctx, vk_xi_smu_kernel<RSD, NLR>, grid, lds, a);
+}
+
 template <int RSD, int NLR>
 int launch_generic_nl(vk_ctx* ctx, const TheoryArgs& a, int grid, size_t lds) {
   switch (a.n_ell) {
-    case 1: return launch_on_stream(ctx, vk_theory_kernel<RSD, NLR, 1>, grid, lds, a);
-    case 2: return launch_on_stream(ctx, vk_theory_kernel<RSD, NLR, 2>, grid, lds, a);
-    case 3: return launch_on_stream(ctx, vk_theory_kernel<RSD, NLR, 3>, grid, lds, a);
+    case 1: return launch_generic_one<RSD, NLR, 1>(ctx, a, grid, lds);
+    case 2: return launch_generic_one<RSD, NLR, 2>(ctx, a, grid, lds);
+    case 3: return launch_generic_one<RSD, NLR, 3>(ctx, a, grid, lds);
   }
   return fail(ctx, VK_E_ARG, "n_ell must be 1..3");
 }
@@ -279,9 +328,9 @@ int launch_generic(vk_ctx* ctx, const TheoryArgs& a, int nlr, int grid, size_t l
 template <int NLR, int GRID, int MODE>
 int launch_fast_ngf(vk_ctx* ctx, const TheoryArgs& a, int grid, size_t lds) {
   switch (a.n_ell) {
-    case 1: return launch_on_stream(ctx, vk_theory_fast_kernel<NLR, 1, GRID, MODE>, grid, lds, a);
-    case 2: return launch_on_stream(ctx, vk_theory_fast_kernel<NLR, 2, GRID, MODE>, grid, lds, a);
-    case 3: return launch_on_stream(ctx, vk_theory_fast_kernel<NLR, 3, GRID, MODE>, grid, lds, a);
+    case 1: return launch_fast<NLR, 1, GRID, MODE>(ctx, a, grid, lds);
+    case 2: return launch_fast<NLR, 2, GRID, MODE>(ctx, a, grid, lds);
+    case 3: return launch_fast<NLR, 3, GRID, MODE>(ctx, a, grid, lds);
   }
   return fail(ctx, VK_E_ARG, "n_ell must be 1..3");
 }
@@ -290,9 +339,9 @@ int launch_fast_ngf(vk_ctx* ctx, const TheoryArgs& a, int grid, size_t lds) {
 template <int NLR>
 int launch_fast_sva(vk_ctx* ctx, const TheoryArgs& a, int grid, size_t lds) {
   switch (a.n_ell) {
-    case 1: return launch_on_stream(ctx, vk_theory_fast_kernel<NLR, 1, 0, kModeStreaming, 1>, grid, lds, a);
-    case 2: return launch_on_stream(ctx, vk_theory_fast_kernel<NLR, 2, 0, kModeStreaming, 1>, grid, lds, a);
-    case 3: return launch_on_stream(ctx, vk_theory_fast_kernel<NLR, 3, 0, kModeStreaming, 1>, grid, lds, a);
+    case 1: return launch_fast<NLR, 1, 0, kModeStreaming, 1>(ctx, a, grid, lds);
+    case 2: return launch_fast<NLR, 2, 0, kModeStreaming, 1>(ctx, a, grid, lds);
+    case 3: return launch_fast<NLR, 3, 0, kModeStreaming, 1>(ctx, a, grid, lds);
   }
   return fail(ctx, VK_E_ARG, "n_ell must be 1..3");
 }
@@ -301,9 +350,9 @@ int launch_fast_sva(vk_ctx* ctx, const TheoryArgs& a, int grid, size_t lds) {
 template <int NLR>
 int launch_cells_sva_disp(vk_ctx* ctx, const TheoryArgs& a, int grid, size_t lds) {
   switch (a.n_ell) {
-    case 1: return launch_on_stream(ctx, vk_theory_cells_kernel<NLR, 1, 0, kModeDispersion, 1>, grid, lds, a);
-    case 2: return launch_on_stream(ctx, vk_theory_cells_kernel<NLR, 2, 0, kModeDispersion, 1>, grid, lds, a);
-    case 3: return launch_on_stream(ctx, vk_theory_cells_kernel<NLR, 3, 0, kModeDispersion, 1>, grid, lds, a);
+    case 1: return launch_cells<NLR, 1, 0, kModeDispersion, 1>(ctx, a, grid, lds);
+    case 2: return launch_cells<NLR, 2, 0, kModeDispersion, 1>(ctx, a, grid, lds);
+    case 3: return launch_cells<NLR, 3, 0, kModeDispersion, 1>(ctx, a, grid, lds);
   }
   return fail(ctx, VK_E_ARG, "n_ell must be 1..3");
 }
@@ -312,9 +361,9 @@ template <int NLR>
 int launch_cells_sva(vk_ctx* ctx, const TheoryArgs& a, int grid, size_t lds) {
   if (a.rsd == VK_RSD_DISPERSION) return launch_cells_sva_disp<NLR>(ctx, a, grid, lds);
   switch (a.n_ell) {
-    case 1: return launch_on_stream(ctx, vk_theory_cells_kernel<NLR, 1, 0, kModeStreaming, 1>, grid, lds, a);
-    case 2: return launch_on_stream(ctx, vk_theory_cells_kernel<NLR, 2, 0, kModeStreaming, 1>, grid, lds, a);
-    case 3: return launch_on_stream(ctx, vk_theory_cells_kernel<NLR, 3, 0, kModeStreaming, 1>, grid, lds, a);
+    case 1: return launch_cells<NLR, 1, 0, kModeStreaming, 1>(ctx, a, grid, lds);
+    case 2: return launch_cells<NLR, 2, 0, kModeStreaming, 1>(ctx, a, grid, lds);
+    case 3: return launch_cells<NLR, 3, 0, kModeStreaming, 1>(ctx, a, grid, lds);
   }
   return fail(ctx, VK_E_ARG, "n_ell must be 1..3");
 }
@@ -335,12 +384,19 @@ int launch_fast_nl(vk_ctx* ctx, const TheoryArgs& a, int grid, size_t lds) {
 }
 
 #ifdef VK_DEV_LANES
+template <int NLR, int NL, int GRID>
+int launch_lanes(vk_ctx* ctx, const TheoryArgs& a, int grid, size_t lds) {
+  static const std::string name = "lanes<" + std::to_string(NLR) + "," + std::to_string(NL) + "," + std::to_string(GRID) + ">";
+  ctx->last_theory = name.c_str();
+  return launch_on_stream(ctx, vk_theory_lanes_kernel<NLR, NL, GRID>, grid, lds, a);
+}
+
 template <int NLR, int GRID>
 int launch_lanes_ng(vk_ctx* ctx, const TheoryArgs& a, int grid, size_t lds) {
   switch (a.n_ell) {
-    case 1: return launch_on_stream(ctx, vk_theory_lanes_kernel<NLR, 1, GRID>, grid, lds, a);
-    case 2: return launch_on_stream(ctx, vk_theory_lanes_kernel<NLR, 2, GRID>, grid, lds, a);
-    case 3: return launch_on_stream(ctx, vk_theory_lanes_kernel<NLR, 3, GRID>, grid, lds, a);
+    case 1: return launch_lanes<NLR, 1, GRID>(ctx, a, grid, lds);
+    case 2: return launch_lanes<NLR, 2, GRID>(ctx, a, grid, lds);
+    case 3: return launch_lanes<NLR, 3, GRID>(ctx, a, grid, lds);
   }
   return fail(ctx, VK_E_ARG, "n_ell must be 1..3");
 }
@@ -354,9 +410,9 @@ int launch_lanes_nl(vk_ctx* ctx, const TheoryArgs& a, int grid, size_t lds) {
 template <int NLR, int GRID, int MODE>
 int launch_cells_ngf(vk_ctx* ctx, const TheoryArgs& a, int grid, size_t lds) {
   switch (a.n_ell) {
-    case 1: return launch_on_stream(ctx, vk_theory_cells_kernel<NLR, 1, GRID, MODE>, grid, lds, a);
-    case 2: return launch_on_stream(ctx, vk_theory_cells_kernel<NLR, 2, GRID, MODE>, grid, lds, a);
-    case 3: return launch_on_stream(ctx, vk_theory_cells_kernel<NLR, 3, GRID, MODE>, grid, lds, a);
+    case 1: return launch_cells<NLR, 1, GRID, MODE>(ctx, a, grid, lds);
+    case 2: return launch_cells<NLR, 2, GRID, MODE>(ctx, a, grid, lds);
+    case 3: return launch_cells<NLR, 3, GRID, MODE>(ctx, a, grid, lds);
   }
   return fail(ctx, VK_E_ARG, "n_ell must be 1..3");
 }
@@ -380,9 +436,9 @@ int launch_cells_nl(vk_ctx* ctx, const TheoryArgs& a, int grid, size_t lds) {
 template <int RSD>
 int launch_xi_smu(vk_ctx* ctx, const TheoryArgs& a, int nlr, int grid, size_t lds) {
   switch (nlr) {
-    case 1: return launch_on_stream(ctx, vk_xi_smu_kernel<RSD, 1>, grid, lds, a);
-    case 2: return launch_on_stream(ctx, vk_xi_smu_kernel<RSD, 2>, grid, lds, a);
-    case 3: return launch_on_stream(ctx, vk_xi_smu_kernel<RSD, 3>, grid, lds, a);
+    case 1: return launch_xi_one<RSD, 1>(ctx, a, grid, lds);
+    case 2: return launch_xi_one<RSD, 2>(ctx, a, grid, lds);
+    case 3: return launch_xi_one<RSD, 3>(ctx, a, grid, lds);
   }
   return fail(ctx, VK_E_ARG, "bad number of real-space multipoles %d", nlr);
 }
@@ -515,6 +571,7 @@ unsigned div_magic(int d) { return (unsigned)((0x100000000ULL + (unsigned)d - 1)
 int launch_theory(vk_ctx* ctx, TheoryArgs a, int nlr, const LikeArgs* like, bool* fused) {
   if (fused) *fused = false;
   ctx->last_polled = false;
+  ctx->last_like = "none";      // the caller names the chi-square launch that follows (vk_eval_batch_device_async)
   if (a.n <= 0) return VK_OK;
   if (a.n > (1LL << 31) / ((long long)a.n_s * kMaxParts)) return fail(ctx, VK_E_ARG, "batch of %lld points is too large for one launch", a.n);
   const int N = a.n_ell * a.n_s;
@@ -804,6 +861,7 @@ int launch_like(vk_ctx* ctx, const LikeArgs& a) {
   const size_t lds_wide = (size_t)like_lds_doubles(ctx->N) * sizeof(double);
   const bool wide = ctx->knobs.like_wide >= 0 ? ctx->knobs.like_wide == 1 : n <= 2048;
   if (wide && lds_wide <= 160 * 1024) {
+    ctx->last_like = "like_wide";
     return launch_on_stream(ctx, vk_like_wide_kernel, (int)n, lds_wide, a);      // one point per workgroup
   }
   // fixed covariance: 8 points per wave share the loads of the precision matrix (LDS: 4 waves x 8 x N doubles)
@@ -813,12 +871,15 @@ int launch_like(vk_ctx* ctx, const LikeArgs& a) {
     const long long tiles = (n + kTile - 1) / kTile;
     const long long blocks = (tiles + kWaves - 1) / kWaves;
     const int grid = (int)(blocks < cap ? blocks : cap);
+    static_assert(kTile == 8, "vk_last_instance names like_tiled<8>");
+    ctx->last_like = "like_tiled<8>";
     return launch_on_stream(ctx, vk_like_tiled_kernel<kTile>, grid, lds_tiled, a);
   }
   const long long blocks = (n + kWaves - 1) / kWaves;
   const int grid = (int)(blocks < cap ? blocks : cap);
   const size_t lds = (size_t)kWaves * ctx->N * sizeof(double);
   if (lds > 160 * 1024) return fail(ctx, VK_E_ARG, "data vector of %d bins needs %zu bytes of LDS (> 160 KiB)", ctx->N, lds);
+  ctx->last_like = "like";
   return launch_on_stream(ctx, vk_like_kernel, grid, lds, a);
 }
 
@@ -909,6 +970,13 @@ void vk_default_opts(vk_eval_opts* o) {
 const char* vk_last_error(const vk_ctx* ctx) { return ctx ? ctx->err.c_str() : g_create_err.c_str(); }
 
 const char* vk_last_kernel(const vk_ctx* ctx) { return ctx ? ctx->last_kernel : "none"; }
+
+const char* vk_last_instance(const vk_ctx* ctx) {
+  if (!ctx) return "none";
+  ctx->last_instance = ctx->last_theory;
+  if (ctx->last_like) ctx->last_instance.append("+").append(ctx->last_like);
+  return ctx->last_instance.c_str();
+}
 
 int vk_last_fused(const vk_ctx* ctx) { return ctx && ctx->last_fused ? 1 : 0; }
 
@@ -1430,6 +1498,7 @@ int vk_eval_batch_device_async(vk_ctx* ctx, const vk_eval_opts* opts, const doub
     rc = launch_theory(ctx, a, nlr, want_like ? &la : nullptr, &fused);
     if (rc) return rc;
     ctx->last_fused = fused;
+    if (fused) ctx->last_like = "fused";
     if (timed) VK_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
     if (want_like && !fused) {
       rc = launch_like(ctx, la);
@@ -1535,7 +1604,7 @@ static int eval_batch_graph(vk_ctx* ctx, const vk_eval_opts* opts, const double*
       ctx->graph_seen[key] = -1;                       // e.g. an unsupported option combination: the eager path reports it
       return 0;
     }
-    ctx->graph_kernel[key] = ctx->last_kernel;
+    ctx->graph_kernel[key] = {ctx->last_kernel, ctx->last_theory, ctx->last_like, ctx->last_fused};
     hit = ctx->graphs.emplace(key, exec).first;
   }
   double* h_in = ctx->h_pin;
@@ -1543,7 +1612,11 @@ static int eval_batch_graph(vk_ctx* ctx, const vk_eval_opts* opts, const double*
   memcpy(h_in, params, (size_t)n * VK_NPAR * sizeof(double));
   VK_HIP(ctx, hipGraphLaunch(hit->second, ctx->stream));
   VK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->last_kernel = ctx->graph_kernel[key];
+  const vk_ctx::Replayed& rp = ctx->graph_kernel[key];
+  ctx->last_kernel = rp.kernel;
+  ctx->last_theory = rp.theory;
+  ctx->last_like = rp.like;
+  ctx->last_fused = rp.fused;
   if (ctx->h_poll_failed && *ctx->h_poll_failed)      // (set before the results were written, see finish_point)
     return fail(ctx, VK_E_HIP, "a workgroup waited %.0f s for partial sums that never arrived; the context is unusable", (double)kPollTicks * 1e-8);
   if (lnl) memcpy(lnl, h_out, (size_t)n * sizeof(double));
@@ -1919,6 +1992,7 @@ int vk_eval_realisations(vk_ctx* ctx, const vk_eval_opts* opts, const double* pa
     ra.block = ctx->real_block;
     ra.n_real = ctx->n_real;
     ra.which = which ? d_which : nullptr;
+    ctx->last_like = ctx->knobs.real_valu ? "like_real<false>" : "like_real<true>";
     rc = ctx->knobs.real_valu ? launch_on_stream(ctx, vk_like_real_kernel<false>, (int)m, lds, ra)
                               : launch_on_stream(ctx, vk_like_real_kernel<true>, (int)m, lds, ra);
     if (rc) return rc;

@@ -107,6 +107,9 @@ struct vk_ctx {
   std::map<int, double*> images;     // LDS images per (kernel kind, real-space multipoles, dispersion tables), built on first use
   std::map<const void*, int> lds_opt_in;   // dynamic LDS above 64 KiB a kernel has been opted in for (launch_on_stream)
   const char* last_kernel = "none";  // theory kernel variant of the most recent launch
+  const char* last_theory = "none";  // ... the exact instantiation of it, "cells<3,2,1,dispersion,0>" (named at the launch)
+  const char* last_like = "none";    // ... and the chi-square kernel that ran with it ("fused": its tail; NULL: K1x, no pair)
+  mutable std::string last_instance; // vk_last_instance's "theory+chi2" string
   bool last_fused = false;           // ... and whether it took the chi-square as well
   bool last_polled = false;          // ... and whether its split planes were handed over by polling (vk_poll_rule)
   // scratch for the host-buffer entry points
@@ -136,7 +139,8 @@ struct vk_ctx {
   double* h_pin = nullptr;                      // pinned: params[kGraphMaxN][VK_NPAR] | lnl, chi2 [2 kGraphMaxN]
   std::map<std::string, hipGraphExec_t> graphs;  // key: n + option bytes + requested outputs
   std::map<std::string, int> graph_seen;         // a key is captured on its second use (the first one runs eagerly)
-  std::map<std::string, const char*> graph_kernel;
+  struct Replayed { const char* kernel; const char* theory; const char* like; bool fused; };
+  std::map<std::string, Replayed> graph_kernel;   // what a captured graph launches, reported when it is replayed
   bool graphs_off = false;
   double* h_zc = nullptr;                       // pinned, device-mapped: params[kZeroCopyCap][VK_NPAR] | lnl, chi2 [2 kZeroCopyCap]
   double* d_zc = nullptr;                       // the same memory through the device's eyes

@@ -501,6 +501,11 @@ class Engine:
     def last_kernel(self):
         return self._lib.vk_last_kernel(self._ctx).decode()
 
+    def last_instance(self):
+        """The exact theory-kernel instantiation of the last evaluation and its chi-square kernel, as
+        ``"cells<3,2,1,dispersion,0>+fused"`` (``vk_last_instance``)."""
+        return self._lib.vk_last_instance(self._ctx).decode()
+
     def last_fused(self):
         return bool(self._lib.vk_last_fused(self._ctx))
 
