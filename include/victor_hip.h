@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define VK_ABI_VERSION 20
+#define VK_ABI_VERSION 21
 
 /* error codes */
 #define VK_OK 0
@@ -46,6 +46,7 @@ extern "C" {
 #define VK_E_HIP (-2)      /* a HIP runtime call failed */
 #define VK_E_NODEVICE (-3) /* no usable GPU */
 #define VK_E_RCCL (-4)     /* an RCCL call failed */
+#define VK_E_NOMEM (-5)    /* a host allocation failed */
 
 /* one row of the parameter batch: VK_NPAR doubles (ccf_model.py:583-613,638,695-696) */
 #define VK_NPAR 12
@@ -297,7 +298,8 @@ const char* vk_last_error(const vk_ctx* ctx);
 const char* vk_last_kernel(const vk_ctx* ctx);
 /* the exact instantiation of that launch and the chi-square kernel that ran with it, "cells<3,2,1,dispersion,0>+fused",
  * "fast<1,1,0,from_data,0>+like_tiled<8>", "generic<kaiser,2,3>+like", "cells<1,1,0,streaming,0>+none" (theory only),
- * "xi<euclid,1>" (K1x); valid until the next call on ctx */
+ * "xi<euclid,1>" (K1x), "cells<3,2,1,streaming,0>+joint_chi2" (the lead context of vk_joint_cov_eval_device_async: the
+ * lead block's theory launch and the joint chi-square kernel); valid until the next call on ctx */
 const char* vk_last_instance(const vk_ctx* ctx);
 /* 1 when that launch also took the chi-square / log-likelihood (fused tail), 0 when K2 ran as its own launch */
 int vk_last_fused(const vk_ctx* ctx);
@@ -416,6 +418,42 @@ int vk_sync(vk_ctx* ctx);
 size_t vk_joint_workspace_doubles(vk_ctx* const* ctxs, int32_t n_ctx, int64_t n);
 int vk_joint_eval_device_async(vk_ctx* const* ctxs, int32_t n_ctx, const vk_eval_opts* opts, const double* d_params,
                                int64_t n, double* d_lnl, double* d_chi2, double* d_ws);
+
+/* ---- joint fit under ONE covariance matrix across the data vectors ---------------------------------------------------
+ * The quantiles of a density-split analysis share their galaxies and voids: their data vectors are correlated and the
+ * covariance estimated from mocks is one dense (NT x NT) matrix, NT = sum of the blocks' N.  The joint vector is the blocks'
+ * data vectors concatenated in block order; with it the evaluation is CCFFit's (victor/ccf_fit.py:325-483) on that vector:
+ * r = concat_q (t_q - d_q(beta)), chi2 = r^T Psi(beta) r, the covariance bracket of ccf_fit.py:213-228 across the slices, -1/2
+ * log det C(beta) for a beta-dependent covariance (the generalised-eigenvalue scheme of vk_tables.logdet / eig) and the
+ * likelihood form with p = NT.  The blocks' own covariances (vk_tables.prec ...) are not used.
+ *
+ * vk_joint_cov_tables: n_blocks (<= 32) block sizes in block order; n_beta = 0 for one fixed precision matrix prec [NT][NT],
+ *   else the strictly increasing grid beta [n_beta], the precision slices prec [n_beta][NT][NT], logdet [n_beta] (NaN where
+ *   the slice's determinant is not positive) and eig [n_beta][NT] (the factors of vk_tables.eig; a NaN row fails every
+ *   blended evaluation that starts from its slice).
+ * vk_joint_cov_create copies the tables to lead's device and returns the handle in *out; errors (VK_E_ARG, VK_E_HIP, VK_E_NOMEM)
+ *   are reported through vk_last_error(lead).  vk_joint_cov_destroy waits for the evaluations that read the handle, not for
+ *   other work on the device.  The handle may be used with any contexts on that device whose N match the block sizes, lead first.
+ * vk_joint_cov_eval_device_async: every block's theory launch (theory only) on its own stream behind the lead stream, then the
+ *   joint chi-square kernel on the lead stream; lnl / chi2 [n] (either may be NULL, not both).  Enqueued; vk_sync(ctxs[0])
+ *   waits for it.  d_ws: vk_joint_cov_workspace_doubles(...) doubles of device memory. */
+typedef struct vk_joint_cov_tables {
+  int32_t n_blocks;
+  const int32_t* block_n;    /* [n_blocks] */
+  int32_t n_beta;            /* 0: fixed covariance */
+  const double* beta;        /* [n_beta] */
+  const double* prec;        /* [max(n_beta, 1)][NT][NT] */
+  const double* logdet;      /* [n_beta] */
+  const double* eig;         /* [n_beta][NT] */
+} vk_joint_cov_tables;
+
+typedef struct vk_joint_cov vk_joint_cov;
+
+int vk_joint_cov_create(vk_ctx* lead, const vk_joint_cov_tables* tables, vk_joint_cov** out);
+void vk_joint_cov_destroy(vk_joint_cov* h);
+size_t vk_joint_cov_workspace_doubles(const vk_joint_cov* h, int64_t n);
+int vk_joint_cov_eval_device_async(vk_joint_cov* h, vk_ctx* const* ctxs, int32_t n_ctx, const vk_eval_opts* opts,
+                                   const double* d_params, int64_t n, double* d_lnl, double* d_chi2, double* d_ws);
 
 /* ---- many one-point callers sharing one GPU: mailboxes in shared memory -----------------------------------------------
  * The reference is sampled by cobaya, which asks for ONE likelihood per call (victor/likelihoods/CCFLikelihood.py:32-39); more

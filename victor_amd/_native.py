@@ -11,7 +11,7 @@ import os
 
 import numpy as np
 
-VK_ABI_VERSION = 20
+VK_ABI_VERSION = 21
 VK_NPAR = 12
 (P_FSIGMA8, P_SIGMAV, P_APERP, P_APAR, P_EPSILON, P_BETA, P_ASTAR, P_M, P_Q, P_BIAS, P_AV, P_SPARE) = range(12)
 MATTER = {"template": 0, "linear_bias": 1, "velocity_template": 2}
@@ -51,6 +51,11 @@ class vk_eval_opts(C.Structure):
         ("kaiser_approx", C.c_int32), ("kaiser_coord_shift", C.c_int32), ("niter", C.c_int32),
         ("from_data", C.c_int32), ("empirical_corr", C.c_int32), ("reserved", C.c_int32),
     ]
+
+
+class vk_joint_cov_tables(C.Structure):
+    _fields_ = [("n_blocks", C.c_int32), ("block_n", C.POINTER(C.c_int32)), ("n_beta", C.c_int32), ("beta", _dp),
+                ("prec", _dp), ("logdet", _dp), ("eig", _dp)]
 
 
 class vk_mailbox(C.Structure):
@@ -130,6 +135,10 @@ SYMBOLS = {
     "vk_sync": (C.c_int, [_vp]),
     "vk_joint_workspace_doubles": (C.c_size_t, [C.POINTER(C.c_void_p), C.c_int32, C.c_int64]),
     "vk_joint_eval_device_async": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, _optp, _vp, C.c_int64, _vp, _vp, _vp]),
+    "vk_joint_cov_create": (C.c_int, [_vp, C.POINTER(vk_joint_cov_tables), C.POINTER(C.c_void_p)]),
+    "vk_joint_cov_destroy": (None, [_vp]),
+    "vk_joint_cov_workspace_doubles": (C.c_size_t, [_vp, C.c_int64]),
+    "vk_joint_cov_eval_device_async": (C.c_int, [_vp, C.POINTER(C.c_void_p), C.c_int32, _optp, _vp, C.c_int64, _vp, _vp, _vp]),
     "vk_serve_mailboxes": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, _optp, _vp, C.c_int32, _vp, C.c_double, C.c_int32,
                            C.c_double, C.POINTER(vk_serve_stats)]),
     "vk_timing_enable": (C.c_int, [_vp, C.c_int]),

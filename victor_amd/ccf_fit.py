@@ -21,6 +21,37 @@ from .utils import InputError
 _SCALARS = (float, int, np.float64)     # the common types of a sampler's parameter values: no np.ndim() call needed
 
 
+def load_covariance_matrix(covariance, input_fn, extensions, n, fixed_data, beta_ccf=None):
+    """Read a covariance block of the reference's ``covariance_matrix`` schema (ccf_fit.py:116-164) for a data vector of ``n``
+    entries: ``(fixed_covmat, beta_covmat, covmat, icov)``.  ``beta_covmat`` is ``None`` for a fixed covariance; without a
+    ``beta_key`` in the file it is ``beta_ccf``, the data's own grid.  Used by ``CCFFit`` and by the full-covariance
+    ``JointFit`` (``n`` = the joint vector's length)."""
+    input_data = utils.read_input_file(input_fn, extensions)
+    beta_covmat = None
+    if not fixed_data:
+        fixed_covmat = covariance.get("fixed_beta", True)
+        if not fixed_covmat:
+            beta_key = covariance.get("beta_key", None)
+            if beta_key and beta_key in input_data:
+                beta_covmat = np.asarray(input_data[beta_key], dtype=float)
+                if not np.all(np.diff(beta_covmat) > 0):
+                    raise InputError("Covariance beta grid must be strictly monotonically increasing")
+            else:
+                beta_covmat = beta_ccf
+    else:
+        fixed_covmat = True
+    cov_key = covariance["cov_key"]
+    if cov_key not in input_data:
+        raise InputError(f"Key {cov_key} not found in file {input_fn}")
+    covmat = np.asarray(input_data[cov_key], dtype=float)
+    if fixed_covmat:
+        if covmat.shape != (n, n):
+            raise InputError("Unexpected shape of (fixed) covariance matrix")
+    elif covmat.shape != (len(beta_covmat), n, n):
+        raise InputError("Unexpected shape of (beta-varying) covariance matrix")
+    return fixed_covmat, beta_covmat, covmat, np.linalg.inv(covmat)
+
+
 class CCFFit(CCFModel):
     """Fits of the CCF model to measured redshift-space multipoles."""
 
@@ -94,31 +125,11 @@ class CCFFit(CCFModel):
 
     def _load_covariance_matrix(self, covariance, input_fn):
         """Covariance and its inverse (reference: ccf_fit.py:116-164)."""
-        input_data = utils.read_input_file(input_fn, self.extensions)
-        if not self.fixed_data:
-            self.fixed_covmat = covariance.get("fixed_beta", True)
-            if not self.fixed_covmat:
-                beta_key = covariance.get("beta_key", None)
-                if beta_key and beta_key in input_data:
-                    self.beta_covmat = np.asarray(input_data[beta_key], dtype=float)
-                    if not np.all(np.diff(self.beta_covmat) > 0):
-                        raise InputError("Covariance beta grid must be strictly monotonically increasing")
-                else:
-                    self.beta_covmat = self.beta_ccf
-        else:
-            self.fixed_covmat = True
-        cov_key = covariance["cov_key"]
-        if cov_key not in input_data:
-            raise InputError(f"Key {cov_key} not found in file {input_fn}")
-        covmat = np.asarray(input_data[cov_key], dtype=float)
-        n = len(self.s) * len(self.poles_s)
-        if self.fixed_covmat:
-            if covmat.shape != (n, n):
-                raise InputError("Unexpected shape of (fixed) covariance matrix")
-        elif covmat.shape != (len(self.beta_covmat), n, n):
-            raise InputError("Unexpected shape of (beta-varying) covariance matrix")
-        self.covmat = covmat
-        self.icov = np.linalg.inv(self.covmat)
+        self.fixed_covmat, beta_covmat, self.covmat, self.icov = load_covariance_matrix(
+            covariance, input_fn, self.extensions, len(self.s) * len(self.poles_s), self.fixed_data,
+            None if self.fixed_data else self.beta_ccf)
+        if beta_covmat is not None:
+            self.beta_covmat = beta_covmat
 
     # ------------------------------------------------------------------ host-side accessors ---
     def get_interpolated_redshift_multipoles(self, beta=None):

@@ -14,14 +14,16 @@
 //   vk_kernel_cells.h    K1 cells (workgroup = point, lanes over (s, mu) cells, v loop innermost; per-point tables)
 //   vk_kernel_like.h     K2 residual . precision . residual, log det, likelihood form, NaN guard
 //   vk_kernel_real.h     K2 against many realisations of the data vector (vk_eval_realisations): f64 MFMA, one point per workgroup
+//   vk_kernel_joint.h    K2 of a joint fit under one covariance across its data vectors (vk_joint_cov_eval_device_async): f64 MFMA,
+//                        16 points per workgroup, the precision streamed from L2
 //
 // K1 restates CCFModel.theory_xi (streaming branch victor/ccf_model.py:589-690; the other branches :658-784),
 // theory_multipoles (:816-825) and utils.multipoles_from_fn (victor/utils.py:45-56); K2 restates CCFFit.chi_squared
 // (victor/ccf_fit.py:349-354), get_interpolated_{covariance,precision} (:195-260) and log_likelihood (:444-481).
 // All arithmetic is IEEE binary64 on the vector ALU: an evaluation is n_s*n_mu*n_x (= 200 000) integrand points of
 // ~80 FP64 instructions each against ~100 bytes of HBM traffic, so the kernels are laid out for VALU issue and LDS
-// gather bandwidth, not for HBM or MFMA - except the chi-square against many realisations, a batched
-// matrix product on the FP64 matrix cores.  launch_theory() picks the K1 variant per call.
+// gather bandwidth, not for HBM or MFMA - except the chi-square against many realisations and the
+// chi-square of a joint fit under a full covariance, batched matrix products on the FP64 matrix cores.  launch_theory() picks the K1 variant per call.
 
 #include <hip/hip_runtime.h>
 #include <chrono>
@@ -51,6 +53,7 @@
 #endif
 #include "vk_kernel_like.h"
 #include "vk_kernel_real.h"
+#include "vk_kernel_joint.h"
 
 // The theory kernels' instantiations are generated in translation units of their own (vk_instances.h names what lives where);
 // here they are declared only.
@@ -1558,6 +1561,217 @@ int vk_joint_eval_device_async(vk_ctx* const* ctxs, int32_t n_ctx, const vk_eval
   hipLaunchKernelGGL(vk_joint_sum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, lead->stream, d_ws, (long long)n, n_ctx,
                      block_stride, d_lnl, d_chi2);
   VK_HIP(lead, hipGetLastError());
+  return VK_OK;
+}
+
+// ---- joint fit under one covariance across the data vectors (include/victor_hip.h, vk_kernel_joint.h) -----------------
+}  // extern "C"
+
+struct vk_joint_cov {
+  vk_ctx* lead = nullptr;
+  int device = -1;
+  std::vector<int> block_n;
+  int NT = 0, NTp = 0, n_beta = 0;
+  double* d_mem = nullptr;        // beta [n_beta] | precision slices [max(n_beta, 1)][NTp][NTp] (zero-padded) | logdet | eig
+  hipEvent_t ev_done = nullptr;   // recorded behind every evaluation's chi-square kernel (the last reader of d_mem)
+  const double *d_beta = nullptr, *d_prec = nullptr, *d_logdet = nullptr, *d_eig = nullptr;
+};
+
+extern "C" {
+
+int vk_joint_cov_create(vk_ctx* lead, const vk_joint_cov_tables* t, vk_joint_cov** out) {
+  if (!lead) return VK_E_ARG;
+  if (!t || !out) return fail(lead, VK_E_ARG, "joint covariance: tables or out is NULL");
+  *out = nullptr;
+  if (t->n_blocks < 1 || t->n_blocks > kJointMaxBlocks || !t->block_n)
+    return fail(lead, VK_E_ARG, "joint covariance: %d blocks (1 .. %d)", t->n_blocks, kJointMaxBlocks);
+  long long NT = 0;
+  for (int q = 0; q < t->n_blocks; ++q) {
+    if (t->block_n[q] < 1) return fail(lead, VK_E_ARG, "joint covariance: block %d has %d entries", q, t->block_n[q]);
+    NT += t->block_n[q];
+  }
+  if (joint_lds_doubles((int)std::min<long long>(NT, 1 << 20), t->n_blocks, 0) * sizeof(double) > 160 * 1024)
+    return fail(lead, VK_E_ARG, "joint covariance: a joint vector of %lld entries needs more than 160 KiB of LDS", NT);
+  if (t->n_beta < 0 || t->n_beta > 4096) return fail(lead, VK_E_ARG, "joint covariance: bad n_beta %d", t->n_beta);
+  if (!t->prec) return fail(lead, VK_E_ARG, "joint covariance: prec is NULL");
+  if (t->n_beta > 0) {
+    if (!t->beta || !t->logdet || !t->eig) return fail(lead, VK_E_ARG, "joint covariance: beta, logdet and eig are required with n_beta > 0");
+    for (int i = 1; i < t->n_beta; ++i)
+      if (!(t->beta[i] > t->beta[i - 1])) return fail(lead, VK_E_ARG, "Covariance beta grid must be strictly monotonically increasing");
+  }
+  if (joint_lds_doubles((int)NT, t->n_blocks, t->n_beta) * sizeof(double) > 160 * 1024)
+    return fail(lead, VK_E_ARG, "joint covariance: %lld entries and %d slices need more than 160 KiB of LDS", NT, t->n_beta);
+  const int nt = (int)NT, ntp = joint_ntp(nt), slices = std::max(t->n_beta, 1);
+  // one host image, one allocation: beta | padded slices | logdet | eig
+  std::vector<double> img;
+  const size_t o_prec = ((size_t)t->n_beta + 1) & ~size_t(1);
+  const size_t o_logdet = o_prec + (size_t)slices * ntp * ntp;
+  const size_t o_eig = o_logdet + (((size_t)t->n_beta + 1) & ~size_t(1));
+  try {
+    img.assign(o_eig + (size_t)t->n_beta * nt, 0.0);
+  } catch (const std::bad_alloc&) {
+    return fail(lead, VK_E_NOMEM, "joint covariance: no host memory for a %zu-byte image of the tables", (o_eig + (size_t)t->n_beta * nt) * sizeof(double));
+  }
+  for (int i = 0; i < t->n_beta; ++i) img[i] = t->beta[i];
+  for (int s = 0; s < slices; ++s)
+    for (int i = 0; i < nt; ++i)
+      memcpy(&img[o_prec + ((size_t)s * ntp + i) * ntp], t->prec + ((size_t)s * nt + i) * nt, (size_t)nt * sizeof(double));
+  if (t->n_beta > 0) {
+    memcpy(&img[o_logdet], t->logdet, (size_t)t->n_beta * sizeof(double));
+    memcpy(&img[o_eig], t->eig, (size_t)t->n_beta * nt * sizeof(double));
+  }
+  VK_HIP(lead, hipSetDevice(lead->device));
+  vk_joint_cov* h = new (std::nothrow) vk_joint_cov;
+  if (!h) return fail(lead, VK_E_NOMEM, "joint covariance: out of host memory");
+  h->lead = lead;
+  h->device = lead->device;
+  h->block_n.assign(t->block_n, t->block_n + t->n_blocks);
+  h->NT = nt;
+  h->NTp = ntp;
+  h->n_beta = t->n_beta;
+  if (hipMalloc((void**)&h->d_mem, img.size() * sizeof(double)) != hipSuccess ||
+      hipMemcpy(h->d_mem, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+      hipEventCreateWithFlags(&h->ev_done, hipEventDisableTiming) != hipSuccess) {
+    if (h->d_mem) (void)hipFree(h->d_mem);
+    if (h->ev_done) (void)hipEventDestroy(h->ev_done);
+    delete h;
+    return fail(lead, VK_E_HIP, "joint covariance: upload of %zu bytes failed", img.size() * sizeof(double));
+  }
+  h->d_beta = h->d_mem;
+  h->d_prec = h->d_mem + o_prec;
+  h->d_logdet = h->d_mem + o_logdet;
+  h->d_eig = h->d_mem + o_eig;
+  *out = h;
+  return VK_OK;
+}
+
+void vk_joint_cov_destroy(vk_joint_cov* h) {
+  if (!h) return;
+  (void)hipSetDevice(h->device);
+  if (h->ev_done) {
+    (void)hipEventSynchronize(h->ev_done);   // the last evaluation that read the tables (its lead stream); nothing else is waited for
+    (void)hipEventDestroy(h->ev_done);
+  }
+  if (h->d_mem) (void)hipFree(h->d_mem);
+  delete h;
+}
+
+// workspace: theory vectors [n][NT] (block q at offset n * off_q) | sort: lo, rank, perm [n] ints, histograms [chunks + 1][n_beta]
+static size_t joint_cov_ws(const vk_joint_cov* h, int64_t n, size_t* o_sort) {
+  const size_t chunks = (size_t)(n + kJointSortChunk - 1) / kJointSortChunk;
+  *o_sort = (size_t)n * h->NT;
+  const size_t ints = h->n_beta > 0 ? 3 * (size_t)n + (chunks + 1) * h->n_beta : 0;
+  return *o_sort + (ints + 1) / 2;
+}
+
+size_t vk_joint_cov_workspace_doubles(const vk_joint_cov* h, int64_t n) {
+  if (!h || n < 0) return 0;
+  size_t o_sort;
+  return joint_cov_ws(h, n, &o_sort);
+}
+
+int vk_joint_cov_eval_device_async(vk_joint_cov* h, vk_ctx* const* ctxs, int32_t n_ctx, const vk_eval_opts* opts,
+                                   const double* d_params, int64_t n, double* d_lnl, double* d_chi2, double* d_ws) {
+  if (!ctxs || n_ctx < 1 || !ctxs[0]) return VK_E_ARG;
+  vk_ctx* lead = ctxs[0];
+  if (!h) return fail(lead, VK_E_ARG, "joint covariance: handle is NULL");
+  if (h->lead != lead) return fail(lead, VK_E_ARG, "joint covariance: ctxs[0] is not the context the handle was created with");
+  if (n_ctx != (int)h->block_n.size())
+    return fail(lead, VK_E_ARG, "joint covariance: %d contexts for %d blocks", n_ctx, (int)h->block_n.size());
+  for (int q = 0; q < n_ctx; ++q) {
+    if (!ctxs[q]) return fail(lead, VK_E_ARG, "context %d is NULL", q);
+    if (ctxs[q]->device != h->device) return fail(lead, VK_E_ARG, "joint fit: every context must live on the same device");
+    if (!ctxs[q]->d_data) return fail(lead, VK_E_ARG, "joint fit: context %d was created without a data vector", q);
+    if (ctxs[q]->N != h->block_n[q])
+      return fail(lead, VK_E_ARG, "joint covariance: block %d has %d entries, its context %d", q, h->block_n[q], ctxs[q]->N);
+  }
+  int rc = check_opts(lead, opts);
+  if (rc) return rc;
+  if (n < 0 || n > (1LL << 31) - kJointSortChunk || (n > 0 && (!d_params || !d_ws || !(d_lnl || d_chi2))))
+    return fail(lead, VK_E_ARG, "bad device buffers");
+  if (n == 0) return VK_OK;
+  VK_HIP(lead, hipSetDevice(lead->device));
+  size_t o_sort;
+  (void)joint_cov_ws(h, n, &o_sort);
+  for (int q = 0; q < n_ctx; ++q)
+    if (!ctxs[q]->ev_joint) VK_HIP(lead, hipEventCreateWithFlags(&ctxs[q]->ev_joint, hipEventDisableTiming));
+
+  JointArgs ja{};
+  fill_like_args(lead, opts, d_params, nullptr, n, d_lnl, d_chi2, &ja.like);
+  ja.like.N = h->NT;                    // the likelihood forms' p is the joint vector's length
+  ja.like.n_beta_d = 0;
+  ja.like.beta_d = nullptr;
+  ja.like.data = nullptr;
+  ja.like.n_beta_c = h->n_beta;
+  ja.like.beta_c = h->n_beta > 0 ? h->d_beta : nullptr;
+  ja.like.prec = h->d_prec;
+  ja.like.grids_in_lds = 0;
+  ja.like.tri = nullptr;
+  ja.like.logdet = h->n_beta > 0 ? h->d_logdet : nullptr;
+  ja.like.eig = h->n_beta > 0 ? h->d_eig : nullptr;
+  ja.NTp = h->NTp;
+  ja.n_blocks = n_ctx;
+
+  // the blocks' theory launches, theory only, each on its own stream behind what the lead stream has enqueued so far
+  VK_HIP(lead, hipEventRecord(lead->ev_joint, lead->stream));
+  int off = 0;
+  for (int q = 0; q < n_ctx; ++q) {
+    vk_ctx* c = ctxs[q];
+    if (q > 0) VK_HIP(lead, hipStreamWaitEvent(c->stream, lead->ev_joint, 0));
+    double* th = d_ws + (size_t)n * off;
+    c->depth_mult = n_ctx;
+    rc = vk_eval_batch_device_async(c, opts, d_params, n, nullptr, nullptr, th);
+    c->depth_mult = 1;
+    if (rc) {
+      if (c != lead) lead->err = c->err;
+      return rc;
+    }
+    JointBlock& b = ja.blk[q];
+    b.theory = th;
+    b.data = c->d_data;
+    b.beta_d = c->n_beta_d > 0 ? c->d_beta_d : nullptr;
+    b.n_beta_d = c->n_beta_d;
+    b.N = c->N;
+    b.off = off;
+    off += c->N;
+  }
+  // meanwhile on the lead stream: the points sorted by covariance slice (the data tables and params are ready behind ev_joint)
+  // from the first launch that reads the handle's tables on, every exit records ev_done behind what was enqueued
+  // (vk_joint_cov_destroy waits for it)
+  hipError_t e = hipSuccess;
+  if (h->n_beta > 0) {
+    int* lo = reinterpret_cast<int*>(d_ws + o_sort);
+    int* rank = lo + n;
+    int* perm = rank + n;
+    int* hist = perm + n;
+    const int chunks = (int)((n + kJointSortChunk - 1) / kJointSortChunk);
+    hipLaunchKernelGGL(vk_joint_rank_kernel, dim3(chunks), dim3(kBlock), 0, lead->stream, ja, lo, rank, hist);
+    if ((e = hipGetLastError()) == hipSuccess) {
+      hipLaunchKernelGGL(vk_joint_offsets_kernel, dim3(1), dim3(kBlock), 0, lead->stream, hist, chunks, h->n_beta);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(vk_joint_scatter_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, lead->stream,
+                         (const int*)lo, (const int*)rank, (const int*)hist, h->n_beta, (long long)n, perm);
+      e = hipGetLastError();
+    }
+    ja.perm = perm;
+  }
+  for (int q = 1; q < n_ctx && e == hipSuccess; ++q) {
+    e = hipEventRecord(ctxs[q]->ev_joint, ctxs[q]->stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(lead->stream, ctxs[q]->ev_joint, 0);
+  }
+  rc = VK_OK;
+  if (e != hipSuccess) {
+    rc = fail(lead, VK_E_HIP, "joint covariance: enqueue failed: %s", hipGetErrorString(e));
+  } else {
+    const size_t lds = joint_lds_doubles(h->NT, n_ctx, h->n_beta) * sizeof(double);
+    lead->last_like = "joint_chi2";
+    rc = launch_on_stream(lead, vk_joint_chi2_kernel, (int)((n + kJointRows - 1) / kJointRows), lds, ja);
+  }
+  const hipError_t er = hipEventRecord(h->ev_done, lead->stream);
+  if (rc) return rc;
+  if (er != hipSuccess) return fail(lead, VK_E_HIP, "hipEventRecord failed: %s", hipGetErrorString(er));
   return VK_OK;
 }
 

@@ -205,7 +205,6 @@ def build_tables(model, fit=None, matter_model=None, simpson_even=None):
 
     # data side -----------------------------------------------------------------------------
     if fit is not None:
-        Nd = len(s) * len(poles)
         stack = np.array([fit.redshift_multipoles[f"{l}"] for l in poles])   # (n_ell, [n_beta,] n_s)
         d = arr(data_table(stack, fit.fixed_data, fit.beta_ccf if not fit.fixed_data else None))
         if fit.fixed_data:
@@ -220,30 +219,9 @@ def build_tables(model, fit=None, matter_model=None, simpson_even=None):
         if fit.fixed_covmat:
             t.n_beta_c = 0
         else:
-            import scipy.linalg as sl
             bc = arr(fit.beta_covmat)
             nb = len(bc)
-            logdet = np.empty(nb)
-            eig = np.ones((nb, Nd))
-            for kk in range(nb):
-                sign, ld = np.linalg.slogdet(fit.covmat[kk])
-                logdet[kk] = ld if sign == 1 else np.nan
-                if kk < nb - 1 and sign == 1:
-                    # cov[last] v = lambda cov[k] v  =>  det((1-t) cov[k] + t cov[last]) = det(cov[k]) prod(1-t+t lambda)
-                    try:
-                        eig[kk] = sl.eigh(fit.covmat[-1], fit.covmat[kk], eigvals_only=True)
-                    except np.linalg.LinAlgError:
-                        # slice k has a positive determinant but is not positive definite (an even number of negative
-                        # eigenvalues): the identity above does not hold through eigh.  The reference constructs such a
-                        # fit and decides point by point from slogdet of the blend (ccf_fit.py:447-450).  Here the slice
-                        # keeps its own log det - a point ON this grid value (t = 0, no blend) evaluates as in the
-                        # reference - and NaN factors mark every BLENDED evaluation that starts from it as failed
-                        # (-inf, inf): a covariance matrix that is not positive definite is an input error in any case.
-                        import warnings
-                        warnings.warn("covariance slice %d (beta = %g) has a positive determinant but is not positive "
-                                      "definite: likelihood evaluations that interpolate from it (beta between this grid "
-                                      "value and the next) will report -inf" % (kk, float(bc[kk])), RuntimeWarning)
-                        eig[kk] = np.nan
+            logdet, eig = covariance_logdets(fit.covmat, bc)
             logdet = arr(logdet)
             eig = arr(eig)
             t.n_beta_c = nb
@@ -251,6 +229,38 @@ def build_tables(model, fit=None, matter_model=None, simpson_even=None):
             t.logdet = N.as_dp(logdet)
             t.eig = N.as_dp(eig)
     return t, keep
+
+
+def covariance_logdets(covmat, beta):
+    """``vk_tables.logdet`` and ``vk_tables.eig`` of the covariance slices ``covmat`` [n_beta][N][N] on the grid ``beta``: the log
+    det of every slice (NaN where its sign is not +1) and the generalised eigenvalues that give the determinant of a blend of
+    slice k with the last one (ccf_fit.py:445-451).  Shared by single fits (:func:`build_tables`) and the full-covariance joint
+    fit (:class:`victor_amd.joint.JointFit`)."""
+    import scipy.linalg as sl
+    nb = len(beta)
+    Nd = covmat.shape[-1]
+    logdet = np.empty(nb)
+    eig = np.ones((nb, Nd))
+    for kk in range(nb):
+        sign, ld = np.linalg.slogdet(covmat[kk])
+        logdet[kk] = ld if sign == 1 else np.nan
+        if kk < nb - 1 and sign == 1:
+            # cov[last] v = lambda cov[k] v  =>  det((1-t) cov[k] + t cov[last]) = det(cov[k]) prod(1-t+t lambda)
+            try:
+                eig[kk] = sl.eigh(covmat[-1], covmat[kk], eigvals_only=True)
+            except np.linalg.LinAlgError:
+                # slice k has a positive determinant but is not positive definite (an even number of negative
+                # eigenvalues): the identity above does not hold through eigh.  The reference constructs such a
+                # fit and decides point by point from slogdet of the blend (ccf_fit.py:447-450).  Here the slice
+                # keeps its own log det - a point ON this grid value (t = 0, no blend) evaluates as in the
+                # reference - and NaN factors mark every BLENDED evaluation that starts from it as failed
+                # (-inf, inf): a covariance matrix that is not positive definite is an input error in any case.
+                import warnings
+                warnings.warn("covariance slice %d (beta = %g) has a positive determinant but is not positive "
+                              "definite: likelihood evaluations that interpolate from it (beta between this grid "
+                              "value and the next) will report -inf" % (kk, float(beta[kk])), RuntimeWarning)
+                eig[kk] = np.nan
+    return logdet, eig
 
 
 def data_table(stack, fixed_data, beta=None):

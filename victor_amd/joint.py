@@ -4,7 +4,14 @@ The reference mentions density-split centres only in passing (``ccf_model.py:28-
 class; BASELINE config "density-split 5-quantile joint fit" is defined as Q independent ``CCFFit`` blocks with a
 block-diagonal covariance, so chi-square and log-likelihood add.  Each block keeps its own context (tables in
 HBM) on the same GPU; one batch of parameter rows is run through every block.
+
+With ``covariance=`` the blocks are fitted under ONE covariance matrix across the joint vector - the concatenation of the
+blocks' data vectors in block order - as the reference's ``CCFFit`` would fit that vector: the quantiles of a density-split
+analysis share their galaxies and voids, so their data vectors are correlated.  The blocks' theory vectors come from their
+own theory launches; the joint chi-square is one kernel (``vk_joint_cov_eval_device_async``, ``vk_kernel_joint.h``).
 """
+
+import os
 
 import numpy as np
 
@@ -12,14 +19,203 @@ import numpy as np
 import ctypes as C
 
 from . import _native as N
+from .utils import InputError
 
 
 class JointFit:
-    def __init__(self, fits):
+    def __init__(self, fits, covariance=None, likelihood=None):
+        """``covariance``: ``None`` - block-diagonal, each block under its own covariance (chi-square and lnL add); a
+        ``(NT, NT)`` array - one fixed covariance of the joint vector, NT = the sum of the blocks' N; or a dict in the
+        reference's ``covariance_matrix`` schema (``data_file``, ``cov_key``, ``fixed_beta``, ``beta_key``, plus ``dir``), read
+        as ``CCFFit`` reads its own.  ``likelihood``: ``{"form", "nmocks", "nparams"}`` of the joint fit (default: the first
+        block's); the Hartlap and Percival corrections take p = NT."""
         self.fits = list(fits)
         if not self.fits:
             raise ValueError("need at least one fit")
         self._buffers = None
+        self.covariance = None
+        self._handle = None
+        if covariance is None:
+            if likelihood is not None:
+                raise InputError("JointFit: likelihood= applies to a joint covariance only (covariance=None keeps each block's own)")
+            return
+        self.likelihood = dict(likelihood if likelihood is not None else self.fits[0].fit_options["likelihood"])
+        self._load_joint_covariance(covariance)
+
+    # ------------------------------------------------------------------ full covariance: set-up (host)
+    def _load_joint_covariance(self, covariance):
+        from .ccf_fit import load_covariance_matrix
+        from .engine import covariance_logdets
+        nt = self.n_data
+        self.fixed_data = all(f.fixed_data for f in self.fits)
+        if isinstance(covariance, dict):
+            fn = os.path.join(covariance.get("dir", ""), covariance.get("data_file"))
+            if not os.path.isfile(fn):
+                raise InputError(f"Data file {fn} not found")
+            grids = [f.beta_ccf for f in self.fits if not f.fixed_data]
+            self.fixed_covmat, beta_covmat, self.covmat, self.icov = load_covariance_matrix(
+                covariance, fn, self.fits[0].extensions, nt, self.fixed_data, grids[0] if grids else None)
+            if not self.fixed_covmat:
+                # the loader falls back to the data's grid (hands back grids[0] itself) when beta_key is not given or not in
+                # the file; with blocks on different data grids there is no such grid
+                if beta_covmat is grids[0] and any(not np.array_equal(g, grids[0]) for g in grids[1:]):
+                    raise InputError("JointFit: the blocks' data beta grids differ and the covariance file holds no beta grid "
+                                     "(beta_key)")
+                self.beta_covmat = np.asarray(beta_covmat, dtype=float)
+        else:
+            covmat = np.asarray(covariance, dtype=float)
+            if covmat.shape != (nt, nt):
+                raise InputError("Unexpected shape of (fixed) covariance matrix")
+            self.fixed_covmat = True
+            self.covmat = covmat
+            self.icov = np.linalg.inv(covmat)
+        if self.fixed_covmat:
+            self._logdet = self._eig = None
+        else:
+            self._logdet, self._eig = covariance_logdets(self.covmat, self.beta_covmat)
+        self.covariance = covariance
+
+    def _bracket(self, beta):
+        """(low index, weight of the LAST grid entry) of the covariance slices, as ``CCFFit._bracket`` (ccf_fit.py:213-228)."""
+        g = self.beta_covmat
+        if beta < g.min():
+            return 0, 0.0
+        if beta > g.max():
+            return len(g) - 1, 0.0
+        if beta in g:
+            return int(np.where(g == beta)[0][0]), 0.0
+        lo = int(np.where(g < beta)[0][-1])
+        hi = int(np.where(g >= beta)[0][-1])
+        return lo, (beta - g[lo]) / (g[hi] - g[lo])
+
+    def _interp_stack(self, stack, beta):
+        if self.fixed_covmat:
+            return stack
+        if beta is None:
+            raise InputError("Need to supply a valid value of beta for interpolation")
+        lo, t = self._bracket(beta)
+        if t == 0.0:
+            return stack[lo]
+        return (1 - t) * stack[lo] + t * stack[-1]
+
+    def get_interpolated_covariance(self, beta=None):
+        """(NT, NT) covariance of the joint vector at ``beta`` (the bracket rule of ccf_fit.py:195-228)."""
+        if self.covariance is None:
+            import scipy.linalg as sl
+            return sl.block_diag(*[f.get_interpolated_covariance(beta) for f in self.fits])
+        return self._interp_stack(self.covmat, beta)
+
+    def get_interpolated_precision(self, beta=None):
+        """(NT, NT) precision of the joint vector at ``beta`` (ccf_fit.py:230-260): the blend of the precision slices."""
+        if self.covariance is None:
+            import scipy.linalg as sl
+            return sl.block_diag(*[f.get_interpolated_precision(beta) for f in self.fits])
+        return self._interp_stack(self.icov, beta)
+
+    def multipole_datavector(self, beta=None):
+        """(NT,) joint data vector at ``beta``: the blocks' ``multipole_datavector`` concatenated in the order of ``fits``."""
+        return np.concatenate([f.multipole_datavector(beta) for f in self.fits])
+
+    # ------------------------------------------------------------------ full covariance: evaluation (device)
+    def _plan_cov(self, kwargs):
+        """(engines, opts) of a full-covariance evaluation; InputError where the blocks cannot share one launch: a sum over
+        blocks is wrong under a full covariance, so there is no per-block route."""
+        kw = dict(kwargs)
+        like = kw.pop("likelihood", self.likelihood)
+        models, fos, rowsig = [], [], []
+        for fit in self.fits:
+            model = fit._merged(kw)
+            fit._check_supported(model)
+            fo = fit._merged_fit(kw)
+            fo["likelihood"] = like
+            if fo["beta_interpolation"] == "likelihood" and not fit.fixed_data:
+                raise InputError("JointFit with a joint covariance: beta_interpolation 'likelihood' with beta-dependent data "
+                                 "is not supported")
+            models.append(model)
+            fos.append(fo)
+            rowsig.append((fit._needs_beta(model) or not fit.fixed_data, fit._needs_fsigma8(model), model["bias"]))
+        if len({f._device for f in self.fits}) != 1:
+            raise InputError("JointFit with a joint covariance: every block must live on the same device")
+        if any(m != models[0] for m in models) or any(f != fos[0] for f in fos) or len(set(rowsig)) != 1:
+            raise InputError("JointFit with a joint covariance: every block must share its model and fit options and its "
+                             "data's beta dependence")
+        engines, blobs = [], []
+        opts = None
+        for fit, model, fo in zip(self.fits, models, fos):
+            eng = fit._get_engine(fit._engine_key(model), model["simpson_even"])
+            opts = eng.make_opts(model, fo)
+            engines.append(eng)
+            blobs.append(bytes(opts))
+        if len(set(blobs)) != 1 or len({e.device for e in engines}) != 1:
+            raise InputError("JointFit with a joint covariance: the blocks' option blocks differ")
+        return engines, opts
+
+    def _joint_handle(self, lead):
+        """The device copy of the joint covariance tables (``vk_joint_cov_create``), made once per lead engine."""
+        h = self._handle
+        if h is not None and h[0] is lead:
+            return h[1]
+        self._release_handle()
+        nt = self.n_data
+        block_n = np.array([len(f.s) * len(f.poles_s) for f in self.fits], dtype=np.int32)
+        t = N.vk_joint_cov_tables()
+        t.n_blocks = len(block_n)
+        t.block_n = block_n.ctypes.data_as(C.POINTER(C.c_int32))
+        prec = N.f64(self.icov)
+        t.prec = N.as_dp(prec)
+        keep = [block_n, prec]
+        if self.fixed_covmat:
+            t.n_beta = 0
+        else:
+            beta, logdet, eig = N.f64(self.beta_covmat), N.f64(self._logdet), N.f64(self._eig)
+            keep += [beta, logdet, eig]
+            t.n_beta = len(beta)
+            t.beta, t.logdet, t.eig = N.as_dp(beta), N.as_dp(logdet), N.as_dp(eig)
+        assert prec.size == max(t.n_beta, 1) * nt * nt
+        out = C.c_void_p()
+        lead._check(lead._lib.vk_joint_cov_create(lead._ctx, C.byref(t), C.byref(out)))
+        del keep
+        self._handle = (lead, out.value)
+        return out.value
+
+    def _release_handle(self):
+        h = getattr(self, "_handle", None)
+        if h is not None:
+            h[0]._lib.vk_joint_cov_destroy(h[1])
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self._release_handle()
+        except Exception:
+            pass
+
+    def _log_likelihood_cov(self, params, kwargs):
+        engines, opts = self._plan_cov(kwargs)
+        fit = self.fits[0]
+        rows = fit._fit_rows(params, fit._merged({k: v for k, v in kwargs.items() if k != "likelihood"}))
+        n = len(rows)
+        if n == 0:
+            return np.empty(0), np.empty(0)
+        lead = engines[0]
+        handle = self._joint_handle(lead)
+        ctxs = (C.c_void_p * len(engines))(*[e._ctx for e in engines])
+        need = lead._lib.vk_joint_cov_workspace_doubles(handle, n)
+        b = self._buffers
+        if b is None or b.get("cov", -1) < need or b["n"] < n or b["lead"] is not lead:
+            if b is not None:
+                for ptr in b["ptrs"]:
+                    b["lead"].free(ptr)
+            self._buffers = None
+            b = self._buffers = {"n": n, "lead": lead, "cov": need,
+                                 "ptrs": [lead.alloc(n * N.VK_NPAR), lead.alloc(2 * n), lead.alloc(need)]}
+        d_rows, d_out, d_ws = b["ptrs"]
+        lead.upload(d_rows, rows)
+        d_chi = C.c_void_p(d_out + 8 * n)
+        lead._check(lead._lib.vk_joint_cov_eval_device_async(handle, ctxs, len(engines), C.byref(opts), d_rows, n, d_out,
+                                                             d_chi, d_ws))
+        out = lead.download(d_out, 2 * n)
+        return out[:n].copy(), out[n:].copy()
 
     # ------------------------------------------------------------------ device-resident joint evaluation
     def _plan(self, kwargs):
@@ -64,7 +260,10 @@ class JointFit:
 
     def log_likelihood_batch(self, params, **kwargs):
         """(lnL[n], chi2[n]) summed over the blocks: one parameter upload, every block's kernels enqueued without a host
-        synchronisation in between, the sums taken on the device (``vk_joint_eval_device_async``)."""
+        synchronisation in between, the sums taken on the device (``vk_joint_eval_device_async``).  Under a joint covariance:
+        the chi-square of the joint vector and its likelihood form (``vk_joint_cov_eval_device_async``)."""
+        if self.covariance is not None:
+            return self._log_likelihood_cov(params, kwargs)
         plan = self._plan(kwargs)
         if plan is None:
             return self._sequential(params, kwargs)
