@@ -15,6 +15,8 @@
  *   vk_xi_smu_batch      CCFModel.theory_xi           victor/ccf_model.py:538-789
  *   vk_eval_realisations CCFFit.log_likelihood against every simulation realisation of the
  *                        data file (simulation_number, victor/ccf_fit.py:59-61,93-100)
+ *   vk_joint_cov_eval_realisations  the same for a joint fit under one covariance: realisation m
+ *                        of every block's own file (victor/ccf_fit.py:59-61,93-100,325-483)
  *   vk_create            CCFModel.__init__ / CCFFit.__init__ table set-up
  *                        victor/ccf_model.py:33-97, victor/ccf_fit.py:15-42
  *                        (the host has already turned every spline into explicit
@@ -38,7 +40,7 @@
 extern "C" {
 #endif
 
-#define VK_ABI_VERSION 21
+#define VK_ABI_VERSION 22
 
 /* error codes */
 #define VK_OK 0
@@ -299,7 +301,8 @@ const char* vk_last_kernel(const vk_ctx* ctx);
 /* the exact instantiation of that launch and the chi-square kernel that ran with it, "cells<3,2,1,dispersion,0>+fused",
  * "fast<1,1,0,from_data,0>+like_tiled<8>", "generic<kaiser,2,3>+like", "cells<1,1,0,streaming,0>+none" (theory only),
  * "xi<euclid,1>" (K1x), "cells<3,2,1,streaming,0>+joint_chi2" (the lead context of vk_joint_cov_eval_device_async: the
- * lead block's theory launch and the joint chi-square kernel); valid until the next call on ctx */
+ * lead block's theory launch and the joint chi-square kernel; "+joint_real_chi2" after vk_joint_cov_eval_realisations);
+ * valid until the next call on ctx */
 const char* vk_last_instance(const vk_ctx* ctx);
 /* 1 when that launch also took the chi-square / log-likelihood (fused tail), 0 when K2 ran as its own launch */
 int vk_last_fused(const vk_ctx* ctx);
@@ -454,6 +457,23 @@ void vk_joint_cov_destroy(vk_joint_cov* h);
 size_t vk_joint_cov_workspace_doubles(const vk_joint_cov* h, int64_t n);
 int vk_joint_cov_eval_device_async(vk_joint_cov* h, vk_ctx* const* ctxs, int32_t n_ctx, const vk_eval_opts* opts,
                                    const double* d_params, int64_t n, double* d_lnl, double* d_chi2, double* d_ws);
+
+/* ---- joint fit under ONE covariance against many simulation realisations of every block --------------------------------
+ * Validating a density-split pipeline on the mocks its joint covariance was estimated from: joint realisation m is realisation
+ * m of EVERY block, each read from that block's own stacked file as simulation_number reads it (victor/ccf_fit.py:59-61,93-100),
+ * and the joint vector is evaluated as vk_joint_cov_eval_device_async evaluates it (victor/ccf_fit.py:325-483 on the
+ * concatenation: the bracket rule of :213-228, -1/2 log det C(beta) of :444-451, the likelihood forms of :455-473 with p = NT,
+ * the (-inf, inf) guards of :448-450, 477-481).  The theory vectors do not depend on the realisation: each chunk of points runs
+ * every block's theory launch once (theory only, on its own stream), then one chi-square kernel over the (point, realisation)
+ * pairs; -1/2 log det is taken once per point.
+ * vk_joint_cov_eval_realisations: the realisations of block q are those set on ctxs[q] with vk_set_realisations; every context
+ *   must hold the same n_real.  which == NULL - every point against every realisation, lnl / chi2 [n][n_real]; otherwise
+ *   which[i] is the realisation (0 .. n_real-1) of point i and lnl / chi2 are [n].  Both modes return the same bits for the same
+ *   (point, realisation).  Either output may be NULL.  Host buffers, synchronous; large batches are cut into launches whose
+ *   outputs stay below 256 MB.  VK_E_ARG for the checks of vk_joint_cov_eval_device_async, a context without realisations,
+ *   contexts with different n_real and an index of which out of range. */
+int vk_joint_cov_eval_realisations(vk_joint_cov* h, vk_ctx* const* ctxs, int32_t n_ctx, const vk_eval_opts* opts,
+                                   const double* params, int64_t n, const int32_t* which, double* lnl, double* chi2);
 
 /* ---- many one-point callers sharing one GPU: mailboxes in shared memory -----------------------------------------------
  * The reference is sampled by cobaya, which asks for ONE likelihood per call (victor/likelihoods/CCFLikelihood.py:32-39); more

@@ -8,8 +8,9 @@ from . import utils
 from .ccf_fit import CCFFit
 from .ccf_model import CCFModel
 from .cosmology import BackgroundCosmology
+from .joint import JointFit, JointRealisations
 from .realisations import Realisations
 from .utils import InputError
 
 __version__ = "0.1.0"
-__all__ = ["CCFModel", "CCFFit", "BackgroundCosmology", "InputError", "Realisations", "utils", "__version__"]
+__all__ = ["CCFModel", "CCFFit", "BackgroundCosmology", "InputError", "JointFit", "JointRealisations", "Realisations", "utils", "__version__"]

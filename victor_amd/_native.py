@@ -11,7 +11,7 @@ import os
 
 import numpy as np
 
-VK_ABI_VERSION = 21
+VK_ABI_VERSION = 22
 VK_NPAR = 12
 (P_FSIGMA8, P_SIGMAV, P_APERP, P_APAR, P_EPSILON, P_BETA, P_ASTAR, P_M, P_Q, P_BIAS, P_AV, P_SPARE) = range(12)
 MATTER = {"template": 0, "linear_bias": 1, "velocity_template": 2}
@@ -139,6 +139,8 @@ SYMBOLS = {
     "vk_joint_cov_destroy": (None, [_vp]),
     "vk_joint_cov_workspace_doubles": (C.c_size_t, [_vp, C.c_int64]),
     "vk_joint_cov_eval_device_async": (C.c_int, [_vp, C.POINTER(C.c_void_p), C.c_int32, _optp, _vp, C.c_int64, _vp, _vp, _vp]),
+    "vk_joint_cov_eval_realisations": (C.c_int, [_vp, C.POINTER(C.c_void_p), C.c_int32, _optp, _dp, C.c_int64,
+                                                 C.POINTER(C.c_int32), _dp, _dp]),
     "vk_serve_mailboxes": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, _optp, _vp, C.c_int32, _vp, C.c_double, C.c_int32,
                            C.c_double, C.POINTER(vk_serve_stats)]),
     "vk_timing_enable": (C.c_int, [_vp, C.c_int]),

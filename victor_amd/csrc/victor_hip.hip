@@ -16,6 +16,8 @@
 //   vk_kernel_real.h     K2 against many realisations of the data vector (vk_eval_realisations): f64 MFMA, one point per workgroup
 //   vk_kernel_joint.h    K2 of a joint fit under one covariance across its data vectors (vk_joint_cov_eval_device_async): f64 MFMA,
 //                        16 points per workgroup, the precision streamed from L2
+//   vk_kernel_joint_real.h  the same against many realisations of every block (vk_joint_cov_eval_realisations): rows are
+//                        (point, realisation) pairs, 16 realisations of one point per workgroup
 //
 // K1 restates CCFModel.theory_xi (streaming branch victor/ccf_model.py:589-690; the other branches :658-784),
 // theory_multipoles (:816-825) and utils.multipoles_from_fn (victor/utils.py:45-56); K2 restates CCFFit.chi_squared
@@ -23,7 +25,7 @@
 // All arithmetic is IEEE binary64 on the vector ALU: an evaluation is n_s*n_mu*n_x (= 200 000) integrand points of
 // ~80 FP64 instructions each against ~100 bytes of HBM traffic, so the kernels are laid out for VALU issue and LDS
 // gather bandwidth, not for HBM or MFMA - except the chi-square against many realisations and the
-// chi-square of a joint fit under a full covariance, batched matrix products on the FP64 matrix cores.  launch_theory() picks the K1 variant per call.
+// chi-square of a joint fit under a full covariance (against one or many realisations), batched matrix products on the FP64 matrix cores.  launch_theory() picks the K1 variant per call.
 
 #include <hip/hip_runtime.h>
 #include <chrono>
@@ -54,6 +56,7 @@
 #include "vk_kernel_like.h"
 #include "vk_kernel_real.h"
 #include "vk_kernel_joint.h"
+#include "vk_kernel_joint_real.h"
 
 // The theory kernels' instantiations are generated in translation units of their own (vk_instances.h names what lives where);
 // here they are declared only.
@@ -2218,6 +2221,166 @@ int vk_eval_realisations(vk_ctx* ctx, const vk_eval_opts* opts, const double* pa
     if (lnl) VK_HIP(ctx, hipMemcpyAsync(lnl + off * per_point, d_lnl, nb, hipMemcpyDeviceToHost, ctx->stream));
     if (chi2) VK_HIP(ctx, hipMemcpyAsync(chi2 + off * per_point, d_chi, nb, hipMemcpyDeviceToHost, ctx->stream));
     rc = vk_sync(ctx);
+    if (rc) return rc;
+  }
+  return VK_OK;
+}
+
+// ---- joint fit under one covariance against many realisations of every block (include/victor_hip.h, vk_kernel_joint_real.h) -
+int vk_joint_cov_eval_realisations(vk_joint_cov* h, vk_ctx* const* ctxs, int32_t n_ctx, const vk_eval_opts* opts,
+                                   const double* params, int64_t n, const int32_t* which, double* lnl, double* chi2) {
+  if (!ctxs || n_ctx < 1 || !ctxs[0]) return VK_E_ARG;
+  vk_ctx* lead = ctxs[0];
+  if (!h) return fail(lead, VK_E_ARG, "joint covariance: handle is NULL");
+  if (h->lead != lead) return fail(lead, VK_E_ARG, "joint covariance: ctxs[0] is not the context the handle was created with");
+  if (n_ctx != (int)h->block_n.size())
+    return fail(lead, VK_E_ARG, "joint covariance: %d contexts for %d blocks", n_ctx, (int)h->block_n.size());
+  for (int q = 0; q < n_ctx; ++q) {
+    vk_ctx* c = ctxs[q];
+    if (!c) return fail(lead, VK_E_ARG, "context %d is NULL", q);
+    if (c->device != h->device) return fail(lead, VK_E_ARG, "joint fit: every context must live on the same device");
+    if (!c->d_data) return fail(lead, VK_E_ARG, "joint fit: context %d was created without a data vector", q);
+    if (c->N != h->block_n[q])
+      return fail(lead, VK_E_ARG, "joint covariance: block %d has %d entries, its context %d", q, h->block_n[q], c->N);
+    if (c->begun_n != 0)
+      return fail(lead, VK_E_ARG, "a batch begun with vk_eval_batch_begin is awaiting vk_eval_batch_finish on context %d", q);
+    if (c->n_real <= 0 || !c->d_real)
+      return fail(lead, VK_E_ARG, "no realisations are set on context %d (vk_set_realisations)", q);
+    if (c->n_real != ctxs[0]->n_real)
+      return fail(lead, VK_E_ARG, "context %d holds %d realisations, context 0 holds %d", q, c->n_real, ctxs[0]->n_real);
+  }
+  const int n_real = lead->n_real;
+  int rc = check_opts(lead, opts);
+  if (rc) return rc;
+  if (n < 0 || (n > 0 && !params)) return fail(lead, VK_E_ARG, "params is NULL");
+  if (n > (1LL << 31) - kJointSortChunk) return fail(lead, VK_E_ARG, "%lld points: at most 2^31 - %d", (long long)n, kJointSortChunk);
+  if (which)
+    for (int64_t i = 0; i < n; ++i)
+      if (which[i] < 0 || which[i] >= n_real)
+        return fail(lead, VK_E_ARG, "realisation index %d of point %lld is outside 0..%d", which[i], (long long)i, n_real - 1);
+  if (n == 0) return VK_OK;
+  const size_t lds = joint_real_lds_doubles(h->NT, n_ctx, h->n_beta) * sizeof(double);
+  if (lds > 160 * 1024)
+    return fail(lead, VK_E_ARG, "joint covariance: %d entries and %d slices need more than 160 KiB of LDS", h->NT, h->n_beta);
+  VK_HIP(lead, hipSetDevice(lead->device));
+  // Points go through in chunks whose two output arrays stay below 256 MB, as in vk_eval_realisations; a chunk is every block's
+  // theory launch (theory only, each on its own stream) and the joint chi-square launch behind them.
+  const long long per_point = which ? 1 : n_real;
+  const long long chunk = std::max<long long>(1, std::min<long long>(65536, (256LL << 20) / (8 * per_point)));
+  const long long m_max = std::min<long long>(chunk, n);
+  const long long chunks_max = (m_max + kJointSortChunk - 1) / kJointSortChunk;
+  // scratch: params | theory [m][NT] (block q at offset m * off_q) | lnl | chi2 | -1/2 log det [m] | ints: which, singular,
+  // and the slice sort's lo, rank, perm [m] and histograms [chunks + 1][n_beta]
+  const size_t ints = (size_t)m_max * 5 + (size_t)(chunks_max + 1) * h->n_beta;
+  const size_t doubles = (size_t)m_max * (VK_NPAR + h->NT + 2 * per_point + 1) + (ints + 1) / 2 + 1;
+  rc = ensure_scratch(lead, doubles * sizeof(double));
+  if (rc) return rc;
+  double* d_par = lead->d_scratch;
+  double* d_th = d_par + (size_t)m_max * VK_NPAR;
+  double* d_lnl = d_th + (size_t)m_max * h->NT;
+  double* d_chi = d_lnl + (size_t)m_max * per_point;
+  double* d_fac = d_chi + (size_t)m_max * per_point;
+  int32_t* d_which = reinterpret_cast<int32_t*>(d_fac + m_max);
+  int* d_bad = d_which + m_max;
+  int* d_lo = d_bad + m_max;
+  int* d_rank = d_lo + m_max;
+  int* d_perm = d_rank + m_max;
+  int* d_hist = d_perm + m_max;
+  for (int q = 0; q < n_ctx; ++q)
+    if (!ctxs[q]->ev_joint) VK_HIP(lead, hipEventCreateWithFlags(&ctxs[q]->ev_joint, hipEventDisableTiming));
+
+  for (long long off = 0; off < n; off += m_max) {
+    const long long m = std::min<long long>(m_max, n - off);
+    VK_HIP(lead, hipMemcpyAsync(d_par, params + off * VK_NPAR, (size_t)m * VK_NPAR * sizeof(double), hipMemcpyHostToDevice,
+                                lead->stream));
+    if (which)
+      VK_HIP(lead, hipMemcpyAsync(d_which, which + off, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, lead->stream));
+    JointRealArgs jr{};
+    JointArgs& ja = jr.joint;
+    fill_like_args(lead, opts, d_par, nullptr, m, lnl ? d_lnl : nullptr, chi2 ? d_chi : nullptr, &ja.like);
+    ja.like.N = h->NT;                  // the likelihood forms' p is the joint vector's length
+    ja.like.n_beta_d = 0;
+    ja.like.beta_d = nullptr;
+    ja.like.data = nullptr;
+    ja.like.n_beta_c = h->n_beta;
+    ja.like.beta_c = h->n_beta > 0 ? h->d_beta : nullptr;
+    ja.like.prec = h->d_prec;
+    ja.like.grids_in_lds = 0;
+    ja.like.tri = nullptr;
+    ja.like.logdet = h->n_beta > 0 ? h->d_logdet : nullptr;
+    ja.like.eig = h->n_beta > 0 ? h->d_eig : nullptr;
+    ja.NTp = h->NTp;
+    ja.n_blocks = n_ctx;
+    jr.n_real = n_real;
+    jr.which = which ? d_which : nullptr;
+
+    // the blocks' theory launches, theory only, each on its own stream behind the lead stream (the parameters are there)
+    VK_HIP(lead, hipEventRecord(lead->ev_joint, lead->stream));
+    int at = 0;
+    for (int q = 0; q < n_ctx; ++q) {
+      vk_ctx* c = ctxs[q];
+      if (q > 0) VK_HIP(lead, hipStreamWaitEvent(c->stream, lead->ev_joint, 0));
+      double* th = d_th + (size_t)m * at;
+      c->depth_mult = n_ctx;
+      rc = vk_eval_batch_device_async(c, opts, d_par, m, nullptr, nullptr, th);
+      c->depth_mult = 1;
+      if (rc) {
+        if (c != lead) lead->err = c->err;
+        return rc;
+      }
+      JointBlock& b = ja.blk[q];
+      b.theory = th;
+      b.data = c->d_real;
+      b.beta_d = c->n_beta_d > 0 ? c->d_beta_d : nullptr;
+      b.n_beta_d = c->n_beta_d;
+      b.N = c->N;
+      b.off = at;
+      jr.stride[q] = c->real_block;
+      at += c->N;
+    }
+    // meanwhile on the lead stream: the log-det factor of every point and, in pairs mode, the points sorted by covariance slice;
+    // from the first launch that reads the handle's tables on, every exit records ev_done behind what was enqueued
+    hipError_t e = hipSuccess;
+    if (h->n_beta > 0) {
+      hipLaunchKernelGGL(vk_joint_real_factor_kernel, dim3((unsigned)((m + kWaves - 1) / kWaves)), dim3(kBlock), 0, lead->stream,
+                         ja, d_fac, d_bad);
+      e = hipGetLastError();
+      jr.fac = d_fac;
+      jr.bad = d_bad;
+      if (which && e == hipSuccess) {
+        const int chunks = (int)((m + kJointSortChunk - 1) / kJointSortChunk);
+        hipLaunchKernelGGL(vk_joint_rank_kernel, dim3(chunks), dim3(kBlock), 0, lead->stream, ja, d_lo, d_rank, d_hist);
+        if ((e = hipGetLastError()) == hipSuccess) {
+          hipLaunchKernelGGL(vk_joint_offsets_kernel, dim3(1), dim3(kBlock), 0, lead->stream, d_hist, chunks, h->n_beta);
+          e = hipGetLastError();
+        }
+        if (e == hipSuccess) {
+          hipLaunchKernelGGL(vk_joint_scatter_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, lead->stream,
+                             (const int*)d_lo, (const int*)d_rank, (const int*)d_hist, h->n_beta, (long long)m, d_perm);
+          e = hipGetLastError();
+        }
+        ja.perm = d_perm;
+      }
+    }
+    for (int q = 1; q < n_ctx && e == hipSuccess; ++q) {
+      e = hipEventRecord(ctxs[q]->ev_joint, ctxs[q]->stream);
+      if (e == hipSuccess) e = hipStreamWaitEvent(lead->stream, ctxs[q]->ev_joint, 0);
+    }
+    if (e != hipSuccess) {
+      rc = fail(lead, VK_E_HIP, "joint covariance: enqueue failed: %s", hipGetErrorString(e));
+    } else {
+      // cross mode: ceil(n_real / 16) tiles per point, one point per tile; pairs mode: 16 points per tile
+      const long long tiles = which ? (m + kJointRows - 1) / kJointRows : m * ((n_real + kJointRows - 1) / kJointRows);
+      lead->last_like = "joint_real_chi2";
+      rc = launch_on_stream(lead, vk_joint_real_chi2_kernel, (int)tiles, lds, jr);
+    }
+    const hipError_t er = hipEventRecord(h->ev_done, lead->stream);
+    if (rc) return rc;
+    if (er != hipSuccess) return fail(lead, VK_E_HIP, "hipEventRecord failed: %s", hipGetErrorString(er));
+    const size_t nb = (size_t)m * per_point * sizeof(double);
+    if (lnl) VK_HIP(lead, hipMemcpyAsync(lnl + off * per_point, d_lnl, nb, hipMemcpyDeviceToHost, lead->stream));
+    if (chi2) VK_HIP(lead, hipMemcpyAsync(chi2 + off * per_point, d_chi, nb, hipMemcpyDeviceToHost, lead->stream));
+    rc = vk_sync(lead);
     if (rc) return rc;
   }
   return VK_OK;

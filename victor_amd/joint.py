@@ -9,6 +9,10 @@ With ``covariance=`` the blocks are fitted under ONE covariance matrix across th
 blocks' data vectors in block order - as the reference's ``CCFFit`` would fit that vector: the quantiles of a density-split
 analysis share their galaxies and voids, so their data vectors are correlated.  The blocks' theory vectors come from their
 own theory launches; the joint chi-square is one kernel (``vk_joint_cov_eval_device_async``, ``vk_kernel_joint.h``).
+
+``JointFit.realisations()`` validates the joint fit on mocks: joint realisation m is realisation m of every block's own stacked
+file (``redshift_space_ccf.simulation_number``, reference ``ccf_fit.py:59-61,93-100``), and every parameter point is evaluated
+against all of them in one call (:class:`JointRealisations`).
 """
 
 import os
@@ -19,6 +23,7 @@ import numpy as np
 import ctypes as C
 
 from . import _native as N
+from .realisations import Realisations, check_which
 from .utils import InputError
 
 
@@ -299,3 +304,89 @@ class JointFit:
     @property
     def n_data(self):
         return sum(len(f.s) * len(f.poles_s) for f in self.fits)
+
+    def realisations(self, simulation_numbers=None):
+        """Every simulation realisation of the blocks' data files (or the listed ``simulation_numbers``) against this joint fit:
+        :class:`JointRealisations`.  Every block's fit must have been built with an integer ``simulation_number``."""
+        return JointRealisations(self, simulation_numbers)
+
+
+class JointRealisations:
+    """Realisations ``numbers`` of every block of ``joint`` (``JointFit.realisations``): joint realisation i is realisation
+    ``numbers[i]`` of each block, read from that block's own file and keys.  ``blocks[q]`` is block q's
+    :class:`victor_amd.realisations.Realisations` (its reader, checks and tables).
+
+    Value contract: entry ``[p, i]`` equals ``JointFit([CCFFit(model_q, data_q with simulation_number=numbers[i]) for q],
+    covariance=joint.covariance, likelihood=joint.likelihood).log_likelihood_batch(point p)`` to rounding, ``(-inf, inf)``
+    exactly where that call returns it.  Under a joint covariance the theory vectors are computed once per point and every
+    (point, realisation) pair is one row of the joint chi-square kernel (``vk_joint_cov_eval_realisations``); block-diagonal,
+    the blocks' own ``Realisations`` results are summed on the host in block order."""
+
+    def __init__(self, joint, simulation_numbers=None):
+        blocks = [Realisations(f, simulation_numbers) for f in joint.fits]
+        for q, r in enumerate(blocks[1:], 1):
+            if len(r) != len(blocks[0]):
+                raise InputError(f"JointFit.realisations: block 0 holds {len(blocks[0])} realisations and block {q} holds "
+                                 f"{len(r)}; pass simulation_numbers to pick the same ones from every block")
+        self.joint = joint
+        self.blocks = blocks
+        self.numbers = blocks[0].numbers
+
+    def __len__(self):
+        return len(self.numbers)
+
+    def _eval(self, params, kwargs, which=None):
+        joint = self.joint
+        if joint.covariance is None:
+            return self._block_diagonal(params, kwargs, which)
+        fit = joint.fits[0]
+        rows = fit._fit_rows(params, fit._merged({k: v for k, v in kwargs.items() if k != "likelihood"}))
+        rows, which = check_which(rows, which, len(self))
+        rows = N.f64(rows).reshape(-1, N.VK_NPAR)
+        engines, opts = joint._plan_cov(kwargs)
+        n = len(rows)
+        shape = (n,) if which is not None else (n, len(self))
+        lnl, chi2 = np.empty(shape), np.empty(shape)
+        if n == 0:
+            return lnl, chi2
+        for r, eng in zip(self.blocks, engines):
+            r._upload(eng)
+        lead = engines[0]
+        handle = joint._joint_handle(lead)
+        ctxs = (C.c_void_p * len(engines))(*[e._ctx for e in engines])
+        w = None
+        if which is not None:
+            which = np.ascontiguousarray(which, dtype=np.int32)
+            w = which.ctypes.data_as(C.POINTER(C.c_int32))
+        lead._check(lead._lib.vk_joint_cov_eval_realisations(handle, ctxs, len(engines), C.byref(opts), N.as_dp(rows), n, w,
+                                                             N.as_dp(lnl), N.as_dp(chi2)))
+        return lnl, chi2
+
+    def _block_diagonal(self, params, kwargs, which):
+        """Each block's realisations under its own covariance, summed in block order; a failed block fails the entry (as
+        ``JointFit._sequential``)."""
+        lnl = chi2 = None
+        for r in self.blocks:
+            a, b = r._eval(params, kwargs, which)
+            lnl = a if lnl is None else lnl + a
+            chi2 = b if chi2 is None else chi2 + b
+        bad = ~np.isfinite(lnl)
+        lnl[bad], chi2[bad] = -np.inf, np.inf
+        return lnl, chi2
+
+    def log_likelihood(self, params, **kwargs):
+        """(lnL, chi2) of the points against every joint realisation: each ``(n_real,)`` for a dict of scalars, ``(n_points,
+        n_real)`` for a batch (as ``Realisations.log_likelihood``)."""
+        lnl, chi2 = self._eval(params, kwargs)
+        if isinstance(params, dict) and all(np.ndim(v) == 0 for v in params.values()):
+            return lnl[0], chi2[0]
+        return lnl, chi2
+
+    def chi_squared(self, params, **kwargs):
+        """The chi-square half of :meth:`log_likelihood` (data vectors interpolated in beta)."""
+        return self.log_likelihood(params, **dict(kwargs, beta_interpolation="datavector"))[1]
+
+    def log_likelihood_pairs(self, params, which, **kwargs):
+        """(lnL, chi2), each ``(n_points,)``: point p against joint realisation ``numbers[which[p]]`` only.  The same bits as
+        the matching entries of :meth:`log_likelihood`."""
+        return self._eval(params, kwargs, which)

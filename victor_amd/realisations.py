@@ -21,6 +21,21 @@ from .engine import data_table
 from .utils import InputError
 
 
+def check_which(rows, which, n_real):
+    """(rows, which) of a pairs-mode call: one realisation index in 0 .. n_real - 1 per row (a single row is repeated for
+    every index); ``which=None`` passes through."""
+    if which is None:
+        return rows, None
+    which = np.atleast_1d(np.asarray(which))
+    if len(rows) == 1 and len(which) > 1:
+        rows = np.repeat(rows, len(which), axis=0)
+    if which.ndim != 1 or len(which) != len(rows) or not np.issubdtype(which.dtype, np.integer):
+        raise InputError(f"which must hold one realisation index per point ({len(rows)})")
+    if np.any((which < 0) | (which >= n_real)):
+        raise InputError(f"realisation index out of range 0..{n_real - 1}")
+    return rows, which
+
+
 class Realisations:
     """Realisations ``numbers`` of ``fit``'s data file (``CCFFit.realisations``).  ``blocks[i]`` is realisation ``numbers[i]``
     in the layout of ``vk_tables.data``; it is uploaded once per engine the object evaluates on."""
@@ -69,23 +84,19 @@ class Realisations:
         fit._check_supported(model)
         fit_options = fit._merged_fit(kwargs)
         eng = fit._get_engine(fit._engine_key(model), model["simpson_even"])
+        self._upload(eng)
+        return model, fit_options, eng, eng.make_opts(model, fit_options)
+
+    def _upload(self, eng):
+        """Make this object's realisations the ones set on ``eng`` (uploaded only when another object's, or none, are there)."""
         owner = getattr(eng, "_real_owner", None)
-        if owner is None or owner() is not self:        # another object's realisations (or none) are on this engine
+        if owner is None or owner() is not self:
             eng.set_realisations(self.blocks)
             eng._real_owner = weakref.ref(self)
-        return model, fit_options, eng, eng.make_opts(model, fit_options)
 
     def _eval(self, params, kwargs, which=None):
         model, fit_options, eng, opts = self._plan(kwargs)
-        rows = self.fit._fit_rows(params, model)
-        if which is not None:
-            which = np.atleast_1d(np.asarray(which))
-            if len(rows) == 1 and len(which) > 1:
-                rows = np.repeat(rows, len(which), axis=0)
-            if which.ndim != 1 or len(which) != len(rows) or not np.issubdtype(which.dtype, np.integer):
-                raise InputError(f"which must hold one realisation index per point ({len(rows)})")
-            if np.any((which < 0) | (which >= len(self))):
-                raise InputError(f"realisation index out of range 0..{len(self) - 1}")
+        rows, which = check_which(self.fit._fit_rows(params, model), which, len(self))
         if fit_options["beta_interpolation"] == "likelihood" and not self.fit.fixed_data:
             return self._likelihood_interp(eng, opts, rows, which)
         return eng.eval_realisations(opts, rows, len(self), which)
