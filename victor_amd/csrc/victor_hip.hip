@@ -286,168 +286,100 @@ const char* xi_instance() {
   return s.c_str();
 }
 
-template <int NLR, int NL, int GRID, int MODE, int SVA = 0>
-int launch_cells(vk_ctx* ctx, const TheoryArgs& a, int grid, size_t lds) {
-  ctx->last_theory = owned_instance<0, NLR, NL, GRID, MODE, SVA>();
-  return launch_on_stream(ctx, vk_theory_cells_kernel<NLR, NL, GRID, MODE, SVA>, grid, lds, a);
+// The runtime value v as the compile-time constant std::integral_constant<int, v> of f's argument, for v among V...: with_const
+// tells whether v was one of them, dispatch fails with `msg` (formatted with v) when it was not.  Only the V... given at a call
+// site are instantiated, so the branches below instantiate exactly the kernels of vk_instances.h.
+template <int V>
+constexpr std::integral_constant<int, V> ic{};
+
+template <int... V, class F>
+bool with_const(int v, F&& f) {
+  return ((v == V && (f(ic<V>), true)) || ...);
 }
 
-template <int NLR, int NL, int GRID, int MODE, int SVA = 0>
-int launch_fast(vk_ctx* ctx, const TheoryArgs& a, int grid, size_t lds) {
-  ctx->last_theory = owned_instance<1, NLR, NL, GRID, MODE, SVA>();
-  return launch_on_stream(ctx, vk_theory_fast_kernel<NLR, NL, GRID, MODE, SVA>, grid, lds, a);
+template <int... V, class F>
+int dispatch(vk_ctx* ctx, int v, const char* msg, F&& f) {
+  int rc = VK_OK;
+  if (with_const<V...>(v, [&](auto c) { rc = f(c); })) return rc;
+  return fail(ctx, VK_E_ARG, msg, v);
 }
 
-template <int RSD, int NLR, int NL>
-int launch_generic_one(vk_ctx* ctx, const TheoryArgs& a, int grid, size_t lds) {
-  ctx->last_theory = generic_instance<RSD, NLR, NL>();
-  return launch_on_stream(ctx, vk_theory_kernel<RSD, NLR, NL>, grid, lds, a);
+constexpr const char* kBadNl = "n_ell must be 1..3";
+constexpr const char* kBadNlr = "bad number of real-space multipoles %d";
+constexpr const char* kBadRsd = "unknown rsd_model %d";
+
+// The point-major (FAST) and cells kernels on the context's own tables: the instantiation for the call, in this order of
+// precedence - kaiser / euclid_special (cells only, either grid); anisotropic sigma_v(r, mu), whose bicubic patches ride in LDS
+// on the lattice form only (SVA = 1, GRID = 0: the streaming model, or the dispersion model on the cells kernel); then the mode
+// (dispersion, dispersion from data, from data, streaming) at the context's grid (GRID 1: union grid with its lookup table).
+template <int FAST>
+int launch_owned(vk_ctx* ctx, const TheoryArgs& a, int nlr, int grid, size_t lds) {
+  return dispatch<1, 2, 3>(ctx, nlr, kBadNlr, [&](auto NLR) {
+    return dispatch<1, 2, 3>(ctx, a.n_ell, kBadNl, [&](auto NL) {
+      auto go = [&](auto GRID, auto MODE, auto SVA) {
+        ctx->last_theory = owned_instance<FAST, NLR, NL, GRID, MODE, SVA>();
+        if constexpr (FAST) return launch_on_stream(ctx, vk_theory_fast_kernel<NLR, NL, GRID, MODE, SVA>, grid, lds, a);
+        else return launch_on_stream(ctx, vk_theory_cells_kernel<NLR, NL, GRID, MODE, SVA>, grid, lds, a);
+      };
+      auto at_grid = [&](auto GRID) {
+        if (a.rsd == VK_RSD_DISPERSION)
+          return a.from_data ? go(GRID, ic<kModeDispersionFromData>, ic<0>) : go(GRID, ic<kModeDispersion>, ic<0>);
+        return a.from_data ? go(GRID, ic<kModeFromData>, ic<0>) : go(GRID, ic<kModeStreaming>, ic<0>);
+      };
+      if constexpr (!FAST) {
+        if (a.rsd == VK_RSD_KAISER || a.rsd == VK_RSD_EUCLID)
+          return a.uni_lut_n > 0 ? go(ic<1>, ic<kModeKaiser>, ic<0>) : go(ic<0>, ic<kModeKaiser>, ic<0>);
+        if (a.sv_n_mu > 0 && a.rsd == VK_RSD_DISPERSION) return go(ic<0>, ic<kModeDispersion>, ic<1>);
+      }
+      if (a.sv_n_mu > 0) return go(ic<0>, ic<kModeStreaming>, ic<1>);
+      return a.uni_lut_n > 0 ? at_grid(ic<1>) : at_grid(ic<0>);
+    });
+  });
 }
 
-template <int RSD, int NLR>
-int launch_xi_one(vk_ctx* ctx, const TheoryArgs& a, int grid, size_t lds) {
-  ctx->last_theory = xi_instance<RSD, NLR>();
-  ctx->last_like = nullptr;                    // K1x stores xi(s, mu): no chi-square pairs with it
-  return launch_on_stream(ctx, vk_xi_smu_kernel<RSD, NLR>, grid, lds, a);
-}
-
-template <int RSD, int NLR>
-int launch_generic_nl(vk_ctx* ctx, const TheoryArgs& a, int grid, size_t lds) {
-  switch (a.n_ell) {
-    case 1: return launch_generic_one<RSD, NLR, 1>(ctx, a, grid, lds);
-    case 2: return launch_generic_one<RSD, NLR, 2>(ctx, a, grid, lds);
-    case 3: return launch_generic_one<RSD, NLR, 3>(ctx, a, grid, lds);
-  }
-  return fail(ctx, VK_E_ARG, "n_ell must be 1..3");
-}
-
-template <int RSD>
+// the generic kernel <RSD, NLR, NL>
 int launch_generic(vk_ctx* ctx, const TheoryArgs& a, int nlr, int grid, size_t lds) {
-  switch (nlr) {
-    case 1: return launch_generic_nl<RSD, 1>(ctx, a, grid, lds);
-    case 2: return launch_generic_nl<RSD, 2>(ctx, a, grid, lds);
-    case 3: return launch_generic_nl<RSD, 3>(ctx, a, grid, lds);
-  }
-  return fail(ctx, VK_E_ARG, "bad number of real-space multipoles %d", nlr);
+  return dispatch<VK_RSD_STREAMING, VK_RSD_DISPERSION, VK_RSD_KAISER, VK_RSD_EUCLID>(ctx, a.rsd, kBadRsd, [&](auto RSD) {
+    return dispatch<1, 2, 3>(ctx, nlr, kBadNlr, [&](auto NLR) {
+      return dispatch<1, 2, 3>(ctx, a.n_ell, kBadNl, [&](auto NL) {
+        ctx->last_theory = generic_instance<RSD, NLR, NL>();
+        return launch_on_stream(ctx, vk_theory_kernel<RSD, NLR, NL>, grid, lds, a);
+      });
+    });
+  });
 }
 
-template <int NLR, int GRID, int MODE>
-int launch_fast_ngf(vk_ctx* ctx, const TheoryArgs& a, int grid, size_t lds) {
-  switch (a.n_ell) {
-    case 1: return launch_fast<NLR, 1, GRID, MODE>(ctx, a, grid, lds);
-    case 2: return launch_fast<NLR, 2, GRID, MODE>(ctx, a, grid, lds);
-    case 3: return launch_fast<NLR, 3, GRID, MODE>(ctx, a, grid, lds);
-  }
-  return fail(ctx, VK_E_ARG, "n_ell must be 1..3");
-}
-
-// anisotropic sigma_v(r, mu) template on the fast kernels (SVA instantiations): streaming model, lattice form
-template <int NLR>
-int launch_fast_sva(vk_ctx* ctx, const TheoryArgs& a, int grid, size_t lds) {
-  switch (a.n_ell) {
-    case 1: return launch_fast<NLR, 1, 0, kModeStreaming, 1>(ctx, a, grid, lds);
-    case 2: return launch_fast<NLR, 2, 0, kModeStreaming, 1>(ctx, a, grid, lds);
-    case 3: return launch_fast<NLR, 3, 0, kModeStreaming, 1>(ctx, a, grid, lds);
-  }
-  return fail(ctx, VK_E_ARG, "n_ell must be 1..3");
-}
-
-// ... and the dispersion model with it (cells kernel only)
-template <int NLR>
-int launch_cells_sva_disp(vk_ctx* ctx, const TheoryArgs& a, int grid, size_t lds) {
-  switch (a.n_ell) {
-    case 1: return launch_cells<NLR, 1, 0, kModeDispersion, 1>(ctx, a, grid, lds);
-    case 2: return launch_cells<NLR, 2, 0, kModeDispersion, 1>(ctx, a, grid, lds);
-    case 3: return launch_cells<NLR, 3, 0, kModeDispersion, 1>(ctx, a, grid, lds);
-  }
-  return fail(ctx, VK_E_ARG, "n_ell must be 1..3");
-}
-
-template <int NLR>
-int launch_cells_sva(vk_ctx* ctx, const TheoryArgs& a, int grid, size_t lds) {
-  if (a.rsd == VK_RSD_DISPERSION) return launch_cells_sva_disp<NLR>(ctx, a, grid, lds);
-  switch (a.n_ell) {
-    case 1: return launch_cells<NLR, 1, 0, kModeStreaming, 1>(ctx, a, grid, lds);
-    case 2: return launch_cells<NLR, 2, 0, kModeStreaming, 1>(ctx, a, grid, lds);
-    case 3: return launch_cells<NLR, 3, 0, kModeStreaming, 1>(ctx, a, grid, lds);
-  }
-  return fail(ctx, VK_E_ARG, "n_ell must be 1..3");
-}
-
-template <int NLR, int GRID>
-int launch_fast_ng(vk_ctx* ctx, const TheoryArgs& a, int grid, size_t lds) {
-  if (a.sv_n_mu > 0) return launch_fast_sva<NLR>(ctx, a, grid, lds);
-  if (a.rsd == VK_RSD_DISPERSION)
-    return a.from_data ? launch_fast_ngf<NLR, GRID, kModeDispersionFromData>(ctx, a, grid, lds)
-                       : launch_fast_ngf<NLR, GRID, kModeDispersion>(ctx, a, grid, lds);
-  return a.from_data ? launch_fast_ngf<NLR, GRID, kModeFromData>(ctx, a, grid, lds)
-                     : launch_fast_ngf<NLR, GRID, kModeStreaming>(ctx, a, grid, lds);
-}
-
-template <int NLR>
-int launch_fast_nl(vk_ctx* ctx, const TheoryArgs& a, int grid, size_t lds) {
-  return a.uni_lut_n > 0 ? launch_fast_ng<NLR, 1>(ctx, a, grid, lds) : launch_fast_ng<NLR, 0>(ctx, a, grid, lds);
+// K1x <RSD, NLR>
+int launch_xi_smu(vk_ctx* ctx, const TheoryArgs& a, int nlr, int grid, size_t lds) {
+  return dispatch<VK_RSD_STREAMING, VK_RSD_DISPERSION, VK_RSD_KAISER, VK_RSD_EUCLID>(ctx, a.rsd, kBadRsd, [&](auto RSD) {
+    return dispatch<1, 2, 3>(ctx, nlr, kBadNlr, [&](auto NLR) {
+      ctx->last_theory = xi_instance<RSD, NLR>();
+      ctx->last_like = nullptr;                    // K1x stores xi(s, mu): no chi-square pairs with it
+      return launch_on_stream(ctx, vk_xi_smu_kernel<RSD, NLR>, grid, lds, a);
+    });
+  });
 }
 
 #ifdef VK_DEV_LANES
 template <int NLR, int NL, int GRID>
-int launch_lanes(vk_ctx* ctx, const TheoryArgs& a, int grid, size_t lds) {
-  static const std::string name = "lanes<" + std::to_string(NLR) + "," + std::to_string(NL) + "," + std::to_string(GRID) + ">";
-  ctx->last_theory = name.c_str();
-  return launch_on_stream(ctx, vk_theory_lanes_kernel<NLR, NL, GRID>, grid, lds, a);
+const char* lanes_instance() {
+  static const std::string s = "lanes<" + std::to_string(NLR) + "," + std::to_string(NL) + "," + std::to_string(GRID) + ">";
+  return s.c_str();
 }
 
-template <int NLR, int GRID>
-int launch_lanes_ng(vk_ctx* ctx, const TheoryArgs& a, int grid, size_t lds) {
-  switch (a.n_ell) {
-    case 1: return launch_lanes<NLR, 1, GRID>(ctx, a, grid, lds);
-    case 2: return launch_lanes<NLR, 2, GRID>(ctx, a, grid, lds);
-    case 3: return launch_lanes<NLR, 3, GRID>(ctx, a, grid, lds);
-  }
-  return fail(ctx, VK_E_ARG, "n_ell must be 1..3");
-}
-
-template <int NLR>
-int launch_lanes_nl(vk_ctx* ctx, const TheoryArgs& a, int grid, size_t lds) {
-  return a.uni_lut_n > 0 ? launch_lanes_ng<NLR, 1>(ctx, a, grid, lds) : launch_lanes_ng<NLR, 0>(ctx, a, grid, lds);
+// the lanes-over-the-batch kernel <NLR, NL, GRID> (development build)
+int launch_lanes(vk_ctx* ctx, const TheoryArgs& a, int nlr, int grid, size_t lds) {
+  return dispatch<1, 2, 3>(ctx, nlr, kBadNlr, [&](auto NLR) {
+    return dispatch<1, 2, 3>(ctx, a.n_ell, kBadNl, [&](auto NL) {
+      auto go = [&](auto GRID) {
+        ctx->last_theory = lanes_instance<NLR, NL, GRID>();
+        return launch_on_stream(ctx, vk_theory_lanes_kernel<NLR, NL, GRID>, grid, lds, a);
+      };
+      return a.uni_lut_n > 0 ? go(ic<1>) : go(ic<0>);
+    });
+  });
 }
 #endif
-
-template <int NLR, int GRID, int MODE>
-int launch_cells_ngf(vk_ctx* ctx, const TheoryArgs& a, int grid, size_t lds) {
-  switch (a.n_ell) {
-    case 1: return launch_cells<NLR, 1, GRID, MODE>(ctx, a, grid, lds);
-    case 2: return launch_cells<NLR, 2, GRID, MODE>(ctx, a, grid, lds);
-    case 3: return launch_cells<NLR, 3, GRID, MODE>(ctx, a, grid, lds);
-  }
-  return fail(ctx, VK_E_ARG, "n_ell must be 1..3");
-}
-
-template <int NLR, int GRID>
-int launch_cells_ng(vk_ctx* ctx, const TheoryArgs& a, int grid, size_t lds) {
-  if (a.rsd == VK_RSD_KAISER || a.rsd == VK_RSD_EUCLID) return launch_cells_ngf<NLR, GRID, kModeKaiser>(ctx, a, grid, lds);
-  if (a.sv_n_mu > 0) return launch_cells_sva<NLR>(ctx, a, grid, lds);
-  if (a.rsd == VK_RSD_DISPERSION)
-    return a.from_data ? launch_cells_ngf<NLR, GRID, kModeDispersionFromData>(ctx, a, grid, lds)
-                       : launch_cells_ngf<NLR, GRID, kModeDispersion>(ctx, a, grid, lds);
-  return a.from_data ? launch_cells_ngf<NLR, GRID, kModeFromData>(ctx, a, grid, lds)
-                     : launch_cells_ngf<NLR, GRID, kModeStreaming>(ctx, a, grid, lds);
-}
-
-template <int NLR>
-int launch_cells_nl(vk_ctx* ctx, const TheoryArgs& a, int grid, size_t lds) {
-  return a.uni_lut_n > 0 ? launch_cells_ng<NLR, 1>(ctx, a, grid, lds) : launch_cells_ng<NLR, 0>(ctx, a, grid, lds);
-}
-
-template <int RSD>
-int launch_xi_smu(vk_ctx* ctx, const TheoryArgs& a, int nlr, int grid, size_t lds) {
-  switch (nlr) {
-    case 1: return launch_xi_one<RSD, 1>(ctx, a, grid, lds);
-    case 2: return launch_xi_one<RSD, 2>(ctx, a, grid, lds);
-    case 3: return launch_xi_one<RSD, 3>(ctx, a, grid, lds);
-  }
-  return fail(ctx, VK_E_ARG, "bad number of real-space multipoles %d", nlr);
-}
 
 // K1x generic: one wave per (point, mu, s) cell, library math, any knot layout (vk_kernel_generic.h) - what serves
 // vk_xi_smu_batch where the cells kernel cannot go
@@ -463,12 +395,7 @@ int launch_xi_generic(vk_ctx* ctx, TheoryArgs a, int nlr) {
   a.parts = 1;
   a.exp_tab = ctx->d_exp_tab;
   ctx->last_kernel = "vk_xi_smu_kernel";
-  switch (a.rsd) {
-    case VK_RSD_STREAMING: return launch_xi_smu<VK_RSD_STREAMING>(ctx, a, nlr, grid, lds);
-    case VK_RSD_DISPERSION: return launch_xi_smu<VK_RSD_DISPERSION>(ctx, a, nlr, grid, lds);
-    case VK_RSD_KAISER: return launch_xi_smu<VK_RSD_KAISER>(ctx, a, nlr, grid, lds);
-    default: return launch_xi_smu<VK_RSD_EUCLID>(ctx, a, nlr, grid, lds);
-  }
+  return launch_xi_smu(ctx, a, nlr, grid, lds);
 }
 
 // fills the grid-independent part of TheoryArgs
@@ -546,21 +473,12 @@ const double* get_image(vk_ctx* ctx, const TheoryArgs& a, int kind, int nlr, int
   const size_t lds = (size_t)image_end * sizeof(double);
   double* img = nullptr;
   if (lds > 160 * 1024 || hipMalloc((void**)&img, lds) != hipSuccess) return nullptr;
-  bool ok = true;
-  switch (nlr) {
-    case 1:
-      if (lds > 64 * 1024) ok = hipFuncSetAttribute(reinterpret_cast<const void*>(vk_image_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
-      if (ok) hipLaunchKernelGGL(vk_image_kernel<1>, dim3(1), dim3(kBlock), lds, ctx->stream, a, kind, with_da | (sva ? 4 : 0), img, image_end);
-      break;
-    case 2:
-      if (lds > 64 * 1024) ok = hipFuncSetAttribute(reinterpret_cast<const void*>(vk_image_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
-      if (ok) hipLaunchKernelGGL(vk_image_kernel<2>, dim3(1), dim3(kBlock), lds, ctx->stream, a, kind, with_da | (sva ? 4 : 0), img, image_end);
-      break;
-    default:
-      if (lds > 64 * 1024) ok = hipFuncSetAttribute(reinterpret_cast<const void*>(vk_image_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
-      if (ok) hipLaunchKernelGGL(vk_image_kernel<3>, dim3(1), dim3(kBlock), lds, ctx->stream, a, kind, with_da | (sva ? 4 : 0), img, image_end);
-      break;
-  }
+  bool ok = false;
+  with_const<1, 2, 3>(nlr, [&](auto NLR) {
+    const void* kern = reinterpret_cast<const void*>(vk_image_kernel<NLR>);
+    ok = lds <= 64 * 1024 || hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
+    if (ok) hipLaunchKernelGGL(vk_image_kernel<NLR>, dim3(1), dim3(kBlock), lds, ctx->stream, a, kind, with_da | (sva ? 4 : 0), img, image_end);
+  });
   if (!ok || hipGetLastError() != hipSuccess) {
     (void)hipFree(img);
     return nullptr;
@@ -669,12 +587,7 @@ int launch_theory(vk_ctx* ctx, TheoryArgs a, int nlr, const LikeArgs* like, bool
         a.cells_per_item = cpi;
         a.ns_magic = div_magic(a.n_s);
         a.image = nullptr;                 // the caller's own grid: staged inside the kernel
-        const int grid_c = (int)(a.n * R);
-        switch (nlr) {
-          case 1: return launch_cells_nl<1>(ctx, a, grid_c, lds_c);
-          case 2: return launch_cells_nl<2>(ctx, a, grid_c, lds_c);
-          case 3: return launch_cells_nl<3>(ctx, a, grid_c, lds_c);
-        }
+        return launch_owned<0>(ctx, a, nlr, (int)(a.n * R), lds_c);
       }
     }
     return launch_xi_generic(ctx, a, nlr);
@@ -699,11 +612,7 @@ int launch_theory(vk_ctx* ctx, TheoryArgs a, int nlr, const LikeArgs* like, bool
       // tail of 0.6 ms items: 131072 points ran at 1.61 M evals/s under a 64-per-CU cap against 2.35 M without)
       const long long capl = (long long)INT32_MAX;
       const int grid_l = (int)(blocks < capl ? blocks : capl);
-      switch (nlr) {
-        case 1: return launch_lanes_nl<1>(ctx, a, grid_l, lds_l);
-        case 2: return launch_lanes_nl<2>(ctx, a, grid_l, lds_l);
-        case 3: return launch_lanes_nl<3>(ctx, a, grid_l, lds_l);
-      }
+      return launch_lanes(ctx, a, nlr, grid_l, lds_l);
     }
   }
 #endif
@@ -756,11 +665,7 @@ int launch_theory(vk_ctx* ctx, TheoryArgs a, int nlr, const LikeArgs* like, bool
     const long long items_c = a.n * R;
     const int grid_c = (int)items_c;                                       // one item per workgroup, always (vk_kernel_cells.h)
     if (fused) *fused = a.fuse != 0;
-    switch (nlr) {
-      case 1: return launch_cells_nl<1>(ctx, a, grid_c, lds_c);
-      case 2: return launch_cells_nl<2>(ctx, a, grid_c, lds_c);
-      case 3: return launch_cells_nl<3>(ctx, a, grid_c, lds_c);
-    }
+    return launch_owned<0>(ctx, a, nlr, grid_c, lds_c);
   }
   if (kais || sva_disp) fast = false;   // grids the cells kernel cannot take (n_mu < 64): the generic kernel
   ctx->last_kernel = fast ? "vk_theory_fast_kernel" : "vk_theory_kernel";
@@ -811,12 +716,7 @@ int launch_theory(vk_ctx* ctx, TheoryArgs a, int nlr, const LikeArgs* like, bool
       }
     }
     if (fused) *fused = a.fuse != 0;
-    switch (nlr) {
-      case 1: return launch_fast_nl<1>(ctx, a, grid, lds);
-      case 2: return launch_fast_nl<2>(ctx, a, grid, lds);
-      case 3: return launch_fast_nl<3>(ctx, a, grid, lds);
-    }
-    return fail(ctx, VK_E_ARG, "bad number of real-space multipoles %d", nlr);
+    return launch_owned<1>(ctx, a, nlr, grid, lds);
   }
   a.parts = 1;
   const size_t lds = (size_t)make_plan(a.n_mu, a.n_x, a.n_ell, a.sv.n_int, a.vr.n_int, a.xi.n_int, nlr, a.n_beta_r).total *
@@ -824,14 +724,7 @@ int launch_theory(vk_ctx* ctx, TheoryArgs a, int nlr, const LikeArgs* like, bool
   if (lds > 160 * 1024) return fail(ctx, VK_E_ARG, "tables need %zu bytes of LDS (> 160 KiB)", lds);
   const long long groups = (a.n_s + a.sbins_per_item - 1) / a.sbins_per_item;
   const long long items = a.n * groups;
-  const int grid = (int)(items < cap ? items : cap);
-  switch (a.rsd) {
-    case VK_RSD_STREAMING: return launch_generic<VK_RSD_STREAMING>(ctx, a, nlr, grid, lds);
-    case VK_RSD_DISPERSION: return launch_generic<VK_RSD_DISPERSION>(ctx, a, nlr, grid, lds);
-    case VK_RSD_KAISER: return launch_generic<VK_RSD_KAISER>(ctx, a, nlr, grid, lds);
-    case VK_RSD_EUCLID: return launch_generic<VK_RSD_EUCLID>(ctx, a, nlr, grid, lds);
-  }
-  return fail(ctx, VK_E_ARG, "unknown rsd_model %d", a.rsd);
+  return launch_generic(ctx, a, nlr, (int)(items < cap ? items : cap), lds);
 }
 
 void fill_like_args(const vk_ctx* ctx, const vk_eval_opts* o, const double* d_params, const double* d_theory, long long n,
@@ -1518,6 +1411,196 @@ int vk_eval_batch_device_async(vk_ctx* ctx, const vk_eval_opts* opts, const doub
   return VK_OK;
 }
 
+}  // extern "C"
+
+// ---- joint fits: the block-diagonal and the joint-covariance entry points (include/victor_hip.h, vk_kernel_joint*.h) ----------
+struct vk_joint_cov {
+  vk_ctx* lead = nullptr;
+  int device = -1;
+  std::vector<int> block_n;
+  int NT = 0, NTp = 0, n_beta = 0;
+  double* d_mem = nullptr;        // beta [n_beta] | precision slices [max(n_beta, 1)][NTp][NTp] (zero-padded) | logdet | eig
+  hipEvent_t ev_done = nullptr;   // recorded behind every evaluation's chi-square kernel (the last reader of d_mem)
+  const double *d_beta = nullptr, *d_prec = nullptr, *d_logdet = nullptr, *d_eig = nullptr;
+};
+
+// The contexts of a joint fit: each present, on the lead's device, with a data vector; under a covariance handle (h), the handle's
+// own lead and block sizes; against realisations (need_real), no batch pending from vk_eval_batch_begin and as many realisations
+// set on every context as on the lead.  Checked before anything is enqueued.
+static int check_blocks(vk_ctx* lead, const vk_joint_cov* h, vk_ctx* const* ctxs, int n_ctx, bool need_real) {
+  if (h && h->lead != lead) return fail(lead, VK_E_ARG, "joint covariance: ctxs[0] is not the context the handle was created with");
+  if (h && n_ctx != (int)h->block_n.size())
+    return fail(lead, VK_E_ARG, "joint covariance: %d contexts for %d blocks", n_ctx, (int)h->block_n.size());
+  for (int q = 0; q < n_ctx; ++q) {
+    const vk_ctx* c = ctxs[q];
+    if (!c) return fail(lead, VK_E_ARG, "context %d is NULL", q);
+    if (c->device != lead->device) return fail(lead, VK_E_ARG, "joint fit: every context must live on the same device");
+    if (!c->d_data) return fail(lead, VK_E_ARG, "joint fit: context %d was created without a data vector", q);
+    if (h && c->N != h->block_n[q])
+      return fail(lead, VK_E_ARG, "joint covariance: block %d has %d entries, its context %d", q, h->block_n[q], c->N);
+    if (!need_real) continue;
+    if (c->begun_n != 0)
+      return fail(lead, VK_E_ARG, "a batch begun with vk_eval_batch_begin is awaiting vk_eval_batch_finish on context %d", q);
+    if (c->n_real <= 0 || !c->d_real)
+      return fail(lead, VK_E_ARG, "no realisations are set on context %d (vk_set_realisations)", q);
+    if (c->n_real != lead->n_real)
+      return fail(lead, VK_E_ARG, "context %d holds %d realisations, context 0 holds %d", q, c->n_real, lead->n_real);
+  }
+  return VK_OK;
+}
+
+// pairs mode: every point's realisation index in 0 .. n_real - 1
+static int check_which(vk_ctx* ctx, const int32_t* which, int64_t n, int n_real) {
+  if (which)
+    for (int64_t i = 0; i < n; ++i)
+      if (which[i] < 0 || which[i] >= n_real)
+        return fail(ctx, VK_E_ARG, "realisation index %d of point %lld is outside 0..%d", which[i], (long long)i, n_real - 1);
+  return VK_OK;
+}
+
+// The joint chi-square's arguments: the lead's likelihood stage with the handle's covariance tables, p = NT and no data of its
+// own, and block q's theory vectors at th + n * off_q against its data vector (real: its realisations).
+static void joint_args(const vk_joint_cov* h, vk_ctx* const* ctxs, const vk_eval_opts* opts, const double* d_par, long long n,
+                       double* d_lnl, double* d_chi2, const double* th, bool real, JointArgs* ja) {
+  LikeArgs& l = ja->like;
+  fill_like_args(ctxs[0], opts, d_par, nullptr, n, d_lnl, d_chi2, &l);
+  l.N = h->NT;                        // the likelihood forms' p is the joint vector's length
+  l.n_beta_d = 0;
+  l.beta_d = nullptr;
+  l.data = nullptr;
+  l.n_beta_c = h->n_beta;
+  l.beta_c = h->n_beta > 0 ? h->d_beta : nullptr;
+  l.prec = h->d_prec;
+  l.grids_in_lds = 0;
+  l.tri = nullptr;
+  l.logdet = h->n_beta > 0 ? h->d_logdet : nullptr;
+  l.eig = h->n_beta > 0 ? h->d_eig : nullptr;
+  ja->NTp = h->NTp;
+  ja->n_blocks = (int)h->block_n.size();
+  int off = 0;
+  for (int q = 0; q < ja->n_blocks; ++q) {
+    const vk_ctx* c = ctxs[q];
+    JointBlock& b = ja->blk[q];
+    b.theory = th + (size_t)n * off;
+    b.data = real ? c->d_real : c->d_data;
+    b.beta_d = c->n_beta_d > 0 ? c->d_beta_d : nullptr;
+    b.n_beta_d = c->n_beta_d;
+    b.N = c->N;
+    b.off = off;
+    off += c->N;
+  }
+}
+
+// The blocks' launches, each on its own stream, all behind what the lead stream has enqueued so far (e.g. the parameter upload):
+// block q's lnl, chi2 and theory workspace are out(q).  The first failing block's error reaches the lead.
+struct BlockOut {
+  double *lnl, *chi2, *theory;
+};
+
+template <class Out>
+static int fan_out(vk_ctx* const* ctxs, int n_ctx, const vk_eval_opts* opts, const double* d_par, long long n, Out out) {
+  vk_ctx* lead = ctxs[0];
+  for (int q = 0; q < n_ctx; ++q)
+    if (!ctxs[q]->ev_joint) VK_HIP(lead, hipEventCreateWithFlags(&ctxs[q]->ev_joint, hipEventDisableTiming));
+  VK_HIP(lead, hipEventRecord(lead->ev_joint, lead->stream));
+  for (int q = 0; q < n_ctx; ++q) {
+    vk_ctx* c = ctxs[q];
+    if (q > 0) VK_HIP(lead, hipStreamWaitEvent(c->stream, lead->ev_joint, 0));
+    const BlockOut o = out(q);
+    const int rc = vk_eval_batch_device_async(c, opts, d_par, n, o.lnl, o.chi2, o.theory);
+    if (rc) {
+      if (c != lead) lead->err = c->err;
+      return rc;
+    }
+  }
+  return VK_OK;
+}
+
+// the lead stream waits for every block's stream
+static hipError_t join_block_streams(vk_ctx* const* ctxs, int n_ctx) {
+  hipError_t e = hipSuccess;
+  for (int q = 1; q < n_ctx && e == hipSuccess; ++q) {
+    e = hipEventRecord(ctxs[q]->ev_joint, ctxs[q]->stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(ctxs[0]->stream, ctxs[q]->ev_joint, 0);
+  }
+  return e;
+}
+
+// The points sorted by covariance slice (vk_kernel_joint.h), on stream s: ranks within chunks, the chunks' offsets, the scatter
+// into ja->perm.  sort: lo | rank | perm [stride] ints | histograms [chunks + 1][n_beta].
+static hipError_t enqueue_slice_sort(hipStream_t s, JointArgs* ja, int* sort, long long stride) {
+  const long long n = ja->like.n;
+  const int n_beta = ja->like.n_beta_c;
+  int *lo = sort, *rank = lo + stride, *perm = rank + stride, *hist = perm + stride;
+  const int chunks = (int)((n + kJointSortChunk - 1) / kJointSortChunk);
+  hipLaunchKernelGGL(vk_joint_rank_kernel, dim3(chunks), dim3(kBlock), 0, s, *ja, lo, rank, hist);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(vk_joint_offsets_kernel, dim3(1), dim3(kBlock), 0, s, hist, chunks, n_beta);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(vk_joint_scatter_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const int*)lo, (const int*)rank,
+                       (const int*)hist, n_beta, n, perm);
+    e = hipGetLastError();
+  }
+  ja->perm = perm;
+  return e;
+}
+
+// The end of a joint-covariance evaluation (e: how the lead stream's own launches were enqueued): the lead stream joins the
+// blocks' and runs the joint chi-square kernel.  From the first launch that reads the handle's tables on, every exit records
+// h->ev_done behind what was enqueued (vk_joint_cov_destroy waits for it).
+template <typename Kern, typename Args>
+static int joint_chi2(vk_joint_cov* h, vk_ctx* const* ctxs, int n_ctx, hipError_t e, const char* name, Kern kern, long long tiles,
+                      size_t lds, const Args& args) {
+  vk_ctx* lead = ctxs[0];
+  if (e == hipSuccess) e = join_block_streams(ctxs, n_ctx);
+  int rc = VK_OK;
+  if (e != hipSuccess) {
+    rc = fail(lead, VK_E_HIP, "joint covariance: enqueue failed: %s", hipGetErrorString(e));
+  } else {
+    lead->last_like = name;
+    rc = launch_on_stream(lead, kern, (int)tiles, lds, args);
+  }
+  const hipError_t er = hipEventRecord(h->ev_done, lead->stream);
+  if (rc) return rc;
+  if (er != hipSuccess) return fail(lead, VK_E_HIP, "hipEventRecord failed: %s", hipGetErrorString(er));
+  return VK_OK;
+}
+
+// The realisation entry points' points go through in chunks whose two output arrays stay below 256 MB (65536 points x 1000
+// realisations would be 0.5 GB each).  Per chunk of m points: the parameters (and in pairs mode the realisation indices) go up
+// into the device buffers, enqueue(m) launches on ctx's stream, lnl and chi2 come back from d_lnl / d_chi, and the host waits.
+struct RealChunks {
+  long long per_point, m_max;         // outputs per point (n_real; pairs mode 1), points per chunk
+  double *d_par = nullptr, *d_lnl = nullptr, *d_chi = nullptr;
+  int32_t* d_which = nullptr;
+
+  RealChunks(const int32_t* which, int n_real, int64_t n)
+      : per_point(which ? 1 : n_real),
+        m_max(std::min<long long>(std::max<long long>(1, std::min<long long>(65536, (256LL << 20) / (8 * per_point))), n)) {}
+
+  template <class Enqueue>
+  int run(vk_ctx* ctx, const double* params, const int32_t* which, int64_t n, double* lnl, double* chi2, Enqueue enqueue) const {
+    for (long long off = 0; off < n; off += m_max) {
+      const long long m = std::min<long long>(m_max, n - off);
+      VK_HIP(ctx, hipMemcpyAsync(d_par, params + off * VK_NPAR, (size_t)m * VK_NPAR * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+      if (which) VK_HIP(ctx, hipMemcpyAsync(d_which, which + off, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+      int rc = enqueue(m);
+      if (rc) return rc;
+      const size_t nb = (size_t)m * per_point * sizeof(double);
+      if (lnl) VK_HIP(ctx, hipMemcpyAsync(lnl + off * per_point, d_lnl, nb, hipMemcpyDeviceToHost, ctx->stream));
+      if (chi2) VK_HIP(ctx, hipMemcpyAsync(chi2 + off * per_point, d_chi, nb, hipMemcpyDeviceToHost, ctx->stream));
+      rc = vk_sync(ctx);
+      if (rc) return rc;
+    }
+    return VK_OK;
+  }
+};
+
+extern "C" {
+
 size_t vk_joint_workspace_doubles(vk_ctx* const* ctxs, int32_t n_ctx, int64_t n) {
   if (!ctxs || n_ctx < 1 || n < 0) return 0;
   int n_max = 0;
@@ -1530,37 +1613,21 @@ int vk_joint_eval_device_async(vk_ctx* const* ctxs, int32_t n_ctx, const vk_eval
                                double* d_lnl, double* d_chi2, double* d_ws) {
   if (!ctxs || n_ctx < 1 || !ctxs[0]) return VK_E_ARG;
   vk_ctx* lead = ctxs[0];
-  for (int q = 0; q < n_ctx; ++q) {
-    if (!ctxs[q]) return fail(lead, VK_E_ARG, "context %d is NULL", q);
-    if (ctxs[q]->device != lead->device) return fail(lead, VK_E_ARG, "joint fit: every context must live on the same device");
-    if (!ctxs[q]->d_data) return fail(lead, VK_E_ARG, "joint fit: context %d was created without a data vector", q);
-  }
+  int rc = check_blocks(lead, nullptr, ctxs, n_ctx, false);
+  if (rc) return rc;
   if (n < 0 || (n > 0 && (!d_params || !d_ws || !(d_lnl || d_chi2)))) return fail(lead, VK_E_ARG, "bad device buffers");
   if (n == 0) return VK_OK;
   VK_HIP(lead, hipSetDevice(lead->device));
   int n_max = 0;
   for (int q = 0; q < n_ctx; ++q) n_max = std::max(n_max, ctxs[q]->N);
   const long long block_stride = (long long)n * (n_max + 2);    // per block: lnl[n] | chi2[n] | theory workspace [n][N]
-  for (int q = 0; q < n_ctx; ++q)
-    if (!ctxs[q]->ev_joint) VK_HIP(lead, hipEventCreateWithFlags(&ctxs[q]->ev_joint, hipEventDisableTiming));
-  // the blocks run on their own streams, all behind what the lead stream has enqueued so far (e.g. the parameter upload)
-  VK_HIP(lead, hipEventRecord(lead->ev_joint, lead->stream));
-  for (int q = 0; q < n_ctx; ++q) {
-    vk_ctx* c = ctxs[q];
-    if (q > 0) VK_HIP(lead, hipStreamWaitEvent(c->stream, lead->ev_joint, 0));
+  rc = fan_out(ctxs, n_ctx, opts, d_params, n, [&](int q) {
     double* blk = d_ws + q * block_stride;
-    c->depth_mult = n_ctx;       // the launches overlap on the GPU: the lanes kernel's depth rule sees all of them
-    const int rc = vk_eval_batch_device_async(c, opts, d_params, n, blk, blk + n, blk + 2 * n);
-    c->depth_mult = 1;
-    if (rc) {
-      if (c != lead) lead->err = c->err;
-      return rc;
-    }
-  }
-  for (int q = 1; q < n_ctx; ++q) {
-    VK_HIP(lead, hipEventRecord(ctxs[q]->ev_joint, ctxs[q]->stream));
-    VK_HIP(lead, hipStreamWaitEvent(lead->stream, ctxs[q]->ev_joint, 0));
-  }
+    return BlockOut{blk, blk + n, blk + 2 * n};
+  });
+  if (rc) return rc;
+  const hipError_t e = join_block_streams(ctxs, n_ctx);
+  if (e != hipSuccess) return fail(lead, VK_E_HIP, "joint fit: enqueue failed: %s", hipGetErrorString(e));
   hipLaunchKernelGGL(vk_joint_sum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, lead->stream, d_ws, (long long)n, n_ctx,
                      block_stride, d_lnl, d_chi2);
   VK_HIP(lead, hipGetLastError());
@@ -1568,20 +1635,6 @@ int vk_joint_eval_device_async(vk_ctx* const* ctxs, int32_t n_ctx, const vk_eval
 }
 
 // ---- joint fit under one covariance across the data vectors (include/victor_hip.h, vk_kernel_joint.h) -----------------
-}  // extern "C"
-
-struct vk_joint_cov {
-  vk_ctx* lead = nullptr;
-  int device = -1;
-  std::vector<int> block_n;
-  int NT = 0, NTp = 0, n_beta = 0;
-  double* d_mem = nullptr;        // beta [n_beta] | precision slices [max(n_beta, 1)][NTp][NTp] (zero-padded) | logdet | eig
-  hipEvent_t ev_done = nullptr;   // recorded behind every evaluation's chi-square kernel (the last reader of d_mem)
-  const double *d_beta = nullptr, *d_prec = nullptr, *d_logdet = nullptr, *d_eig = nullptr;
-};
-
-extern "C" {
-
 int vk_joint_cov_create(vk_ctx* lead, const vk_joint_cov_tables* t, vk_joint_cov** out) {
   if (!lead) return VK_E_ARG;
   if (!t || !out) return fail(lead, VK_E_ARG, "joint covariance: tables or out is NULL");
@@ -1678,17 +1731,9 @@ int vk_joint_cov_eval_device_async(vk_joint_cov* h, vk_ctx* const* ctxs, int32_t
   if (!ctxs || n_ctx < 1 || !ctxs[0]) return VK_E_ARG;
   vk_ctx* lead = ctxs[0];
   if (!h) return fail(lead, VK_E_ARG, "joint covariance: handle is NULL");
-  if (h->lead != lead) return fail(lead, VK_E_ARG, "joint covariance: ctxs[0] is not the context the handle was created with");
-  if (n_ctx != (int)h->block_n.size())
-    return fail(lead, VK_E_ARG, "joint covariance: %d contexts for %d blocks", n_ctx, (int)h->block_n.size());
-  for (int q = 0; q < n_ctx; ++q) {
-    if (!ctxs[q]) return fail(lead, VK_E_ARG, "context %d is NULL", q);
-    if (ctxs[q]->device != h->device) return fail(lead, VK_E_ARG, "joint fit: every context must live on the same device");
-    if (!ctxs[q]->d_data) return fail(lead, VK_E_ARG, "joint fit: context %d was created without a data vector", q);
-    if (ctxs[q]->N != h->block_n[q])
-      return fail(lead, VK_E_ARG, "joint covariance: block %d has %d entries, its context %d", q, h->block_n[q], ctxs[q]->N);
-  }
-  int rc = check_opts(lead, opts);
+  int rc = check_blocks(lead, h, ctxs, n_ctx, false);
+  if (rc) return rc;
+  rc = check_opts(lead, opts);
   if (rc) return rc;
   if (n < 0 || n > (1LL << 31) - kJointSortChunk || (n > 0 && (!d_params || !d_ws || !(d_lnl || d_chi2))))
     return fail(lead, VK_E_ARG, "bad device buffers");
@@ -1696,86 +1741,15 @@ int vk_joint_cov_eval_device_async(vk_joint_cov* h, vk_ctx* const* ctxs, int32_t
   VK_HIP(lead, hipSetDevice(lead->device));
   size_t o_sort;
   (void)joint_cov_ws(h, n, &o_sort);
-  for (int q = 0; q < n_ctx; ++q)
-    if (!ctxs[q]->ev_joint) VK_HIP(lead, hipEventCreateWithFlags(&ctxs[q]->ev_joint, hipEventDisableTiming));
-
   JointArgs ja{};
-  fill_like_args(lead, opts, d_params, nullptr, n, d_lnl, d_chi2, &ja.like);
-  ja.like.N = h->NT;                    // the likelihood forms' p is the joint vector's length
-  ja.like.n_beta_d = 0;
-  ja.like.beta_d = nullptr;
-  ja.like.data = nullptr;
-  ja.like.n_beta_c = h->n_beta;
-  ja.like.beta_c = h->n_beta > 0 ? h->d_beta : nullptr;
-  ja.like.prec = h->d_prec;
-  ja.like.grids_in_lds = 0;
-  ja.like.tri = nullptr;
-  ja.like.logdet = h->n_beta > 0 ? h->d_logdet : nullptr;
-  ja.like.eig = h->n_beta > 0 ? h->d_eig : nullptr;
-  ja.NTp = h->NTp;
-  ja.n_blocks = n_ctx;
-
-  // the blocks' theory launches, theory only, each on its own stream behind what the lead stream has enqueued so far
-  VK_HIP(lead, hipEventRecord(lead->ev_joint, lead->stream));
-  int off = 0;
-  for (int q = 0; q < n_ctx; ++q) {
-    vk_ctx* c = ctxs[q];
-    if (q > 0) VK_HIP(lead, hipStreamWaitEvent(c->stream, lead->ev_joint, 0));
-    double* th = d_ws + (size_t)n * off;
-    c->depth_mult = n_ctx;
-    rc = vk_eval_batch_device_async(c, opts, d_params, n, nullptr, nullptr, th);
-    c->depth_mult = 1;
-    if (rc) {
-      if (c != lead) lead->err = c->err;
-      return rc;
-    }
-    JointBlock& b = ja.blk[q];
-    b.theory = th;
-    b.data = c->d_data;
-    b.beta_d = c->n_beta_d > 0 ? c->d_beta_d : nullptr;
-    b.n_beta_d = c->n_beta_d;
-    b.N = c->N;
-    b.off = off;
-    off += c->N;
-  }
-  // meanwhile on the lead stream: the points sorted by covariance slice (the data tables and params are ready behind ev_joint)
-  // from the first launch that reads the handle's tables on, every exit records ev_done behind what was enqueued
-  // (vk_joint_cov_destroy waits for it)
-  hipError_t e = hipSuccess;
-  if (h->n_beta > 0) {
-    int* lo = reinterpret_cast<int*>(d_ws + o_sort);
-    int* rank = lo + n;
-    int* perm = rank + n;
-    int* hist = perm + n;
-    const int chunks = (int)((n + kJointSortChunk - 1) / kJointSortChunk);
-    hipLaunchKernelGGL(vk_joint_rank_kernel, dim3(chunks), dim3(kBlock), 0, lead->stream, ja, lo, rank, hist);
-    if ((e = hipGetLastError()) == hipSuccess) {
-      hipLaunchKernelGGL(vk_joint_offsets_kernel, dim3(1), dim3(kBlock), 0, lead->stream, hist, chunks, h->n_beta);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(vk_joint_scatter_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, lead->stream,
-                         (const int*)lo, (const int*)rank, (const int*)hist, h->n_beta, (long long)n, perm);
-      e = hipGetLastError();
-    }
-    ja.perm = perm;
-  }
-  for (int q = 1; q < n_ctx && e == hipSuccess; ++q) {
-    e = hipEventRecord(ctxs[q]->ev_joint, ctxs[q]->stream);
-    if (e == hipSuccess) e = hipStreamWaitEvent(lead->stream, ctxs[q]->ev_joint, 0);
-  }
-  rc = VK_OK;
-  if (e != hipSuccess) {
-    rc = fail(lead, VK_E_HIP, "joint covariance: enqueue failed: %s", hipGetErrorString(e));
-  } else {
-    const size_t lds = joint_lds_doubles(h->NT, n_ctx, h->n_beta) * sizeof(double);
-    lead->last_like = "joint_chi2";
-    rc = launch_on_stream(lead, vk_joint_chi2_kernel, (int)((n + kJointRows - 1) / kJointRows), lds, ja);
-  }
-  const hipError_t er = hipEventRecord(h->ev_done, lead->stream);
+  joint_args(h, ctxs, opts, d_params, n, d_lnl, d_chi2, d_ws, false, &ja);
+  // the blocks' theory launches, theory only
+  rc = fan_out(ctxs, n_ctx, opts, d_params, n, [&](int q) { return BlockOut{nullptr, nullptr, d_ws + (size_t)n * ja.blk[q].off}; });
   if (rc) return rc;
-  if (er != hipSuccess) return fail(lead, VK_E_HIP, "hipEventRecord failed: %s", hipGetErrorString(er));
-  return VK_OK;
+  // meanwhile on the lead stream: the points sorted by covariance slice (the data tables and params are ready behind ev_joint)
+  const hipError_t e = h->n_beta > 0 ? enqueue_slice_sort(lead->stream, &ja, reinterpret_cast<int*>(d_ws + o_sort), n) : hipSuccess;
+  return joint_chi2(h, ctxs, n_ctx, e, "joint_chi2", vk_joint_chi2_kernel, (n + kJointRows - 1) / kJointRows,
+                    joint_lds_doubles(h->NT, n_ctx, h->n_beta) * sizeof(double), ja);
 }
 
 // The launch-bound small-batch case of vk_eval_batch: one hipGraph launch per call (see vk_ctx::graphs).
@@ -2169,46 +2143,39 @@ int vk_eval_realisations(vk_ctx* ctx, const vk_eval_opts* opts, const double* pa
   if (n < 0 || (n > 0 && !params)) return fail(ctx, VK_E_ARG, "params is NULL");
   if (ctx->begun_n != 0) return fail(ctx, VK_E_ARG, "a batch begun with vk_eval_batch_begin is awaiting vk_eval_batch_finish on this context");
   if (ctx->n_real <= 0 || !ctx->d_real) return fail(ctx, VK_E_ARG, "no realisations are set on this context (vk_set_realisations)");
-  if (which)
-    for (int64_t i = 0; i < n; ++i)
-      if (which[i] < 0 || which[i] >= ctx->n_real)
-        return fail(ctx, VK_E_ARG, "realisation index %d of point %lld is outside 0..%d", which[i], (long long)i, ctx->n_real - 1);
+  rc = check_which(ctx, which, n, ctx->n_real);
+  if (rc) return rc;
   if (n == 0) return VK_OK;
   const int N = ctx->N;
   const size_t lds = real_lds_doubles(N) * sizeof(double);
   if (lds > 160 * 1024) return fail(ctx, VK_E_ARG, "data vector of %d bins needs %zu bytes of LDS for the realisation kernel (> 160 KiB)", N, lds);
   VK_HIP(ctx, hipSetDevice(ctx->device));
-  // Points go through in chunks whose two output arrays stay below 256 MB (65536 points x 1000 realisations would be 0.5 GB
-  // each); a chunk is one theory launch into the workspace and one realisation launch behind it.
-  const long long per_point = which ? 1 : ctx->n_real;
-  const long long chunk = std::max<long long>(1, std::min<long long>(65536, (256LL << 20) / (8 * per_point)));
-  const long long m_max = std::min<long long>(chunk, n);
-  const size_t doubles = (size_t)m_max * (VK_NPAR + N + 2 * per_point) + (size_t)m_max / 2 + 2;
+  // a chunk is one theory launch into the workspace and one realisation launch behind it
+  RealChunks ch(which, ctx->n_real, n);
+  const long long m_max = ch.m_max;
+  const size_t doubles = (size_t)m_max * (VK_NPAR + N + 2 * ch.per_point) + (size_t)m_max / 2 + 2;
   rc = ensure_scratch(ctx, doubles * sizeof(double));
   if (rc) return rc;
-  double* d_par = ctx->d_scratch;
-  double* d_th = d_par + (size_t)m_max * VK_NPAR;
-  double* d_lnl = d_th + (size_t)m_max * N;
-  double* d_chi = d_lnl + (size_t)m_max * per_point;
-  int32_t* d_which = reinterpret_cast<int32_t*>(d_chi + (size_t)m_max * per_point);
+  ch.d_par = ctx->d_scratch;
+  double* d_th = ch.d_par + (size_t)m_max * VK_NPAR;
+  ch.d_lnl = d_th + (size_t)m_max * N;
+  ch.d_chi = ch.d_lnl + (size_t)m_max * ch.per_point;
+  ch.d_which = reinterpret_cast<int32_t*>(ch.d_chi + (size_t)m_max * ch.per_point);
   const bool timed = ctx->timing;
-  for (long long off = 0; off < n; off += m_max) {
-    const long long m = std::min<long long>(m_max, n - off);
-    VK_HIP(ctx, hipMemcpyAsync(d_par, params + off * VK_NPAR, (size_t)m * VK_NPAR * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    if (which) VK_HIP(ctx, hipMemcpyAsync(d_which, which + off, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  return ch.run(ctx, params, which, n, lnl, chi2, [&](long long m) {
     if (timed) {
       harvest_timing(ctx);
       VK_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
     }
-    rc = vk_eval_batch_device_async(ctx, opts, d_par, m, nullptr, nullptr, d_th);     // theory vectors only, into the workspace
+    int rc = vk_eval_batch_device_async(ctx, opts, ch.d_par, m, nullptr, nullptr, d_th);     // theory vectors only, into the workspace
     if (rc) return rc;
     if (timed) VK_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
     RealArgs ra{};
-    fill_like_args(ctx, opts, d_par, d_th, m, lnl ? d_lnl : nullptr, chi2 ? d_chi : nullptr, &ra.like);
+    fill_like_args(ctx, opts, ch.d_par, d_th, m, lnl ? ch.d_lnl : nullptr, chi2 ? ch.d_chi : nullptr, &ra.like);
     ra.real = ctx->d_real;
     ra.block = ctx->real_block;
     ra.n_real = ctx->n_real;
-    ra.which = which ? d_which : nullptr;
+    ra.which = which ? ch.d_which : nullptr;
     ctx->last_like = ctx->knobs.real_valu ? "like_real<false>" : "like_real<true>";
     rc = ctx->knobs.real_valu ? launch_on_stream(ctx, vk_like_real_kernel<false>, (int)m, lds, ra)
                               : launch_on_stream(ctx, vk_like_real_kernel<true>, (int)m, lds, ra);
@@ -2217,13 +2184,8 @@ int vk_eval_realisations(vk_ctx* ctx, const vk_eval_opts* opts, const double* pa
       VK_HIP(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
       ctx->pending = true;
     }
-    const size_t nb = (size_t)m * per_point * sizeof(double);
-    if (lnl) VK_HIP(ctx, hipMemcpyAsync(lnl + off * per_point, d_lnl, nb, hipMemcpyDeviceToHost, ctx->stream));
-    if (chi2) VK_HIP(ctx, hipMemcpyAsync(chi2 + off * per_point, d_chi, nb, hipMemcpyDeviceToHost, ctx->stream));
-    rc = vk_sync(ctx);
-    if (rc) return rc;
-  }
-  return VK_OK;
+    return VK_OK;
+  });
 }
 
 // ---- joint fit under one covariance against many realisations of every block (include/victor_hip.h, vk_kernel_joint_real.h) -
@@ -2232,114 +2194,48 @@ int vk_joint_cov_eval_realisations(vk_joint_cov* h, vk_ctx* const* ctxs, int32_t
   if (!ctxs || n_ctx < 1 || !ctxs[0]) return VK_E_ARG;
   vk_ctx* lead = ctxs[0];
   if (!h) return fail(lead, VK_E_ARG, "joint covariance: handle is NULL");
-  if (h->lead != lead) return fail(lead, VK_E_ARG, "joint covariance: ctxs[0] is not the context the handle was created with");
-  if (n_ctx != (int)h->block_n.size())
-    return fail(lead, VK_E_ARG, "joint covariance: %d contexts for %d blocks", n_ctx, (int)h->block_n.size());
-  for (int q = 0; q < n_ctx; ++q) {
-    vk_ctx* c = ctxs[q];
-    if (!c) return fail(lead, VK_E_ARG, "context %d is NULL", q);
-    if (c->device != h->device) return fail(lead, VK_E_ARG, "joint fit: every context must live on the same device");
-    if (!c->d_data) return fail(lead, VK_E_ARG, "joint fit: context %d was created without a data vector", q);
-    if (c->N != h->block_n[q])
-      return fail(lead, VK_E_ARG, "joint covariance: block %d has %d entries, its context %d", q, h->block_n[q], c->N);
-    if (c->begun_n != 0)
-      return fail(lead, VK_E_ARG, "a batch begun with vk_eval_batch_begin is awaiting vk_eval_batch_finish on context %d", q);
-    if (c->n_real <= 0 || !c->d_real)
-      return fail(lead, VK_E_ARG, "no realisations are set on context %d (vk_set_realisations)", q);
-    if (c->n_real != ctxs[0]->n_real)
-      return fail(lead, VK_E_ARG, "context %d holds %d realisations, context 0 holds %d", q, c->n_real, ctxs[0]->n_real);
-  }
+  int rc = check_blocks(lead, h, ctxs, n_ctx, true);
+  if (rc) return rc;
   const int n_real = lead->n_real;
-  int rc = check_opts(lead, opts);
+  rc = check_opts(lead, opts);
   if (rc) return rc;
   if (n < 0 || (n > 0 && !params)) return fail(lead, VK_E_ARG, "params is NULL");
   if (n > (1LL << 31) - kJointSortChunk) return fail(lead, VK_E_ARG, "%lld points: at most 2^31 - %d", (long long)n, kJointSortChunk);
-  if (which)
-    for (int64_t i = 0; i < n; ++i)
-      if (which[i] < 0 || which[i] >= n_real)
-        return fail(lead, VK_E_ARG, "realisation index %d of point %lld is outside 0..%d", which[i], (long long)i, n_real - 1);
+  rc = check_which(lead, which, n, n_real);
+  if (rc) return rc;
   if (n == 0) return VK_OK;
   const size_t lds = joint_real_lds_doubles(h->NT, n_ctx, h->n_beta) * sizeof(double);
   if (lds > 160 * 1024)
     return fail(lead, VK_E_ARG, "joint covariance: %d entries and %d slices need more than 160 KiB of LDS", h->NT, h->n_beta);
   VK_HIP(lead, hipSetDevice(lead->device));
-  // Points go through in chunks whose two output arrays stay below 256 MB, as in vk_eval_realisations; a chunk is every block's
-  // theory launch (theory only, each on its own stream) and the joint chi-square launch behind them.
-  const long long per_point = which ? 1 : n_real;
-  const long long chunk = std::max<long long>(1, std::min<long long>(65536, (256LL << 20) / (8 * per_point)));
-  const long long m_max = std::min<long long>(chunk, n);
+  // a chunk is every block's theory launch (theory only, each on its own stream) and the joint chi-square launch behind them
+  RealChunks ch(which, n_real, n);
+  const long long m_max = ch.m_max;
   const long long chunks_max = (m_max + kJointSortChunk - 1) / kJointSortChunk;
   // scratch: params | theory [m][NT] (block q at offset m * off_q) | lnl | chi2 | -1/2 log det [m] | ints: which, singular,
   // and the slice sort's lo, rank, perm [m] and histograms [chunks + 1][n_beta]
   const size_t ints = (size_t)m_max * 5 + (size_t)(chunks_max + 1) * h->n_beta;
-  const size_t doubles = (size_t)m_max * (VK_NPAR + h->NT + 2 * per_point + 1) + (ints + 1) / 2 + 1;
+  const size_t doubles = (size_t)m_max * (VK_NPAR + h->NT + 2 * ch.per_point + 1) + (ints + 1) / 2 + 1;
   rc = ensure_scratch(lead, doubles * sizeof(double));
   if (rc) return rc;
-  double* d_par = lead->d_scratch;
-  double* d_th = d_par + (size_t)m_max * VK_NPAR;
-  double* d_lnl = d_th + (size_t)m_max * h->NT;
-  double* d_chi = d_lnl + (size_t)m_max * per_point;
-  double* d_fac = d_chi + (size_t)m_max * per_point;
-  int32_t* d_which = reinterpret_cast<int32_t*>(d_fac + m_max);
-  int* d_bad = d_which + m_max;
-  int* d_lo = d_bad + m_max;
-  int* d_rank = d_lo + m_max;
-  int* d_perm = d_rank + m_max;
-  int* d_hist = d_perm + m_max;
-  for (int q = 0; q < n_ctx; ++q)
-    if (!ctxs[q]->ev_joint) VK_HIP(lead, hipEventCreateWithFlags(&ctxs[q]->ev_joint, hipEventDisableTiming));
-
-  for (long long off = 0; off < n; off += m_max) {
-    const long long m = std::min<long long>(m_max, n - off);
-    VK_HIP(lead, hipMemcpyAsync(d_par, params + off * VK_NPAR, (size_t)m * VK_NPAR * sizeof(double), hipMemcpyHostToDevice,
-                                lead->stream));
-    if (which)
-      VK_HIP(lead, hipMemcpyAsync(d_which, which + off, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, lead->stream));
+  ch.d_par = lead->d_scratch;
+  double* d_th = ch.d_par + (size_t)m_max * VK_NPAR;
+  ch.d_lnl = d_th + (size_t)m_max * h->NT;
+  ch.d_chi = ch.d_lnl + (size_t)m_max * ch.per_point;
+  double* d_fac = ch.d_chi + (size_t)m_max * ch.per_point;
+  ch.d_which = reinterpret_cast<int32_t*>(d_fac + m_max);
+  int* d_bad = ch.d_which + m_max;
+  int* d_sort = d_bad + m_max;
+  return ch.run(lead, params, which, n, lnl, chi2, [&](long long m) {
     JointRealArgs jr{};
     JointArgs& ja = jr.joint;
-    fill_like_args(lead, opts, d_par, nullptr, m, lnl ? d_lnl : nullptr, chi2 ? d_chi : nullptr, &ja.like);
-    ja.like.N = h->NT;                  // the likelihood forms' p is the joint vector's length
-    ja.like.n_beta_d = 0;
-    ja.like.beta_d = nullptr;
-    ja.like.data = nullptr;
-    ja.like.n_beta_c = h->n_beta;
-    ja.like.beta_c = h->n_beta > 0 ? h->d_beta : nullptr;
-    ja.like.prec = h->d_prec;
-    ja.like.grids_in_lds = 0;
-    ja.like.tri = nullptr;
-    ja.like.logdet = h->n_beta > 0 ? h->d_logdet : nullptr;
-    ja.like.eig = h->n_beta > 0 ? h->d_eig : nullptr;
-    ja.NTp = h->NTp;
-    ja.n_blocks = n_ctx;
+    joint_args(h, ctxs, opts, ch.d_par, m, lnl ? ch.d_lnl : nullptr, chi2 ? ch.d_chi : nullptr, d_th, true, &ja);
+    for (int q = 0; q < n_ctx; ++q) jr.stride[q] = ctxs[q]->real_block;
     jr.n_real = n_real;
-    jr.which = which ? d_which : nullptr;
-
-    // the blocks' theory launches, theory only, each on its own stream behind the lead stream (the parameters are there)
-    VK_HIP(lead, hipEventRecord(lead->ev_joint, lead->stream));
-    int at = 0;
-    for (int q = 0; q < n_ctx; ++q) {
-      vk_ctx* c = ctxs[q];
-      if (q > 0) VK_HIP(lead, hipStreamWaitEvent(c->stream, lead->ev_joint, 0));
-      double* th = d_th + (size_t)m * at;
-      c->depth_mult = n_ctx;
-      rc = vk_eval_batch_device_async(c, opts, d_par, m, nullptr, nullptr, th);
-      c->depth_mult = 1;
-      if (rc) {
-        if (c != lead) lead->err = c->err;
-        return rc;
-      }
-      JointBlock& b = ja.blk[q];
-      b.theory = th;
-      b.data = c->d_real;
-      b.beta_d = c->n_beta_d > 0 ? c->d_beta_d : nullptr;
-      b.n_beta_d = c->n_beta_d;
-      b.N = c->N;
-      b.off = at;
-      jr.stride[q] = c->real_block;
-      at += c->N;
-    }
-    // meanwhile on the lead stream: the log-det factor of every point and, in pairs mode, the points sorted by covariance slice;
-    // from the first launch that reads the handle's tables on, every exit records ev_done behind what was enqueued
+    jr.which = which ? ch.d_which : nullptr;
+    int rc = fan_out(ctxs, n_ctx, opts, ch.d_par, m, [&](int q) { return BlockOut{nullptr, nullptr, d_th + (size_t)m * ja.blk[q].off}; });
+    if (rc) return rc;
+    // meanwhile on the lead stream: the log-det factor of every point and, in pairs mode, the points sorted by covariance slice
     hipError_t e = hipSuccess;
     if (h->n_beta > 0) {
       hipLaunchKernelGGL(vk_joint_real_factor_kernel, dim3((unsigned)((m + kWaves - 1) / kWaves)), dim3(kBlock), 0, lead->stream,
@@ -2347,43 +2243,12 @@ int vk_joint_cov_eval_realisations(vk_joint_cov* h, vk_ctx* const* ctxs, int32_t
       e = hipGetLastError();
       jr.fac = d_fac;
       jr.bad = d_bad;
-      if (which && e == hipSuccess) {
-        const int chunks = (int)((m + kJointSortChunk - 1) / kJointSortChunk);
-        hipLaunchKernelGGL(vk_joint_rank_kernel, dim3(chunks), dim3(kBlock), 0, lead->stream, ja, d_lo, d_rank, d_hist);
-        if ((e = hipGetLastError()) == hipSuccess) {
-          hipLaunchKernelGGL(vk_joint_offsets_kernel, dim3(1), dim3(kBlock), 0, lead->stream, d_hist, chunks, h->n_beta);
-          e = hipGetLastError();
-        }
-        if (e == hipSuccess) {
-          hipLaunchKernelGGL(vk_joint_scatter_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, lead->stream,
-                             (const int*)d_lo, (const int*)d_rank, (const int*)d_hist, h->n_beta, (long long)m, d_perm);
-          e = hipGetLastError();
-        }
-        ja.perm = d_perm;
-      }
+      if (which && e == hipSuccess) e = enqueue_slice_sort(lead->stream, &ja, d_sort, m_max);
     }
-    for (int q = 1; q < n_ctx && e == hipSuccess; ++q) {
-      e = hipEventRecord(ctxs[q]->ev_joint, ctxs[q]->stream);
-      if (e == hipSuccess) e = hipStreamWaitEvent(lead->stream, ctxs[q]->ev_joint, 0);
-    }
-    if (e != hipSuccess) {
-      rc = fail(lead, VK_E_HIP, "joint covariance: enqueue failed: %s", hipGetErrorString(e));
-    } else {
-      // cross mode: ceil(n_real / 16) tiles per point, one point per tile; pairs mode: 16 points per tile
-      const long long tiles = which ? (m + kJointRows - 1) / kJointRows : m * ((n_real + kJointRows - 1) / kJointRows);
-      lead->last_like = "joint_real_chi2";
-      rc = launch_on_stream(lead, vk_joint_real_chi2_kernel, (int)tiles, lds, jr);
-    }
-    const hipError_t er = hipEventRecord(h->ev_done, lead->stream);
-    if (rc) return rc;
-    if (er != hipSuccess) return fail(lead, VK_E_HIP, "hipEventRecord failed: %s", hipGetErrorString(er));
-    const size_t nb = (size_t)m * per_point * sizeof(double);
-    if (lnl) VK_HIP(lead, hipMemcpyAsync(lnl + off * per_point, d_lnl, nb, hipMemcpyDeviceToHost, lead->stream));
-    if (chi2) VK_HIP(lead, hipMemcpyAsync(chi2 + off * per_point, d_chi, nb, hipMemcpyDeviceToHost, lead->stream));
-    rc = vk_sync(lead);
-    if (rc) return rc;
-  }
-  return VK_OK;
+    // cross mode: ceil(n_real / 16) tiles per point, one point per tile; pairs mode: 16 points per tile
+    const long long tiles = which ? (m + kJointRows - 1) / kJointRows : m * ((n_real + kJointRows - 1) / kJointRows);
+    return joint_chi2(h, ctxs, n_ctx, e, "joint_real_chi2", vk_joint_real_chi2_kernel, tiles, lds, jr);
+  });
 }
 
 }  // extern "C"

@@ -102,7 +102,6 @@ struct vk_ctx {
   int poll_refused_launches = 0;       // ... or every kPollRetryLaunches launches (a reservation may have died with its process)
   std::string bus;                     // PCI bus id of the device (the device-wide ledger of reserved waiters is kept per GPU)
   double wsum[3] = {0, 0, 0};
-  int depth_mult = 1;                // joint fits: launches of this many contexts share the GPU (vk_joint_eval_device_async)
   hipEvent_t ev_joint = nullptr;
   std::map<int, double*> images;     // LDS images per (kernel kind, real-space multipoles, dispersion tables), built on first use
   std::map<const void*, int> lds_opt_in;   // dynamic LDS above 64 KiB a kernel has been opted in for (launch_on_stream)
