@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput of the likelihood hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 One "step" = one pass of the whole path (theory kernel + likelihood kernel [+ RCCL all-gather of lnL when
 N > 1]) over one batch of synthetic parameter points per GPU.  Workload = BASELINE config 3, the grid the
@@ -14,9 +14,15 @@ For N > 1 the driver launches one process per GPU with torch.distributed.run; th
 RANK / WORLD_SIZE come from the environment, the rendezvous (RCCL unique id, barriers, max-over-ranks of the time) is a
 standard-library socket group (victor_amd/rendezvous.py), the data path is libvictor_hip.so + RCCL.  Started on its own,
 `python bench.py --gpus N` drives N contexts from ONE process (ncclCommInitAll, one grouped ncclAllGather per step).
-After the weak-scaling line's timed loop a multi-GPU run also times a fixed global batch (65536 points in total,
-`strong_scaling`) and every GPU's copy of the gathered lnL vector is checked against local recomputation of rows from every
-other shard.
+After the weak-scaling line's timed loop every GPU's copy of the gathered lnL vector is checked against local recomputation of
+rows from every other shard.
+
+A plain run does what the headline needs and no more: it sets up, warms up, times the K steps, writes its outputs when
+`--dump-outputs` is given and prints the line.  `--full` adds everything else the bench measures: on one GPU the CPU baseline
+with its comparison against the oracle, the counter passes (HBM traffic and sustained clock: child runs under rocprofv3), the
+secondary legs (BOSS CMASS, batch sweep, density-split joint fit, host API latencies, chains sharing one GPU, walker ensembles,
+model options); at N > 1 the fixed global batch (65536 points in total, `strong_scaling`) and BASELINE configs 4 and 5
+(`dsplit5`, `walker_ensembles`).  The `--no-*` switches leave out single parts of a `--full` run.
 
 `--dump-outputs DIR` writes what the last timed step computed, as a caller of the path receives it: `DIR/lnl.npy` and
 `DIR/chi2.npy`, float64, one entry per point of the global batch in Halton order (a seeded sample of the points when the two
@@ -118,6 +124,9 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=BATCH_PER_GPU, help="points per GPU per step")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline as well: CPU baseline and oracle comparison, counter passes, the "
+                         "secondary legs; at N > 1 strong scaling and the config 4 / 5 legs (a plain run times the headline alone)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-boss", action="store_true", help="skip the secondary BOSS CMASS measurement")
     ap.add_argument("--no-chains", action="store_true", help="skip the chains-sharing-one-GPU measurement (child processes)")
@@ -173,7 +182,7 @@ def main():
 
     # CPU baseline first: it spawns worker processes, which must happen before this process touches the GPU
     base = None
-    if rank == 0 and total == 1 and not args.no_cpu_baseline:
+    if rank == 0 and total == 1 and args.full and not args.no_cpu_baseline:
         cores = host_cores()
         ns = min(args.cpu_sample or max(16, 40 * cores), B)      # ~40 oracle evaluations per core (~50 ms each): ~30 core-seconds of CPU work
         sel = np.linspace(0, B - 1, ns).astype(int)
@@ -184,7 +193,7 @@ def main():
     # ... and the shader clock every measured kernel sustains, from a third child run (GRBM_GUI_ACTIVE): the clock behind
     # `frac_at_sustained_clock` is measured in THIS run on THIS box, or the field is null
     traffic_live = clocks = None
-    if rank == 0 and total == 1 and not args.no_live_traffic and not args.no_boss:
+    if rank == 0 and total == 1 and args.full and not args.no_live_traffic and not args.no_boss:
         import bench_pmc
         gdir = os.path.join(ROOT, "gpurun_out")
         gdir = gdir if os.path.isdir(gdir) else None
@@ -192,7 +201,7 @@ def main():
         clocks = bench_pmc.live_clocks(B, args.simpson_even, gdir)
     # the reference's own calling convention under load (P chains, one point per call): child processes again, so before the GPU
     chains = None
-    if rank == 0 and total == 1 and not args.no_boss and not args.no_chains:
+    if rank == 0 and total == 1 and args.full and not args.no_boss and not args.no_chains:
         try:
             chains = chains_sharing_one_gpu()
         except Exception as exc:       # noqa: BLE001 - a secondary leg must not take the headline measurement down with it
@@ -288,9 +297,9 @@ def main():
     k_local = np.array([p[0] for p in per_slot])
     kernel_ms_ranks = (dist.allgather_host(k_local, len(k_local)) if launched else k_local).tolist() if total > 1 or launched else None
 
-    # fixed global batch next to the weak-scaling line: BATCH_PER_GPU points in total, B / total per GPU
+    # fixed global batch next to the weak-scaling line (--full): BATCH_PER_GPU points in total, B / total per GPU
     strong = None
-    if total > 1:
+    if total > 1 and args.full:
         Bs = max(1, args.batch // total)
         for s in slots:
             mine_s = {k: v[s.g * Bs:(s.g + 1) * Bs] for k, v in hp_all.items()}
@@ -365,7 +374,7 @@ def main():
             out["theory_kernel_ms_per_rank"] = kernel_ms_ranks
         if strong is not None:
             out["strong_scaling"] = strong
-        if total == 1 and not args.no_boss:
+        if total == 1 and args.full and not args.no_boss:
             out["boss_cmass"] = boss_measurement(args, clocks=clocks)
             out["batch_sweep"] = batch_sweep()
             out["dsplit5"] = dsplit_measurement()
@@ -416,7 +425,7 @@ def main():
     # above is complete by now; these legs build communicators of their own, so they run under a watchdog: a leg that raises is
     # reported as {"error": ...}, a collective that hangs costs LEG_TIMEOUT seconds - never the headline's record.
     legs = {}
-    if total > 1 and not args.no_boss:
+    if total > 1 and args.full and not args.no_boss:
         gatherer.close()                      # one communicator at a time: every leg builds its own on its own contexts
         for s_ in slots:
             s_.free()

@@ -37,3 +37,11 @@ def test_bench_rejects_zero_steps():
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True,
                          timeout=120)
     assert res.returncode == 2 and "--steps" in res.stderr and res.stdout == ""
+
+
+def test_bench_takes_full_and_documents_it():
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "0"], capture_output=True,
+                         text=True, timeout=120)
+    assert res.returncode == 2 and "--steps must be at least 1" in res.stderr and res.stdout == ""
+    helped = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert helped.returncode == 0 and "--full" in helped.stdout

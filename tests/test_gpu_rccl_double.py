@@ -46,7 +46,7 @@ def test_bench_two_ranks_gather_through_the_communicator(tmp_path):
     from tests.test_gpu_workloads import _launch_ranks
     double = build_double(tmp_path)
     res = _launch_ranks([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "4096",
-                         "--no-cpu-baseline", "--no-boss"], 2, extra_env=_env(double, tmp_path))
+                         "--full", "--no-cpu-baseline", "--no-boss"], 2, extra_env=_env(double, tmp_path))
     for rc, out, err in res:
         assert rc == 0, err[-3000:]
     lines = [ln for ln in res[0][1].splitlines() if ln.startswith("{")]
@@ -99,7 +99,7 @@ def test_bench_two_ranks_sharded_joint_fit_and_walker_legs(tmp_path):
     from tests.test_gpu_workloads import _launch_ranks
     double = build_double(tmp_path)
     res = _launch_ranks([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "4096",
-                         "--no-cpu-baseline"], 2, extra_env=_env(double, tmp_path), timeout=600)
+                         "--full", "--no-cpu-baseline"], 2, extra_env=_env(double, tmp_path), timeout=600)
     for rc, out, err in res:
         assert rc == 0, err[-3000:]
     out = json.loads([ln for ln in res[0][1].splitlines() if ln.startswith("{")][0])

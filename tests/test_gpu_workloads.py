@@ -305,7 +305,7 @@ def test_bench_two_launched_ranks_on_one_gpu():
     the library diagnostics in the JSON line."""
     import json
     res = _launch_ranks([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "4096",
-                         "--no-cpu-baseline", "--no-boss"], 2)
+                         "--full", "--no-cpu-baseline", "--no-boss"], 2)
     for rc, out, err in res:
         assert rc == 0, err[-2000:]
     lines = [ln for ln in res[0][1].splitlines() if ln.startswith("{")]
@@ -334,7 +334,7 @@ def test_bench_under_the_drivers_launcher_command():
         port = so.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--batch", "4096", "--no-cpu-baseline", "--no-boss"]
+           "--batch", "4096", "--full", "--no-cpu-baseline", "--no-boss"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=360)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -366,7 +366,7 @@ def test_bench_one_process_two_contexts_on_one_gpu():
     one-GPU box ncclCommInitAll is refused for the shared device and the gather is the host concatenation."""
     import json
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                          "--batch", "4096", "--no-cpu-baseline", "--no-boss"], capture_output=True, text=True, timeout=240)
+                          "--batch", "4096", "--full", "--no-cpu-baseline", "--no-boss"], capture_output=True, text=True, timeout=240)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, res.stdout[-2000:]
@@ -381,7 +381,7 @@ def test_bench_one_process_two_contexts_with_the_config_4_and_5_legs():
     host, and every check of what was gathered must still hold."""
     import json
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                          "--batch", "4096", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600)
+                          "--batch", "4096", "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-3000:]
     out = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][0])
     _check_two_gpu_line(out)
@@ -389,6 +389,27 @@ def test_bench_one_process_two_contexts_with_the_config_4_and_5_legs():
     assert d5["global_batch"] == 16384 and d5["batch_per_gpu"] == 8192 and d5["gather_matches_local"] is True
     assert d5["kernel"] == "vk_theory_cells_kernel"
     assert w["walkers_total"] == 16 and w["gather_matches_local"] is True
+
+
+def test_plain_bench_run_times_the_headline_alone(tmp_path):
+    """``python bench.py`` without ``--full``: the headline line with its dumped outputs, and none of the measurements that
+    ``--full`` adds (CPU baseline, counter passes, secondary legs)."""
+    import json
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                          "--batch", "4096", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=240)
+    assert res.returncode == 0, res.stderr[-2000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, res.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["n_gpus"] == 1 and out["steps"] == 2 and out["warmup"] == 1 and out["config"]["batch_per_gpu"] == 4096
+    assert out["unit"] == "evals/s" and out["dtype"] == "f64" and out["higher_is_better"] is True
+    assert out["value"] > 0 and out["outputs_finite"] is True
+    assert out["roofline"]["traffic"] is None and out["roofline"]["clock_source"] is None
+    moved = ("cpu_baseline", "max_rel_dchi2_vs_oracle", "boss_cmass", "batch_sweep", "dsplit5", "host_api",
+             "chains_sharing_one_gpu", "walker_ensembles", "model_options", "strong_scaling")
+    assert not [k for k in moved if k in out], out.keys()
+    lnl, chi2 = np.load(tmp_path / "lnl.npy"), np.load(tmp_path / "chi2.npy")
+    assert lnl.shape == chi2.shape == (4096,) and np.all(np.isfinite(lnl)) and np.all(chi2 > 0)
 
 
 def test_integration_stub_runs_as_written():

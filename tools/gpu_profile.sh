@@ -6,10 +6,10 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd $R
-python bench.py > $OUT/bench_n1.json 2> $OUT/bench_n1.err
+python bench.py --full > $OUT/bench_n1.json 2> $OUT/bench_n1.err
 tail -c 3000 $OUT/bench_n1.json
 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 \
-    bench.py --gpus 1 --steps 5 --warmup 2 > $OUT/bench_torchrun1.json 2> $OUT/bench_torchrun1.err || { tail -20 $OUT/bench_torchrun1.err; exit 1; }
+    bench.py --gpus 1 --steps 5 --warmup 2 --full > $OUT/bench_torchrun1.json 2> $OUT/bench_torchrun1.err || { tail -20 $OUT/bench_torchrun1.err; exit 1; }
 tail -c 1500 $OUT/bench_torchrun1.json
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-boss > $OUT/trace.log 2>&1

@@ -14,7 +14,7 @@ PORT=$((29600 + RANDOM % 200))
 for RANK in $(seq 0 $((N - 1))); do
   VICTOR_HIP_DEV=1 VICTOR_HIP_RCCL_LIB=$OUT/librccl_double.so VICTOR_HIP_RCCL_SHARED_DEVICE_OK=1 RCCL_DOUBLE_DIR=$OUT \
   RANK=$RANK LOCAL_RANK=$RANK WORLD_SIZE=$N MASTER_ADDR=127.0.0.1 MASTER_PORT=$PORT \
-    timeout -k 5 300 python tools/with_watchdog.py 280 bench.py --gpus $N --steps 5 --warmup 2 --batch 16384 --no-cpu-baseline \
+    timeout -k 5 300 python tools/with_watchdog.py 280 bench.py --gpus $N --steps 5 --warmup 2 --batch 16384 --full --no-cpu-baseline \
     > $OUT/bench_two_ranks_double_rank$RANK.json 2> $OUT/bench_two_ranks_double_rank$RANK.err &
 done
 wait
