@@ -389,6 +389,43 @@ int vk_set_realisations(vk_ctx* ctx, const double* data, int32_t n_real);
 int vk_eval_realisations(vk_ctx* ctx, const vk_eval_opts* opts, const double* params, int64_t n, const int32_t* which,
                          double* lnl, double* chi2);
 
+/* ---- best-fit points: bounded Nelder-Mead on the device, one simplex per problem ----------------------------------------
+ * The reference has no optimiser: a user maximises CCFFit.log_likelihood (victor/ccf_fit.py:356-483) with a host optimiser,
+ * one call per point.  A PROBLEM is one maximisation of that lnL - the likelihood form, and for a beta-dependent covariance
+ * the log-determinant term (:444-481), included: with uniform priors the MAP point - over the d sampled parameters inside
+ * their prior box, against the context's data vector or against one simulation realisation (vk_set_realisations).  The
+ * chi-square reported is the chi-square AT that point (:325-354), not a separate chi-square minimum.
+ * Every problem runs textbook Nelder-Mead (Lagarias et al. 1998, the rules of scipy.optimize's 'Nelder-Mead'; DESIGN.md
+ * section 7a) with the four candidates of an iteration evaluated in one launch: a problem owns S = max(4, d + 1) rows per
+ * launch, all problems advance together, one launch per iteration, no host round trip per iteration.
+ *   columns[j]  row column (VK_P_*) of the j-th sampled parameter, or VK_WALK_EPSILON (the columns APERP, APAR, EPSILON follow
+ *               from it and `alpha` as vk_epsilon_to_ap forms them); each column once, 1 <= n_params <= 10
+ *   lo, hi      [n_params] the box; a candidate outside it reads f = +inf and is not evaluated
+ *   base_rows   [n_problems][VK_NPAR]: the fixed parameters and defaults of each problem's rows
+ *   which       [n_problems] realisation (0 .. n_real - 1 of the context's set) of each problem; NULL: the data vector
+ * vk_fit_run: x0 [n_problems][n_params] starts (inside the box), step [n_params] initial steps (> 0: vertex j of the start
+ *   simplex is x0 + step_j e_j, else x0 - step_j e_j, else clamped to the box), xtol [n_params] and ftol (in lnL) the
+ *   convergence test (every parameter's spread over the simplex <= xtol_j, and the spread of -lnL <= ftol), max_iter the
+ *   iteration limit (launches of the problem: init, candidate and shrink launches), restarts the number of times a converged
+ *   simplex is rebuilt around its best vertex before the problem is done.  Out, per problem: x [n_problems][n_params] the best
+ *   vertex, lnl / chi2 there, status VK_FIT_*, n_iter, n_evals (rows whose value the search used: what a one-point-at-a-time
+ *   Nelder-Mead would have evaluated; the GPU evaluates S rows per iteration).  VK_FIT_NO_FINITE_START: every start vertex
+ *   read -inf; then x = x0, lnl = -inf, chi2 = inf.  Synchronous.  A run owns its context: nothing else may use it until the
+ *   run returns.  On error the code is returned, vk_fit_last_error gives the text and nothing stays in flight.
+ *   Refused (VK_E_ARG): a batch begun with vk_eval_batch_begin, realisation mode without (enough) realisations set, a start
+ *   outside the box, a step <= 0. */
+#define VK_FIT_CONVERGED 0
+#define VK_FIT_MAX_ITER 1
+#define VK_FIT_NO_FINITE_START 2
+typedef struct vk_fit vk_fit;
+vk_fit* vk_fit_create(vk_ctx* ctx, const vk_eval_opts* opts, int32_t n_problems, int32_t n_params, const int32_t* columns,
+                      const double* lo, const double* hi, const double* base_rows, double alpha, const int32_t* which,
+                      char* err, size_t errlen);
+int vk_fit_run(vk_fit* f, const double* x0, const double* step, const double* xtol, double ftol, int32_t max_iter,
+               int32_t restarts, double* x, double* lnl, double* chi2, int32_t* status, int32_t* n_iter, int64_t* n_evals);
+const char* vk_fit_last_error(const vk_fit* f);
+void vk_fit_destroy(vk_fit* f);
+
 /* Theory multipoles on a caller-supplied s grid: out[n][n_ell][n_s] with the caller's own
  * projection weights w_ell[n_ell][n_mu] on mu[n_mu] (host buffers). */
 int vk_theory_batch(vk_ctx* ctx, const vk_eval_opts* opts, const double* params, int64_t n,

@@ -4,5 +4,5 @@ Existing scripts, notebooks and cobaya YAML files written for seshnadathur/victo
 (``from victor import CCFFit``; ``python_path: ./victor/likelihoods/``) keep working unchanged.
 """
 
-from victor_amd import (BackgroundCosmology, CCFFit, CCFModel, InputError, JointFit, JointRealisations, Realisations,  # noqa: F401
-                        __version__, utils)
+from victor_amd import (BackgroundCosmology, BestFit, CCFFit, CCFModel, InputError, JointFit, JointRealisations,  # noqa: F401
+                        Realisations, __version__, utils)

@@ -8,9 +8,10 @@ from . import utils
 from .ccf_fit import CCFFit
 from .ccf_model import CCFModel
 from .cosmology import BackgroundCosmology
+from .fitting import BestFit
 from .joint import JointFit, JointRealisations
 from .realisations import Realisations
 from .utils import InputError
 
 __version__ = "0.1.0"
-__all__ = ["CCFModel", "CCFFit", "BackgroundCosmology", "InputError", "JointFit", "JointRealisations", "Realisations", "utils", "__version__"]
+__all__ = ["CCFModel", "CCFFit", "BackgroundCosmology", "BestFit", "InputError", "JointFit", "JointRealisations", "Realisations", "utils", "__version__"]

@@ -19,6 +19,10 @@ RSD = {"streaming": 0, "dispersion": 1, "kaiser": 2, "euclid_special": 3}
 LIKE = {"gaussian": 0, "sellentin": 1, "hartlap": 2, "percival": 3}
 VK_COMM_ID_BYTES = 128
 VK_WALK_EPSILON = -1
+# row column of every parameter a sampler or optimiser may vary (epsilon: VK_WALK_EPSILON, it sets aperp / apar / epsilon)
+ROW_COLUMNS = {"fsigma8": P_FSIGMA8, "sigma_v": P_SIGMAV, "beta": P_BETA, "astar": P_ASTAR, "M": P_M, "Q": P_Q, "bias": P_BIAS,
+               "Av": P_AV}
+VK_FIT_CONVERGED, VK_FIT_MAX_ITER, VK_FIT_NO_FINITE_START = 0, 1, 2
 
 _dp = C.POINTER(C.c_double)
 
@@ -127,6 +131,12 @@ SYMBOLS = {
     "vk_xi_smu_batch": (C.c_int, [_vp, _optp, _dp, C.c_int64, _dp, C.c_int32, _dp, C.c_int32, _dp]),
     "vk_set_realisations": (C.c_int, [_vp, _dp, C.c_int32]),
     "vk_eval_realisations": (C.c_int, [_vp, _optp, _dp, C.c_int64, C.POINTER(C.c_int32), _dp, _dp]),
+    "vk_fit_create": (_vp, [_vp, _optp, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _dp, _dp, _dp, C.c_double,
+                            C.POINTER(C.c_int32), C.c_char_p, C.c_size_t]),
+    "vk_fit_run": (C.c_int, [_vp, _dp, _dp, _dp, C.c_double, C.c_int32, C.c_int32, _dp, _dp, _dp, C.POINTER(C.c_int32),
+                             C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "vk_fit_last_error": (C.c_char_p, [_vp]),
+    "vk_fit_destroy": (None, [_vp]),
     "vk_device_alloc": (_vp, [_vp, C.c_size_t]),
     "vk_device_free": (None, [_vp, _vp]),
     "vk_memcpy_h2d": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),

@@ -310,6 +310,20 @@ class CCFFit(CCFModel):
         lnl, chi2, _ = self._run(params, kwargs)
         return lnl, chi2
 
+    def best_fit(self, params, fixed=None, start=None, step=None, xtol=None, ftol=1e-6, max_iter=None, restarts=1, **kwargs):
+        """Maximum of lnL (the value :meth:`log_likelihood` returns: with uniform priors the MAP point) over the sampled
+        parameters of a cobaya ``params`` block, inside their prior box, by a bounded Nelder-Mead search on the GPU
+        (:mod:`victor_amd.fitting`).  Sampled: the uniform prior (the box), ``ref.loc`` (the start), ``proposal`` (the initial
+        step); scalar entries are fixed values.  ``fixed``: name -> value overrides, which also take a sampled parameter out of
+        the fit; arrays of one common length R give R problems against the data vector (a profile likelihood).  ``start``:
+        name -> scalar or one value per problem; ``step``, ``xtol`` (default 1e-4 x step): name -> scalar; ``ftol`` in lnL;
+        ``max_iter`` (default 200 d) counts launches; ``restarts``: rebuilds of a converged simplex around its best vertex.
+        ``kwargs``: model and fit option overrides as :meth:`log_likelihood_batch` takes them.  Returns a
+        :class:`victor_amd.fitting.BestFit`; its ``chi2`` is the chi-square at the best point, not a chi-square minimum.
+        Runs on this fit's own context (never through the broker)."""
+        from .fitting import best_fit
+        return best_fit(self, params, fixed, start, step, xtol, ftol, max_iter, restarts, kwargs)
+
     def realisations(self, simulation_numbers=None):
         """Every simulation realisation of this fit's data file (or the listed ``simulation_numbers``) against one model:
         :class:`victor_amd.realisations.Realisations`.  The fit must have been built with an integer ``simulation_number``."""

@@ -18,6 +18,8 @@
 //                        16 points per workgroup, the precision streamed from L2
 //   vk_kernel_joint_real.h  the same against many realisations of every block (vk_joint_cov_eval_realisations): rows are
 //                        (point, realisation) pairs, 16 realisations of one point per workgroup
+//   vk_kernel_fit.h      the best-fit search (vk_fit_run): start simplex, step and re-layout kernels, one thread per problem, over
+//                        the one-problem transition of vk_fit_simplex.h (plain C++, also compiled on its own by the CPU tests)
 //
 // K1 restates CCFModel.theory_xi (streaming branch victor/ccf_model.py:589-690; the other branches :658-784),
 // theory_multipoles (:816-825) and utils.multipoles_from_fn (victor/utils.py:45-56); K2 restates CCFFit.chi_squared
@@ -57,6 +59,7 @@
 #include "vk_kernel_real.h"
 #include "vk_kernel_joint.h"
 #include "vk_kernel_joint_real.h"
+#include "vk_kernel_fit.h"
 
 // The theory kernels' instantiations are generated in translation units of their own (vk_instances.h names what lives where);
 // here they are declared only.
@@ -1599,6 +1602,46 @@ struct RealChunks {
   }
 };
 
+// The realisation kernel keeps a point's precision, theory vector and a tile of residuals in LDS: refused above 160 KiB.
+static int check_real_lds(vk_ctx* ctx) {
+  const size_t lds = real_lds_doubles(ctx->N) * sizeof(double);
+  if (lds > 160 * 1024)
+    return fail(ctx, VK_E_ARG, "data vector of %d bins needs %zu bytes of LDS for the realisation kernel (> 160 KiB)", ctx->N, lds);
+  return VK_OK;
+}
+
+// Enqueue on ctx's stream: the theory vectors of m device rows d_par into the workspace d_th, then the realisation chi-square
+// kernel behind them - every point against every realisation (d_which NULL: outputs [m][n_real]) or point i against realisation
+// d_which[i] (pairs mode, indices in device memory: outputs [m]).  The caller has checked the LDS limit (check_real_lds) and the
+// indices.  Shared by vk_eval_realisations and the best-fit loop (vk_fit_run).
+static int enqueue_realisations(vk_ctx* ctx, const vk_eval_opts* opts, const double* d_par, long long m, double* d_th, double* d_lnl,
+                                double* d_chi, const int32_t* d_which) {
+  const bool timed = ctx->timing;
+  if (timed) {
+    harvest_timing(ctx);
+    VK_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+  }
+  int rc = vk_eval_batch_device_async(ctx, opts, d_par, m, nullptr, nullptr, d_th);     // theory vectors only, into the workspace
+  if (rc) return rc;
+  if (timed) VK_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+  RealArgs ra{};
+  fill_like_args(ctx, opts, d_par, d_th, m, d_lnl, d_chi, &ra.like);
+  ra.real = ctx->d_real;
+  ra.block = ctx->real_block;
+  ra.n_real = ctx->n_real;
+  ra.which = d_which;
+  ctx->last_like = ctx->knobs.real_valu ? "like_real<false>" : "like_real<true>";
+  const size_t lds = real_lds_doubles(ctx->N) * sizeof(double);
+  rc = ctx->knobs.real_valu ? launch_on_stream(ctx, vk_like_real_kernel<false>, (int)m, lds, ra)
+                            : launch_on_stream(ctx, vk_like_real_kernel<true>, (int)m, lds, ra);
+  if (rc) return rc;
+  if (timed) {
+    VK_HIP(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
+    ctx->pending = true;
+  }
+  return VK_OK;
+}
+
 extern "C" {
 
 size_t vk_joint_workspace_doubles(vk_ctx* const* ctxs, int32_t n_ctx, int64_t n) {
@@ -2147,8 +2190,8 @@ int vk_eval_realisations(vk_ctx* ctx, const vk_eval_opts* opts, const double* pa
   if (rc) return rc;
   if (n == 0) return VK_OK;
   const int N = ctx->N;
-  const size_t lds = real_lds_doubles(N) * sizeof(double);
-  if (lds > 160 * 1024) return fail(ctx, VK_E_ARG, "data vector of %d bins needs %zu bytes of LDS for the realisation kernel (> 160 KiB)", N, lds);
+  rc = check_real_lds(ctx);
+  if (rc) return rc;
   VK_HIP(ctx, hipSetDevice(ctx->device));
   // a chunk is one theory launch into the workspace and one realisation launch behind it
   RealChunks ch(which, ctx->n_real, n);
@@ -2161,30 +2204,9 @@ int vk_eval_realisations(vk_ctx* ctx, const vk_eval_opts* opts, const double* pa
   ch.d_lnl = d_th + (size_t)m_max * N;
   ch.d_chi = ch.d_lnl + (size_t)m_max * ch.per_point;
   ch.d_which = reinterpret_cast<int32_t*>(ch.d_chi + (size_t)m_max * ch.per_point);
-  const bool timed = ctx->timing;
   return ch.run(ctx, params, which, n, lnl, chi2, [&](long long m) {
-    if (timed) {
-      harvest_timing(ctx);
-      VK_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-    }
-    int rc = vk_eval_batch_device_async(ctx, opts, ch.d_par, m, nullptr, nullptr, d_th);     // theory vectors only, into the workspace
-    if (rc) return rc;
-    if (timed) VK_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-    RealArgs ra{};
-    fill_like_args(ctx, opts, ch.d_par, d_th, m, lnl ? ch.d_lnl : nullptr, chi2 ? ch.d_chi : nullptr, &ra.like);
-    ra.real = ctx->d_real;
-    ra.block = ctx->real_block;
-    ra.n_real = ctx->n_real;
-    ra.which = which ? ch.d_which : nullptr;
-    ctx->last_like = ctx->knobs.real_valu ? "like_real<false>" : "like_real<true>";
-    rc = ctx->knobs.real_valu ? launch_on_stream(ctx, vk_like_real_kernel<false>, (int)m, lds, ra)
-                              : launch_on_stream(ctx, vk_like_real_kernel<true>, (int)m, lds, ra);
-    if (rc) return rc;
-    if (timed) {
-      VK_HIP(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
-      ctx->pending = true;
-    }
-    return VK_OK;
+    return enqueue_realisations(ctx, opts, ch.d_par, m, d_th, lnl ? ch.d_lnl : nullptr, chi2 ? ch.d_chi : nullptr,
+                                which ? ch.d_which : nullptr);
   });
 }
 
@@ -2249,6 +2271,245 @@ int vk_joint_cov_eval_realisations(vk_joint_cov* h, vk_ctx* const* ctxs, int32_t
     const long long tiles = which ? (m + kJointRows - 1) / kJointRows : m * ((n_real + kJointRows - 1) / kJointRows);
     return joint_chi2(h, ctxs, n_ctx, e, "joint_real_chi2", vk_joint_real_chi2_kernel, tiles, lds, jr);
   });
+}
+
+}  // extern "C"
+
+// ---- best fits: bounded Nelder-Mead, one simplex per problem, one launch per iteration (include/victor_hip.h, vk_kernel_fit.h) --
+// An iteration enqueues, on the context's stream, the evaluation of the active problems' S rows each (the fit's own data
+// vector: vk_eval_batch_device_async with lnL / chi2, so the fused tail applies; realisations: enqueue_realisations in pairs
+// mode) and the step kernel behind it - no host synchronisation and no graph inside an iteration.  Every kFitCheck iterations
+// the host reads the status words, keeps the problems still running (in problem order) and lays their rows out again, so a
+// finished problem stops costing evaluations and which rows share a launch does not depend on timing.
+constexpr int kFitCheck = 8;
+constexpr int kFitMaxProblems = 65536;
+
+struct vk_fit {
+  vk_ctx* ctx = nullptr;
+  vk_eval_opts opts{};
+  int R = 0, P = 0, S = 0;
+  int col[vkfit::kMaxP] = {};
+  double alpha = 1.0;
+  double lo[vkfit::kMaxP] = {}, hi[vkfit::kMaxP] = {};
+  bool real = false;
+  int max_which = -1;
+  void* d_mem = nullptr;                   // one allocation holding everything below
+  vkfit::State* d_state = nullptr;         // [R]
+  double *d_base = nullptr, *d_x0 = nullptr, *d_rows = nullptr, *d_lnl = nullptr, *d_chi = nullptr, *d_th = nullptr;
+  int *d_active = nullptr, *d_row_which = nullptr, *d_which = nullptr, *d_status = nullptr;
+  std::string err;
+};
+
+static int fit_launch(vk_ctx* ctx, void (*kern)(FitArgs), const FitArgs& a) {
+  hipLaunchKernelGGL(kern, dim3((unsigned)((a.n_active + kFitBlock - 1) / kFitBlock)), dim3(kFitBlock), 0, ctx->stream, a);
+  VK_HIP(ctx, hipGetLastError());
+  return VK_OK;
+}
+
+// the loop of vk_fit_run; errors are reported through ctx->err
+static int fit_loop(vk_fit* f, const vkfit::Params& q, const double* x0, std::vector<vkfit::State>* out) {
+  vk_ctx* ctx = f->ctx;
+  const int R = f->R, S = f->S;
+  VK_HIP(ctx, hipSetDevice(ctx->device));
+  std::vector<int> act(R), status(R);
+  for (int p = 0; p < R; ++p) act[p] = p;
+  VK_HIP(ctx, hipMemcpyAsync(f->d_x0, x0, (size_t)R * f->P * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  VK_HIP(ctx, hipMemcpyAsync(f->d_active, act.data(), (size_t)R * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+  FitArgs a{};
+  a.q = q;
+  a.state = f->d_state;
+  a.base = f->d_base;
+  a.x0 = f->d_x0;
+  a.active = f->d_active;
+  a.n_active = R;
+  a.lnl = f->d_lnl;
+  a.chi2 = f->d_chi;
+  a.rows = f->d_rows;
+  a.row_which = f->real ? f->d_row_which : nullptr;
+  a.which = f->real ? f->d_which : nullptr;
+  a.status = f->d_status;
+  for (int j = 0; j < vkfit::kMaxP; ++j) a.col[j] = f->col[j];
+  a.alpha = f->alpha;
+  int rc = fit_launch(ctx, vk_fit_init_kernel, a);
+  while (rc == VK_OK) {
+    const long long n_rows = (long long)a.n_active * S;
+    for (int t = 0; t < kFitCheck && rc == VK_OK; ++t) {
+      rc = f->real ? enqueue_realisations(ctx, &f->opts, f->d_rows, n_rows, f->d_th, f->d_lnl, f->d_chi, f->d_row_which)
+                   : vk_eval_batch_device_async(ctx, &f->opts, f->d_rows, n_rows, f->d_lnl, f->d_chi, f->d_th);
+      if (rc == VK_OK) rc = fit_launch(ctx, vk_fit_step_kernel, a);
+    }
+    if (rc) return rc;
+    VK_HIP(ctx, hipMemcpyAsync(status.data(), f->d_status, (size_t)R * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    VK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<int> next;
+    for (int p : act)
+      if (status[p] < 0) next.push_back(p);
+    if (next.empty()) break;
+    if ((int)next.size() < a.n_active) {
+      act.swap(next);
+      a.n_active = (int)act.size();
+      VK_HIP(ctx, hipMemcpyAsync(f->d_active, act.data(), act.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+      rc = fit_launch(ctx, vk_fit_emit_kernel, a);
+    }
+  }
+  if (rc) return rc;
+  out->resize(R);
+  VK_HIP(ctx, hipMemcpy(out->data(), f->d_state, (size_t)R * sizeof(vkfit::State), hipMemcpyDeviceToHost));
+  return VK_OK;
+}
+
+extern "C" {
+
+vk_fit* vk_fit_create(vk_ctx* ctx, const vk_eval_opts* opts, int32_t n_problems, int32_t n_params, const int32_t* columns,
+                      const double* lo, const double* hi, const double* base_rows, double alpha, const int32_t* which, char* err,
+                      size_t errlen) {
+  auto bail = [&](const std::string& msg) -> vk_fit* {
+    if (err && errlen) {
+      strncpy(err, msg.c_str(), errlen - 1);
+      err[errlen - 1] = 0;
+    }
+    return nullptr;
+  };
+  if (!ctx || !opts || !columns || !lo || !hi || !base_rows) return bail("vk_fit_create: NULL argument");
+  if (n_problems < 1 || n_problems > kFitMaxProblems) return bail("vk_fit_create: need 1 <= problems <= 65536");
+  if (n_params < 1 || n_params > vkfit::kMaxP)
+    return bail("vk_fit_create: need 1 <= parameters <= 10 (the row columns other than aperp / apar / epsilon, and epsilon)");
+  sync_knobs(ctx);
+  if (check_opts(ctx, opts) != VK_OK) return bail(ctx->err);
+  if (!ctx->d_data) return bail("vk_fit_create: context was created without a data vector");
+  bool used[VK_NPAR] = {};
+  int n_eps = 0;
+  for (int j = 0; j < n_params; ++j) {
+    const int c = columns[j];
+    if (c == VK_WALK_EPSILON) {
+      ++n_eps;
+    } else if (c < 0 || c >= VK_NPAR || (c >= VK_P_APERP && c <= VK_P_EPSILON) || used[c]) {
+      return bail("vk_fit_create: a sampled parameter must name a row column other than aperp / apar / epsilon, or VK_WALK_EPSILON, once");
+    } else {
+      used[c] = true;
+    }
+    if (!(hi[j] > lo[j])) return bail("vk_fit_create: the prior box needs lo < hi");
+  }
+  if (n_eps > 1) return bail("vk_fit_create: epsilon sampled twice");
+  int max_which = -1;
+  if (which)
+    for (int i = 0; i < n_problems; ++i) {
+      if (which[i] < 0 || which[i] >= ctx->n_real)
+        return bail("vk_fit_create: realisation index " + std::to_string(which[i]) + " of problem " + std::to_string(i) +
+                    " is outside 0.." + std::to_string(ctx->n_real - 1));
+      max_which = std::max(max_which, (int)which[i]);
+    }
+  vk_fit* f = new (std::nothrow) vk_fit();
+  if (!f) return bail("out of memory");
+  f->ctx = ctx;
+  f->opts = *opts;
+  f->R = n_problems;
+  f->P = n_params;
+  f->S = vkfit::slots(n_params);
+  for (int j = 0; j < n_params; ++j) {
+    f->col[j] = columns[j];
+    f->lo[j] = lo[j];
+    f->hi[j] = hi[j];
+  }
+  f->alpha = alpha;
+  f->real = which != nullptr;
+  f->max_which = max_which;
+  const size_t R = n_problems, RS = R * f->S;
+  const size_t doubles = R * VK_NPAR + R * n_params + RS * VK_NPAR + 2 * RS + RS * ctx->N;
+  const size_t ints = R + RS + R + R;
+  const size_t bytes = R * sizeof(vkfit::State) + doubles * sizeof(double) + ints * sizeof(int);
+  if (hipSetDevice(ctx->device) != hipSuccess || hipMalloc(&f->d_mem, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    delete f;
+    return bail("vk_fit_create: cannot allocate " + std::to_string(bytes) + " bytes of device memory");
+  }
+  char* m = static_cast<char*>(f->d_mem);
+  f->d_state = reinterpret_cast<vkfit::State*>(m);
+  double* d = reinterpret_cast<double*>(m + R * sizeof(vkfit::State));
+  f->d_base = d;
+  f->d_x0 = f->d_base + R * VK_NPAR;
+  f->d_rows = f->d_x0 + R * n_params;
+  f->d_lnl = f->d_rows + RS * VK_NPAR;
+  f->d_chi = f->d_lnl + RS;
+  f->d_th = f->d_chi + RS;
+  int* i = reinterpret_cast<int*>(f->d_th + RS * ctx->N);
+  f->d_active = i;
+  f->d_row_which = f->d_active + R;
+  f->d_which = f->d_row_which + RS;
+  f->d_status = f->d_which + R;
+  bool ok = hipMemcpy(f->d_base, base_rows, R * VK_NPAR * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+  if (ok && which) ok = hipMemcpy(f->d_which, which, R * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    vk_fit_destroy(f);
+    return bail("vk_fit_create: upload failed");
+  }
+  return f;
+}
+
+const char* vk_fit_last_error(const vk_fit* f) { return f ? f->err.c_str() : ""; }
+
+void vk_fit_destroy(vk_fit* f) {
+  if (!f) return;
+  if (f->d_mem) {
+    (void)hipSetDevice(f->ctx->device);
+    (void)hipFree(f->d_mem);
+  }
+  delete f;
+}
+
+int vk_fit_run(vk_fit* f, const double* x0, const double* step, const double* xtol, double ftol, int32_t max_iter, int32_t restarts,
+               double* x, double* lnl, double* chi2, int32_t* status, int32_t* n_iter, int64_t* n_evals) {
+  if (!f) return VK_E_ARG;
+  vk_ctx* ctx = f->ctx;
+  auto refuse = [&](const std::string& msg) {
+    f->err = msg;
+    return VK_E_ARG;
+  };
+  if (!x0 || !step || !xtol || !x || !lnl || !chi2 || !status || !n_iter || !n_evals) return refuse("vk_fit_run: NULL argument");
+  if (ctx->begun_n != 0) return refuse("vk_fit_run: a batch begun with vk_eval_batch_begin is awaiting vk_eval_batch_finish on the context");
+  if (f->real) {
+    if (ctx->n_real <= 0 || !ctx->d_real) return refuse("vk_fit_run: no realisations are set on the context (vk_set_realisations)");
+    if (f->max_which >= ctx->n_real)
+      return refuse("vk_fit_run: the context holds " + std::to_string(ctx->n_real) + " realisations, a problem asks for number " +
+                    std::to_string(f->max_which));
+    if (check_real_lds(ctx) != VK_OK) return refuse(ctx->err);
+  }
+  if (max_iter < 1 || restarts < 0 || !(ftol >= 0)) return refuse("vk_fit_run: need max_iter >= 1, restarts >= 0, ftol >= 0");
+  vkfit::Params q{};
+  q.d = f->P;
+  q.S = f->S;
+  q.max_iter = max_iter;
+  q.restarts = restarts;
+  q.ftol = ftol;
+  for (int j = 0; j < f->P; ++j) {
+    if (!(step[j] > 0) || !(xtol[j] >= 0)) return refuse("vk_fit_run: parameter " + std::to_string(j) + " needs step > 0 and xtol >= 0");
+    q.lo[j] = f->lo[j];
+    q.hi[j] = f->hi[j];
+    q.step[j] = step[j];
+    q.xtol[j] = xtol[j];
+  }
+  for (int p = 0; p < f->R; ++p)
+    if (!vkfit::in_box(q, x0 + (size_t)p * f->P)) return refuse("vk_fit_run: the start of problem " + std::to_string(p) + " is outside the box");
+  std::vector<vkfit::State> st;
+  const int rc = fit_loop(f, q, x0, &st);
+  if (rc != VK_OK) {
+    f->err = ctx->err;
+    (void)hipStreamSynchronize(ctx->stream);          // nothing stays in flight
+    (void)hipGetLastError();
+    return rc;
+  }
+  for (int p = 0; p < f->R; ++p) {
+    const vkfit::State& s = st[p];
+    for (int j = 0; j < f->P; ++j) x[(size_t)p * f->P + j] = s.v[0][j];
+    lnl[p] = -s.f[0];
+    chi2[p] = s.chi[0];
+    status[p] = s.status;
+    n_iter[p] = s.iter;
+    n_evals[p] = s.n_evals;
+  }
+  f->err.clear();
+  return VK_OK;
 }
 
 }  // extern "C"

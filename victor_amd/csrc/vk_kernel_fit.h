@@ -1,0 +1,96 @@
+// vk_kernel_fit.h: the bounded Nelder-Mead search of vk_fit_run (include/victor_hip.h) on the device - part of libvictor_hip.so
+// (see victor_hip.hip for the overview, DESIGN.md section 7a for the algorithm and the measurements).
+//
+// One thread per problem.  The search's state lives in device memory (vkfit::State, one per problem); between two of these
+// kernels the library evaluates the S rows of every active problem (the fit's own data vector: the theory launch with its
+// chi-square; a realisation: the theory launch and vk_like_real_kernel in pairs mode).  The step kernel reads those S
+// (lnL, chi2) pairs, applies vkfit::transition and writes the problem's next S rows - the base row with the sampled columns
+// overwritten and epsilon turned into the Alcock-Paczynski factors as vk_epsilon_to_ap forms them - and, against realisations,
+// each row's realisation index.  Rows of launch position k are rows k S .. k S + S - 1; the host keeps the list of active
+// problems (in problem order) and, when it shrinks, lays the rows out again with vk_fit_emit_kernel.
+#pragma once
+#include "vk_common.h"
+#include "vk_fit_simplex.h"
+
+namespace vk {
+
+constexpr int kFitBlock = 64;
+
+struct FitArgs {
+  vkfit::Params q;
+  vkfit::State* state;      // [n_problems]
+  const double* base;       // [n_problems][VK_NPAR]: fixed parameters and defaults of each problem's rows
+  const double* x0;         // [n_problems][d]: starts (vk_fit_init_kernel)
+  const int* active;        // [n_active]: problem at each launch position (NULL: position = problem)
+  int n_active;
+  const double* lnl;        // [n_active * S] results of the launch just evaluated
+  const double* chi2;
+  double* rows;             // [n_active * S][VK_NPAR]: the next launch's rows
+  int* row_which;           // [n_active * S]: realisation of each row, or NULL (the fit's own data vector)
+  const int* which;         // [n_problems]: realisation of each problem, or NULL
+  int* status;              // [n_problems]: -1 while the problem runs, then its VK_FIT_* status
+  int col[vkfit::kMaxP];    // row column of each sampled parameter; VK_WALK_EPSILON: epsilon -> aperp, apar, epsilon
+  double alpha;
+};
+
+__device__ __forceinline__ void fit_emit(const FitArgs& a, const vkfit::State& s, int p, int k) {
+  const int S = a.q.S, d = a.q.d;
+  const double* b = a.base + (size_t)p * VK_NPAR;
+  for (int slot = 0; slot < S; ++slot) {
+    const size_t r = (size_t)k * S + slot;
+    double* row = a.rows + r * VK_NPAR;
+    for (int c = 0; c < VK_NPAR; ++c) row[c] = b[c];
+#pragma unroll
+    for (int j = 0; j < vkfit::kMaxP; ++j) {
+      if (j >= d) break;
+      const double x = s.pt[slot][j];
+      const int c = a.col[j];
+      if (c >= 0) {
+        row[c] = x;
+      } else {                                  // apar = alpha eps^(-2/3), aperp = eps apar (vk_epsilon_to_ap, ccf_model.py:589-592)
+        double ap = pow(x, -2.0 / 3.0);
+        if (a.alpha != 1.0) ap = a.alpha * ap;
+        row[VK_P_APAR] = ap;
+        row[VK_P_APERP] = x * ap;
+        row[VK_P_EPSILON] = x;
+      }
+    }
+    if (a.row_which) a.row_which[r] = a.which[p];
+  }
+}
+
+// the start simplex of every problem (launch position = problem)
+__global__ void __launch_bounds__(kFitBlock) vk_fit_init_kernel(FitArgs a) {
+  const int p = blockIdx.x * kFitBlock + threadIdx.x;
+  if (p >= a.n_active) return;
+  vkfit::State& s = a.state[p];
+  vkfit::start(s, a.q, a.x0 + (size_t)p * a.q.d);
+  a.status[p] = -1;
+  fit_emit(a, s, p, p);
+}
+
+// one transition per active problem, then its next rows at its launch position
+__global__ void __launch_bounds__(kFitBlock) vk_fit_step_kernel(FitArgs a) {
+  const int k = blockIdx.x * kFitBlock + threadIdx.x;
+  if (k >= a.n_active) return;
+  const int p = a.active[k];
+  vkfit::State& s = a.state[p];
+  if (s.phase == vkfit::kDone) return;
+  const int S = a.q.S;
+  vkfit::transition(s, a.q, a.lnl + (size_t)k * S, a.chi2 + (size_t)k * S);
+  if (s.phase == vkfit::kDone) {
+    a.status[p] = s.status;
+    return;
+  }
+  fit_emit(a, s, p, k);
+}
+
+// the pending rows of the active problems at their new launch positions (after the host has dropped finished problems)
+__global__ void __launch_bounds__(kFitBlock) vk_fit_emit_kernel(FitArgs a) {
+  const int k = blockIdx.x * kFitBlock + threadIdx.x;
+  if (k >= a.n_active) return;
+  const int p = a.active[k];
+  fit_emit(a, a.state[p], p, k);
+}
+
+}  // namespace vk

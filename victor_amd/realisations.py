@@ -136,6 +136,12 @@ class Realisations:
         """The chi-square half of :meth:`log_likelihood` (data vector interpolated in beta, as ``CCFFit.chi_squared``)."""
         return self.log_likelihood(params, **dict(kwargs, beta_interpolation="datavector"))[1]
 
+    def best_fit(self, params, fixed=None, start=None, step=None, xtol=None, ftol=1e-6, max_iter=None, restarts=1, **kwargs):
+        """Best-fit point of every realisation: problem i maximises lnL against realisation ``numbers[i]``, all of them in one
+        run on the GPU.  Arguments as ``CCFFit.best_fit``; ``fixed`` values must be scalars here."""
+        from .fitting import best_fit
+        return best_fit(self.fit, params, fixed, start, step, xtol, ftol, max_iter, restarts, kwargs, realisations=self)
+
     def log_likelihood_pairs(self, params, which, **kwargs):
         """(lnL, chi2), each ``(n_points,)``: point p against realisation ``numbers[which[p]]`` only - the form an ensemble of
         independent per-mock chains needs.  The same bits as the matching entries of :meth:`log_likelihood`."""

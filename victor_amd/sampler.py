@@ -131,7 +131,7 @@ class EnsembleMetropolis:
         return batch
 
     # ---- the direct route: rows written in place, two half-ensembles on two contexts, results into preallocated buffers ----
-    _COLUMNS = {"fsigma8": 0, "sigma_v": 1, "beta": 5, "astar": 6, "M": 7, "Q": 8, "bias": 9, "Av": 10}
+    _COLUMNS = N.ROW_COLUMNS
 
     def _bind(self, x):
         """Set up the direct route for the fit given at construction; False when the sampled parameters are not ones whose
