@@ -426,6 +426,49 @@ int vk_fit_run(vk_fit* f, const double* x0, const double* step, const double* xt
 const char* vk_fit_last_error(const vk_fit* f);
 void vk_fit_destroy(vk_fit* f);
 
+/* ---- Metropolis chains of the data vector or one realisation each, stepped on the device ---------------------------------
+ * The reference is sampled by cobaya, one likelihood per call (victor/likelihoods/CCFLikelihood.py:32), one data vector at a
+ * time; under MPI it runs independent chains, one process each (README.md:30).  Here C independent random-walk Metropolis
+ * chains of that lnL (victor/ccf_fit.py:356-483) - against the context's data vector, or chain c against realisation which[c]
+ * (vk_set_realisations) - advance in lock step with the step loop on the device: per step one evaluation of C rows and one
+ * small kernel that decides and writes the next rows.  Random numbers are the caller's: the chain is
+ * defined by a host loop (victor_amd/chains.py) and the device reproduces it.
+ *   columns, lo, hi, base_rows, alpha, which   as vk_fit_create, per CHAIN ([n_chains][VK_NPAR] base rows, [n_chains] indices);
+ *               1 <= n_chains <= 65536, 1 <= n_params <= 10.  Device memory is bounded by one block of 64 steps.
+ * One step of one chain: prop = x + dz; a proposal outside the box is evaluated at the chain's current position, discarded, and
+ *   reads lnL = -inf (every launch has n_chains rows); accept when logu < lnL' - lnL (IEEE: a NaN difference rejects); on accept
+ *   x, lnL, chi2 are replaced.  The decisions use additions and comparisons only; with the same rows in the same launches the
+ *   log-likelihoods are the bits vk_eval_batch / vk_eval_realisations (pairs mode) return for them.  When epsilon is sampled the
+ *   Alcock-Paczynski factors of a row are formed with the device's pow, the host's (vk_epsilon_to_ap) with libm's: rows, and so
+ *   log-likelihoods, then agree with a host-driven chain to rounding, not bit for bit.
+ * vk_chain_start: x0 [n_chains][n_params], inside the box; evaluates the starts.  Resets counters and moment sums; the pivot
+ *   of a chain's moment sums is its start.  Synchronous.
+ * vk_chain_begin: enqueues n_steps (1 .. 64) steps: dz [n_steps][n_chains][n_params] proposal increments, logu
+ *   [n_steps][n_chains] log acceptance levels.  Step t of the block is step first_step + t of the chains' life; it is KEPT when
+ *   it is >= burn and (step - burn) % thin == 0.  A kept step enters the chain's moment sums and, with want_history, the
+ *   block's history; *n_kept (may be NULL) receives the number of history slots the block fills.  Returns with the work
+ *   enqueued and the inputs consumed: the caller draws the next block meanwhile.
+ * vk_chain_finish: waits for the block and copies its history: x [n_kept][n_chains][n_params], lnl, chi2 [n_kept][n_chains]
+ *   (state after each kept step; NULL allowed when the block keeps none).
+ * vk_chain_state (between blocks): x [n_chains][n_params], lnl, chi2 [n_chains], the counters n_accept, n_steps, n_kept
+ *   [n_chains], pivot, sum1 [n_chains][n_params] (sum over kept steps of x_j - pivot_j), sum2 [n_chains][n_params][n_params]
+ *   (sum of (x_j - pivot_j)(x_k - pivot_k), symmetric), plain double sums in step order.  Any output may be NULL.
+ * A chain handle owns its context from vk_chain_begin to vk_chain_finish.  On error the code is returned, vk_chain_last_error
+ *   gives the text and nothing stays in flight.  Refused (VK_E_ARG): a batch begun with vk_eval_batch_begin, realisation mode
+ *   without (enough) realisations set, a start outside the box, begin without start or before the previous finish. */
+typedef struct vk_chain vk_chain;
+vk_chain* vk_chain_create(vk_ctx* ctx, const vk_eval_opts* opts, int32_t n_chains, int32_t n_params, const int32_t* columns,
+                          const double* lo, const double* hi, const double* base_rows, double alpha, const int32_t* which,
+                          char* err, size_t errlen);
+int vk_chain_start(vk_chain* f, const double* x0);
+int vk_chain_begin(vk_chain* f, int32_t n_steps, const double* dz, const double* logu, int64_t first_step, int64_t burn,
+                   int64_t thin, int32_t want_history, int32_t* n_kept);
+int vk_chain_finish(vk_chain* f, double* x, double* lnl, double* chi2);
+int vk_chain_state(vk_chain* f, double* x, double* lnl, double* chi2, int64_t* n_accept, int64_t* n_steps, int64_t* n_kept,
+                   double* pivot, double* sum1, double* sum2);
+const char* vk_chain_last_error(const vk_chain* f);
+void vk_chain_destroy(vk_chain* f);
+
 /* Theory multipoles on a caller-supplied s grid: out[n][n_ell][n_s] with the caller's own
  * projection weights w_ell[n_ell][n_mu] on mu[n_mu] (host buffers). */
 int vk_theory_batch(vk_ctx* ctx, const vk_eval_opts* opts, const double* params, int64_t n,

@@ -137,6 +137,15 @@ SYMBOLS = {
                              C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "vk_fit_last_error": (C.c_char_p, [_vp]),
     "vk_fit_destroy": (None, [_vp]),
+    "vk_chain_create": (_vp, [_vp, _optp, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _dp, _dp, _dp, C.c_double,
+                              C.POINTER(C.c_int32), C.c_char_p, C.c_size_t]),
+    "vk_chain_start": (C.c_int, [_vp, _dp]),
+    "vk_chain_begin": (C.c_int, [_vp, C.c_int32, _dp, _dp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_int32)]),
+    "vk_chain_finish": (C.c_int, [_vp, _dp, _dp, _dp]),
+    "vk_chain_state": (C.c_int, [_vp, _dp, _dp, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), _dp, _dp,
+                                 _dp]),
+    "vk_chain_last_error": (C.c_char_p, [_vp]),
+    "vk_chain_destroy": (None, [_vp]),
     "vk_device_alloc": (_vp, [_vp, C.c_size_t]),
     "vk_device_free": (None, [_vp, _vp]),
     "vk_memcpy_h2d": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),

@@ -1,0 +1,439 @@
+"""Metropolis chains of the data vector and of every realisation, stepped on the GPU: ``CCFFit.sample_chains`` and
+``Realisations.sample_chains``.
+
+The reference is sampled by cobaya, one likelihood per call and one data vector at a time (reference:
+``victor/likelihoods/CCFLikelihood.py:32``).  Mock validation wants the posterior of EVERY mock beside its best fit: here
+C = R x W independent random-walk Metropolis chains - R problems (the fit's data vector: R = 1; or the R realisations of a
+:class:`victor_amd.realisations.Realisations`), W chains per problem, chain c belonging to problem c // W - advance in lock step.
+Prior box, proposal widths and start distribution come from the cobaya ``params`` block (``parse_cobaya_params``), as
+:class:`victor_amd.sampler.EnsembleMetropolis` and ``best_fit`` read it.
+
+**A Python loop is the definition and the device loop reproduces it.**  Random numbers are drawn on the host with the generator
+and the block protocol of ``EnsembleMetropolis`` (blocks of 64 steps: ``dz = width * rng.standard_normal((64, C, d))``, then
+``logu = np.log(rng.random((64, C)))``; the start as ``initialise()`` draws it), so for the same seed and C the numbers are those
+an ``EnsembleMetropolis`` of C walkers consumes.  One step of one chain: ``prop = x + dz``; a proposal outside the box is
+evaluated at the chain's current position, discarded, and reads -inf (every launch has exactly C rows); accept when
+``logu < lnl_prop - lnl`` with IEEE semantics as NumPy applies them (a NaN difference rejects; a NaN lnL is stored as -inf).
+
+``device=False`` runs that loop in NumPy, all C rows per step through ``Realisations.log_likelihood_pairs`` (or
+``CCFFit.log_likelihood_batch``, or an ``evaluate`` callable: no GPU needed).  ``device=True`` hands blocks of 64 steps to
+``vk_chain_begin`` (``include/victor_hip.h``): per step the same evaluation of the same C rows and a small
+step kernel, no host round trip inside a block, the next block's numbers drawn while the block runs.  Both routes launch the same
+rows in the same order: with epsilon fixed the rows are the same bytes and so are the log-likelihoods.  **When epsilon is sampled**
+the device forms the Alcock-Paczynski factors of a row with its own ``pow``, the host with libm's: the log-likelihoods then agree
+to rounding, not bit for bit, and a decision ``logu < lnl_prop - lnl`` taken within that margin could fall the other way (as
+documented for ``speculate`` in :mod:`victor_amd.sampler`).
+
+"Kept" steps - step index >= ``burn`` and ``(step - burn) % thin == 0``, counted over the whole life of the object - enter the
+history (``keep_chain``) and the per-chain moment sums about the chain's start (the pivot), which are accumulated where the chain
+runs; ``mean`` and ``cov`` pool the W chains of a problem from those sums, so they cost O(C d^2) host memory whatever the length.
+"""
+
+import ctypes as C
+
+import numpy as np
+
+from . import _native as N
+from .sampler import EnsembleMetropolis, gelman_rubin, parse_cobaya_params
+from .utils import InputError
+
+BLOCK = EnsembleMetropolis.BLOCK
+MAX_CHAINS = 65536
+
+
+def pooled_moments(n_kept, pivot, sum1, sum2):
+    """(mean (R, d), cov (R, d, d)) of each problem's kept steps, pooled over its W chains, from the per-chain sums about the
+    chains' pivots: ``n_kept`` (R, W), ``pivot`` and ``sum1`` (R, W, d), ``sum2`` (R, W, d, d).  With delta_w = pivot_w - mean,
+
+        mean = sum_w (n_w pivot_w + S1_w) / n,      (n - 1) cov = sum_w (S2_w + S1_w delta_w^T + delta_w S1_w^T + n_w delta_w delta_w^T)
+
+    formed in extended precision, so that what the result carries is the rounding of the sums it was given (amplified by
+    1 + |mean - pivot|^2 / var where a pivot lies far from the mean: tests/test_chains.py).  NaN where a problem kept fewer
+    than one (mean) or two (cov) steps."""
+    ld = np.longdouble
+    nw = np.asarray(n_kept, dtype=ld)
+    p, s1, s2 = np.asarray(pivot, dtype=ld), np.asarray(sum1, dtype=ld), np.asarray(sum2, dtype=ld)
+    n = nw.sum(axis=1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = (nw[:, :, None] * p + s1).sum(axis=1) / n[:, None]
+        delta = p - mean[:, None, :]
+        cross = s1[:, :, :, None] * delta[:, :, None, :]
+        m2 = s2 + cross + np.swapaxes(cross, 2, 3) + nw[:, :, None, None] * delta[:, :, :, None] * delta[:, :, None, :]
+        cov = m2.sum(axis=1) / (n - 1)[:, None, None]
+    mean, cov = mean.astype(float), cov.astype(float)
+    mean[np.asarray(n < 1)] = np.nan
+    cov[np.asarray(n < 2)] = np.nan
+    return mean, cov
+
+
+class Chains:
+    """C = R x W chains and what they have produced so far.
+
+    ``names``; ``x`` (R, W, d), ``lnl``, ``chi2`` (R, W): the final state; ``chain`` (n_kept, R, W, d), ``lnl_chain``,
+    ``chi2_chain`` (n_kept, R, W): the kept steps (None with ``keep_chain=False``); ``mean`` (R, d), ``cov`` (R, d, d): pooled
+    over a problem's W chains and its kept steps (ddof = 1); ``n_accept`` (R, W), ``acceptance`` (R,); ``rhat`` (R, d):
+    :func:`victor_amd.sampler.gelman_rubin` of each problem's history (None without one, for W == 1 or fewer than two kept
+    steps); ``pivot`` (R, W, d), ``n_kept``, ``sum1`` (R, W, d), ``sum2`` (R, W, d, d): the per-chain moment sums as the route that
+    ran the chains returns them; ``n_steps``: steps taken.  :meth:`extend` continues the same chains.
+
+    Diagnostics of the definition route only (None on the device route): ``decision_margin``, the smallest
+    ``|lnl_prop - lnl - logu|`` over the decisions taken inside the box with a finite difference (how far the closest decision was
+    from falling the other way), and ``n_outside`` (R, W), the proposals that left the box."""
+
+    def __init__(self, names, specs, fixed, R, W, rng, width, burn, thin, keep_chain, evaluator, device_handle):
+        self.names = list(names)
+        self._specs, self.fixed = specs, fixed
+        self.R, self.W = R, W
+        self._rng, self._width = rng, width
+        self.burn, self.thin, self.keep_chain = burn, thin, keep_chain
+        self._evaluate = evaluator
+        self._dev = device_handle
+        self._engine = self._realisations = None
+        self._lo = np.array([s.lo for s in specs])
+        self._hi = np.array([s.hi for s in specs])
+        self._dz = self._logu = None
+        self._at = BLOCK
+        self.n_steps = 0
+        self._hist = ([], [], [])
+        self.chain = self.lnl_chain = self.chi2_chain = None
+        self.decision_margin = self.n_outside = None
+
+    # ------------------------------------------------------------------ random numbers: the blocks of EnsembleMetropolis ---
+    def _draw_block(self):
+        C_, d = self.R * self.W, len(self.names)
+        dz = self._width * self._rng.standard_normal((BLOCK, C_, d))
+        logu = np.log(self._rng.random((BLOCK, C_)))
+        return dz, logu
+
+    def _piece(self, remaining, ahead=None):
+        """The next piece of the current block (drawing a new one when it is used up; ``ahead``: one drawn in advance):
+        (dz [k, C, d], logu [k, C]), k <= remaining."""
+        if self._at >= BLOCK:
+            self._dz, self._logu = ahead if ahead is not None else self._draw_block()
+            self._at = 0
+        k = min(BLOCK - self._at, remaining)
+        t = self._at
+        self._at = t + k
+        return self._dz[t:t + k], self._logu[t:t + k]
+
+    def _kept(self, step):
+        return step >= self.burn and (step - self.burn) % self.thin == 0
+
+    # ------------------------------------------------------------------ the definition -----------------------------------
+    def _start_host(self, x0):
+        C_, d = x0.shape
+        self._x = x0.copy()
+        lnl, chi2 = self._evaluate(self._x)
+        self._lnl = np.where(np.isnan(lnl), -np.inf, lnl)
+        self._chi2 = np.array(chi2, dtype=float)
+        self._pivot = x0.copy()
+        self._n_accept = np.zeros(C_, dtype=np.int64)
+        self._n_kept = np.zeros(C_, dtype=np.int64)
+        self._sum1 = np.zeros((C_, d))
+        self._sum2 = np.zeros((C_, d, d))
+        self._n_outside = np.zeros(C_, dtype=np.int64)
+        self.decision_margin = np.inf
+
+    def _run_host(self, n_steps):
+        lo, hi = self._lo, self._hi
+        x, lnl, chi2 = self._x, self._lnl, self._chi2
+        done = 0
+        while done < n_steps:
+            dz, logu = self._piece(n_steps - done)
+            for t in range(len(dz)):
+                prop = x + dz[t]
+                inside = ((prop >= lo) & (prop <= hi)).all(axis=1)
+                rows = np.where(inside[:, None], prop, x)            # outside: the current position, result discarded
+                lnl_p, chi2_p = self._evaluate(rows)
+                lnl_p = np.where(inside, lnl_p, -np.inf)
+                with np.errstate(invalid="ignore"):
+                    accept = logu[t] < lnl_p - lnl                   # NaN (both -inf, or a NaN lnL): False
+                    margin = np.abs(lnl_p - lnl - logu[t])
+                margin = margin[np.isfinite(margin)]
+                if margin.size:
+                    self.decision_margin = min(self.decision_margin, float(margin.min()))
+                self._n_outside += ~inside
+                x[accept] = prop[accept]
+                lnl[accept] = lnl_p[accept]
+                chi2[accept] = chi2_p[accept]
+                self._n_accept += accept
+                if self._kept(self.n_steps):
+                    dx = x - self._pivot
+                    self._sum1 += dx
+                    self._sum2 += dx[:, :, None] * dx[:, None, :]
+                    self._n_kept += 1
+                    if self.keep_chain:
+                        for h, a in zip(self._hist, (x, lnl, chi2)):
+                            h.append(a.copy())
+                self.n_steps += 1
+            done += len(dz)
+
+    # ------------------------------------------------------------------ the device route ---------------------------------
+    def _check(self, rc, what):
+        if rc != 0:
+            lib, h = self._dev
+            msg = (lib.vk_chain_last_error(h) or b"").decode() or f"{what} failed ({rc})"
+            raise (InputError if rc == -1 else N.NativeError)(msg)
+
+    def _run_device(self, n_steps):
+        lib, h = self._dev
+        C_, d = self.R * self.W, len(self.names)
+        done = 0
+        ahead = None
+        while done < n_steps:
+            dz, logu = self._piece(n_steps - done, ahead)
+            ahead = None
+            k = len(dz)
+            n_kept = C.c_int32(0)
+            self._check(lib.vk_chain_begin(h, k, N.as_dp(np.ascontiguousarray(dz)), N.as_dp(np.ascontiguousarray(logu)), self.n_steps,
+                                           self.burn, self.thin, 1 if self.keep_chain else 0, C.byref(n_kept)), "vk_chain_begin")
+            try:
+                if self._at >= BLOCK and done + k < n_steps:         # the next block's numbers, drawn while this one runs
+                    ahead = self._draw_block()
+            finally:
+                m = n_kept.value
+                hx, hl, hc = np.empty((m, C_, d)), np.empty((m, C_)), np.empty((m, C_))
+                self._check(lib.vk_chain_finish(h, N.as_dp(hx), N.as_dp(hl), N.as_dp(hc)), "vk_chain_finish")
+            if m:
+                for hist, a in zip(self._hist, (hx, hl, hc)):
+                    hist.append(a)
+            self.n_steps += k
+            done += k
+
+    def _read_device(self):
+        lib, h = self._dev
+        C_, d = self.R * self.W, len(self.names)
+        i64 = C.POINTER(C.c_int64)
+        self._x, self._lnl, self._chi2 = np.empty((C_, d)), np.empty(C_), np.empty(C_)
+        self._n_accept, self._n_kept = np.empty(C_, dtype=np.int64), np.empty(C_, dtype=np.int64)
+        self._pivot, self._sum1, self._sum2 = np.empty((C_, d)), np.empty((C_, d)), np.empty((C_, d, d))
+        self._check(lib.vk_chain_state(h, N.as_dp(self._x), N.as_dp(self._lnl), N.as_dp(self._chi2),
+                                       self._n_accept.ctypes.data_as(i64), None, self._n_kept.ctypes.data_as(i64),
+                                       N.as_dp(self._pivot), N.as_dp(self._sum1), N.as_dp(self._sum2)), "vk_chain_state")
+
+    def __del__(self):
+        dev = getattr(self, "_dev", None)
+        if dev:
+            try:
+                dev[0].vk_chain_destroy(dev[1])
+            except Exception:
+                pass
+            self._dev = None
+
+    # ------------------------------------------------------------------ public ------------------------------------------
+    def extend(self, n_steps):
+        """Continue the same chains for ``n_steps`` more steps: the same generator, the same blocks of random numbers, the same
+        burn / thin pattern - the chains of one longer call."""
+        n_steps = int(n_steps)
+        if n_steps < 0:
+            raise InputError("sample_chains: n_steps must be >= 0")
+        if self._dev and self._realisations is not None:
+            self._realisations._upload(self._engine)      # another object's realisations may have been set on the engine since
+        if n_steps:
+            (self._run_device if self._dev else self._run_host)(n_steps)
+        if self._dev:
+            self._read_device()
+        self._publish()
+        return self
+
+    def _publish(self):
+        R, W, d = self.R, self.W, len(self.names)
+        self.x = self._x.reshape(R, W, d).copy()
+        self.lnl, self.chi2 = self._lnl.reshape(R, W).copy(), self._chi2.reshape(R, W).copy()
+        self.n_accept = self._n_accept.reshape(R, W).copy()
+        self.acceptance = self.n_accept.sum(axis=1) / max(1, self.n_steps * W)
+        self.pivot, self.sum1 = self._pivot.reshape(R, W, d).copy(), self._sum1.reshape(R, W, d).copy()
+        self.sum2 = self._sum2.reshape(R, W, d, d).copy()
+        per_chain = self._n_kept.reshape(R, W)
+        self.n_kept = int(per_chain[0, 0])
+        self.mean, self.cov = pooled_moments(per_chain, self.pivot, self.sum1, self.sum2)
+        if not self._dev:
+            self.n_outside = self._n_outside.reshape(R, W).copy()
+        self.rhat = None
+        if self.keep_chain:
+            hx, hl, hc = self._hist
+            if len(hx) > 1:                                  # one array per block -> one array
+                self._hist = ([np.concatenate([a.reshape(-1, R * W, d) for a in hx])],
+                              [np.concatenate([a.reshape(-1, R * W) for a in hl])], [np.concatenate([a.reshape(-1, R * W) for a in hc])])
+                hx, hl, hc = self._hist
+            self.chain = (hx[0].reshape(-1, R, W, d) if hx else np.empty((0, R, W, d)))
+            self.lnl_chain = hl[0].reshape(-1, R, W) if hl else np.empty((0, R, W))
+            self.chi2_chain = hc[0].reshape(-1, R, W) if hc else np.empty((0, R, W))
+            if W > 1 and len(self.chain) > 1:
+                with np.errstate(invalid="ignore", divide="ignore"):
+                    self.rhat = np.stack([gelman_rubin(self.chain[:, r]) for r in range(R)])
+
+
+def _per_problem(name, v, R):
+    a = np.asarray(v, dtype=float)
+    if a.ndim == 0:
+        return np.full(R, float(a))
+    if a.shape != (R,):
+        raise InputError(f"sample_chains: {name}: one value per problem ({R}) or a scalar")
+    return a
+
+
+def _draw_start(rng, loc, scale, lo, hi, what):
+    """One start as ``EnsembleMetropolis.initialise`` draws it: redrawn until inside the box."""
+    for _ in range(1000):
+        cand = loc + scale * rng.standard_normal(len(loc))
+        if np.all((cand >= lo) & (cand <= hi)):
+            return cand
+    raise InputError(f"sample_chains: {what} lies outside the prior")
+
+
+def sample_chains(fit, params, n_steps, walkers=8, seed=0, fixed=None, start=None, scatter=None, proposal=None, burn=0, thin=1,
+                  keep_chain=True, device=True, kwargs=None, realisations=None, evaluate=None):
+    """The work of ``CCFFit.sample_chains`` (``realisations=None``: the fit's data vector, R = 1) and
+    ``Realisations.sample_chains`` (R = the realisations); see the module docstring.  With ``evaluate`` - a callable taking a dict
+    of ``(C,)`` arrays (sampled and fixed parameters) and returning ``lnL (C,)`` or ``(lnL, chi2)`` - in place of ``fit`` only the
+    definition route (``device=False``) is possible, R = 1 and no GPU is needed (chi2 reads -2 lnL when it is not returned).
+
+    ``params``: the cobaya block; ``fixed``: name -> scalar overrides, which also take a sampled parameter out of the chain;
+    ``walkers``: chains per problem; ``start``: None (each chain drawn from the ``ref`` distribution), a
+    :class:`victor_amd.fitting.BestFit` or a dict name -> scalar or ``(R,)`` array: every chain of problem i starts at
+    ``start_i + scatter * normal`` (``scatter``: name -> scalar, default the proposal widths; 0 starts every chain at the point
+    itself), redrawn until inside the box; ``proposal``: name -> width overrides.  Every argument is checked before the first
+    device call.  Returns a :class:`Chains`."""
+    kwargs = kwargs or {}
+    n_steps, walkers, burn, thin = int(n_steps), int(walkers), int(burn), int(thin)
+    if n_steps < 0:
+        raise InputError("sample_chains: n_steps must be >= 0")
+    if walkers < 1:
+        raise InputError("sample_chains: walkers must be >= 1")
+    if burn < 0:
+        raise InputError("sample_chains: burn must be >= 0")
+    if thin < 1:
+        raise InputError("sample_chains: thin must be >= 1")
+    if evaluate is not None and device:
+        raise InputError("sample_chains: an evaluate callable runs the definition route only (device=False)")
+    if evaluate is None and fit is None:
+        raise InputError("sample_chains: a fit or an evaluate callable is needed")
+    specs, block_fixed = parse_cobaya_params(params)
+    fixed_in = dict(fixed or {})
+    fixed_all = dict(block_fixed)
+    fixed_all.update(fixed_in)
+    specs = [s for s in specs if s.name not in fixed_in]
+    if not specs:
+        raise InputError("sample_chains: every parameter is fixed")
+    names = [s.name for s in specs]
+    d = len(specs)
+    arrays = sorted(k for k, v in fixed_all.items() if np.ndim(v) > 0)
+    if evaluate is None:
+        for name in names:
+            if name not in N.ROW_COLUMNS and name != "epsilon":
+                raise InputError(f"sample_chains: {name} has no column of its own in a parameter row and cannot be sampled")
+        if d > 10:
+            raise InputError("sample_chains: at most 10 sampled parameters")
+        if "epsilon" in names and np.ndim(fixed_all.get("alpha", 1)) > 0:
+            raise InputError("sample_chains: alpha must be a scalar when epsilon is sampled")
+        if arrays:
+            raise InputError(f"sample_chains: fixed values must be scalars ({arrays} are not)")
+        fit_options = fit._merged_fit(kwargs)
+        if fit_options["beta_interpolation"] == "likelihood" and not fit.fixed_data:
+            raise InputError("sample_chains: beta_interpolation 'likelihood' on a beta-dependent data vector is not supported "
+                             "(its blend of two evaluations runs on the host)")
+    elif arrays:
+        raise InputError(f"sample_chains: fixed values must be scalars ({arrays} are not)")
+    R = len(realisations) if realisations is not None else 1
+    W = walkers
+    n_chains = R * W
+    if n_chains > MAX_CHAINS:
+        raise InputError(f"sample_chains: {R} problems x {W} walkers = {n_chains} chains: at most {MAX_CHAINS}")
+    lo = np.array([s.lo for s in specs])
+    hi = np.array([s.hi for s in specs])
+
+    def per_param(what, given, default):
+        given = dict(given or {})
+        out = np.array([float(given.pop(n, dv)) for n, dv in zip(names, default)])
+        if given:
+            raise InputError(f"sample_chains: {what} names parameters that are not sampled: {sorted(given)}")
+        return out
+
+    width = per_param("proposal", proposal, [s.proposal for s in specs])
+    if np.any(~(width > 0)):
+        raise InputError(f"sample_chains: every proposal width must be > 0 ({dict(zip(names, width.tolist()))})")
+    centre = None
+    if start is not None:
+        given = dict(start.params) if hasattr(start, "params") and hasattr(start, "names") else dict(start)
+        if hasattr(start, "names"):
+            given = {n: v for n, v in given.items() if n in names}      # a BestFit also carries its fixed values
+        centre = np.empty((R, d))
+        for j, s in enumerate(specs):
+            centre[:, j] = _per_problem(f"start of {s.name}", given.pop(s.name, s.ref_loc), R)
+        if given:
+            raise InputError(f"sample_chains: start names parameters that are not sampled: {sorted(given)}")
+        bad = ~(centre >= lo) | ~(centre <= hi)
+        if np.any(bad):
+            p, j = np.argwhere(bad)[0]
+            raise InputError(f"sample_chains: the start of {names[j]} ({centre[p, j]}) of problem {p} is outside its prior "
+                             f"[{lo[j]}, {hi[j]}]")
+        spread = per_param("scatter", scatter if not np.isscalar(scatter) else {n: scatter for n in names}, width)
+        if np.any(~(spread >= 0)):
+            raise InputError("sample_chains: scatter must be >= 0")
+    elif scatter is not None:
+        raise InputError("sample_chains: scatter needs a start")
+
+    # ---- the start: the generator's first draws, as EnsembleMetropolis.initialise makes them
+    rng = np.random.default_rng(seed)
+    x0 = np.empty((n_chains, d))
+    if centre is None:
+        loc = np.array([s.ref_loc for s in specs])
+        scale = np.array([s.ref_scale for s in specs])
+        for c in range(n_chains):
+            x0[c] = _draw_start(rng, loc, scale, lo, hi, "the reference distribution")
+    else:
+        for c in range(n_chains):
+            x0[c] = _draw_start(rng, centre[c // W], spread, lo, hi, f"the scattered start of problem {c // W}")
+    which = np.repeat(np.arange(R, dtype=np.int32), W)
+    fixed_out = {k: float(v) for k, v in fixed_all.items()}
+
+    def batch_of(x):
+        batch = dict(fixed_out)
+        batch.update({n: np.ascontiguousarray(x[:, j]) for j, n in enumerate(names)})
+        return batch
+
+    handle = None
+    if evaluate is not None:
+        def evaluator(x):
+            out = evaluate(batch_of(x))
+            if isinstance(out, tuple):
+                return np.asarray(out[0], dtype=float), np.asarray(out[1], dtype=float)
+            lnl = np.asarray(out, dtype=float)
+            return lnl, -2.0 * lnl
+    elif not device:
+        if realisations is not None:
+            def evaluator(x):
+                return realisations.log_likelihood_pairs(batch_of(x), which, **kwargs)
+        else:
+            def evaluator(x):
+                return fit.log_likelihood_batch(batch_of(x), **kwargs)
+    else:
+        evaluator = None
+        model = fit._merged(kwargs)
+        fit._check_supported(model)
+        rows = np.ascontiguousarray(fit._fit_rows(batch_of(x0), model), dtype=np.float64)
+        cols = np.array([N.ROW_COLUMNS.get(n, N.VK_WALK_EPSILON) for n in names], dtype=np.int32)
+        if realisations is None:
+            eng = fit._get_engine(fit._engine_key(model), model["simpson_even"])
+            opts = eng.make_opts(model, fit_options)
+        else:
+            _, _, eng, opts = realisations._plan(kwargs)
+        lib = eng._lib
+        i32 = C.POINTER(C.c_int32)
+        err = C.create_string_buffer(512)
+        h = lib.vk_chain_create(eng._ctx, C.byref(opts), n_chains, d, cols.ctypes.data_as(i32), N.as_dp(N.f64(lo)), N.as_dp(N.f64(hi)),
+                                N.as_dp(rows), float(fixed_all.get("alpha", 1)),
+                                None if realisations is None else which.ctypes.data_as(i32), err, len(err))
+        if not h:
+            msg = err.value.decode()
+            raise (N.NativeError if "device memory" in msg else InputError)(msg)
+        handle = (lib, h)
+    ch = Chains(names, specs, fixed_out, R, W, rng, width, burn, thin, bool(keep_chain), evaluator, handle)
+    if handle:
+        ch._engine, ch._realisations = eng, realisations     # the context the handle runs on
+    if handle:
+        ch._check(handle[0].vk_chain_start(handle[1], N.as_dp(N.f64(x0))), "vk_chain_start")
+    else:
+        ch._start_host(x0)
+    return ch.extend(n_steps)
