@@ -553,7 +553,7 @@ def test_no_kernel_of_the_library_spills(lib, tmp_path):
     import subprocess
     from victor_amd.build import UNITS
     paths = _gfx950_code_objects(tmp_path)
-    assert len(paths) == len(UNITS) == 7                    # one code object per translation unit with device code
+    assert len(paths) == len(UNITS) == 8                    # one code object per translation unit with device code
     notes = "".join(subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-readelf", "--notes", co], capture_output=True, text=True).stdout
                     for co in paths)
     kernels = re.findall(r"\.name:\s+(\S+)[\s\S]*?\.private_segment_fixed_size:\s+(\d+)[\s\S]*?\.vgpr_count:\s+(\d+)", notes)

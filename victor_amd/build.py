@@ -3,6 +3,7 @@ library with the host compiler, every unit side by side, linked into one library
 
 hipcc (device code; ``vk_instances.h`` names which kernel instantiation lives in which unit):
 ``victor_hip.hip``           the launch side of the C ABI (context, table upload, kernel selection), the chi-square kernels;
+``vk_sampled.hip``           ``vk_fit_*`` and ``vk_chain_*``: best fits and Metropolis chains stepped on the device, their kernels;
 ``vk_cells_streaming.hip``   the cells kernel's instantiations for the streaming model (the kernels of the headline
                          metric and of the BOSS configuration), compiled with LLVM's ``iterative-ilp`` machine scheduler: it
                          interleaves the independent chains of the node loop and fills the hazard slots the default
@@ -32,9 +33,9 @@ CSRC = os.path.join(HERE, "csrc")
 SRC = os.path.join(CSRC, "victor_hip.hip")
 ILP = ("-mllvm", "-amdgpu-sched-strategy=iterative-ilp")
 # (source, extra flags, takes the flavour's defines): only victor_hip.hip depends on VK_DEV_LANES
-UNITS = (("victor_hip.hip", (), True), ("vk_cells_streaming.hip", ILP, False), ("vk_cells_dispersion.hip", (), False),
-         ("vk_cells_kaiser.hip", (), False), ("vk_fast_streaming.hip", (), False), ("vk_fast_dispersion.hip", (), False),
-         ("vk_generic.hip", (), False))
+UNITS = (("victor_hip.hip", (), True), ("vk_sampled.hip", (), False), ("vk_cells_streaming.hip", ILP, False),
+         ("vk_cells_dispersion.hip", (), False), ("vk_cells_kaiser.hip", (), False), ("vk_fast_streaming.hip", (), False),
+         ("vk_fast_dispersion.hip", (), False), ("vk_generic.hip", (), False))
 HOST_UNITS = ("vk_ledger.cpp", "vk_walk.cpp", "vk_serve.cpp", "vk_rccl.cpp")
 HOST_FLAGS = ("-O2", "-std=c++17", "-fPIC", "-Wall", "-Wno-invalid-offsetof", "-D__HIP_PLATFORM_AMD__")   # (the define: HIP's headers under a compiler that is not hipcc)
 OBJ = os.path.join(CSRC, "obj")

@@ -34,7 +34,8 @@ import ctypes as C
 import numpy as np
 
 from . import _native as N
-from .sampler import EnsembleMetropolis, gelman_rubin, parse_cobaya_params
+from .fitting import _Sampled
+from .sampler import EnsembleMetropolis, gelman_rubin
 from .utils import InputError
 
 BLOCK = EnsembleMetropolis.BLOCK
@@ -264,15 +265,6 @@ class Chains:
                     self.rhat = np.stack([gelman_rubin(self.chain[:, r]) for r in range(R)])
 
 
-def _per_problem(name, v, R):
-    a = np.asarray(v, dtype=float)
-    if a.ndim == 0:
-        return np.full(R, float(a))
-    if a.shape != (R,):
-        raise InputError(f"sample_chains: {name}: one value per problem ({R}) or a scalar")
-    return a
-
-
 def _draw_start(rng, loc, scale, lo, hi, what):
     """One start as ``EnsembleMetropolis.initialise`` draws it: redrawn until inside the box."""
     for _ in range(1000):
@@ -309,48 +301,24 @@ def sample_chains(fit, params, n_steps, walkers=8, seed=0, fixed=None, start=Non
         raise InputError("sample_chains: an evaluate callable runs the definition route only (device=False)")
     if evaluate is None and fit is None:
         raise InputError("sample_chains: a fit or an evaluate callable is needed")
-    specs, block_fixed = parse_cobaya_params(params)
-    fixed_in = dict(fixed or {})
-    fixed_all = dict(block_fixed)
-    fixed_all.update(fixed_in)
-    specs = [s for s in specs if s.name not in fixed_in]
-    if not specs:
-        raise InputError("sample_chains: every parameter is fixed")
-    names = [s.name for s in specs]
-    d = len(specs)
+    q = _Sampled("sample_chains", "sampled", params, fixed)
+    specs, names, fixed_all, lo, hi, d = q.specs, q.names, q.fixed_all, q.lo, q.hi, len(q.names)
     arrays = sorted(k for k, v in fixed_all.items() if np.ndim(v) > 0)
     if evaluate is None:
-        for name in names:
-            if name not in N.ROW_COLUMNS and name != "epsilon":
-                raise InputError(f"sample_chains: {name} has no column of its own in a parameter row and cannot be sampled")
+        q.check_columns()
         if d > 10:
             raise InputError("sample_chains: at most 10 sampled parameters")
-        if "epsilon" in names and np.ndim(fixed_all.get("alpha", 1)) > 0:
-            raise InputError("sample_chains: alpha must be a scalar when epsilon is sampled")
-        if arrays:
-            raise InputError(f"sample_chains: fixed values must be scalars ({arrays} are not)")
-        fit_options = fit._merged_fit(kwargs)
-        if fit_options["beta_interpolation"] == "likelihood" and not fit.fixed_data:
-            raise InputError("sample_chains: beta_interpolation 'likelihood' on a beta-dependent data vector is not supported "
-                             "(its blend of two evaluations runs on the host)")
-    elif arrays:
+        q.check_alpha()
+    if arrays:
         raise InputError(f"sample_chains: fixed values must be scalars ({arrays} are not)")
+    if evaluate is None:
+        fit_options = q.fit_options(fit, kwargs)
     R = len(realisations) if realisations is not None else 1
     W = walkers
     n_chains = R * W
     if n_chains > MAX_CHAINS:
         raise InputError(f"sample_chains: {R} problems x {W} walkers = {n_chains} chains: at most {MAX_CHAINS}")
-    lo = np.array([s.lo for s in specs])
-    hi = np.array([s.hi for s in specs])
-
-    def per_param(what, given, default):
-        given = dict(given or {})
-        out = np.array([float(given.pop(n, dv)) for n, dv in zip(names, default)])
-        if given:
-            raise InputError(f"sample_chains: {what} names parameters that are not sampled: {sorted(given)}")
-        return out
-
-    width = per_param("proposal", proposal, [s.proposal for s in specs])
+    width = q.per_param("proposal", proposal, [s.proposal for s in specs])
     if np.any(~(width > 0)):
         raise InputError(f"sample_chains: every proposal width must be > 0 ({dict(zip(names, width.tolist()))})")
     centre = None
@@ -358,17 +326,8 @@ def sample_chains(fit, params, n_steps, walkers=8, seed=0, fixed=None, start=Non
         given = dict(start.params) if hasattr(start, "params") and hasattr(start, "names") else dict(start)
         if hasattr(start, "names"):
             given = {n: v for n, v in given.items() if n in names}      # a BestFit also carries its fixed values
-        centre = np.empty((R, d))
-        for j, s in enumerate(specs):
-            centre[:, j] = _per_problem(f"start of {s.name}", given.pop(s.name, s.ref_loc), R)
-        if given:
-            raise InputError(f"sample_chains: start names parameters that are not sampled: {sorted(given)}")
-        bad = ~(centre >= lo) | ~(centre <= hi)
-        if np.any(bad):
-            p, j = np.argwhere(bad)[0]
-            raise InputError(f"sample_chains: the start of {names[j]} ({centre[p, j]}) of problem {p} is outside its prior "
-                             f"[{lo[j]}, {hi[j]}]")
-        spread = per_param("scatter", scatter if not np.isscalar(scatter) else {n: scatter for n in names}, width)
+        centre = q.starts(given, R, "sample_chains: ")
+        spread = q.per_param("scatter", scatter if not np.isscalar(scatter) else {n: scatter for n in names}, width)
         if np.any(~(spread >= 0)):
             raise InputError("sample_chains: scatter must be >= 0")
     elif scatter is not None:
@@ -410,25 +369,8 @@ def sample_chains(fit, params, n_steps, walkers=8, seed=0, fixed=None, start=Non
                 return fit.log_likelihood_batch(batch_of(x), **kwargs)
     else:
         evaluator = None
-        model = fit._merged(kwargs)
-        fit._check_supported(model)
-        rows = np.ascontiguousarray(fit._fit_rows(batch_of(x0), model), dtype=np.float64)
-        cols = np.array([N.ROW_COLUMNS.get(n, N.VK_WALK_EPSILON) for n in names], dtype=np.int32)
-        if realisations is None:
-            eng = fit._get_engine(fit._engine_key(model), model["simpson_even"])
-            opts = eng.make_opts(model, fit_options)
-        else:
-            _, _, eng, opts = realisations._plan(kwargs)
-        lib = eng._lib
-        i32 = C.POINTER(C.c_int32)
-        err = C.create_string_buffer(512)
-        h = lib.vk_chain_create(eng._ctx, C.byref(opts), n_chains, d, cols.ctypes.data_as(i32), N.as_dp(N.f64(lo)), N.as_dp(N.f64(hi)),
-                                N.as_dp(rows), float(fixed_all.get("alpha", 1)),
-                                None if realisations is None else which.ctypes.data_as(i32), err, len(err))
-        if not h:
-            msg = err.value.decode()
-            raise (N.NativeError if "device memory" in msg else InputError)(msg)
-        handle = (lib, h)
+        eng, h = q.create("vk_chain_create", fit, realisations, kwargs, fit_options, batch_of(x0), which)
+        handle = (eng._lib, h)
     ch = Chains(names, specs, fixed_out, R, W, rng, width, burn, thin, bool(keep_chain), evaluator, handle)
     if handle:
         ch._engine, ch._realisations = eng, realisations     # the context the handle runs on

@@ -1,8 +1,9 @@
 // victor_hip.hip - the launch side of libvictor_hip.so: context, table upload, kernel selection, the evaluating entry points of
-// the C ABI (include/victor_hip.h).  The host-only parts of the library are translation units of their own, compiled by the host
-// compiler (vk_host.h is what they share with this file): vk_ledger.cpp (the polling hand-off's launch rule and the device-wide
-// ledger of reserved waiters), vk_walk.cpp (vk_walk_*: the walkers' step loop), vk_serve.cpp (vk_serve_mailboxes), vk_rccl.cpp
-// (vk_comm_*: RCCL through dlopen).
+// the C ABI (include/victor_hip.h).  The drivers that step best fits and Metropolis chains on the device (vk_fit_*, vk_chain_*)
+// are a unit of their own with their kernels, vk_sampled.hip.  The host-only parts of the library are units of their own as
+// well, compiled by the host compiler (vk_host.h is what they share with this file): vk_ledger.cpp (the polling hand-off's
+// launch rule and the device-wide ledger of reserved waiters), vk_walk.cpp (vk_walk_*: the walkers' step loop), vk_serve.cpp
+// (vk_serve_mailboxes), vk_rccl.cpp (vk_comm_*: RCCL through dlopen).
 //
 // Device code lives in the headers next to this file:
 //   vk_common.h          argument structs, LDS table evaluation, per-point scalars (AP factors, growth amplitudes)
@@ -18,10 +19,6 @@
 //                        16 points per workgroup, the precision streamed from L2
 //   vk_kernel_joint_real.h  the same against many realisations of every block (vk_joint_cov_eval_realisations): rows are
 //                        (point, realisation) pairs, 16 realisations of one point per workgroup
-//   vk_kernel_fit.h      the best-fit search (vk_fit_run): start simplex, step and re-layout kernels, one thread per problem, over
-//                        the one-problem transition of vk_fit_simplex.h (plain C++, also compiled on its own by the CPU tests)
-//   vk_kernel_chain.h    Metropolis chains of the data vector or one realisation each (vk_chain_begin): start, propose and step
-//                        kernels, one thread per chain, over the one-chain transition of vk_chain_step.h (plain C++, likewise)
 //
 // K1 restates CCFModel.theory_xi (streaming branch victor/ccf_model.py:589-690; the other branches :658-784),
 // theory_multipoles (:816-825) and utils.multipoles_from_fn (victor/utils.py:45-56); K2 restates CCFFit.chi_squared
@@ -61,8 +58,6 @@
 #include "vk_kernel_real.h"
 #include "vk_kernel_joint.h"
 #include "vk_kernel_joint_real.h"
-#include "vk_kernel_fit.h"
-#include "vk_kernel_chain.h"
 
 // The theory kernels' instantiations are generated in translation units of their own (vk_instances.h names what lives where);
 // here they are declared only.
@@ -141,7 +136,9 @@ __global__ void vk_init_stage_kernel(const double* mu, const double* w_ell, int 
 // host side
 // ==================================================================================================
 using vkh::check_opts;
+using vkh::check_real_lds;
 using vkh::cpu_relax;
+using vkh::enqueue_realisations;
 using vkh::fail;
 using vkh::host_scratch;
 using vkh::HostScratch;
@@ -1606,7 +1603,7 @@ struct RealChunks {
 };
 
 // The realisation kernel keeps a point's precision, theory vector and a tile of residuals in LDS: refused above 160 KiB.
-static int check_real_lds(vk_ctx* ctx) {
+int vkh::check_real_lds(vk_ctx* ctx) {
   const size_t lds = real_lds_doubles(ctx->N) * sizeof(double);
   if (lds > 160 * 1024)
     return fail(ctx, VK_E_ARG, "data vector of %d bins needs %zu bytes of LDS for the realisation kernel (> 160 KiB)", ctx->N, lds);
@@ -1616,9 +1613,9 @@ static int check_real_lds(vk_ctx* ctx) {
 // Enqueue on ctx's stream: the theory vectors of m device rows d_par into the workspace d_th, then the realisation chi-square
 // kernel behind them - every point against every realisation (d_which NULL: outputs [m][n_real]) or point i against realisation
 // d_which[i] (pairs mode, indices in device memory: outputs [m]).  The caller has checked the LDS limit (check_real_lds) and the
-// indices.  Shared by vk_eval_realisations and the best-fit loop (vk_fit_run).
-static int enqueue_realisations(vk_ctx* ctx, const vk_eval_opts* opts, const double* d_par, long long m, double* d_th, double* d_lnl,
-                                double* d_chi, const int32_t* d_which) {
+// indices.  Shared by vk_eval_realisations and the best fits and chains of vk_sampled.hip.
+int vkh::enqueue_realisations(vk_ctx* ctx, const vk_eval_opts* opts, const double* d_par, long long m, double* d_th, double* d_lnl,
+                              double* d_chi, const int32_t* d_which) {
   const bool timed = ctx->timing;
   if (timed) {
     harvest_timing(ctx);
@@ -2274,610 +2271,6 @@ int vk_joint_cov_eval_realisations(vk_joint_cov* h, vk_ctx* const* ctxs, int32_t
     const long long tiles = which ? (m + kJointRows - 1) / kJointRows : m * ((n_real + kJointRows - 1) / kJointRows);
     return joint_chi2(h, ctxs, n_ctx, e, "joint_real_chi2", vk_joint_real_chi2_kernel, tiles, lds, jr);
   });
-}
-
-}  // extern "C"
-
-// ---- best fits: bounded Nelder-Mead, one simplex per problem, one launch per iteration (include/victor_hip.h, vk_kernel_fit.h) --
-// An iteration enqueues, on the context's stream, the evaluation of the active problems' S rows each (the fit's own data
-// vector: vk_eval_batch_device_async with lnL / chi2, so the fused tail applies; realisations: enqueue_realisations in pairs
-// mode) and the step kernel behind it - no host synchronisation and no graph inside an iteration.  Every kFitCheck iterations
-// the host reads the status words, keeps the problems still running (in problem order) and lays their rows out again, so a
-// finished problem stops costing evaluations and which rows share a launch does not depend on timing.
-constexpr int kFitCheck = 8;
-constexpr int kFitMaxProblems = 65536;
-
-struct vk_fit {
-  vk_ctx* ctx = nullptr;
-  vk_eval_opts opts{};
-  int R = 0, P = 0, S = 0;
-  int col[vkfit::kMaxP] = {};
-  double alpha = 1.0;
-  double lo[vkfit::kMaxP] = {}, hi[vkfit::kMaxP] = {};
-  bool real = false;
-  int max_which = -1;
-  void* d_mem = nullptr;                   // one allocation holding everything below
-  vkfit::State* d_state = nullptr;         // [R]
-  double *d_base = nullptr, *d_x0 = nullptr, *d_rows = nullptr, *d_lnl = nullptr, *d_chi = nullptr, *d_th = nullptr;
-  int *d_active = nullptr, *d_row_which = nullptr, *d_which = nullptr, *d_status = nullptr;
-  std::string err;
-};
-
-static int fit_launch(vk_ctx* ctx, void (*kern)(FitArgs), const FitArgs& a) {
-  hipLaunchKernelGGL(kern, dim3((unsigned)((a.n_active + kFitBlock - 1) / kFitBlock)), dim3(kFitBlock), 0, ctx->stream, a);
-  VK_HIP(ctx, hipGetLastError());
-  return VK_OK;
-}
-
-// the loop of vk_fit_run; errors are reported through ctx->err
-static int fit_loop(vk_fit* f, const vkfit::Params& q, const double* x0, std::vector<vkfit::State>* out) {
-  vk_ctx* ctx = f->ctx;
-  const int R = f->R, S = f->S;
-  VK_HIP(ctx, hipSetDevice(ctx->device));
-  std::vector<int> act(R), status(R);
-  for (int p = 0; p < R; ++p) act[p] = p;
-  VK_HIP(ctx, hipMemcpyAsync(f->d_x0, x0, (size_t)R * f->P * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  VK_HIP(ctx, hipMemcpyAsync(f->d_active, act.data(), (size_t)R * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-  FitArgs a{};
-  a.q = q;
-  a.state = f->d_state;
-  a.base = f->d_base;
-  a.x0 = f->d_x0;
-  a.active = f->d_active;
-  a.n_active = R;
-  a.lnl = f->d_lnl;
-  a.chi2 = f->d_chi;
-  a.rows = f->d_rows;
-  a.row_which = f->real ? f->d_row_which : nullptr;
-  a.which = f->real ? f->d_which : nullptr;
-  a.status = f->d_status;
-  for (int j = 0; j < vkfit::kMaxP; ++j) a.col[j] = f->col[j];
-  a.alpha = f->alpha;
-  int rc = fit_launch(ctx, vk_fit_init_kernel, a);
-  while (rc == VK_OK) {
-    const long long n_rows = (long long)a.n_active * S;
-    for (int t = 0; t < kFitCheck && rc == VK_OK; ++t) {
-      rc = f->real ? enqueue_realisations(ctx, &f->opts, f->d_rows, n_rows, f->d_th, f->d_lnl, f->d_chi, f->d_row_which)
-                   : vk_eval_batch_device_async(ctx, &f->opts, f->d_rows, n_rows, f->d_lnl, f->d_chi, f->d_th);
-      if (rc == VK_OK) rc = fit_launch(ctx, vk_fit_step_kernel, a);
-    }
-    if (rc) return rc;
-    VK_HIP(ctx, hipMemcpyAsync(status.data(), f->d_status, (size_t)R * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    VK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    std::vector<int> next;
-    for (int p : act)
-      if (status[p] < 0) next.push_back(p);
-    if (next.empty()) break;
-    if ((int)next.size() < a.n_active) {
-      act.swap(next);
-      a.n_active = (int)act.size();
-      VK_HIP(ctx, hipMemcpyAsync(f->d_active, act.data(), act.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-      rc = fit_launch(ctx, vk_fit_emit_kernel, a);
-    }
-  }
-  if (rc) return rc;
-  out->resize(R);
-  VK_HIP(ctx, hipMemcpy(out->data(), f->d_state, (size_t)R * sizeof(vkfit::State), hipMemcpyDeviceToHost));
-  return VK_OK;
-}
-
-extern "C" {
-
-vk_fit* vk_fit_create(vk_ctx* ctx, const vk_eval_opts* opts, int32_t n_problems, int32_t n_params, const int32_t* columns,
-                      const double* lo, const double* hi, const double* base_rows, double alpha, const int32_t* which, char* err,
-                      size_t errlen) {
-  auto bail = [&](const std::string& msg) -> vk_fit* {
-    if (err && errlen) {
-      strncpy(err, msg.c_str(), errlen - 1);
-      err[errlen - 1] = 0;
-    }
-    return nullptr;
-  };
-  if (!ctx || !opts || !columns || !lo || !hi || !base_rows) return bail("vk_fit_create: NULL argument");
-  if (n_problems < 1 || n_problems > kFitMaxProblems) return bail("vk_fit_create: need 1 <= problems <= 65536");
-  if (n_params < 1 || n_params > vkfit::kMaxP)
-    return bail("vk_fit_create: need 1 <= parameters <= 10 (the row columns other than aperp / apar / epsilon, and epsilon)");
-  sync_knobs(ctx);
-  if (check_opts(ctx, opts) != VK_OK) return bail(ctx->err);
-  if (!ctx->d_data) return bail("vk_fit_create: context was created without a data vector");
-  bool used[VK_NPAR] = {};
-  int n_eps = 0;
-  for (int j = 0; j < n_params; ++j) {
-    const int c = columns[j];
-    if (c == VK_WALK_EPSILON) {
-      ++n_eps;
-    } else if (c < 0 || c >= VK_NPAR || (c >= VK_P_APERP && c <= VK_P_EPSILON) || used[c]) {
-      return bail("vk_fit_create: a sampled parameter must name a row column other than aperp / apar / epsilon, or VK_WALK_EPSILON, once");
-    } else {
-      used[c] = true;
-    }
-    if (!(hi[j] > lo[j])) return bail("vk_fit_create: the prior box needs lo < hi");
-  }
-  if (n_eps > 1) return bail("vk_fit_create: epsilon sampled twice");
-  int max_which = -1;
-  if (which)
-    for (int i = 0; i < n_problems; ++i) {
-      if (which[i] < 0 || which[i] >= ctx->n_real)
-        return bail("vk_fit_create: realisation index " + std::to_string(which[i]) + " of problem " + std::to_string(i) +
-                    " is outside 0.." + std::to_string(ctx->n_real - 1));
-      max_which = std::max(max_which, (int)which[i]);
-    }
-  vk_fit* f = new (std::nothrow) vk_fit();
-  if (!f) return bail("out of memory");
-  f->ctx = ctx;
-  f->opts = *opts;
-  f->R = n_problems;
-  f->P = n_params;
-  f->S = vkfit::slots(n_params);
-  for (int j = 0; j < n_params; ++j) {
-    f->col[j] = columns[j];
-    f->lo[j] = lo[j];
-    f->hi[j] = hi[j];
-  }
-  f->alpha = alpha;
-  f->real = which != nullptr;
-  f->max_which = max_which;
-  const size_t R = n_problems, RS = R * f->S;
-  const size_t doubles = R * VK_NPAR + R * n_params + RS * VK_NPAR + 2 * RS + RS * ctx->N;
-  const size_t ints = R + RS + R + R;
-  const size_t bytes = R * sizeof(vkfit::State) + doubles * sizeof(double) + ints * sizeof(int);
-  if (hipSetDevice(ctx->device) != hipSuccess || hipMalloc(&f->d_mem, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    delete f;
-    return bail("vk_fit_create: cannot allocate " + std::to_string(bytes) + " bytes of device memory");
-  }
-  char* m = static_cast<char*>(f->d_mem);
-  f->d_state = reinterpret_cast<vkfit::State*>(m);
-  double* d = reinterpret_cast<double*>(m + R * sizeof(vkfit::State));
-  f->d_base = d;
-  f->d_x0 = f->d_base + R * VK_NPAR;
-  f->d_rows = f->d_x0 + R * n_params;
-  f->d_lnl = f->d_rows + RS * VK_NPAR;
-  f->d_chi = f->d_lnl + RS;
-  f->d_th = f->d_chi + RS;
-  int* i = reinterpret_cast<int*>(f->d_th + RS * ctx->N);
-  f->d_active = i;
-  f->d_row_which = f->d_active + R;
-  f->d_which = f->d_row_which + RS;
-  f->d_status = f->d_which + R;
-  bool ok = hipMemcpy(f->d_base, base_rows, R * VK_NPAR * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
-  if (ok && which) ok = hipMemcpy(f->d_which, which, R * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
-  if (!ok) {
-    (void)hipGetLastError();
-    vk_fit_destroy(f);
-    return bail("vk_fit_create: upload failed");
-  }
-  return f;
-}
-
-const char* vk_fit_last_error(const vk_fit* f) { return f ? f->err.c_str() : ""; }
-
-void vk_fit_destroy(vk_fit* f) {
-  if (!f) return;
-  if (f->d_mem) {
-    (void)hipSetDevice(f->ctx->device);
-    (void)hipFree(f->d_mem);
-  }
-  delete f;
-}
-
-int vk_fit_run(vk_fit* f, const double* x0, const double* step, const double* xtol, double ftol, int32_t max_iter, int32_t restarts,
-               double* x, double* lnl, double* chi2, int32_t* status, int32_t* n_iter, int64_t* n_evals) {
-  if (!f) return VK_E_ARG;
-  vk_ctx* ctx = f->ctx;
-  auto refuse = [&](const std::string& msg) {
-    f->err = msg;
-    return VK_E_ARG;
-  };
-  if (!x0 || !step || !xtol || !x || !lnl || !chi2 || !status || !n_iter || !n_evals) return refuse("vk_fit_run: NULL argument");
-  if (ctx->begun_n != 0) return refuse("vk_fit_run: a batch begun with vk_eval_batch_begin is awaiting vk_eval_batch_finish on the context");
-  if (f->real) {
-    if (ctx->n_real <= 0 || !ctx->d_real) return refuse("vk_fit_run: no realisations are set on the context (vk_set_realisations)");
-    if (f->max_which >= ctx->n_real)
-      return refuse("vk_fit_run: the context holds " + std::to_string(ctx->n_real) + " realisations, a problem asks for number " +
-                    std::to_string(f->max_which));
-    if (check_real_lds(ctx) != VK_OK) return refuse(ctx->err);
-  }
-  if (max_iter < 1 || restarts < 0 || !(ftol >= 0)) return refuse("vk_fit_run: need max_iter >= 1, restarts >= 0, ftol >= 0");
-  vkfit::Params q{};
-  q.d = f->P;
-  q.S = f->S;
-  q.max_iter = max_iter;
-  q.restarts = restarts;
-  q.ftol = ftol;
-  for (int j = 0; j < f->P; ++j) {
-    if (!(step[j] > 0) || !(xtol[j] >= 0)) return refuse("vk_fit_run: parameter " + std::to_string(j) + " needs step > 0 and xtol >= 0");
-    q.lo[j] = f->lo[j];
-    q.hi[j] = f->hi[j];
-    q.step[j] = step[j];
-    q.xtol[j] = xtol[j];
-  }
-  for (int p = 0; p < f->R; ++p)
-    if (!vkfit::in_box(q, x0 + (size_t)p * f->P)) return refuse("vk_fit_run: the start of problem " + std::to_string(p) + " is outside the box");
-  std::vector<vkfit::State> st;
-  const int rc = fit_loop(f, q, x0, &st);
-  if (rc != VK_OK) {
-    f->err = ctx->err;
-    (void)hipStreamSynchronize(ctx->stream);          // nothing stays in flight
-    (void)hipGetLastError();
-    return rc;
-  }
-  for (int p = 0; p < f->R; ++p) {
-    const vkfit::State& s = st[p];
-    for (int j = 0; j < f->P; ++j) x[(size_t)p * f->P + j] = s.v[0][j];
-    lnl[p] = -s.f[0];
-    chi2[p] = s.chi[0];
-    status[p] = s.status;
-    n_iter[p] = s.iter;
-    n_evals[p] = s.n_evals;
-  }
-  f->err.clear();
-  return VK_OK;
-}
-
-}  // extern "C"
-
-// ---- Metropolis chains: one chain per thread, one launch per step (include/victor_hip.h, vk_kernel_chain.h) ------------------
-// A step enqueues, on the context's stream, the evaluation of the C chains' rows (the fit's own data vector:
-// vk_eval_batch_device_async with lnL / chi2; realisations: enqueue_realisations in pairs mode - the launches fit_loop makes) and
-// the step kernel behind it, which decides and writes the next rows.  No host synchronisation and no graph inside a block of up
-// to 64 steps: vk_chain_begin uploads the block's random numbers and enqueues all of it, vk_chain_finish waits and brings the
-// block's kept steps home, and the host draws the next block's numbers in between.
-constexpr int kChainMax = 65536;
-
-struct vk_chain {
-  vk_ctx* ctx = nullptr;
-  vk_eval_opts opts{};
-  int C = 0, P = 0, T = 0;                 // chains, sampled parameters, entries of a packed second-moment triangle
-  vkchain::Box box{};
-  int col[vkchain::kMaxP] = {};
-  double alpha = 1.0;
-  bool real = false;
-  int max_which = -1;
-  bool started = false;
-  int in_flight = 0;                       // steps of the block begun and not finished
-  int block_kept = 0;                      // history slots the block in flight fills (0 without a history)
-  void* d_mem = nullptr;                   // one allocation holding everything below
-  double *d_x = nullptr, *d_lnl = nullptr, *d_chi = nullptr, *d_pivot = nullptr, *d_sum1 = nullptr, *d_sum2 = nullptr;
-  double *d_base = nullptr, *d_x0 = nullptr, *d_rows = nullptr, *d_res_lnl = nullptr, *d_res_chi = nullptr, *d_th = nullptr;
-  double *d_dz = nullptr, *d_logu = nullptr, *d_hx = nullptr, *d_hl = nullptr, *d_hc = nullptr;
-  long long *d_acc = nullptr, *d_steps = nullptr, *d_kept = nullptr;
-  int *d_which = nullptr, *d_row_which = nullptr;
-  std::string err;
-};
-
-static int chain_launch(vk_ctx* ctx, void (*kern)(ChainArgs), const ChainArgs& a) {
-  hipLaunchKernelGGL(kern, dim3((unsigned)((a.C + kChainBlock - 1) / kChainBlock)), dim3(kChainBlock), 0, ctx->stream, a);
-  VK_HIP(ctx, hipGetLastError());
-  return VK_OK;
-}
-
-static ChainArgs chain_args(const vk_chain* f) {
-  ChainArgs a{};
-  a.box = f->box;
-  a.C = f->C;
-  a.x = f->d_x;
-  a.lnl = f->d_lnl;
-  a.chi2 = f->d_chi;
-  a.pivot = f->d_pivot;
-  a.sum1 = f->d_sum1;
-  a.sum2 = f->d_sum2;
-  a.n_accept = f->d_acc;
-  a.n_steps = f->d_steps;
-  a.n_kept = f->d_kept;
-  a.base = f->d_base;
-  a.which = f->real ? f->d_which : nullptr;
-  a.x0 = f->d_x0;
-  a.res_lnl = f->d_res_lnl;
-  a.res_chi2 = f->d_res_chi;
-  a.rows = f->d_rows;
-  a.row_which = f->real ? f->d_row_which : nullptr;
-  for (int j = 0; j < vkchain::kMaxP; ++j) a.col[j] = f->col[j];
-  a.alpha = f->alpha;
-  return a;
-}
-
-// the evaluation of the C pending rows into d_res_lnl / d_res_chi, on the context's stream
-static int chain_evaluate(vk_chain* f) {
-  return f->real ? enqueue_realisations(f->ctx, &f->opts, f->d_rows, f->C, f->d_th, f->d_res_lnl, f->d_res_chi, f->d_row_which)
-                 : vk_eval_batch_device_async(f->ctx, &f->opts, f->d_rows, f->C, f->d_res_lnl, f->d_res_chi, f->d_th);
-}
-
-// what every call that touches the context checks first
-static int chain_ready(vk_chain* f, const char* who) {
-  vk_ctx* ctx = f->ctx;
-  auto refuse = [&](const std::string& msg) {
-    f->err = std::string(who) + ": " + msg;
-    return VK_E_ARG;
-  };
-  if (ctx->begun_n != 0) return refuse("a batch begun with vk_eval_batch_begin is awaiting vk_eval_batch_finish on the context");
-  if (f->real) {
-    if (ctx->n_real <= 0 || !ctx->d_real) return refuse("no realisations are set on the context (vk_set_realisations)");
-    if (f->max_which >= ctx->n_real)
-      return refuse("the context holds " + std::to_string(ctx->n_real) + " realisations, a chain asks for number " +
-                    std::to_string(f->max_which));
-    if (check_real_lds(ctx) != VK_OK) return refuse(ctx->err);
-  }
-  return VK_OK;
-}
-
-// an error after something was enqueued: report it, leave nothing in flight
-static int chain_abort(vk_chain* f, int rc) {
-  f->err = f->ctx->err;
-  (void)hipStreamSynchronize(f->ctx->stream);
-  (void)hipGetLastError();
-  f->in_flight = 0;
-  f->block_kept = 0;
-  return rc;
-}
-
-// a HIP call on behalf of a chain handle: the error text goes to the handle (vk_chain_last_error)
-#define VK_CHAIN_HIP(f, call)                                                          \
-  do {                                                                                 \
-    hipError_t e_ = (call);                                                            \
-    if (e_ != hipSuccess) {                                                            \
-      (f)->err = std::string(#call " failed: ") + hipGetErrorString(e_);               \
-      return VK_E_HIP;                                                                 \
-    }                                                                                  \
-  } while (0)
-
-extern "C" {
-
-vk_chain* vk_chain_create(vk_ctx* ctx, const vk_eval_opts* opts, int32_t n_chains, int32_t n_params, const int32_t* columns,
-                          const double* lo, const double* hi, const double* base_rows, double alpha, const int32_t* which, char* err,
-                          size_t errlen) {
-  auto bail = [&](const std::string& msg) -> vk_chain* {
-    if (err && errlen) {
-      strncpy(err, msg.c_str(), errlen - 1);
-      err[errlen - 1] = 0;
-    }
-    return nullptr;
-  };
-  if (!ctx || !opts || !columns || !lo || !hi || !base_rows) return bail("vk_chain_create: NULL argument");
-  if (n_chains < 1 || n_chains > kChainMax) return bail("vk_chain_create: need 1 <= chains <= 65536");
-  if (n_params < 1 || n_params > vkchain::kMaxP)
-    return bail("vk_chain_create: need 1 <= parameters <= 10 (the row columns other than aperp / apar / epsilon, and epsilon)");
-  sync_knobs(ctx);
-  if (check_opts(ctx, opts) != VK_OK) return bail(ctx->err);
-  if (!ctx->d_data) return bail("vk_chain_create: context was created without a data vector");
-  bool used[VK_NPAR] = {};
-  int n_eps = 0;
-  for (int j = 0; j < n_params; ++j) {
-    const int c = columns[j];
-    if (c == VK_WALK_EPSILON) {
-      ++n_eps;
-    } else if (c < 0 || c >= VK_NPAR || (c >= VK_P_APERP && c <= VK_P_EPSILON) || used[c]) {
-      return bail("vk_chain_create: a sampled parameter must name a row column other than aperp / apar / epsilon, or VK_WALK_EPSILON, once");
-    } else {
-      used[c] = true;
-    }
-    if (!(hi[j] > lo[j])) return bail("vk_chain_create: the prior box needs lo < hi");
-  }
-  if (n_eps > 1) return bail("vk_chain_create: epsilon sampled twice");
-  int max_which = -1;
-  if (which)
-    for (int i = 0; i < n_chains; ++i) {
-      if (which[i] < 0 || which[i] >= ctx->n_real)
-        return bail("vk_chain_create: realisation index " + std::to_string(which[i]) + " of chain " + std::to_string(i) +
-                    " is outside 0.." + std::to_string(ctx->n_real - 1));
-      max_which = std::max(max_which, (int)which[i]);
-    }
-  vk_chain* f = new (std::nothrow) vk_chain();
-  if (!f) return bail("out of memory");
-  f->ctx = ctx;
-  f->opts = *opts;
-  f->C = n_chains;
-  f->P = n_params;
-  f->T = vkchain::n_tri(n_params);
-  f->box.d = n_params;
-  for (int j = 0; j < n_params; ++j) {
-    f->col[j] = columns[j];
-    f->box.lo[j] = lo[j];
-    f->box.hi[j] = hi[j];
-  }
-  f->alpha = alpha;
-  f->real = which != nullptr;
-  f->max_which = max_which;
-  const size_t C = n_chains, P = n_params, T = f->T, B = vkchain::kBlock;
-  // state | base, x0, rows, results, theory workspace | one block of random numbers | one block of history | counters | indices
-  const size_t doubles = C * (P + 2 + P + P + T) + C * (2 * VK_NPAR + P + 2 + (size_t)ctx->N) + B * C * (P + 1) + B * C * (P + 2);
-  const size_t bytes = doubles * sizeof(double) + 3 * C * sizeof(long long) + 2 * C * sizeof(int);
-  if (hipSetDevice(ctx->device) != hipSuccess || hipMalloc(&f->d_mem, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    delete f;
-    return bail("vk_chain_create: cannot allocate " + std::to_string(bytes) + " bytes of device memory");
-  }
-  double* d = static_cast<double*>(f->d_mem);
-  auto take = [&](size_t n) {
-    double* p = d;
-    d += n;
-    return p;
-  };
-  f->d_x = take(C * P);
-  f->d_lnl = take(C);
-  f->d_chi = take(C);
-  f->d_pivot = take(C * P);
-  f->d_sum1 = take(C * P);
-  f->d_sum2 = take(C * T);
-  f->d_base = take(C * VK_NPAR);
-  f->d_x0 = take(C * P);
-  f->d_rows = take(C * VK_NPAR);
-  f->d_res_lnl = take(C);
-  f->d_res_chi = take(C);
-  f->d_th = take(C * ctx->N);
-  f->d_dz = take(B * C * P);
-  f->d_logu = take(B * C);
-  f->d_hx = take(B * C * P);
-  f->d_hl = take(B * C);
-  f->d_hc = take(B * C);
-  f->d_acc = reinterpret_cast<long long*>(d);
-  f->d_steps = f->d_acc + C;
-  f->d_kept = f->d_steps + C;
-  f->d_which = reinterpret_cast<int*>(f->d_kept + C);
-  f->d_row_which = f->d_which + C;
-  bool ok = hipMemcpy(f->d_base, base_rows, C * VK_NPAR * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
-  if (ok && which) ok = hipMemcpy(f->d_which, which, C * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
-  if (!ok) {
-    (void)hipGetLastError();
-    vk_chain_destroy(f);
-    return bail("vk_chain_create: upload failed");
-  }
-  return f;
-}
-
-const char* vk_chain_last_error(const vk_chain* f) { return f ? f->err.c_str() : ""; }
-
-void vk_chain_destroy(vk_chain* f) {
-  if (!f) return;
-  if (f->d_mem) {
-    (void)hipSetDevice(f->ctx->device);
-    if (f->in_flight) (void)hipStreamSynchronize(f->ctx->stream);
-    (void)hipFree(f->d_mem);
-  }
-  delete f;
-}
-
-int vk_chain_start(vk_chain* f, const double* x0) {
-  if (!f) return VK_E_ARG;
-  vk_ctx* ctx = f->ctx;
-  auto refuse = [&](const std::string& msg) {
-    f->err = msg;
-    return VK_E_ARG;
-  };
-  if (!x0) return refuse("vk_chain_start: NULL argument");
-  if (f->in_flight) return refuse("vk_chain_start: a block begun with vk_chain_begin is awaiting vk_chain_finish");
-  int rc = chain_ready(f, "vk_chain_start");
-  if (rc) return rc;
-  for (int c = 0; c < f->C; ++c)
-    if (!vkchain::in_box(f->box, x0 + (size_t)c * f->P))
-      return refuse("vk_chain_start: the start of chain " + std::to_string(c) + " is outside the box");
-  VK_CHAIN_HIP(f, hipSetDevice(ctx->device));
-  VK_CHAIN_HIP(f, hipMemcpy(f->d_x0, x0, (size_t)f->C * f->P * sizeof(double), hipMemcpyHostToDevice));
-  ChainArgs a = chain_args(f);
-  rc = chain_launch(ctx, vk_chain_init_kernel, a);
-  if (rc == VK_OK) rc = chain_evaluate(f);
-  a.adopt = 1;
-  if (rc == VK_OK) rc = chain_launch(ctx, vk_chain_step_kernel, a);
-  if (rc) return chain_abort(f, rc);
-  VK_CHAIN_HIP(f, hipStreamSynchronize(ctx->stream));
-  f->started = true;
-  f->err.clear();
-  return VK_OK;
-}
-
-int vk_chain_begin(vk_chain* f, int32_t n_steps, const double* dz, const double* logu, int64_t first_step, int64_t burn, int64_t thin,
-                   int32_t want_history, int32_t* n_kept) {
-  if (!f) return VK_E_ARG;
-  vk_ctx* ctx = f->ctx;
-  auto refuse = [&](const std::string& msg) {
-    f->err = msg;
-    return VK_E_ARG;
-  };
-  if (!dz || !logu) return refuse("vk_chain_begin: NULL argument");
-  if (!f->started) return refuse("vk_chain_begin: the chains have no start (vk_chain_start)");
-  if (f->in_flight) return refuse("vk_chain_begin: the previous block has not been finished (vk_chain_finish)");
-  if (n_steps < 1 || n_steps > vkchain::kBlock) return refuse("vk_chain_begin: need 1 <= steps <= 64 in a block");
-  if (first_step < 0 || burn < 0 || thin < 1) return refuse("vk_chain_begin: need first_step >= 0, burn >= 0, thin >= 1");
-  int rc = chain_ready(f, "vk_chain_begin");
-  if (rc) return rc;
-  const size_t C = f->C, P = f->P;
-  VK_CHAIN_HIP(f, hipSetDevice(ctx->device));
-  // the stream is idle (the block before was finished): plain copies, complete on return
-  VK_CHAIN_HIP(f, hipMemcpy(f->d_dz, dz, (size_t)n_steps * C * P * sizeof(double), hipMemcpyHostToDevice));
-  VK_CHAIN_HIP(f, hipMemcpy(f->d_logu, logu, (size_t)n_steps * C * sizeof(double), hipMemcpyHostToDevice));
-  ChainArgs a = chain_args(f);
-  a.dz = f->d_dz;
-  rc = chain_launch(ctx, vk_chain_propose_kernel, a);
-  int slot = 0;
-  for (int t = 0; t < n_steps && rc == VK_OK; ++t) {
-    rc = chain_evaluate(f);
-    if (rc) break;
-    const bool kept = vkchain::is_kept(first_step + t, burn, thin);
-    a.dz = f->d_dz + (size_t)t * C * P;
-    a.logu = f->d_logu + (size_t)t * C;
-    a.dz_next = t + 1 < n_steps ? a.dz + C * P : nullptr;
-    a.kept = kept ? 1 : 0;
-    const bool hist = kept && want_history;
-    a.hist_x = hist ? f->d_hx + (size_t)slot * C * P : nullptr;
-    a.hist_lnl = hist ? f->d_hl + (size_t)slot * C : nullptr;
-    a.hist_chi2 = hist ? f->d_hc + (size_t)slot * C : nullptr;
-    if (hist) ++slot;
-    rc = chain_launch(ctx, vk_chain_step_kernel, a);
-  }
-  if (rc) return chain_abort(f, rc);
-  f->in_flight = n_steps;
-  f->block_kept = slot;
-  if (n_kept) *n_kept = slot;
-  f->err.clear();
-  return VK_OK;
-}
-
-int vk_chain_finish(vk_chain* f, double* x, double* lnl, double* chi2) {
-  if (!f) return VK_E_ARG;
-  vk_ctx* ctx = f->ctx;
-  if (!f->in_flight) {
-    f->err = "vk_chain_finish: nothing was begun";
-    return VK_E_ARG;
-  }
-  if (f->block_kept > 0 && (!x || !lnl || !chi2)) {
-    (void)chain_abort(f, VK_E_ARG);
-    f->err = "vk_chain_finish: the block keeps a history: NULL argument";
-    return VK_E_ARG;
-  }
-  const size_t n = (size_t)f->block_kept * f->C;
-  hipError_t e = hipSetDevice(ctx->device);
-  if (e == hipSuccess && n) e = hipMemcpyAsync(x, f->d_hx, n * f->P * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess && n) e = hipMemcpyAsync(lnl, f->d_hl, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess && n) e = hipMemcpyAsync(chi2, f->d_hc, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  f->in_flight = 0;
-  f->block_kept = 0;
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    f->err = std::string("vk_chain_finish: ") + hipGetErrorString(e);
-    return VK_E_HIP;
-  }
-  f->err.clear();
-  return VK_OK;
-}
-
-int vk_chain_state(vk_chain* f, double* x, double* lnl, double* chi2, int64_t* n_accept, int64_t* n_steps, int64_t* n_kept,
-                   double* pivot, double* sum1, double* sum2) {
-  if (!f) return VK_E_ARG;
-  vk_ctx* ctx = f->ctx;
-  if (!f->started || f->in_flight) {
-    f->err = f->started ? "vk_chain_state: a block begun with vk_chain_begin is awaiting vk_chain_finish"
-                        : "vk_chain_state: the chains have no start (vk_chain_start)";
-    return VK_E_ARG;
-  }
-  const size_t C = f->C, P = f->P, T = f->T;
-  VK_CHAIN_HIP(f, hipSetDevice(ctx->device));
-  // the state block x | lnl | chi2 | pivot | sum1 | sum2 and the three counters are contiguous
-  std::vector<double> h(C * (3 * P + 2 + T));
-  std::vector<long long> n(3 * C);
-  VK_CHAIN_HIP(f, hipMemcpy(h.data(), f->d_x, h.size() * sizeof(double), hipMemcpyDeviceToHost));
-  VK_CHAIN_HIP(f, hipMemcpy(n.data(), f->d_acc, n.size() * sizeof(long long), hipMemcpyDeviceToHost));
-  const double *hx = h.data(), *hl = hx + C * P, *hc = hl + C, *hp = hc + C, *h1 = hp + C * P, *h2 = h1 + C * P;
-  for (size_t c = 0; c < C; ++c) {
-    for (size_t j = 0; j < P; ++j) {
-      if (x) x[c * P + j] = hx[j * C + c];
-      if (pivot) pivot[c * P + j] = hp[j * C + c];
-      if (sum1) sum1[c * P + j] = h1[j * C + c];
-      if (sum2)
-        for (size_t k = j; k < P; ++k) {           // the packed triangle, mirrored into a full symmetric matrix
-          const double v = h2[(size_t)vkchain::tri((int)P, (int)j, (int)k) * C + c];
-          sum2[(c * P + j) * P + k] = v;
-          sum2[(c * P + k) * P + j] = v;
-        }
-    }
-    if (lnl) lnl[c] = hl[c];
-    if (chi2) chi2[c] = hc[c];
-    if (n_accept) n_accept[c] = n[c];
-    if (n_steps) n_steps[c] = n[C + c];
-    if (n_kept) n_kept[c] = n[2 * C + c];
-  }
-  f->err.clear();
-  return VK_OK;
 }
 
 }  // extern "C"

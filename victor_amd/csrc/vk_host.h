@@ -1,9 +1,9 @@
 // vk_host.h - what the host-side translation units of libvictor_hip.so share: the context, the development knobs and the
-// internal entry points that cross files.  No device code: victor_hip.hip (hipcc; the ABI's launch side and every kernel)
-// includes it next to the kernel headers, vk_walk.cpp / vk_serve.cpp / vk_rccl.cpp (host compiler) include nothing else of
-// the library.  The layout of vk_ctx must be the same in every unit: one definition, no conditional members, standard-library
-// members only (hipcc and the host compiler use the same libstdc++); vk_create checks the sizes the units report against each
-// other once (ctx_layout_*).
+// internal entry points that cross files.  No device code: victor_hip.hip and vk_sampled.hip (hipcc; the ABI's launch side and
+// every kernel) include it next to the kernel headers, vk_walk.cpp / vk_serve.cpp / vk_rccl.cpp (host compiler) include nothing
+// else of the library.  The layout of vk_ctx must be the same in every unit: one definition, no conditional members,
+// standard-library members only (hipcc and the host compiler use the same libstdc++); vk_create checks the sizes the units
+// report against each other once (ctx_layout_*).
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -174,6 +174,12 @@ int host_scratch(vk_ctx* ctx, int64_t n, HostScratch* sc);
 // 1 = the results are in lnl / chi2, 0 = not yet (only with block == false), < 0 = error.
 int zc_begin(vk_ctx* ctx, const vk_eval_opts* opts, const double* params, int64_t n, bool want_out, double* d_th);
 int zc_finish(vk_ctx* ctx, int64_t n, double* lnl, double* chi2, bool block);
+
+// Against the context's realisations, for vk_sampled.hip (the contract is at the definitions): may the realisation kernel
+// run on this data vector; enqueue the theory vectors of m device rows and the realisation chi-square behind them.
+int check_real_lds(vk_ctx* ctx);
+int enqueue_realisations(vk_ctx* ctx, const vk_eval_opts* opts, const double* d_par, long long m, double* d_th, double* d_lnl,
+                         double* d_chi, const int32_t* d_which);
 
 // sizeof(vk_ctx) and the offset of its last member as each host-compiled unit sees them (vk_create compares them with its own)
 size_t ctx_layout_walk(size_t* last_offset);

@@ -1,5 +1,5 @@
 // vk_kernel_chain.h: the Metropolis chains of vk_chain_begin (include/victor_hip.h) on the device - part of libvictor_hip.so
-// (see victor_hip.hip for the overview, DESIGN.md section 7b for the algorithm and the measurements).
+// (see vk_sampled.hip for the host side, DESIGN.md section 7b for the algorithm and the measurements).
 //
 // One thread per chain.  The chains' state lives in device memory, structure-of-arrays (x[j][c], sum1[j][c], sum2[jk][c], ...:
 // the 64 lanes of a wave touch consecutive doubles); the transition itself is vkchain::transition (vk_chain_step.h) on a strided
@@ -7,12 +7,14 @@
 // chi-square; a realisation: the theory launch and vk_like_real_kernel in pairs mode).  The step kernel reads the (lnL, chi2) of
 // its chain's row, decides, accounts (accept count, moment sums and the history slot of a kept step) and writes the chain's next
 // row from the increment of the following step: the base row with the sampled columns overwritten and epsilon turned into the
-// Alcock-Paczynski factors as fit_emit (vk_kernel_fit.h) forms them - with the device's pow, so a row with a sampled epsilon
-// equals the host's row (libm's pow through vk_epsilon_to_ap) to rounding, any other row bit for bit.  A proposal outside the
-// box is not evaluated: its row carries the chain's current position and the step kernel ignores what comes back.
+// Alcock-Paczynski factors by sampled_row (vk_sampled_row.h), as the best fits' rows are - with the device's pow, so a row
+// with a sampled epsilon equals the host's row (libm's pow through vk_epsilon_to_ap) to rounding, any other row bit for bit.
+// A proposal outside the box is not evaluated: its row carries the chain's current position and the step kernel ignores what
+// comes back.
 #pragma once
 #include "vk_common.h"
 #include "vk_chain_step.h"
+#include "vk_sampled_row.h"
 
 namespace vk {
 
@@ -69,23 +71,10 @@ __device__ __forceinline__ vkchain::View chain_view(const ChainArgs& a, int c) {
 // the row of chain c at x (+ dz when dz is given and x + dz is inside the box)
 __device__ __forceinline__ void chain_emit(const ChainArgs& a, const vkchain::View& s, int c, const double* dz) {
   const bool move = dz != nullptr && vkchain::proposal_inside(a.box, s, dz);
-  const double* b = a.base + (size_t)c * VK_NPAR;
-  double* row = a.rows + (size_t)c * VK_NPAR;
-  for (int k = 0; k < VK_NPAR; ++k) row[k] = b[k];
-  for (int j = 0; j < a.box.d; ++j) {
-    double v = s.x[j * s.stride];
-    if (move) v = v + dz[j];
-    const int k = a.col[j];
-    if (k >= 0) {
-      row[k] = v;
-    } else {                                    // apar = alpha eps^(-2/3), aperp = eps apar (vk_epsilon_to_ap, ccf_model.py:589-592)
-      double ap = pow(v, -2.0 / 3.0);
-      if (a.alpha != 1.0) ap = a.alpha * ap;
-      row[VK_P_APAR] = ap;
-      row[VK_P_APERP] = v * ap;
-      row[VK_P_EPSILON] = v;
-    }
-  }
+  sampled_row(a.base + (size_t)c * VK_NPAR, a.rows + (size_t)c * VK_NPAR, a.col, a.box.d, a.alpha, [&](int j) {
+    const double v = s.x[j * s.stride];
+    return move ? v + dz[j] : v;
+  });
   if (a.row_which) a.row_which[c] = a.which[c];
 }
 

@@ -1,16 +1,17 @@
 // vk_kernel_fit.h: the bounded Nelder-Mead search of vk_fit_run (include/victor_hip.h) on the device - part of libvictor_hip.so
-// (see victor_hip.hip for the overview, DESIGN.md section 7a for the algorithm and the measurements).
+// (see vk_sampled.hip for the host side, DESIGN.md section 7a for the algorithm and the measurements).
 //
 // One thread per problem.  The search's state lives in device memory (vkfit::State, one per problem); between two of these
 // kernels the library evaluates the S rows of every active problem (the fit's own data vector: the theory launch with its
 // chi-square; a realisation: the theory launch and vk_like_real_kernel in pairs mode).  The step kernel reads those S
 // (lnL, chi2) pairs, applies vkfit::transition and writes the problem's next S rows - the base row with the sampled columns
-// overwritten and epsilon turned into the Alcock-Paczynski factors as vk_epsilon_to_ap forms them - and, against realisations,
+// overwritten and epsilon turned into the Alcock-Paczynski factors (sampled_row, vk_sampled_row.h) - and, against realisations,
 // each row's realisation index.  Rows of launch position k are rows k S .. k S + S - 1; the host keeps the list of active
 // problems (in problem order) and, when it shrinks, lays the rows out again with vk_fit_emit_kernel.
 #pragma once
 #include "vk_common.h"
 #include "vk_fit_simplex.h"
+#include "vk_sampled_row.h"
 
 namespace vk {
 
@@ -34,27 +35,10 @@ struct FitArgs {
 };
 
 __device__ __forceinline__ void fit_emit(const FitArgs& a, const vkfit::State& s, int p, int k) {
-  const int S = a.q.S, d = a.q.d;
-  const double* b = a.base + (size_t)p * VK_NPAR;
+  const int S = a.q.S;
   for (int slot = 0; slot < S; ++slot) {
     const size_t r = (size_t)k * S + slot;
-    double* row = a.rows + r * VK_NPAR;
-    for (int c = 0; c < VK_NPAR; ++c) row[c] = b[c];
-#pragma unroll
-    for (int j = 0; j < vkfit::kMaxP; ++j) {
-      if (j >= d) break;
-      const double x = s.pt[slot][j];
-      const int c = a.col[j];
-      if (c >= 0) {
-        row[c] = x;
-      } else {                                  // apar = alpha eps^(-2/3), aperp = eps apar (vk_epsilon_to_ap, ccf_model.py:589-592)
-        double ap = pow(x, -2.0 / 3.0);
-        if (a.alpha != 1.0) ap = a.alpha * ap;
-        row[VK_P_APAR] = ap;
-        row[VK_P_APERP] = x * ap;
-        row[VK_P_EPSILON] = x;
-      }
-    }
+    sampled_row(a.base + (size_t)p * VK_NPAR, a.rows + r * VK_NPAR, a.col, a.q.d, a.alpha, [&](int j) { return s.pt[slot][j]; });
     if (a.row_which) a.row_which[r] = a.which[p];
   }
 }

@@ -1,0 +1,571 @@
+// vk_sampled.hip - the drivers of libvictor_hip.so that step sets of sampled-parameter problems on the device: best fits
+// (vk_fit_*) and Metropolis chains (vk_chain_*) of the C ABI (include/victor_hip.h), and what they share.  A problem names the
+// row columns it samples inside a prior box, over a base row of its own, against the context's data vector or one of its
+// realisations; its rows are formed on the device (vk_sampled_row.h) and evaluated by victor_hip.hip, which this unit reaches
+// through vk_eval_batch_device_async and, in vk_host.h, enqueue_realisations / check_real_lds.  The same object serves every
+// flavour of the library.
+//
+// Device code lives in the headers next to this file:
+//   vk_sampled_row.h     a parameter row from a base row and the sampled values
+//   vk_kernel_fit.h      the best-fit search (vk_fit_run): start simplex, step and re-layout kernels, one thread per problem, over
+//                        the one-problem transition of vk_fit_simplex.h (plain C++, also compiled on its own by the CPU tests)
+//   vk_kernel_chain.h    Metropolis chains of the data vector or one realisation each (vk_chain_begin): start, propose and step
+//                        kernels, one thread per chain, over the one-chain transition of vk_chain_step.h (plain C++, likewise)
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "victor_hip.h"
+#include "vk_host.h"
+#include "vk_kernel_fit.h"
+#include "vk_kernel_chain.h"
+
+using namespace vk;
+using vkh::check_opts;
+using vkh::check_real_lds;
+using vkh::enqueue_realisations;
+using vkh::sync_knobs;
+
+// ---- the shared core: a set of sampled-parameter problems on a context ---------------------------------------------------------
+constexpr int kSampledMax = 65536;         // problems (chains) of one handle
+constexpr int kSampledMaxP = vkfit::kMaxP;
+static_assert(vkchain::kMaxP == kSampledMaxP, "best fits and chains sample the same columns");
+
+struct Sampled {
+  vk_ctx* ctx = nullptr;
+  vk_eval_opts opts{};
+  int P = 0;                               // sampled parameters
+  int col[kSampledMaxP] = {};
+  double alpha = 1.0;
+  bool real = false;
+  int max_which = -1;
+  void* d_mem = nullptr;                   // one allocation holding every device array of the handle
+  double *d_base = nullptr, *d_rows = nullptr, *d_th = nullptr;   // each problem's base row; the pending rows, their theory vectors
+  int *d_which = nullptr, *d_row_which = nullptr;                 // realisation of each problem, of each pending row
+  std::string err;
+};
+
+// The typed arrays of a handle inside its one allocation: a handle's layout() names them once, in order of descending
+// alignment - without a base to count the bytes, then over the allocation to hand the pointers out.
+struct Carve {
+  char* base = nullptr;
+  size_t bytes = 0;
+  template <class T>
+  void take(T*& p, size_t count) {
+    p = base ? reinterpret_cast<T*>(base + bytes) : nullptr;
+    bytes += count * sizeof(T);
+  }
+};
+
+// a HIP call on behalf of a handle: the error text goes to the handle (vk_fit_last_error / vk_chain_last_error)
+#define VK_SAMPLED_HIP(f, call)                                                        \
+  do {                                                                                 \
+    hipError_t e_ = (call);                                                            \
+    if (e_ != hipSuccess) {                                                            \
+      (f)->err = std::string(#call " failed: ") + hipGetErrorString(e_);               \
+      return VK_E_HIP;                                                                 \
+    }                                                                                  \
+  } while (0)
+
+// vk_fit_destroy / vk_chain_destroy, after whatever was in flight has been waited for
+template <class H>
+static void sampled_destroy(H* f) {
+  if (f->d_mem) {
+    (void)hipSetDevice(f->ctx->device);
+    (void)hipFree(f->d_mem);
+  }
+  delete f;
+}
+
+// vk_fit_create / vk_chain_create (`who`; a problem is a `noun` in its texts).  H is a Sampled with shape(n, lo, hi), which
+// keeps the count, the box and what follows from P, and layout(Carve&) (hidden: no symbol of theirs leaves the library).
+template <class H>
+static H* sampled_create(const char* who, const char* noun, vk_ctx* ctx, const vk_eval_opts* opts, int32_t n, int32_t n_params,
+                         const int32_t* columns, const double* lo, const double* hi, const double* base_rows, double alpha,
+                         const int32_t* which, char* err, size_t errlen) {
+  auto bail = [&](const std::string& msg) -> H* {
+    if (err && errlen) {
+      strncpy(err, msg.c_str(), errlen - 1);
+      err[errlen - 1] = 0;
+    }
+    return nullptr;
+  };
+  const std::string me = std::string(who) + ": ";
+  if (!ctx || !opts || !columns || !lo || !hi || !base_rows) return bail(me + "NULL argument");
+  if (n < 1 || n > kSampledMax) return bail(me + "need 1 <= " + noun + "s <= 65536");
+  if (n_params < 1 || n_params > kSampledMaxP)
+    return bail(me + "need 1 <= parameters <= 10 (the row columns other than aperp / apar / epsilon, and epsilon)");
+  sync_knobs(ctx);
+  if (check_opts(ctx, opts) != VK_OK) return bail(ctx->err);
+  if (!ctx->d_data) return bail(me + "context was created without a data vector");
+  bool used[VK_NPAR] = {};
+  int n_eps = 0;
+  for (int j = 0; j < n_params; ++j) {
+    const int c = columns[j];
+    if (c == VK_WALK_EPSILON) {
+      ++n_eps;
+    } else if (c < 0 || c >= VK_NPAR || (c >= VK_P_APERP && c <= VK_P_EPSILON) || used[c]) {
+      return bail(me + "a sampled parameter must name a row column other than aperp / apar / epsilon, or VK_WALK_EPSILON, once");
+    } else {
+      used[c] = true;
+    }
+    if (!(hi[j] > lo[j])) return bail(me + "the prior box needs lo < hi");
+  }
+  if (n_eps > 1) return bail(me + "epsilon sampled twice");
+  int max_which = -1;
+  if (which)
+    for (int i = 0; i < n; ++i) {
+      if (which[i] < 0 || which[i] >= ctx->n_real)
+        return bail(me + "realisation index " + std::to_string(which[i]) + " of " + noun + " " + std::to_string(i) +
+                    " is outside 0.." + std::to_string(ctx->n_real - 1));
+      max_which = std::max(max_which, (int)which[i]);
+    }
+  H* f = new (std::nothrow) H();
+  if (!f) return bail("out of memory");
+  f->ctx = ctx;
+  f->opts = *opts;
+  f->P = n_params;
+  for (int j = 0; j < n_params; ++j) f->col[j] = columns[j];
+  f->alpha = alpha;
+  f->real = which != nullptr;
+  f->max_which = max_which;
+  f->shape(n, lo, hi);
+  Carve count;
+  f->layout(count);
+  if (hipSetDevice(ctx->device) != hipSuccess || hipMalloc(&f->d_mem, count.bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    delete f;
+    return bail(me + "cannot allocate " + std::to_string(count.bytes) + " bytes of device memory");
+  }
+  Carve mem{static_cast<char*>(f->d_mem)};
+  f->layout(mem);
+  bool ok = hipMemcpy(f->d_base, base_rows, (size_t)n * VK_NPAR * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+  if (ok && which) ok = hipMemcpy(f->d_which, which, (size_t)n * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    sampled_destroy(f);
+    return bail(me + "upload failed");
+  }
+  return f;
+}
+
+// a call refused before anything was enqueued: the text goes to the handle
+static int refused(Sampled* f, const std::string& msg) {
+  f->err = msg;
+  return VK_E_ARG;
+}
+
+// May the handle use its context now?  What every call that touches the context checks first.  (vk_fit_run reports an LDS
+// refusal in the context's words alone, the chain entry points under their own name: name_lds.)
+static int sampled_ready(Sampled* f, const char* who, const char* noun, bool name_lds) {
+  vk_ctx* ctx = f->ctx;
+  auto refuse = [&](const std::string& msg) { return refused(f, std::string(who) + ": " + msg); };
+  if (ctx->begun_n != 0) return refuse("a batch begun with vk_eval_batch_begin is awaiting vk_eval_batch_finish on the context");
+  if (f->real) {
+    if (ctx->n_real <= 0 || !ctx->d_real) return refuse("no realisations are set on the context (vk_set_realisations)");
+    if (f->max_which >= ctx->n_real)
+      return refuse("the context holds " + std::to_string(ctx->n_real) + " realisations, a " + noun + " asks for number " +
+                    std::to_string(f->max_which));
+    if (check_real_lds(ctx) != VK_OK) return name_lds ? refuse(ctx->err) : refused(f, ctx->err);
+  }
+  return VK_OK;
+}
+
+// the evaluation of the first m pending rows into d_lnl / d_chi, on the context's stream: the fit's own data vector with lnL /
+// chi2 in the theory launch (the fused tail applies), realisations in pairs mode
+static int sampled_evaluate(Sampled* f, long long m, double* d_lnl, double* d_chi) {
+  const int rc = f->real ? enqueue_realisations(f->ctx, &f->opts, f->d_rows, m, f->d_th, d_lnl, d_chi, f->d_row_which)
+                         : vk_eval_batch_device_async(f->ctx, &f->opts, f->d_rows, m, d_lnl, d_chi, f->d_th);
+  if (rc) f->err = f->ctx->err;
+  return rc;
+}
+
+// a kernel of one thread per problem behind it
+template <class Args>
+static int sampled_launch(Sampled* f, void (*kern)(Args), int threads, int block, const Args& a) {
+  hipLaunchKernelGGL(kern, dim3((unsigned)((threads + block - 1) / block)), dim3(block), 0, f->ctx->stream, a);
+  VK_SAMPLED_HIP(f, hipGetLastError());
+  return VK_OK;
+}
+
+// an error after something was enqueued (the handle holds its text): leave nothing in flight
+static int sampled_abort(Sampled* f, int rc) {
+  (void)hipStreamSynchronize(f->ctx->stream);
+  (void)hipGetLastError();
+  return rc;
+}
+
+// ---- best fits: bounded Nelder-Mead, one simplex per problem, one launch per iteration (include/victor_hip.h, vk_kernel_fit.h) --
+// An iteration enqueues, on the context's stream, the evaluation of the active problems' S rows each (sampled_evaluate) and the
+// step kernel behind it - no host synchronisation and no graph inside an iteration.  Every kFitCheck iterations the host reads
+// the status words, keeps the problems still running (in problem order) and lays their rows out again, so a finished problem
+// stops costing evaluations and which rows share a launch does not depend on timing.
+constexpr int kFitCheck = 8;
+
+struct __attribute__((visibility("hidden"))) vk_fit : Sampled {
+  int R = 0, S = 0;                        // problems, rows of a problem in a launch
+  double lo[vkfit::kMaxP] = {}, hi[vkfit::kMaxP] = {};
+  vkfit::State* d_state = nullptr;         // [R]
+  double *d_x0 = nullptr, *d_lnl = nullptr, *d_chi = nullptr;
+  int *d_active = nullptr, *d_status = nullptr;
+
+  void shape(int n, const double* lo_, const double* hi_) {
+    R = n;
+    S = vkfit::slots(P);
+    for (int j = 0; j < P; ++j) {
+      lo[j] = lo_[j];
+      hi[j] = hi_[j];
+    }
+  }
+  void layout(Carve& c) {
+    const size_t n = R, rows = n * S;
+    c.take(d_state, n);
+    c.take(d_base, n * VK_NPAR);
+    c.take(d_x0, n * P);
+    c.take(d_rows, rows * VK_NPAR);
+    c.take(d_lnl, rows);
+    c.take(d_chi, rows);
+    c.take(d_th, rows * ctx->N);
+    c.take(d_active, n);
+    c.take(d_row_which, rows);
+    c.take(d_which, n);
+    c.take(d_status, n);
+  }
+};
+
+// the loop of vk_fit_run
+static int fit_loop(vk_fit* f, const vkfit::Params& q, const double* x0, std::vector<vkfit::State>* out) {
+  vk_ctx* ctx = f->ctx;
+  const int R = f->R, S = f->S;
+  VK_SAMPLED_HIP(f, hipSetDevice(ctx->device));
+  std::vector<int> act(R), status(R);
+  for (int p = 0; p < R; ++p) act[p] = p;
+  VK_SAMPLED_HIP(f, hipMemcpyAsync(f->d_x0, x0, (size_t)R * f->P * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  VK_SAMPLED_HIP(f, hipMemcpyAsync(f->d_active, act.data(), (size_t)R * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+  FitArgs a{};
+  a.q = q;
+  a.state = f->d_state;
+  a.base = f->d_base;
+  a.x0 = f->d_x0;
+  a.active = f->d_active;
+  a.n_active = R;
+  a.lnl = f->d_lnl;
+  a.chi2 = f->d_chi;
+  a.rows = f->d_rows;
+  a.row_which = f->real ? f->d_row_which : nullptr;
+  a.which = f->real ? f->d_which : nullptr;
+  a.status = f->d_status;
+  for (int j = 0; j < vkfit::kMaxP; ++j) a.col[j] = f->col[j];
+  a.alpha = f->alpha;
+  int rc = sampled_launch(f, vk_fit_init_kernel, R, kFitBlock, a);
+  while (rc == VK_OK) {
+    for (int t = 0; t < kFitCheck && rc == VK_OK; ++t) {
+      rc = sampled_evaluate(f, (long long)a.n_active * S, f->d_lnl, f->d_chi);
+      if (rc == VK_OK) rc = sampled_launch(f, vk_fit_step_kernel, a.n_active, kFitBlock, a);
+    }
+    if (rc) return rc;
+    VK_SAMPLED_HIP(f, hipMemcpyAsync(status.data(), f->d_status, (size_t)R * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    VK_SAMPLED_HIP(f, hipStreamSynchronize(ctx->stream));
+    std::vector<int> next;
+    for (int p : act)
+      if (status[p] < 0) next.push_back(p);
+    if (next.empty()) break;
+    if ((int)next.size() < a.n_active) {
+      act.swap(next);
+      a.n_active = (int)act.size();
+      VK_SAMPLED_HIP(f, hipMemcpyAsync(f->d_active, act.data(), act.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+      rc = sampled_launch(f, vk_fit_emit_kernel, a.n_active, kFitBlock, a);
+    }
+  }
+  if (rc) return rc;
+  out->resize(R);
+  VK_SAMPLED_HIP(f, hipMemcpy(out->data(), f->d_state, (size_t)R * sizeof(vkfit::State), hipMemcpyDeviceToHost));
+  return VK_OK;
+}
+
+extern "C" {
+
+vk_fit* vk_fit_create(vk_ctx* ctx, const vk_eval_opts* opts, int32_t n_problems, int32_t n_params, const int32_t* columns,
+                      const double* lo, const double* hi, const double* base_rows, double alpha, const int32_t* which, char* err,
+                      size_t errlen) {
+  return sampled_create<vk_fit>("vk_fit_create", "problem", ctx, opts, n_problems, n_params, columns, lo, hi, base_rows, alpha,
+                                which, err, errlen);
+}
+
+const char* vk_fit_last_error(const vk_fit* f) { return f ? f->err.c_str() : ""; }
+
+void vk_fit_destroy(vk_fit* f) {
+  if (f) sampled_destroy(f);
+}
+
+int vk_fit_run(vk_fit* f, const double* x0, const double* step, const double* xtol, double ftol, int32_t max_iter, int32_t restarts,
+               double* x, double* lnl, double* chi2, int32_t* status, int32_t* n_iter, int64_t* n_evals) {
+  if (!f) return VK_E_ARG;
+  if (!x0 || !step || !xtol || !x || !lnl || !chi2 || !status || !n_iter || !n_evals) return refused(f, "vk_fit_run: NULL argument");
+  int rc = sampled_ready(f, "vk_fit_run", "problem", false);
+  if (rc) return rc;
+  if (max_iter < 1 || restarts < 0 || !(ftol >= 0)) return refused(f, "vk_fit_run: need max_iter >= 1, restarts >= 0, ftol >= 0");
+  vkfit::Params q{};
+  q.d = f->P;
+  q.S = f->S;
+  q.max_iter = max_iter;
+  q.restarts = restarts;
+  q.ftol = ftol;
+  for (int j = 0; j < f->P; ++j) {
+    if (!(step[j] > 0) || !(xtol[j] >= 0)) return refused(f, "vk_fit_run: parameter " + std::to_string(j) + " needs step > 0 and xtol >= 0");
+    q.lo[j] = f->lo[j];
+    q.hi[j] = f->hi[j];
+    q.step[j] = step[j];
+    q.xtol[j] = xtol[j];
+  }
+  for (int p = 0; p < f->R; ++p)
+    if (!vkfit::in_box(q, x0 + (size_t)p * f->P)) return refused(f, "vk_fit_run: the start of problem " + std::to_string(p) + " is outside the box");
+  std::vector<vkfit::State> st;
+  rc = fit_loop(f, q, x0, &st);
+  if (rc != VK_OK) return sampled_abort(f, rc);
+  for (int p = 0; p < f->R; ++p) {
+    const vkfit::State& s = st[p];
+    for (int j = 0; j < f->P; ++j) x[(size_t)p * f->P + j] = s.v[0][j];
+    lnl[p] = -s.f[0];
+    chi2[p] = s.chi[0];
+    status[p] = s.status;
+    n_iter[p] = s.iter;
+    n_evals[p] = s.n_evals;
+  }
+  f->err.clear();
+  return VK_OK;
+}
+
+}  // extern "C"
+
+// ---- Metropolis chains: one chain per thread, one launch per step (include/victor_hip.h, vk_kernel_chain.h) ------------------
+// A step enqueues, on the context's stream, the evaluation of the C chains' rows (sampled_evaluate: the launches fit_loop makes)
+// and the step kernel behind it, which decides and writes the next rows.  No host synchronisation and no graph inside a block of
+// up to 64 steps: vk_chain_begin uploads the block's random numbers and enqueues all of it, vk_chain_finish waits and brings the
+// block's kept steps home, and the host draws the next block's numbers in between.
+struct __attribute__((visibility("hidden"))) vk_chain : Sampled {
+  int C = 0, T = 0;                        // chains, entries of a packed second-moment triangle
+  vkchain::Box box{};
+  bool started = false;
+  int in_flight = 0;                       // steps of the block begun and not finished
+  int block_kept = 0;                      // history slots the block in flight fills (0 without a history)
+  double *d_x = nullptr, *d_lnl = nullptr, *d_chi = nullptr, *d_pivot = nullptr, *d_sum1 = nullptr, *d_sum2 = nullptr;
+  double *d_x0 = nullptr, *d_res_lnl = nullptr, *d_res_chi = nullptr;
+  double *d_dz = nullptr, *d_logu = nullptr, *d_hx = nullptr, *d_hl = nullptr, *d_hc = nullptr;
+  long long *d_acc = nullptr, *d_steps = nullptr, *d_kept = nullptr;
+
+  void shape(int n, const double* lo, const double* hi) {
+    C = n;
+    T = vkchain::n_tri(P);
+    box.d = P;
+    for (int j = 0; j < P; ++j) {
+      box.lo[j] = lo[j];
+      box.hi[j] = hi[j];
+    }
+  }
+  // state | base, x0, rows, results, theory workspace | one block of random numbers | one block of history | counters | indices
+  void layout(Carve& c) {
+    const size_t n = C, block = vkchain::kBlock * n;
+    c.take(d_x, n * P);
+    c.take(d_lnl, n);
+    c.take(d_chi, n);
+    c.take(d_pivot, n * P);
+    c.take(d_sum1, n * P);
+    c.take(d_sum2, n * T);
+    c.take(d_base, n * VK_NPAR);
+    c.take(d_x0, n * P);
+    c.take(d_rows, n * VK_NPAR);
+    c.take(d_res_lnl, n);
+    c.take(d_res_chi, n);
+    c.take(d_th, n * ctx->N);
+    c.take(d_dz, block * P);
+    c.take(d_logu, block);
+    c.take(d_hx, block * P);
+    c.take(d_hl, block);
+    c.take(d_hc, block);
+    c.take(d_acc, n);
+    c.take(d_steps, n);
+    c.take(d_kept, n);
+    c.take(d_which, n);
+    c.take(d_row_which, n);
+  }
+};
+
+static ChainArgs chain_args(const vk_chain* f) {
+  ChainArgs a{};
+  a.box = f->box;
+  a.C = f->C;
+  a.x = f->d_x;
+  a.lnl = f->d_lnl;
+  a.chi2 = f->d_chi;
+  a.pivot = f->d_pivot;
+  a.sum1 = f->d_sum1;
+  a.sum2 = f->d_sum2;
+  a.n_accept = f->d_acc;
+  a.n_steps = f->d_steps;
+  a.n_kept = f->d_kept;
+  a.base = f->d_base;
+  a.which = f->real ? f->d_which : nullptr;
+  a.x0 = f->d_x0;
+  a.res_lnl = f->d_res_lnl;
+  a.res_chi2 = f->d_res_chi;
+  a.rows = f->d_rows;
+  a.row_which = f->real ? f->d_row_which : nullptr;
+  for (int j = 0; j < vkchain::kMaxP; ++j) a.col[j] = f->col[j];
+  a.alpha = f->alpha;
+  return a;
+}
+
+extern "C" {
+
+vk_chain* vk_chain_create(vk_ctx* ctx, const vk_eval_opts* opts, int32_t n_chains, int32_t n_params, const int32_t* columns,
+                          const double* lo, const double* hi, const double* base_rows, double alpha, const int32_t* which, char* err,
+                          size_t errlen) {
+  return sampled_create<vk_chain>("vk_chain_create", "chain", ctx, opts, n_chains, n_params, columns, lo, hi, base_rows, alpha,
+                                  which, err, errlen);
+}
+
+const char* vk_chain_last_error(const vk_chain* f) { return f ? f->err.c_str() : ""; }
+
+void vk_chain_destroy(vk_chain* f) {
+  if (!f) return;
+  if (f->in_flight) (void)hipStreamSynchronize(f->ctx->stream);
+  sampled_destroy(f);
+}
+
+int vk_chain_start(vk_chain* f, const double* x0) {
+  if (!f) return VK_E_ARG;
+  vk_ctx* ctx = f->ctx;
+  if (!x0) return refused(f, "vk_chain_start: NULL argument");
+  if (f->in_flight) return refused(f, "vk_chain_start: a block begun with vk_chain_begin is awaiting vk_chain_finish");
+  int rc = sampled_ready(f, "vk_chain_start", "chain", true);
+  if (rc) return rc;
+  for (int c = 0; c < f->C; ++c)
+    if (!vkchain::in_box(f->box, x0 + (size_t)c * f->P))
+      return refused(f, "vk_chain_start: the start of chain " + std::to_string(c) + " is outside the box");
+  VK_SAMPLED_HIP(f, hipSetDevice(ctx->device));
+  VK_SAMPLED_HIP(f, hipMemcpy(f->d_x0, x0, (size_t)f->C * f->P * sizeof(double), hipMemcpyHostToDevice));
+  ChainArgs a = chain_args(f);
+  rc = sampled_launch(f, vk_chain_init_kernel, a.C, kChainBlock, a);
+  if (rc == VK_OK) rc = sampled_evaluate(f, f->C, f->d_res_lnl, f->d_res_chi);
+  a.adopt = 1;
+  if (rc == VK_OK) rc = sampled_launch(f, vk_chain_step_kernel, a.C, kChainBlock, a);
+  if (rc) return sampled_abort(f, rc);
+  VK_SAMPLED_HIP(f, hipStreamSynchronize(ctx->stream));
+  f->started = true;
+  f->err.clear();
+  return VK_OK;
+}
+
+int vk_chain_begin(vk_chain* f, int32_t n_steps, const double* dz, const double* logu, int64_t first_step, int64_t burn, int64_t thin,
+                   int32_t want_history, int32_t* n_kept) {
+  if (!f) return VK_E_ARG;
+  vk_ctx* ctx = f->ctx;
+  if (!dz || !logu) return refused(f, "vk_chain_begin: NULL argument");
+  if (!f->started) return refused(f, "vk_chain_begin: the chains have no start (vk_chain_start)");
+  if (f->in_flight) return refused(f, "vk_chain_begin: the previous block has not been finished (vk_chain_finish)");
+  if (n_steps < 1 || n_steps > vkchain::kBlock) return refused(f, "vk_chain_begin: need 1 <= steps <= 64 in a block");
+  if (first_step < 0 || burn < 0 || thin < 1) return refused(f, "vk_chain_begin: need first_step >= 0, burn >= 0, thin >= 1");
+  int rc = sampled_ready(f, "vk_chain_begin", "chain", true);
+  if (rc) return rc;
+  const size_t C = f->C, P = f->P;
+  VK_SAMPLED_HIP(f, hipSetDevice(ctx->device));
+  // the stream is idle (the block before was finished): plain copies, complete on return
+  VK_SAMPLED_HIP(f, hipMemcpy(f->d_dz, dz, (size_t)n_steps * C * P * sizeof(double), hipMemcpyHostToDevice));
+  VK_SAMPLED_HIP(f, hipMemcpy(f->d_logu, logu, (size_t)n_steps * C * sizeof(double), hipMemcpyHostToDevice));
+  ChainArgs a = chain_args(f);
+  a.dz = f->d_dz;
+  rc = sampled_launch(f, vk_chain_propose_kernel, a.C, kChainBlock, a);
+  int slot = 0;
+  for (int t = 0; t < n_steps && rc == VK_OK; ++t) {
+    rc = sampled_evaluate(f, f->C, f->d_res_lnl, f->d_res_chi);
+    if (rc) break;
+    const bool kept = vkchain::is_kept(first_step + t, burn, thin);
+    a.dz = f->d_dz + (size_t)t * C * P;
+    a.logu = f->d_logu + (size_t)t * C;
+    a.dz_next = t + 1 < n_steps ? a.dz + C * P : nullptr;
+    a.kept = kept ? 1 : 0;
+    const bool hist = kept && want_history;
+    a.hist_x = hist ? f->d_hx + (size_t)slot * C * P : nullptr;
+    a.hist_lnl = hist ? f->d_hl + (size_t)slot * C : nullptr;
+    a.hist_chi2 = hist ? f->d_hc + (size_t)slot * C : nullptr;
+    if (hist) ++slot;
+    rc = sampled_launch(f, vk_chain_step_kernel, a.C, kChainBlock, a);
+  }
+  if (rc) return sampled_abort(f, rc);
+  f->in_flight = n_steps;
+  f->block_kept = slot;
+  if (n_kept) *n_kept = slot;
+  f->err.clear();
+  return VK_OK;
+}
+
+int vk_chain_finish(vk_chain* f, double* x, double* lnl, double* chi2) {
+  if (!f) return VK_E_ARG;
+  vk_ctx* ctx = f->ctx;
+  if (!f->in_flight) return refused(f, "vk_chain_finish: nothing was begun");
+  if (f->block_kept > 0 && (!x || !lnl || !chi2)) {
+    f->in_flight = f->block_kept = 0;
+    f->err = "vk_chain_finish: the block keeps a history: NULL argument";
+    return sampled_abort(f, VK_E_ARG);
+  }
+  const size_t n = (size_t)f->block_kept * f->C;
+  hipError_t e = hipSetDevice(ctx->device);
+  if (e == hipSuccess && n) e = hipMemcpyAsync(x, f->d_hx, n * f->P * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess && n) e = hipMemcpyAsync(lnl, f->d_hl, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess && n) e = hipMemcpyAsync(chi2, f->d_hc, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  f->in_flight = 0;
+  f->block_kept = 0;
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    f->err = std::string("vk_chain_finish: ") + hipGetErrorString(e);
+    return VK_E_HIP;
+  }
+  f->err.clear();
+  return VK_OK;
+}
+
+int vk_chain_state(vk_chain* f, double* x, double* lnl, double* chi2, int64_t* n_accept, int64_t* n_steps, int64_t* n_kept,
+                   double* pivot, double* sum1, double* sum2) {
+  if (!f) return VK_E_ARG;
+  vk_ctx* ctx = f->ctx;
+  if (!f->started || f->in_flight)
+    return refused(f, f->started ? "vk_chain_state: a block begun with vk_chain_begin is awaiting vk_chain_finish"
+                                 : "vk_chain_state: the chains have no start (vk_chain_start)");
+  const size_t C = f->C, P = f->P, T = f->T;
+  VK_SAMPLED_HIP(f, hipSetDevice(ctx->device));
+  // the state block x | lnl | chi2 | pivot | sum1 | sum2 and the three counters are contiguous
+  std::vector<double> h(C * (3 * P + 2 + T));
+  std::vector<long long> n(3 * C);
+  VK_SAMPLED_HIP(f, hipMemcpy(h.data(), f->d_x, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+  VK_SAMPLED_HIP(f, hipMemcpy(n.data(), f->d_acc, n.size() * sizeof(long long), hipMemcpyDeviceToHost));
+  const double *hx = h.data(), *hl = hx + C * P, *hc = hl + C, *hp = hc + C, *h1 = hp + C * P, *h2 = h1 + C * P;
+  for (size_t c = 0; c < C; ++c) {
+    for (size_t j = 0; j < P; ++j) {
+      if (x) x[c * P + j] = hx[j * C + c];
+      if (pivot) pivot[c * P + j] = hp[j * C + c];
+      if (sum1) sum1[c * P + j] = h1[j * C + c];
+      if (sum2)
+        for (size_t k = j; k < P; ++k) {           // the packed triangle, mirrored into a full symmetric matrix
+          const double v = h2[(size_t)vkchain::tri((int)P, (int)j, (int)k) * C + c];
+          sum2[(c * P + j) * P + k] = v;
+          sum2[(c * P + k) * P + j] = v;
+        }
+    }
+    if (lnl) lnl[c] = hl[c];
+    if (chi2) chi2[c] = hc[c];
+    if (n_accept) n_accept[c] = n[c];
+    if (n_steps) n_steps[c] = n[C + c];
+    if (n_kept) n_kept[c] = n[2 * C + c];
+  }
+  f->err.clear();
+  return VK_OK;
+}
+
+}  // extern "C"

@@ -45,13 +45,93 @@ class BestFit:
         return {name: float(v[i]) for name, v in self.params.items()}
 
 
-def _per_problem(name, v, R):
+def _per_problem(name, v, R, who=""):
     a = np.asarray(v, dtype=float)
     if a.ndim == 0:
         return np.full(R, float(a))
     if a.shape != (R,):
-        raise InputError(f"{name}: one value per problem ({R}) or a scalar")
+        raise InputError(f"{who}{name}: one value per problem ({R}) or a scalar")
     return a
+
+
+class _Sampled:
+    """What ``best_fit`` and ``sample_chains`` (``who``; their parameters are ``verb``: "fitted" / "sampled") share: the sampled
+    parameters of a cobaya ``params`` block with their prior box, the checks on them, and the handle of their device loop.  Each
+    caller runs the checks in its own order, so that a call refused for several reasons names the reason it always named."""
+
+    def __init__(self, who, verb, params, fixed):
+        self.who, self.verb = who, verb
+        specs, block_fixed = parse_cobaya_params(params)
+        fixed_in = dict(fixed or {})
+        self.fixed_all = dict(block_fixed)
+        self.fixed_all.update(fixed_in)
+        self.specs = [s for s in specs if s.name not in fixed_in]
+        if not self.specs:
+            raise InputError(f"{who}: every parameter is fixed")
+        self.names = [s.name for s in self.specs]
+        self.lo = np.array([s.lo for s in self.specs])
+        self.hi = np.array([s.hi for s in self.specs])
+
+    def check_columns(self):
+        for name in self.names:
+            if name not in N.ROW_COLUMNS and name != "epsilon":
+                raise InputError(f"{self.who}: {name} has no column of its own in a parameter row and cannot be {self.verb}")
+
+    def check_alpha(self):
+        if "epsilon" in self.names and np.ndim(self.fixed_all.get("alpha", 1)) > 0:
+            raise InputError(f"{self.who}: alpha must be a scalar when epsilon is {self.verb}")
+
+    def fit_options(self, fit, kwargs):
+        fit_options = fit._merged_fit(kwargs)
+        if fit_options["beta_interpolation"] == "likelihood" and not fit.fixed_data:
+            raise InputError(f"{self.who}: beta_interpolation 'likelihood' on a beta-dependent data vector is not supported "
+                             "(its blend of two evaluations runs on the host)")
+        return fit_options
+
+    def per_param(self, what, given, default):
+        """One value per sampled parameter: ``given`` (name -> value) over ``default``."""
+        given = dict(given or {})
+        out = np.array([float(given.pop(n, dv)) for n, dv in zip(self.names, default)])
+        if given:
+            raise InputError(f"{self.who}: {what} names parameters that are not {self.verb}: {sorted(given)}")
+        return out
+
+    def starts(self, given, R, prefix=""):
+        """``(R, d)`` start points inside the prior: ``given`` (name -> scalar or ``(R,)`` array) over the ``ref`` locations."""
+        given = dict(given or {})
+        x0 = np.empty((R, len(self.specs)))
+        for j, s in enumerate(self.specs):
+            x0[:, j] = _per_problem(f"start of {s.name}", given.pop(s.name, s.ref_loc), R, prefix)
+        if given:
+            raise InputError(f"{self.who}: start names parameters that are not {self.verb}: {sorted(given)}")
+        bad = ~(x0 >= self.lo) | ~(x0 <= self.hi)
+        if np.any(bad):
+            p, j = np.argwhere(bad)[0]
+            raise InputError(f"{self.who}: the start of {self.names[j]} ({x0[p, j]}) of problem {p} is outside its prior "
+                             f"[{self.lo[j]}, {self.hi[j]}]")
+        return x0
+
+    def create(self, entry, fit, realisations, kwargs, fit_options, batch, which):
+        """``(engine, handle)`` of ``entry`` (``vk_fit_create`` / ``vk_chain_create``): one problem per row of ``batch`` (the
+        sampled and fixed values its rows start from), against the fit's data vector or realisation ``which[i]``."""
+        model = fit._merged(kwargs)
+        fit._check_supported(model)
+        rows = np.ascontiguousarray(fit._fit_rows(batch, model), dtype=np.float64)
+        cols = np.array([N.ROW_COLUMNS.get(n, N.VK_WALK_EPSILON) for n in self.names], dtype=np.int32)
+        if realisations is None:
+            eng = fit._get_engine(fit._engine_key(model), model["simpson_even"])
+            opts = eng.make_opts(model, fit_options)
+        else:
+            _, _, eng, opts = realisations._plan(kwargs)
+        i32 = C.POINTER(C.c_int32)
+        err = C.create_string_buffer(512)
+        h = getattr(eng._lib, entry)(eng._ctx, C.byref(opts), len(rows), len(cols), cols.ctypes.data_as(i32), N.as_dp(N.f64(self.lo)),
+                                     N.as_dp(N.f64(self.hi)), N.as_dp(rows), float(self.fixed_all.get("alpha", 1)),
+                                     None if realisations is None else which.ctypes.data_as(i32), err, len(err))
+        if not h:
+            msg = err.value.decode()
+            raise (N.NativeError if "device memory" in msg else InputError)(msg)
+        return eng, h
 
 
 def best_fit(fit, params, fixed=None, start=None, step=None, xtol=None, ftol=1e-6, max_iter=None, restarts=1, kwargs=None,
@@ -59,17 +139,9 @@ def best_fit(fit, params, fixed=None, start=None, step=None, xtol=None, ftol=1e-
     """The work of ``CCFFit.best_fit`` (``realisations=None``: against the fit's data vector) and ``Realisations.best_fit``.
     Every argument is checked before the first device call."""
     kwargs = kwargs or {}
-    specs, block_fixed = parse_cobaya_params(params)
-    fixed_in = dict(fixed or {})
-    fixed_all = dict(block_fixed)
-    fixed_all.update(fixed_in)
-    specs = [s for s in specs if s.name not in fixed_in]
-    if not specs:
-        raise InputError("best_fit: every parameter is fixed")
-    names = [s.name for s in specs]
-    for name in names:
-        if name not in N.ROW_COLUMNS and name != "epsilon":
-            raise InputError(f"best_fit: {name} has no column of its own in a parameter row and cannot be fitted")
+    q = _Sampled("best_fit", "fitted", params, fixed)
+    names, fixed_all, d = q.names, q.fixed_all, len(q.names)
+    q.check_columns()
     arrays = {k: v for k, v in fixed_all.items() if np.ndim(v) > 0}
     if realisations is not None:
         if arrays:
@@ -80,65 +152,25 @@ def best_fit(fit, params, fixed=None, start=None, step=None, xtol=None, ftol=1e-
         if len(lengths) > 1:
             raise InputError(f"best_fit: fixed arrays have different lengths: {sorted(lengths)}")
         R = lengths.pop() if lengths else 1
-    if "epsilon" in names and np.ndim(fixed_all.get("alpha", 1)) > 0:
-        raise InputError("best_fit: alpha must be a scalar when epsilon is fitted")
-    fit_options = fit._merged_fit(kwargs)
-    if fit_options["beta_interpolation"] == "likelihood" and not fit.fixed_data:
-        raise InputError("best_fit: beta_interpolation 'likelihood' on a beta-dependent data vector is not supported "
-                         "(its blend of two evaluations runs on the host)")
-    d = len(specs)
-    lo = np.array([s.lo for s in specs])
-    hi = np.array([s.hi for s in specs])
-    start = dict(start or {})
-    x0 = np.empty((R, d))
-    for j, s in enumerate(specs):
-        x0[:, j] = _per_problem(f"start of {s.name}", start.pop(s.name, s.ref_loc), R)
-    if start:
-        raise InputError(f"best_fit: start names parameters that are not fitted: {sorted(start)}")
-    if np.any(~(x0 >= lo) | ~(x0 <= hi)):
-        p, j = np.argwhere(~(x0 >= lo) | ~(x0 <= hi))[0]
-        raise InputError(f"best_fit: the start of {names[j]} ({x0[p, j]}) of problem {p} is outside its prior [{lo[j]}, {hi[j]}]")
-
-    def per_param(what, given, default):
-        given = dict(given or {})
-        out = np.array([float(given.pop(n, dv)) for n, dv in zip(names, default)])
-        if given:
-            raise InputError(f"best_fit: {what} names parameters that are not fitted: {sorted(given)}")
-        return out
-
-    steps = per_param("step", step, [s.proposal for s in specs])
+    q.check_alpha()
+    fit_options = q.fit_options(fit, kwargs)
+    x0 = q.starts(start, R)
+    steps = q.per_param("step", step, [s.proposal for s in q.specs])
     if np.any(~(steps > 0)):
         raise InputError(f"best_fit: every step must be > 0 ({dict(zip(names, steps.tolist()))})")
-    xtols = per_param("xtol", xtol, 1e-4 * steps)
+    xtols = q.per_param("xtol", xtol, 1e-4 * steps)
     if np.any(~(xtols >= 0)) or not float(ftol) >= 0:
         raise InputError("best_fit: xtol and ftol must be >= 0")
     max_iter = 200 * d if max_iter is None else int(max_iter)
     if max_iter < 1 or int(restarts) < 0:
         raise InputError("best_fit: need max_iter >= 1 and restarts >= 0")
-    model = fit._merged(kwargs)
-    fit._check_supported(model)
-    batch = {k: v for k, v in fixed_all.items()}
+    batch = dict(fixed_all)
     batch.update({n: np.ascontiguousarray(x0[:, j]) for j, n in enumerate(names)})
-    rows = np.ascontiguousarray(fit._fit_rows(batch, model), dtype=np.float64)
-    cols = np.array([N.ROW_COLUMNS.get(n, N.VK_WALK_EPSILON) for n in names], dtype=np.int32)
 
     # ---- device
-    if realisations is None:
-        eng = fit._get_engine(fit._engine_key(model), model["simpson_even"])
-        opts = eng.make_opts(model, fit_options)
-        which = None
-    else:
-        _, _, eng, opts = realisations._plan(kwargs)
-        which = np.arange(R, dtype=np.int32)
+    eng, h = q.create("vk_fit_create", fit, realisations, kwargs, fit_options, batch, np.arange(R, dtype=np.int32))
     lib = eng._lib
     i32 = C.POINTER(C.c_int32)
-    err = C.create_string_buffer(512)
-    h = lib.vk_fit_create(eng._ctx, C.byref(opts), R, d, cols.ctypes.data_as(i32), N.as_dp(N.f64(lo)), N.as_dp(N.f64(hi)),
-                          N.as_dp(rows), float(fixed_all.get("alpha", 1)), None if which is None else which.ctypes.data_as(i32),
-                          err, len(err))
-    if not h:
-        msg = err.value.decode()
-        raise (N.NativeError if "device memory" in msg else InputError)(msg)
     x = np.empty((R, d))
     lnl, chi2 = np.empty(R), np.empty(R)
     status, n_iter = np.empty(R, dtype=np.int32), np.empty(R, dtype=np.int32)
