@@ -1046,7 +1046,11 @@ vk_ctx* vk_create(const vk_tables* t, int device, char* err, size_t errlen) {
       xgw.back() = t->w_x[k0];
     }
     ctx->n_xg = (int)(xgw.size() / 2);
-    xgw.resize(xgw.size() + 2, 0.0);      // pad pair
+    // The streaming cells kernel takes this sequence in blocks of four consecutive entries - one shared reciprocal per block
+    // (vk_kernel_cells.h: stream_cell) - whatever groups they belong to: a group is closed where its last node sits, so the
+    // blocks need no table of their own and are the same for every weight rule, ceil(n_xg / 4) of them.  It reads one block
+    // ahead: four pad pairs.
+    xgw.resize(xgw.size() + 8, 0.0);
   }
   const size_t o_xgw = up.add(xgw.data(), xgw.size());
   const size_t o_br = t->n_beta_r > 0 ? up.add(t->beta_r, t->n_beta_r) : 0;

@@ -69,7 +69,8 @@ struct TheoryArgs {
   double xw_max;            // max |kExpScale x_k| (cell_in_table)
   // velocity nodes in groups of equal quadrature weight (Simpson: a handful of distinct values) for the kernels whose node
   // loop is wave-uniform (lanes, cells): the weight multiplies the group's sum once instead of every integrand point
-  const double* xgw;        // [n_xg + 1][2]: {kExpScale x_k in group order, the group's weight at its LAST node else 0} (scalar-cache reads)
+  const double* xgw;        // [n_xg + 4][2]: {kExpScale x_k in group order, the group's weight at its LAST node else 0} (scalar-cache reads;
+                            // zero pad entries: the streaming cells kernel fetches one block of four ahead)
   int n_xg;                 // nodes in xgw: the n_x nodes without those of weight zero (which contribute nothing and could not end a group)
   int n_beta_r;           // 0 = fixed xi tables
   const double* beta_r;

@@ -158,6 +158,49 @@ __device__ __forceinline__ double recip_nr(double x) {
   return fma(y, e, y);
 }
 
+// Shared reciprocals: 1/a, 1/b (, 1/c, 1/d) from ONE v_rcp_f64 - of the operands' product P, refined to third order as in
+// `recip` (y' = y (1 + e + e^2), e = 1 - P y: 1/P to one rounding) and multiplied back by the products of the other operands.
+// A reciprocal costs 3.2 fused multiply-adds of issue time and a multiply 0.8 (profiles/r03/o_inst_rate.txt), so the 3, 6 and 9
+// multiplies of a pair, a triple and a quad are cheaper than the reciprocals they replace; for the streaming cells kernel, whose
+// velocity nodes are independent and wave-uniform (vk_kernel_cells.h), that is 3.4-4.3 fma-units per node against recip_nr's 5.2.
+//   accuracy  every result is a chain of k roundings of products (k = the multiplies on its path, counting those that make P;
+//             the factors an operand shares with P cancel) on top of y's own rounding and e^3 ~ 1e-22:
+//             |rel| <= (k + 1) 2^-53 + e^3 with k = 2 (pair), 4 / 4 / 3 (triple: a, b / c), 5 (quad) - rounding only, where
+//             recip_nr leaves e^2 ~ 3.6e-15 (measured on the hardware by tools/shared_recip_check.hip, asserted in
+//             tests/test_gpu_shared_recip.py).
+//   signs     come out of the products: operands of either sign.
+//   range     the PRODUCT of the block must be a normal number, and so must the partial products: operands of order one (the
+//             streaming integrand's sigma_v(r) / sigma_v is within a few binades of 1; [2^-8, 2^8] is what the check covers, and
+//             2^+-250 per operand would still do for a quad).
+//   poison    a zero, infinite or NaN operand makes every result of its block NaN (or infinite), not only its own.  The callers'
+//             blocks hold velocity nodes of ONE (s, mu) cell, whose sum over the nodes such an operand spoils either way.
+__device__ __forceinline__ void recip_shared2(double a, double b, double& ra, double& rb) {
+  const double P = a * b;
+  const double y = recip(P);
+  ra = y * b;
+  rb = y * a;
+}
+__device__ __forceinline__ void recip_shared3(double a, double b, double c, double& ra, double& rb, double& rc) {
+  const double ab = a * b;
+  const double P = ab * c;
+  const double y = recip(P);
+  const double yc = y * c;         // 1 / (a b)
+  rc = y * ab;
+  ra = yc * b;
+  rb = yc * a;
+}
+__device__ __forceinline__ void recip_shared4(double a, double b, double c, double d, double& ra, double& rb, double& rc, double& rd) {
+  const double ab = a * b, cd = c * d;
+  const double P = ab * cd;
+  const double y = recip(P);
+  const double yab = y * ab;       // 1 / (c d)
+  const double ycd = y * cd;       // 1 / (a b)
+  ra = ycd * b;
+  rb = ycd * a;
+  rc = yab * d;
+  rd = yab * c;
+}
+
 // Twice the refined 1/sqrt(x) in four instructions: y' = y (3 - x y^2) / 2 is Newton's step, and the callers want 2 y' anyway
 // once every length they feed in is halved (an exact power-of-two rescaling on the host side of the loop: X = r'^2 / 4,
 // 2 y' = 4 / r', X * 2y' = r', (num / 2) * 2y' = 2 mu_r - see vk_kernel_fast.h: uni_accum).  Same accuracy as rsqrt_nr.

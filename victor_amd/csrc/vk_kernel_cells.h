@@ -103,6 +103,11 @@ __device__ __forceinline__ void finish_point_ranges(const TheoryArgs& a, long lo
 // the next, kWaves from a bin to the next).  The 2 NL sums are folded together (fold32, fold16: two values per addition) down
 // to rows of 16 lanes, the rows to octets with one exchange, the octets by DPP: 50 vector instructions for NL = 3 where six
 // full-wave DPP chains took 150.  Lane -> sum it ends up with (NL = 3): bits 5, 4, 3 of the lane = (second bin, l & 1, l == 2).
+// a wave-uniform double that the compiler holds in a vector register pair (it was computed there), moved to a scalar pair
+__device__ __forceinline__ double uniform_f64(double v) {
+  return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
+}
+
 template <int NL>
 __device__ __forceinline__ void project_trip(double g, bool first, bool second, const double* w_i, int n_mu, double* acc, int lstride, int lane) {
   const double ga = first ? g : 0.0, gb = second ? g : 0.0;
@@ -132,6 +137,79 @@ __device__ __forceinline__ void project_trip(double g, bool first, bool second, 
   }
   x = vkm::octet_sum(x);
   if (mine) acc[l_mine * lstride + (lane >> 5) * kWaves] += x;
+}
+
+// Velocity integral of one (s, mu) cell of the streaming modes: sum over the weight groups of w_group * sum_k p_k / SV_k, the
+// nodes in the order of TheoryArgs::xgw.  The nodes of a cell are independent and the loop over them is wave-uniform, so they
+// are taken in BLOCKS of kNodeBlock = 4 consecutive table entries (stream_block): the heads of the block's nodes (uni_point_head:
+// geometry, records, ynum), ONE shared third-order reciprocal for their 1/SV (vkm::recip_shared4: one v_rcp_f64 and 9 multiplies
+// where four recip_nr took four v_rcp_f64 and 8 fma), their tails (uni_point_tail: the Gaussian), then gs = fma(1/SV_k, p_k, gs)
+// node by node in table order, a group's weight applied where its last node sits - a scalar branch on the node's weight word as
+// before.  A block may therefore straddle weight groups, and the blocks are the same for every weight rule: n_xg / 4 quads and
+// one triple, pair or single node (the one-node uni_point) for what is left at the end of the table - ceil(n_xg / 4) reciprocals
+// per cell, 13 for 50 nodes.  The block structure depends on the context's table alone: the same for every trip, range split,
+// batch size and position in the batch.
+// The next block's entries are fetched through the scalar cache while the current one is worked on (the table is padded to
+// n_xg + 4 entries).  CL: the clamp pair of the interval coordinate (0: the trip lies inside the table, see cell_in_table).
+// Registers: a finished head is three doubles per lane.  Each head's results are pinned where it ends (an empty asm, and a
+// scheduling barrier behind it) - otherwise the compiler sinks the xi^r cubics of a head past the reciprocal and carries their
+// coefficients, 24 registers per node for the anisotropic sum, instead of the one value.
+constexpr int kNodeBlock = 4;
+
+template <int W, int NLR, int GRID, int FD, int CL, int SVA>
+__device__ __forceinline__ void stream_block(const double* __restrict__ lds, const FastConsts& fc, const FastPoint& fp, double s_par,
+                                             double sperp2, double sperp2x, const VelocityNode (&c)[kNodeBlock], double& g, double& gs) {
+  UniHead h[W];
+  double inv[W], p[W];
+#pragma unroll
+  for (int i = 0; i < W; ++i) {
+    h[i] = uni_point_head<NLR, GRID, FD, 1, CL, 0, SVA>(lds, fc, 0.0, fma(-c[i].x, fp.Bk, s_par), sperp2, c[i].x, fp.fa, sperp2x);
+    asm volatile("" : "+v"(h[i].SV), "+v"(h[i].ynum), "+v"(h[i].xi1));
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  if (W == 4) vkm::recip_shared4(h[0].SV, h[1 % W].SV, h[2 % W].SV, h[3 % W].SV, inv[0], inv[1 % W], inv[2 % W], inv[3 % W]);
+  if (W == 3) vkm::recip_shared3(h[0].SV, h[1 % W].SV, h[2 % W].SV, inv[0], inv[1 % W], inv[2 % W]);
+  if (W == 2) vkm::recip_shared2(h[0].SV, h[1 % W].SV, inv[0], inv[1 % W]);
+  if (W == 1) inv[0] = vkm::recip_nr(h[0].SV);               // head, recip_nr, tail: uni_point
+#pragma unroll
+  for (int i = 0; i < W; ++i) p[i] = uni_point_tail<0>(lds, h[i], inv[i], 0u);
+#pragma unroll
+  for (int i = 0; i < W; ++i) {
+    gs = fma(inv[i], p[i], gs);
+    if (c[i].last != 0) {            // wave-uniform: a scalar branch, taken at the last node of a group
+      asm volatile("" ::: "memory");            // (keeps the compiler from turning it into per-lane selects)
+      g = fma(c[i].w, gs, g);
+      gs = 0.0;
+    }
+  }
+}
+
+template <int NLR, int GRID, int FD, int CL, int SVA>
+__device__ __forceinline__ double stream_cell(const TheoryArgs& a, const double* __restrict__ lds, const FastConsts& fc, const FastPoint& fp,
+                                              double s_par, double sperp2, double sperp2x) {
+  constexpr int W = kNodeBlock;
+  double g = 0.0, gs = 0.0;
+  // the table's address as a fresh value per cell: the first block is then LOADED at the top of every trip (one scalar load)
+  // instead of being kept across the trips - sixteen scalar registers the kernel does not have, i.e. sixteen v_readlane per trip
+  const double* xgw = a.xgw;
+  asm volatile("" : "+s"(xgw));
+  VelocityNode nx[W];
+#pragma unroll
+  for (int i = 0; i < W; ++i) nx[i] = load_node(xgw, i);
+  const int quads = a.n_xg / W;
+  for (int b = 0; b < quads; ++b) {
+    VelocityNode c[W];
+#pragma unroll
+    for (int i = 0; i < W; ++i) c[i] = nx[i];
+#pragma unroll
+    for (int i = 0; i < W; ++i) nx[i] = load_node(xgw, W * b + W + i);           // one block ahead
+    stream_block<W, NLR, GRID, FD, CL, SVA>(lds, fc, fp, s_par, sperp2, sperp2x, c, g, gs);
+  }
+  const int rest = a.n_xg - quads * W;                  // wave-uniform; its nodes are in nx already
+  if (rest == 3) stream_block<3, NLR, GRID, FD, CL, SVA>(lds, fc, fp, s_par, sperp2, sperp2x, nx, g, gs);
+  else if (rest == 2) stream_block<2, NLR, GRID, FD, CL, SVA>(lds, fc, fp, s_par, sperp2, sperp2x, nx, g, gs);
+  else if (rest == 1) stream_block<1, NLR, GRID, FD, CL, SVA>(lds, fc, fp, s_par, sperp2, sperp2x, nx, g, gs);
+  return g;
 }
 
 // 5 workgroups per CU for the streaming mode (<= 96 VGPRs); the from_data and dispersion modes need more registers and
@@ -184,8 +262,28 @@ __global__ __launch_bounds__(kBlock, (MODE == kModeStreaming && !SVA) || MODE ==
     const int jf = (int)__umulhi((unsigned)c0, a.nmu_magic);         // first s bin it touches
     const int nb = (int)__umulhi((unsigned)(c1 - 1), a.nmu_magic) - jf + 1;
     const double* row = a.params + point * VK_NPAR;
-    const PointScalars ps = point_scalars(a, row);
-    const FastPoint fp = make_fast_point(ps, fc, kHalf);
+    // The streaming modes' node loop works on blocks of four nodes (stream_cell) and needs the registers of three finished heads
+    // beside the one in progress: for them (kStream; the other modes' code is as it was) values that only LOOK per-lane are moved
+    // to scalar registers, and what the projection needs of the cell's indices is formed again behind the loop.
+    constexpr bool kStream = !mode_has_da(MODE);
+    PointScalars ps = point_scalars(a, row);
+    // the NaN carrier of the row, formed HERE and kept as a scalar: left to itself the compiler forms it where it is used, behind
+    // the node loops, and carries the row's values it is the sum of through them in sixteen vector registers
+    if (kStream) ps.poison = uniform_f64(ps.poison);
+    FastPoint fp = make_fast_point(ps, fc, kHalf);
+    // what a trip uses once - not the node loop - out of the vector registers: wave-uniform, but computed on the vector ALU
+    if (kStream) {
+      fp.k_perp = uniform_f64(fp.k_perp);
+      fp.k_par = uniform_f64(fp.k_par);
+    }
+    const double xi_max = kStream ? uniform_f64(a.xw_max * fabs(fp.Bk)) : 0.0;
+    const double rlo2 = kStream ? uniform_f64(fc.rlo2) : 0.0, rhi2 = kStream ? uniform_f64(fc.rhi2) : 0.0;
+    FastConsts fcs = fc;               // the node loop's copy: offset and clamp bounds of the interval coordinate as scalars
+    if (kStream && GRID == 0) {
+      fcs.off = uniform_f64(fc.off);
+      fcs.t_lo = uniform_f64(fc.t_lo);
+      fcs.n_eps = uniform_f64(fc.n_eps);
+    }
     // the V cubics carry the point's factor: AVk (streaming), -Gk (dispersion, see disp_value), none (kaiser / euclid_special)
     constexpr int PV = MODE == kModeKaiser ? 0 : 1;
     __syncthreads();      // every wave is done with the previous item's records and accumulators
@@ -196,18 +294,21 @@ __global__ __launch_bounds__(kBlock, (MODE == kModeStreaming && !SVA) || MODE ==
     __syncthreads();
     VK_STAMP(a, 2);
     for (int base = c0 + 64 * wave; base < c1; base += 64 * kWaves) {
-      const int e = base + lane;
-      const bool live = e < c1;
-      const unsigned ec = (unsigned)(live ? e : c1 - 1);
-      // ec / n_mu: s bin major (ec / n_s: mu major for xi_out; a single s bin has no 32-bit magic number - ceil(2^32 / 1) - and
-      // needs none)
-      const int hi = xi_out ? (a.n_s == 1 ? (int)ec : (int)__umulhi(ec, a.ns_magic)) : (int)__umulhi(ec, a.nmu_magic);
-      const int lo = (int)ec - hi * (xi_out ? a.n_s : a.n_mu);
-      const int j = xi_out ? lo : hi;
-      const int i = xi_out ? hi : lo;
-      const int jj = j - jf;
+      // (s bin, mu) of this lane's cell: ec / n_mu, s bin major (ec / n_s: mu major for xi_out; a single s bin has no 32-bit magic
+      // number - ceil(2^32 / 1) - and needs none)
+      auto cell_of = [&](int e_, bool& live_, int& i_, int& j_) {
+        live_ = e_ < c1;
+        const unsigned ec = (unsigned)(live_ ? e_ : c1 - 1);
+        const int hi = xi_out ? (a.n_s == 1 ? (int)ec : (int)__umulhi(ec, a.ns_magic)) : (int)__umulhi(ec, a.nmu_magic);
+        const int lo = (int)ec - hi * (xi_out ? a.n_s : a.n_mu);
+        j_ = xi_out ? lo : hi;
+        i_ = xi_out ? hi : lo;
+      };
+      int i0, j;
+      bool live0;
+      cell_of(base + lane, live0, i0, j);
       const double sj = l_s[j];
-      const vk_d2 mm = *reinterpret_cast<const vk_d2*>(l_mu + 2 * i);
+      const vk_d2 mm = *reinterpret_cast<const vk_d2*>(l_mu + 2 * i0);
       const double s_perp = sj * fp.k_perp * mm.y;
       const double sperp2 = s_perp * s_perp;
       const double sperp2x = sperp2 * fp.fp2;      // from_data only
@@ -215,7 +316,7 @@ __global__ __launch_bounds__(kBlock, (MODE == kModeStreaming && !SVA) || MODE ==
       double g = 0.0;
       // trips whose 64 x 50 radii all fall inside the table skip the clamp pair of the interval coordinate (see the lanes
       // kernel; a trip that holds a mu = 1 cell reaches r < 0.01 and keeps it)
-      const bool inside = !mode_has_da(MODE) && !__any(!cell_in_table(fc, s_par, sperp2, a.xw_max * fabs(fp.Bk)));
+      const bool inside = kStream && !__any(!cell_in_table(rlo2, rhi2, s_par, sperp2, xi_max));
       double gs = 0.0;
       if (MODE == kModeKaiser) {
         g = kaiser_value<NLR, GRID>(lds, lds + pl.da, fc, fp, ps.M, ps.Q, a.niter, a.coord_shift != 0, a.kaiser_approx != 0,
@@ -233,43 +334,25 @@ __global__ __launch_bounds__(kBlock, (MODE == kModeStreaming && !SVA) || MODE ==
           }
         }
       } else if (inside) {
-        VelocityNode nxt = load_node(a.xgw, 0);
-        for (int k = 0; k < a.n_xg; ++k) {
-          const VelocityNode xw = nxt;
-          nxt = load_node(a.xgw, k + 1);            // one node ahead (the table has n_xg + 1 entries)
-          double inv_sv;
-          const double p = uni_point<NLR, GRID, MODE == kModeFromData, 1, 0, 0, SVA>(lds, fc, 0.0, fma(-xw.x, fp.Bk, s_par), sperp2, xw.x, fp.fa,
-                                                                            sperp2x, 0u, inv_sv);
-          gs = fma(inv_sv, p, gs);
-          if (xw.last != 0) {            // wave-uniform: a scalar branch, taken at the last node of a group
-            asm volatile("" ::: "memory");            // (keeps the compiler from turning it into per-lane selects)
-            g = fma(xw.w, gs, g);
-            gs = 0.0;
-          }
-        }
+        g = stream_cell<NLR, GRID, MODE == kModeFromData, 0, SVA>(a, lds, fcs, fp, s_par, sperp2, sperp2x);
       } else {
-        VelocityNode nxt = load_node(a.xgw, 0);
-        for (int k = 0; k < a.n_xg; ++k) {
-          const VelocityNode xw = nxt;
-          nxt = load_node(a.xgw, k + 1);            // one node ahead (the table has n_xg + 1 entries)
-          double inv_sv;
-          const double p = uni_point<NLR, GRID, MODE == kModeFromData, 1, 1, 0, SVA>(lds, fc, 0.0, fma(-xw.x, fp.Bk, s_par), sperp2, xw.x, fp.fa,
-                                                                            sperp2x, 0u, inv_sv);
-          gs = fma(inv_sv, p, gs);
-          if (xw.last != 0) {            // wave-uniform: a scalar branch, taken at the last node of a group
-            asm volatile("" ::: "memory");            // (keeps the compiler from turning it into per-lane selects)
-            g = fma(xw.w, gs, g);
-            gs = 0.0;
-          }
-        }
+        g = stream_cell<NLR, GRID, MODE == kModeFromData, GRID == 0 ? 2 : 1, SVA>(a, lds, fcs, fp, s_par, sperp2, sperp2x);
       }
+      // streaming modes: the cell's indices once more, from a fresh thread index - four integers per lane less to carry through
+      // the node loops
+      const int lane2 = kStream ? late_tid() & 63 : lane;
+      const int e = base + lane2;
+      int i = i0, j2 = j;
+      bool live = live0;
+      if (kStream) cell_of(e, live, i, j2);
       if (xi_out) {                                  // xi^s = sum - 1 (ccf_model.py:690), cell e = (i, j) of out[point][n_mu][n_s]
         if (live) a.out[point * (long long)all_cells + e] = g - 1.0 + ps.poison;
         continue;
       }
       // projection: this trip's cells belong to local bin jj0 or jj0 + 1 (the latter may be the spill bin)
+      const int jj = j2 - jf;
       const int jj0 = __builtin_amdgcn_readfirstlane(jj);
-      project_trip<NL>(g, live && jj == jj0, live && jj != jj0, l_w + i, a.n_mu, l_acc + jj0 * kWaves + wave, slots * kWaves, lane);
+      project_trip<NL>(g, live && jj == jj0, live && jj != jj0, l_w + i, a.n_mu, l_acc + jj0 * kWaves + wave, slots * kWaves, lane2);
     }
     if (xi_out) return;
     // this range's share of the theory vector is complete in LDS once every wave has finished its trips

@@ -69,6 +69,18 @@ __device__ __forceinline__ double vmax_f64(double a, double b) {
   return r;
 }
 
+// the same with the bound in a scalar register pair (wave-uniform bounds of kernels that are short of vector registers)
+__device__ __forceinline__ double vmin_f64_s(double a, double b) {
+  double r;
+  asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "s"(b));
+  return r;
+}
+__device__ __forceinline__ double vmax_f64_s(double a, double b) {
+  double r;
+  asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "s"(b));
+  return r;
+}
+
 __device__ __forceinline__ const double* lds_at(const double* base, int byte_off) {
   return reinterpret_cast<const double*>(reinterpret_cast<const char*>(base) + byte_off);
 }
@@ -132,6 +144,12 @@ __device__ __forceinline__ bool cell_in_table(const FastConsts& fc, double s_par
   const double spx = fabs(s_par) + xi_max;
   const double spn = fmax(fabs(s_par) - xi_max, 0.0);
   return (fma(spn, spn, sperp2) >= fc.rlo2) && (fma(spx, spx, sperp2) < fc.rhi2);
+}
+// the same test for a caller that holds the two bounds itself (the streaming cells kernel: as scalars)
+__device__ __forceinline__ bool cell_in_table(double rlo2, double rhi2, double s_par, double sperp2, double xi_max) {
+  const double spx = fabs(s_par) + xi_max;
+  const double spn = fmax(fabs(s_par) - xi_max, 0.0);
+  return (fma(spn, spn, sperp2) >= rlo2) && (fma(spx, spx, sperp2) < rhi2);
 }
 
 // Stage the batch-constant parts of the records: sigma_v and V always, xi^r_l when it does not depend on beta;
@@ -301,13 +319,14 @@ __device__ __forceinline__ FastPoint make_fast_point(const PointScalars& ps, con
 // Record and local coordinate of a radius: `x` is the interval coordinate t = r' + off (GRID 0) or the radius u = r'
 // itself (GRID 1, union grid), not yet clamped.
 // CL = 0: the caller has shown that t lies inside [t_lo, n_eps] for every lane (cell_in_table), the clamp pair is dropped.
+// CL = 2: the clamp pair with its bounds in scalar registers (the caller made fc.t_lo and fc.n_eps wave-uniform scalars).
 template <int NLR, int GRID, int CL = 1, int EXPT = 0>
 __device__ __forceinline__ const double* locate(const double* __restrict__ lds, const FastConsts& fc, double x,
                                                 double& tq, int& qi) {
   constexpr int stride = uni_stride(NLR);
   constexpr int roff = recs_off<EXPT>();
   if (GRID == 0) {
-    const double t = CL ? vmin_f64(vmax_f64(x, fc.t_lo), fc.n_eps) : x;
+    const double t = CL == 2 ? vmin_f64_s(vmax_f64_s(x, fc.t_lo), fc.n_eps) : (CL ? vmin_f64(vmax_f64(x, fc.t_lo), fc.n_eps) : x);
     tq = __builtin_amdgcn_fract(t);
     qi = (int)t;
     return lds_at(lds + roff, __mul24(qi, stride * 8));
@@ -364,10 +383,16 @@ __device__ __forceinline__ double sv_aniso(const double* __restrict__ lds, const
 // PV = 1: the V cubics in the records already carry the per-point factor AVh (the kernels that own a point per workgroup
 // rescale them once per work item, scale_uni_v) - one multiply less per integrand point.
 // SVA = 1: sigma_v from the anisotropic template's bicubic patches (sv_aniso) instead of the record's cubic; lattice form only.
+// The point comes in two halves so that a caller whose nodes are independent can take the reciprocals of several of them from
+// one v_rcp_f64 in between (vkm::recip_shared*; the streaming cells kernel, vk_kernel_cells.h):
+//   uni_point_head  geometry, records, everything that does not need 1/SV: {SV, ynum, xi1} of the node
+//   uni_point_tail  the Gaussian at 1/SV, times 1 + xi^r
+// uni_point itself is head, vkm::recip_nr, tail - the one-node form of every other caller.
+struct UniHead { double SV, ynum, xi1; };
+
 template <int NLR, int GRID, int FD, int PV = 0, int CL = 1, int EXPT = 0, int SVA = 0>
-__device__ __forceinline__ double uni_point(const double* __restrict__ lds, const FastConsts& fc, double AVh,
-                                            double num, double sperp2, double xk, double fa, double sperp2x,
-                                            unsigned lane_off, double& inv_sv) {
+__device__ __forceinline__ UniHead uni_point_head(const double* __restrict__ lds, const FastConsts& fc, double AVh,
+                                                  double num, double sperp2, double xk, double fa, double sperp2x) {
   const double X = fma(num, num, sperp2);
   const double yy = vkm::rsqrt_nr_x2(X);
   const double mu2 = num * yy;
@@ -384,7 +409,7 @@ __device__ __forceinline__ double uni_point(const double* __restrict__ lds, cons
     const double Xx = fma(rp, rp, sperp2x);
     const double yyx = vkm::rsqrt_nr_x2(Xx);
     mu_x = rp * yyx;
-    rec = locate<NLR, GRID, 1, EXPT>(lds, fc, GRID == 0 ? fma(Xx, yyx, fc.off) : Xx * yyx, tq, qi);
+    rec = locate<NLR, GRID, CL == 2 ? 2 : 1, EXPT>(lds, fc, GRID == 0 ? fma(Xx, yyx, fc.off) : Xx * yyx, tq, qi);
   }
   double xi1 = cubic_b128(rec + 8, tq);
   if (NLR > 1) {
@@ -395,9 +420,26 @@ __device__ __forceinline__ double uni_point(const double* __restrict__ lds, cons
       xi1 = fma(fma(cubic_b128(rec + 16, tq), m2, cubic_b128(rec + 12, tq)), m2, xi1);
     }
   }
-  inv_sv = vkm::recip_nr(SV);
-  const double e = vkm::exp_gauss<EXPT>(ynum, inv_sv, lds + kEtabOff, lane_off);
-  return e * xi1;
+  UniHead h;
+  h.SV = SV;
+  h.ynum = ynum;
+  h.xi1 = xi1;
+  return h;
+}
+
+template <int EXPT = 0>
+__device__ __forceinline__ double uni_point_tail(const double* __restrict__ lds, const UniHead& h, double inv_sv, unsigned lane_off) {
+  const double e = vkm::exp_gauss<EXPT>(h.ynum, inv_sv, lds + kEtabOff, lane_off);
+  return e * h.xi1;
+}
+
+template <int NLR, int GRID, int FD, int PV = 0, int CL = 1, int EXPT = 0, int SVA = 0>
+__device__ __forceinline__ double uni_point(const double* __restrict__ lds, const FastConsts& fc, double AVh,
+                                            double num, double sperp2, double xk, double fa, double sperp2x,
+                                            unsigned lane_off, double& inv_sv) {
+  const UniHead h = uni_point_head<NLR, GRID, FD, PV, CL, EXPT, SVA>(lds, fc, AVh, num, sperp2, xk, fa, sperp2x);
+  inv_sv = vkm::recip_nr(h.SV);
+  return uni_point_tail<EXPT>(lds, h, inv_sv, lane_off);
 }
 
 // The dispersion model (ccf_model.py:658-671) on the same records: zero-mean Gaussian pdf of width sigma_v SV(r), the
