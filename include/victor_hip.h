@@ -17,6 +17,9 @@
  *                        data file (simulation_number, victor/ccf_fit.py:59-61,93-100)
  *   vk_joint_cov_eval_realisations  the same for a joint fit under one covariance: realisation m
  *                        of every block's own file (victor/ccf_fit.py:59-61,93-100,325-483)
+ *   vk_fit_create_joint, vk_chain_create_joint   a host optimiser / cobaya (victor/likelihoods/
+ *                        CCFLikelihood.py:32) around that joint likelihood, data vectors or every
+ *                        joint realisation: the loops of vk_fit_run / vk_chain_begin over a joint fit
  *   vk_create            CCFModel.__init__ / CCFFit.__init__ table set-up
  *                        victor/ccf_model.py:33-97, victor/ccf_fit.py:15-42
  *                        (the host has already turned every spline into explicit
@@ -554,6 +557,34 @@ int vk_joint_cov_eval_device_async(vk_joint_cov* h, vk_ctx* const* ctxs, int32_t
  *   contexts with different n_real and an index of which out of range. */
 int vk_joint_cov_eval_realisations(vk_joint_cov* h, vk_ctx* const* ctxs, int32_t n_ctx, const vk_eval_opts* opts,
                                    const double* params, int64_t n, const int32_t* which, double* lnl, double* chi2);
+
+/* ---- best fits and Metropolis chains of a joint fit: the data vectors, or every joint realisation ------------------------
+ * The handles of the two sections above over a joint fit instead of one context: a problem (a chain) samples ONE parameter row
+ * for all blocks, and every other call of those sections (run, start, begin, finish, state, last_error, destroy) serves the
+ * handle unchanged.  ctxs [n_ctx]: the blocks' contexts, lead first, all on one device, each with a data vector.
+ *   cov == NULL   block-diagonal: lnL and chi2 of the blocks add in block order and a failed block fails the row, the rule of
+ *                 vk_joint_eval_device_async;
+ *   otherwise     the joint vector under the handle's covariance, ctxs[0] the context it was created with and the blocks'
+ *                 sizes the handle's, as vk_joint_cov_eval_device_async checks them.
+ *   which == NULL the blocks' own data vectors; otherwise problem i runs against joint realisation which[i] - realisation
+ *                 which[i] of EVERY block (vk_set_realisations on each context, the same n_real on all of them).
+ * The other arguments and every check are those of the single-context forms, applied to every context.  An evaluation makes
+ * the launches of the joint entry points - block-diagonal against realisations: each block's theory and realisation chi-square
+ * launches on its own stream (pairs mode) and the block-order sum behind them; under a covariance: the launches of
+ * vk_joint_cov_eval_realisations in pairs mode - enqueued on the blocks' streams with the loop on the lead's: no host
+ * synchronisation and no graph inside an iteration or a block of steps, and the same bits as those entry points return for
+ * the same rows in the same launches.  Block-diagonal against realisations no host entry point makes these launches: each
+ * block's pair is that of vk_eval_realisations in pairs mode, and the device's block-order sum returns the bits of the same sum
+ * of those results in IEEE doubles on the host (0 + a_0 + a_1 + ...; a non-finite lnL reads -inf, inf).
+ * Refused with NULL and the text in err: a NULL entry of ctxs, contexts on different devices, a context without a data vector,
+ * a block count or size that differs from the handle's, (with which) a context without realisations or with another n_real, an
+ * index out of range, a joint vector that needs more than 160 KiB of LDS. */
+vk_fit* vk_fit_create_joint(vk_ctx* const* ctxs, int32_t n_ctx, vk_joint_cov* cov, const vk_eval_opts* opts,
+                            int32_t n_problems, int32_t n_params, const int32_t* columns, const double* lo, const double* hi,
+                            const double* base_rows, double alpha, const int32_t* which, char* err, size_t errlen);
+vk_chain* vk_chain_create_joint(vk_ctx* const* ctxs, int32_t n_ctx, vk_joint_cov* cov, const vk_eval_opts* opts,
+                                int32_t n_chains, int32_t n_params, const int32_t* columns, const double* lo, const double* hi,
+                                const double* base_rows, double alpha, const int32_t* which, char* err, size_t errlen);
 
 /* ---- many one-point callers sharing one GPU: mailboxes in shared memory -----------------------------------------------
  * The reference is sampled by cobaya, which asks for ONE likelihood per call (victor/likelihoods/CCFLikelihood.py:32-39); more

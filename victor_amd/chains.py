@@ -1,5 +1,7 @@
 """Metropolis chains of the data vector and of every realisation, stepped on the GPU: ``CCFFit.sample_chains`` and
-``Realisations.sample_chains``.
+``Realisations.sample_chains``; of a joint fit, ``JointFit.sample_chains`` and ``JointRealisations.sample_chains`` (one parameter
+row for all blocks: ``fit`` is the ``JointFit`` below, the definition route runs over its ``log_likelihood_batch`` /
+``JointRealisations.log_likelihood_pairs``, the device route through ``vk_chain_create_joint``).
 
 The reference is sampled by cobaya, one likelihood per call and one data vector at a time (reference:
 ``victor/likelihoods/CCFLikelihood.py:32``).  Mock validation wants the posterior of EVERY mock beside its best fit: here
@@ -89,7 +91,7 @@ class Chains:
         self.burn, self.thin, self.keep_chain = burn, thin, keep_chain
         self._evaluate = evaluator
         self._dev = device_handle
-        self._engine = self._realisations = None
+        self._refresh = self._fit = None
         self._lo = np.array([s.lo for s in specs])
         self._hi = np.array([s.hi for s in specs])
         self._dz = self._logu = None
@@ -228,8 +230,8 @@ class Chains:
         n_steps = int(n_steps)
         if n_steps < 0:
             raise InputError("sample_chains: n_steps must be >= 0")
-        if self._dev and self._realisations is not None:
-            self._realisations._upload(self._engine)      # another object's realisations may have been set on the engine since
+        if self._dev and self._refresh is not None:
+            self._refresh()                               # another object's realisations may have been set on the engine since
         if n_steps:
             (self._run_device if self._dev else self._run_host)(n_steps)
         if self._dev:
@@ -369,11 +371,12 @@ def sample_chains(fit, params, n_steps, walkers=8, seed=0, fixed=None, start=Non
                 return fit.log_likelihood_batch(batch_of(x), **kwargs)
     else:
         evaluator = None
-        eng, h = q.create("vk_chain_create", fit, realisations, kwargs, fit_options, batch_of(x0), which)
-        handle = (eng._lib, h)
+        lib, h, refresh = q.create("vk_chain_create", fit, realisations, kwargs, fit_options, batch_of(x0), which)
+        handle = (lib, h)
     ch = Chains(names, specs, fixed_out, R, W, rng, width, burn, thin, bool(keep_chain), evaluator, handle)
     if handle:
-        ch._engine, ch._realisations = eng, realisations     # the context the handle runs on
+        ch._refresh = refresh                                # (keeps the realisations and the contexts the handle runs on)
+        ch._fit = fit                                        # (a joint fit owns the covariance handles the chains read)
     if handle:
         ch._check(handle[0].vk_chain_start(handle[1], N.as_dp(N.f64(x0))), "vk_chain_start")
     else:

@@ -1504,8 +1504,8 @@ struct BlockOut {
   double *lnl, *chi2, *theory;
 };
 
-template <class Out>
-static int fan_out(vk_ctx* const* ctxs, int n_ctx, const vk_eval_opts* opts, const double* d_par, long long n, Out out) {
+template <class Launch>
+static int fan_out_with(vk_ctx* const* ctxs, int n_ctx, Launch launch) {
   vk_ctx* lead = ctxs[0];
   for (int q = 0; q < n_ctx; ++q)
     if (!ctxs[q]->ev_joint) VK_HIP(lead, hipEventCreateWithFlags(&ctxs[q]->ev_joint, hipEventDisableTiming));
@@ -1513,14 +1513,21 @@ static int fan_out(vk_ctx* const* ctxs, int n_ctx, const vk_eval_opts* opts, con
   for (int q = 0; q < n_ctx; ++q) {
     vk_ctx* c = ctxs[q];
     if (q > 0) VK_HIP(lead, hipStreamWaitEvent(c->stream, lead->ev_joint, 0));
-    const BlockOut o = out(q);
-    const int rc = vk_eval_batch_device_async(c, opts, d_par, n, o.lnl, o.chi2, o.theory);
+    const int rc = launch(q, c);
     if (rc) {
       if (c != lead) lead->err = c->err;
       return rc;
     }
   }
   return VK_OK;
+}
+
+template <class Out>
+static int fan_out(vk_ctx* const* ctxs, int n_ctx, const vk_eval_opts* opts, const double* d_par, long long n, Out out) {
+  return fan_out_with(ctxs, n_ctx, [&](int q, vk_ctx* c) {
+    const BlockOut o = out(q);
+    return vk_eval_batch_device_async(c, opts, d_par, n, o.lnl, o.chi2, o.theory);
+  });
 }
 
 // the lead stream waits for every block's stream
@@ -1643,6 +1650,98 @@ int vkh::enqueue_realisations(vk_ctx* ctx, const vk_eval_opts* opts, const doubl
     VK_HIP(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
     ctx->pending = true;
   }
+  return VK_OK;
+}
+
+// ---- joint fits against the blocks' realisations: what the host entry points share with vk_sampled.hip (vk_host.h) ----------
+static size_t joint_real_lds(const vk_joint_cov* h) {
+  return joint_real_lds_doubles(h->NT, (int)h->block_n.size(), h->n_beta) * sizeof(double);
+}
+
+int vkh::check_joint(const vk_joint_cov* h, vk_ctx* const* ctxs, int n_ctx, bool need_real) {
+  vk_ctx* lead = ctxs[0];
+  int rc = check_blocks(lead, h, ctxs, n_ctx, need_real);
+  if (rc || !need_real) return rc;
+  if (h) {
+    if (joint_real_lds(h) > 160 * 1024)
+      return fail(lead, VK_E_ARG, "joint covariance: %d entries and %d slices need more than 160 KiB of LDS", h->NT, h->n_beta);
+    return VK_OK;
+  }
+  for (int q = 0; q < n_ctx; ++q) {
+    rc = check_real_lds(ctxs[q]);
+    if (rc) {
+      if (q > 0) lead->err = ctxs[q]->err;
+      return rc;
+    }
+  }
+  return VK_OK;
+}
+
+// real, under a covariance: theory [m][NT] | -1/2 log det [m] | ints: sign test [m], the slice sort's lo, rank, perm [m] and
+// histograms [chunks + 1][n_beta]
+size_t vkh::joint_workspace_doubles(const vk_joint_cov* h, vk_ctx* const* ctxs, int n_ctx, long long m, bool real) {
+  if (!h) return vk_joint_workspace_doubles(ctxs, n_ctx, m);       // real or not: per block lnl | chi2 | theory
+  if (!real) return vk_joint_cov_workspace_doubles(h, m);
+  const size_t chunks = (size_t)(m + kJointSortChunk - 1) / kJointSortChunk;
+  const size_t ints = (size_t)m * 4 + (chunks + 1) * h->n_beta;
+  return (size_t)m * (h->NT + 1) + (ints + 1) / 2 + 1;
+}
+
+vkh::JointRealWs vkh::joint_real_carve(const vk_joint_cov* h, double* d_ws, long long m_max) {
+  JointRealWs w{};
+  w.th = d_ws;
+  w.fac = d_ws + (size_t)m_max * h->NT;
+  w.bad = reinterpret_cast<int*>(w.fac + m_max);
+  w.sort = w.bad + m_max;
+  w.sort_stride = m_max;
+  return w;
+}
+
+int vkh::enqueue_joint_cov_realisations(vk_joint_cov* h, vk_ctx* const* ctxs, int n_ctx, const vk_eval_opts* opts, const double* d_par,
+                                        long long m, const int32_t* d_which, double* d_lnl, double* d_chi, const JointRealWs& w) {
+  vk_ctx* lead = ctxs[0];
+  VK_HIP(lead, hipSetDevice(lead->device));
+  const int n_real = lead->n_real;
+  JointRealArgs jr{};
+  JointArgs& ja = jr.joint;
+  joint_args(h, ctxs, opts, d_par, m, d_lnl, d_chi, w.th, true, &ja);
+  for (int q = 0; q < n_ctx; ++q) jr.stride[q] = ctxs[q]->real_block;
+  jr.n_real = n_real;
+  jr.which = d_which;
+  int rc = fan_out(ctxs, n_ctx, opts, d_par, m, [&](int q) { return BlockOut{nullptr, nullptr, w.th + (size_t)m * ja.blk[q].off}; });
+  if (rc) return rc;
+  // meanwhile on the lead stream: the log-det factor of every point and, in pairs mode, the points sorted by covariance slice
+  hipError_t e = hipSuccess;
+  if (h->n_beta > 0) {
+    hipLaunchKernelGGL(vk_joint_real_factor_kernel, dim3((unsigned)((m + kWaves - 1) / kWaves)), dim3(kBlock), 0, lead->stream, ja,
+                       w.fac, w.bad);
+    e = hipGetLastError();
+    jr.fac = w.fac;
+    jr.bad = w.bad;
+    if (d_which && e == hipSuccess) e = enqueue_slice_sort(lead->stream, &ja, w.sort, w.sort_stride);
+  }
+  // cross mode: ceil(n_real / 16) tiles per point, one point per tile; pairs mode: 16 points per tile
+  const long long tiles = d_which ? (m + kJointRows - 1) / kJointRows : m * ((n_real + kJointRows - 1) / kJointRows);
+  return joint_chi2(h, ctxs, n_ctx, e, "joint_real_chi2", vk_joint_real_chi2_kernel, tiles, joint_real_lds(h), jr);
+}
+
+int vkh::enqueue_joint_sum_realisations(vk_ctx* const* ctxs, int n_ctx, const vk_eval_opts* opts, const double* d_par, long long m,
+                                        const int32_t* d_which, double* d_lnl, double* d_chi, double* d_ws) {
+  vk_ctx* lead = ctxs[0];
+  VK_HIP(lead, hipSetDevice(lead->device));
+  int n_max = 0;
+  for (int q = 0; q < n_ctx; ++q) n_max = std::max(n_max, ctxs[q]->N);
+  const long long block_stride = m * (n_max + 2);               // per block: lnl[m] | chi2[m] | theory workspace [m][N]
+  int rc = fan_out_with(ctxs, n_ctx, [&](int q, vk_ctx* c) {
+    double* blk = d_ws + q * block_stride;
+    return enqueue_realisations(c, opts, d_par, m, blk + 2 * m, blk, blk + m, d_which);
+  });
+  if (rc) return rc;
+  const hipError_t e = join_block_streams(ctxs, n_ctx);
+  if (e != hipSuccess) return fail(lead, VK_E_HIP, "joint fit: enqueue failed: %s", hipGetErrorString(e));
+  hipLaunchKernelGGL(vk_joint_sum_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, lead->stream, d_ws, m, n_ctx, block_stride,
+                     d_lnl, d_chi);
+  VK_HIP(lead, hipGetLastError());
   return VK_OK;
 }
 
@@ -2230,8 +2329,7 @@ int vk_joint_cov_eval_realisations(vk_joint_cov* h, vk_ctx* const* ctxs, int32_t
   rc = check_which(lead, which, n, n_real);
   if (rc) return rc;
   if (n == 0) return VK_OK;
-  const size_t lds = joint_real_lds_doubles(h->NT, n_ctx, h->n_beta) * sizeof(double);
-  if (lds > 160 * 1024)
+  if (joint_real_lds(h) > 160 * 1024)
     return fail(lead, VK_E_ARG, "joint covariance: %d entries and %d slices need more than 160 KiB of LDS", h->NT, h->n_beta);
   VK_HIP(lead, hipSetDevice(lead->device));
   // a chunk is every block's theory launch (theory only, each on its own stream) and the joint chi-square launch behind them
@@ -2251,29 +2349,10 @@ int vk_joint_cov_eval_realisations(vk_joint_cov* h, vk_ctx* const* ctxs, int32_t
   double* d_fac = ch.d_chi + (size_t)m_max * ch.per_point;
   ch.d_which = reinterpret_cast<int32_t*>(d_fac + m_max);
   int* d_bad = ch.d_which + m_max;
-  int* d_sort = d_bad + m_max;
+  const vkh::JointRealWs w{d_th, d_fac, d_bad, d_bad + m_max, m_max};
   return ch.run(lead, params, which, n, lnl, chi2, [&](long long m) {
-    JointRealArgs jr{};
-    JointArgs& ja = jr.joint;
-    joint_args(h, ctxs, opts, ch.d_par, m, lnl ? ch.d_lnl : nullptr, chi2 ? ch.d_chi : nullptr, d_th, true, &ja);
-    for (int q = 0; q < n_ctx; ++q) jr.stride[q] = ctxs[q]->real_block;
-    jr.n_real = n_real;
-    jr.which = which ? ch.d_which : nullptr;
-    int rc = fan_out(ctxs, n_ctx, opts, ch.d_par, m, [&](int q) { return BlockOut{nullptr, nullptr, d_th + (size_t)m * ja.blk[q].off}; });
-    if (rc) return rc;
-    // meanwhile on the lead stream: the log-det factor of every point and, in pairs mode, the points sorted by covariance slice
-    hipError_t e = hipSuccess;
-    if (h->n_beta > 0) {
-      hipLaunchKernelGGL(vk_joint_real_factor_kernel, dim3((unsigned)((m + kWaves - 1) / kWaves)), dim3(kBlock), 0, lead->stream,
-                         ja, d_fac, d_bad);
-      e = hipGetLastError();
-      jr.fac = d_fac;
-      jr.bad = d_bad;
-      if (which && e == hipSuccess) e = enqueue_slice_sort(lead->stream, &ja, d_sort, m_max);
-    }
-    // cross mode: ceil(n_real / 16) tiles per point, one point per tile; pairs mode: 16 points per tile
-    const long long tiles = which ? (m + kJointRows - 1) / kJointRows : m * ((n_real + kJointRows - 1) / kJointRows);
-    return joint_chi2(h, ctxs, n_ctx, e, "joint_real_chi2", vk_joint_real_chi2_kernel, tiles, lds, jr);
+    return vkh::enqueue_joint_cov_realisations(h, ctxs, n_ctx, opts, ch.d_par, m, which ? ch.d_which : nullptr,
+                                               lnl ? ch.d_lnl : nullptr, chi2 ? ch.d_chi : nullptr, w);
   });
 }
 

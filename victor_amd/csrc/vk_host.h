@@ -181,6 +181,31 @@ int check_real_lds(vk_ctx* ctx);
 int enqueue_realisations(vk_ctx* ctx, const vk_eval_opts* opts, const double* d_par, long long m, double* d_th, double* d_lnl,
                          double* d_chi, const int32_t* d_which);
 
+// Joint fits against the blocks' realisations, for vk_sampled.hip and the host entry points (contracts at the definitions).
+// check_joint: may these contexts (lead first) be evaluated together - under the covariance handle h, or block-diagonal (h NULL);
+// need_real: against their realisations (pairs mode).  The text of a refusal is the lead's vk_last_error.
+int check_joint(const vk_joint_cov* h, vk_ctx* const* ctxs, int n_ctx, bool need_real);
+// doubles of workspace the joint evaluation of up to m rows needs (data: the public workspace sizes; real: the layouts below)
+size_t joint_workspace_doubles(const vk_joint_cov* h, vk_ctx* const* ctxs, int n_ctx, long long m, bool real);
+// the device arrays of one joint-covariance launch against realisations: theory vectors [m][NT] (block q at m * off_q), -1/2 log
+// det [m], the sign test's word [m], the slice sort's lo | rank | perm [sort_stride] and histograms
+struct JointRealWs {
+  double *th, *fac;
+  int *bad, *sort;
+  long long sort_stride;
+};
+JointRealWs joint_real_carve(const vk_joint_cov* h, double* d_ws, long long m_max);
+// One launch set of vk_joint_cov_eval_realisations on m device rows: every block's theory launch (theory only, on its own stream
+// behind the lead's), the log-det factor and - pairs mode - the slice sort on the lead stream, the joint chi-square kernel behind
+// all of them.  d_which NULL: every realisation (outputs [m][n_real]); else device indices, outputs [m].  Enqueue only.
+// Both enqueue functions make the lead's device current themselves; the caller has run check_joint.
+int enqueue_joint_cov_realisations(vk_joint_cov* h, vk_ctx* const* ctxs, int n_ctx, const vk_eval_opts* opts, const double* d_par,
+                                   long long m, const int32_t* d_which, double* d_lnl, double* d_chi, const JointRealWs& w);
+// Block-diagonal, pairs mode: every block's enqueue_realisations on its own stream behind the lead's, into block q's part of d_ws
+// (lnl [m] | chi2 [m] | theory [m][N_max], the layout of vk_joint_eval_device_async), then the block-order sum on the lead stream.
+int enqueue_joint_sum_realisations(vk_ctx* const* ctxs, int n_ctx, const vk_eval_opts* opts, const double* d_par, long long m,
+                                   const int32_t* d_which, double* d_lnl, double* d_chi, double* d_ws);
+
 // sizeof(vk_ctx) and the offset of its last member as each host-compiled unit sees them (vk_create compares them with its own)
 size_t ctx_layout_walk(size_t* last_offset);
 size_t ctx_layout_serve(size_t* last_offset);

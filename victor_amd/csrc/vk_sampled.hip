@@ -2,7 +2,10 @@
 // (vk_fit_*) and Metropolis chains (vk_chain_*) of the C ABI (include/victor_hip.h), and what they share.  A problem names the
 // row columns it samples inside a prior box, over a base row of its own, against the context's data vector or one of its
 // realisations; its rows are formed on the device (vk_sampled_row.h) and evaluated by victor_hip.hip, which this unit reaches
-// through vk_eval_batch_device_async and, in vk_host.h, enqueue_realisations / check_real_lds.  The same object serves every
+// through vk_eval_batch_device_async and, in vk_host.h, enqueue_realisations / check_real_lds.  A handle made by
+// vk_fit_create_joint / vk_chain_create_joint runs the same loops over a joint fit of several contexts - block-diagonal or under
+// one covariance handle, against the blocks' data vectors or joint realisation which[i] (that realisation of every block) -
+// through the joint entry points and their enqueue-only twins against realisations (vk_host.h).  The same object serves every
 // flavour of the library.
 //
 // Device code lives in the headers next to this file:
@@ -26,6 +29,7 @@
 #include "vk_kernel_chain.h"
 
 using namespace vk;
+using vkh::check_joint;
 using vkh::check_opts;
 using vkh::check_real_lds;
 using vkh::enqueue_realisations;
@@ -37,7 +41,10 @@ constexpr int kSampledMaxP = vkfit::kMaxP;
 static_assert(vkchain::kMaxP == kSampledMaxP, "best fits and chains sample the same columns");
 
 struct Sampled {
-  vk_ctx* ctx = nullptr;
+  vk_ctx* ctx = nullptr;                   // of a joint fit: the lead block's (its stream carries the loop)
+  std::vector<vk_ctx*> blocks;             // a joint fit's contexts in block order, blocks[0] == ctx (empty: a single fit)
+  vk_joint_cov* cov = nullptr;             // ... under this covariance handle (NULL: block-diagonal)
+  size_t rows_max = 0;                     // rows of the largest launch the handle makes
   vk_eval_opts opts{};
   int P = 0;                               // sampled parameters
   int col[kSampledMaxP] = {};
@@ -48,6 +55,12 @@ struct Sampled {
   double *d_base = nullptr, *d_rows = nullptr, *d_th = nullptr;   // each problem's base row; the pending rows, their theory vectors
   int *d_which = nullptr, *d_row_which = nullptr;                 // realisation of each problem, of each pending row
   std::string err;
+
+  // doubles of d_th: the theory vectors of rows_max rows; of a joint fit, the workspace of its evaluation of that many rows
+  // (whose head is the rows' theory vectors, block by block)
+  size_t workspace_doubles() const {
+    return blocks.empty() ? rows_max * ctx->N : vkh::joint_workspace_doubles(cov, blocks.data(), (int)blocks.size(), (long long)rows_max, real);
+  }
 };
 
 // The typed arrays of a handle inside its one allocation: a handle's layout() names them once, in order of descending
@@ -82,12 +95,14 @@ static void sampled_destroy(H* f) {
   delete f;
 }
 
-// vk_fit_create / vk_chain_create (`who`; a problem is a `noun` in its texts).  H is a Sampled with shape(n, lo, hi), which
-// keeps the count, the box and what follows from P, and layout(Carve&) (hidden: no symbol of theirs leaves the library).
+// vk_fit_create / vk_chain_create and their _joint forms (`who`; a problem is a `noun` in its texts).  H is a Sampled with
+// shape(n, lo, hi), which keeps the count, the box and what follows from P, and layout(Carve&) (hidden: no symbol of theirs
+// leaves the library).  joint: ctxs are the n_ctx blocks of a joint fit, lead first, under cov (NULL: block-diagonal); otherwise
+// ctxs is the one context.
 template <class H>
-static H* sampled_create(const char* who, const char* noun, vk_ctx* ctx, const vk_eval_opts* opts, int32_t n, int32_t n_params,
-                         const int32_t* columns, const double* lo, const double* hi, const double* base_rows, double alpha,
-                         const int32_t* which, char* err, size_t errlen) {
+static H* sampled_create(const char* who, const char* noun, vk_ctx* const* ctxs, int n_ctx, bool joint, vk_joint_cov* cov,
+                         const vk_eval_opts* opts, int32_t n, int32_t n_params, const int32_t* columns, const double* lo,
+                         const double* hi, const double* base_rows, double alpha, const int32_t* which, char* err, size_t errlen) {
   auto bail = [&](const std::string& msg) -> H* {
     if (err && errlen) {
       strncpy(err, msg.c_str(), errlen - 1);
@@ -96,13 +111,22 @@ static H* sampled_create(const char* who, const char* noun, vk_ctx* ctx, const v
     return nullptr;
   };
   const std::string me = std::string(who) + ": ";
-  if (!ctx || !opts || !columns || !lo || !hi || !base_rows) return bail(me + "NULL argument");
+  if (!ctxs || (!joint && !ctxs[0]) || !opts || !columns || !lo || !hi || !base_rows) return bail(me + "NULL argument");
+  if (n_ctx < 1 || n_ctx > 32) return bail(me + "need 1 <= contexts <= 32");
+  for (int q = 0; q < n_ctx; ++q)
+    if (!ctxs[q]) return bail(me + "context " + std::to_string(q) + " is NULL");
+  vk_ctx* ctx = ctxs[0];
   if (n < 1 || n > kSampledMax) return bail(me + "need 1 <= " + noun + "s <= 65536");
   if (n_params < 1 || n_params > kSampledMaxP)
     return bail(me + "need 1 <= parameters <= 10 (the row columns other than aperp / apar / epsilon, and epsilon)");
-  sync_knobs(ctx);
-  if (check_opts(ctx, opts) != VK_OK) return bail(ctx->err);
-  if (!ctx->d_data) return bail(me + "context was created without a data vector");
+  for (int q = 0; q < n_ctx; ++q) {
+    sync_knobs(ctxs[q]);
+    if (check_opts(ctxs[q], opts) != VK_OK) return bail(ctxs[q]->err);
+  }
+  if (!joint && !ctx->d_data) return bail(me + "context was created without a data vector");
+  // a joint fit: one device, data vectors, the handle's lead and block sizes; against realisations, the same number of them on
+  // every context and the LDS the realisation kernels need
+  if (joint && check_joint(cov, ctxs, n_ctx, which != nullptr) != VK_OK) return bail(me + ctx->err);
   bool used[VK_NPAR] = {};
   int n_eps = 0;
   for (int j = 0; j < n_params; ++j) {
@@ -128,6 +152,8 @@ static H* sampled_create(const char* who, const char* noun, vk_ctx* ctx, const v
   H* f = new (std::nothrow) H();
   if (!f) return bail("out of memory");
   f->ctx = ctx;
+  if (joint) f->blocks.assign(ctxs, ctxs + n_ctx);
+  f->cov = cov;
   f->opts = *opts;
   f->P = n_params;
   for (int j = 0; j < n_params; ++j) f->col[j] = columns[j];
@@ -165,6 +191,16 @@ static int refused(Sampled* f, const std::string& msg) {
 static int sampled_ready(Sampled* f, const char* who, const char* noun, bool name_lds) {
   vk_ctx* ctx = f->ctx;
   auto refuse = [&](const std::string& msg) { return refused(f, std::string(who) + ": " + msg); };
+  if (!f->blocks.empty()) {                // a joint fit: every block's context
+    for (size_t q = 0; q < f->blocks.size(); ++q)
+      if (f->blocks[q]->begun_n != 0)
+        return refuse("a batch begun with vk_eval_batch_begin is awaiting vk_eval_batch_finish on context " + std::to_string(q));
+    if (check_joint(f->cov, f->blocks.data(), (int)f->blocks.size(), f->real) != VK_OK) return refuse(ctx->err);
+    if (f->real && f->max_which >= ctx->n_real)
+      return refuse("the contexts hold " + std::to_string(ctx->n_real) + " realisations, a " + noun + " asks for number " +
+                    std::to_string(f->max_which));
+    return VK_OK;
+  }
   if (ctx->begun_n != 0) return refuse("a batch begun with vk_eval_batch_begin is awaiting vk_eval_batch_finish on the context");
   if (f->real) {
     if (ctx->n_real <= 0 || !ctx->d_real) return refuse("no realisations are set on the context (vk_set_realisations)");
@@ -179,8 +215,27 @@ static int sampled_ready(Sampled* f, const char* who, const char* noun, bool nam
 // the evaluation of the first m pending rows into d_lnl / d_chi, on the context's stream: the fit's own data vector with lnL /
 // chi2 in the theory launch (the fused tail applies), realisations in pairs mode
 static int sampled_evaluate(Sampled* f, long long m, double* d_lnl, double* d_chi) {
-  const int rc = f->real ? enqueue_realisations(f->ctx, &f->opts, f->d_rows, m, f->d_th, d_lnl, d_chi, f->d_row_which)
-                         : vk_eval_batch_device_async(f->ctx, &f->opts, f->d_rows, m, d_lnl, d_chi, f->d_th);
+  int rc;
+  if (f->blocks.empty()) {
+    rc = f->real ? enqueue_realisations(f->ctx, &f->opts, f->d_rows, m, f->d_th, d_lnl, d_chi, f->d_row_which)
+                 : vk_eval_batch_device_async(f->ctx, &f->opts, f->d_rows, m, d_lnl, d_chi, f->d_th);
+  } else {
+    // A joint fit: the launches of the joint entry points, enqueue only.  Stream order: the rows (and their realisation
+    // indices) were written on the lead stream; every route first puts each block's stream behind an event of the lead stream
+    // (fan_out), so the blocks' launches read finished rows, and ends on the lead stream behind an event of every block's
+    // stream (the joint chi-square kernel, or the block-order sum) - so the step kernel that follows on the lead stream reads
+    // finished results, and overwrites the rows only once no block reads them any more.
+    vk_ctx* const* cs = f->blocks.data();
+    const int nb = (int)f->blocks.size();
+    if (!f->real)
+      rc = f->cov ? vk_joint_cov_eval_device_async(f->cov, cs, nb, &f->opts, f->d_rows, m, d_lnl, d_chi, f->d_th)
+                  : vk_joint_eval_device_async(cs, nb, &f->opts, f->d_rows, m, d_lnl, d_chi, f->d_th);
+    else if (f->cov)
+      rc = vkh::enqueue_joint_cov_realisations(f->cov, cs, nb, &f->opts, f->d_rows, m, f->d_row_which, d_lnl, d_chi,
+                                               vkh::joint_real_carve(f->cov, f->d_th, (long long)f->rows_max));
+    else
+      rc = vkh::enqueue_joint_sum_realisations(cs, nb, &f->opts, f->d_rows, m, f->d_row_which, d_lnl, d_chi, f->d_th);
+  }
   if (rc) f->err = f->ctx->err;
   return rc;
 }
@@ -195,6 +250,7 @@ static int sampled_launch(Sampled* f, void (*kern)(Args), int threads, int block
 
 // an error after something was enqueued (the handle holds its text): leave nothing in flight
 static int sampled_abort(Sampled* f, int rc) {
+  for (size_t q = 1; q < f->blocks.size(); ++q) (void)hipStreamSynchronize(f->blocks[q]->stream);   // (a joint fit's other blocks)
   (void)hipStreamSynchronize(f->ctx->stream);
   (void)hipGetLastError();
   return rc;
@@ -217,6 +273,7 @@ struct __attribute__((visibility("hidden"))) vk_fit : Sampled {
   void shape(int n, const double* lo_, const double* hi_) {
     R = n;
     S = vkfit::slots(P);
+    rows_max = (size_t)R * S;
     for (int j = 0; j < P; ++j) {
       lo[j] = lo_[j];
       hi[j] = hi_[j];
@@ -230,7 +287,7 @@ struct __attribute__((visibility("hidden"))) vk_fit : Sampled {
     c.take(d_rows, rows * VK_NPAR);
     c.take(d_lnl, rows);
     c.take(d_chi, rows);
-    c.take(d_th, rows * ctx->N);
+    c.take(d_th, workspace_doubles());
     c.take(d_active, n);
     c.take(d_row_which, rows);
     c.take(d_which, n);
@@ -293,8 +350,15 @@ extern "C" {
 vk_fit* vk_fit_create(vk_ctx* ctx, const vk_eval_opts* opts, int32_t n_problems, int32_t n_params, const int32_t* columns,
                       const double* lo, const double* hi, const double* base_rows, double alpha, const int32_t* which, char* err,
                       size_t errlen) {
-  return sampled_create<vk_fit>("vk_fit_create", "problem", ctx, opts, n_problems, n_params, columns, lo, hi, base_rows, alpha,
-                                which, err, errlen);
+  return sampled_create<vk_fit>("vk_fit_create", "problem", &ctx, 1, false, nullptr, opts, n_problems, n_params, columns, lo, hi,
+                                base_rows, alpha, which, err, errlen);
+}
+
+vk_fit* vk_fit_create_joint(vk_ctx* const* ctxs, int32_t n_ctx, vk_joint_cov* cov, const vk_eval_opts* opts, int32_t n_problems,
+                            int32_t n_params, const int32_t* columns, const double* lo, const double* hi, const double* base_rows,
+                            double alpha, const int32_t* which, char* err, size_t errlen) {
+  return sampled_create<vk_fit>("vk_fit_create_joint", "problem", ctxs, n_ctx, true, cov, opts, n_problems, n_params, columns, lo,
+                                hi, base_rows, alpha, which, err, errlen);
 }
 
 const char* vk_fit_last_error(const vk_fit* f) { return f ? f->err.c_str() : ""; }
@@ -362,6 +426,7 @@ struct __attribute__((visibility("hidden"))) vk_chain : Sampled {
   void shape(int n, const double* lo, const double* hi) {
     C = n;
     T = vkchain::n_tri(P);
+    rows_max = (size_t)C;
     box.d = P;
     for (int j = 0; j < P; ++j) {
       box.lo[j] = lo[j];
@@ -382,7 +447,7 @@ struct __attribute__((visibility("hidden"))) vk_chain : Sampled {
     c.take(d_rows, n * VK_NPAR);
     c.take(d_res_lnl, n);
     c.take(d_res_chi, n);
-    c.take(d_th, n * ctx->N);
+    c.take(d_th, workspace_doubles());
     c.take(d_dz, block * P);
     c.take(d_logu, block);
     c.take(d_hx, block * P);
@@ -426,8 +491,15 @@ extern "C" {
 vk_chain* vk_chain_create(vk_ctx* ctx, const vk_eval_opts* opts, int32_t n_chains, int32_t n_params, const int32_t* columns,
                           const double* lo, const double* hi, const double* base_rows, double alpha, const int32_t* which, char* err,
                           size_t errlen) {
-  return sampled_create<vk_chain>("vk_chain_create", "chain", ctx, opts, n_chains, n_params, columns, lo, hi, base_rows, alpha,
-                                  which, err, errlen);
+  return sampled_create<vk_chain>("vk_chain_create", "chain", &ctx, 1, false, nullptr, opts, n_chains, n_params, columns, lo, hi,
+                                  base_rows, alpha, which, err, errlen);
+}
+
+vk_chain* vk_chain_create_joint(vk_ctx* const* ctxs, int32_t n_ctx, vk_joint_cov* cov, const vk_eval_opts* opts, int32_t n_chains,
+                                int32_t n_params, const int32_t* columns, const double* lo, const double* hi, const double* base_rows,
+                                double alpha, const int32_t* which, char* err, size_t errlen) {
+  return sampled_create<vk_chain>("vk_chain_create_joint", "chain", ctxs, n_ctx, true, cov, opts, n_chains, n_params, columns, lo,
+                                  hi, base_rows, alpha, which, err, errlen);
 }
 
 const char* vk_chain_last_error(const vk_chain* f) { return f ? f->err.c_str() : ""; }

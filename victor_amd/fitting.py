@@ -1,4 +1,5 @@
-"""Best-fit points on the GPU: ``CCFFit.best_fit`` and ``Realisations.best_fit``.
+"""Best-fit points on the GPU: ``CCFFit.best_fit`` and ``Realisations.best_fit``; of a joint fit, ``JointFit.best_fit`` and
+``JointRealisations.best_fit`` (one parameter row for all blocks; ``vk_fit_create_joint``).
 
 The reference has no optimiser; its users maximise ``CCFFit.log_likelihood`` (reference: ``ccf_fit.py:356-483``) with a host
 optimiser, one call per point and one data vector at a time.  Here every *problem* - one maximisation of lnL over the sampled
@@ -82,11 +83,19 @@ class _Sampled:
             raise InputError(f"{self.who}: alpha must be a scalar when epsilon is {self.verb}")
 
     def fit_options(self, fit, kwargs):
-        fit_options = fit._merged_fit(kwargs)
-        if fit_options["beta_interpolation"] == "likelihood" and not fit.fixed_data:
-            raise InputError(f"{self.who}: beta_interpolation 'likelihood' on a beta-dependent data vector is not supported "
-                             "(its blend of two evaluations runs on the host)")
-        return fit_options
+        """The merged fit options (of a joint fit: its lead block's; every block is checked)."""
+        from .joint import JointFit
+        blocks = fit.fits if isinstance(fit, JointFit) else None
+        if blocks is not None and fit.covariance is not None:
+            kwargs = {k: v for k, v in kwargs.items() if k != "likelihood"}     # (the joint covariance's own form)
+        first = None
+        for f in blocks if blocks is not None else [fit]:
+            fit_options = f._merged_fit(kwargs)
+            if fit_options["beta_interpolation"] == "likelihood" and not f.fixed_data:
+                raise InputError(f"{self.who}: beta_interpolation 'likelihood' on a beta-dependent data vector is not supported "
+                                 "(its blend of two evaluations runs on the host)")
+            first = fit_options if first is None else first
+        return first
 
     def per_param(self, what, given, default):
         """One value per sampled parameter: ``given`` (name -> value) over ``default``."""
@@ -112,17 +121,27 @@ class _Sampled:
         return x0
 
     def create(self, entry, fit, realisations, kwargs, fit_options, batch, which):
-        """``(engine, handle)`` of ``entry`` (``vk_fit_create`` / ``vk_chain_create``): one problem per row of ``batch`` (the
-        sampled and fixed values its rows start from), against the fit's data vector or realisation ``which[i]``."""
+        """``(lib, handle, refresh)`` of ``entry`` (``vk_fit_create`` / ``vk_chain_create``): one problem per row of ``batch``
+        (the sampled and fixed values its rows start from), against the fit's data vector or realisation ``which[i]``.
+        ``refresh`` (None against the data vector) makes ``realisations`` the ones set on the handle's context(s) again - another
+        object's may have been set since.  A :class:`victor_amd.joint.JointFit` builds its own handle, of ``entry + "_joint"``
+        (``JointFit._sampled_create``)."""
+        from .joint import JointFit
+        if isinstance(fit, JointFit):
+            return fit._sampled_create(entry + "_joint", self, realisations, kwargs, batch, which)
         model = fit._merged(kwargs)
         fit._check_supported(model)
         rows = np.ascontiguousarray(fit._fit_rows(batch, model), dtype=np.float64)
         cols = np.array([N.ROW_COLUMNS.get(n, N.VK_WALK_EPSILON) for n in self.names], dtype=np.int32)
+        refresh = None
         if realisations is None:
             eng = fit._get_engine(fit._engine_key(model), model["simpson_even"])
             opts = eng.make_opts(model, fit_options)
         else:
             _, _, eng, opts = realisations._plan(kwargs)
+
+            def refresh():
+                realisations._upload(eng)
         i32 = C.POINTER(C.c_int32)
         err = C.create_string_buffer(512)
         h = getattr(eng._lib, entry)(eng._ctx, C.byref(opts), len(rows), len(cols), cols.ctypes.data_as(i32), N.as_dp(N.f64(self.lo)),
@@ -131,13 +150,14 @@ class _Sampled:
         if not h:
             msg = err.value.decode()
             raise (N.NativeError if "device memory" in msg else InputError)(msg)
-        return eng, h
+        return eng._lib, h, refresh
 
 
 def best_fit(fit, params, fixed=None, start=None, step=None, xtol=None, ftol=1e-6, max_iter=None, restarts=1, kwargs=None,
              realisations=None):
-    """The work of ``CCFFit.best_fit`` (``realisations=None``: against the fit's data vector) and ``Realisations.best_fit``.
-    Every argument is checked before the first device call."""
+    """The work of ``CCFFit.best_fit`` (``realisations=None``: against the fit's data vector) and ``Realisations.best_fit``;
+    with a ``JointFit`` for ``fit`` (and its ``JointRealisations``), of theirs.  Every argument is checked before the first
+    device call."""
     kwargs = kwargs or {}
     q = _Sampled("best_fit", "fitted", params, fixed)
     names, fixed_all, d = q.names, q.fixed_all, len(q.names)
@@ -168,8 +188,7 @@ def best_fit(fit, params, fixed=None, start=None, step=None, xtol=None, ftol=1e-
     batch.update({n: np.ascontiguousarray(x0[:, j]) for j, n in enumerate(names)})
 
     # ---- device
-    eng, h = q.create("vk_fit_create", fit, realisations, kwargs, fit_options, batch, np.arange(R, dtype=np.int32))
-    lib = eng._lib
+    lib, h, _ = q.create("vk_fit_create", fit, realisations, kwargs, fit_options, batch, np.arange(R, dtype=np.int32))
     i32 = C.POINTER(C.c_int32)
     x = np.empty((R, d))
     lnl, chi2 = np.empty(R), np.empty(R)

@@ -39,7 +39,7 @@ class JointFit:
             raise ValueError("need at least one fit")
         self._buffers = None
         self.covariance = None
-        self._handle = None
+        self._handles = {}
         if covariance is None:
             if likelihood is not None:
                 raise InputError("JointFit: likelihood= applies to a joint covariance only (covariance=None keeps each block's own)")
@@ -156,11 +156,13 @@ class JointFit:
         return engines, opts
 
     def _joint_handle(self, lead):
-        """The device copy of the joint covariance tables (``vk_joint_cov_create``), made once per lead engine."""
-        h = self._handle
-        if h is not None and h[0] is lead:
+        """The device copy of the joint covariance tables (``vk_joint_cov_create``), made once per lead engine and kept for
+        the life of this object: which engine leads depends on a call's options (matter model, Simpson rule), and a handle
+        may be held by the best-fit or chain handle of an earlier call (``vk_fit_create_joint`` / ``vk_chain_create_joint``;
+        a ``Chains`` keeps this object alive), so a call with other options must never destroy it."""
+        h = self._handles.get(id(lead))
+        if h is not None:
             return h[1]
-        self._release_handle()
         nt = self.n_data
         block_n = np.array([len(f.s) * len(f.poles_s) for f in self.fits], dtype=np.int32)
         t = N.vk_joint_cov_tables()
@@ -180,14 +182,16 @@ class JointFit:
         out = C.c_void_p()
         lead._check(lead._lib.vk_joint_cov_create(lead._ctx, C.byref(t), C.byref(out)))
         del keep
-        self._handle = (lead, out.value)
+        self._handles[id(lead)] = (lead, out.value)              # (the entry keeps the lead engine, and so its id, alive)
         return out.value
 
     def _release_handle(self):
-        h = getattr(self, "_handle", None)
-        if h is not None:
-            h[0]._lib.vk_joint_cov_destroy(h[1])
-            self._handle = None
+        """Destroy every device copy of the covariance tables.  Nothing that holds one may be alive: ``__del__``, and tests
+        that have finished with this object."""
+        handles = getattr(self, "_handles", None) or {}
+        while handles:
+            lead, h = handles.popitem()[1]
+            lead._lib.vk_joint_cov_destroy(h)
 
     def __del__(self):
         try:
@@ -301,6 +305,62 @@ class JointFit:
         lnl, chi2 = self.log_likelihood_batch(params, **kwargs)
         return float(lnl[0]), float(chi2[0])
 
+    # ------------------------------------------------------------------ best fits and chains (fitting.py, chains.py)
+    def _sampled_create(self, entry, q, realisations, kwargs, batch, which):
+        """``(lib, handle, refresh)`` of ``vk_fit_create_joint`` / ``vk_chain_create_joint`` (``entry``) for the sampled
+        parameters ``q`` (the contract of ``fitting._Sampled.create``): one problem per row of ``batch``, against the joint data
+        vector or joint realisation ``which[i]`` of ``realisations``.  The rows are the lead fit's, as
+        :meth:`log_likelihood_batch` forms them."""
+        if len({f._device for f in self.fits}) != 1:
+            raise InputError(f"{q.who}: every block of a joint fit must live on the same device")
+        if self.covariance is not None:
+            engines, opts = self._plan_cov(kwargs)
+            kwargs = {k: v for k, v in kwargs.items() if k != "likelihood"}
+        else:
+            plan = self._plan(kwargs)
+            if plan is None:
+                raise InputError(f"{q.who}: the blocks of a block-diagonal joint fit must share one option block (their model, "
+                                 "fit options and their data's beta dependence) and one device")
+            engines, opts = plan
+        fit = self.fits[0]
+        rows = np.ascontiguousarray(fit._fit_rows(batch, fit._merged(kwargs)), dtype=np.float64)
+        cols = np.array([N.ROW_COLUMNS.get(n, N.VK_WALK_EPSILON) for n in q.names], dtype=np.int32)
+        refresh = None
+        if realisations is not None:
+            def refresh(realisations=realisations, engines=list(engines)):
+                realisations._upload(engines)
+            refresh()
+        lead = engines[0]
+        handle = self._joint_handle(lead) if self.covariance is not None else None
+        ctxs = (C.c_void_p * len(engines))(*[e._ctx for e in engines])
+        i32 = C.POINTER(C.c_int32)
+        err = C.create_string_buffer(512)
+        h = getattr(lead._lib, entry)(ctxs, len(engines), handle, C.byref(opts), len(rows), len(cols), cols.ctypes.data_as(i32),
+                                      N.as_dp(N.f64(q.lo)), N.as_dp(N.f64(q.hi)), N.as_dp(rows),
+                                      float(q.fixed_all.get("alpha", 1)),
+                                      None if realisations is None else which.ctypes.data_as(i32), err, len(err))
+        if not h:
+            msg = err.value.decode()
+            raise (N.NativeError if "device memory" in msg else InputError)(msg)
+        return lead._lib, h, refresh
+
+    def best_fit(self, params, fixed=None, start=None, step=None, xtol=None, ftol=1e-6, max_iter=None, restarts=1, **kwargs):
+        """Maximum of the joint lnL (the value :meth:`log_likelihood_batch` returns) over the sampled parameters of a cobaya
+        ``params`` block - one parameter vector for all blocks - by the bounded Nelder-Mead search of ``CCFFit.best_fit`` on
+        the GPU, block-diagonal or under the joint covariance.  Arguments and result as ``CCFFit.best_fit``: arrays in
+        ``fixed`` give a profile."""
+        from .fitting import best_fit
+        return best_fit(self, params, fixed, start, step, xtol, ftol, max_iter, restarts, kwargs)
+
+    def sample_chains(self, params, n_steps, walkers=8, seed=0, fixed=None, start=None, scatter=None, proposal=None, burn=0,
+                      thin=1, keep_chain=True, device=True, **kwargs):
+        """``walkers`` Metropolis chains of the joint lnL, stepped on the GPU (``device=True``) or by the NumPy loop over
+        :meth:`log_likelihood_batch` that defines them (``device=False``).  Arguments and result as ``CCFFit.sample_chains``
+        (:mod:`victor_amd.chains`); the result keeps this joint fit alive."""
+        from .chains import sample_chains
+        return sample_chains(self, params, n_steps, walkers, seed, fixed, start, scatter, proposal, burn, thin, keep_chain, device,
+                             kwargs)
+
     @property
     def n_data(self):
         return sum(len(f.s) * len(f.poles_s) for f in self.fits)
@@ -334,6 +394,26 @@ class JointRealisations:
 
     def __len__(self):
         return len(self.numbers)
+
+    def _upload(self, engines):
+        """Make every block's realisations the ones set on its engine (``Realisations._upload``)."""
+        for r, eng in zip(self.blocks, engines):
+            r._upload(eng)
+
+    def best_fit(self, params, fixed=None, start=None, step=None, xtol=None, ftol=1e-6, max_iter=None, restarts=1, **kwargs):
+        """Best-fit point of every joint realisation: problem i maximises the joint lnL against realisation ``numbers[i]`` of
+        every block, all of them in one run on the GPU.  Arguments as ``JointFit.best_fit``; ``fixed`` values must be scalars."""
+        from .fitting import best_fit
+        return best_fit(self.joint, params, fixed, start, step, xtol, ftol, max_iter, restarts, kwargs, realisations=self)
+
+    def sample_chains(self, params, n_steps, walkers=8, seed=0, fixed=None, start=None, scatter=None, proposal=None, burn=0,
+                      thin=1, keep_chain=True, device=True, **kwargs):
+        """``walkers`` Metropolis chains of EVERY joint realisation in lock step, on the GPU (``device=True``) or by the NumPy
+        loop over :meth:`log_likelihood_pairs` that defines them (``device=False``).  Arguments and result as
+        ``Realisations.sample_chains``; ``start`` may be the ``BestFit`` of :meth:`best_fit`."""
+        from .chains import sample_chains
+        return sample_chains(self.joint, params, n_steps, walkers, seed, fixed, start, scatter, proposal, burn, thin, keep_chain,
+                             device, kwargs, realisations=self)
 
     def _eval(self, params, kwargs, which=None):
         joint = self.joint
