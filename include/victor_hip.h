@@ -472,6 +472,32 @@ int vk_chain_state(vk_chain* f, double* x, double* lnl, double* chi2, int64_t* n
 const char* vk_chain_last_error(const vk_chain* f);
 void vk_chain_destroy(vk_chain* f);
 
+/* ---- Stretch-move ensembles on the same handles ------------------------------------------------------------------------------
+ * vk_chain_begin_stretch reads the n_chains chains of a handle made by vk_chain_create / vk_chain_create_joint as
+ * n_chains / walkers ensembles of `walkers` walkers each (walker c = r walkers + w) and enqueues n_steps (1 .. 64) SWEEPS of the
+ * affine-invariant stretch move (Goodman & Weare 2010) in its two-half parallel form: half 0 of every ensemble (w < walkers / 2)
+ * moves against partners drawn from half 1, then half 1 against the updated half 0.  Start, finish, state and destroy are the
+ * entry points above; blocks of vk_chain_begin and of vk_chain_begin_stretch may follow each other on one handle.  The extra
+ * device buffers of a block are allocated by the first call.
+ *   z, lz, logu [n_steps][2][n_chains / 2], partner (int32, same shape): entry [t][h][i] belongs to sweep t, half-step h and
+ *               moving walker i % (walkers / 2) of ensemble i / (walkers / 2): its stretch factor, lz = (n_params - 1) log z
+ *               (formed by the caller), its log acceptance level, and its partner's index within the OTHER half, in
+ *               [0, walkers / 2).
+ * One half-step of one walker at x with partner p: prop = p + z (x - p), a multiplication and an addition, each rounded (no
+ *   fused multiply-add); a proposal outside the box is evaluated at the walker's current position, discarded, and reads
+ *   lnL = -inf (every launch has n_chains / 2 rows); accept when logu < (lz + lnL') - lnL (IEEE: a NaN rejects).  Per half-step the
+ *   library enqueues a kernel that forms the proposals and their rows, the evaluation of those rows and a kernel that decides -
+ *   three launches in stream order, because a half's proposals read what the other half's decisions have just written.
+ * first_step, burn, thin, want_history, n_kept as vk_chain_begin, counting sweeps: a kept sweep enters the moment sums and the
+ *   history with all n_chains walkers as they stand after its second half.  n_steps of vk_chain_state counts a walker's own
+ *   half-steps, one per sweep.
+ * Refused (VK_E_ARG) before anything is enqueued, the handle staying usable: a NULL argument, no start or a block in flight,
+ *   walkers odd or < 2, n_chains not a multiple of walkers, a partner index outside [0, walkers / 2), realisation indices that
+ *   differ within one ensemble, and what vk_chain_begin refuses. */
+int vk_chain_begin_stretch(vk_chain* f, int32_t n_steps, int32_t walkers, const double* z, const double* lz, const double* logu,
+                           const int32_t* partner, int64_t first_step, int64_t burn, int64_t thin, int32_t want_history,
+                           int32_t* n_kept);
+
 /* Theory multipoles on a caller-supplied s grid: out[n][n_ell][n_s] with the caller's own
  * projection weights w_ell[n_ell][n_mu] on mu[n_mu] (host buffers). */
 int vk_theory_batch(vk_ctx* ctx, const vk_eval_opts* opts, const double* params, int64_t n,

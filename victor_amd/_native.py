@@ -141,6 +141,8 @@ SYMBOLS = {
                               C.POINTER(C.c_int32), C.c_char_p, C.c_size_t]),
     "vk_chain_start": (C.c_int, [_vp, _dp]),
     "vk_chain_begin": (C.c_int, [_vp, C.c_int32, _dp, _dp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_int32)]),
+    "vk_chain_begin_stretch": (C.c_int, [_vp, C.c_int32, C.c_int32, _dp, _dp, _dp, C.POINTER(C.c_int32), C.c_int64, C.c_int64,
+                                         C.c_int64, C.c_int32, C.POINTER(C.c_int32)]),
     "vk_chain_finish": (C.c_int, [_vp, _dp, _dp, _dp]),
     "vk_chain_state": (C.c_int, [_vp, _dp, _dp, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), _dp, _dp,
                                  _dp]),

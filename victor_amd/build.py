@@ -3,7 +3,8 @@ library with the host compiler, every unit side by side, linked into one library
 
 hipcc (device code; ``vk_instances.h`` names which kernel instantiation lives in which unit):
 ``victor_hip.hip``           the launch side of the C ABI (context, table upload, kernel selection), the chi-square kernels;
-``vk_sampled.hip``           ``vk_fit_*`` and ``vk_chain_*``: best fits and Metropolis chains stepped on the device, their kernels;
+``vk_sampled.hip``           ``vk_fit_*`` and ``vk_chain_*``: best fits, Metropolis chains and stretch-move ensembles stepped on the
+                         device, their kernels;
 ``vk_cells_streaming.hip``   the cells kernel's instantiations for the streaming model (the kernels of the headline
                          metric and of the BOSS configuration), compiled with LLVM's ``iterative-ilp`` machine scheduler: it
                          interleaves the independent chains of the node loop and fills the hazard slots the default

@@ -325,14 +325,16 @@ class CCFFit(CCFModel):
         return best_fit(self, params, fixed, start, step, xtol, ftol, max_iter, restarts, kwargs)
 
     def sample_chains(self, params, n_steps, walkers=8, seed=0, fixed=None, start=None, scatter=None, proposal=None, burn=0,
-                      thin=1, keep_chain=True, device=True, **kwargs):
+                      thin=1, keep_chain=True, device=True, move="metropolis", stretch_a=2.0, **kwargs):
         """``walkers`` independent random-walk Metropolis chains of this fit's lnL, stepped on the GPU (``device=True``: the
         step loop runs on the device, ``vk_chain_begin``) or by the NumPy loop that defines them (``device=False``, over
         :meth:`log_likelihood_batch`): :func:`victor_amd.chains.sample_chains`, which documents the arguments.  Returns a
-        :class:`victor_amd.chains.Chains` with R = 1.  Runs on this fit's own context (never through the broker)."""
+        :class:`victor_amd.chains.Chains` with R = 1.  ``move="stretch"``: the ``walkers`` are one affine-invariant stretch-move
+        ensemble instead (``stretch_a``: its scale; ``vk_chain_begin_stretch``).  Runs on this fit's own context (never through
+        the broker)."""
         from .chains import sample_chains
         return sample_chains(self, params, n_steps, walkers, seed, fixed, start, scatter, proposal, burn, thin, keep_chain, device,
-                             kwargs)
+                             kwargs, move=move, stretch_a=stretch_a)
 
     def realisations(self, simulation_numbers=None):
         """Every simulation realisation of this fit's data file (or the listed ``simulation_numbers``) against one model:

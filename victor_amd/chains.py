@@ -1,4 +1,4 @@
-"""Metropolis chains of the data vector and of every realisation, stepped on the GPU: ``CCFFit.sample_chains`` and
+"""Metropolis chains and stretch-move ensembles of the data vector and of every realisation, stepped on the GPU: ``CCFFit.sample_chains`` and
 ``Realisations.sample_chains``; of a joint fit, ``JointFit.sample_chains`` and ``JointRealisations.sample_chains`` (one parameter
 row for all blocks: ``fit`` is the ``JointFit`` below, the definition route runs over its ``log_likelihood_batch`` /
 ``JointRealisations.log_likelihood_pairs``, the device route through ``vk_chain_create_joint``).
@@ -29,6 +29,22 @@ documented for ``speculate`` in :mod:`victor_amd.sampler`).
 "Kept" steps - step index >= ``burn`` and ``(step - burn) % thin == 0``, counted over the whole life of the object - enter the
 history (``keep_chain``) and the per-chain moment sums about the chain's start (the pivot), which are accumulated where the chain
 runs; ``mean`` and ``cov`` pool the W chains of a problem from those sums, so they cost O(C d^2) host memory whatever the length.
+
+**``move="stretch"``** replaces the random-walk step by the affine-invariant stretch move of Goodman & Weare (2010) in the
+two-half parallel form of :class:`victor_amd.sampler.EnsembleStretch`, which needs no proposal widths: the W chains of a problem
+are the W walkers of ONE ensemble (W even, at least 2 (d + 1)), walker c = r W + w; half 0 holds the walkers w < W / 2, half 1
+the rest.  One step is one SWEEP: half 0 moves against partners drawn from half 1 of the same problem, then half 1 against the
+updated half 0; ``n_steps``, ``burn``, ``thin``, ``n_kept``, the history and ``acceptance`` count sweeps, and a kept sweep takes
+all W walkers as they stand after its second half.  Per half-step the generator calls are those of ``EnsembleStretch.step`` at
+R W / 2 numbers each - ``z = ((a - 1) rng.random() + 1)**2 / a``, the partners ``rng.integers(0, W / 2)``, ``logu =
+log(rng.random())`` - drawn ahead in blocks of 64 sweeps (those three calls 128 times), so with R = 1 the definition route is
+the chain of an ``EnsembleStretch`` of the same seed bit for bit.  A half-step of one walker: ``prop = partner + z * (x -
+partner)`` (a product and a sum, each rounded: the device forbids the fused multiply-add there); outside the box as above (every
+launch has exactly R W / 2 rows, row i of problem i // (W / 2), member i % (W / 2) of the moving half); accept when ``logu <
+lz + lnl_prop - lnl``, left to right, with ``lz = (d - 1) * log(z)`` formed on the host.  ``device=True`` hands blocks of 64
+sweeps to ``vk_chain_begin_stretch``: per half-step a kernel that forms the proposals and their rows, the evaluation of those
+rows, and a kernel that decides - three launches in stream order, because the proposals of a half read what the decisions of
+the other half have just written.
 """
 
 import ctypes as C
@@ -79,12 +95,18 @@ class Chains:
     steps); ``pivot`` (R, W, d), ``n_kept``, ``sum1`` (R, W, d), ``sum2`` (R, W, d, d): the per-chain moment sums as the route that
     ran the chains returns them; ``n_steps``: steps taken.  :meth:`extend` continues the same chains.
 
-    Diagnostics of the definition route only (None on the device route): ``decision_margin``, the smallest
-    ``|lnl_prop - lnl - logu|`` over the decisions taken inside the box with a finite difference (how far the closest decision was
-    from falling the other way), and ``n_outside`` (R, W), the proposals that left the box."""
+    ``move``: "metropolis" or "stretch", the move that ran.  Under "stretch" the W chains of a problem are the walkers of one
+    ensemble, steps are sweeps, ``stretch_a`` is the move's scale, and ``rhat`` is None: the walkers of an ensemble move along
+    lines through each other, they are not independent chains, and a between- over within-chain variance of them means nothing.
 
-    def __init__(self, names, specs, fixed, R, W, rng, width, burn, thin, keep_chain, evaluator, device_handle):
+    Diagnostics of the definition route only (None on the device route): ``decision_margin``, the smallest
+    ``|lnl_prop - lnl - logu|`` (stretch move: ``|lz + lnl_prop - lnl - logu|``) over the decisions taken inside the box with a
+    finite difference (how far the closest decision was from falling the other way), and ``n_outside`` (R, W), the proposals that left the box."""
+
+    def __init__(self, names, specs, fixed, R, W, rng, width, burn, thin, keep_chain, evaluator, device_handle, move="metropolis",
+                 stretch_a=2.0):
         self.names = list(names)
+        self.move, self.stretch_a = move, float(stretch_a)
         self._specs, self.fixed = specs, fixed
         self.R, self.W = R, W
         self._rng, self._width = rng, width
@@ -94,7 +116,7 @@ class Chains:
         self._refresh = self._fit = None
         self._lo = np.array([s.lo for s in specs])
         self._hi = np.array([s.hi for s in specs])
-        self._dz = self._logu = None
+        self._block = None
         self._at = BLOCK
         self.n_steps = 0
         self._hist = ([], [], [])
@@ -103,21 +125,36 @@ class Chains:
 
     # ------------------------------------------------------------------ random numbers: the blocks of EnsembleMetropolis ---
     def _draw_block(self):
+        if self.move == "stretch":
+            return self._draw_block_stretch()
         C_, d = self.R * self.W, len(self.names)
         dz = self._width * self._rng.standard_normal((BLOCK, C_, d))
         logu = np.log(self._rng.random((BLOCK, C_)))
         return dz, logu
 
+    def _draw_block_stretch(self):
+        """64 sweeps of two half-steps each, every half-step with the three generator calls of ``EnsembleStretch.step`` at
+        R * W / 2 numbers: (z, lz = (d - 1) log z, logu, partner), each [64, 2, R * W / 2]."""
+        half, a, d = self.W // 2, self.stretch_a, len(self.names)
+        M = self.R * half
+        z, logu, partner = np.empty((BLOCK, 2, M)), np.empty((BLOCK, 2, M)), np.empty((BLOCK, 2, M), dtype=np.int32)
+        for t in range(BLOCK):
+            for h in range(2):
+                z[t, h] = ((a - 1.0) * self._rng.random(M) + 1.0) ** 2 / a
+                partner[t, h] = self._rng.integers(0, half, size=M)
+                logu[t, h] = np.log(self._rng.random(M))
+        return z, (d - 1) * np.log(z), logu, partner
+
     def _piece(self, remaining, ahead=None):
         """The next piece of the current block (drawing a new one when it is used up; ``ahead``: one drawn in advance):
-        (dz [k, C, d], logu [k, C]), k <= remaining."""
+        (dz [k, C, d], logu [k, C]) - under the stretch move (z, lz, logu, partner), each [k, 2, C / 2] -, k <= remaining."""
         if self._at >= BLOCK:
-            self._dz, self._logu = ahead if ahead is not None else self._draw_block()
+            self._block = ahead if ahead is not None else self._draw_block()
             self._at = 0
         k = min(BLOCK - self._at, remaining)
         t = self._at
         self._at = t + k
-        return self._dz[t:t + k], self._logu[t:t + k]
+        return tuple(a[t:t + k] for a in self._block)
 
     def _kept(self, step):
         return step >= self.burn and (step - self.burn) % self.thin == 0
@@ -137,7 +174,59 @@ class Chains:
         self._n_outside = np.zeros(C_, dtype=np.int64)
         self.decision_margin = np.inf
 
+    def _account(self, x, lnl, chi2):
+        """The end of a step (a sweep): a kept one enters the moment sums and the history."""
+        if self._kept(self.n_steps):
+            dx = x - self._pivot
+            self._sum1 += dx
+            self._sum2 += dx[:, :, None] * dx[:, None, :]
+            self._n_kept += 1
+            if self.keep_chain:
+                for h, a in zip(self._hist, (x, lnl, chi2)):
+                    h.append(a.copy())
+        self.n_steps += 1
+
+    def _run_host_stretch(self, n_steps):
+        """Sweeps of the stretch move: half 0 of every problem against its half 1, then half 1 against the updated half 0; the
+        arithmetic of ``EnsembleStretch.step``, R problems side by side, R * W / 2 rows per evaluation."""
+        lo, hi = self._lo, self._hi
+        x, lnl, chi2 = self._x, self._lnl, self._chi2
+        R, W, half = self.R, self.W, self.W // 2
+        first = (np.arange(R)[:, None] * W + np.arange(half)[None, :]).ravel()            # half 0, problem by problem
+        halves = (first, first + half)
+        start = (np.repeat(np.arange(R) * W, half), np.repeat(np.arange(R) * W + half, half))
+        which = np.repeat(np.arange(R, dtype=np.int32), half)
+        done = 0
+        while done < n_steps:
+            z, lz, logu, pick = self._piece(n_steps - done)
+            for t in range(len(z)):
+                for h in range(2):
+                    mv = halves[h]
+                    partner = x[start[1 - h] + pick[t, h]]
+                    xm, lnl_m = x[mv], lnl[mv]
+                    prop = partner + z[t, h][:, None] * (xm - partner)
+                    inside = ((prop >= lo) & (prop <= hi)).all(axis=1)
+                    rows = np.where(inside[:, None], prop, xm)           # outside: the current position, result discarded
+                    lnl_p, chi2_p = self._evaluate(rows, which)
+                    lnl_p = np.where(inside, lnl_p, -np.inf)
+                    with np.errstate(invalid="ignore"):
+                        accept = logu[t, h] < lz[t, h] + lnl_p - lnl_m   # NaN: False
+                        margin = np.abs(lz[t, h] + lnl_p - lnl_m - logu[t, h])
+                    margin = margin[np.isfinite(margin)]
+                    if margin.size:
+                        self.decision_margin = min(self.decision_margin, float(margin.min()))
+                    self._n_outside[mv] += ~inside
+                    won = mv[accept]
+                    x[won] = prop[accept]
+                    lnl[won] = lnl_p[accept]
+                    chi2[won] = chi2_p[accept]
+                    self._n_accept[won] += 1
+                self._account(x, lnl, chi2)                              # "kept" is decided after the second half, for all W
+            done += len(z)
+
     def _run_host(self, n_steps):
+        if self.move == "stretch":
+            return self._run_host_stretch(n_steps)
         lo, hi = self._lo, self._hi
         x, lnl, chi2 = self._x, self._lnl, self._chi2
         done = 0
@@ -160,15 +249,7 @@ class Chains:
                 lnl[accept] = lnl_p[accept]
                 chi2[accept] = chi2_p[accept]
                 self._n_accept += accept
-                if self._kept(self.n_steps):
-                    dx = x - self._pivot
-                    self._sum1 += dx
-                    self._sum2 += dx[:, :, None] * dx[:, None, :]
-                    self._n_kept += 1
-                    if self.keep_chain:
-                        for h, a in zip(self._hist, (x, lnl, chi2)):
-                            h.append(a.copy())
-                self.n_steps += 1
+                self._account(x, lnl, chi2)
             done += len(dz)
 
     # ------------------------------------------------------------------ the device route ---------------------------------
@@ -184,12 +265,18 @@ class Chains:
         done = 0
         ahead = None
         while done < n_steps:
-            dz, logu = self._piece(n_steps - done, ahead)
+            piece = [np.ascontiguousarray(a) for a in self._piece(n_steps - done, ahead)]
             ahead = None
-            k = len(dz)
+            k = len(piece[0])
             n_kept = C.c_int32(0)
-            self._check(lib.vk_chain_begin(h, k, N.as_dp(np.ascontiguousarray(dz)), N.as_dp(np.ascontiguousarray(logu)), self.n_steps,
-                                           self.burn, self.thin, 1 if self.keep_chain else 0, C.byref(n_kept)), "vk_chain_begin")
+            tail = (self.n_steps, self.burn, self.thin, 1 if self.keep_chain else 0, C.byref(n_kept))
+            if self.move == "stretch":
+                z, lz, logu, partner = piece
+                self._check(lib.vk_chain_begin_stretch(h, k, self.W, N.as_dp(z), N.as_dp(lz), N.as_dp(logu),
+                                                       partner.ctypes.data_as(C.POINTER(C.c_int32)), *tail), "vk_chain_begin_stretch")
+            else:
+                dz, logu = piece
+                self._check(lib.vk_chain_begin(h, k, N.as_dp(dz), N.as_dp(logu), *tail), "vk_chain_begin")
             try:
                 if self._at >= BLOCK and done + k < n_steps:         # the next block's numbers, drawn while this one runs
                     ahead = self._draw_block()
@@ -262,7 +349,7 @@ class Chains:
             self.chain = (hx[0].reshape(-1, R, W, d) if hx else np.empty((0, R, W, d)))
             self.lnl_chain = hl[0].reshape(-1, R, W) if hl else np.empty((0, R, W))
             self.chi2_chain = hc[0].reshape(-1, R, W) if hc else np.empty((0, R, W))
-            if W > 1 and len(self.chain) > 1:
+            if W > 1 and len(self.chain) > 1 and self.move != "stretch":   # (the walkers of an ensemble are not independent chains)
                 with np.errstate(invalid="ignore", divide="ignore"):
                     self.rhat = np.stack([gelman_rubin(self.chain[:, r]) for r in range(R)])
 
@@ -277,7 +364,7 @@ def _draw_start(rng, loc, scale, lo, hi, what):
 
 
 def sample_chains(fit, params, n_steps, walkers=8, seed=0, fixed=None, start=None, scatter=None, proposal=None, burn=0, thin=1,
-                  keep_chain=True, device=True, kwargs=None, realisations=None, evaluate=None):
+                  keep_chain=True, device=True, kwargs=None, realisations=None, evaluate=None, move="metropolis", stretch_a=2.0):
     """The work of ``CCFFit.sample_chains`` (``realisations=None``: the fit's data vector, R = 1) and
     ``Realisations.sample_chains`` (R = the realisations); see the module docstring.  With ``evaluate`` - a callable taking a dict
     of ``(C,)`` arrays (sampled and fixed parameters) and returning ``lnL (C,)`` or ``(lnL, chi2)`` - in place of ``fit`` only the
@@ -287,8 +374,11 @@ def sample_chains(fit, params, n_steps, walkers=8, seed=0, fixed=None, start=Non
     ``walkers``: chains per problem; ``start``: None (each chain drawn from the ``ref`` distribution), a
     :class:`victor_amd.fitting.BestFit` or a dict name -> scalar or ``(R,)`` array: every chain of problem i starts at
     ``start_i + scatter * normal`` (``scatter``: name -> scalar, default the proposal widths; 0 starts every chain at the point
-    itself), redrawn until inside the box; ``proposal``: name -> width overrides.  Every argument is checked before the first
-    device call.  Returns a :class:`Chains`."""
+    itself), redrawn until inside the box; ``proposal``: name -> width overrides.  ``move``: "metropolis" (the default) or
+    "stretch" (module docstring): ``walkers`` must then be even and at least 2 (d + 1), ``stretch_a`` > 1 is the move's scale
+    (z lies in [1 / a, a]), ``proposal`` is refused (the move has no widths), ``scatter`` keeps its default but must be > 0 in
+    every parameter (an ensemble that starts collapsed onto a point, or into a plane, never leaves it), and the result's
+    ``rhat`` is None.  Every argument is checked before the first device call.  Returns a :class:`Chains`."""
     kwargs = kwargs or {}
     n_steps, walkers, burn, thin = int(n_steps), int(walkers), int(burn), int(thin)
     if n_steps < 0:
@@ -299,6 +389,15 @@ def sample_chains(fit, params, n_steps, walkers=8, seed=0, fixed=None, start=Non
         raise InputError("sample_chains: burn must be >= 0")
     if thin < 1:
         raise InputError("sample_chains: thin must be >= 1")
+    if move not in ("metropolis", "stretch"):
+        raise InputError(f"sample_chains: move must be 'metropolis' or 'stretch', not {move!r}")
+    stretch = move == "stretch"
+    if stretch:
+        stretch_a = float(stretch_a)
+        if not stretch_a > 1.0:
+            raise InputError("sample_chains: stretch_a must be > 1")
+        if proposal is not None:
+            raise InputError("sample_chains: proposal widths mean nothing under move='stretch' (the move has none to tune)")
     if evaluate is not None and device:
         raise InputError("sample_chains: an evaluate callable runs the definition route only (device=False)")
     if evaluate is None and fit is None:
@@ -320,8 +419,10 @@ def sample_chains(fit, params, n_steps, walkers=8, seed=0, fixed=None, start=Non
     n_chains = R * W
     if n_chains > MAX_CHAINS:
         raise InputError(f"sample_chains: {R} problems x {W} walkers = {n_chains} chains: at most {MAX_CHAINS}")
+    if stretch and (W % 2 or W < 2 * (d + 1)):
+        raise InputError(f"sample_chains: the stretch move needs an even number of walkers, at least 2 (n_params + 1) = {2 * (d + 1)}")
     width = q.per_param("proposal", proposal, [s.proposal for s in specs])
-    if np.any(~(width > 0)):
+    if not stretch and np.any(~(width > 0)):
         raise InputError(f"sample_chains: every proposal width must be > 0 ({dict(zip(names, width.tolist()))})")
     centre = None
     if start is not None:
@@ -332,6 +433,9 @@ def sample_chains(fit, params, n_steps, walkers=8, seed=0, fixed=None, start=Non
         spread = q.per_param("scatter", scatter if not np.isscalar(scatter) else {n: scatter for n in names}, width)
         if np.any(~(spread >= 0)):
             raise InputError("sample_chains: scatter must be >= 0")
+        if stretch and np.any(~(spread > 0)):
+            raise InputError("sample_chains: under move='stretch' scatter must be > 0 in every parameter (an ensemble that starts "
+                             f"collapsed never moves: {dict(zip(names, spread.tolist()))})")
     elif scatter is not None:
         raise InputError("sample_chains: scatter needs a start")
 
@@ -356,7 +460,7 @@ def sample_chains(fit, params, n_steps, walkers=8, seed=0, fixed=None, start=Non
 
     handle = None
     if evaluate is not None:
-        def evaluator(x):
+        def evaluator(x, rows_which=None):
             out = evaluate(batch_of(x))
             if isinstance(out, tuple):
                 return np.asarray(out[0], dtype=float), np.asarray(out[1], dtype=float)
@@ -364,16 +468,16 @@ def sample_chains(fit, params, n_steps, walkers=8, seed=0, fixed=None, start=Non
             return lnl, -2.0 * lnl
     elif not device:
         if realisations is not None:
-            def evaluator(x):
-                return realisations.log_likelihood_pairs(batch_of(x), which, **kwargs)
+            def evaluator(x, rows_which=None):
+                return realisations.log_likelihood_pairs(batch_of(x), which if rows_which is None else rows_which, **kwargs)
         else:
-            def evaluator(x):
+            def evaluator(x, rows_which=None):
                 return fit.log_likelihood_batch(batch_of(x), **kwargs)
     else:
         evaluator = None
         lib, h, refresh = q.create("vk_chain_create", fit, realisations, kwargs, fit_options, batch_of(x0), which)
         handle = (lib, h)
-    ch = Chains(names, specs, fixed_out, R, W, rng, width, burn, thin, bool(keep_chain), evaluator, handle)
+    ch = Chains(names, specs, fixed_out, R, W, rng, width, burn, thin, bool(keep_chain), evaluator, handle, move, stretch_a)
     if handle:
         ch._refresh = refresh                                # (keeps the realisations and the contexts the handle runs on)
         ch._fit = fit                                        # (a joint fit owns the covariance handles the chains read)

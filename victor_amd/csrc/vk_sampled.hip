@@ -14,6 +14,8 @@
 //                        the one-problem transition of vk_fit_simplex.h (plain C++, also compiled on its own by the CPU tests)
 //   vk_kernel_chain.h    Metropolis chains of the data vector or one realisation each (vk_chain_begin): start, propose and step
 //                        kernels, one thread per chain, over the one-chain transition of vk_chain_step.h (plain C++, likewise)
+//   vk_kernel_stretch.h  stretch-move ensembles on the same handles (vk_chain_begin_stretch): propose and step kernels of a
+//                        half-step, one thread per moving walker, over the transition of vk_stretch_step.h (plain C++, likewise)
 
 #include <hip/hip_runtime.h>
 
@@ -27,6 +29,7 @@
 #include "vk_host.h"
 #include "vk_kernel_fit.h"
 #include "vk_kernel_chain.h"
+#include "vk_kernel_stretch.h"
 
 using namespace vk;
 using vkh::check_joint;
@@ -422,6 +425,21 @@ struct __attribute__((visibility("hidden"))) vk_chain : Sampled {
   double *d_x0 = nullptr, *d_res_lnl = nullptr, *d_res_chi = nullptr;
   double *d_dz = nullptr, *d_logu = nullptr, *d_hx = nullptr, *d_hl = nullptr, *d_hc = nullptr;
   long long *d_acc = nullptr, *d_steps = nullptr, *d_kept = nullptr;
+  // a stretch block's numbers [64][2][C / 2] and the proposals of a half-step [P][C / 2]: one allocation of its own, made by the
+  // first vk_chain_begin_stretch
+  void* d_stretch = nullptr;
+  double *d_sz = nullptr, *d_slz = nullptr, *d_slogu = nullptr, *d_prop = nullptr;
+  int* d_partner = nullptr;
+  std::vector<int> h_which;                // the chains' realisation indices, read back for vk_chain_begin_stretch's check
+
+  void stretch_layout(Carve& c) {
+    const size_t block = (size_t)vkchain::kBlock * C;         // 64 sweeps x 2 halves x C / 2
+    c.take(d_sz, block);
+    c.take(d_slz, block);
+    c.take(d_slogu, block);
+    c.take(d_prop, (size_t)P * (C / 2));
+    c.take(d_partner, block);
+  }
 
   void shape(int n, const double* lo, const double* hi) {
     C = n;
@@ -507,6 +525,10 @@ const char* vk_chain_last_error(const vk_chain* f) { return f ? f->err.c_str() :
 void vk_chain_destroy(vk_chain* f) {
   if (!f) return;
   if (f->in_flight) (void)hipStreamSynchronize(f->ctx->stream);
+  if (f->d_stretch) {
+    (void)hipSetDevice(f->ctx->device);
+    (void)hipFree(f->d_stretch);
+  }
   sampled_destroy(f);
 }
 
@@ -568,6 +590,94 @@ int vk_chain_begin(vk_chain* f, int32_t n_steps, const double* dz, const double*
     a.hist_chi2 = hist ? f->d_hc + (size_t)slot * C : nullptr;
     if (hist) ++slot;
     rc = sampled_launch(f, vk_chain_step_kernel, a.C, kChainBlock, a);
+  }
+  if (rc) return sampled_abort(f, rc);
+  f->in_flight = n_steps;
+  f->block_kept = slot;
+  if (n_kept) *n_kept = slot;
+  f->err.clear();
+  return VK_OK;
+}
+
+// A block of stretch-move sweeps on the chains of a handle read as C / walkers ensembles (vk_kernel_stretch.h).  Per half-step:
+// the propose kernel, the evaluation of the C / 2 rows (sampled_evaluate: of a joint fit, forked onto the blocks' streams and
+// joined back onto the lead stream) and the step kernel - plain launches on the handle's stream, no host synchronisation and no
+// graph inside the block.  Everything the kernels index with is checked here first.
+int vk_chain_begin_stretch(vk_chain* f, int32_t n_steps, int32_t walkers, const double* z, const double* lz, const double* logu,
+                           const int32_t* partner, int64_t first_step, int64_t burn, int64_t thin, int32_t want_history,
+                           int32_t* n_kept) {
+  if (!f) return VK_E_ARG;
+  vk_ctx* ctx = f->ctx;
+  const char* me = "vk_chain_begin_stretch: ";
+  if (!z || !lz || !logu || !partner) return refused(f, std::string(me) + "NULL argument");
+  if (!f->started) return refused(f, std::string(me) + "the chains have no start (vk_chain_start)");
+  if (f->in_flight) return refused(f, std::string(me) + "the previous block has not been finished (vk_chain_finish)");
+  if (n_steps < 1 || n_steps > vkchain::kBlock) return refused(f, std::string(me) + "need 1 <= sweeps <= 64 in a block");
+  if (first_step < 0 || burn < 0 || thin < 1) return refused(f, std::string(me) + "need first_step >= 0, burn >= 0, thin >= 1");
+  if (walkers < 2 || walkers % 2) return refused(f, std::string(me) + "an ensemble needs an even number of walkers, at least 2");
+  if (f->C % walkers)
+    return refused(f, std::string(me) + std::to_string(f->C) + " chains are not a whole number of ensembles of " + std::to_string(walkers));
+  const int half = walkers / 2;
+  const size_t M = (size_t)f->C / 2, n = (size_t)n_steps * 2 * M;
+  for (size_t i = 0; i < n; ++i)
+    if (partner[i] < 0 || partner[i] >= half)
+      return refused(f, std::string(me) + "partner index " + std::to_string(partner[i]) + " (entry " + std::to_string(i) +
+                            ") is outside 0.." + std::to_string(half - 1));
+  int rc = sampled_ready(f, "vk_chain_begin_stretch", "chain", true);
+  if (rc) return rc;
+  VK_SAMPLED_HIP(f, hipSetDevice(ctx->device));
+  if (f->real) {                           // partners share their walker's data vector: one realisation per ensemble
+    if (f->h_which.empty()) {
+      f->h_which.resize(f->C);
+      VK_SAMPLED_HIP(f, hipMemcpy(f->h_which.data(), f->d_which, (size_t)f->C * sizeof(int), hipMemcpyDeviceToHost));
+    }
+    for (int c = 0; c < f->C; ++c)
+      if (f->h_which[c] != f->h_which[c - c % walkers])
+        return refused(f, std::string(me) + "chain " + std::to_string(c) + " is not of the realisation of its ensemble's first walker");
+  }
+  if (!f->d_stretch) {
+    Carve count;
+    f->stretch_layout(count);
+    if (hipMalloc(&f->d_stretch, count.bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      f->d_stretch = nullptr;
+      f->err = std::string(me) + "cannot allocate " + std::to_string(count.bytes) + " bytes of device memory";
+      return VK_E_HIP;
+    }
+    Carve mem{static_cast<char*>(f->d_stretch)};
+    f->stretch_layout(mem);
+  }
+  // the stream is idle (the block before was finished): plain copies, complete on return
+  VK_SAMPLED_HIP(f, hipMemcpy(f->d_sz, z, n * sizeof(double), hipMemcpyHostToDevice));
+  VK_SAMPLED_HIP(f, hipMemcpy(f->d_slz, lz, n * sizeof(double), hipMemcpyHostToDevice));
+  VK_SAMPLED_HIP(f, hipMemcpy(f->d_slogu, logu, n * sizeof(double), hipMemcpyHostToDevice));
+  VK_SAMPLED_HIP(f, hipMemcpy(f->d_partner, partner, n * sizeof(int), hipMemcpyHostToDevice));
+  StretchArgs a{};
+  a.c = chain_args(f);
+  a.half = half;
+  a.M = (int)M;
+  a.prop = f->d_prop;
+  const size_t CP = (size_t)f->C * f->P;
+  int slot = 0;
+  for (int t = 0; t < n_steps && rc == VK_OK; ++t) {
+    const bool kept = vkchain::is_kept(first_step + t, burn, thin);
+    const bool hist = kept && want_history;
+    a.c.kept = kept ? 1 : 0;
+    a.c.hist_x = hist ? f->d_hx + (size_t)slot * CP : nullptr;
+    a.c.hist_lnl = hist ? f->d_hl + (size_t)slot * f->C : nullptr;
+    a.c.hist_chi2 = hist ? f->d_hc + (size_t)slot * f->C : nullptr;
+    if (hist) ++slot;
+    for (int side = 0; side < 2 && rc == VK_OK; ++side) {
+      const size_t at = ((size_t)t * 2 + side) * M;
+      a.side = side;
+      a.z = f->d_sz + at;
+      a.lz = f->d_slz + at;
+      a.logu = f->d_slogu + at;
+      a.partner = f->d_partner + at;
+      rc = sampled_launch(f, vk_stretch_propose_kernel, a.M, kChainBlock, a);
+      if (rc == VK_OK) rc = sampled_evaluate(f, (long long)M, f->d_res_lnl, f->d_res_chi);
+      if (rc == VK_OK) rc = sampled_launch(f, vk_stretch_step_kernel, a.M, kChainBlock, a);
+    }
   }
   if (rc) return sampled_abort(f, rc);
   f->in_flight = n_steps;

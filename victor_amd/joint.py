@@ -353,13 +353,13 @@ class JointFit:
         return best_fit(self, params, fixed, start, step, xtol, ftol, max_iter, restarts, kwargs)
 
     def sample_chains(self, params, n_steps, walkers=8, seed=0, fixed=None, start=None, scatter=None, proposal=None, burn=0,
-                      thin=1, keep_chain=True, device=True, **kwargs):
+                      thin=1, keep_chain=True, device=True, move="metropolis", stretch_a=2.0, **kwargs):
         """``walkers`` Metropolis chains of the joint lnL, stepped on the GPU (``device=True``) or by the NumPy loop over
         :meth:`log_likelihood_batch` that defines them (``device=False``).  Arguments and result as ``CCFFit.sample_chains``
-        (:mod:`victor_amd.chains`); the result keeps this joint fit alive."""
+        (:mod:`victor_amd.chains`), ``move="stretch"`` included; the result keeps this joint fit alive."""
         from .chains import sample_chains
         return sample_chains(self, params, n_steps, walkers, seed, fixed, start, scatter, proposal, burn, thin, keep_chain, device,
-                             kwargs)
+                             kwargs, move=move, stretch_a=stretch_a)
 
     @property
     def n_data(self):
@@ -407,13 +407,14 @@ class JointRealisations:
         return best_fit(self.joint, params, fixed, start, step, xtol, ftol, max_iter, restarts, kwargs, realisations=self)
 
     def sample_chains(self, params, n_steps, walkers=8, seed=0, fixed=None, start=None, scatter=None, proposal=None, burn=0,
-                      thin=1, keep_chain=True, device=True, **kwargs):
+                      thin=1, keep_chain=True, device=True, move="metropolis", stretch_a=2.0, **kwargs):
         """``walkers`` Metropolis chains of EVERY joint realisation in lock step, on the GPU (``device=True``) or by the NumPy
         loop over :meth:`log_likelihood_pairs` that defines them (``device=False``).  Arguments and result as
-        ``Realisations.sample_chains``; ``start`` may be the ``BestFit`` of :meth:`best_fit`."""
+        ``Realisations.sample_chains`` (``move="stretch"``: one ensemble per joint realisation); ``start`` may be the ``BestFit``
+        of :meth:`best_fit`."""
         from .chains import sample_chains
         return sample_chains(self.joint, params, n_steps, walkers, seed, fixed, start, scatter, proposal, burn, thin, keep_chain,
-                             device, kwargs, realisations=self)
+                             device, kwargs, realisations=self, move=move, stretch_a=stretch_a)
 
     def _eval(self, params, kwargs, which=None):
         joint = self.joint
