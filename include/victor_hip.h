@@ -530,6 +530,12 @@ int vk_sync(vk_ctx* ctx);
 size_t vk_joint_workspace_doubles(vk_ctx* const* ctxs, int32_t n_ctx, int64_t n);
 int vk_joint_eval_device_async(vk_ctx* const* ctxs, int32_t n_ctx, const vk_eval_opts* opts, const double* d_params,
                                int64_t n, double* d_lnl, double* d_chi2, double* d_ws);
+/* The same with a row set per block (per-block nuisance parameters: a sigma_v of each quantile's own): d_params holds n_ctx sets
+ * of n rows and block q's launches read d_params + q * par_stride (par_stride in doubles, 0 or >= n * VK_NPAR).  par_stride == 0
+ * is the call above - it IS that call: the same launches on the same rows.  Block-diagonal, every block reads every column,
+ * beta included, from its own rows. */
+int vk_joint_eval_blocks_device_async(vk_ctx* const* ctxs, int32_t n_ctx, const vk_eval_opts* opts, const double* d_params,
+                                      int64_t par_stride, int64_t n, double* d_lnl, double* d_chi2, double* d_ws);
 
 /* ---- joint fit under ONE covariance matrix across the data vectors ---------------------------------------------------
  * The quantiles of a density-split analysis share their galaxies and voids: their data vectors are correlated and the
@@ -566,6 +572,14 @@ void vk_joint_cov_destroy(vk_joint_cov* h);
 size_t vk_joint_cov_workspace_doubles(const vk_joint_cov* h, int64_t n);
 int vk_joint_cov_eval_device_async(vk_joint_cov* h, vk_ctx* const* ctxs, int32_t n_ctx, const vk_eval_opts* opts,
                                    const double* d_params, int64_t n, double* d_lnl, double* d_chi2, double* d_ws);
+/* The same with a row set per block, as vk_joint_eval_blocks_device_async takes them: block q's theory launch reads d_params +
+ * q * par_stride; par_stride == 0 is the call above.  UNDER A JOINT COVARIANCE BETA OF A POINT IS READ FROM BLOCK 0'S ROW: the
+ * joint chi-square kernel brackets the covariance slices, takes -1/2 log det C(beta) and interpolates every block's data vector
+ * with that one beta.  A block's own beta column reaches its theory launch only; callers that grid the covariance in beta keep
+ * beta the same in every block's row. */
+int vk_joint_cov_eval_blocks_device_async(vk_joint_cov* h, vk_ctx* const* ctxs, int32_t n_ctx, const vk_eval_opts* opts,
+                                          const double* d_params, int64_t par_stride, int64_t n, double* d_lnl, double* d_chi2,
+                                          double* d_ws);
 
 /* ---- joint fit under ONE covariance against many simulation realisations of every block --------------------------------
  * Validating a density-split pipeline on the mocks its joint covariance was estimated from: joint realisation m is realisation
@@ -583,11 +597,17 @@ int vk_joint_cov_eval_device_async(vk_joint_cov* h, vk_ctx* const* ctxs, int32_t
  *   contexts with different n_real and an index of which out of range. */
 int vk_joint_cov_eval_realisations(vk_joint_cov* h, vk_ctx* const* ctxs, int32_t n_ctx, const vk_eval_opts* opts,
                                    const double* params, int64_t n, const int32_t* which, double* lnl, double* chi2);
+/* The same with a row set per block: params [n_ctx][n][VK_NPAR] (host), block q's rows at params + q * n * VK_NPAR.  The points
+ * are cut into the chunks of the call above (at most 65536 points) and each block's slice of a chunk is uploaded for that block's
+ * theory launch; beta of a point is block 0's (vk_joint_cov_eval_blocks_device_async).  With the same rows in every set it
+ * returns the bits of the call above. */
+int vk_joint_cov_eval_realisations_blocks(vk_joint_cov* h, vk_ctx* const* ctxs, int32_t n_ctx, const vk_eval_opts* opts,
+                                          const double* params, int64_t n, const int32_t* which, double* lnl, double* chi2);
 
 /* ---- best fits and Metropolis chains of a joint fit: the data vectors, or every joint realisation ------------------------
  * The handles of the two sections above over a joint fit instead of one context: a problem (a chain) samples ONE parameter row
- * for all blocks, and every other call of those sections (run, start, begin, finish, state, last_error, destroy) serves the
- * handle unchanged.  ctxs [n_ctx]: the blocks' contexts, lead first, all on one device, each with a data vector.
+ * for all blocks - or, made by the _blocks forms below, a row per block - and every other call of those sections (run, start,
+ * begin, begin_stretch, finish, state, last_error, destroy) serves the handle unchanged.  ctxs [n_ctx]: the blocks' contexts, lead first, all on one device, each with a data vector.
  *   cov == NULL   block-diagonal: lnL and chi2 of the blocks add in block order and a failed block fails the row, the rule of
  *                 vk_joint_eval_device_async;
  *   otherwise     the joint vector under the handle's covariance, ctxs[0] the context it was created with and the blocks'
@@ -611,6 +631,31 @@ vk_fit* vk_fit_create_joint(vk_ctx* const* ctxs, int32_t n_ctx, vk_joint_cov* co
 vk_chain* vk_chain_create_joint(vk_ctx* const* ctxs, int32_t n_ctx, vk_joint_cov* cov, const vk_eval_opts* opts,
                                 int32_t n_chains, int32_t n_params, const int32_t* columns, const double* lo, const double* hi,
                                 const double* base_rows, double alpha, const int32_t* which, char* err, size_t errlen);
+/* Per-block nuisance parameters.  The quantiles of a density split share fsigma8, beta and epsilon; each has a velocity
+ * dispersion (a bias, an Av) of its own.  The _blocks forms keep a ROW PER BLOCK for every problem (chain):
+ *   param_block [n_params]  -1: sampled parameter j is written to every block's row; q (0 .. n_ctx - 1): to block q's row alone.
+ *                A (column, block) pair is named once, and a column is either shared or per block, not both; VK_WALK_EPSILON
+ *                counts as a column (an epsilon per block sets that block's aperp / apar / epsilon).
+ *   base_rows    [n_ctx][n][VK_NPAR]: the fixed parameters and defaults of block q's rows at base_rows + q * n * VK_NPAR (a
+ *                parameter fixed at a value per block differs between the sets).
+ * Everything else is the call above, and 1 <= n_params <= 10 still counts every sampled value: five quantiles with one
+ * nuisance parameter each, fsigma8 and epsilon are 7.  The rows are formed on the device by the one routine the other handles
+ * use (vk_sampled_row.h over the selection rule of vk_row_select.h) and evaluated through
+ * vk_joint_eval_blocks_device_async / vk_joint_cov_eval_blocks_device_async and their twins against realisations, so the bits are
+ * those entry points' for the same rows in the same launches; with every param_block -1 and the same base rows in every set they
+ * are the bits of a handle of vk_*_create_joint.  Under a covariance handle beta of a row is block 0's.
+ * Refused in addition: param_block NULL or outside -1 .. n_ctx - 1, a (column, block) pair named twice, a column both shared and
+ * per block, and VK_P_BETA per block under a handle gridded in beta (n_beta > 0).
+ * Not offered: more than 10 sampled values, a beta per block under a covariance gridded in beta, blocks that cannot share one
+ * option block. */
+vk_fit* vk_fit_create_joint_blocks(vk_ctx* const* ctxs, int32_t n_ctx, vk_joint_cov* cov, const vk_eval_opts* opts,
+                                   int32_t n_problems, int32_t n_params, const int32_t* columns, const int32_t* param_block,
+                                   const double* lo, const double* hi, const double* base_rows, double alpha, const int32_t* which,
+                                   char* err, size_t errlen);
+vk_chain* vk_chain_create_joint_blocks(vk_ctx* const* ctxs, int32_t n_ctx, vk_joint_cov* cov, const vk_eval_opts* opts,
+                                       int32_t n_chains, int32_t n_params, const int32_t* columns, const int32_t* param_block,
+                                       const double* lo, const double* hi, const double* base_rows, double alpha,
+                                       const int32_t* which, char* err, size_t errlen);
 
 /* ---- many one-point callers sharing one GPU: mailboxes in shared memory -----------------------------------------------
  * The reference is sampled by cobaya, which asks for ONE likelihood per call (victor/likelihoods/CCFLikelihood.py:32-39); more

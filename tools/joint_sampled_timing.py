@@ -3,7 +3,9 @@ vk_chain_create_joint): the five-quantile density-split fit under a correlated f
 (beta fixed: the blocks ignore it; d = 3).  best_fit: wall time of a call, iterations and rows per fit.  sample_chains: W = 8 and
 64 chains per mock (C = 128, 1024), 512 steps, the device route against the definition route (device=False: the host loop over
 log_likelihood_pairs a user could write before), the two alternating in one process, median of the repeats after a warm-up, and
-against the ceiling - log_likelihood_pairs alone at batch C, in rows/s.
+against the ceiling - log_likelihood_pairs alone at batch C, in rows/s.  Then the per-block case beside it in the same run: a
+velocity dispersion of each quantile's own (per_block(params, ["sigma_v"], 5): d = 7, a row per block through
+vk_fit_create_joint_blocks / vk_chain_create_joint_blocks), the best fits of the 16 mocks and the device route of the chains.
 
 Usage: joint_sampled_timing.py OUT [--commit SHA] [--steps N] [--repeats N] [--profile]
   --profile: just two best-fit calls and one W = 64 device run (the workload of a `rocprofv3 --kernel-trace --stats` run)."""
@@ -131,10 +133,49 @@ def main():
                "acceptance": acc}
         print(json.dumps({k: v for k, v in rec.items() if not k.endswith("_all")}), flush=True)
         recs.append(rec)
+    blocks = per_block_case(jr, steps, repeats)
     with open(out, "w") as fh:
         json.dump({"commit": commit or None,
                    "config": "five density-split quantiles, correlated fixed joint covariance, d = 3 (beta fixed), 16-mock stacks",
-                   "best_fit": best, "chains": recs}, fh, indent=1)
+                   "best_fit": best, "chains": recs, "per_block": blocks}, fh, indent=1)
+
+
+def per_block_case(jr, steps, repeats):
+    """sigma_v per quantile (d = 7 on the five quantiles, 16 mocks): best fits and the chains' device route, timed as above."""
+    from victor_amd.joint import per_block
+    blk = per_block(PARAMS, ["sigma_v"], 5)
+    names = [n for n in blk if n.partition("@")[0] in NAMES]
+    width = {n: PARAMS[n.partition("@")[0]]["prior"]["max"] - PARAMS[n.partition("@")[0]]["prior"]["min"] for n in names}
+    tol = dict(xtol={n: 1e-5 * w for n, w in width.items()}, ftol=1e-6, restarts=1)
+    jr.best_fit(blk, fixed=FIXED, **tol)
+    warm(jr)
+    tb = []
+    for _ in range(repeats):
+        t0 = time.perf_counter()
+        bf = jr.best_fit(blk, fixed=FIXED, **tol)
+        tb.append(time.perf_counter() - t0)
+    S = len(names) + 1
+    out = {"names": names, "best_fit": {"problems": N_REAL, "wall_s_median": float(np.median(tb)), "wall_s_all": tb,
+                                        "n_iter_mean": float(bf.n_iter.mean()), "n_iter_max": int(bf.n_iter.max()),
+                                        "rows_per_fit": float(bf.n_iter.mean()) * S,
+                                        "converged": int((bf.status == bf.CONVERGED).sum())}, "chains": []}
+    print(json.dumps({"per_block_best_fit": {k: v for k, v in out["best_fit"].items() if not k.endswith("_all")}}), flush=True)
+    for W in (8, 64):
+        C = N_REAL * W
+        jr.sample_chains(blk, 64, walkers=W, seed=0, fixed=FIXED)
+        warm(jr)
+        t = []
+        for _ in range(repeats):
+            t0 = time.perf_counter()
+            ch = jr.sample_chains(blk, steps, walkers=W, seed=0, fixed=FIXED)
+            t.append(time.perf_counter() - t0)
+        dev_s = float(np.median(t))
+        rec = {"walkers": W, "chains": C, "steps": steps, "device_wall_s_median": dev_s, "device_wall_s_all": t,
+               "device_us_per_step": 1e6 * dev_s / steps, "device_rows_per_s": C * steps / dev_s,
+               "acceptance": float(ch.acceptance.mean())}
+        print(json.dumps({"per_block_chains": {k: v for k, v in rec.items() if not k.endswith("_all")}}), flush=True)
+        out["chains"].append(rec)
+    return out
 
 
 if __name__ == "__main__":

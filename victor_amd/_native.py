@@ -166,6 +166,19 @@ SYMBOLS = {
                                   _dp, _dp, C.c_double, C.POINTER(C.c_int32), C.c_char_p, C.c_size_t]),
     "vk_chain_create_joint": (_vp, [C.POINTER(C.c_void_p), C.c_int32, _vp, _optp, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _dp,
                                     _dp, _dp, C.c_double, C.POINTER(C.c_int32), C.c_char_p, C.c_size_t]),
+    # the joint entry points with a row set per block (per-block nuisance parameters)
+    "vk_joint_eval_blocks_device_async": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, _optp, _vp, C.c_int64, C.c_int64, _vp, _vp,
+                                                    _vp]),
+    "vk_joint_cov_eval_blocks_device_async": (C.c_int, [_vp, C.POINTER(C.c_void_p), C.c_int32, _optp, _vp, C.c_int64, C.c_int64,
+                                                        _vp, _vp, _vp]),
+    "vk_joint_cov_eval_realisations_blocks": (C.c_int, [_vp, C.POINTER(C.c_void_p), C.c_int32, _optp, _dp, C.c_int64,
+                                                        C.POINTER(C.c_int32), _dp, _dp]),
+    "vk_fit_create_joint_blocks": (_vp, [C.POINTER(C.c_void_p), C.c_int32, _vp, _optp, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
+                                         C.POINTER(C.c_int32), _dp, _dp, _dp, C.c_double, C.POINTER(C.c_int32), C.c_char_p,
+                                         C.c_size_t]),
+    "vk_chain_create_joint_blocks": (_vp, [C.POINTER(C.c_void_p), C.c_int32, _vp, _optp, C.c_int32, C.c_int32,
+                                           C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp, _dp, _dp, C.c_double,
+                                           C.POINTER(C.c_int32), C.c_char_p, C.c_size_t]),
     "vk_serve_mailboxes": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, _optp, _vp, C.c_int32, _vp, C.c_double, C.c_int32,
                            C.c_double, C.POINTER(vk_serve_stats)]),
     "vk_timing_enable": (C.c_int, [_vp, C.c_int]),

@@ -195,8 +195,17 @@ class CCFFit(CCFModel):
     def _fit_side(self):
         return self
 
+    @staticmethod
+    def _refuse_block_names(params):
+        """``"name@q"`` addresses block q of a :class:`victor_amd.joint.JointFit`: a single fit has no blocks.  Checked once
+        where every route forms its rows (``_fit_rows``) and at the two public entries, which plan their engine first."""
+        if not isinstance(params, np.ndarray) and any(isinstance(k, str) and "@" in k for k in params):
+            raise InputError("per-block parameters ('name@block': "
+                             f"{sorted(k for k in params if isinstance(k, str) and '@' in k)}) need a JointFit")
+
     def _fit_rows(self, params, model):
         need_beta = self._needs_beta(model) or not self.fixed_data
+        self._refuse_block_names(params)
         if not isinstance(params, np.ndarray) and not self.fixed_data and params.get("beta", None) is None:
             raise InputError("Need to supply a valid value of beta for interpolation")   # ccf_fit.py:188-189
         return self._param_rows(params, need_beta, self._needs_fsigma8(model))
@@ -275,6 +284,7 @@ class CCFFit(CCFModel):
 
     def log_likelihood(self, params, **kwargs):
         """(lnL, chi2) at one parameter point (reference: ccf_fit.py:356-483)."""
+        self._refuse_block_names(params)
         plan = self._single_point_plan() if (not kwargs and type(params) is dict) else None
         row = None
         if plan is not None:
@@ -299,6 +309,7 @@ class CCFFit(CCFModel):
     def log_likelihood_batch(self, params, **kwargs):
         """(lnL[n], chi2[n]) for a batch: ``params`` is a dict of equal-length arrays (scalars broadcast) or an
         ``(n, VK_NPAR)`` array of rows in the column order of ``include/victor_hip.h``."""
+        self._refuse_block_names(params)
         plan = self._single_point_plan() if not kwargs else None
         if plan is not None and plan[0] is not None:
             # plain call (a sampler's step): the cached (engine, option block) pair of log_likelihood, no option merging

@@ -1,7 +1,8 @@
 """Metropolis chains and stretch-move ensembles of the data vector and of every realisation, stepped on the GPU: ``CCFFit.sample_chains`` and
 ``Realisations.sample_chains``; of a joint fit, ``JointFit.sample_chains`` and ``JointRealisations.sample_chains`` (one parameter
 row for all blocks: ``fit`` is the ``JointFit`` below, the definition route runs over its ``log_likelihood_batch`` /
-``JointRealisations.log_likelihood_pairs``, the device route through ``vk_chain_create_joint``).
+``JointRealisations.log_likelihood_pairs``, the device route through ``vk_chain_create_joint``; with ``"name@q"`` parameters, :mod:`victor_amd.joint`, a row per block and
+``vk_chain_create_joint_blocks``).
 
 The reference is sampled by cobaya, one likelihood per call and one data vector at a time (reference:
 ``victor/likelihoods/CCFLikelihood.py:32``).  Mock validation wants the posterior of EVERY mock beside its best fit: here
@@ -406,7 +407,7 @@ def sample_chains(fit, params, n_steps, walkers=8, seed=0, fixed=None, start=Non
     specs, names, fixed_all, lo, hi, d = q.specs, q.names, q.fixed_all, q.lo, q.hi, len(q.names)
     arrays = sorted(k for k, v in fixed_all.items() if np.ndim(v) > 0)
     if evaluate is None:
-        q.check_columns()
+        q.check_columns(fit)
         if d > 10:
             raise InputError("sample_chains: at most 10 sampled parameters")
         q.check_alpha()

@@ -1522,12 +1522,21 @@ static int fan_out_with(vk_ctx* const* ctxs, int n_ctx, Launch launch) {
   return VK_OK;
 }
 
+// Block q reads its rows at d_par + q * par_stride (doubles; 0: one row set for all blocks).
 template <class Out>
-static int fan_out(vk_ctx* const* ctxs, int n_ctx, const vk_eval_opts* opts, const double* d_par, long long n, Out out) {
+static int fan_out(vk_ctx* const* ctxs, int n_ctx, const vk_eval_opts* opts, const double* d_par, long long par_stride, long long n,
+                   Out out) {
   return fan_out_with(ctxs, n_ctx, [&](int q, vk_ctx* c) {
     const BlockOut o = out(q);
-    return vk_eval_batch_device_async(c, opts, d_par, n, o.lnl, o.chi2, o.theory);
+    return vk_eval_batch_device_async(c, opts, d_par + q * par_stride, n, o.lnl, o.chi2, o.theory);
   });
+}
+
+// a per-block row set of n rows: sets back to back or further apart, never overlapping
+static int check_par_stride(vk_ctx* lead, long long par_stride, long long n) {
+  if (par_stride != 0 && par_stride < n * VK_NPAR)
+    return fail(lead, VK_E_ARG, "joint fit: par_stride %lld is neither 0 nor at least n * VK_NPAR = %lld", par_stride, n * VK_NPAR);
+  return VK_OK;
 }
 
 // the lead stream waits for every block's stream
@@ -1590,6 +1599,7 @@ struct RealChunks {
   long long per_point, m_max;         // outputs per point (n_real; pairs mode 1), points per chunk
   double *d_par = nullptr, *d_lnl = nullptr, *d_chi = nullptr;
   int32_t* d_which = nullptr;
+  int sets = 1;                       // row sets of params: [sets][n][VK_NPAR] on the host, [sets][m_max][VK_NPAR] in d_par
 
   RealChunks(const int32_t* which, int n_real, int64_t n)
       : per_point(which ? 1 : n_real),
@@ -1599,7 +1609,9 @@ struct RealChunks {
   int run(vk_ctx* ctx, const double* params, const int32_t* which, int64_t n, double* lnl, double* chi2, Enqueue enqueue) const {
     for (long long off = 0; off < n; off += m_max) {
       const long long m = std::min<long long>(m_max, n - off);
-      VK_HIP(ctx, hipMemcpyAsync(d_par, params + off * VK_NPAR, (size_t)m * VK_NPAR * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+      for (int q = 0; q < sets; ++q)
+        VK_HIP(ctx, hipMemcpyAsync(d_par + (size_t)q * m_max * VK_NPAR, params + ((size_t)q * n + off) * VK_NPAR,
+                                   (size_t)m * VK_NPAR * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
       if (which) VK_HIP(ctx, hipMemcpyAsync(d_which, which + off, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
       int rc = enqueue(m);
       if (rc) return rc;
@@ -1697,8 +1709,11 @@ vkh::JointRealWs vkh::joint_real_carve(const vk_joint_cov* h, double* d_ws, long
   return w;
 }
 
+int vkh::joint_cov_n_beta(const vk_joint_cov* h) { return h ? h->n_beta : 0; }
+
 int vkh::enqueue_joint_cov_realisations(vk_joint_cov* h, vk_ctx* const* ctxs, int n_ctx, const vk_eval_opts* opts, const double* d_par,
-                                        long long m, const int32_t* d_which, double* d_lnl, double* d_chi, const JointRealWs& w) {
+                                        long long par_stride, long long m, const int32_t* d_which, double* d_lnl, double* d_chi,
+                                        const JointRealWs& w) {
   vk_ctx* lead = ctxs[0];
   VK_HIP(lead, hipSetDevice(lead->device));
   const int n_real = lead->n_real;
@@ -1708,7 +1723,8 @@ int vkh::enqueue_joint_cov_realisations(vk_joint_cov* h, vk_ctx* const* ctxs, in
   for (int q = 0; q < n_ctx; ++q) jr.stride[q] = ctxs[q]->real_block;
   jr.n_real = n_real;
   jr.which = d_which;
-  int rc = fan_out(ctxs, n_ctx, opts, d_par, m, [&](int q) { return BlockOut{nullptr, nullptr, w.th + (size_t)m * ja.blk[q].off}; });
+  int rc = fan_out(ctxs, n_ctx, opts, d_par, par_stride, m,
+                   [&](int q) { return BlockOut{nullptr, nullptr, w.th + (size_t)m * ja.blk[q].off}; });
   if (rc) return rc;
   // meanwhile on the lead stream: the log-det factor of every point and, in pairs mode, the points sorted by covariance slice
   hipError_t e = hipSuccess;
@@ -1725,8 +1741,9 @@ int vkh::enqueue_joint_cov_realisations(vk_joint_cov* h, vk_ctx* const* ctxs, in
   return joint_chi2(h, ctxs, n_ctx, e, "joint_real_chi2", vk_joint_real_chi2_kernel, tiles, joint_real_lds(h), jr);
 }
 
-int vkh::enqueue_joint_sum_realisations(vk_ctx* const* ctxs, int n_ctx, const vk_eval_opts* opts, const double* d_par, long long m,
-                                        const int32_t* d_which, double* d_lnl, double* d_chi, double* d_ws) {
+int vkh::enqueue_joint_sum_realisations(vk_ctx* const* ctxs, int n_ctx, const vk_eval_opts* opts, const double* d_par,
+                                        long long par_stride, long long m, const int32_t* d_which, double* d_lnl, double* d_chi,
+                                        double* d_ws) {
   vk_ctx* lead = ctxs[0];
   VK_HIP(lead, hipSetDevice(lead->device));
   int n_max = 0;
@@ -1734,7 +1751,7 @@ int vkh::enqueue_joint_sum_realisations(vk_ctx* const* ctxs, int n_ctx, const vk
   const long long block_stride = m * (n_max + 2);               // per block: lnl[m] | chi2[m] | theory workspace [m][N]
   int rc = fan_out_with(ctxs, n_ctx, [&](int q, vk_ctx* c) {
     double* blk = d_ws + q * block_stride;
-    return enqueue_realisations(c, opts, d_par, m, blk + 2 * m, blk, blk + m, d_which);
+    return enqueue_realisations(c, opts, d_par + q * par_stride, m, blk + 2 * m, blk, blk + m, d_which);
   });
   if (rc) return rc;
   const hipError_t e = join_block_streams(ctxs, n_ctx);
@@ -1757,17 +1774,24 @@ size_t vk_joint_workspace_doubles(vk_ctx* const* ctxs, int32_t n_ctx, int64_t n)
 
 int vk_joint_eval_device_async(vk_ctx* const* ctxs, int32_t n_ctx, const vk_eval_opts* opts, const double* d_params, int64_t n,
                                double* d_lnl, double* d_chi2, double* d_ws) {
+  return vk_joint_eval_blocks_device_async(ctxs, n_ctx, opts, d_params, 0, n, d_lnl, d_chi2, d_ws);
+}
+
+int vk_joint_eval_blocks_device_async(vk_ctx* const* ctxs, int32_t n_ctx, const vk_eval_opts* opts, const double* d_params,
+                                      int64_t par_stride, int64_t n, double* d_lnl, double* d_chi2, double* d_ws) {
   if (!ctxs || n_ctx < 1 || !ctxs[0]) return VK_E_ARG;
   vk_ctx* lead = ctxs[0];
   int rc = check_blocks(lead, nullptr, ctxs, n_ctx, false);
   if (rc) return rc;
   if (n < 0 || (n > 0 && (!d_params || !d_ws || !(d_lnl || d_chi2)))) return fail(lead, VK_E_ARG, "bad device buffers");
+  rc = check_par_stride(lead, par_stride, n);
+  if (rc) return rc;
   if (n == 0) return VK_OK;
   VK_HIP(lead, hipSetDevice(lead->device));
   int n_max = 0;
   for (int q = 0; q < n_ctx; ++q) n_max = std::max(n_max, ctxs[q]->N);
   const long long block_stride = (long long)n * (n_max + 2);    // per block: lnl[n] | chi2[n] | theory workspace [n][N]
-  rc = fan_out(ctxs, n_ctx, opts, d_params, n, [&](int q) {
+  rc = fan_out(ctxs, n_ctx, opts, d_params, par_stride, n, [&](int q) {
     double* blk = d_ws + q * block_stride;
     return BlockOut{blk, blk + n, blk + 2 * n};
   });
@@ -1874,6 +1898,12 @@ size_t vk_joint_cov_workspace_doubles(const vk_joint_cov* h, int64_t n) {
 
 int vk_joint_cov_eval_device_async(vk_joint_cov* h, vk_ctx* const* ctxs, int32_t n_ctx, const vk_eval_opts* opts,
                                    const double* d_params, int64_t n, double* d_lnl, double* d_chi2, double* d_ws) {
+  return vk_joint_cov_eval_blocks_device_async(h, ctxs, n_ctx, opts, d_params, 0, n, d_lnl, d_chi2, d_ws);
+}
+
+int vk_joint_cov_eval_blocks_device_async(vk_joint_cov* h, vk_ctx* const* ctxs, int32_t n_ctx, const vk_eval_opts* opts,
+                                          const double* d_params, int64_t par_stride, int64_t n, double* d_lnl, double* d_chi2,
+                                          double* d_ws) {
   if (!ctxs || n_ctx < 1 || !ctxs[0]) return VK_E_ARG;
   vk_ctx* lead = ctxs[0];
   if (!h) return fail(lead, VK_E_ARG, "joint covariance: handle is NULL");
@@ -1883,6 +1913,8 @@ int vk_joint_cov_eval_device_async(vk_joint_cov* h, vk_ctx* const* ctxs, int32_t
   if (rc) return rc;
   if (n < 0 || n > (1LL << 31) - kJointSortChunk || (n > 0 && (!d_params || !d_ws || !(d_lnl || d_chi2))))
     return fail(lead, VK_E_ARG, "bad device buffers");
+  rc = check_par_stride(lead, par_stride, n);
+  if (rc) return rc;
   if (n == 0) return VK_OK;
   VK_HIP(lead, hipSetDevice(lead->device));
   size_t o_sort;
@@ -1890,7 +1922,8 @@ int vk_joint_cov_eval_device_async(vk_joint_cov* h, vk_ctx* const* ctxs, int32_t
   JointArgs ja{};
   joint_args(h, ctxs, opts, d_params, n, d_lnl, d_chi2, d_ws, false, &ja);
   // the blocks' theory launches, theory only
-  rc = fan_out(ctxs, n_ctx, opts, d_params, n, [&](int q) { return BlockOut{nullptr, nullptr, d_ws + (size_t)n * ja.blk[q].off}; });
+  rc = fan_out(ctxs, n_ctx, opts, d_params, par_stride, n,
+               [&](int q) { return BlockOut{nullptr, nullptr, d_ws + (size_t)n * ja.blk[q].off}; });
   if (rc) return rc;
   // meanwhile on the lead stream: the points sorted by covariance slice (the data tables and params are ready behind ev_joint)
   const hipError_t e = h->n_beta > 0 ? enqueue_slice_sort(lead->stream, &ja, reinterpret_cast<int*>(d_ws + o_sort), n) : hipSuccess;
@@ -2314,8 +2347,9 @@ int vk_eval_realisations(vk_ctx* ctx, const vk_eval_opts* opts, const double* pa
 }
 
 // ---- joint fit under one covariance against many realisations of every block (include/victor_hip.h, vk_kernel_joint_real.h) -
-int vk_joint_cov_eval_realisations(vk_joint_cov* h, vk_ctx* const* ctxs, int32_t n_ctx, const vk_eval_opts* opts,
-                                   const double* params, int64_t n, const int32_t* which, double* lnl, double* chi2) {
+// sets: row sets of params - 1 (one row for all blocks) or n_ctx (block q's rows at params + q * n * VK_NPAR)
+static int joint_cov_eval_realisations(vk_joint_cov* h, vk_ctx* const* ctxs, int32_t n_ctx, const vk_eval_opts* opts,
+                                       const double* params, int sets, int64_t n, const int32_t* which, double* lnl, double* chi2) {
   if (!ctxs || n_ctx < 1 || !ctxs[0]) return VK_E_ARG;
   vk_ctx* lead = ctxs[0];
   if (!h) return fail(lead, VK_E_ARG, "joint covariance: handle is NULL");
@@ -2334,16 +2368,18 @@ int vk_joint_cov_eval_realisations(vk_joint_cov* h, vk_ctx* const* ctxs, int32_t
   VK_HIP(lead, hipSetDevice(lead->device));
   // a chunk is every block's theory launch (theory only, each on its own stream) and the joint chi-square launch behind them
   RealChunks ch(which, n_real, n);
+  ch.sets = sets;
   const long long m_max = ch.m_max;
+  const long long par_stride = sets > 1 ? m_max * VK_NPAR : 0;
   const long long chunks_max = (m_max + kJointSortChunk - 1) / kJointSortChunk;
   // scratch: params | theory [m][NT] (block q at offset m * off_q) | lnl | chi2 | -1/2 log det [m] | ints: which, singular,
   // and the slice sort's lo, rank, perm [m] and histograms [chunks + 1][n_beta]
   const size_t ints = (size_t)m_max * 5 + (size_t)(chunks_max + 1) * h->n_beta;
-  const size_t doubles = (size_t)m_max * (VK_NPAR + h->NT + 2 * ch.per_point + 1) + (ints + 1) / 2 + 1;
+  const size_t doubles = (size_t)m_max * ((size_t)sets * VK_NPAR + h->NT + 2 * ch.per_point + 1) + (ints + 1) / 2 + 1;
   rc = ensure_scratch(lead, doubles * sizeof(double));
   if (rc) return rc;
   ch.d_par = lead->d_scratch;
-  double* d_th = ch.d_par + (size_t)m_max * VK_NPAR;
+  double* d_th = ch.d_par + (size_t)sets * m_max * VK_NPAR;
   ch.d_lnl = d_th + (size_t)m_max * h->NT;
   ch.d_chi = ch.d_lnl + (size_t)m_max * ch.per_point;
   double* d_fac = ch.d_chi + (size_t)m_max * ch.per_point;
@@ -2351,9 +2387,19 @@ int vk_joint_cov_eval_realisations(vk_joint_cov* h, vk_ctx* const* ctxs, int32_t
   int* d_bad = ch.d_which + m_max;
   const vkh::JointRealWs w{d_th, d_fac, d_bad, d_bad + m_max, m_max};
   return ch.run(lead, params, which, n, lnl, chi2, [&](long long m) {
-    return vkh::enqueue_joint_cov_realisations(h, ctxs, n_ctx, opts, ch.d_par, m, which ? ch.d_which : nullptr,
+    return vkh::enqueue_joint_cov_realisations(h, ctxs, n_ctx, opts, ch.d_par, par_stride, m, which ? ch.d_which : nullptr,
                                                lnl ? ch.d_lnl : nullptr, chi2 ? ch.d_chi : nullptr, w);
   });
+}
+
+int vk_joint_cov_eval_realisations(vk_joint_cov* h, vk_ctx* const* ctxs, int32_t n_ctx, const vk_eval_opts* opts,
+                                   const double* params, int64_t n, const int32_t* which, double* lnl, double* chi2) {
+  return joint_cov_eval_realisations(h, ctxs, n_ctx, opts, params, 1, n, which, lnl, chi2);
+}
+
+int vk_joint_cov_eval_realisations_blocks(vk_joint_cov* h, vk_ctx* const* ctxs, int32_t n_ctx, const vk_eval_opts* opts,
+                                          const double* params, int64_t n, const int32_t* which, double* lnl, double* chi2) {
+  return joint_cov_eval_realisations(h, ctxs, n_ctx, opts, params, n_ctx, n, which, lnl, chi2);
 }
 
 }  // extern "C"

@@ -198,13 +198,19 @@ JointRealWs joint_real_carve(const vk_joint_cov* h, double* d_ws, long long m_ma
 // One launch set of vk_joint_cov_eval_realisations on m device rows: every block's theory launch (theory only, on its own stream
 // behind the lead's), the log-det factor and - pairs mode - the slice sort on the lead stream, the joint chi-square kernel behind
 // all of them.  d_which NULL: every realisation (outputs [m][n_real]); else device indices, outputs [m].  Enqueue only.
-// Both enqueue functions make the lead's device current themselves; the caller has run check_joint.
+// Both enqueue functions make the lead's device current themselves; the caller has run check_joint.  Block q's theory launch
+// reads its rows at d_par + q * par_stride (doubles; 0: one row set for all blocks); under a covariance beta of a point is block
+// 0's.
 int enqueue_joint_cov_realisations(vk_joint_cov* h, vk_ctx* const* ctxs, int n_ctx, const vk_eval_opts* opts, const double* d_par,
-                                   long long m, const int32_t* d_which, double* d_lnl, double* d_chi, const JointRealWs& w);
+                                   long long par_stride, long long m, const int32_t* d_which, double* d_lnl, double* d_chi,
+                                   const JointRealWs& w);
 // Block-diagonal, pairs mode: every block's enqueue_realisations on its own stream behind the lead's, into block q's part of d_ws
 // (lnl [m] | chi2 [m] | theory [m][N_max], the layout of vk_joint_eval_device_async), then the block-order sum on the lead stream.
-int enqueue_joint_sum_realisations(vk_ctx* const* ctxs, int n_ctx, const vk_eval_opts* opts, const double* d_par, long long m,
-                                   const int32_t* d_which, double* d_lnl, double* d_chi, double* d_ws);
+int enqueue_joint_sum_realisations(vk_ctx* const* ctxs, int n_ctx, const vk_eval_opts* opts, const double* d_par,
+                                   long long par_stride, long long m, const int32_t* d_which, double* d_lnl, double* d_chi,
+                                   double* d_ws);
+// slices of the handle's beta grid (0: one fixed covariance, or no handle)
+int joint_cov_n_beta(const vk_joint_cov* h);
 
 // sizeof(vk_ctx) and the offset of its last member as each host-compiled unit sees them (vk_create compares them with its own)
 size_t ctx_layout_walk(size_t* last_offset);

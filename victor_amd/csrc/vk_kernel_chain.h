@@ -32,7 +32,7 @@ struct ChainArgs {
   long long* n_accept;      // [C]
   long long* n_steps;       // [C]
   long long* n_kept;        // [C]
-  const double* base;       // [C][VK_NPAR]: fixed parameters and defaults of each chain's rows
+  const double* base;       // [C][VK_NPAR]: fixed parameters and defaults of each chain's rows (per row set)
   const int* which;         // [C]: realisation of each chain, or NULL (the fit's own data vector)
   const double* x0;         // [C][d]: starts (vk_chain_init_kernel)
   const double* res_lnl;    // [C]: results of the launch just evaluated
@@ -40,7 +40,7 @@ struct ChainArgs {
   const double* dz;         // [C][d]: increments of the step being decided (step kernel) / proposed (propose kernel)
   const double* logu;       // [C]
   const double* dz_next;    // [C][d]: increments of the following step, or NULL: no next row (the block ends)
-  double* rows;             // [C][VK_NPAR]: the next launch's rows
+  double* rows;             // [C][VK_NPAR]: the next launch's rows (per row set, blocks.row_stride apart)
   int* row_which;           // [C]: realisation of each row, or NULL
   double* hist_x;           // [C][d]: history slot of this step, or NULL (not kept, or no history wanted)
   double* hist_lnl;         // [C]
@@ -49,6 +49,7 @@ struct ChainArgs {
   int adopt;                // the launch just evaluated held the start positions: take its results, no decision
   int col[vkchain::kMaxP];  // row column of each sampled parameter; VK_WALK_EPSILON: epsilon -> aperp, apar, epsilon
   double alpha;
+  vkrow::Blocks blocks;     // the row sets of base and rows (one, or one per block of a joint fit) and each parameter's set
 };
 
 static_assert(sizeof(long long) == sizeof(int64_t), "the chain counters are 64-bit");
@@ -71,7 +72,7 @@ __device__ __forceinline__ vkchain::View chain_view(const ChainArgs& a, int c) {
 // the row of chain c at x (+ dz when dz is given and x + dz is inside the box)
 __device__ __forceinline__ void chain_emit(const ChainArgs& a, const vkchain::View& s, int c, const double* dz) {
   const bool move = dz != nullptr && vkchain::proposal_inside(a.box, s, dz);
-  sampled_row(a.base + (size_t)c * VK_NPAR, a.rows + (size_t)c * VK_NPAR, a.col, a.box.d, a.alpha, [&](int j) {
+  sampled_row(a.blocks, a.base, (size_t)c, a.rows, (size_t)c, a.col, a.box.d, a.alpha, [&](int j) {
     const double v = s.x[j * s.stride];
     return move ? v + dz[j] : v;
   });

@@ -20,25 +20,26 @@ constexpr int kFitBlock = 64;
 struct FitArgs {
   vkfit::Params q;
   vkfit::State* state;      // [n_problems]
-  const double* base;       // [n_problems][VK_NPAR]: fixed parameters and defaults of each problem's rows
+  const double* base;       // [n_problems][VK_NPAR]: fixed parameters and defaults of each problem's rows (per row set)
   const double* x0;         // [n_problems][d]: starts (vk_fit_init_kernel)
   const int* active;        // [n_active]: problem at each launch position (NULL: position = problem)
   int n_active;
   const double* lnl;        // [n_active * S] results of the launch just evaluated
   const double* chi2;
-  double* rows;             // [n_active * S][VK_NPAR]: the next launch's rows
+  double* rows;             // [n_active * S][VK_NPAR]: the next launch's rows (per row set, blocks.row_stride apart)
   int* row_which;           // [n_active * S]: realisation of each row, or NULL (the fit's own data vector)
   const int* which;         // [n_problems]: realisation of each problem, or NULL
   int* status;              // [n_problems]: -1 while the problem runs, then its VK_FIT_* status
   int col[vkfit::kMaxP];    // row column of each sampled parameter; VK_WALK_EPSILON: epsilon -> aperp, apar, epsilon
   double alpha;
+  vkrow::Blocks blocks;     // the row sets of base and rows (one, or one per block of a joint fit) and each parameter's set
 };
 
 __device__ __forceinline__ void fit_emit(const FitArgs& a, const vkfit::State& s, int p, int k) {
   const int S = a.q.S;
   for (int slot = 0; slot < S; ++slot) {
     const size_t r = (size_t)k * S + slot;
-    sampled_row(a.base + (size_t)p * VK_NPAR, a.rows + r * VK_NPAR, a.col, a.q.d, a.alpha, [&](int j) { return s.pt[slot][j]; });
+    sampled_row(a.blocks, a.base, (size_t)p, a.rows, r, a.col, a.q.d, a.alpha, [&](int j) { return s.pt[slot][j]; });
     if (a.row_which) a.row_which[r] = a.which[p];
   }
 }

@@ -44,7 +44,7 @@ __global__ void __launch_bounds__(kChainBlock) vk_stretch_propose_kernel(Stretch
   const vkchain::View s = chain_view(a.c, c);
   const size_t M = (size_t)a.M;
   const bool in = vkchain::propose(a.c.box, s, a.c.x + p, a.z[i], a.prop + i, M);
-  sampled_row(a.c.base + (size_t)c * VK_NPAR, a.c.rows + (size_t)i * VK_NPAR, a.c.col, a.c.box.d, a.c.alpha,
+  sampled_row(a.c.blocks, a.c.base, (size_t)c, a.c.rows, (size_t)i, a.c.col, a.c.box.d, a.c.alpha,
               [&](int j) { return in ? a.prop[j * M + i] : s.x[j * s.stride]; });
   if (a.c.row_which) a.c.row_which[i] = a.c.which[c];
 }

@@ -5,8 +5,10 @@
 // through vk_eval_batch_device_async and, in vk_host.h, enqueue_realisations / check_real_lds.  A handle made by
 // vk_fit_create_joint / vk_chain_create_joint runs the same loops over a joint fit of several contexts - block-diagonal or under
 // one covariance handle, against the blocks' data vectors or joint realisation which[i] (that realisation of every block) -
-// through the joint entry points and their enqueue-only twins against realisations (vk_host.h).  The same object serves every
-// flavour of the library.
+// through the joint entry points and their enqueue-only twins against realisations (vk_host.h).  Their _blocks forms keep a row
+// set per block (base rows and pending rows, par_stride() apart) and write each sampled parameter to the block it belongs to, or
+// to all of them (vk_row_select.h); a handle of the other create calls has one row set and makes the launches it always made.
+// The same object serves every flavour of the library.
 //
 // Device code lives in the headers next to this file:
 //   vk_sampled_row.h     a parameter row from a base row and the sampled values
@@ -20,6 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstdio>
 #include <cstring>
 #include <new>
 #include <string>
@@ -41,7 +44,7 @@ using vkh::sync_knobs;
 // ---- the shared core: a set of sampled-parameter problems on a context ---------------------------------------------------------
 constexpr int kSampledMax = 65536;         // problems (chains) of one handle
 constexpr int kSampledMaxP = vkfit::kMaxP;
-static_assert(vkchain::kMaxP == kSampledMaxP, "best fits and chains sample the same columns");
+static_assert(vkchain::kMaxP == kSampledMaxP && vkrow::kMaxP == kSampledMaxP, "best fits and chains sample the same columns");
 
 struct Sampled {
   vk_ctx* ctx = nullptr;                   // of a joint fit: the lead block's (its stream carries the loop)
@@ -51,6 +54,8 @@ struct Sampled {
   vk_eval_opts opts{};
   int P = 0;                               // sampled parameters
   int col[kSampledMaxP] = {};
+  int sets = 1;                            // row sets of d_base and d_rows: 1, or a set per block (the _blocks create calls)
+  int pblock[kSampledMaxP] = {};           // ... and the set each sampled parameter is written to (-1: every set)
   double alpha = 1.0;
   bool real = false;
   int max_which = -1;
@@ -58,6 +63,17 @@ struct Sampled {
   double *d_base = nullptr, *d_rows = nullptr, *d_th = nullptr;   // each problem's base row; the pending rows, their theory vectors
   int *d_which = nullptr, *d_row_which = nullptr;                 // realisation of each problem, of each pending row
   std::string err;
+
+  // doubles between two row sets of d_rows (fixed per handle: a best fit's launches shrink, its sets stay where they are)
+  long long par_stride() const { return sets > 1 ? (long long)rows_max * VK_NPAR : 0; }
+  vkrow::Blocks row_sets(size_t n) const {
+    vkrow::Blocks b{};
+    b.n = sets;
+    b.row_stride = par_stride();
+    b.base_stride = sets > 1 ? (long long)n * VK_NPAR : 0;
+    for (int j = 0; j < vkrow::kMaxP; ++j) b.param_block[j] = pblock[j];
+    return b;
+  }
 
   // doubles of d_th: the theory vectors of rows_max rows; of a joint fit, the workspace of its evaluation of that many rows
   // (whose head is the rows' theory vectors, block by block)
@@ -101,11 +117,13 @@ static void sampled_destroy(H* f) {
 // vk_fit_create / vk_chain_create and their _joint forms (`who`; a problem is a `noun` in its texts).  H is a Sampled with
 // shape(n, lo, hi), which keeps the count, the box and what follows from P, and layout(Carve&) (hidden: no symbol of theirs
 // leaves the library).  joint: ctxs are the n_ctx blocks of a joint fit, lead first, under cov (NULL: block-diagonal); otherwise
-// ctxs is the one context.
+// ctxs is the one context.  param_block (the _blocks forms; NULL otherwise): the block each sampled parameter belongs to, or -1;
+// base_rows then holds a set of n rows per block.
 template <class H>
 static H* sampled_create(const char* who, const char* noun, vk_ctx* const* ctxs, int n_ctx, bool joint, vk_joint_cov* cov,
-                         const vk_eval_opts* opts, int32_t n, int32_t n_params, const int32_t* columns, const double* lo,
-                         const double* hi, const double* base_rows, double alpha, const int32_t* which, char* err, size_t errlen) {
+                         const vk_eval_opts* opts, int32_t n, int32_t n_params, const int32_t* columns, const int32_t* param_block,
+                         const double* lo, const double* hi, const double* base_rows, double alpha, const int32_t* which, char* err,
+                         size_t errlen) {
   auto bail = [&](const std::string& msg) -> H* {
     if (err && errlen) {
       strncpy(err, msg.c_str(), errlen - 1);
@@ -130,20 +148,34 @@ static H* sampled_create(const char* who, const char* noun, vk_ctx* const* ctxs,
   // a joint fit: one device, data vectors, the handle's lead and block sizes; against realisations, the same number of them on
   // every context and the LDS the realisation kernels need
   if (joint && check_joint(cov, ctxs, n_ctx, which != nullptr) != VK_OK) return bail(me + ctx->err);
-  bool used[VK_NPAR] = {};
-  int n_eps = 0;
+  // a column (epsilon: slot VK_NPAR) is named once for all blocks, or once per block it belongs to
+  bool shared[VK_NPAR + 1] = {};
+  uint32_t owned[VK_NPAR + 1] = {};
+  bool eps_twice = false;                  // (without param_block: reported after every parameter's own checks, as it always was)
   for (int j = 0; j < n_params; ++j) {
-    const int c = columns[j];
-    if (c == VK_WALK_EPSILON) {
-      ++n_eps;
-    } else if (c < 0 || c >= VK_NPAR || (c >= VK_P_APERP && c <= VK_P_EPSILON) || used[c]) {
+    const int c = columns[j], b = param_block ? param_block[j] : -1;
+    if (c != VK_WALK_EPSILON && (c < 0 || c >= VK_NPAR || (c >= VK_P_APERP && c <= VK_P_EPSILON)))
       return bail(me + "a sampled parameter must name a row column other than aperp / apar / epsilon, or VK_WALK_EPSILON, once");
-    } else {
-      used[c] = true;
+    if (b < -1 || b >= n_ctx)
+      return bail(me + "param_block " + std::to_string(b) + " of parameter " + std::to_string(j) + " is outside -1.." +
+                  std::to_string(n_ctx - 1));
+    const int k = c == VK_WALK_EPSILON ? VK_NPAR : c;
+    if (b < 0 ? owned[k] != 0 : shared[k])
+      return bail(me + "parameter " + std::to_string(j) + ": a column is sampled for all blocks or per block, not both");
+    if (b < 0 ? shared[k] : (owned[k] >> b & 1u) != 0) {
+      if (param_block) return bail(me + "parameter " + std::to_string(j) + " names a (column, block) pair a second time");
+      if (c != VK_WALK_EPSILON)
+        return bail(me + "a sampled parameter must name a row column other than aperp / apar / epsilon, or VK_WALK_EPSILON, once");
+      eps_twice = true;
     }
+    if (b < 0) shared[k] = true;
+    else owned[k] |= 1u << b;
+    if (b >= 0 && c == VK_P_BETA && vkh::joint_cov_n_beta(cov) > 0)
+      return bail(me + "beta cannot be sampled per block under a covariance gridded in beta (the joint chi-square brackets the "
+                       "covariance with one beta per point)");
     if (!(hi[j] > lo[j])) return bail(me + "the prior box needs lo < hi");
   }
-  if (n_eps > 1) return bail(me + "epsilon sampled twice");
+  if (eps_twice) return bail(me + "epsilon sampled twice");
   int max_which = -1;
   if (which)
     for (int i = 0; i < n; ++i) {
@@ -159,7 +191,12 @@ static H* sampled_create(const char* who, const char* noun, vk_ctx* const* ctxs,
   f->cov = cov;
   f->opts = *opts;
   f->P = n_params;
-  for (int j = 0; j < n_params; ++j) f->col[j] = columns[j];
+  for (int j = 0; j < kSampledMaxP; ++j) f->pblock[j] = -1;
+  for (int j = 0; j < n_params; ++j) {
+    f->col[j] = columns[j];
+    if (param_block) f->pblock[j] = param_block[j];
+  }
+  f->sets = param_block ? n_ctx : 1;
   f->alpha = alpha;
   f->real = which != nullptr;
   f->max_which = max_which;
@@ -173,7 +210,7 @@ static H* sampled_create(const char* who, const char* noun, vk_ctx* const* ctxs,
   }
   Carve mem{static_cast<char*>(f->d_mem)};
   f->layout(mem);
-  bool ok = hipMemcpy(f->d_base, base_rows, (size_t)n * VK_NPAR * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+  bool ok = hipMemcpy(f->d_base, base_rows, (size_t)f->sets * n * VK_NPAR * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
   if (ok && which) ok = hipMemcpy(f->d_which, which, (size_t)n * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
   if (!ok) {
     (void)hipGetLastError();
@@ -230,14 +267,15 @@ static int sampled_evaluate(Sampled* f, long long m, double* d_lnl, double* d_ch
     // finished results, and overwrites the rows only once no block reads them any more.
     vk_ctx* const* cs = f->blocks.data();
     const int nb = (int)f->blocks.size();
+    const long long ps = f->par_stride();  // block q's rows: d_rows + q * ps (0: one row set)
     if (!f->real)
-      rc = f->cov ? vk_joint_cov_eval_device_async(f->cov, cs, nb, &f->opts, f->d_rows, m, d_lnl, d_chi, f->d_th)
-                  : vk_joint_eval_device_async(cs, nb, &f->opts, f->d_rows, m, d_lnl, d_chi, f->d_th);
+      rc = f->cov ? vk_joint_cov_eval_blocks_device_async(f->cov, cs, nb, &f->opts, f->d_rows, ps, m, d_lnl, d_chi, f->d_th)
+                  : vk_joint_eval_blocks_device_async(cs, nb, &f->opts, f->d_rows, ps, m, d_lnl, d_chi, f->d_th);
     else if (f->cov)
-      rc = vkh::enqueue_joint_cov_realisations(f->cov, cs, nb, &f->opts, f->d_rows, m, f->d_row_which, d_lnl, d_chi,
+      rc = vkh::enqueue_joint_cov_realisations(f->cov, cs, nb, &f->opts, f->d_rows, ps, m, f->d_row_which, d_lnl, d_chi,
                                                vkh::joint_real_carve(f->cov, f->d_th, (long long)f->rows_max));
     else
-      rc = vkh::enqueue_joint_sum_realisations(cs, nb, &f->opts, f->d_rows, m, f->d_row_which, d_lnl, d_chi, f->d_th);
+      rc = vkh::enqueue_joint_sum_realisations(cs, nb, &f->opts, f->d_rows, ps, m, f->d_row_which, d_lnl, d_chi, f->d_th);
   }
   if (rc) f->err = f->ctx->err;
   return rc;
@@ -285,9 +323,9 @@ struct __attribute__((visibility("hidden"))) vk_fit : Sampled {
   void layout(Carve& c) {
     const size_t n = R, rows = n * S;
     c.take(d_state, n);
-    c.take(d_base, n * VK_NPAR);
+    c.take(d_base, sets * n * VK_NPAR);
     c.take(d_x0, n * P);
-    c.take(d_rows, rows * VK_NPAR);
+    c.take(d_rows, sets * rows * VK_NPAR);
     c.take(d_lnl, rows);
     c.take(d_chi, rows);
     c.take(d_th, workspace_doubles());
@@ -322,6 +360,7 @@ static int fit_loop(vk_fit* f, const vkfit::Params& q, const double* x0, std::ve
   a.status = f->d_status;
   for (int j = 0; j < vkfit::kMaxP; ++j) a.col[j] = f->col[j];
   a.alpha = f->alpha;
+  a.blocks = f->row_sets((size_t)R);
   int rc = sampled_launch(f, vk_fit_init_kernel, R, kFitBlock, a);
   while (rc == VK_OK) {
     for (int t = 0; t < kFitCheck && rc == VK_OK; ++t) {
@@ -353,15 +392,27 @@ extern "C" {
 vk_fit* vk_fit_create(vk_ctx* ctx, const vk_eval_opts* opts, int32_t n_problems, int32_t n_params, const int32_t* columns,
                       const double* lo, const double* hi, const double* base_rows, double alpha, const int32_t* which, char* err,
                       size_t errlen) {
-  return sampled_create<vk_fit>("vk_fit_create", "problem", &ctx, 1, false, nullptr, opts, n_problems, n_params, columns, lo, hi,
-                                base_rows, alpha, which, err, errlen);
+  return sampled_create<vk_fit>("vk_fit_create", "problem", &ctx, 1, false, nullptr, opts, n_problems, n_params, columns, nullptr,
+                                lo, hi, base_rows, alpha, which, err, errlen);
 }
 
 vk_fit* vk_fit_create_joint(vk_ctx* const* ctxs, int32_t n_ctx, vk_joint_cov* cov, const vk_eval_opts* opts, int32_t n_problems,
                             int32_t n_params, const int32_t* columns, const double* lo, const double* hi, const double* base_rows,
                             double alpha, const int32_t* which, char* err, size_t errlen) {
-  return sampled_create<vk_fit>("vk_fit_create_joint", "problem", ctxs, n_ctx, true, cov, opts, n_problems, n_params, columns, lo,
-                                hi, base_rows, alpha, which, err, errlen);
+  return sampled_create<vk_fit>("vk_fit_create_joint", "problem", ctxs, n_ctx, true, cov, opts, n_problems, n_params, columns,
+                                nullptr, lo, hi, base_rows, alpha, which, err, errlen);
+}
+
+vk_fit* vk_fit_create_joint_blocks(vk_ctx* const* ctxs, int32_t n_ctx, vk_joint_cov* cov, const vk_eval_opts* opts,
+                                   int32_t n_problems, int32_t n_params, const int32_t* columns, const int32_t* param_block,
+                                   const double* lo, const double* hi, const double* base_rows, double alpha, const int32_t* which,
+                                   char* err, size_t errlen) {
+  if (!param_block) {
+    if (err && errlen) snprintf(err, errlen, "vk_fit_create_joint_blocks: NULL argument");
+    return nullptr;
+  }
+  return sampled_create<vk_fit>("vk_fit_create_joint_blocks", "problem", ctxs, n_ctx, true, cov, opts, n_problems, n_params, columns,
+                                param_block, lo, hi, base_rows, alpha, which, err, errlen);
 }
 
 const char* vk_fit_last_error(const vk_fit* f) { return f ? f->err.c_str() : ""; }
@@ -460,9 +511,9 @@ struct __attribute__((visibility("hidden"))) vk_chain : Sampled {
     c.take(d_pivot, n * P);
     c.take(d_sum1, n * P);
     c.take(d_sum2, n * T);
-    c.take(d_base, n * VK_NPAR);
+    c.take(d_base, sets * n * VK_NPAR);
     c.take(d_x0, n * P);
-    c.take(d_rows, n * VK_NPAR);
+    c.take(d_rows, sets * n * VK_NPAR);
     c.take(d_res_lnl, n);
     c.take(d_res_chi, n);
     c.take(d_th, workspace_doubles());
@@ -501,6 +552,7 @@ static ChainArgs chain_args(const vk_chain* f) {
   a.row_which = f->real ? f->d_row_which : nullptr;
   for (int j = 0; j < vkchain::kMaxP; ++j) a.col[j] = f->col[j];
   a.alpha = f->alpha;
+  a.blocks = f->row_sets((size_t)f->C);
   return a;
 }
 
@@ -509,15 +561,27 @@ extern "C" {
 vk_chain* vk_chain_create(vk_ctx* ctx, const vk_eval_opts* opts, int32_t n_chains, int32_t n_params, const int32_t* columns,
                           const double* lo, const double* hi, const double* base_rows, double alpha, const int32_t* which, char* err,
                           size_t errlen) {
-  return sampled_create<vk_chain>("vk_chain_create", "chain", &ctx, 1, false, nullptr, opts, n_chains, n_params, columns, lo, hi,
-                                  base_rows, alpha, which, err, errlen);
+  return sampled_create<vk_chain>("vk_chain_create", "chain", &ctx, 1, false, nullptr, opts, n_chains, n_params, columns, nullptr,
+                                  lo, hi, base_rows, alpha, which, err, errlen);
 }
 
 vk_chain* vk_chain_create_joint(vk_ctx* const* ctxs, int32_t n_ctx, vk_joint_cov* cov, const vk_eval_opts* opts, int32_t n_chains,
                                 int32_t n_params, const int32_t* columns, const double* lo, const double* hi, const double* base_rows,
                                 double alpha, const int32_t* which, char* err, size_t errlen) {
-  return sampled_create<vk_chain>("vk_chain_create_joint", "chain", ctxs, n_ctx, true, cov, opts, n_chains, n_params, columns, lo,
-                                  hi, base_rows, alpha, which, err, errlen);
+  return sampled_create<vk_chain>("vk_chain_create_joint", "chain", ctxs, n_ctx, true, cov, opts, n_chains, n_params, columns,
+                                  nullptr, lo, hi, base_rows, alpha, which, err, errlen);
+}
+
+vk_chain* vk_chain_create_joint_blocks(vk_ctx* const* ctxs, int32_t n_ctx, vk_joint_cov* cov, const vk_eval_opts* opts,
+                                       int32_t n_chains, int32_t n_params, const int32_t* columns, const int32_t* param_block,
+                                       const double* lo, const double* hi, const double* base_rows, double alpha,
+                                       const int32_t* which, char* err, size_t errlen) {
+  if (!param_block) {
+    if (err && errlen) snprintf(err, errlen, "vk_chain_create_joint_blocks: NULL argument");
+    return nullptr;
+  }
+  return sampled_create<vk_chain>("vk_chain_create_joint_blocks", "chain", ctxs, n_ctx, true, cov, opts, n_chains, n_params, columns,
+                                  param_block, lo, hi, base_rows, alpha, which, err, errlen);
 }
 
 const char* vk_chain_last_error(const vk_chain* f) { return f ? f->err.c_str() : ""; }

@@ -1,5 +1,6 @@
 """Best-fit points on the GPU: ``CCFFit.best_fit`` and ``Realisations.best_fit``; of a joint fit, ``JointFit.best_fit`` and
-``JointRealisations.best_fit`` (one parameter row for all blocks; ``vk_fit_create_joint``).
+``JointRealisations.best_fit`` (one parameter row for all blocks, ``vk_fit_create_joint``; with ``"name@q"`` parameters a row per
+block, ``vk_fit_create_joint_blocks``: :mod:`victor_amd.joint`).
 
 The reference has no optimiser; its users maximise ``CCFFit.log_likelihood`` (reference: ``ccf_fit.py:356-483``) with a host
 optimiser, one call per point and one data vector at a time.  Here every *problem* - one maximisation of lnL over the sampled
@@ -73,13 +74,32 @@ class _Sampled:
         self.lo = np.array([s.lo for s in self.specs])
         self.hi = np.array([s.hi for s in self.specs])
 
-    def check_columns(self):
+    def check_columns(self, fit=None):
+        """Every sampled name has a row column of its own (or is epsilon); ``"name@q"`` addresses block q of a joint ``fit``
+        and is refused, sampled or fixed, on anything else."""
+        from .joint import JointFit, split_name
+        joint = fit if isinstance(fit, JointFit) else None
+        every = list(self.names) + list(self.fixed_all)
+        if joint is not None:
+            joint._check_block_names(every, self.who)
+            # a plain sampled name means "every block without an entry of its own"; the device writes a sampled value to one
+            # block or to all of them, so beside an @ entry of the same name it is refused
+            own = {split_name(n)[0] for n in every if split_name(n)[1] is not None}
+            mixed = sorted(n for n in self.names if n in own)
+            if mixed:
+                raise InputError(f"{self.who}: {mixed} cannot be {self.verb} for all blocks beside per-block entries of the same name "
+                                 f"({sorted(n for n in every if split_name(n)[1] is not None and split_name(n)[0] in mixed)}): "
+                                 "fix the plain name, or give every block an entry of its own (per_block)")
+        elif any(split_name(n)[1] is not None for n in every):
+            raise InputError(f"{self.who}: per-block parameters ('name@block': {sorted(n for n in every if '@' in n)}) need a "
+                             "JointFit")
         for name in self.names:
-            if name not in N.ROW_COLUMNS and name != "epsilon":
+            base = split_name(name)[0]
+            if base not in N.ROW_COLUMNS and base != "epsilon":
                 raise InputError(f"{self.who}: {name} has no column of its own in a parameter row and cannot be {self.verb}")
 
     def check_alpha(self):
-        if "epsilon" in self.names and np.ndim(self.fixed_all.get("alpha", 1)) > 0:
+        if any(n.partition("@")[0] == "epsilon" for n in self.names) and np.ndim(self.fixed_all.get("alpha", 1)) > 0:
             raise InputError(f"{self.who}: alpha must be a scalar when epsilon is {self.verb}")
 
     def fit_options(self, fit, kwargs):
@@ -161,7 +181,7 @@ def best_fit(fit, params, fixed=None, start=None, step=None, xtol=None, ftol=1e-
     kwargs = kwargs or {}
     q = _Sampled("best_fit", "fitted", params, fixed)
     names, fixed_all, d = q.names, q.fixed_all, len(q.names)
-    q.check_columns()
+    q.check_columns(fit)
     arrays = {k: v for k, v in fixed_all.items() if np.ndim(v) > 0}
     if realisations is not None:
         if arrays:

@@ -10,6 +10,12 @@ blocks' data vectors in block order - as the reference's ``CCFFit`` would fit th
 analysis share their galaxies and voids, so their data vectors are correlated.  The blocks' theory vectors come from their
 own theory launches; the joint chi-square is one kernel (``vk_joint_cov_eval_device_async``, ``vk_kernel_joint.h``).
 
+Per-block parameters: a name ``"<name>@<q>"`` addresses block ``q`` (0-based, the order of ``fits``), a plain ``"<name>"`` every
+block without an ``@`` entry of its own - the quantiles of a density split share fsigma8, beta and epsilon, each has its own
+velocity dispersion (and bias / ``Av``).  Block q's rows are ``fits[q]._fit_rows`` of the dictionary resolved for it
+(:func:`block_params`); the device entry points are the ``_blocks`` forms of ``include/victor_hip.h``.  Without an ``@`` key every
+call is the call it was.  :func:`per_block` writes the ``@`` entries of a cobaya ``params`` block.
+
 ``JointFit.realisations()`` validates the joint fit on mocks: joint realisation m is realisation m of every block's own stacked
 file (``redshift_space_ccf.simulation_number``, reference ``ccf_fit.py:59-61,93-100``), and every parameter point is evaluated
 against all of them in one call (:class:`JointRealisations`).
@@ -27,6 +33,71 @@ from .realisations import Realisations, check_which
 from .utils import InputError
 
 
+def split_name(name):
+    """``("sigma_v", 2)`` of ``"sigma_v@2"``, ``(name, None)`` of a plain name; ``InputError`` for a suffix that is no
+    non-negative integer."""
+    base, at, suffix = str(name).partition("@")
+    if not at:
+        return name, None
+    if not base or not suffix.isdigit():
+        raise InputError(f"{name}: a per-block parameter is named '<name>@<block>' with the block's number (0, 1, ...)")
+    return base, int(suffix)
+
+
+def has_block_names(params):
+    """Does the dictionary address a block of its own anywhere (an ``@`` key)?"""
+    return isinstance(params, dict) and any("@" in str(k) for k in params)
+
+
+def check_block_names(names, n_blocks, beta_gridded=False, who="JointFit"):
+    """The refusals of per-block names: a block outside ``0 .. n_blocks - 1``, ``alpha@q`` (alpha stays one scalar) and, under
+    a joint covariance gridded in beta, ``beta@q`` (the joint chi-square brackets the covariance with ONE beta per point)."""
+    for name in names:
+        base, q = split_name(name)
+        if q is None:
+            continue
+        if q >= n_blocks:
+            raise InputError(f"{who}: {name} names block {q} of {n_blocks} (0..{n_blocks - 1})")
+        if base == "alpha":
+            raise InputError(f"{who}: {name}: alpha is one scalar for all blocks")
+        if base == "beta" and beta_gridded:
+            raise InputError(f"{who}: {name}: under a joint covariance gridded in beta every block shares one beta (the joint "
+                             "chi-square brackets the covariance with one beta per point)")
+
+
+def block_params(params, q):
+    """The dictionary block ``q`` reads: ``params["name@q"]`` where present, else ``params["name"]``; other blocks' entries
+    dropped."""
+    out = {k: v for k, v in params.items() if "@" not in str(k)}
+    for k, v in params.items():
+        base, b = split_name(k)
+        if b == q:
+            out[base] = v
+    return out
+
+
+def per_block(params, names, n_blocks):
+    """A copy of the cobaya ``params`` block in which every entry listed in ``names`` is replaced by its ``n_blocks`` copies
+    ``"<name>@0" .. "<name>@<n_blocks - 1>"`` (the same prior, ref and proposal, at the entry's place in the block):
+    ``joint.realisations().best_fit(per_block(params, ["sigma_v"], 5))`` fits a velocity dispersion of each quantile's own."""
+    import copy
+    names = [names] if isinstance(names, str) else list(names)
+    missing = [n for n in names if n not in params]
+    if missing:
+        raise InputError(f"per_block: {missing} are not in the params block")
+    if int(n_blocks) < 1:
+        raise InputError("per_block: need at least one block")
+    check_block_names([f"{n}@0" for n in names], int(n_blocks), who="per_block")
+    out = {}
+    for key, spec in params.items():
+        if key in names:
+            for q in range(int(n_blocks)):
+                out[f"{key}@{q}"] = copy.deepcopy(spec)
+        else:
+            out[key] = spec
+    return out
+
+
 class JointFit:
     def __init__(self, fits, covariance=None, likelihood=None):
         """``covariance``: ``None`` - block-diagonal, each block under its own covariance (chi-square and lnL add); a
@@ -38,6 +109,7 @@ class JointFit:
         if not self.fits:
             raise ValueError("need at least one fit")
         self._buffers = None
+        self._block_buffers = None
         self.covariance = None
         self._handles = {}
         if covariance is None:
@@ -193,13 +265,25 @@ class JointFit:
             lead, h = handles.popitem()[1]
             lead._lib.vk_joint_cov_destroy(h)
 
+    def _release_buffers(self):
+        """Free the device buffers of the evaluation calls (the shared calls' and the per-block calls')."""
+        for attr in ("_buffers", "_block_buffers"):
+            b = getattr(self, attr, None)
+            setattr(self, attr, None)
+            if b is not None:
+                for ptr in b["ptrs"]:
+                    b["lead"].free(ptr)
+
     def __del__(self):
-        try:
-            self._release_handle()
-        except Exception:
-            pass
+        for release in (self._release_handle, self._release_buffers):
+            try:
+                release()
+            except Exception:
+                pass
 
     def _log_likelihood_cov(self, params, kwargs):
+        if has_block_names(params):
+            return self._log_likelihood_blocks(params, kwargs)
         engines, opts = self._plan_cov(kwargs)
         fit = self.fits[0]
         rows = fit._fit_rows(params, fit._merged({k: v for k, v in kwargs.items() if k != "likelihood"}))
@@ -223,6 +307,62 @@ class JointFit:
         d_chi = C.c_void_p(d_out + 8 * n)
         lead._check(lead._lib.vk_joint_cov_eval_device_async(handle, ctxs, len(engines), C.byref(opts), d_rows, n, d_out,
                                                              d_chi, d_ws))
+        out = lead.download(d_out, 2 * n)
+        return out[:n].copy(), out[n:].copy()
+
+    # ------------------------------------------------------------------ per-block parameters ("name@q")
+    def _check_block_names(self, names, who="JointFit"):
+        check_block_names(names, len(self.fits), self.covariance is not None and not self.fixed_covmat, who)
+
+    def _block_rows(self, params, kwargs):
+        """``(B, n, VK_NPAR)`` rows, block q's formed by ``fits[q]._fit_rows`` from the dictionary resolved for it."""
+        self._check_block_names(params)
+        kw = {k: v for k, v in kwargs.items() if k != "likelihood"} if self.covariance is not None else kwargs
+        rows = [np.asarray(f._fit_rows(block_params(params, q), f._merged(kw))) for q, f in enumerate(self.fits)]
+        n = max(len(r) for r in rows)
+        if any(len(r) not in (1, n) for r in rows):
+            raise InputError(f"parameter arrays have different lengths: {sorted({len(r) for r in rows})}")
+        return np.ascontiguousarray([np.broadcast_to(r, (n, N.VK_NPAR)) for r in rows], dtype=np.float64)
+
+    def _log_likelihood_blocks(self, params, kwargs):
+        """:meth:`log_likelihood_batch` with ``@`` names: a row set per block through ``vk_joint_cov_eval_blocks_device_async`` /
+        ``vk_joint_eval_blocks_device_async``; blocks that cannot share one launch, one call per block and the host's sum."""
+        self._check_block_names(params)
+        if self.covariance is not None:
+            engines, opts = self._plan_cov(kwargs)
+        else:
+            plan = self._plan(kwargs)
+            if plan is None:
+                return self._sequential(params, kwargs)
+            engines, opts = plan
+        rows = self._block_rows(params, kwargs)
+        B, n = rows.shape[:2]
+        if n == 0:
+            return np.empty(0), np.empty(0)
+        lead = engines[0]
+        ctxs = (C.c_void_p * B)(*[e._ctx for e in engines])
+        if self.covariance is not None:
+            handle = self._joint_handle(lead)
+            need = lead._lib.vk_joint_cov_workspace_doubles(handle, n)
+        else:
+            need = lead._lib.vk_joint_workspace_doubles(ctxs, B, n)
+        b = self._block_buffers                                 # (its own buffers: the shared calls keep theirs as they were)
+        if b is None or b["lead"] is not lead or b["n"] < n or b["ws"] < need:
+            if b is not None:
+                for ptr in b["ptrs"]:
+                    b["lead"].free(ptr)
+            self._block_buffers = None
+            b = self._block_buffers = {"lead": lead, "n": n, "ws": need,
+                                       "ptrs": [lead.alloc(B * n * N.VK_NPAR), lead.alloc(2 * n), lead.alloc(need)]}
+        d_rows, d_out, d_ws = b["ptrs"]
+        lead.upload(d_rows, rows)
+        d_chi = C.c_void_p(d_out + 8 * n)
+        if self.covariance is not None:
+            rc = lead._lib.vk_joint_cov_eval_blocks_device_async(handle, ctxs, B, C.byref(opts), d_rows, n * N.VK_NPAR, n, d_out,
+                                                                 d_chi, d_ws)
+        else:
+            rc = lead._lib.vk_joint_eval_blocks_device_async(ctxs, B, C.byref(opts), d_rows, n * N.VK_NPAR, n, d_out, d_chi, d_ws)
+        lead._check(rc)
         out = lead.download(d_out, 2 * n)
         return out[:n].copy(), out[n:].copy()
 
@@ -273,6 +413,8 @@ class JointFit:
         the chi-square of the joint vector and its likelihood form (``vk_joint_cov_eval_device_async``)."""
         if self.covariance is not None:
             return self._log_likelihood_cov(params, kwargs)
+        if has_block_names(params):
+            return self._log_likelihood_blocks(params, kwargs)
         plan = self._plan(kwargs)
         if plan is None:
             return self._sequential(params, kwargs)
@@ -293,8 +435,11 @@ class JointFit:
     def _sequential(self, params, kwargs):
         """Blocks with different options: one call per block, sums on the host."""
         lnl = chi2 = None
-        for fit in self.fits:
-            a, b = fit.log_likelihood_batch(params, **kwargs)
+        blocks = has_block_names(params)
+        if blocks:
+            self._check_block_names(params)
+        for q, fit in enumerate(self.fits):
+            a, b = fit.log_likelihood_batch(block_params(params, q) if blocks else params, **kwargs)
             lnl = a if lnl is None else lnl + a
             chi2 = b if chi2 is None else chi2 + b
         bad = ~np.isfinite(lnl)
@@ -307,7 +452,8 @@ class JointFit:
 
     # ------------------------------------------------------------------ best fits and chains (fitting.py, chains.py)
     def _sampled_create(self, entry, q, realisations, kwargs, batch, which):
-        """``(lib, handle, refresh)`` of ``vk_fit_create_joint`` / ``vk_chain_create_joint`` (``entry``) for the sampled
+        """``(lib, handle, refresh)`` of ``vk_fit_create_joint`` / ``vk_chain_create_joint`` (``entry``; with ``@`` names among the
+        sampled or fixed parameters their ``_blocks`` forms, a row per block) for the sampled
         parameters ``q`` (the contract of ``fitting._Sampled.create``): one problem per row of ``batch``, against the joint data
         vector or joint realisation ``which[i]`` of ``realisations``.  The rows are the lead fit's, as
         :meth:`log_likelihood_batch` forms them."""
@@ -322,9 +468,22 @@ class JointFit:
                 raise InputError(f"{q.who}: the blocks of a block-diagonal joint fit must share one option block (their model, "
                                  "fit options and their data's beta dependence) and one device")
             engines, opts = plan
-        fit = self.fits[0]
-        rows = np.ascontiguousarray(fit._fit_rows(batch, fit._merged(kwargs)), dtype=np.float64)
-        cols = np.array([N.ROW_COLUMNS.get(n, N.VK_WALK_EPSILON) for n in q.names], dtype=np.int32)
+        blocks = has_block_names(batch)
+        extra = ()
+        if blocks:
+            # a row set per block: block b's base rows from the values resolved for it, each sampled value to its own block
+            rows = self._block_rows(batch, kwargs).reshape(-1, N.VK_NPAR)
+            split = [split_name(n) for n in q.names]
+            cols = np.array([N.ROW_COLUMNS.get(base, N.VK_WALK_EPSILON) for base, _ in split], dtype=np.int32)
+            param_block = np.array([-1 if b is None else b for _, b in split], dtype=np.int32)
+            extra = (param_block.ctypes.data_as(C.POINTER(C.c_int32)),)
+            entry += "_blocks"
+            n_rows = len(rows) // len(self.fits)
+        else:
+            fit = self.fits[0]
+            rows = np.ascontiguousarray(fit._fit_rows(batch, fit._merged(kwargs)), dtype=np.float64)
+            cols = np.array([N.ROW_COLUMNS.get(n, N.VK_WALK_EPSILON) for n in q.names], dtype=np.int32)
+            n_rows = len(rows)
         refresh = None
         if realisations is not None:
             def refresh(realisations=realisations, engines=list(engines)):
@@ -335,8 +494,8 @@ class JointFit:
         ctxs = (C.c_void_p * len(engines))(*[e._ctx for e in engines])
         i32 = C.POINTER(C.c_int32)
         err = C.create_string_buffer(512)
-        h = getattr(lead._lib, entry)(ctxs, len(engines), handle, C.byref(opts), len(rows), len(cols), cols.ctypes.data_as(i32),
-                                      N.as_dp(N.f64(q.lo)), N.as_dp(N.f64(q.hi)), N.as_dp(rows),
+        h = getattr(lead._lib, entry)(ctxs, len(engines), handle, C.byref(opts), n_rows, len(cols), cols.ctypes.data_as(i32),
+                                      *extra, N.as_dp(N.f64(q.lo)), N.as_dp(N.f64(q.hi)), N.as_dp(rows),
                                       float(q.fixed_all.get("alpha", 1)),
                                       None if realisations is None else which.ctypes.data_as(i32), err, len(err))
         if not h:
@@ -346,7 +505,8 @@ class JointFit:
 
     def best_fit(self, params, fixed=None, start=None, step=None, xtol=None, ftol=1e-6, max_iter=None, restarts=1, **kwargs):
         """Maximum of the joint lnL (the value :meth:`log_likelihood_batch` returns) over the sampled parameters of a cobaya
-        ``params`` block - one parameter vector for all blocks - by the bounded Nelder-Mead search of ``CCFFit.best_fit`` on
+        ``params`` block - one parameter vector for all blocks, or with ``"name@q"`` entries (:func:`per_block`) a value of
+        that parameter per block, at most 10 sampled values in all - by the bounded Nelder-Mead search of ``CCFFit.best_fit`` on
         the GPU, block-diagonal or under the joint covariance.  Arguments and result as ``CCFFit.best_fit``: arrays in
         ``fixed`` give a profile."""
         from .fitting import best_fit
@@ -418,14 +578,27 @@ class JointRealisations:
 
     def _eval(self, params, kwargs, which=None):
         joint = self.joint
+        blocks = has_block_names(params)
+        if blocks:
+            joint._check_block_names(params)
         if joint.covariance is None:
             return self._block_diagonal(params, kwargs, which)
-        fit = joint.fits[0]
-        rows = fit._fit_rows(params, fit._merged({k: v for k, v in kwargs.items() if k != "likelihood"}))
-        rows, which = check_which(rows, which, len(self))
-        rows = N.f64(rows).reshape(-1, N.VK_NPAR)
+        entry = "vk_joint_cov_eval_realisations"
+        if blocks:
+            # a row set per block, [B][n][VK_NPAR]: each block's theory launch reads its own slice of every chunk
+            sets = joint._block_rows(params, kwargs)
+            checked = [check_which(r, which, len(self)) for r in sets]
+            which = checked[0][1]
+            rows = np.ascontiguousarray([r for r, _ in checked], dtype=np.float64)
+            n = rows.shape[1]
+            entry += "_blocks"
+        else:
+            fit = joint.fits[0]
+            rows = fit._fit_rows(params, fit._merged({k: v for k, v in kwargs.items() if k != "likelihood"}))
+            rows, which = check_which(rows, which, len(self))
+            rows = N.f64(rows).reshape(-1, N.VK_NPAR)
+            n = len(rows)
         engines, opts = joint._plan_cov(kwargs)
-        n = len(rows)
         shape = (n,) if which is not None else (n, len(self))
         lnl, chi2 = np.empty(shape), np.empty(shape)
         if n == 0:
@@ -439,16 +612,17 @@ class JointRealisations:
         if which is not None:
             which = np.ascontiguousarray(which, dtype=np.int32)
             w = which.ctypes.data_as(C.POINTER(C.c_int32))
-        lead._check(lead._lib.vk_joint_cov_eval_realisations(handle, ctxs, len(engines), C.byref(opts), N.as_dp(rows), n, w,
-                                                             N.as_dp(lnl), N.as_dp(chi2)))
+        lead._check(getattr(lead._lib, entry)(handle, ctxs, len(engines), C.byref(opts), N.as_dp(rows), n, w, N.as_dp(lnl),
+                                              N.as_dp(chi2)))
         return lnl, chi2
 
     def _block_diagonal(self, params, kwargs, which):
         """Each block's realisations under its own covariance, summed in block order; a failed block fails the entry (as
         ``JointFit._sequential``)."""
         lnl = chi2 = None
-        for r in self.blocks:
-            a, b = r._eval(params, kwargs, which)
+        blocks = has_block_names(params)
+        for q, r in enumerate(self.blocks):
+            a, b = r._eval(block_params(params, q) if blocks else params, kwargs, which)
             lnl = a if lnl is None else lnl + a
             chi2 = b if chi2 is None else chi2 + b
         bad = ~np.isfinite(lnl)
