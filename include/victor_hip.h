@@ -498,6 +498,31 @@ int vk_chain_begin_stretch(vk_chain* f, int32_t n_steps, int32_t walkers, const 
                            const int32_t* partner, int64_t first_step, int64_t burn, int64_t thin, int32_t want_history,
                            int32_t* n_kept);
 
+/* ---- A Gaussian prior on the sampled parameters of a best-fit or chain handle ------------------------------------------------
+ * The handles above know the uniform box.  vk_fit_set_prior / vk_chain_set_prior multiply a Gaussian onto it, on any handle of
+ * the create calls (single fit, joint, joint with a row set per block): ln prior = -1/2 (x - mu)^T P (x - mu), no normalisation
+ * constant (a constant changes no decision and no maximum).  The device evaluates it, because the accept / reject decision and
+ * the Nelder-Mead comparison run on the device between launches.
+ *   mu         [n_params] the mean, in the order of the handle's sampled parameters (0 for a parameter without a prior)
+ *   pp_packed  [n_params (n_params + 1) / 2] the upper triangle of the precision matrix P of the sampled parameters (zero rows
+ *              for parameters without a prior), row by row - (j, k), j <= k, at j n - j (j - 1) / 2 + (k - j) - with every
+ *              OFF-DIAGONAL entry doubled.  The arithmetic order is fixed (vk_prior.h): q = sum over j, then k >= j, of
+ *              (pp[jk] * (x_j - mu_j)) * (x_k - mu_k), each product and each sum rounded (no fused multiply-add);
+ *              ln prior = -0.5 q.
+ * Both copy their inputs; NULL, NULL clears the prior, and a handle without one takes the code path, makes the launches and
+ * returns the bytes it always did.  The prior holds for every later vk_fit_run / block of vk_chain_begin or
+ * vk_chain_begin_stretch.
+ *   best fits  the search maximises lnL + ln prior: the value of a live row is lnL + ln prior at its point.  vk_fit_run then
+ *              returns that sum in `lnl`; chi2 stays the chi-square of the row.
+ *   Metropolis accept when logu < (lnL' + lp') - (lnL + lp): lp' the prior at the proposal, lp recomputed at the current position.
+ *   stretch    accept when logu < (lz + (lnL' + lp')) - (lnL + lp): lp' the prior at the stored proposal.
+ *              Outside the box lnL' = -inf as before, and -inf plus a finite lp' is -inf; a NaN lnL' rejects.  The chains' state
+ *              and history keep the log-LIKELIHOOD.
+ * Refused (VK_E_ARG, the handle's last_error gives the text): one of the two NULL, a value that is not finite, and
+ * vk_chain_set_prior while a block begun with vk_chain_begin / vk_chain_begin_stretch awaits vk_chain_finish. */
+int vk_fit_set_prior(vk_fit* f, const double* mu, const double* pp_packed);
+int vk_chain_set_prior(vk_chain* f, const double* mu, const double* pp_packed);
+
 /* Theory multipoles on a caller-supplied s grid: out[n][n_ell][n_s] with the caller's own
  * projection weights w_ell[n_ell][n_mu] on mu[n_mu] (host buffers). */
 int vk_theory_batch(vk_ctx* ctx, const vk_eval_opts* opts, const double* params, int64_t n,

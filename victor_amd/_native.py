@@ -179,6 +179,9 @@ SYMBOLS = {
     "vk_chain_create_joint_blocks": (_vp, [C.POINTER(C.c_void_p), C.c_int32, _vp, _optp, C.c_int32, C.c_int32,
                                            C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp, _dp, _dp, C.c_double,
                                            C.POINTER(C.c_int32), C.c_char_p, C.c_size_t]),
+    # a Gaussian prior on the sampled parameters of a best-fit or chain handle
+    "vk_fit_set_prior": (C.c_int, [_vp, _dp, _dp]),
+    "vk_chain_set_prior": (C.c_int, [_vp, _dp, _dp]),
     "vk_serve_mailboxes": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, _optp, _vp, C.c_int32, _vp, C.c_double, C.c_int32,
                            C.c_double, C.POINTER(vk_serve_stats)]),
     "vk_timing_enable": (C.c_int, [_vp, C.c_int]),

@@ -321,7 +321,8 @@ class CCFFit(CCFModel):
         lnl, chi2, _ = self._run(params, kwargs)
         return lnl, chi2
 
-    def best_fit(self, params, fixed=None, start=None, step=None, xtol=None, ftol=1e-6, max_iter=None, restarts=1, **kwargs):
+    def best_fit(self, params, fixed=None, start=None, step=None, xtol=None, ftol=1e-6, max_iter=None, restarts=1, prior=None,
+                 **kwargs):
         """Maximum of lnL (the value :meth:`log_likelihood` returns: with uniform priors the MAP point) over the sampled
         parameters of a cobaya ``params`` block, inside their prior box, by a bounded Nelder-Mead search on the GPU
         (:mod:`victor_amd.fitting`).  Sampled: the uniform prior (the box), ``ref.loc`` (the start), ``proposal`` (the initial
@@ -331,21 +332,25 @@ class CCFFit(CCFModel):
         ``max_iter`` (default 200 d) counts launches; ``restarts``: rebuilds of a converged simplex around its best vertex.
         ``kwargs``: model and fit option overrides as :meth:`log_likelihood_batch` takes them.  Returns a
         :class:`victor_amd.fitting.BestFit`; its ``chi2`` is the chi-square at the best point, not a chi-square minimum.
-        Runs on this fit's own context (never through the broker)."""
+        ``prior``: a :class:`victor_amd.priors.GaussianPrior` (or a list of them with disjoint names) multiplied onto the box -
+        a Gaussian truncated by the box, without a normalisation constant; the search then maximises lnL + ln prior
+        (``BestFit.lnpost``).  Runs on this fit's own context (never through the broker)."""
         from .fitting import best_fit
-        return best_fit(self, params, fixed, start, step, xtol, ftol, max_iter, restarts, kwargs)
+        return best_fit(self, params, fixed, start, step, xtol, ftol, max_iter, restarts, kwargs, prior=prior)
 
     def sample_chains(self, params, n_steps, walkers=8, seed=0, fixed=None, start=None, scatter=None, proposal=None, burn=0,
-                      thin=1, keep_chain=True, device=True, move="metropolis", stretch_a=2.0, **kwargs):
+                      thin=1, keep_chain=True, device=True, move="metropolis", stretch_a=2.0, prior=None, **kwargs):
         """``walkers`` independent random-walk Metropolis chains of this fit's lnL, stepped on the GPU (``device=True``: the
         step loop runs on the device, ``vk_chain_begin``) or by the NumPy loop that defines them (``device=False``, over
         :meth:`log_likelihood_batch`): :func:`victor_amd.chains.sample_chains`, which documents the arguments.  Returns a
         :class:`victor_amd.chains.Chains` with R = 1.  ``move="stretch"``: the ``walkers`` are one affine-invariant stretch-move
-        ensemble instead (``stretch_a``: its scale; ``vk_chain_begin_stretch``).  Runs on this fit's own context (never through
+        ensemble instead (``stretch_a``: its scale; ``vk_chain_begin_stretch``).  ``prior``: a
+        :class:`victor_amd.priors.GaussianPrior` (or a list of them) multiplied onto the box, honoured by both moves on both
+        routes.  Runs on this fit's own context (never through
         the broker)."""
         from .chains import sample_chains
         return sample_chains(self, params, n_steps, walkers, seed, fixed, start, scatter, proposal, burn, thin, keep_chain, device,
-                             kwargs, move=move, stretch_a=stretch_a)
+                             kwargs, move=move, stretch_a=stretch_a, prior=prior)
 
     def realisations(self, simulation_numbers=None):
         """Every simulation realisation of this fit's data file (or the listed ``simulation_numbers``) against one model:

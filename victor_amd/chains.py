@@ -46,6 +46,14 @@ lz + lnl_prop - lnl``, left to right, with ``lz = (d - 1) * log(z)`` formed on t
 sweeps to ``vk_chain_begin_stretch``: per half-step a kernel that forms the proposals and their rows, the evaluation of those
 rows, and a kernel that decides - three launches in stream order, because the proposals of a half read what the decisions of
 the other half have just written.
+
+**``prior=``** multiplies a Gaussian prior (:class:`victor_amd.priors.GaussianPrior`, or a list of them) onto the box: what is
+sampled is the Gaussian truncated by the box (no normalisation constant: it changes no decision).  The Metropolis decision becomes
+``logu < (lnl_prop + lp_prop) - (lnl + lp)``, the stretch decision ``logu < (lz + (lnl_prop + lp_prop)) - (lnl + lp)``, with
+``lp_prop`` the prior at the proposal and ``lp`` the prior recomputed at the current position, in the arithmetic order of
+:meth:`victor_amd.priors.ResolvedPrior.lnprior`; outside the box ``lnl_prop = -inf`` as before (-inf plus a finite prior is
+-inf).  The device evaluates the same statement (``vk_chain_set_prior``, ``victor_amd/csrc/vk_prior.h``) bit for bit.  The
+state and ``lnl_chain`` keep the log-LIKELIHOOD; ``lnprior_chain`` is the prior of the kept positions, computed on the host.
 """
 
 import ctypes as C
@@ -102,11 +110,16 @@ class Chains:
 
     Diagnostics of the definition route only (None on the device route): ``decision_margin``, the smallest
     ``|lnl_prop - lnl - logu|`` (stretch move: ``|lz + lnl_prop - lnl - logu|``) over the decisions taken inside the box with a
-    finite difference (how far the closest decision was from falling the other way), and ``n_outside`` (R, W), the proposals that left the box."""
+    finite difference (how far the closest decision was from falling the other way), and ``n_outside`` (R, W), the proposals that left the box.
+
+    Under a Gaussian prior (``prior=``) ``lnl`` and ``lnl_chain`` stay the log-LIKELIHOOD; ``lnprior_chain`` (n_kept, R, W) is the
+    prior of the kept positions, computed on the host (zeros without a prior, None with ``keep_chain=False``), and
+    ``decision_margin`` includes the prior terms.  :meth:`extend` keeps the prior."""
 
     def __init__(self, names, specs, fixed, R, W, rng, width, burn, thin, keep_chain, evaluator, device_handle, move="metropolis",
-                 stretch_a=2.0):
+                 stretch_a=2.0, prior=None):
         self.names = list(names)
+        self._prior = prior                               # a victor_amd.priors.ResolvedPrior, or None
         self.move, self.stretch_a = move, float(stretch_a)
         self._specs, self.fixed = specs, fixed
         self.R, self.W = R, W
@@ -121,7 +134,7 @@ class Chains:
         self._at = BLOCK
         self.n_steps = 0
         self._hist = ([], [], [])
-        self.chain = self.lnl_chain = self.chi2_chain = None
+        self.chain = self.lnl_chain = self.chi2_chain = self.lnprior_chain = None
         self.decision_margin = self.n_outside = None
 
     # ------------------------------------------------------------------ random numbers: the blocks of EnsembleMetropolis ---
@@ -211,8 +224,12 @@ class Chains:
                     lnl_p, chi2_p = self._evaluate(rows, which)
                     lnl_p = np.where(inside, lnl_p, -np.inf)
                     with np.errstate(invalid="ignore"):
-                        accept = logu[t, h] < lz[t, h] + lnl_p - lnl_m   # NaN: False
-                        margin = np.abs(lz[t, h] + lnl_p - lnl_m - logu[t, h])
+                        if self._prior is None:
+                            gain = lz[t, h] + lnl_p - lnl_m
+                        else:                                            # (lz + (lnL' + lp')) - (lnL + lp)
+                            gain = (lz[t, h] + (lnl_p + self._prior.lnprior(prop))) - (lnl_m + self._prior.lnprior(xm))
+                        accept = logu[t, h] < gain                       # NaN: False
+                        margin = np.abs(gain - logu[t, h])
                     margin = margin[np.isfinite(margin)]
                     if margin.size:
                         self.decision_margin = min(self.decision_margin, float(margin.min()))
@@ -240,8 +257,12 @@ class Chains:
                 lnl_p, chi2_p = self._evaluate(rows)
                 lnl_p = np.where(inside, lnl_p, -np.inf)
                 with np.errstate(invalid="ignore"):
-                    accept = logu[t] < lnl_p - lnl                   # NaN (both -inf, or a NaN lnL): False
-                    margin = np.abs(lnl_p - lnl - logu[t])
+                    if self._prior is None:
+                        gain = lnl_p - lnl
+                    else:                                            # (lnL' + lp') - (lnL + lp)
+                        gain = (lnl_p + self._prior.lnprior(prop)) - (lnl + self._prior.lnprior(x))
+                    accept = logu[t] < gain                          # NaN (both -inf, or a NaN lnL): False
+                    margin = np.abs(gain - logu[t])
                 margin = margin[np.isfinite(margin)]
                 if margin.size:
                     self.decision_margin = min(self.decision_margin, float(margin.min()))
@@ -350,6 +371,7 @@ class Chains:
             self.chain = (hx[0].reshape(-1, R, W, d) if hx else np.empty((0, R, W, d)))
             self.lnl_chain = hl[0].reshape(-1, R, W) if hl else np.empty((0, R, W))
             self.chi2_chain = hc[0].reshape(-1, R, W) if hc else np.empty((0, R, W))
+            self.lnprior_chain = np.zeros(self.chain.shape[:-1]) if self._prior is None else self._prior.lnprior(self.chain)
             if W > 1 and len(self.chain) > 1 and self.move != "stretch":   # (the walkers of an ensemble are not independent chains)
                 with np.errstate(invalid="ignore", divide="ignore"):
                     self.rhat = np.stack([gelman_rubin(self.chain[:, r]) for r in range(R)])
@@ -365,7 +387,8 @@ def _draw_start(rng, loc, scale, lo, hi, what):
 
 
 def sample_chains(fit, params, n_steps, walkers=8, seed=0, fixed=None, start=None, scatter=None, proposal=None, burn=0, thin=1,
-                  keep_chain=True, device=True, kwargs=None, realisations=None, evaluate=None, move="metropolis", stretch_a=2.0):
+                  keep_chain=True, device=True, kwargs=None, realisations=None, evaluate=None, move="metropolis", stretch_a=2.0,
+                  prior=None):
     """The work of ``CCFFit.sample_chains`` (``realisations=None``: the fit's data vector, R = 1) and
     ``Realisations.sample_chains`` (R = the realisations); see the module docstring.  With ``evaluate`` - a callable taking a dict
     of ``(C,)`` arrays (sampled and fixed parameters) and returning ``lnL (C,)`` or ``(lnL, chi2)`` - in place of ``fit`` only the
@@ -379,7 +402,9 @@ def sample_chains(fit, params, n_steps, walkers=8, seed=0, fixed=None, start=Non
     "stretch" (module docstring): ``walkers`` must then be even and at least 2 (d + 1), ``stretch_a`` > 1 is the move's scale
     (z lies in [1 / a, a]), ``proposal`` is refused (the move has no widths), ``scatter`` keeps its default but must be > 0 in
     every parameter (an ensemble that starts collapsed onto a point, or into a plane, never leaves it), and the result's
-    ``rhat`` is None.  Every argument is checked before the first device call.  Returns a :class:`Chains`."""
+    ``rhat`` is None.  ``prior``: a :class:`victor_amd.priors.GaussianPrior` or a list of them with disjoint names, multiplied
+    onto the box (module docstring); both moves and both routes honour it.  Every argument is checked before the first device
+    call.  Returns a :class:`Chains`."""
     kwargs = kwargs or {}
     n_steps, walkers, burn, thin = int(n_steps), int(walkers), int(burn), int(thin)
     if n_steps < 0:
@@ -413,6 +438,7 @@ def sample_chains(fit, params, n_steps, walkers=8, seed=0, fixed=None, start=Non
         q.check_alpha()
     if arrays:
         raise InputError(f"sample_chains: fixed values must be scalars ({arrays} are not)")
+    prior = q.prior(prior, fit)
     if evaluate is None:
         fit_options = q.fit_options(fit, kwargs)
     R = len(realisations) if realisations is not None else 1
@@ -478,10 +504,12 @@ def sample_chains(fit, params, n_steps, walkers=8, seed=0, fixed=None, start=Non
         evaluator = None
         lib, h, refresh = q.create("vk_chain_create", fit, realisations, kwargs, fit_options, batch_of(x0), which)
         handle = (lib, h)
-    ch = Chains(names, specs, fixed_out, R, W, rng, width, burn, thin, bool(keep_chain), evaluator, handle, move, stretch_a)
+    ch = Chains(names, specs, fixed_out, R, W, rng, width, burn, thin, bool(keep_chain), evaluator, handle, move, stretch_a, prior)
     if handle:
         ch._refresh = refresh                                # (keeps the realisations and the contexts the handle runs on)
         ch._fit = fit                                        # (a joint fit owns the covariance handles the chains read)
+    if handle and prior is not None:
+        q.set_prior("vk_chain_set_prior", lib, h, prior)  # (the handle is the Chains' from here on: a refusal destroys it with ch)
     if handle:
         ch._check(handle[0].vk_chain_start(handle[1], N.as_dp(N.f64(x0))), "vk_chain_start")
     else:

@@ -25,6 +25,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "vk_prior.h"
+
 #if defined(__HIPCC__)
 #define VK_CHAIN_HD __host__ __device__
 #else
@@ -35,6 +37,7 @@ namespace vkchain {
 
 constexpr int kMaxP = 10;              // sampled parameters, as vkfit::kMaxP
 constexpr int kBlock = 64;             // steps whose random numbers travel together (EnsembleMetropolis.BLOCK)
+static_assert(vkprior::kMaxP == kMaxP, "a prior covers the sampled parameters");
 
 struct Box {
   int d;
@@ -120,6 +123,32 @@ VK_CHAIN_HD inline bool transition(const Box& b, View& s, const double* dz, doub
   const bool in = proposal_inside(b, s, dz);
   const double lnl_prop = in ? lnl_row : neg_inf();
   const bool accept = logu < lnl_prop - *s.lnl;            // false for a NaN difference
+  if (accept) {
+    for (int j = 0; j < b.d; ++j) s.x[j * s.stride] = s.x[j * s.stride] + dz[j];
+    *s.lnl = lnl_prop;
+    *s.chi2 = chi2_row;
+    *s.n_accept += 1;
+  }
+  *s.n_steps += 1;
+  if (kept) accumulate(b, s);
+  return accept;
+}
+
+// One step under a Gaussian prior (vk_prior.h) multiplied onto the box: the posterior decides,
+//   accept  <=>  logu < (lnL' + lp') - (lnL + lp)
+// with lp' the prior at the proposal x + dz and lp the prior recomputed at the current position - one addition on each side, one
+// subtraction and one comparison.  The state still holds the log-LIKELIHOOD of the chain's position.  A proposal outside the box
+// reads lnL' = -inf as in transition(), and -inf plus a finite lp' is -inf; a NaN lnL' rejects.  Without a prior (pr.on == 0)
+// this is transition().
+VK_CHAIN_HD inline bool transition_prior(const Box& b, const vkprior::Prior& pr, View& s, const double* dz, double logu,
+                                         double lnl_row, double chi2_row, bool kept) {
+  if (!pr.on) return transition(b, s, dz, logu, lnl_row, chi2_row, kept);
+  const bool in = proposal_inside(b, s, dz);
+  const double lnl_prop = in ? lnl_row : neg_inf();
+  const double lp_prop = vkprior::lnprior(pr, b.d, [&](int j) { return s.x[j * s.stride] + dz[j]; });
+  const double lp = vkprior::lnprior(pr, b.d, [&](int j) { return s.x[j * s.stride]; });
+  const double post_prop = lnl_prop + lp_prop, post = *s.lnl + lp;
+  const bool accept = logu < post_prop - post;             // false for a NaN difference
   if (accept) {
     for (int j = 0; j < b.d; ++j) s.x[j * s.stride] = s.x[j * s.stride] + dz[j];
     *s.lnl = lnl_prop;

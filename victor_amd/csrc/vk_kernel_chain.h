@@ -10,7 +10,8 @@
 // Alcock-Paczynski factors by sampled_row (vk_sampled_row.h), as the best fits' rows are - with the device's pow, so a row
 // with a sampled epsilon equals the host's row (libm's pow through vk_epsilon_to_ap) to rounding, any other row bit for bit.
 // A proposal outside the box is not evaluated: its row carries the chain's current position and the step kernel ignores what
-// comes back.
+// comes back.  Under a Gaussian prior (a.prior.on, vk_prior.h) the step kernel decides on lnL + ln prior (transition_prior); the
+// state and the history keep the log-likelihood.
 #pragma once
 #include "vk_common.h"
 #include "vk_chain_step.h"
@@ -50,6 +51,7 @@ struct ChainArgs {
   int col[vkchain::kMaxP];  // row column of each sampled parameter; VK_WALK_EPSILON: epsilon -> aperp, apar, epsilon
   double alpha;
   vkrow::Blocks blocks;     // the row sets of base and rows (one, or one per block of a joint fit) and each parameter's set
+  vkprior::Prior prior;     // the Gaussian prior of the sampled parameters (vk_chain_set_prior); on == 0: none
 };
 
 static_assert(sizeof(long long) == sizeof(int64_t), "the chain counters are 64-bit");
@@ -106,7 +108,8 @@ __global__ void __launch_bounds__(kChainBlock) vk_chain_step_kernel(ChainArgs a)
     vkchain::adopt(s, a.res_lnl[c], a.res_chi2[c]);
     return;
   }
-  vkchain::transition(a.box, s, a.dz + (size_t)c * d, a.logu[c], a.res_lnl[c], a.res_chi2[c], a.kept != 0);
+  if (a.prior.on) vkchain::transition_prior(a.box, a.prior, s, a.dz + (size_t)c * d, a.logu[c], a.res_lnl[c], a.res_chi2[c], a.kept != 0);
+  else vkchain::transition(a.box, s, a.dz + (size_t)c * d, a.logu[c], a.res_lnl[c], a.res_chi2[c], a.kept != 0);
   if (a.hist_x) {
     for (int j = 0; j < d; ++j) a.hist_x[(size_t)c * d + j] = s.x[j * s.stride];
     a.hist_lnl[c] = *s.lnl;

@@ -7,10 +7,13 @@
 // (lnL, chi2) pairs, applies vkfit::transition and writes the problem's next S rows - the base row with the sampled columns
 // overwritten and epsilon turned into the Alcock-Paczynski factors (sampled_row, vk_sampled_row.h) - and, against realisations,
 // each row's realisation index.  Rows of launch position k are rows k S .. k S + S - 1; the host keeps the list of active
-// problems (in problem order) and, when it shrinks, lays the rows out again with vk_fit_emit_kernel.
+// problems (in problem order) and, when it shrinks, lays the rows out again with vk_fit_emit_kernel.  Under a Gaussian prior
+// (a.prior.on, vk_prior.h) the value handed to vkfit::transition for a live slot is lnL + ln prior at the slot's point: the search
+// and its State are unchanged, f is minus the log-posterior.
 #pragma once
 #include "vk_common.h"
 #include "vk_fit_simplex.h"
+#include "vk_prior.h"
 #include "vk_sampled_row.h"
 
 namespace vk {
@@ -33,7 +36,10 @@ struct FitArgs {
   int col[vkfit::kMaxP];    // row column of each sampled parameter; VK_WALK_EPSILON: epsilon -> aperp, apar, epsilon
   double alpha;
   vkrow::Blocks blocks;     // the row sets of base and rows (one, or one per block of a joint fit) and each parameter's set
+  vkprior::Prior prior;     // the Gaussian prior of the sampled parameters (vk_fit_set_prior); on == 0: none
+  double* post;             // [n_active * S]: with a prior, lnL + ln prior of each live row (the results buffer itself: lnl == post)
 };
+static_assert(vkprior::kMaxP == vkfit::kMaxP, "a prior covers the sampled parameters");
 
 __device__ __forceinline__ void fit_emit(const FitArgs& a, const vkfit::State& s, int p, int k) {
   const int S = a.q.S;
@@ -62,6 +68,15 @@ __global__ void __launch_bounds__(kFitBlock) vk_fit_step_kernel(FitArgs a) {
   vkfit::State& s = a.state[p];
   if (s.phase == vkfit::kDone) return;
   const int S = a.q.S;
+  if (a.prior.on) {
+    // the search maximises the posterior: a live slot's value becomes lnL + lp(pt[slot]), written over the result it came from
+    // (global memory: no local array, no scratch); chi2 stays the chi-square of the row
+    for (int slot = 0; slot < S; ++slot)
+      if (s.live[slot]) {
+        const size_t r = (size_t)k * S + slot;
+        a.post[r] = a.post[r] + vkprior::lnprior(a.prior, a.q.d, [&](int j) { return s.pt[slot][j]; });
+      }
+  }
   vkfit::transition(s, a.q, a.lnl + (size_t)k * S, a.chi2 + (size_t)k * S);
   if (s.phase == vkfit::kDone) {
     a.status[p] = s.status;

@@ -5,7 +5,8 @@
 // through vk_eval_batch_device_async and, in vk_host.h, enqueue_realisations / check_real_lds.  A handle made by
 // vk_fit_create_joint / vk_chain_create_joint runs the same loops over a joint fit of several contexts - block-diagonal or under
 // one covariance handle, against the blocks' data vectors or joint realisation which[i] (that realisation of every block) -
-// through the joint entry points and their enqueue-only twins against realisations (vk_host.h).  Their _blocks forms keep a row
+// through the joint entry points and their enqueue-only twins against realisations (vk_host.h).  vk_fit_set_prior /
+// vk_chain_set_prior give any of these handles a Gaussian prior (vk_prior.h) that its step kernels add to lnL.  Their _blocks forms keep a row
 // set per block (base rows and pending rows, par_stride() apart) and write each sampled parameter to the block it belongs to, or
 // to all of them (vk_row_select.h); a handle of the other create calls has one row set and makes the launches it always made.
 // The same object serves every flavour of the library.
@@ -18,6 +19,7 @@
 //                        kernels, one thread per chain, over the one-chain transition of vk_chain_step.h (plain C++, likewise)
 //   vk_kernel_stretch.h  stretch-move ensembles on the same handles (vk_chain_begin_stretch): propose and step kernels of a
 //                        half-step, one thread per moving walker, over the transition of vk_stretch_step.h (plain C++, likewise)
+//   vk_prior.h           the Gaussian prior of the sampled parameters that the three step kernels add to lnL (plain C++, likewise)
 
 #include <hip/hip_runtime.h>
 
@@ -62,6 +64,7 @@ struct Sampled {
   void* d_mem = nullptr;                   // one allocation holding every device array of the handle
   double *d_base = nullptr, *d_rows = nullptr, *d_th = nullptr;   // each problem's base row; the pending rows, their theory vectors
   int *d_which = nullptr, *d_row_which = nullptr;                 // realisation of each problem, of each pending row
+  vkprior::Prior prior{};                  // the Gaussian prior the step kernels add to lnL (vk_fit_set_prior / vk_chain_set_prior)
   std::string err;
 
   // doubles between two row sets of d_rows (fixed per handle: a best fit's launches shrink, its sets stay where they are)
@@ -226,6 +229,28 @@ static int refused(Sampled* f, const std::string& msg) {
   return VK_E_ARG;
 }
 
+// vk_fit_set_prior / vk_chain_set_prior (`who`): mu [P] and the packed triangle [P (P + 1) / 2] of vk_prior.h, or NULL, NULL
+static int sampled_set_prior(Sampled* f, const char* who, const double* mu, const double* pp) {
+  if (!mu && !pp) {
+    f->prior = vkprior::Prior{};
+    f->err.clear();
+    return VK_OK;
+  }
+  if (!mu || !pp) return refused(f, std::string(who) + ": mu and pp_packed are both given or both NULL");
+  const int T = f->P * (f->P + 1) / 2;
+  for (int j = 0; j < f->P; ++j)
+    if (!__builtin_isfinite(mu[j])) return refused(f, std::string(who) + ": the mean of parameter " + std::to_string(j) + " is not finite");
+  for (int i = 0; i < T; ++i)
+    if (!__builtin_isfinite(pp[i])) return refused(f, std::string(who) + ": entry " + std::to_string(i) + " of the packed precision matrix is not finite");
+  vkprior::Prior p{};
+  p.on = 1;
+  for (int j = 0; j < f->P; ++j) p.mu[j] = mu[j];
+  for (int i = 0; i < T; ++i) p.pp[i] = pp[i];
+  f->prior = p;
+  f->err.clear();
+  return VK_OK;
+}
+
 // May the handle use its context now?  What every call that touches the context checks first.  (vk_fit_run reports an LDS
 // refusal in the context's words alone, the chain entry points under their own name: name_lds.)
 static int sampled_ready(Sampled* f, const char* who, const char* noun, bool name_lds) {
@@ -361,6 +386,8 @@ static int fit_loop(vk_fit* f, const vkfit::Params& q, const double* x0, std::ve
   for (int j = 0; j < vkfit::kMaxP; ++j) a.col[j] = f->col[j];
   a.alpha = f->alpha;
   a.blocks = f->row_sets((size_t)R);
+  a.prior = f->prior;
+  a.post = f->d_lnl;
   int rc = sampled_launch(f, vk_fit_init_kernel, R, kFitBlock, a);
   while (rc == VK_OK) {
     for (int t = 0; t < kFitCheck && rc == VK_OK; ++t) {
@@ -416,6 +443,11 @@ vk_fit* vk_fit_create_joint_blocks(vk_ctx* const* ctxs, int32_t n_ctx, vk_joint_
 }
 
 const char* vk_fit_last_error(const vk_fit* f) { return f ? f->err.c_str() : ""; }
+
+int vk_fit_set_prior(vk_fit* f, const double* mu, const double* pp_packed) {
+  if (!f) return VK_E_ARG;
+  return sampled_set_prior(f, "vk_fit_set_prior", mu, pp_packed);       // (vk_fit_run is synchronous: nothing is ever in flight)
+}
 
 void vk_fit_destroy(vk_fit* f) {
   if (f) sampled_destroy(f);
@@ -553,6 +585,7 @@ static ChainArgs chain_args(const vk_chain* f) {
   for (int j = 0; j < vkchain::kMaxP; ++j) a.col[j] = f->col[j];
   a.alpha = f->alpha;
   a.blocks = f->row_sets((size_t)f->C);
+  a.prior = f->prior;
   return a;
 }
 
@@ -585,6 +618,12 @@ vk_chain* vk_chain_create_joint_blocks(vk_ctx* const* ctxs, int32_t n_ctx, vk_jo
 }
 
 const char* vk_chain_last_error(const vk_chain* f) { return f ? f->err.c_str() : ""; }
+
+int vk_chain_set_prior(vk_chain* f, const double* mu, const double* pp_packed) {
+  if (!f) return VK_E_ARG;
+  if (f->in_flight) return refused(f, "vk_chain_set_prior: a block begun with vk_chain_begin is awaiting vk_chain_finish");
+  return sampled_set_prior(f, "vk_chain_set_prior", mu, pp_packed);
+}
 
 void vk_chain_destroy(vk_chain* f) {
   if (!f) return;

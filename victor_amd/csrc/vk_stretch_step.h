@@ -73,4 +73,28 @@ VK_CHAIN_HD inline bool stretch_transition(const Box& b, View& s, const double* 
   return accept;
 }
 
+// The half-step under a Gaussian prior (vk_prior.h): accept  <=>  logu < (lz + (lnL' + lp')) - (lnL + lp), lp' the prior at the
+// STORED proposal (formed only by propose()), lp the prior recomputed at the walker's position.  Outside the box lnL' = -inf as
+// above.  Without a prior (pr.on == 0) this is stretch_transition().
+VK_CHAIN_HD inline bool stretch_transition_prior(const Box& b, const vkprior::Prior& pr, View& s, const double* prop, size_t prop_stride,
+                                                 double lz, double logu, double lnl_row, double chi2_row, bool kept) {
+  if (!pr.on) return stretch_transition(b, s, prop, prop_stride, lz, logu, lnl_row, chi2_row, kept);
+  const bool in = stored_inside(b, prop, prop_stride);
+  const double lnl_prop = in ? lnl_row : neg_inf();
+  const double lp_prop = vkprior::lnprior(pr, b.d, [&](int j) { return prop[j * prop_stride]; });
+  const double lp = vkprior::lnprior(pr, b.d, [&](int j) { return s.x[j * s.stride]; });
+  const double post_prop = lnl_prop + lp_prop, post = *s.lnl + lp;
+  const double gain = lz + post_prop;
+  const bool accept = logu < gain - post;                  // false for a NaN
+  if (accept) {
+    for (int j = 0; j < b.d; ++j) s.x[j * s.stride] = prop[j * prop_stride];
+    *s.lnl = lnl_prop;
+    *s.chi2 = chi2_row;
+    *s.n_accept += 1;
+  }
+  *s.n_steps += 1;
+  if (kept) accumulate(b, s);
+  return accept;
+}
+
 }  // namespace vkchain

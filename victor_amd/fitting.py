@@ -10,7 +10,9 @@ one launch per iteration, with no host round trip per iteration.
 
 What is maximised is the fit's own lnL, the value ``log_likelihood`` returns: the likelihood form and, for a beta-dependent
 covariance, the log-determinant term are included, so with uniform priors the result is the MAP point.  The chi-square reported
-is the chi-square AT that point, not a separate chi-square minimum.
+is the chi-square AT that point, not a separate chi-square minimum.  With ``prior=`` (a Gaussian prior multiplied onto the box,
+:mod:`victor_amd.priors`) the device adds ln prior to the value of every point the search uses, and the result is the MAP point
+of that posterior.
 """
 
 import ctypes as C
@@ -28,11 +30,20 @@ class BestFit:
     ``names``: the sampled parameters; ``x``: ``(R, d)`` best vertices; ``params``: name -> ``(R,)`` array of every sampled
     and fixed value; ``lnl``, ``chi2``: lnL and chi-square there; ``status``: ``BestFit.CONVERGED``, ``MAX_ITER`` or
     ``NO_FINITE_START`` (every start vertex failed: ``x`` is the start, lnL -inf); ``n_iter``: iterations (launches) of each
-    problem; ``n_evals``: evaluations the search used (what a one-point-at-a-time Nelder-Mead evaluates)."""
+    problem; ``n_evals``: evaluations the search used (what a one-point-at-a-time Nelder-Mead evaluates).
+
+    ``lnpost``: what the device maximised, lnL + ln prior at the best vertex, in the device's bits; ``lnprior``: the prior
+    evaluated on the host at ``x`` (:mod:`victor_amd.priors`: no normalisation constant).  Without a prior ``lnprior`` is 0 and
+    ``lnpost`` is ``lnl``.  With one, ``lnl`` is ``lnpost - lnprior``: the log-likelihood at ``x`` up to that one subtraction's
+    rounding."""
 
     CONVERGED, MAX_ITER, NO_FINITE_START = N.VK_FIT_CONVERGED, N.VK_FIT_MAX_ITER, N.VK_FIT_NO_FINITE_START
 
-    def __init__(self, names, x, fixed, lnl, chi2, status, n_iter, n_evals):
+    def __init__(self, names, x, fixed, lnl, chi2, status, n_iter, n_evals, lnprior=None):
+        self.lnpost = lnl
+        self.lnprior = np.zeros(len(x)) if lnprior is None else lnprior
+        if lnprior is not None:
+            lnl = lnl - lnprior
         self.names = list(names)
         self.x = x
         self.params = {name: x[:, j].copy() for j, name in enumerate(self.names)}
@@ -125,8 +136,25 @@ class _Sampled:
             raise InputError(f"{self.who}: {what} names parameters that are not {self.verb}: {sorted(given)}")
         return out
 
+    def prior(self, prior, fit=None):
+        """The :class:`victor_amd.priors.ResolvedPrior` of the ``prior=`` argument against the sampled parameters (None for
+        None); every refusal before any device call."""
+        from .joint import JointFit
+        from .priors import resolve_prior
+        return resolve_prior(prior, self.who, self.names, self.lo, self.hi, self.fixed_all, isinstance(fit, JointFit))
+
+    def set_prior(self, entry, lib, h, prior):
+        """Hand a resolved prior to the handle ``h`` (``entry``: ``vk_fit_set_prior`` / ``vk_chain_set_prior``)."""
+        rc = getattr(lib, entry)(h, N.as_dp(prior.mu), N.as_dp(prior.pp))
+        if rc != 0:
+            last = lib.vk_fit_last_error if entry.startswith("vk_fit") else lib.vk_chain_last_error
+            raise (InputError if rc == -1 else N.NativeError)((last(h) or b"").decode() or f"{entry} failed ({rc})")
+
     def starts(self, given, R, prefix=""):
-        """``(R, d)`` start points inside the prior: ``given`` (name -> scalar or ``(R,)`` array) over the ``ref`` locations."""
+        """``(R, d)`` start points inside the prior: ``given`` (name -> scalar or ``(R,)`` array, or a :class:`BestFit`, whose
+        fitted values of the sampled names are taken) over the ``ref`` locations."""
+        if hasattr(given, "params") and hasattr(given, "names"):
+            given = {n: v for n, v in given.params.items() if n in self.names}
         given = dict(given or {})
         x0 = np.empty((R, len(self.specs)))
         for j, s in enumerate(self.specs):
@@ -174,10 +202,11 @@ class _Sampled:
 
 
 def best_fit(fit, params, fixed=None, start=None, step=None, xtol=None, ftol=1e-6, max_iter=None, restarts=1, kwargs=None,
-             realisations=None):
+             realisations=None, prior=None):
     """The work of ``CCFFit.best_fit`` (``realisations=None``: against the fit's data vector) and ``Realisations.best_fit``;
-    with a ``JointFit`` for ``fit`` (and its ``JointRealisations``), of theirs.  Every argument is checked before the first
-    device call."""
+    with a ``JointFit`` for ``fit`` (and its ``JointRealisations``), of theirs.  ``prior``: a
+    :class:`victor_amd.priors.GaussianPrior` (or a list of them) multiplied onto the box; the search then maximises
+    lnL + ln prior (``vk_fit_set_prior``).  Every argument is checked before the first device call."""
     kwargs = kwargs or {}
     q = _Sampled("best_fit", "fitted", params, fixed)
     names, fixed_all, d = q.names, q.fixed_all, len(q.names)
@@ -193,6 +222,7 @@ def best_fit(fit, params, fixed=None, start=None, step=None, xtol=None, ftol=1e-
             raise InputError(f"best_fit: fixed arrays have different lengths: {sorted(lengths)}")
         R = lengths.pop() if lengths else 1
     q.check_alpha()
+    prior = q.prior(prior, fit)
     fit_options = q.fit_options(fit, kwargs)
     x0 = q.starts(start, R)
     steps = q.per_param("step", step, [s.proposal for s in q.specs])
@@ -215,6 +245,8 @@ def best_fit(fit, params, fixed=None, start=None, step=None, xtol=None, ftol=1e-
     status, n_iter = np.empty(R, dtype=np.int32), np.empty(R, dtype=np.int32)
     n_evals = np.empty(R, dtype=np.int64)
     try:
+        if prior is not None:
+            q.set_prior("vk_fit_set_prior", lib, h, prior)
         rc = lib.vk_fit_run(h, N.as_dp(N.f64(x0)), N.as_dp(N.f64(steps)), N.as_dp(N.f64(xtols)), float(ftol), max_iter,
                             int(restarts), N.as_dp(x), N.as_dp(lnl), N.as_dp(chi2), status.ctypes.data_as(i32),
                             n_iter.ctypes.data_as(i32), n_evals.ctypes.data_as(C.POINTER(C.c_int64)))
@@ -224,4 +256,4 @@ def best_fit(fit, params, fixed=None, start=None, step=None, xtol=None, ftol=1e-
     finally:
         lib.vk_fit_destroy(h)
     fixed_out = {k: _per_problem(k, v, R) for k, v in fixed_all.items()}
-    return BestFit(names, x, fixed_out, lnl, chi2, status, n_iter, n_evals)
+    return BestFit(names, x, fixed_out, lnl, chi2, status, n_iter, n_evals, None if prior is None else prior.lnprior(x))

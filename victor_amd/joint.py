@@ -503,23 +503,24 @@ class JointFit:
             raise (N.NativeError if "device memory" in msg else InputError)(msg)
         return lead._lib, h, refresh
 
-    def best_fit(self, params, fixed=None, start=None, step=None, xtol=None, ftol=1e-6, max_iter=None, restarts=1, **kwargs):
+    def best_fit(self, params, fixed=None, start=None, step=None, xtol=None, ftol=1e-6, max_iter=None, restarts=1, prior=None,
+                 **kwargs):
         """Maximum of the joint lnL (the value :meth:`log_likelihood_batch` returns) over the sampled parameters of a cobaya
         ``params`` block - one parameter vector for all blocks, or with ``"name@q"`` entries (:func:`per_block`) a value of
         that parameter per block, at most 10 sampled values in all - by the bounded Nelder-Mead search of ``CCFFit.best_fit`` on
         the GPU, block-diagonal or under the joint covariance.  Arguments and result as ``CCFFit.best_fit``: arrays in
-        ``fixed`` give a profile."""
+        ``fixed`` give a profile; a ``prior`` (:class:`victor_amd.priors.GaussianPrior`) may name ``"name@q"`` parameters."""
         from .fitting import best_fit
-        return best_fit(self, params, fixed, start, step, xtol, ftol, max_iter, restarts, kwargs)
+        return best_fit(self, params, fixed, start, step, xtol, ftol, max_iter, restarts, kwargs, prior=prior)
 
     def sample_chains(self, params, n_steps, walkers=8, seed=0, fixed=None, start=None, scatter=None, proposal=None, burn=0,
-                      thin=1, keep_chain=True, device=True, move="metropolis", stretch_a=2.0, **kwargs):
+                      thin=1, keep_chain=True, device=True, move="metropolis", stretch_a=2.0, prior=None, **kwargs):
         """``walkers`` Metropolis chains of the joint lnL, stepped on the GPU (``device=True``) or by the NumPy loop over
         :meth:`log_likelihood_batch` that defines them (``device=False``).  Arguments and result as ``CCFFit.sample_chains``
         (:mod:`victor_amd.chains`), ``move="stretch"`` included; the result keeps this joint fit alive."""
         from .chains import sample_chains
         return sample_chains(self, params, n_steps, walkers, seed, fixed, start, scatter, proposal, burn, thin, keep_chain, device,
-                             kwargs, move=move, stretch_a=stretch_a)
+                             kwargs, move=move, stretch_a=stretch_a, prior=prior)
 
     @property
     def n_data(self):
@@ -560,21 +561,23 @@ class JointRealisations:
         for r, eng in zip(self.blocks, engines):
             r._upload(eng)
 
-    def best_fit(self, params, fixed=None, start=None, step=None, xtol=None, ftol=1e-6, max_iter=None, restarts=1, **kwargs):
+    def best_fit(self, params, fixed=None, start=None, step=None, xtol=None, ftol=1e-6, max_iter=None, restarts=1, prior=None,
+                 **kwargs):
         """Best-fit point of every joint realisation: problem i maximises the joint lnL against realisation ``numbers[i]`` of
         every block, all of them in one run on the GPU.  Arguments as ``JointFit.best_fit``; ``fixed`` values must be scalars."""
         from .fitting import best_fit
-        return best_fit(self.joint, params, fixed, start, step, xtol, ftol, max_iter, restarts, kwargs, realisations=self)
+        return best_fit(self.joint, params, fixed, start, step, xtol, ftol, max_iter, restarts, kwargs, realisations=self,
+                        prior=prior)
 
     def sample_chains(self, params, n_steps, walkers=8, seed=0, fixed=None, start=None, scatter=None, proposal=None, burn=0,
-                      thin=1, keep_chain=True, device=True, move="metropolis", stretch_a=2.0, **kwargs):
+                      thin=1, keep_chain=True, device=True, move="metropolis", stretch_a=2.0, prior=None, **kwargs):
         """``walkers`` Metropolis chains of EVERY joint realisation in lock step, on the GPU (``device=True``) or by the NumPy
         loop over :meth:`log_likelihood_pairs` that defines them (``device=False``).  Arguments and result as
         ``Realisations.sample_chains`` (``move="stretch"``: one ensemble per joint realisation); ``start`` may be the ``BestFit``
         of :meth:`best_fit`."""
         from .chains import sample_chains
         return sample_chains(self.joint, params, n_steps, walkers, seed, fixed, start, scatter, proposal, burn, thin, keep_chain,
-                             device, kwargs, realisations=self, move=move, stretch_a=stretch_a)
+                             device, kwargs, realisations=self, move=move, stretch_a=stretch_a, prior=prior)
 
     def _eval(self, params, kwargs, which=None):
         joint = self.joint

@@ -136,14 +136,16 @@ class Realisations:
         """The chi-square half of :meth:`log_likelihood` (data vector interpolated in beta, as ``CCFFit.chi_squared``)."""
         return self.log_likelihood(params, **dict(kwargs, beta_interpolation="datavector"))[1]
 
-    def best_fit(self, params, fixed=None, start=None, step=None, xtol=None, ftol=1e-6, max_iter=None, restarts=1, **kwargs):
+    def best_fit(self, params, fixed=None, start=None, step=None, xtol=None, ftol=1e-6, max_iter=None, restarts=1, prior=None,
+                 **kwargs):
         """Best-fit point of every realisation: problem i maximises lnL against realisation ``numbers[i]``, all of them in one
-        run on the GPU.  Arguments as ``CCFFit.best_fit``; ``fixed`` values must be scalars here."""
+        run on the GPU.  Arguments as ``CCFFit.best_fit`` (``prior``: one Gaussian prior for all realisations); ``fixed``
+        values must be scalars here."""
         from .fitting import best_fit
-        return best_fit(self.fit, params, fixed, start, step, xtol, ftol, max_iter, restarts, kwargs, realisations=self)
+        return best_fit(self.fit, params, fixed, start, step, xtol, ftol, max_iter, restarts, kwargs, realisations=self, prior=prior)
 
     def sample_chains(self, params, n_steps, walkers=8, seed=0, fixed=None, start=None, scatter=None, proposal=None, burn=0,
-                      thin=1, keep_chain=True, device=True, move="metropolis", stretch_a=2.0, **kwargs):
+                      thin=1, keep_chain=True, device=True, move="metropolis", stretch_a=2.0, prior=None, **kwargs):
         """``walkers`` Metropolis chains of EVERY realisation, all of them in lock step: problem i samples lnL against realisation
         ``numbers[i]``, on the GPU (``device=True``) or by the NumPy loop over :meth:`log_likelihood_pairs` that defines the
         chains (``device=False``).  Arguments and result as ``CCFFit.sample_chains`` (:mod:`victor_amd.chains`); ``start`` may be
@@ -151,7 +153,7 @@ class Realisations:
         ``walkers`` walkers per realisation instead."""
         from .chains import sample_chains
         return sample_chains(self.fit, params, n_steps, walkers, seed, fixed, start, scatter, proposal, burn, thin, keep_chain,
-                             device, kwargs, realisations=self, move=move, stretch_a=stretch_a)
+                             device, kwargs, realisations=self, move=move, stretch_a=stretch_a, prior=prior)
 
     def log_likelihood_pairs(self, params, which, **kwargs):
         """(lnL, chi2), each ``(n_points,)``: point p against realisation ``numbers[which[p]]`` only - the form an ensemble of
