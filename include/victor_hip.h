@@ -523,6 +523,37 @@ int vk_chain_begin_stretch(vk_chain* f, int32_t n_steps, int32_t walkers, const 
 int vk_fit_set_prior(vk_fit* f, const double* mu, const double* pp_packed);
 int vk_chain_set_prior(vk_chain* f, const double* mu, const double* pp_packed);
 
+/* ---- Marginal histograms of a chain handle's kept positions ------------------------------------------------------------------
+ * With keep-nothing runs (want_history = 0) the moment sums are all a handle returns of its posterior.  vk_chain_set_marginals
+ * makes the step kernels of vk_chain_begin and vk_chain_begin_stretch count, on any handle of the create calls, every position
+ * that enters the moment sums - a kept step; a kept sweep, in the walker's own moving half-step - in 64-bit histograms on the
+ * device: one of every sampled parameter and one of each of n_pairs pairs of them.  Integer adds commute, so the counts do not
+ * depend on the order the chains arrive in.
+ *   group      chains per problem: the histograms are pooled, chain c adds to problem c / group (n_chains / group problems)
+ *   n_bins     bins of a 1-D histogram, 1..1024; lo, hi [n_params]: the range [a_j, b_j] of each sampled parameter, in the order
+ *              of the handle's sampled parameters (any finite lo < hi: it need not be the box)
+ *   pairs      [n_pairs][2] parameter indices (j, k), j < k, each pair once, n_pairs in 0..45 (NULL for 0); n_bins2: bins per axis
+ *              of a 2-D histogram, 1..128 (not read when n_pairs == 0)
+ * The slot rule (vk_marginals.h), with inv_j = n_bins / (b_j - a_j), one IEEE division made once on the host: a value v < a_j
+ * goes to slot 0 ("below"), v > b_j to slot n_bins + 1 ("above"), any other to slot 1 + min(n_bins - 1, (int)((v - a_j) * inv_j))
+ * - one subtraction, one multiplication, one truncating conversion, nothing to fuse; v == b_j lands in the last bin.  A sample
+ * enters the histogram of pair (j, k) only when it lies inside both ranges, in cell (bin_j, bin_k) by the same rule with n_bins2.
+ * vk_chain_marginals copies the counts out, between blocks; either pointer may be NULL:
+ *   h1         [n_chains / group][n_params][n_bins + 2]
+ *   h2         [n_chains / group][n_pairs][n_bins2][n_bins2], row bin_j
+ * The handle owns the buffers: made and zeroed by vk_chain_set_marginals (a second call replaces them), zeroed again by
+ * vk_chain_start - which resets the counters and the moment sums too -, kept across blocks, freed by vk_chain_destroy.
+ * n_bins == 0 with lo == hi == NULL clears the marginals and frees the buffers; a handle that never had them, or had them
+ * cleared, makes the launches and returns the bytes it always did.
+ * Refused (VK_E_ARG, vk_chain_last_error gives the text, the handle stays usable and keeps the marginals it had): a block begun
+ * and not finished; group < 1 or n_chains % group != 0; n_bins outside 1..1024; n_pairs outside 0..45; with pairs, n_bins2
+ * outside 1..128; a pair with j >= k or an index outside 0..n_params - 1, or a repeated pair; a range that is not finite or
+ * without lo < hi; vk_chain_marginals on a handle without marginals.  Device memory that cannot be had is reported as
+ * vk_chain_create reports it (VK_E_HIP, "cannot allocate ... bytes of device memory"); the handle then has no marginals. */
+int vk_chain_set_marginals(vk_chain* f, int32_t group, int32_t n_bins, const double* lo, const double* hi, int32_t n_pairs,
+                           const int32_t* pairs, int32_t n_bins2);
+int vk_chain_marginals(vk_chain* f, int64_t* h1, int64_t* h2);
+
 /* Theory multipoles on a caller-supplied s grid: out[n][n_ell][n_s] with the caller's own
  * projection weights w_ell[n_ell][n_mu] on mu[n_mu] (host buffers). */
 int vk_theory_batch(vk_ctx* ctx, const vk_eval_opts* opts, const double* params, int64_t n,

@@ -182,6 +182,9 @@ SYMBOLS = {
     # a Gaussian prior on the sampled parameters of a best-fit or chain handle
     "vk_fit_set_prior": (C.c_int, [_vp, _dp, _dp]),
     "vk_chain_set_prior": (C.c_int, [_vp, _dp, _dp]),
+    # marginal histograms of a chain handle's kept positions
+    "vk_chain_set_marginals": (C.c_int, [_vp, C.c_int32, C.c_int32, _dp, _dp, C.c_int32, C.POINTER(C.c_int32), C.c_int32]),
+    "vk_chain_marginals": (C.c_int, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "vk_serve_mailboxes": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, _optp, _vp, C.c_int32, _vp, C.c_double, C.c_int32,
                            C.c_double, C.POINTER(vk_serve_stats)]),
     "vk_timing_enable": (C.c_int, [_vp, C.c_int]),

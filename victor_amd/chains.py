@@ -54,6 +54,12 @@ sampled is the Gaussian truncated by the box (no normalisation constant: it chan
 :meth:`victor_amd.priors.ResolvedPrior.lnprior`; outside the box ``lnl_prop = -inf`` as before (-inf plus a finite prior is
 -inf).  The device evaluates the same statement (``vk_chain_set_prior``, ``victor_amd/csrc/vk_prior.h``) bit for bit.  The
 state and ``lnl_chain`` keep the log-LIKELIHOOD; ``lnprior_chain`` is the prior of the kept positions, computed on the host.
+
+**``marginals=``** counts every kept position in per-problem histograms (:mod:`victor_amd.marginals`: one of every sampled
+parameter, and of chosen pairs), where the moment sums are accumulated and with the same "kept": on the device route by the step
+kernels (``vk_chain_set_marginals``; integer atomic increments), on the definition route by the NumPy statement of the same binning
+rule - so the two routes give equal counts wherever they give equal positions, with or without a history.  ``Chains.marginals``
+reads medians and equal-tailed intervals from them.
 """
 
 import ctypes as C
@@ -114,12 +120,18 @@ class Chains:
 
     Under a Gaussian prior (``prior=``) ``lnl`` and ``lnl_chain`` stay the log-LIKELIHOOD; ``lnprior_chain`` (n_kept, R, W) is the
     prior of the kept positions, computed on the host (zeros without a prior, None with ``keep_chain=False``), and
-    ``decision_margin`` includes the prior terms.  :meth:`extend` keeps the prior."""
+    ``decision_margin`` includes the prior terms.  :meth:`extend` keeps the prior.
+
+    ``marginals``: a :class:`victor_amd.marginals.Marginals` of the kept positions' histograms (None without ``marginals=``),
+    rebuilt after every :meth:`extend`, which keeps counting."""
 
     def __init__(self, names, specs, fixed, R, W, rng, width, burn, thin, keep_chain, evaluator, device_handle, move="metropolis",
-                 stretch_a=2.0, prior=None):
+                 stretch_a=2.0, prior=None, binning=None):
         self.names = list(names)
         self._prior = prior                               # a victor_amd.priors.ResolvedPrior, or None
+        self._binning = binning                           # a victor_amd.marginals.Binning, or None
+        self._h1, self._h2 = binning.zeros(R) if binning is not None else (None, None)
+        self.marginals = None
         self.move, self.stretch_a = move, float(stretch_a)
         self._specs, self.fixed = specs, fixed
         self.R, self.W = R, W
@@ -195,6 +207,8 @@ class Chains:
             self._sum1 += dx
             self._sum2 += dx[:, :, None] * dx[:, None, :]
             self._n_kept += 1
+            if self._binning is not None:
+                self._binning.add(self._h1, self._h2, x, self.W)
             if self.keep_chain:
                 for h, a in zip(self._hist, (x, lnl, chi2)):
                     h.append(a.copy())
@@ -322,6 +336,16 @@ class Chains:
         self._check(lib.vk_chain_state(h, N.as_dp(self._x), N.as_dp(self._lnl), N.as_dp(self._chi2),
                                        self._n_accept.ctypes.data_as(i64), None, self._n_kept.ctypes.data_as(i64),
                                        N.as_dp(self._pivot), N.as_dp(self._sum1), N.as_dp(self._sum2)), "vk_chain_state")
+        if self._binning is not None:
+            self._check(lib.vk_chain_marginals(h, self._h1.ctypes.data_as(i64), self._h2.ctypes.data_as(i64)), "vk_chain_marginals")
+
+    def _set_marginals_device(self):
+        """Hand the binning to the handle (before ``vk_chain_start``): the W chains of a problem pool."""
+        lib, h = self._dev
+        q = self._binning
+        pairs = q.pairs.ctypes.data_as(C.POINTER(C.c_int32)) if len(q.pairs) else None
+        self._check(lib.vk_chain_set_marginals(h, self.W, q.n_bins, N.as_dp(q.a), N.as_dp(q.b), len(q.pairs), pairs, q.n_bins2),
+                    "vk_chain_set_marginals")
 
     def __del__(self):
         dev = getattr(self, "_dev", None)
@@ -361,6 +385,9 @@ class Chains:
         self.mean, self.cov = pooled_moments(per_chain, self.pivot, self.sum1, self.sum2)
         if not self._dev:
             self.n_outside = self._n_outside.reshape(R, W).copy()
+        if self._binning is not None:
+            from .marginals import Marginals
+            self.marginals = Marginals(self._binning, self._h1, self._h2, per_chain.sum(axis=1))
         self.rhat = None
         if self.keep_chain:
             hx, hl, hc = self._hist
@@ -388,7 +415,7 @@ def _draw_start(rng, loc, scale, lo, hi, what):
 
 def sample_chains(fit, params, n_steps, walkers=8, seed=0, fixed=None, start=None, scatter=None, proposal=None, burn=0, thin=1,
                   keep_chain=True, device=True, kwargs=None, realisations=None, evaluate=None, move="metropolis", stretch_a=2.0,
-                  prior=None):
+                  prior=None, marginals=None):
     """The work of ``CCFFit.sample_chains`` (``realisations=None``: the fit's data vector, R = 1) and
     ``Realisations.sample_chains`` (R = the realisations); see the module docstring.  With ``evaluate`` - a callable taking a dict
     of ``(C,)`` arrays (sampled and fixed parameters) and returning ``lnL (C,)`` or ``(lnL, chi2)`` - in place of ``fit`` only the
@@ -403,8 +430,11 @@ def sample_chains(fit, params, n_steps, walkers=8, seed=0, fixed=None, start=Non
     (z lies in [1 / a, a]), ``proposal`` is refused (the move has no widths), ``scatter`` keeps its default but must be > 0 in
     every parameter (an ensemble that starts collapsed onto a point, or into a plane, never leaves it), and the result's
     ``rhat`` is None.  ``prior``: a :class:`victor_amd.priors.GaussianPrior` or a list of them with disjoint names, multiplied
-    onto the box (module docstring); both moves and both routes honour it.  Every argument is checked before the first device
-    call.  Returns a :class:`Chains`."""
+    onto the box (module docstring); both moves and both routes honour it.  ``marginals``: None (off), True (a 128-bin histogram
+    of every sampled parameter over its prior box) or a dict ``{"bins": int, "range": {name: (a, b)}, "pairs": [(name, name), ...]
+    | "all", "bins2d": int}`` - ranges not given are the box, ``bins`` at most 1024, ``bins2d`` (default 32) at most 128, at
+    most 45 pairs - for per-problem histograms of the kept positions, counted where the chains run (:mod:`victor_amd.marginals`;
+    ``Chains.marginals``).  Every argument is checked before the first device call.  Returns a :class:`Chains`."""
     kwargs = kwargs or {}
     n_steps, walkers, burn, thin = int(n_steps), int(walkers), int(burn), int(thin)
     if n_steps < 0:
@@ -439,6 +469,8 @@ def sample_chains(fit, params, n_steps, walkers=8, seed=0, fixed=None, start=Non
     if arrays:
         raise InputError(f"sample_chains: fixed values must be scalars ({arrays} are not)")
     prior = q.prior(prior, fit)
+    from .marginals import resolve_marginals
+    binning = resolve_marginals(marginals, "sample_chains", names, lo, hi)
     if evaluate is None:
         fit_options = q.fit_options(fit, kwargs)
     R = len(realisations) if realisations is not None else 1
@@ -504,12 +536,15 @@ def sample_chains(fit, params, n_steps, walkers=8, seed=0, fixed=None, start=Non
         evaluator = None
         lib, h, refresh = q.create("vk_chain_create", fit, realisations, kwargs, fit_options, batch_of(x0), which)
         handle = (lib, h)
-    ch = Chains(names, specs, fixed_out, R, W, rng, width, burn, thin, bool(keep_chain), evaluator, handle, move, stretch_a, prior)
+    ch = Chains(names, specs, fixed_out, R, W, rng, width, burn, thin, bool(keep_chain), evaluator, handle, move, stretch_a, prior,
+                binning)
     if handle:
         ch._refresh = refresh                                # (keeps the realisations and the contexts the handle runs on)
         ch._fit = fit                                        # (a joint fit owns the covariance handles the chains read)
     if handle and prior is not None:
         q.set_prior("vk_chain_set_prior", lib, h, prior)  # (the handle is the Chains' from here on: a refusal destroys it with ch)
+    if handle and binning is not None:
+        ch._set_marginals_device()
     if handle:
         ch._check(handle[0].vk_chain_start(handle[1], N.as_dp(N.f64(x0))), "vk_chain_start")
     else:

@@ -11,10 +11,12 @@
 // with a sampled epsilon equals the host's row (libm's pow through vk_epsilon_to_ap) to rounding, any other row bit for bit.
 // A proposal outside the box is not evaluated: its row carries the chain's current position and the step kernel ignores what
 // comes back.  Under a Gaussian prior (a.prior.on, vk_prior.h) the step kernel decides on lnL + ln prior (transition_prior); the
-// state and the history keep the log-likelihood.
+// state and the history keep the log-likelihood.  With marginal histograms set (a.marg.on, vk_marginals.h) a kept step also counts
+// the position the moment sums have just taken, in the histograms of the chain's problem: integer atomic increments on global memory.
 #pragma once
 #include "vk_common.h"
 #include "vk_chain_step.h"
+#include "vk_marginals.h"
 #include "vk_sampled_row.h"
 
 namespace vk {
@@ -52,9 +54,24 @@ struct ChainArgs {
   double alpha;
   vkrow::Blocks blocks;     // the row sets of base and rows (one, or one per block of a joint fit) and each parameter's set
   vkprior::Prior prior;     // the Gaussian prior of the sampled parameters (vk_chain_set_prior); on == 0: none
+  vkmarg::Marginals marg;   // the marginal histograms of the kept positions (vk_chain_set_marginals); on == 0: none
 };
 
 static_assert(sizeof(long long) == sizeof(int64_t), "the chain counters are 64-bit");
+static_assert(sizeof(unsigned long long) == sizeof(int64_t) && vkmarg::kMaxP == vkchain::kMaxP, "the histograms count in 64 bits");
+
+static_assert(sizeof(unsigned long) == sizeof(unsigned long long), "the atomic increment below is 64 bits wide");
+
+// The position vkchain::accumulate has just taken for chain c, counted in the histograms of the chain's problem.  The count is
+// the 64-bit atomic increment with its wrap bound at 2^64 - 1 - a plain + 1, global_atomic_inc_x2, no value returned - and not
+// atomicAdd(at, 1): global_atomic_add in this library's code objects is the completion counter of the theory kernels' hand-off
+// between workgroups, whose ordering tests/test_host.py checks on the shipped ISA of every kernel that contains one.  A count
+// hands nothing over: nothing is read back inside the launch, and the host reads the histograms behind a stream synchronise.
+__device__ __forceinline__ void chain_count(const vkmarg::Marginals& m, const vkchain::View& s, int d, int c) {
+  vkmarg::count(m, d, (size_t)(c / m.group), [&](int j) { return s.x[j * s.stride]; }, [](unsigned long long* at) {
+    __builtin_amdgcn_atomic_inc64(reinterpret_cast<unsigned long*>(at), ~0ul, __ATOMIC_RELAXED, "agent");
+  });
+}
 
 __device__ __forceinline__ vkchain::View chain_view(const ChainArgs& a, int c) {
   vkchain::View s;
@@ -110,6 +127,7 @@ __global__ void __launch_bounds__(kChainBlock) vk_chain_step_kernel(ChainArgs a)
   }
   if (a.prior.on) vkchain::transition_prior(a.box, a.prior, s, a.dz + (size_t)c * d, a.logu[c], a.res_lnl[c], a.res_chi2[c], a.kept != 0);
   else vkchain::transition(a.box, s, a.dz + (size_t)c * d, a.logu[c], a.res_lnl[c], a.res_chi2[c], a.kept != 0);
+  if (a.marg.on && a.kept) chain_count(a.marg, s, d, c);
   if (a.hist_x) {
     for (int j = 0; j < d; ++j) a.hist_x[(size_t)c * d + j] = s.x[j * s.stride];
     a.hist_lnl[c] = *s.lnl;

@@ -9,7 +9,8 @@
 //                               the proposal, or outside the box the walker's current position;
 //   the evaluation of the M rows (the launches the Metropolis chains make for C rows);
 //   vk_stretch_step_kernel      decides on the STORED proposal (vkchain::stretch_transition; under a Gaussian prior, a.c.prior.on,
-//                               stretch_transition_prior with the prior at the stored proposal), accounts and fills the history slot.
+//                               stretch_transition_prior with the prior at the stored proposal), accounts (with a.c.marg.on also in
+//                               the marginal histograms of the walker's problem, vk_marginals.h) and fills the history slot.
 // The proposals of a half read positions that the step kernel of the other half has just written, by other threads and other
 // workgroups: that is why they are formed in a launch of their own behind it, and why the step kernel writes no rows - stream
 // order is the only hand-off between workgroups.
@@ -61,6 +62,7 @@ __global__ void __launch_bounds__(kChainBlock) vk_stretch_step_kernel(StretchArg
                                       a.c.res_chi2[i], a.c.kept != 0);
   else
     vkchain::stretch_transition(a.c.box, s, a.prop + i, (size_t)a.M, a.lz[i], a.logu[i], a.c.res_lnl[i], a.c.res_chi2[i], a.c.kept != 0);
+  if (a.c.marg.on && a.c.kept) chain_count(a.c.marg, s, d, c);       // (a kept sweep, in the walker's own moving half-step)
   if (a.c.hist_x) {
     for (int j = 0; j < d; ++j) a.c.hist_x[(size_t)c * d + j] = s.x[j * s.stride];
     a.c.hist_lnl[c] = *s.lnl;

@@ -20,6 +20,8 @@
 //   vk_kernel_stretch.h  stretch-move ensembles on the same handles (vk_chain_begin_stretch): propose and step kernels of a
 //                        half-step, one thread per moving walker, over the transition of vk_stretch_step.h (plain C++, likewise)
 //   vk_prior.h           the Gaussian prior of the sampled parameters that the three step kernels add to lnL (plain C++, likewise)
+//   vk_marginals.h       the binning rule of the marginal histograms the two chain step kernels count kept positions in
+//                        (vk_chain_set_marginals; plain C++, likewise)
 
 #include <hip/hip_runtime.h>
 
@@ -513,6 +515,10 @@ struct __attribute__((visibility("hidden"))) vk_chain : Sampled {
   void* d_stretch = nullptr;
   double *d_sz = nullptr, *d_slz = nullptr, *d_slogu = nullptr, *d_prop = nullptr;
   int* d_partner = nullptr;
+  // the marginal histograms h1 | h2 of vk_marginals.h: one allocation of its own, made (and zeroed) by vk_chain_set_marginals
+  vkmarg::Marginals marg{};
+  void* d_marg = nullptr;
+  size_t marg_n1 = 0, marg_n2 = 0;         // counts of h1, of h2
   std::vector<int> h_which;                // the chains' realisation indices, read back for vk_chain_begin_stretch's check
 
   void stretch_layout(Carve& c) {
@@ -586,7 +592,19 @@ static ChainArgs chain_args(const vk_chain* f) {
   a.alpha = f->alpha;
   a.blocks = f->row_sets((size_t)f->C);
   a.prior = f->prior;
+  a.marg = f->marg;
   return a;
+}
+
+// no histograms any more: the handle makes the launches it made before it had any
+static void chain_drop_marginals(vk_chain* f) {
+  if (f->d_marg) {
+    (void)hipSetDevice(f->ctx->device);
+    (void)hipFree(f->d_marg);
+  }
+  f->d_marg = nullptr;
+  f->marg = vkmarg::Marginals{};
+  f->marg_n1 = f->marg_n2 = 0;
 }
 
 extern "C" {
@@ -625,9 +643,91 @@ int vk_chain_set_prior(vk_chain* f, const double* mu, const double* pp_packed) {
   return sampled_set_prior(f, "vk_chain_set_prior", mu, pp_packed);
 }
 
+// The marginal histograms of the kept positions (vk_marginals.h).  Everything the kernels index with is checked here: the
+// group, the bin counts and the pair list fix the size of the buffers the slots address.
+int vk_chain_set_marginals(vk_chain* f, int32_t group, int32_t n_bins, const double* lo, const double* hi, int32_t n_pairs,
+                           const int32_t* pairs, int32_t n_bins2) {
+  if (!f) return VK_E_ARG;
+  const std::string me = "vk_chain_set_marginals: ";
+  if (f->in_flight) return refused(f, me + "a block begun with vk_chain_begin is awaiting vk_chain_finish");
+  if (n_bins == 0 && !lo && !hi) {
+    chain_drop_marginals(f);
+    f->err.clear();
+    return VK_OK;
+  }
+  if (n_bins < 1 || n_bins > vkmarg::kMaxBins) return refused(f, me + "need 1 <= n_bins <= 1024 (0 with NULL ranges clears)");
+  if (!lo || !hi) return refused(f, me + "NULL argument");
+  if (group < 1 || f->C % group)
+    return refused(f, me + std::to_string(f->C) + " chains are not a whole number of groups of " + std::to_string(group));
+  if (n_pairs < 0 || n_pairs > vkmarg::kMaxPairs) return refused(f, me + "need 0 <= n_pairs <= 45");
+  if (n_pairs > 0 && !pairs) return refused(f, me + "NULL argument");
+  if (n_pairs > 0 && (n_bins2 < 1 || n_bins2 > vkmarg::kMaxBins2)) return refused(f, me + "need 1 <= n_bins2 <= 128");
+  for (int j = 0; j < f->P; ++j)
+    if (!__builtin_isfinite(lo[j]) || !__builtin_isfinite(hi[j]) || !(lo[j] < hi[j]) || !__builtin_isfinite(hi[j] - lo[j]))
+      return refused(f, me + "the range of parameter " + std::to_string(j) + " is not finite with lo < hi");
+  vkmarg::Marginals m{};
+  for (int p = 0; p < n_pairs; ++p) {
+    const int j = pairs[2 * p], k = pairs[2 * p + 1];
+    if (j < 0 || k >= f->P || j >= k)
+      return refused(f, me + "pair " + std::to_string(p) + " (" + std::to_string(j) + ", " + std::to_string(k) + ") needs 0 <= j < k < " +
+                            std::to_string(f->P));
+    for (int q = 0; q < p; ++q)
+      if (m.pair[q][0] == j && m.pair[q][1] == k) return refused(f, me + "pair " + std::to_string(p) + " repeats pair " + std::to_string(q));
+    m.pair[p][0] = j;
+    m.pair[p][1] = k;
+  }
+  m.on = 1;
+  m.group = group;
+  m.n_bins = n_bins;
+  m.n_pairs = n_pairs;
+  m.n_bins2 = n_pairs > 0 ? n_bins2 : 1;
+  for (int j = 0; j < f->P; ++j) {
+    m.a[j] = lo[j];
+    m.b[j] = hi[j];
+    m.inv[j] = vkmarg::inverse_width(m.n_bins, lo[j], hi[j]);
+    m.inv2[j] = vkmarg::inverse_width(m.n_bins2, lo[j], hi[j]);
+  }
+  chain_drop_marginals(f);
+  const size_t problems = (size_t)(f->C / group);
+  const size_t n1 = problems * f->P * ((size_t)n_bins + 2), n2 = problems * n_pairs * ((size_t)m.n_bins2 * m.n_bins2);
+  const size_t bytes = (n1 + n2) * sizeof(unsigned long long);
+  if (hipSetDevice(f->ctx->device) != hipSuccess || hipMalloc(&f->d_marg, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    f->d_marg = nullptr;
+    f->err = me + "cannot allocate " + std::to_string(bytes) + " bytes of device memory";
+    return VK_E_HIP;
+  }
+  // (on the handle's stream, idle now: the step kernels that count run there)
+  if (hipMemsetAsync(f->d_marg, 0, bytes, f->ctx->stream) != hipSuccess || hipStreamSynchronize(f->ctx->stream) != hipSuccess) {
+    (void)hipGetLastError();
+    chain_drop_marginals(f);
+    f->err = me + "hipMemsetAsync failed";
+    return VK_E_HIP;
+  }
+  m.h1 = static_cast<unsigned long long*>(f->d_marg);
+  m.h2 = m.h1 + n1;
+  f->marg = m;
+  f->marg_n1 = n1;
+  f->marg_n2 = n2;
+  f->err.clear();
+  return VK_OK;
+}
+
+int vk_chain_marginals(vk_chain* f, int64_t* h1, int64_t* h2) {
+  if (!f) return VK_E_ARG;
+  if (f->in_flight) return refused(f, "vk_chain_marginals: a block begun with vk_chain_begin is awaiting vk_chain_finish");
+  if (!f->marg.on) return refused(f, "vk_chain_marginals: the handle has no marginals (vk_chain_set_marginals)");
+  VK_SAMPLED_HIP(f, hipSetDevice(f->ctx->device));
+  if (h1 && f->marg_n1) VK_SAMPLED_HIP(f, hipMemcpy(h1, f->marg.h1, f->marg_n1 * sizeof(int64_t), hipMemcpyDeviceToHost));
+  if (h2 && f->marg_n2) VK_SAMPLED_HIP(f, hipMemcpy(h2, f->marg.h2, f->marg_n2 * sizeof(int64_t), hipMemcpyDeviceToHost));
+  f->err.clear();
+  return VK_OK;
+}
+
 void vk_chain_destroy(vk_chain* f) {
   if (!f) return;
   if (f->in_flight) (void)hipStreamSynchronize(f->ctx->stream);
+  chain_drop_marginals(f);
   if (f->d_stretch) {
     (void)hipSetDevice(f->ctx->device);
     (void)hipFree(f->d_stretch);
@@ -647,6 +747,8 @@ int vk_chain_start(vk_chain* f, const double* x0) {
       return refused(f, "vk_chain_start: the start of chain " + std::to_string(c) + " is outside the box");
   VK_SAMPLED_HIP(f, hipSetDevice(ctx->device));
   VK_SAMPLED_HIP(f, hipMemcpy(f->d_x0, x0, (size_t)f->C * f->P * sizeof(double), hipMemcpyHostToDevice));
+  if (f->marg.on)                          // fresh chains: fresh histograms, as the counters and the moment sums (in stream order)
+    VK_SAMPLED_HIP(f, hipMemsetAsync(f->d_marg, 0, (f->marg_n1 + f->marg_n2) * sizeof(unsigned long long), ctx->stream));
   ChainArgs a = chain_args(f);
   rc = sampled_launch(f, vk_chain_init_kernel, a.C, kChainBlock, a);
   if (rc == VK_OK) rc = sampled_evaluate(f, f->C, f->d_res_lnl, f->d_res_chi);
