@@ -554,6 +554,34 @@ int vk_chain_set_marginals(vk_chain* f, int32_t group, int32_t n_bins, const dou
                            const int32_t* pairs, int32_t n_bins2);
 int vk_chain_marginals(vk_chain* f, int64_t* h1, int64_t* h2);
 
+/* ---- Autocorrelation of a chain handle's ensemble series ---------------------------------------------------------------------
+ * How many independent samples stand behind the moment sums and the histograms of a run without a history?  vk_chain_set_autocorr
+ * makes vk_chain_begin and vk_chain_begin_stretch keep, on any handle of the create calls, one series per problem and sampled
+ * parameter - the per-step SUM over the problem's `group` chains (walkers), one value per kept step (per kept sweep, after its
+ * second half) - and that series' lagged products up to lag max_lag - 1 (vk_autocorr.h states the update):
+ *   series value   lane l of 64 starts from +0.0 and adds the chains w = l, l + 64, ... in increasing w; a 64-lane xor butterfly
+ *                  (offsets 32 .. 1, v = v + v_partner) follows.  No division by `group`.
+ *   a_n            0 at the first kept step, whose series value becomes the pivot; s - pivot afterwards
+ *   kept step n    acc[k] += a_n a_{n - k} for 0 <= k <= min(n, L - 1), product and sum each rounded; total += a_n;
+ *                  head[n] = a_n while n < L; ring[n mod L] = a_n
+ * in a small launch of its own behind the step kernel of every kept step (the second half's, of a kept sweep) on the handle's
+ * stream: no host synchronisation, no atomics.  Series (problem r, parameter j) is number r n_params + j.
+ * vk_chain_autocorr copies the state out, between blocks; any pointer may be NULL:
+ *   pivot, total   [n_chains / group][n_params]
+ *   head, ring, acc  [n_chains / group][n_params][max_lag]
+ *   n              kept steps the series hold (the same for every series; the host counts them)
+ * With mu = total / n, H_k the sum of the first k head values and Z_k the sum of the last k ring values, the centred lagged sum
+ * is  n c_k = acc[k] - mu (2 total - H_k - Z_k) + (n - k) mu^2  and rho_k = c_k / c_0 (victor_amd/autocorr.py reads it in extended
+ * precision and applies Sokal's window).
+ * The handle owns the state, (3 max_lag + 2) doubles per series: made and zeroed by vk_chain_set_autocorr (a second call replaces
+ * it), zeroed again by vk_chain_start together with n, kept across blocks, freed by vk_chain_destroy.  max_lag == 0 clears it; a
+ * handle that never had it, or had it cleared, makes the launches and returns the bytes it always did.
+ * Refused (VK_E_ARG, vk_chain_last_error gives the text, the handle stays usable and keeps the state it had): a block begun and
+ * not finished; group < 1 or n_chains % group != 0; max_lag outside 1..1024; vk_chain_autocorr on a handle without it.  Device
+ * memory that cannot be had is reported as vk_chain_create reports it (VK_E_HIP); the handle then has no autocorrelation. */
+int vk_chain_set_autocorr(vk_chain* f, int32_t group, int32_t max_lag);
+int vk_chain_autocorr(vk_chain* f, double* pivot, double* total, double* head, double* ring, double* acc, int64_t* n);
+
 /* Theory multipoles on a caller-supplied s grid: out[n][n_ell][n_s] with the caller's own
  * projection weights w_ell[n_ell][n_mu] on mu[n_mu] (host buffers). */
 int vk_theory_batch(vk_ctx* ctx, const vk_eval_opts* opts, const double* params, int64_t n,

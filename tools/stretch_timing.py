@@ -14,10 +14,16 @@ acceptance, and per parameter the integrated autocorrelation time of the ensembl
 A sweep and a step both cost W likelihood evaluations, so the effective samples of the ensemble mean per likelihood evaluation are
 1 / (W tau).
 
+Cost of ``autocorr=`` (--autocorr parent|this): the 16-realisation stack, stretch, keep_chain=False, W = 10, 64, 1024, wall time
+per sweep as the median of five runs (512 sweeps at W = 1024, 2048 below) after a warm-up.  ``parent``: the plain run alone (for the parent commit's
+checkout, given with --root, in a process of its own); ``this``: ``autocorr`` off and on (max_lag 128) alternating in one process.
+
 Usage: stretch_timing.py [OUT] [--commit SHA] [--sweeps N] [--repeats N] [--walkers 10,64,1024] [--no-mixing] [--only-device W]
+                         [--autocorr parent|this] [--root DIR]
   OUT defaults to profiles/r15/stretch_timing.json.
   --only-device W: just the device route at W walkers per realisation, twice (the workload of a `rocprofv3 --kernel-trace
-  --stats` run)."""
+  --stats` run).
+  --root DIR: import the package and the test cases from another checkout (built there) instead of this one."""
 
 import json
 import os
@@ -27,6 +33,8 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if "--root" in sys.argv:
+    ROOT = os.path.abspath(sys.argv[sys.argv.index("--root") + 1])
 sys.path.insert(0, ROOT)
 
 from tests import cases                                   # noqa: E402
@@ -47,19 +55,6 @@ def warm(rs, seconds=0.5):
     t0 = time.perf_counter()
     while time.perf_counter() - t0 < seconds:
         rs.log_likelihood_pairs(pts, np.arange(1024, dtype=np.int32) % R)
-
-
-def sokal_tau(x, c=5.0):
-    """Integrated autocorrelation time of the series ``x``: tau(M) = 1 + 2 sum_{t <= M} rho_t at the smallest M >= c tau(M)."""
-    x = np.asarray(x, dtype=float) - np.mean(x)
-    n = len(x)
-    f = np.fft.rfft(x, 2 * n)
-    acf = np.fft.irfft(f * np.conj(f))[:n]
-    acf = acf / acf[0]
-    taus = 2.0 * np.cumsum(acf) - 1.0
-    ok = np.arange(n) >= c * taus
-    m = int(np.argmax(ok)) if ok.any() else n - 1
-    return float(taus[m]), m
 
 
 def yardstick(fits, specs, fixed, W, sweeps):
@@ -119,8 +114,42 @@ def time_table(sweeps, repeats, walkers, save):
     return recs
 
 
+def autocorr_cost(which, sweeps, repeats, walkers, save):
+    """Wall time per sweep of the keep-nothing stretch run: plain (``parent``), or with ``autocorr`` off and on (``this``)."""
+    import victor_amd
+    rs = victor_amd.CCFFit(*stack_options()).realisations()
+    variants = [("plain", {})] if which == "parent" else [("off", {}), ("on", {"autocorr": {"max_lag": 128}})]
+    recs = []
+    for W in walkers:
+        kw = dict(walkers=W, seed=0, move="stretch", keep_chain=False)
+        n = sweeps if W >= 1024 else 4 * sweeps                       # (as the marginals table: 2048 sweeps at W = 10 and 64)
+        for _, extra in variants:
+            rs.sample_chains(PARAMS, 64, **kw, **extra)               # code objects, buffers
+        warm(rs)
+        t = {k: [] for k, _ in variants}
+        for _ in range(repeats):
+            for name, extra in variants:
+                t0 = time.perf_counter()
+                ch = rs.sample_chains(PARAMS, n, **kw, **extra)
+                t[name].append(time.perf_counter() - t0)
+        rec = {"walkers": W, "sweeps": n, "wall_s_all": t,
+               "us_per_sweep_median": {k: 1e6 * float(np.median(v)) / n for k, v in t.items()},
+               "spread_over_median": {k: float((max(v) - min(v)) / np.median(v)) for k, v in t.items()}}
+        if which != "parent":
+            med = rec["us_per_sweep_median"]
+            rec["on_minus_off_us_per_sweep"] = med["on"] - med["off"]
+            ac = ch.autocorr                                          # (of the last run: autocorr on)
+            rec["reached_fraction"] = float(ac.reached.mean())
+            rec["tau_median_of_reached"] = float(np.nanmedian(ac.tau)) if ac.reached.any() else None
+        print(json.dumps({k: v for k, v in rec.items() if k != "wall_s_all"}), flush=True)
+        recs.append(rec)
+        save(recs)
+    return recs
+
+
 def mixing(sweeps=4096, burn=512, W=16):
     import victor_amd
+    from victor_amd.autocorr import sokal_tau
     fit = victor_amd.CCFFit(*cases.boss_options("config"))
     out = {}
     for move in ("metropolis", "stretch"):
@@ -153,6 +182,15 @@ def main():
     walkers = [int(w) for w in arg("--walkers", "10,64,1024").split(",")]
     result = {"commit": arg("--commit", "") or None, "config": "BOSS cobaya configuration, d = 4"}
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    if "--autocorr" in sys.argv:
+        which = arg("--autocorr", "this")
+
+        def keep(records):
+            result["autocorr_cost"] = {"data": "16-realisation stack, stretch, keep_chain=False", "library": which, "records": records}
+            with open(out, "w") as fh:
+                json.dump(result, fh, indent=1)
+        autocorr_cost(which, sweeps, repeats, walkers, keep)
+        return
 
     def save(records=None):
         if records is not None:

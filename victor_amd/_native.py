@@ -185,6 +185,9 @@ SYMBOLS = {
     # marginal histograms of a chain handle's kept positions
     "vk_chain_set_marginals": (C.c_int, [_vp, C.c_int32, C.c_int32, _dp, _dp, C.c_int32, C.POINTER(C.c_int32), C.c_int32]),
     "vk_chain_marginals": (C.c_int, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    # the ensemble series of a chain handle and its lagged products
+    "vk_chain_set_autocorr": (C.c_int, [_vp, C.c_int32, C.c_int32]),
+    "vk_chain_autocorr": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int64)]),
     "vk_serve_mailboxes": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, _optp, _vp, C.c_int32, _vp, C.c_double, C.c_int32,
                            C.c_double, C.POINTER(vk_serve_stats)]),
     "vk_timing_enable": (C.c_int, [_vp, C.c_int]),

@@ -339,7 +339,7 @@ class CCFFit(CCFModel):
         return best_fit(self, params, fixed, start, step, xtol, ftol, max_iter, restarts, kwargs, prior=prior)
 
     def sample_chains(self, params, n_steps, walkers=8, seed=0, fixed=None, start=None, scatter=None, proposal=None, burn=0,
-                      thin=1, keep_chain=True, device=True, move="metropolis", stretch_a=2.0, prior=None, marginals=None,
+                      thin=1, keep_chain=True, device=True, move="metropolis", stretch_a=2.0, prior=None, marginals=None, autocorr=None,
                       **kwargs):
         """``walkers`` independent random-walk Metropolis chains of this fit's lnL, stepped on the GPU (``device=True``: the
         step loop runs on the device, ``vk_chain_begin``) or by the NumPy loop that defines them (``device=False``, over
@@ -348,11 +348,14 @@ class CCFFit(CCFModel):
         ensemble instead (``stretch_a``: its scale; ``vk_chain_begin_stretch``).  ``prior``: a
         :class:`victor_amd.priors.GaussianPrior` (or a list of them) multiplied onto the box, honoured by both moves on both
         routes.  ``marginals``: histograms of the kept positions, counted where the chains run, and the medians and credible
-        intervals read from them (``Chains.marginals``, :mod:`victor_amd.marginals`).  Runs on this fit's own context (never
+        intervals read from them (``Chains.marginals``, :mod:`victor_amd.marginals`).  ``autocorr``: integrated
+        autocorrelation times and effective sample sizes from the series of the per-step sum over the chains, accumulated
+        where the chains run (``Chains.autocorr``, :mod:`victor_amd.autocorr`).  Runs on this fit's own context (never
         through the broker)."""
         from .chains import sample_chains
         return sample_chains(self, params, n_steps, walkers, seed, fixed, start, scatter, proposal, burn, thin, keep_chain, device,
-                             kwargs, move=move, stretch_a=stretch_a, prior=prior, marginals=marginals)
+                             kwargs, move=move, stretch_a=stretch_a, prior=prior, marginals=marginals,
+                             autocorr=autocorr)
 
     def realisations(self, simulation_numbers=None):
         """Every simulation realisation of this fit's data file (or the listed ``simulation_numbers``) against one model:

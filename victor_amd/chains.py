@@ -60,6 +60,13 @@ parameter, and of chosen pairs), where the moment sums are accumulated and with 
 kernels (``vk_chain_set_marginals``; integer atomic increments), on the definition route by the NumPy statement of the same binning
 rule - so the two routes give equal counts wherever they give equal positions, with or without a history.  ``Chains.marginals``
 reads medians and equal-tailed intervals from them.
+
+**``autocorr=``** keeps, per problem and sampled parameter, the series of the per-step sum over the problem's W chains (one value
+per kept step or kept sweep) and its lagged products up to ``max_lag`` (:mod:`victor_amd.autocorr`): on the device route by a
+small kernel behind the step kernel of every kept step (``vk_chain_set_autocorr``), on the definition route by the NumPy statement
+of the same update - every rounding fixed, so the two routes give the same bytes wherever they give the same positions, with or
+without a history.  ``Chains.autocorr`` reads integrated autocorrelation times (Sokal's window) and effective sample sizes from it:
+the convergence diagnostic of a run without a history, and of the stretch move, whose ``rhat`` is None by design.
 """
 
 import ctypes as C
@@ -123,11 +130,18 @@ class Chains:
     ``decision_margin`` includes the prior terms.  :meth:`extend` keeps the prior.
 
     ``marginals``: a :class:`victor_amd.marginals.Marginals` of the kept positions' histograms (None without ``marginals=``),
-    rebuilt after every :meth:`extend`, which keeps counting."""
+    rebuilt after every :meth:`extend`, which keeps counting.
+
+    ``autocorr``: a :class:`victor_amd.autocorr.Autocorr` of the ensemble series - ``tau``, ``window``, ``ess``, ``reached`` (R, d),
+    ``acf`` (R, d, max_lag) - (None without ``autocorr=``), rebuilt after every :meth:`extend`, which keeps accumulating."""
 
     def __init__(self, names, specs, fixed, R, W, rng, width, burn, thin, keep_chain, evaluator, device_handle, move="metropolis",
-                 stretch_a=2.0, prior=None, binning=None):
+                 stretch_a=2.0, prior=None, binning=None, lags=None):
         self.names = list(names)
+        self._series = self._lag_c = self.autocorr = None
+        if lags is not None:                              # (max_lag, c) of victor_amd.autocorr.resolve_autocorr
+            from .autocorr import SeriesState
+            self._series, self._lag_c = SeriesState(R, len(self.names), W, lags[0]), lags[1]
         self._prior = prior                               # a victor_amd.priors.ResolvedPrior, or None
         self._binning = binning                           # a victor_amd.marginals.Binning, or None
         self._h1, self._h2 = binning.zeros(R) if binning is not None else (None, None)
@@ -209,6 +223,8 @@ class Chains:
             self._n_kept += 1
             if self._binning is not None:
                 self._binning.add(self._h1, self._h2, x, self.W)
+            if self._series is not None:
+                self._series.add(x)
             if self.keep_chain:
                 for h, a in zip(self._hist, (x, lnl, chi2)):
                     h.append(a.copy())
@@ -338,6 +354,11 @@ class Chains:
                                        N.as_dp(self._pivot), N.as_dp(self._sum1), N.as_dp(self._sum2)), "vk_chain_state")
         if self._binning is not None:
             self._check(lib.vk_chain_marginals(h, self._h1.ctypes.data_as(i64), self._h2.ctypes.data_as(i64)), "vk_chain_marginals")
+        if self._series is not None:
+            q, n = self._series, C.c_int64(0)
+            self._check(lib.vk_chain_autocorr(h, N.as_dp(q.pivot), N.as_dp(q.total), N.as_dp(q.head), N.as_dp(q.ring), N.as_dp(q.acc),
+                                              C.byref(n)), "vk_chain_autocorr")
+            q.n = int(n.value)
 
     def _set_marginals_device(self):
         """Hand the binning to the handle (before ``vk_chain_start``): the W chains of a problem pool."""
@@ -346,6 +367,11 @@ class Chains:
         pairs = q.pairs.ctypes.data_as(C.POINTER(C.c_int32)) if len(q.pairs) else None
         self._check(lib.vk_chain_set_marginals(h, self.W, q.n_bins, N.as_dp(q.a), N.as_dp(q.b), len(q.pairs), pairs, q.n_bins2),
                     "vk_chain_set_marginals")
+
+    def _set_autocorr_device(self):
+        """Hand the series' shape to the handle (before ``vk_chain_start``): the W chains of a problem make one series."""
+        lib, h = self._dev
+        self._check(lib.vk_chain_set_autocorr(h, self.W, self._series.L), "vk_chain_set_autocorr")
 
     def __del__(self):
         dev = getattr(self, "_dev", None)
@@ -388,6 +414,9 @@ class Chains:
         if self._binning is not None:
             from .marginals import Marginals
             self.marginals = Marginals(self._binning, self._h1, self._h2, per_chain.sum(axis=1))
+        if self._series is not None:
+            from .autocorr import Autocorr
+            self.autocorr = Autocorr(self.names, W, self._series.n, self._lag_c, self._series.arrays())
         self.rhat = None
         if self.keep_chain:
             hx, hl, hc = self._hist
@@ -415,7 +444,7 @@ def _draw_start(rng, loc, scale, lo, hi, what):
 
 def sample_chains(fit, params, n_steps, walkers=8, seed=0, fixed=None, start=None, scatter=None, proposal=None, burn=0, thin=1,
                   keep_chain=True, device=True, kwargs=None, realisations=None, evaluate=None, move="metropolis", stretch_a=2.0,
-                  prior=None, marginals=None):
+                  prior=None, marginals=None, autocorr=None):
     """The work of ``CCFFit.sample_chains`` (``realisations=None``: the fit's data vector, R = 1) and
     ``Realisations.sample_chains`` (R = the realisations); see the module docstring.  With ``evaluate`` - a callable taking a dict
     of ``(C,)`` arrays (sampled and fixed parameters) and returning ``lnL (C,)`` or ``(lnL, chi2)`` - in place of ``fit`` only the
@@ -434,7 +463,10 @@ def sample_chains(fit, params, n_steps, walkers=8, seed=0, fixed=None, start=Non
     of every sampled parameter over its prior box) or a dict ``{"bins": int, "range": {name: (a, b)}, "pairs": [(name, name), ...]
     | "all", "bins2d": int}`` - ranges not given are the box, ``bins`` at most 1024, ``bins2d`` (default 32) at most 128, at
     most 45 pairs - for per-problem histograms of the kept positions, counted where the chains run (:mod:`victor_amd.marginals`;
-    ``Chains.marginals``).  Every argument is checked before the first device call.  Returns a :class:`Chains`."""
+    ``Chains.marginals``).  ``autocorr``: None (off), True or a dict ``{"max_lag": int, "c": float}`` (defaults 128 and 5.0;
+    ``max_lag`` at most 1024) for the integrated autocorrelation time and the effective sample size of every problem and
+    parameter, from the series of the per-step sum over the problem's chains, accumulated where the chains run
+    (:mod:`victor_amd.autocorr`; ``Chains.autocorr``).  Every argument is checked before the first device call.  Returns a :class:`Chains`."""
     kwargs = kwargs or {}
     n_steps, walkers, burn, thin = int(n_steps), int(walkers), int(burn), int(thin)
     if n_steps < 0:
@@ -471,6 +503,8 @@ def sample_chains(fit, params, n_steps, walkers=8, seed=0, fixed=None, start=Non
     prior = q.prior(prior, fit)
     from .marginals import resolve_marginals
     binning = resolve_marginals(marginals, "sample_chains", names, lo, hi)
+    from .autocorr import resolve_autocorr
+    lags = resolve_autocorr(autocorr, "sample_chains")
     if evaluate is None:
         fit_options = q.fit_options(fit, kwargs)
     R = len(realisations) if realisations is not None else 1
@@ -537,7 +571,7 @@ def sample_chains(fit, params, n_steps, walkers=8, seed=0, fixed=None, start=Non
         lib, h, refresh = q.create("vk_chain_create", fit, realisations, kwargs, fit_options, batch_of(x0), which)
         handle = (lib, h)
     ch = Chains(names, specs, fixed_out, R, W, rng, width, burn, thin, bool(keep_chain), evaluator, handle, move, stretch_a, prior,
-                binning)
+                binning, lags)
     if handle:
         ch._refresh = refresh                                # (keeps the realisations and the contexts the handle runs on)
         ch._fit = fit                                        # (a joint fit owns the covariance handles the chains read)
@@ -545,6 +579,8 @@ def sample_chains(fit, params, n_steps, walkers=8, seed=0, fixed=None, start=Non
         q.set_prior("vk_chain_set_prior", lib, h, prior)  # (the handle is the Chains' from here on: a refusal destroys it with ch)
     if handle and binning is not None:
         ch._set_marginals_device()
+    if handle and lags is not None:
+        ch._set_autocorr_device()
     if handle:
         ch._check(handle[0].vk_chain_start(handle[1], N.as_dp(N.f64(x0))), "vk_chain_start")
     else:

@@ -22,6 +22,8 @@
 //   vk_prior.h           the Gaussian prior of the sampled parameters that the three step kernels add to lnL (plain C++, likewise)
 //   vk_marginals.h       the binning rule of the marginal histograms the two chain step kernels count kept positions in
 //                        (vk_chain_set_marginals; plain C++, likewise)
+//   vk_kernel_autocorr.h the series kernel behind the step kernel of every kept step: the per-step sum over a problem's chains and
+//                        its lagged products (vk_chain_set_autocorr), over the update of vk_autocorr.h (plain C++, likewise)
 
 #include <hip/hip_runtime.h>
 
@@ -37,6 +39,7 @@
 #include "vk_kernel_fit.h"
 #include "vk_kernel_chain.h"
 #include "vk_kernel_stretch.h"
+#include "vk_kernel_autocorr.h"
 
 using namespace vk;
 using vkh::check_joint;
@@ -519,6 +522,11 @@ struct __attribute__((visibility("hidden"))) vk_chain : Sampled {
   vkmarg::Marginals marg{};
   void* d_marg = nullptr;
   size_t marg_n1 = 0, marg_n2 = 0;         // counts of h1, of h2
+  // the series state pivot | total | head | ring | acc of vk_autocorr.h: one allocation of its own, made (and zeroed) by
+  // vk_chain_set_autocorr; ac.n counts the kept steps enqueued since vk_chain_start
+  vkac::Autocorr ac{};
+  void* d_ac = nullptr;
+  size_t ac_series = 0;                    // C / group problems x P parameters
   std::vector<int> h_which;                // the chains' realisation indices, read back for vk_chain_begin_stretch's check
 
   void stretch_layout(Carve& c) {
@@ -605,6 +613,30 @@ static void chain_drop_marginals(vk_chain* f) {
   f->d_marg = nullptr;
   f->marg = vkmarg::Marginals{};
   f->marg_n1 = f->marg_n2 = 0;
+}
+
+// no series any more: the handle makes the launches it made before it had any
+static void chain_drop_autocorr(vk_chain* f) {
+  if (f->d_ac) {
+    (void)hipSetDevice(f->ctx->device);
+    (void)hipFree(f->d_ac);
+  }
+  f->d_ac = nullptr;
+  f->ac = vkac::Autocorr{};
+  f->ac_series = 0;
+}
+
+// the series kernel behind the step kernel of a kept step (a kept sweep's second half): one wave per (problem, parameter)
+static int chain_series(vk_chain* f) {
+  SeriesArgs s{};
+  s.ac = f->ac;
+  s.x = f->d_x;
+  s.C = f->C;
+  s.d = f->P;
+  hipLaunchKernelGGL(vk_chain_series_kernel, dim3((unsigned)f->ac_series), dim3(kChainBlock), 0, f->ctx->stream, s);
+  VK_SAMPLED_HIP(f, hipGetLastError());
+  f->ac.n += 1;
+  return VK_OK;
 }
 
 extern "C" {
@@ -724,10 +756,75 @@ int vk_chain_marginals(vk_chain* f, int64_t* h1, int64_t* h2) {
   return VK_OK;
 }
 
+// The running autocorrelation of the ensemble series (vk_autocorr.h).  Everything the series kernel indexes with is checked
+// here: the group and the lag count fix the size of the state it addresses.
+int vk_chain_set_autocorr(vk_chain* f, int32_t group, int32_t max_lag) {
+  if (!f) return VK_E_ARG;
+  const std::string me = "vk_chain_set_autocorr: ";
+  if (f->in_flight) return refused(f, me + "a block begun with vk_chain_begin is awaiting vk_chain_finish");
+  if (max_lag == 0) {
+    chain_drop_autocorr(f);
+    f->err.clear();
+    return VK_OK;
+  }
+  if (max_lag < 1 || max_lag > vkac::kMaxLag) return refused(f, me + "need 1 <= max_lag <= 1024 (0 clears)");
+  if (group < 1 || f->C % group)
+    return refused(f, me + std::to_string(f->C) + " chains are not a whole number of groups of " + std::to_string(group));
+  const size_t series = (size_t)(f->C / group) * f->P;
+  const size_t bytes = vkac::state_doubles(series, max_lag) * sizeof(double);
+  void* mem = nullptr;
+  if (hipSetDevice(f->ctx->device) != hipSuccess || hipMalloc(&mem, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    chain_drop_autocorr(f);
+    f->err = me + "cannot allocate " + std::to_string(bytes) + " bytes of device memory";
+    return VK_E_HIP;
+  }
+  chain_drop_autocorr(f);
+  f->d_ac = mem;
+  // (on the handle's stream, idle now: the series kernel runs there)
+  if (hipMemsetAsync(f->d_ac, 0, bytes, f->ctx->stream) != hipSuccess || hipStreamSynchronize(f->ctx->stream) != hipSuccess) {
+    (void)hipGetLastError();
+    chain_drop_autocorr(f);
+    f->err = me + "hipMemsetAsync failed";
+    return VK_E_HIP;
+  }
+  vkac::Autocorr a{};
+  a.on = 1;
+  a.group = group;
+  a.max_lag = max_lag;
+  a.n = 0;
+  a.pivot = static_cast<double*>(f->d_ac);
+  a.total = a.pivot + series;
+  a.head = a.total + series;
+  a.ring = a.head + series * (size_t)max_lag;
+  a.acc = a.ring + series * (size_t)max_lag;
+  f->ac = a;
+  f->ac_series = series;
+  f->err.clear();
+  return VK_OK;
+}
+
+int vk_chain_autocorr(vk_chain* f, double* pivot, double* total, double* head, double* ring, double* acc, int64_t* n) {
+  if (!f) return VK_E_ARG;
+  if (f->in_flight) return refused(f, "vk_chain_autocorr: a block begun with vk_chain_begin is awaiting vk_chain_finish");
+  if (!f->ac.on) return refused(f, "vk_chain_autocorr: the handle has no autocorrelation (vk_chain_set_autocorr)");
+  VK_SAMPLED_HIP(f, hipSetDevice(f->ctx->device));
+  const size_t one = f->ac_series * sizeof(double), lags = one * (size_t)f->ac.max_lag;
+  if (pivot) VK_SAMPLED_HIP(f, hipMemcpy(pivot, f->ac.pivot, one, hipMemcpyDeviceToHost));
+  if (total) VK_SAMPLED_HIP(f, hipMemcpy(total, f->ac.total, one, hipMemcpyDeviceToHost));
+  if (head) VK_SAMPLED_HIP(f, hipMemcpy(head, f->ac.head, lags, hipMemcpyDeviceToHost));
+  if (ring) VK_SAMPLED_HIP(f, hipMemcpy(ring, f->ac.ring, lags, hipMemcpyDeviceToHost));
+  if (acc) VK_SAMPLED_HIP(f, hipMemcpy(acc, f->ac.acc, lags, hipMemcpyDeviceToHost));
+  if (n) *n = (int64_t)f->ac.n;
+  f->err.clear();
+  return VK_OK;
+}
+
 void vk_chain_destroy(vk_chain* f) {
   if (!f) return;
   if (f->in_flight) (void)hipStreamSynchronize(f->ctx->stream);
   chain_drop_marginals(f);
+  chain_drop_autocorr(f);
   if (f->d_stretch) {
     (void)hipSetDevice(f->ctx->device);
     (void)hipFree(f->d_stretch);
@@ -749,6 +846,10 @@ int vk_chain_start(vk_chain* f, const double* x0) {
   VK_SAMPLED_HIP(f, hipMemcpy(f->d_x0, x0, (size_t)f->C * f->P * sizeof(double), hipMemcpyHostToDevice));
   if (f->marg.on)                          // fresh chains: fresh histograms, as the counters and the moment sums (in stream order)
     VK_SAMPLED_HIP(f, hipMemsetAsync(f->d_marg, 0, (f->marg_n1 + f->marg_n2) * sizeof(unsigned long long), ctx->stream));
+  if (f->ac.on) {                          // ... and fresh series
+    VK_SAMPLED_HIP(f, hipMemsetAsync(f->d_ac, 0, vkac::state_doubles(f->ac_series, f->ac.max_lag) * sizeof(double), ctx->stream));
+    f->ac.n = 0;
+  }
   ChainArgs a = chain_args(f);
   rc = sampled_launch(f, vk_chain_init_kernel, a.C, kChainBlock, a);
   if (rc == VK_OK) rc = sampled_evaluate(f, f->C, f->d_res_lnl, f->d_res_chi);
@@ -795,6 +896,7 @@ int vk_chain_begin(vk_chain* f, int32_t n_steps, const double* dz, const double*
     a.hist_chi2 = hist ? f->d_hc + (size_t)slot * C : nullptr;
     if (hist) ++slot;
     rc = sampled_launch(f, vk_chain_step_kernel, a.C, kChainBlock, a);
+    if (rc == VK_OK && kept && f->ac.on) rc = chain_series(f);
   }
   if (rc) return sampled_abort(f, rc);
   f->in_flight = n_steps;
@@ -883,6 +985,7 @@ int vk_chain_begin_stretch(vk_chain* f, int32_t n_steps, int32_t walkers, const 
       if (rc == VK_OK) rc = sampled_evaluate(f, (long long)M, f->d_res_lnl, f->d_res_chi);
       if (rc == VK_OK) rc = sampled_launch(f, vk_stretch_step_kernel, a.M, kChainBlock, a);
     }
+    if (rc == VK_OK && kept && f->ac.on) rc = chain_series(f);     // (behind the second half: all W walkers as the sweep leaves them)
   }
   if (rc) return sampled_abort(f, rc);
   f->in_flight = n_steps;

@@ -514,14 +514,15 @@ class JointFit:
         return best_fit(self, params, fixed, start, step, xtol, ftol, max_iter, restarts, kwargs, prior=prior)
 
     def sample_chains(self, params, n_steps, walkers=8, seed=0, fixed=None, start=None, scatter=None, proposal=None, burn=0,
-                      thin=1, keep_chain=True, device=True, move="metropolis", stretch_a=2.0, prior=None, marginals=None,
+                      thin=1, keep_chain=True, device=True, move="metropolis", stretch_a=2.0, prior=None, marginals=None, autocorr=None,
                       **kwargs):
         """``walkers`` Metropolis chains of the joint lnL, stepped on the GPU (``device=True``) or by the NumPy loop over
         :meth:`log_likelihood_batch` that defines them (``device=False``).  Arguments and result as ``CCFFit.sample_chains``
         (:mod:`victor_amd.chains`), ``move="stretch"`` included; the result keeps this joint fit alive."""
         from .chains import sample_chains
         return sample_chains(self, params, n_steps, walkers, seed, fixed, start, scatter, proposal, burn, thin, keep_chain, device,
-                             kwargs, move=move, stretch_a=stretch_a, prior=prior, marginals=marginals)
+                             kwargs, move=move, stretch_a=stretch_a, prior=prior, marginals=marginals,
+                             autocorr=autocorr)
 
     @property
     def n_data(self):
@@ -571,7 +572,7 @@ class JointRealisations:
                         prior=prior)
 
     def sample_chains(self, params, n_steps, walkers=8, seed=0, fixed=None, start=None, scatter=None, proposal=None, burn=0,
-                      thin=1, keep_chain=True, device=True, move="metropolis", stretch_a=2.0, prior=None, marginals=None,
+                      thin=1, keep_chain=True, device=True, move="metropolis", stretch_a=2.0, prior=None, marginals=None, autocorr=None,
                       **kwargs):
         """``walkers`` Metropolis chains of EVERY joint realisation in lock step, on the GPU (``device=True``) or by the NumPy
         loop over :meth:`log_likelihood_pairs` that defines them (``device=False``).  Arguments and result as
@@ -579,7 +580,8 @@ class JointRealisations:
         of :meth:`best_fit`."""
         from .chains import sample_chains
         return sample_chains(self.joint, params, n_steps, walkers, seed, fixed, start, scatter, proposal, burn, thin, keep_chain,
-                             device, kwargs, realisations=self, move=move, stretch_a=stretch_a, prior=prior, marginals=marginals)
+                             device, kwargs, realisations=self, move=move, stretch_a=stretch_a, prior=prior, marginals=marginals,
+                             autocorr=autocorr)
 
     def _eval(self, params, kwargs, which=None):
         joint = self.joint
