@@ -582,6 +582,41 @@ int vk_chain_marginals(vk_chain* f, int64_t* h1, int64_t* h2);
 int vk_chain_set_autocorr(vk_chain* f, int32_t group, int32_t max_lag);
 int vk_chain_autocorr(vk_chain* f, double* pivot, double* total, double* head, double* ring, double* acc, int64_t* n);
 
+/* ---- Hessians of lnL + ln prior at given points of a best-fit handle: Laplace covariances -----------------------------------
+ * vk_fit_run returns a point per problem and nothing about its uncertainty.  vk_fit_hessian evaluates, on any handle of the
+ * three vk_fit_create calls (before or after vk_fit_run; with the prior of vk_fit_set_prior, if any), one central-difference
+ * stencil per problem - M = vk_hessian_rows(n_params) = 2 n_params^2 + 1 rows - around the point x_p with the steps h_p, and
+ * from its values the Hessian of lnL + ln prior there and its negative inverse, the covariance of the local Gaussian
+ * approximation of the posterior (vk_hessian.h states the stencil and every rounding; victor_amd/laplace.py restates it in
+ * NumPy, bit for bit):
+ *   point m     0: x;  1 + 2 j + s: x +- h_j e_j (s = 0: +);  1 + 2 d + 4 q + c: x_j and x_k displaced, q the pair j < k in the
+ *               order (0,1), (0,2), .., (1,2), .., c = 0..3 the signs (+,+), (+,-), (-,+), (-,-); a displaced coordinate is the
+ *               rounded sum.  Rows are formed on the device as the search forms them (epsilon -> aperp, apar; row sets).
+ *   a           A = -H o (h h^T):  A_jj = ((v0 + v0) - v(+j)) - v(-j),  A_jk = 0.25 ((v(+-) - v(++)) + (v(-+) - v(--)))
+ *   hess, cov   hess_jk = -A_jk / (h_j h_k);  cov_jk = (h_j h_k) B_jk with B = A^-1 through the Cholesky factor of A
+ *   status      VK_HESS_AT_BOUND: some x_j - h_j < lo_j or x_j + h_j > hi_j, or x outside the box - the problem's rows are all
+ *               evaluated at x (the launch shape never depends on the data) and a, hess, cov are NaN;  VK_HESS_NOT_FINITE: a
+ *               value of the stencil is not finite (a, hess, cov NaN);  VK_HESS_NOT_POSDEF: a Cholesky pivot fails > 0 (a and
+ *               hess given, cov NaN);  VK_HESS_OK otherwise - in this precedence.  The caller chooses the steps: the device
+ *               only flags.
+ *   x, h        [n_problems][n_params] each: the points and per-problem steps (> 0)
+ *   values      [n_problems][M] the value of every stencil point: lnL of its row, plus ln prior at the point under a prior
+ *   a, hess, cov  [n_problems][n_params][n_params], symmetric;  lnpost, chi2 [n_problems]: value and chi-square of the centre;
+ *               status [n_problems].  Any output may be NULL.
+ * The R M rows are evaluated in chunks of the handle's largest launch (n_problems S rows, S = max(4, n_params + 1): at most
+ * ceil(M / S) <= 19 evaluations, chunk boundaries inside problems), with the launches vk_fit_run makes for as many rows; the
+ * values and outputs live in an allocation of the call, freed before it returns.  Synchronous; the call owns the context as
+ * vk_fit_run does.  On error the code is returned, vk_fit_last_error gives the text and nothing stays in flight.  Refused
+ * (VK_E_ARG): what vk_fit_run refuses of the context, a NULL x or h, a point that is not finite, a step that is not finite
+ * or <= 0.  A handle that never calls it makes the launches it made before and returns the bytes it returned. */
+#define VK_HESS_OK 0
+#define VK_HESS_AT_BOUND 1
+#define VK_HESS_NOT_FINITE 2
+#define VK_HESS_NOT_POSDEF 3
+int64_t vk_hessian_rows(int32_t n_params);
+int vk_fit_hessian(vk_fit* f, const double* x, const double* h, double* values, double* a, double* hess, double* cov,
+                   double* lnpost, double* chi2, int32_t* status);
+
 /* Theory multipoles on a caller-supplied s grid: out[n][n_ell][n_s] with the caller's own
  * projection weights w_ell[n_ell][n_mu] on mu[n_mu] (host buffers). */
 int vk_theory_batch(vk_ctx* ctx, const vk_eval_opts* opts, const double* params, int64_t n,

@@ -23,6 +23,7 @@ VK_WALK_EPSILON = -1
 ROW_COLUMNS = {"fsigma8": P_FSIGMA8, "sigma_v": P_SIGMAV, "beta": P_BETA, "astar": P_ASTAR, "M": P_M, "Q": P_Q, "bias": P_BIAS,
                "Av": P_AV}
 VK_FIT_CONVERGED, VK_FIT_MAX_ITER, VK_FIT_NO_FINITE_START = 0, 1, 2
+VK_HESS_OK, VK_HESS_AT_BOUND, VK_HESS_NOT_FINITE, VK_HESS_NOT_POSDEF = 0, 1, 2, 3
 
 _dp = C.POINTER(C.c_double)
 
@@ -188,6 +189,9 @@ SYMBOLS = {
     # the ensemble series of a chain handle and its lagged products
     "vk_chain_set_autocorr": (C.c_int, [_vp, C.c_int32, C.c_int32]),
     "vk_chain_autocorr": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int64)]),
+    # the Hessian stencil of a best-fit handle and the Laplace covariance from it
+    "vk_hessian_rows": (C.c_int64, [C.c_int32]),
+    "vk_fit_hessian": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int32)]),
     "vk_serve_mailboxes": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, _optp, _vp, C.c_int32, _vp, C.c_double, C.c_int32,
                            C.c_double, C.POINTER(vk_serve_stats)]),
     "vk_timing_enable": (C.c_int, [_vp, C.c_int]),

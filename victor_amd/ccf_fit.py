@@ -322,7 +322,7 @@ class CCFFit(CCFModel):
         return lnl, chi2
 
     def best_fit(self, params, fixed=None, start=None, step=None, xtol=None, ftol=1e-6, max_iter=None, restarts=1, prior=None,
-                 **kwargs):
+                 covariance=None, **kwargs):
         """Maximum of lnL (the value :meth:`log_likelihood` returns: with uniform priors the MAP point) over the sampled
         parameters of a cobaya ``params`` block, inside their prior box, by a bounded Nelder-Mead search on the GPU
         (:mod:`victor_amd.fitting`).  Sampled: the uniform prior (the box), ``ref.loc`` (the start), ``proposal`` (the initial
@@ -336,7 +336,20 @@ class CCFFit(CCFModel):
         a Gaussian truncated by the box, without a normalisation constant; the search then maximises lnL + ln prior
         (``BestFit.lnpost``).  Runs on this fit's own context (never through the broker)."""
         from .fitting import best_fit
-        return best_fit(self, params, fixed, start, step, xtol, ftol, max_iter, restarts, kwargs, prior=prior)
+        return best_fit(self, params, fixed, start, step, xtol, ftol, max_iter, restarts, kwargs, prior=prior, covariance=covariance)
+
+    def laplace(self, params, at, step=None, fixed=None, prior=None, shrink=8, refine=0, keep_values=False, **kwargs):
+        """The Laplace approximation of the posterior at given points: the Hessian of lnL + ln prior over the sampled
+        parameters of a cobaya ``params`` block by one central-difference stencil per problem on the GPU (``vk_fit_hessian``),
+        its negative inverse as the covariance, and a status per problem (:mod:`victor_amd.laplace`).  ``at``: the
+        :class:`victor_amd.fitting.BestFit` of :meth:`best_fit` or a dict name -> scalar or ``(R,)``; ``step``: name -> scalar or
+        ``(R,)``, default the block's proposal widths; ``fixed``, ``prior``, ``kwargs`` as :meth:`best_fit`; ``shrink``: a step
+        is shrunk towards a face of the box down to ``step / shrink``, beyond which the problem reads ``AT_BOUND``; ``refine``:
+        further passes at half the previous pass's sigma; ``keep_values``: keep the stencil's values.  Returns a
+        :class:`victor_amd.laplace.Laplace`.  ``best_fit(..., covariance=True)`` runs the same stencil on the search's own
+        handle.  Runs on this fit's own context (never through the broker)."""
+        from .laplace import laplace
+        return laplace(self, params, at, step, fixed, prior, shrink, refine, keep_values, kwargs)
 
     def sample_chains(self, params, n_steps, walkers=8, seed=0, fixed=None, start=None, scatter=None, proposal=None, burn=0,
                       thin=1, keep_chain=True, device=True, move="metropolis", stretch_a=2.0, prior=None, marginals=None, autocorr=None,

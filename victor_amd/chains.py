@@ -150,6 +150,7 @@ class Chains:
         self._specs, self.fixed = specs, fixed
         self.R, self.W = R, W
         self._rng, self._width = rng, width
+        self._factor = None                               # (C, d, d) proposal factors of a Laplace proposal, or None: the widths
         self.burn, self.thin, self.keep_chain = burn, thin, keep_chain
         self._evaluate = evaluator
         self._dev = device_handle
@@ -168,7 +169,10 @@ class Chains:
         if self.move == "stretch":
             return self._draw_block_stretch()
         C_, d = self.R * self.W, len(self.names)
-        dz = self._width * self._rng.standard_normal((BLOCK, C_, d))
+        if self._factor is None:
+            dz = self._width * self._rng.standard_normal((BLOCK, C_, d))
+        else:                                             # correlated proposals: chain c draws dz = F_(c // W) normal(d)
+            dz = np.einsum("cjk,tck->tcj", self._factor, self._rng.standard_normal((BLOCK, C_, d)))
         logu = np.log(self._rng.random((BLOCK, C_)))
         return dz, logu
 
@@ -454,7 +458,10 @@ def sample_chains(fit, params, n_steps, walkers=8, seed=0, fixed=None, start=Non
     ``walkers``: chains per problem; ``start``: None (each chain drawn from the ``ref`` distribution), a
     :class:`victor_amd.fitting.BestFit` or a dict name -> scalar or ``(R,)`` array: every chain of problem i starts at
     ``start_i + scatter * normal`` (``scatter``: name -> scalar, default the proposal widths; 0 starts every chain at the point
-    itself), redrawn until inside the box; ``proposal``: name -> width overrides.  ``move``: "metropolis" (the default) or
+    itself), redrawn until inside the box; ``proposal``: name -> width overrides, or a :class:`victor_amd.laplace.Laplace` (or
+    a ``BestFit`` carrying one, ``best_fit(..., covariance=True)``) of the same sampled parameters and problems for correlated
+    proposals: the increments of the chains of problem r are ``(2.38 / sqrt(d)) chol(cov_r) normal(d)``, problems whose status
+    is not OK keep the widths; the increments stay the caller's in the ABI, so both routes take them alike.  ``move``: "metropolis" (the default) or
     "stretch" (module docstring): ``walkers`` must then be even and at least 2 (d + 1), ``stretch_a`` > 1 is the move's scale
     (z lies in [1 / a, a]), ``proposal`` is refused (the move has no widths), ``scatter`` keeps its default but must be > 0 in
     every parameter (an ensemble that starts collapsed onto a point, or into a plane, never leaves it), and the result's
@@ -514,6 +521,19 @@ def sample_chains(fit, params, n_steps, walkers=8, seed=0, fixed=None, start=Non
         raise InputError(f"sample_chains: {R} problems x {W} walkers = {n_chains} chains: at most {MAX_CHAINS}")
     if stretch and (W % 2 or W < 2 * (d + 1)):
         raise InputError(f"sample_chains: the stretch move needs an even number of walkers, at least 2 (n_params + 1) = {2 * (d + 1)}")
+    lap = getattr(proposal, "laplace", None) if hasattr(proposal, "n_evals") else proposal     # (a BestFit carries its Laplace)
+    if proposal is not None and not isinstance(proposal, dict):
+        if lap is None or not (hasattr(lap, "proposal_factors") and hasattr(lap, "cov")):
+            raise InputError("sample_chains: proposal must be a dict name -> width, a Laplace, or a BestFit of "
+                             "best_fit(..., covariance=True)")
+        if list(lap.names) != list(names):
+            raise InputError(f"sample_chains: the proposal's Laplace holds the parameters {list(lap.names)}, the chains sample "
+                             f"{list(names)}")
+        if len(lap) != R:
+            raise InputError(f"sample_chains: the proposal's Laplace holds {len(lap)} problems, the chains run {R}")
+        proposal = None
+    else:
+        lap = None
     width = q.per_param("proposal", proposal, [s.proposal for s in specs])
     if not stretch and np.any(~(width > 0)):
         raise InputError(f"sample_chains: every proposal width must be > 0 ({dict(zip(names, width.tolist()))})")
@@ -572,6 +592,8 @@ def sample_chains(fit, params, n_steps, walkers=8, seed=0, fixed=None, start=Non
         handle = (lib, h)
     ch = Chains(names, specs, fixed_out, R, W, rng, width, burn, thin, bool(keep_chain), evaluator, handle, move, stretch_a, prior,
                 binning, lags)
+    if lap is not None:
+        ch._factor = np.repeat(lap.proposal_factors(width), W, axis=0)
     if handle:
         ch._refresh = refresh                                # (keeps the realisations and the contexts the handle runs on)
         ch._fit = fit                                        # (a joint fit owns the covariance handles the chains read)

@@ -24,6 +24,9 @@
 //                        (vk_chain_set_marginals; plain C++, likewise)
 //   vk_kernel_autocorr.h the series kernel behind the step kernel of every kept step: the per-step sum over a problem's chains and
 //                        its lagged products (vk_chain_set_autocorr), over the update of vk_autocorr.h (plain C++, likewise)
+//   vk_kernel_hessian.h  the central-difference stencil of vk_fit_hessian on a best-fit handle: a rows kernel, one thread per
+//                        stencil row, and an assemble kernel, one wave per problem, over the statistic of vk_hessian.h (plain
+//                        C++, likewise)
 
 #include <hip/hip_runtime.h>
 
@@ -40,6 +43,7 @@
 #include "vk_kernel_chain.h"
 #include "vk_kernel_stretch.h"
 #include "vk_kernel_autocorr.h"
+#include "vk_kernel_hessian.h"
 
 using namespace vk;
 using vkh::check_joint;
@@ -494,6 +498,129 @@ int vk_fit_run(vk_fit* f, const double* x0, const double* step, const double* xt
   }
   f->err.clear();
   return VK_OK;
+}
+
+}  // extern "C"
+
+// ---- Hessians at given points: one central-difference stencil per problem (include/victor_hip.h, vk_kernel_hessian.h) --------
+// The R M stencil rows are evaluated in chunks of rows_max consecutive global rows - the pending-row buffers, the workspace and
+// par_stride() stay what the search uses, chunk boundaries fall inside problems - each chunk a rows kernel, sampled_evaluate
+// (the launches fit_loop makes) and two copies of its results into the call's own [R M] arrays; one assemble kernel follows.
+// Everything the call needs beyond the handle lives in one allocation of the call.
+struct HessMem {
+  double *x = nullptr, *h = nullptr, *values = nullptr, *chis = nullptr, *a = nullptr, *hess = nullptr, *cov = nullptr;
+  double *lnpost = nullptr, *chi2 = nullptr;
+  int* status = nullptr;
+  void layout(Carve& c, size_t R, size_t d, size_t M) {
+    c.take(x, R * d);
+    c.take(h, R * d);
+    c.take(values, R * M);
+    c.take(chis, R * M);
+    c.take(a, R * d * d);
+    c.take(hess, R * d * d);
+    c.take(cov, R * d * d);
+    c.take(lnpost, R);
+    c.take(chi2, R);
+    c.take(status, R);
+  }
+};
+
+static int hessian_run(vk_fit* f, const HessMem& m, const double* x, const double* h, double* values, double* a, double* hess,
+                       double* cov, double* lnpost, double* chi2, int32_t* status) {
+  vk_ctx* ctx = f->ctx;
+  const size_t R = f->R, d = f->P, M = (size_t)vkhess::n_points(f->P);
+  VK_SAMPLED_HIP(f, hipMemcpyAsync(m.x, x, R * d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  VK_SAMPLED_HIP(f, hipMemcpyAsync(m.h, h, R * d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  HessArgs q{};
+  q.d = (int)d;
+  q.M = (int)M;
+  q.R = (int)R;
+  for (size_t j = 0; j < d; ++j) {
+    q.lo[j] = f->lo[j];
+    q.hi[j] = f->hi[j];
+  }
+  q.x = m.x;
+  q.h = m.h;
+  q.base = f->d_base;
+  q.rows = f->d_rows;
+  q.row_which = f->real ? f->d_row_which : nullptr;
+  q.which = f->real ? f->d_which : nullptr;
+  for (int j = 0; j < vkhess::kMaxP; ++j) q.col[j] = f->col[j];
+  q.alpha = f->alpha;
+  q.blocks = f->row_sets(R);
+  q.prior = f->prior;
+  q.values = m.values;
+  q.chis = m.chis;
+  q.a = m.a;
+  q.hess = m.hess;
+  q.cov = m.cov;
+  q.lnpost = m.lnpost;
+  q.chi2 = m.chi2;
+  q.status = m.status;
+  const long long total = (long long)(R * M), chunk = (long long)f->rows_max;
+  for (long long g0 = 0; g0 < total; g0 += chunk) {
+    const long long n = std::min(chunk, total - g0);
+    q.g0 = g0;
+    q.n = n;
+    int rc = sampled_launch(f, vk_hess_rows_kernel, (int)n, kHessBlock, q);
+    if (rc == VK_OK) rc = sampled_evaluate(f, n, f->d_lnl, f->d_chi);
+    if (rc) return rc;
+    VK_SAMPLED_HIP(f, hipMemcpyAsync(m.values + g0, f->d_lnl, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    VK_SAMPLED_HIP(f, hipMemcpyAsync(m.chis + g0, f->d_chi, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+  }
+  hipLaunchKernelGGL(vk_hess_assemble_kernel, dim3((unsigned)R), dim3(kHessBlock), 0, ctx->stream, q);
+  VK_SAMPLED_HIP(f, hipGetLastError());
+  auto home = [&](void* dst, const void* src, size_t bytes) {
+    return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess;
+  };
+  VK_SAMPLED_HIP(f, home(values, m.values, R * M * sizeof(double)));
+  VK_SAMPLED_HIP(f, home(a, m.a, R * d * d * sizeof(double)));
+  VK_SAMPLED_HIP(f, home(hess, m.hess, R * d * d * sizeof(double)));
+  VK_SAMPLED_HIP(f, home(cov, m.cov, R * d * d * sizeof(double)));
+  VK_SAMPLED_HIP(f, home(lnpost, m.lnpost, R * sizeof(double)));
+  VK_SAMPLED_HIP(f, home(chi2, m.chi2, R * sizeof(double)));
+  VK_SAMPLED_HIP(f, home(status, m.status, R * sizeof(int)));
+  VK_SAMPLED_HIP(f, hipStreamSynchronize(ctx->stream));
+  return VK_OK;
+}
+
+extern "C" {
+
+int64_t vk_hessian_rows(int32_t n_params) {
+  return n_params >= 1 && n_params <= kSampledMaxP ? (int64_t)vkhess::n_points(n_params) : 0;
+}
+
+int vk_fit_hessian(vk_fit* f, const double* x, const double* h, double* values, double* a, double* hess, double* cov, double* lnpost,
+                   double* chi2, int32_t* status) {
+  if (!f) return VK_E_ARG;
+  if (!x || !h) return refused(f, "vk_fit_hessian: NULL argument");
+  int rc = sampled_ready(f, "vk_fit_hessian", "problem", false);
+  if (rc) return rc;
+  const size_t R = f->R, d = f->P;
+  for (size_t p = 0; p < R; ++p)
+    for (size_t j = 0; j < d; ++j) {
+      if (!__builtin_isfinite(x[p * d + j]))
+        return refused(f, "vk_fit_hessian: the point of problem " + std::to_string(p) + " is not finite in parameter " + std::to_string(j));
+      if (!(h[p * d + j] > 0) || !__builtin_isfinite(h[p * d + j]))
+        return refused(f, "vk_fit_hessian: problem " + std::to_string(p) + ", parameter " + std::to_string(j) + " needs a finite step > 0");
+    }
+  VK_SAMPLED_HIP(f, hipSetDevice(f->ctx->device));
+  HessMem m;
+  Carve count;
+  m.layout(count, R, d, (size_t)vkhess::n_points(f->P));
+  void* mem = nullptr;
+  if (hipMalloc(&mem, count.bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    f->err = "vk_fit_hessian: cannot allocate " + std::to_string(count.bytes) + " bytes of device memory";
+    return VK_E_HIP;
+  }
+  Carve carve{static_cast<char*>(mem)};
+  m.layout(carve, R, d, (size_t)vkhess::n_points(f->P));
+  rc = hessian_run(f, m, x, h, values, a, hess, cov, lnpost, chi2, status);
+  if (rc != VK_OK) rc = sampled_abort(f, rc);
+  (void)hipFree(mem);
+  if (rc == VK_OK) f->err.clear();
+  return rc;
 }
 
 }  // extern "C"

@@ -35,8 +35,12 @@ class BestFit:
     ``lnpost``: what the device maximised, lnL + ln prior at the best vertex, in the device's bits; ``lnprior``: the prior
     evaluated on the host at ``x`` (:mod:`victor_amd.priors`: no normalisation constant).  Without a prior ``lnprior`` is 0 and
     ``lnpost`` is ``lnl``.  With one, ``lnl`` is ``lnpost - lnprior``: the log-likelihood at ``x`` up to that one subtraction's
-    rounding."""
+    rounding.
 
+    With ``best_fit(..., covariance=...)``: ``laplace``, the :class:`victor_amd.laplace.Laplace` of the best vertices (the
+    Hessian stencil run on the search's own handle), and ``cov`` (R, d, d), ``sigma`` (R, d), views of it; None otherwise."""
+
+    laplace = cov = sigma = None
     CONVERGED, MAX_ITER, NO_FINITE_START = N.VK_FIT_CONVERGED, N.VK_FIT_MAX_ITER, N.VK_FIT_NO_FINITE_START
 
     def __init__(self, names, x, fixed, lnl, chi2, status, n_iter, n_evals, lnprior=None):
@@ -202,11 +206,14 @@ class _Sampled:
 
 
 def best_fit(fit, params, fixed=None, start=None, step=None, xtol=None, ftol=1e-6, max_iter=None, restarts=1, kwargs=None,
-             realisations=None, prior=None):
+             realisations=None, prior=None, covariance=None):
     """The work of ``CCFFit.best_fit`` (``realisations=None``: against the fit's data vector) and ``Realisations.best_fit``;
     with a ``JointFit`` for ``fit`` (and its ``JointRealisations``), of theirs.  ``prior``: a
     :class:`victor_amd.priors.GaussianPrior` (or a list of them) multiplied onto the box; the search then maximises
-    lnL + ln prior (``vk_fit_set_prior``).  Every argument is checked before the first device call."""
+    lnL + ln prior (``vk_fit_set_prior``).  ``covariance``: True, or a dict ``{"step", "shrink", "refine", "keep_values"}`` as
+    :func:`victor_amd.laplace.laplace` takes them: the Hessian stencil (``vk_fit_hessian``) runs at the best vertices on the
+    search's own handle before it is destroyed, and the result carries ``laplace``, ``cov`` and ``sigma``.  Every argument is
+    checked before the first device call."""
     kwargs = kwargs or {}
     q = _Sampled("best_fit", "fitted", params, fixed)
     names, fixed_all, d = q.names, q.fixed_all, len(q.names)
@@ -234,6 +241,8 @@ def best_fit(fit, params, fixed=None, start=None, step=None, xtol=None, ftol=1e-
     max_iter = 200 * d if max_iter is None else int(max_iter)
     if max_iter < 1 or int(restarts) < 0:
         raise InputError("best_fit: need max_iter >= 1 and restarts >= 0")
+    from .laplace import resolve_covariance
+    want_cov = resolve_covariance(covariance, q, R)
     batch = dict(fixed_all)
     batch.update({n: np.ascontiguousarray(x0[:, j]) for j, n in enumerate(names)})
 
@@ -253,7 +262,15 @@ def best_fit(fit, params, fixed=None, start=None, step=None, xtol=None, ftol=1e-
         if rc != 0:
             msg = (lib.vk_fit_last_error(h) or b"").decode() or f"vk_fit_run failed ({rc})"
             raise (InputError if rc == -1 else N.NativeError)(msg)
+        fixed_out = {k: _per_problem(k, v, R) for k, v in fixed_all.items()}
+        lap = None
+        if want_cov is not None:
+            from .laplace import device_pass, run_passes
+            requested, shrink, refine, keep_values = want_cov
+            lap = run_passes(q, x, requested, shrink, refine, keep_values, prior, fixed_out, device_pass(lib, h, x, R, d))
     finally:
         lib.vk_fit_destroy(h)
-    fixed_out = {k: _per_problem(k, v, R) for k, v in fixed_all.items()}
-    return BestFit(names, x, fixed_out, lnl, chi2, status, n_iter, n_evals, None if prior is None else prior.lnprior(x))
+    bf = BestFit(names, x, fixed_out, lnl, chi2, status, n_iter, n_evals, None if prior is None else prior.lnprior(x))
+    if lap is not None:
+        bf.laplace, bf.cov, bf.sigma = lap, lap.cov, lap.sigma
+    return bf

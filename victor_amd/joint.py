@@ -504,14 +504,21 @@ class JointFit:
         return lead._lib, h, refresh
 
     def best_fit(self, params, fixed=None, start=None, step=None, xtol=None, ftol=1e-6, max_iter=None, restarts=1, prior=None,
-                 **kwargs):
+                 covariance=None, **kwargs):
         """Maximum of the joint lnL (the value :meth:`log_likelihood_batch` returns) over the sampled parameters of a cobaya
         ``params`` block - one parameter vector for all blocks, or with ``"name@q"`` entries (:func:`per_block`) a value of
         that parameter per block, at most 10 sampled values in all - by the bounded Nelder-Mead search of ``CCFFit.best_fit`` on
         the GPU, block-diagonal or under the joint covariance.  Arguments and result as ``CCFFit.best_fit``: arrays in
         ``fixed`` give a profile; a ``prior`` (:class:`victor_amd.priors.GaussianPrior`) may name ``"name@q"`` parameters."""
         from .fitting import best_fit
-        return best_fit(self, params, fixed, start, step, xtol, ftol, max_iter, restarts, kwargs, prior=prior)
+        return best_fit(self, params, fixed, start, step, xtol, ftol, max_iter, restarts, kwargs, prior=prior, covariance=covariance)
+
+    def laplace(self, params, at, step=None, fixed=None, prior=None, shrink=8, refine=0, keep_values=False, **kwargs):
+        """The Laplace approximation of the joint posterior at given points: the Hessian stencil of ``CCFFit.laplace``
+        over the joint lnL, block-diagonal or under the joint covariance, ``"name@q"`` parameters included (at most 10 sampled
+        values in all).  Arguments and result as ``CCFFit.laplace``."""
+        from .laplace import laplace
+        return laplace(self, params, at, step, fixed, prior, shrink, refine, keep_values, kwargs)
 
     def sample_chains(self, params, n_steps, walkers=8, seed=0, fixed=None, start=None, scatter=None, proposal=None, burn=0,
                       thin=1, keep_chain=True, device=True, move="metropolis", stretch_a=2.0, prior=None, marginals=None, autocorr=None,
@@ -564,12 +571,18 @@ class JointRealisations:
             r._upload(eng)
 
     def best_fit(self, params, fixed=None, start=None, step=None, xtol=None, ftol=1e-6, max_iter=None, restarts=1, prior=None,
-                 **kwargs):
+                 covariance=None, **kwargs):
         """Best-fit point of every joint realisation: problem i maximises the joint lnL against realisation ``numbers[i]`` of
         every block, all of them in one run on the GPU.  Arguments as ``JointFit.best_fit``; ``fixed`` values must be scalars."""
         from .fitting import best_fit
         return best_fit(self.joint, params, fixed, start, step, xtol, ftol, max_iter, restarts, kwargs, realisations=self,
-                        prior=prior)
+                        prior=prior, covariance=covariance)
+
+    def laplace(self, params, at, step=None, fixed=None, prior=None, shrink=8, refine=0, keep_values=False, **kwargs):
+        """The Laplace approximation of every joint realisation's posterior at its own point, all of them in one call on
+        the GPU.  Arguments and result as ``JointFit.laplace``; ``fixed`` values must be scalars."""
+        from .laplace import laplace
+        return laplace(self.joint, params, at, step, fixed, prior, shrink, refine, keep_values, kwargs, realisations=self)
 
     def sample_chains(self, params, n_steps, walkers=8, seed=0, fixed=None, start=None, scatter=None, proposal=None, burn=0,
                       thin=1, keep_chain=True, device=True, move="metropolis", stretch_a=2.0, prior=None, marginals=None, autocorr=None,

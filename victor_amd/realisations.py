@@ -137,12 +137,20 @@ class Realisations:
         return self.log_likelihood(params, **dict(kwargs, beta_interpolation="datavector"))[1]
 
     def best_fit(self, params, fixed=None, start=None, step=None, xtol=None, ftol=1e-6, max_iter=None, restarts=1, prior=None,
-                 **kwargs):
+                 covariance=None, **kwargs):
         """Best-fit point of every realisation: problem i maximises lnL against realisation ``numbers[i]``, all of them in one
         run on the GPU.  Arguments as ``CCFFit.best_fit`` (``prior``: one Gaussian prior for all realisations); ``fixed``
         values must be scalars here."""
         from .fitting import best_fit
-        return best_fit(self.fit, params, fixed, start, step, xtol, ftol, max_iter, restarts, kwargs, realisations=self, prior=prior)
+        return best_fit(self.fit, params, fixed, start, step, xtol, ftol, max_iter, restarts, kwargs, realisations=self, prior=prior,
+                        covariance=covariance)
+
+    def laplace(self, params, at, step=None, fixed=None, prior=None, shrink=8, refine=0, keep_values=False, **kwargs):
+        """The Laplace approximation of EVERY realisation's posterior at its own point (``at``: the ``BestFit`` of
+        :meth:`best_fit`, or a dict name -> scalar or one value per realisation): all R stencils in one call on the GPU.
+        Arguments and result as ``CCFFit.laplace``; ``fixed`` values must be scalars here."""
+        from .laplace import laplace
+        return laplace(self.fit, params, at, step, fixed, prior, shrink, refine, keep_values, kwargs, realisations=self)
 
     def sample_chains(self, params, n_steps, walkers=8, seed=0, fixed=None, start=None, scatter=None, proposal=None, burn=0,
                       thin=1, keep_chain=True, device=True, move="metropolis", stretch_a=2.0, prior=None, marginals=None, autocorr=None,
