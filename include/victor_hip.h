@@ -582,6 +582,46 @@ int vk_chain_marginals(vk_chain* f, int64_t* h1, int64_t* h2);
 int vk_chain_set_autocorr(vk_chain* f, int32_t group, int32_t max_lag);
 int vk_chain_autocorr(vk_chain* f, double* pivot, double* total, double* head, double* ring, double* acc, int64_t* n);
 
+/* ---- Replica exchange on a chain handle: tempered chains and the sums of thermodynamic integration ---------------------------
+ * vk_chain_set_tempering reads the n_chains chains of any handle of the three chain create calls as n_chains / (rungs walkers)
+ * problems of `rungs` inverse temperatures 1 = betas[0] > betas[1] > ... > betas[rungs - 1] >= 0 and `walkers` ladders each: chain
+ * c = (r rungs + k) walkers + w is problem r, rung k, walker w.  A `group` of `walkers` (vk_chain_set_marginals,
+ * vk_chain_set_autocorr) then sees every (r, k) as a problem.  vk_chain_begin_tempered is vk_chain_begin with three changes
+ * (vk_temper_step.h states them, victor_amd/tempering.py is the definition):
+ *   the step       a chain of rung k decides on  post = betas[k] * lnL (+ ln prior), product and sum each rounded:
+ *                  accept <=> the proposal is inside the box and logu < post' - post (a NaN rejects).  At beta = 1 this is the
+ *                  decision of vk_chain_begin bit for bit.  0 * -inf is NaN: at beta = 0 a proposal whose row failed is rejected,
+ *                  and a chain whose stored lnL is -inf never moves by a step.  State, history and chi2 keep the log-likelihood.
+ *   the energy     at every kept step, after the decision and before any swap, a chain whose stored lnL is finite adds it to its
+ *                  sums: n_e += 1; the first such value becomes pivot_e; a = lnL - pivot_e; e1 += a; e2 += a * a (the product
+ *                  rounded before the sum).  ln Z = the integral over beta of the rungs' mean lnL follows on the host.
+ *   the swap       with swap_every > 0 a swap event follows the step with index s (first_step + its place in the block) when
+ *                  (s + 1) % swap_every == 0; event e = (s + 1) / swap_every - 1 pairs rung k with rung k + 1, walker for walker
+ *                  inside a problem, for every k = e % 2, e % 2 + 2, ... with k + 1 < rungs:
+ *                  accept <=> logs < (betas[k] - betas[k + 1]) * (lnL_(k+1) - lnL_k), one subtraction each, one product, a NaN
+ *                  rejects; logs is the entry of the lower rung's chain in the step's row of `logs`.  On accept the sampled
+ *                  values, lnL and chi2 are exchanged; base rows, temperatures, pivots, moment sums, energy sums, histograms
+ *                  and counters stay with the rung.  The lower chain counts n_swap_try and n_swap_acc.
+ * logs is [n_steps][n_chains] like logu (the rows of steps without an event are not read; NULL is allowed with swap_every == 0);
+ * everything else - up to 64 steps, asynchronous, first_step, burn, thin, want_history, n_kept, vk_chain_finish - is the contract
+ * of vk_chain_begin.  A history slot holds the state after the decision and before the swap.  Launches: per step the evaluation
+ * and the tempered step kernel; on a swap step that kernel writes no next rows, the swap kernel (one thread per candidate pair, no
+ * atomics) and the propose kernel follow it.  vk_chain_tempering copies the sums out, between blocks; any pointer may be NULL;
+ * every output is [n_chains].
+ * The handle owns the arrays: made and zeroed by vk_chain_set_tempering (a second call replaces them), zeroed again by
+ * vk_chain_start, kept across blocks, freed by vk_chain_destroy.  rungs == 0 clears the tempering; a handle that never had it, or
+ * had it cleared, makes the launches and returns the bytes it always did.  vk_chain_begin on a handle with tempering steps every
+ * chain at beta = 1 and swaps nothing.
+ * Refused (VK_E_ARG, vk_chain_last_error gives the text, the handle stays usable and keeps what it had): a block begun and not
+ * finished; rungs < 0, walkers < 1 or n_chains % (rungs walkers) != 0; betas[0] != 1; betas not strictly decreasing; a beta below
+ * 0 or not finite; chains of one problem on different realisations; swap_every < 0; vk_chain_begin_tempered or
+ * vk_chain_tempering on a handle without tempering.  Device memory that cannot be had is reported as vk_chain_create reports it
+ * (VK_E_HIP); the handle then has no tempering. */
+int vk_chain_set_tempering(vk_chain* f, int32_t rungs, int32_t walkers, const double* betas);
+int vk_chain_begin_tempered(vk_chain* f, int32_t n_steps, const double* dz, const double* logu, const double* logs, int64_t swap_every,
+                            int64_t first_step, int64_t burn, int64_t thin, int32_t want_history, int32_t* n_kept);
+int vk_chain_tempering(vk_chain* f, double* pivot_e, double* e1, double* e2, int64_t* n_e, int64_t* n_swap_try, int64_t* n_swap_acc);
+
 /* ---- Hessians of lnL + ln prior at given points of a best-fit handle: Laplace covariances -----------------------------------
  * vk_fit_run returns a point per problem and nothing about its uncertainty.  vk_fit_hessian evaluates, on any handle of the
  * three vk_fit_create calls (before or after vk_fit_run; with the prior of vk_fit_set_prior, if any), one central-difference

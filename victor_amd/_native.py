@@ -189,6 +189,11 @@ SYMBOLS = {
     # the ensemble series of a chain handle and its lagged products
     "vk_chain_set_autocorr": (C.c_int, [_vp, C.c_int32, C.c_int32]),
     "vk_chain_autocorr": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int64)]),
+    # replica exchange on a chain handle: tempered steps, swaps and the energy sums of thermodynamic integration
+    "vk_chain_set_tempering": (C.c_int, [_vp, C.c_int32, C.c_int32, _dp]),
+    "vk_chain_begin_tempered": (C.c_int, [_vp, C.c_int32, _dp, _dp, _dp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
+                                          C.POINTER(C.c_int32)]),
+    "vk_chain_tempering": (C.c_int, [_vp, _dp, _dp, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     # the Hessian stencil of a best-fit handle and the Laplace covariance from it
     "vk_hessian_rows": (C.c_int64, [C.c_int32]),
     "vk_fit_hessian": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int32)]),

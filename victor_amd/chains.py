@@ -67,6 +67,12 @@ small kernel behind the step kernel of every kept step (``vk_chain_set_autocorr`
 of the same update - every rounding fixed, so the two routes give the same bytes wherever they give the same positions, with or
 without a history.  ``Chains.autocorr`` reads integrated autocorrelation times (Sokal's window) and effective sample sizes from it:
 the convergence diagnostic of a run without a history, and of the stretch move, whose ``rhat`` is None by design.
+
+**``temper=``** runs K copies of every problem at inverse temperatures from 1 down to 0 and lets neighbouring temperatures
+exchange states (replica exchange; :mod:`victor_amd.tempering` states the step, the energy sums and the swap, the device route
+reproduces them bit for bit through ``vk_chain_begin_tempered``): chain ``c = (r K + k) W + w`` is problem r, rung k, walker w, so
+everything above that groups W chains sees every (r, k) as a problem, and the public fields of ``Chains`` are the cold rung k = 0.
+``Chains.tempering`` carries every rung's state and the evidence by thermodynamic integration.  Metropolis move only.
 """
 
 import ctypes as C
@@ -133,23 +139,34 @@ class Chains:
     rebuilt after every :meth:`extend`, which keeps counting.
 
     ``autocorr``: a :class:`victor_amd.autocorr.Autocorr` of the ensemble series - ``tau``, ``window``, ``ess``, ``reached`` (R, d),
-    ``acf`` (R, d, max_lag) - (None without ``autocorr=``), rebuilt after every :meth:`extend`, which keeps accumulating."""
+    ``acf`` (R, d, max_lag) - (None without ``autocorr=``), rebuilt after every :meth:`extend`, which keeps accumulating.
+
+    ``tempering``: a :class:`victor_amd.tempering.Tempering` (None without ``temper=``) - the ladder, every rung's state and
+    history, the rungs' mean and variance of lnL, swap acceptances and ``ln_evidence`` -, rebuilt after every :meth:`extend`, which
+    continues the ladder (the swap-event count and the swap levels' stream run over the chains' whole life).  Every (R, W, ...)
+    field above is then the cold rung's."""
 
     def __init__(self, names, specs, fixed, R, W, rng, width, burn, thin, keep_chain, evaluator, device_handle, move="metropolis",
-                 stretch_a=2.0, prior=None, binning=None, lags=None):
+                 stretch_a=2.0, prior=None, binning=None, lags=None, temper=None):
         self.names = list(names)
         self._series = self._lag_c = self.autocorr = None
+        self._temper = temper                             # a victor_amd.tempering.TemperState, or None
+        self._K = temper.K if temper is not None else 1
+        self._RK = R * self._K                            # the "problems" of the group = W features: every (problem, rung)
+        self.tempering = None
         if lags is not None:                              # (max_lag, c) of victor_amd.autocorr.resolve_autocorr
             from .autocorr import SeriesState
-            self._series, self._lag_c = SeriesState(R, len(self.names), W, lags[0]), lags[1]
+            self._series, self._lag_c = SeriesState(self._RK, len(self.names), W, lags[0]), lags[1]
         self._prior = prior                               # a victor_amd.priors.ResolvedPrior, or None
         self._binning = binning                           # a victor_amd.marginals.Binning, or None
-        self._h1, self._h2 = binning.zeros(R) if binning is not None else (None, None)
+        self._h1, self._h2 = binning.zeros(self._RK) if binning is not None else (None, None)
         self.marginals = None
         self.move, self.stretch_a = move, float(stretch_a)
         self._specs, self.fixed = specs, fixed
         self.R, self.W = R, W
         self._rng, self._width = rng, width
+        if temper is not None:                            # (C, d): the widths times the rung's scale (a scale of 1 changes no bit)
+            self._width = width[None, :] * temper.scale[:, None]
         self._factor = None                               # (C, d, d) proposal factors of a Laplace proposal, or None: the widths
         self.burn, self.thin, self.keep_chain = burn, thin, keep_chain
         self._evaluate = evaluator
@@ -168,12 +185,14 @@ class Chains:
     def _draw_block(self):
         if self.move == "stretch":
             return self._draw_block_stretch()
-        C_, d = self.R * self.W, len(self.names)
+        C_, d = self._RK * self.W, len(self.names)
         if self._factor is None:
             dz = self._width * self._rng.standard_normal((BLOCK, C_, d))
         else:                                             # correlated proposals: chain c draws dz = F_(c // W) normal(d)
             dz = np.einsum("cjk,tck->tcj", self._factor, self._rng.standard_normal((BLOCK, C_, d)))
         logu = np.log(self._rng.random((BLOCK, C_)))
+        if self._temper is not None:                      # the swap levels: a generator of their own, block by block
+            return dz, logu, self._temper.draw_logs()
         return dz, logu
 
     def _draw_block_stretch(self):
@@ -279,6 +298,8 @@ class Chains:
     def _run_host(self, n_steps):
         if self.move == "stretch":
             return self._run_host_stretch(n_steps)
+        if self._temper is not None:
+            return self._run_host_tempered(n_steps)
         lo, hi = self._lo, self._hi
         x, lnl, chi2 = self._x, self._lnl, self._chi2
         done = 0
@@ -308,6 +329,44 @@ class Chains:
                 self._account(x, lnl, chi2)
             done += len(dz)
 
+    def _run_host_tempered(self, n_steps):
+        """The loop of ``_run_host`` under replica exchange (:mod:`victor_amd.tempering`): the tempered decision at each chain's
+        beta, the energy sums of a kept step, and the swap event that follows a step."""
+        from .tempering import gain as tempered_gain
+        q = self._temper
+        lo, hi = self._lo, self._hi
+        x, lnl, chi2 = self._x, self._lnl, self._chi2
+        done = 0
+        while done < n_steps:
+            dz, logu, logs = self._piece(n_steps - done)
+            for t in range(len(dz)):
+                prop = x + dz[t]
+                inside = ((prop >= lo) & (prop <= hi)).all(axis=1)
+                rows = np.where(inside[:, None], prop, x)            # outside: the current position, result discarded
+                lnl_p, chi2_p = self._evaluate(rows)
+                lnl_p = np.where(inside, lnl_p, -np.inf)
+                with np.errstate(invalid="ignore"):
+                    if self._prior is None:
+                        gain = tempered_gain(q.beta, lnl_p, lnl)
+                    else:                                            # (beta lnL' + lp') - (beta lnL + lp)
+                        gain = tempered_gain(q.beta, lnl_p, lnl, self._prior.lnprior(prop), self._prior.lnprior(x))
+                    accept = inside & (logu[t] < gain)               # NaN (0 * inf, inf - inf, a NaN lnL): False
+                    margin = np.abs(gain - logu[t])
+                margin = margin[np.isfinite(margin)]
+                if margin.size:
+                    self.decision_margin = min(self.decision_margin, float(margin.min()))
+                self._n_outside += ~inside
+                x[accept] = prop[accept]
+                lnl[accept] = lnl_p[accept]
+                chi2[accept] = chi2_p[accept]
+                self._n_accept += accept
+                step = self.n_steps
+                if self._kept(step):
+                    q.energy_add(lnl)
+                self._account(x, lnl, chi2)                          # (before the swap: a kept step is what the decision left)
+                q.swap(step, x, lnl, chi2, logs[t])
+            done += len(dz)
+
     # ------------------------------------------------------------------ the device route ---------------------------------
     def _check(self, rc, what):
         if rc != 0:
@@ -317,7 +376,7 @@ class Chains:
 
     def _run_device(self, n_steps):
         lib, h = self._dev
-        C_, d = self.R * self.W, len(self.names)
+        C_, d = self._RK * self.W, len(self.names)
         done = 0
         ahead = None
         while done < n_steps:
@@ -330,6 +389,10 @@ class Chains:
                 z, lz, logu, partner = piece
                 self._check(lib.vk_chain_begin_stretch(h, k, self.W, N.as_dp(z), N.as_dp(lz), N.as_dp(logu),
                                                        partner.ctypes.data_as(C.POINTER(C.c_int32)), *tail), "vk_chain_begin_stretch")
+            elif self._temper is not None:
+                dz, logu, logs = piece
+                self._check(lib.vk_chain_begin_tempered(h, k, N.as_dp(dz), N.as_dp(logu), N.as_dp(logs),
+                                                        self._temper.ladder.swap_every, *tail), "vk_chain_begin_tempered")
             else:
                 dz, logu = piece
                 self._check(lib.vk_chain_begin(h, k, N.as_dp(dz), N.as_dp(logu), *tail), "vk_chain_begin")
@@ -348,7 +411,7 @@ class Chains:
 
     def _read_device(self):
         lib, h = self._dev
-        C_, d = self.R * self.W, len(self.names)
+        C_, d = self._RK * self.W, len(self.names)
         i64 = C.POINTER(C.c_int64)
         self._x, self._lnl, self._chi2 = np.empty((C_, d)), np.empty(C_), np.empty(C_)
         self._n_accept, self._n_kept = np.empty(C_, dtype=np.int64), np.empty(C_, dtype=np.int64)
@@ -363,6 +426,15 @@ class Chains:
             self._check(lib.vk_chain_autocorr(h, N.as_dp(q.pivot), N.as_dp(q.total), N.as_dp(q.head), N.as_dp(q.ring), N.as_dp(q.acc),
                                               C.byref(n)), "vk_chain_autocorr")
             q.n = int(n.value)
+        if self._temper is not None:
+            q = self._temper
+            self._check(lib.vk_chain_tempering(h, N.as_dp(q.pivot_e), N.as_dp(q.e1), N.as_dp(q.e2), q.n_e.ctypes.data_as(i64),
+                                               q.n_swap_try.ctypes.data_as(i64), q.n_swap_acc.ctypes.data_as(i64)), "vk_chain_tempering")
+
+    def _set_tempering_device(self):
+        """Hand the ladder to the handle (before ``vk_chain_start``)."""
+        lib, h = self._dev
+        self._check(lib.vk_chain_set_tempering(h, self._K, self.W, N.as_dp(self._temper.ladder.betas)), "vk_chain_set_tempering")
 
     def _set_marginals_device(self):
         """Hand the binning to the handle (before ``vk_chain_start``): the W chains of a problem pool."""
@@ -403,38 +475,44 @@ class Chains:
         return self
 
     def _publish(self):
-        R, W, d = self.R, self.W, len(self.names)
-        self.x = self._x.reshape(R, W, d).copy()
-        self.lnl, self.chi2 = self._lnl.reshape(R, W).copy(), self._chi2.reshape(R, W).copy()
-        self.n_accept = self._n_accept.reshape(R, W).copy()
+        R, W, d, K = self.R, self.W, len(self.names), self._K
+        P = self._RK                                         # (problem, rung) pairs; the public fields are the cold rung's
+        cold = slice(None, None, K)
+        self.x = self._x.reshape(P, W, d)[cold].copy()
+        self.lnl, self.chi2 = self._lnl.reshape(P, W)[cold].copy(), self._chi2.reshape(P, W)[cold].copy()
+        self.n_accept = self._n_accept.reshape(P, W)[cold].copy()
         self.acceptance = self.n_accept.sum(axis=1) / max(1, self.n_steps * W)
-        self.pivot, self.sum1 = self._pivot.reshape(R, W, d).copy(), self._sum1.reshape(R, W, d).copy()
-        self.sum2 = self._sum2.reshape(R, W, d, d).copy()
-        per_chain = self._n_kept.reshape(R, W)
+        self.pivot, self.sum1 = self._pivot.reshape(P, W, d)[cold].copy(), self._sum1.reshape(P, W, d)[cold].copy()
+        self.sum2 = self._sum2.reshape(P, W, d, d)[cold].copy()
+        per_chain = self._n_kept.reshape(P, W)[cold]
         self.n_kept = int(per_chain[0, 0])
         self.mean, self.cov = pooled_moments(per_chain, self.pivot, self.sum1, self.sum2)
         if not self._dev:
-            self.n_outside = self._n_outside.reshape(R, W).copy()
+            self.n_outside = self._n_outside.reshape(P, W)[cold].copy()
         if self._binning is not None:
             from .marginals import Marginals
-            self.marginals = Marginals(self._binning, self._h1, self._h2, per_chain.sum(axis=1))
+            self.marginals = Marginals(self._binning, self._h1[cold], self._h2[cold], per_chain.sum(axis=1))
         if self._series is not None:
             from .autocorr import Autocorr
-            self.autocorr = Autocorr(self.names, W, self._series.n, self._lag_c, self._series.arrays())
+            self.autocorr = Autocorr(self.names, W, self._series.n, self._lag_c, {k: v[cold] for k, v in self._series.arrays().items()})
         self.rhat = None
+        hist = None
         if self.keep_chain:
             hx, hl, hc = self._hist
             if len(hx) > 1:                                  # one array per block -> one array
-                self._hist = ([np.concatenate([a.reshape(-1, R * W, d) for a in hx])],
-                              [np.concatenate([a.reshape(-1, R * W) for a in hl])], [np.concatenate([a.reshape(-1, R * W) for a in hc])])
+                self._hist = ([np.concatenate([a.reshape(-1, P * W, d) for a in hx])],
+                              [np.concatenate([a.reshape(-1, P * W) for a in hl])], [np.concatenate([a.reshape(-1, P * W) for a in hc])])
                 hx, hl, hc = self._hist
-            self.chain = (hx[0].reshape(-1, R, W, d) if hx else np.empty((0, R, W, d)))
-            self.lnl_chain = hl[0].reshape(-1, R, W) if hl else np.empty((0, R, W))
-            self.chi2_chain = hc[0].reshape(-1, R, W) if hc else np.empty((0, R, W))
+            hist = (hx[0].reshape(-1, P, W, d) if hx else np.empty((0, P, W, d)), hl[0].reshape(-1, P, W) if hl else np.empty((0, P, W)),
+                    hc[0].reshape(-1, P, W) if hc else np.empty((0, P, W)))
+            self.chain, self.lnl_chain, self.chi2_chain = (a[:, cold] for a in hist) if K > 1 else hist
             self.lnprior_chain = np.zeros(self.chain.shape[:-1]) if self._prior is None else self._prior.lnprior(self.chain)
             if W > 1 and len(self.chain) > 1 and self.move != "stretch":   # (the walkers of an ensemble are not independent chains)
                 with np.errstate(invalid="ignore", divide="ignore"):
                     self.rhat = np.stack([gelman_rubin(self.chain[:, r]) for r in range(R)])
+        if self._temper is not None:
+            from .tempering import Tempering
+            self.tempering = Tempering(self._temper, self._n_accept, self.n_steps, self._n_kept, self._x, self._lnl, self._chi2, hist)
 
 
 def _draw_start(rng, loc, scale, lo, hi, what):
@@ -448,7 +526,7 @@ def _draw_start(rng, loc, scale, lo, hi, what):
 
 def sample_chains(fit, params, n_steps, walkers=8, seed=0, fixed=None, start=None, scatter=None, proposal=None, burn=0, thin=1,
                   keep_chain=True, device=True, kwargs=None, realisations=None, evaluate=None, move="metropolis", stretch_a=2.0,
-                  prior=None, marginals=None, autocorr=None):
+                  prior=None, marginals=None, autocorr=None, temper=None):
     """The work of ``CCFFit.sample_chains`` (``realisations=None``: the fit's data vector, R = 1) and
     ``Realisations.sample_chains`` (R = the realisations); see the module docstring.  With ``evaluate`` - a callable taking a dict
     of ``(C,)`` arrays (sampled and fixed parameters) and returning ``lnL (C,)`` or ``(lnL, chi2)`` - in place of ``fit`` only the
@@ -473,7 +551,13 @@ def sample_chains(fit, params, n_steps, walkers=8, seed=0, fixed=None, start=Non
     ``Chains.marginals``).  ``autocorr``: None (off), True or a dict ``{"max_lag": int, "c": float}`` (defaults 128 and 5.0;
     ``max_lag`` at most 1024) for the integrated autocorrelation time and the effective sample size of every problem and
     parameter, from the series of the per-step sum over the problem's chains, accumulated where the chains run
-    (:mod:`victor_amd.autocorr`; ``Chains.autocorr``).  Every argument is checked before the first device call.  Returns a :class:`Chains`."""
+    (:mod:`victor_amd.autocorr`; ``Chains.autocorr``).  ``temper``: None (off), True or a dict for replica exchange over a ladder
+    of inverse temperatures and the evidence by thermodynamic integration (:mod:`victor_amd.tempering`; ``Chains.tempering``):
+    ``{"rungs": K, "power": p}`` (defaults 16 and 5) for ``beta_k = ((K - 1 - k) / (K - 1))**p`` or ``{"betas": [...]}`` for an
+    explicit ladder (from 1, strictly decreasing, >= 0), ``"swap_every"`` (default 4; 0: never) and ``"scales"``, one factor per
+    rung on the proposal widths and on a Laplace proposal's factors (default ``min(1 / sqrt(beta_k), min_j (hi_j - lo_j) / (2
+    width_j))``).  R x K x ``walkers`` chains run, at most 65536; every public (R, W, ...) field of the result is the cold rung;
+    ``move="stretch"`` is refused with it.  Every argument is checked before the first device call.  Returns a :class:`Chains`."""
     kwargs = kwargs or {}
     n_steps, walkers, burn, thin = int(n_steps), int(walkers), int(burn), int(thin)
     if n_steps < 0:
@@ -516,9 +600,10 @@ def sample_chains(fit, params, n_steps, walkers=8, seed=0, fixed=None, start=Non
         fit_options = q.fit_options(fit, kwargs)
     R = len(realisations) if realisations is not None else 1
     W = walkers
-    n_chains = R * W
-    if n_chains > MAX_CHAINS:
-        raise InputError(f"sample_chains: {R} problems x {W} walkers = {n_chains} chains: at most {MAX_CHAINS}")
+    if R * W > MAX_CHAINS:
+        raise InputError(f"sample_chains: {R} problems x {W} walkers = {R * W} chains: at most {MAX_CHAINS}")
+    if temper is not None and temper is not False and stretch:
+        raise InputError("sample_chains: temper runs the Metropolis move only (a tempered stretch move is not provided)")
     if stretch and (W % 2 or W < 2 * (d + 1)):
         raise InputError(f"sample_chains: the stretch move needs an even number of walkers, at least 2 (n_params + 1) = {2 * (d + 1)}")
     lap = getattr(proposal, "laplace", None) if hasattr(proposal, "n_evals") else proposal     # (a BestFit carries its Laplace)
@@ -537,6 +622,12 @@ def sample_chains(fit, params, n_steps, walkers=8, seed=0, fixed=None, start=Non
     width = q.per_param("proposal", proposal, [s.proposal for s in specs])
     if not stretch and np.any(~(width > 0)):
         raise InputError(f"sample_chains: every proposal width must be > 0 ({dict(zip(names, width.tolist()))})")
+    from .tempering import TemperState, resolve_temper
+    ladder = resolve_temper(temper, "sample_chains", width, lo, hi)
+    K = ladder.K if ladder is not None else 1
+    n_chains = R * K * W
+    if n_chains > MAX_CHAINS:
+        raise InputError(f"sample_chains: {R} problems x {K} rungs x {W} walkers = {n_chains} chains: at most {MAX_CHAINS}")
     centre = None
     if start is not None:
         given = dict(start.params) if hasattr(start, "params") and hasattr(start, "names") else dict(start)
@@ -562,8 +653,8 @@ def sample_chains(fit, params, n_steps, walkers=8, seed=0, fixed=None, start=Non
             x0[c] = _draw_start(rng, loc, scale, lo, hi, "the reference distribution")
     else:
         for c in range(n_chains):
-            x0[c] = _draw_start(rng, centre[c // W], spread, lo, hi, f"the scattered start of problem {c // W}")
-    which = np.repeat(np.arange(R, dtype=np.int32), W)
+            x0[c] = _draw_start(rng, centre[c // (K * W)], spread, lo, hi, f"the scattered start of problem {c // (K * W)}")
+    which = np.repeat(np.arange(R, dtype=np.int32), K * W)
     fixed_out = {k: float(v) for k, v in fixed_all.items()}
 
     def batch_of(x):
@@ -591,9 +682,11 @@ def sample_chains(fit, params, n_steps, walkers=8, seed=0, fixed=None, start=Non
         lib, h, refresh = q.create("vk_chain_create", fit, realisations, kwargs, fit_options, batch_of(x0), which)
         handle = (lib, h)
     ch = Chains(names, specs, fixed_out, R, W, rng, width, burn, thin, bool(keep_chain), evaluator, handle, move, stretch_a, prior,
-                binning, lags)
+                binning, lags, None if ladder is None else TemperState(ladder, R, W, seed))
     if lap is not None:
-        ch._factor = np.repeat(lap.proposal_factors(width), W, axis=0)
+        ch._factor = np.repeat(lap.proposal_factors(width), K * W, axis=0)
+        if ladder is not None:
+            ch._factor = ch._factor * ch._temper.scale[:, None, None]
     if handle:
         ch._refresh = refresh                                # (keeps the realisations and the contexts the handle runs on)
         ch._fit = fit                                        # (a joint fit owns the covariance handles the chains read)
@@ -603,6 +696,8 @@ def sample_chains(fit, params, n_steps, walkers=8, seed=0, fixed=None, start=Non
         ch._set_marginals_device()
     if handle and lags is not None:
         ch._set_autocorr_device()
+    if handle and ladder is not None:
+        ch._set_tempering_device()
     if handle:
         ch._check(handle[0].vk_chain_start(handle[1], N.as_dp(N.f64(x0))), "vk_chain_start")
     else:

@@ -27,6 +27,9 @@
 //   vk_kernel_hessian.h  the central-difference stencil of vk_fit_hessian on a best-fit handle: a rows kernel, one thread per
 //                        stencil row, and an assemble kernel, one wave per problem, over the statistic of vk_hessian.h (plain
 //                        C++, likewise)
+//   vk_kernel_temper.h   replica exchange on the same handles (vk_chain_begin_tempered): the tempered step kernel, one thread per
+//                        chain, and the swap kernel, one thread per candidate pair of neighbouring rungs, over the transition,
+//                        energy sums and swap of vk_temper_step.h (plain C++, likewise)
 
 #include <hip/hip_runtime.h>
 
@@ -42,6 +45,7 @@
 #include "vk_kernel_fit.h"
 #include "vk_kernel_chain.h"
 #include "vk_kernel_stretch.h"
+#include "vk_kernel_temper.h"
 #include "vk_kernel_autocorr.h"
 #include "vk_kernel_hessian.h"
 
@@ -655,6 +659,25 @@ struct __attribute__((visibility("hidden"))) vk_chain : Sampled {
   void* d_ac = nullptr;
   size_t ac_series = 0;                    // C / group problems x P parameters
   std::vector<int> h_which;                // the chains' realisation indices, read back for vk_chain_begin_stretch's check
+  // replica exchange (vk_kernel_temper.h): betas [K] | pivot_e, e1, e2 [C] | a block of swap levels [64][C] | n_e, n_swap_try,
+  // n_swap_acc [C] - one allocation of its own, made (and zeroed) by vk_chain_set_tempering; temper.K == 0: none
+  TemperArgs temper{};
+  void* d_temper = nullptr;
+  double* d_logs = nullptr;
+
+  void temper_layout(Carve& c, int K) {
+    const size_t n = C;
+    double* betas = nullptr;
+    c.take(betas, (size_t)K);
+    temper.betas = betas;
+    c.take(temper.pivot_e, n);               // (pivot_e .. e2 and n_e .. n_swap_acc are contiguous: zeroed in two calls)
+    c.take(temper.e1, n);
+    c.take(temper.e2, n);
+    c.take(d_logs, (size_t)vkchain::kBlock * n);
+    c.take(temper.n_e, n);
+    c.take(temper.n_swap_try, n);
+    c.take(temper.n_swap_acc, n);
+  }
 
   void stretch_layout(Carve& c) {
     const size_t block = (size_t)vkchain::kBlock * C;         // 64 sweeps x 2 halves x C / 2
@@ -751,6 +774,25 @@ static void chain_drop_autocorr(vk_chain* f) {
   f->d_ac = nullptr;
   f->ac = vkac::Autocorr{};
   f->ac_series = 0;
+}
+
+// no tempering any more: the handle makes the launches it made before it had any
+static void chain_drop_tempering(vk_chain* f) {
+  if (f->d_temper) {
+    (void)hipSetDevice(f->ctx->device);
+    (void)hipFree(f->d_temper);
+  }
+  f->d_temper = nullptr;
+  f->d_logs = nullptr;
+  f->temper = TemperArgs{};
+}
+
+// fresh energy sums and swap counters, in stream order
+static hipError_t chain_zero_tempering(vk_chain* f) {
+  const size_t n = f->C;
+  hipError_t e = hipMemsetAsync(f->temper.pivot_e, 0, 3 * n * sizeof(double), f->ctx->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(f->temper.n_e, 0, 3 * n * sizeof(long long), f->ctx->stream);
+  return e;
 }
 
 // the series kernel behind the step kernel of a kept step (a kept sweep's second half): one wave per (problem, parameter)
@@ -952,6 +994,7 @@ void vk_chain_destroy(vk_chain* f) {
   if (f->in_flight) (void)hipStreamSynchronize(f->ctx->stream);
   chain_drop_marginals(f);
   chain_drop_autocorr(f);
+  chain_drop_tempering(f);
   if (f->d_stretch) {
     (void)hipSetDevice(f->ctx->device);
     (void)hipFree(f->d_stretch);
@@ -977,6 +1020,7 @@ int vk_chain_start(vk_chain* f, const double* x0) {
     VK_SAMPLED_HIP(f, hipMemsetAsync(f->d_ac, 0, vkac::state_doubles(f->ac_series, f->ac.max_lag) * sizeof(double), ctx->stream));
     f->ac.n = 0;
   }
+  if (f->temper.K) VK_SAMPLED_HIP(f, chain_zero_tempering(f));          // ... and fresh energy sums and swap counters
   ChainArgs a = chain_args(f);
   rc = sampled_launch(f, vk_chain_init_kernel, a.C, kChainBlock, a);
   if (rc == VK_OK) rc = sampled_evaluate(f, f->C, f->d_res_lnl, f->d_res_chi);
@@ -1113,6 +1157,161 @@ int vk_chain_begin_stretch(vk_chain* f, int32_t n_steps, int32_t walkers, const 
       if (rc == VK_OK) rc = sampled_launch(f, vk_stretch_step_kernel, a.M, kChainBlock, a);
     }
     if (rc == VK_OK && kept && f->ac.on) rc = chain_series(f);     // (behind the second half: all W walkers as the sweep leaves them)
+  }
+  if (rc) return sampled_abort(f, rc);
+  f->in_flight = n_steps;
+  f->block_kept = slot;
+  if (n_kept) *n_kept = slot;
+  f->err.clear();
+  return VK_OK;
+}
+
+// Replica exchange on the chains of a handle read as C / (rungs walkers) problems of `rungs` temperatures and `walkers` ladders
+// each (vk_kernel_temper.h).  Everything the two kernels index with is checked here: rungs and walkers fix the pairs the swap
+// kernel addresses and the size of the arrays the step kernel adds to.
+int vk_chain_set_tempering(vk_chain* f, int32_t rungs, int32_t walkers, const double* betas) {
+  if (!f) return VK_E_ARG;
+  const std::string me = "vk_chain_set_tempering: ";
+  if (f->in_flight) return refused(f, me + "a block begun with vk_chain_begin is awaiting vk_chain_finish");
+  if (rungs == 0) {
+    chain_drop_tempering(f);
+    f->err.clear();
+    return VK_OK;
+  }
+  if (rungs < 1 || walkers < 1) return refused(f, me + "need rungs >= 1 and walkers >= 1 (rungs == 0 clears)");
+  if (!betas) return refused(f, me + "NULL argument");
+  const long long ladder = (long long)rungs * walkers;
+  if (ladder > f->C || f->C % ladder)
+    return refused(f, me + std::to_string(f->C) + " chains are not a whole number of problems of " + std::to_string(rungs) +
+                          " rungs x " + std::to_string(walkers) + " walkers");
+  for (int k = 0; k < rungs; ++k)
+    if (!__builtin_isfinite(betas[k]) || betas[k] < 0.0)
+      return refused(f, me + "the inverse temperature of rung " + std::to_string(k) + " is not finite and >= 0");
+  if (betas[0] != 1.0) return refused(f, me + "rung 0 is the posterior itself: betas[0] must be 1");
+  for (int k = 1; k < rungs; ++k)
+    if (!(betas[k] < betas[k - 1])) return refused(f, me + "the inverse temperatures must decrease strictly from rung to rung");
+  VK_SAMPLED_HIP(f, hipSetDevice(f->ctx->device));
+  if (f->real) {                           // the rungs of a ladder exchange positions: one realisation per problem
+    if (f->h_which.empty()) {
+      f->h_which.resize(f->C);
+      VK_SAMPLED_HIP(f, hipMemcpy(f->h_which.data(), f->d_which, (size_t)f->C * sizeof(int), hipMemcpyDeviceToHost));
+    }
+    for (int c = 0; c < f->C; ++c)
+      if (f->h_which[c] != f->h_which[c - c % (int)ladder])
+        return refused(f, me + "chain " + std::to_string(c) + " is not of the realisation of its problem's first chain");
+  }
+  chain_drop_tempering(f);
+  Carve count;
+  f->temper_layout(count, rungs);
+  if (hipMalloc(&f->d_temper, count.bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    f->d_temper = nullptr;
+    f->temper = TemperArgs{};
+    f->err = me + "cannot allocate " + std::to_string(count.bytes) + " bytes of device memory";
+    return VK_E_HIP;
+  }
+  Carve mem{static_cast<char*>(f->d_temper)};
+  f->temper_layout(mem, rungs);
+  // (on the handle's stream, idle now: the kernels that add to the sums run there)
+  if (hipMemcpy(const_cast<double*>(f->temper.betas), betas, (size_t)rungs * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+      chain_zero_tempering(f) != hipSuccess || hipStreamSynchronize(f->ctx->stream) != hipSuccess) {
+    (void)hipGetLastError();
+    chain_drop_tempering(f);
+    f->err = me + "upload failed";
+    return VK_E_HIP;
+  }
+  f->temper.K = rungs;
+  f->temper.W = walkers;
+  f->err.clear();
+  return VK_OK;
+}
+
+int vk_chain_tempering(vk_chain* f, double* pivot_e, double* e1, double* e2, int64_t* n_e, int64_t* n_swap_try, int64_t* n_swap_acc) {
+  if (!f) return VK_E_ARG;
+  if (f->in_flight) return refused(f, "vk_chain_tempering: a block begun with vk_chain_begin is awaiting vk_chain_finish");
+  if (!f->temper.K) return refused(f, "vk_chain_tempering: the handle has no tempering (vk_chain_set_tempering)");
+  VK_SAMPLED_HIP(f, hipSetDevice(f->ctx->device));
+  const size_t n = f->C;
+  if (pivot_e) VK_SAMPLED_HIP(f, hipMemcpy(pivot_e, f->temper.pivot_e, n * sizeof(double), hipMemcpyDeviceToHost));
+  if (e1) VK_SAMPLED_HIP(f, hipMemcpy(e1, f->temper.e1, n * sizeof(double), hipMemcpyDeviceToHost));
+  if (e2) VK_SAMPLED_HIP(f, hipMemcpy(e2, f->temper.e2, n * sizeof(double), hipMemcpyDeviceToHost));
+  if (n_e) VK_SAMPLED_HIP(f, hipMemcpy(n_e, f->temper.n_e, n * sizeof(int64_t), hipMemcpyDeviceToHost));
+  if (n_swap_try) VK_SAMPLED_HIP(f, hipMemcpy(n_swap_try, f->temper.n_swap_try, n * sizeof(int64_t), hipMemcpyDeviceToHost));
+  if (n_swap_acc) VK_SAMPLED_HIP(f, hipMemcpy(n_swap_acc, f->temper.n_swap_acc, n * sizeof(int64_t), hipMemcpyDeviceToHost));
+  f->err.clear();
+  return VK_OK;
+}
+
+// A block of tempered steps (vk_kernel_temper.h).  Per step: the evaluation of the C rows and the tempered step kernel, which
+// writes the next rows itself - unless a swap event follows the step: then the step kernel writes none, the swap kernel exchanges
+// the states of the event's pairs and the propose kernel forms the next rows from what the swap left.  Plain launches on the
+// handle's stream, no host synchronisation and no graph inside the block.
+int vk_chain_begin_tempered(vk_chain* f, int32_t n_steps, const double* dz, const double* logu, const double* logs, int64_t swap_every,
+                            int64_t first_step, int64_t burn, int64_t thin, int32_t want_history, int32_t* n_kept) {
+  if (!f) return VK_E_ARG;
+  vk_ctx* ctx = f->ctx;
+  const std::string me = "vk_chain_begin_tempered: ";
+  if (!f->temper.K) return refused(f, me + "the handle has no tempering (vk_chain_set_tempering)");
+  if (!dz || !logu || (swap_every > 0 && !logs)) return refused(f, me + "NULL argument");
+  if (!f->started) return refused(f, me + "the chains have no start (vk_chain_start)");
+  if (f->in_flight) return refused(f, me + "the previous block has not been finished (vk_chain_finish)");
+  if (n_steps < 1 || n_steps > vkchain::kBlock) return refused(f, me + "need 1 <= steps <= 64 in a block");
+  if (first_step < 0 || burn < 0 || thin < 1) return refused(f, me + "need first_step >= 0, burn >= 0, thin >= 1");
+  if (swap_every < 0) return refused(f, me + "need swap_every >= 0 (0: never)");
+  int rc = sampled_ready(f, "vk_chain_begin_tempered", "chain", true);
+  if (rc) return rc;
+  const size_t C = f->C, P = f->P;
+  VK_SAMPLED_HIP(f, hipSetDevice(ctx->device));
+  // the stream is idle (the block before was finished): plain copies, complete on return
+  VK_SAMPLED_HIP(f, hipMemcpy(f->d_dz, dz, (size_t)n_steps * C * P * sizeof(double), hipMemcpyHostToDevice));
+  VK_SAMPLED_HIP(f, hipMemcpy(f->d_logu, logu, (size_t)n_steps * C * sizeof(double), hipMemcpyHostToDevice));
+  if (swap_every > 0) VK_SAMPLED_HIP(f, hipMemcpy(f->d_logs, logs, (size_t)n_steps * C * sizeof(double), hipMemcpyHostToDevice));
+  TemperStepArgs g{};
+  g.c = chain_args(f);
+  g.t = f->temper;
+  ChainArgs& a = g.c;
+  SwapArgs w{};
+  w.C = f->C;
+  w.d = f->P;
+  w.x = f->d_x;
+  w.lnl = f->d_lnl;
+  w.chi2 = f->d_chi;
+  w.t = f->temper;
+  const int problems = f->C / (f->temper.K * f->temper.W);
+  a.dz = f->d_dz;
+  rc = sampled_launch(f, vk_chain_propose_kernel, a.C, kChainBlock, a);
+  int slot = 0;
+  for (int t = 0; t < n_steps && rc == VK_OK; ++t) {
+    rc = sampled_evaluate(f, f->C, f->d_res_lnl, f->d_res_chi);
+    if (rc) break;
+    const bool kept = vkchain::is_kept(first_step + t, burn, thin);
+    // a swap event with no pair (one rung; two rungs at odd parity) is no event: the step kernel keeps writing the next rows
+    const int parity = vktemper::is_swap(first_step + t, swap_every) ? vktemper::swap_parity(first_step + t, swap_every) : 0;
+    const int pairs = vktemper::is_swap(first_step + t, swap_every) ? vktemper::pairs_of(f->temper.K, parity) : 0;
+    a.dz = f->d_dz + (size_t)t * C * P;
+    a.logu = f->d_logu + (size_t)t * C;
+    const double* next = t + 1 < n_steps ? a.dz + C * P : nullptr;
+    a.dz_next = pairs ? nullptr : next;
+    a.kept = kept ? 1 : 0;
+    const bool hist = kept && want_history;
+    a.hist_x = hist ? f->d_hx + (size_t)slot * C * P : nullptr;
+    a.hist_lnl = hist ? f->d_hl + (size_t)slot * C : nullptr;
+    a.hist_chi2 = hist ? f->d_hc + (size_t)slot * C : nullptr;
+    if (hist) ++slot;
+    rc = sampled_launch(f, vk_chain_step_tempered_kernel, a.C, kChainBlock, g);
+    if (rc == VK_OK && kept && f->ac.on) rc = chain_series(f);      // (the positions the sums have just taken: before the swap)
+    if (rc == VK_OK && pairs) {
+      w.logs = f->d_logs + (size_t)t * C;
+      w.parity = parity;
+      w.pairs = pairs;
+      w.n = problems * pairs * f->temper.W;
+      rc = sampled_launch(f, vk_chain_swap_kernel, w.n, kChainBlock, w);
+      if (rc == VK_OK && next) {
+        ChainArgs p = a;
+        p.dz = next;
+        rc = sampled_launch(f, vk_chain_propose_kernel, p.C, kChainBlock, p);
+      }
+    }
   }
   if (rc) return sampled_abort(f, rc);
   f->in_flight = n_steps;

@@ -521,7 +521,7 @@ class JointFit:
         return laplace(self, params, at, step, fixed, prior, shrink, refine, keep_values, kwargs)
 
     def sample_chains(self, params, n_steps, walkers=8, seed=0, fixed=None, start=None, scatter=None, proposal=None, burn=0,
-                      thin=1, keep_chain=True, device=True, move="metropolis", stretch_a=2.0, prior=None, marginals=None, autocorr=None,
+                      thin=1, keep_chain=True, device=True, move="metropolis", stretch_a=2.0, prior=None, marginals=None, autocorr=None, temper=None,
                       **kwargs):
         """``walkers`` Metropolis chains of the joint lnL, stepped on the GPU (``device=True``) or by the NumPy loop over
         :meth:`log_likelihood_batch` that defines them (``device=False``).  Arguments and result as ``CCFFit.sample_chains``
@@ -529,7 +529,7 @@ class JointFit:
         from .chains import sample_chains
         return sample_chains(self, params, n_steps, walkers, seed, fixed, start, scatter, proposal, burn, thin, keep_chain, device,
                              kwargs, move=move, stretch_a=stretch_a, prior=prior, marginals=marginals,
-                             autocorr=autocorr)
+                             autocorr=autocorr, temper=temper)
 
     @property
     def n_data(self):
@@ -585,7 +585,7 @@ class JointRealisations:
         return laplace(self.joint, params, at, step, fixed, prior, shrink, refine, keep_values, kwargs, realisations=self)
 
     def sample_chains(self, params, n_steps, walkers=8, seed=0, fixed=None, start=None, scatter=None, proposal=None, burn=0,
-                      thin=1, keep_chain=True, device=True, move="metropolis", stretch_a=2.0, prior=None, marginals=None, autocorr=None,
+                      thin=1, keep_chain=True, device=True, move="metropolis", stretch_a=2.0, prior=None, marginals=None, autocorr=None, temper=None,
                       **kwargs):
         """``walkers`` Metropolis chains of EVERY joint realisation in lock step, on the GPU (``device=True``) or by the NumPy
         loop over :meth:`log_likelihood_pairs` that defines them (``device=False``).  Arguments and result as
@@ -594,7 +594,7 @@ class JointRealisations:
         from .chains import sample_chains
         return sample_chains(self.joint, params, n_steps, walkers, seed, fixed, start, scatter, proposal, burn, thin, keep_chain,
                              device, kwargs, realisations=self, move=move, stretch_a=stretch_a, prior=prior, marginals=marginals,
-                             autocorr=autocorr)
+                             autocorr=autocorr, temper=temper)
 
     def _eval(self, params, kwargs, which=None):
         joint = self.joint
