@@ -42,6 +42,13 @@ def main():
     print(f"one log_likelihood call: {dt * 1e6:.0f} us (the reference needs about 75 ms)")
     multipoles = fit.theory_multipoles(fit.s, dict(params), poles=[0, 2])
     print("model monopole at the first / last s bin:", multipoles["0"][0], multipoles["0"][-1])
+    # the posterior band of the model through the data: chains on the GPU, the theory vectors summed where they run
+    with open(os.path.join("config", "boss_cobaya_config.yaml")) as fh:
+        block = yaml.full_load(fh)["params"]
+    ch = fit.sample_chains(block, 4000, walkers=8, burn=1000, keep_chain=False, predictive=True)
+    mean, std = ch.predictive.multipoles[0]
+    print(f"posterior monopole at the first s bin: {mean[0, 0]:.4f} +- {std[0, 0]:.4f}; mean chi2 = {ch.predictive.mean_chi2[0]:.2f}, "
+          f"p_D = {ch.predictive.p_d[0]:.2f}, DIC = {ch.predictive.dic[0]:.2f}")
 
 
 if __name__ == "__main__":

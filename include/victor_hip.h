@@ -622,6 +622,47 @@ int vk_chain_begin_tempered(vk_chain* f, int32_t n_steps, const double* dz, cons
                             int64_t first_step, int64_t burn, int64_t thin, int32_t want_history, int32_t* n_kept);
 int vk_chain_tempering(vk_chain* f, double* pivot_e, double* e1, double* e2, int64_t* n_e, int64_t* n_swap_try, int64_t* n_swap_acc);
 
+/* ---- Posterior-predictive sums of a chain handle: the model vector's band, mean chi-square and DIC ---------------------------
+ * The runs above return everything about the parameters and nothing about the MODEL VECTOR: the posterior band of xi_0 / xi_2 /
+ * xi_4 drawn through the data needs the theory vector at every kept position, which a run without a history no longer has and a
+ * run with one would have to evaluate a second time.  The theory vector of every proposal is in device memory when its step is
+ * decided; vk_chain_set_predictive makes vk_chain_begin and vk_chain_begin_stretch, on a handle of vk_chain_create, keep each
+ * chain's current one and sum it at the kept steps (vk_predictive.h states the rules, victor_amd/predictive.py is the
+ * definition).  Problem r owns the `group` chains c = r group + w; N is the length of the context's data vector.
+ *   hold           held[c] is the theory vector at chain c's current position, seen[c] the chain's accept count when it was taken.
+ *                  After vk_chain_start's evaluation every chain takes its row; after every decision - kept or not - a chain whose
+ *                  accept count differs from seen[c] takes its row of the launch just decided (row c; in a stretch half-step the
+ *                  row of the moving walker).  A rejected proposal and one outside the box leave held[c] alone.  The step
+ *                  kernels are untouched: the accept counter is the hand-off.
+ *   pivot          at vk_chain_start pivot_t[r][k] = held[r group][k] if finite, else 0; pivot_chi2 and pivot_lnl likewise from the
+ *                  start of chain r group.
+ *   kept step      (a kept sweep, after its second half) for w = 0 .. group - 1 in that order: if chi2[c] and lnL[c] are both
+ *                  finite, v = held[c][k] - pivot_t[r][k], sum_t[r][k] += v, sum_tt[r][k] += v v for every k, chi2 and lnL likewise
+ *                  into s_chi2, s_chi2sq, s_lnl, s_lnlsq about their pivots, n[r] += 1; otherwise n_skipped[r] += 1.  Plain double
+ *                  sums in (step, walker) order - independent of how a run is cut into blocks; a product may be contracted into
+ *                  an fma.
+ * Launches: behind every step kernel (each half's, of a sweep) a hold kernel of one wave per row, before the next evaluation
+ * overwrites the theory vectors; behind the hold of every kept step (a kept sweep's second half) a kernel of one thread per
+ * (problem, entry).  No host synchronisation, no atomics.  On the data-vector route the evaluation is asked to store the theory
+ * vectors its fused chi-square would not otherwise write: stores only, lnL keeps its bits.
+ * vk_chain_predictive copies the state out, between blocks; any pointer may be NULL:
+ *   pivot_t, sum_t, sum_tt   [n_chains / group][N]
+ *   deviance       [n_chains / group][6]: pivot_chi2, pivot_lnl, s_chi2, s_chi2sq, s_lnl, s_lnlsq
+ *   n, n_skipped   [n_chains / group]
+ *   held           [n_chains][N]
+ * The handle owns the state, (n_chains + 3 n_chains / group) N doubles and a few per problem and chain: made and zeroed by
+ * vk_chain_set_predictive (a second call replaces it), after which the chains need a (new) vk_chain_start - the held vectors are
+ * taken there; zeroed again by vk_chain_start, kept across blocks, freed by vk_chain_destroy.  group == 0 clears it; a handle that
+ * never had it, or had it cleared, makes the launches and returns the bytes it always did.
+ * Refused (VK_E_ARG, vk_chain_last_error gives the text, the handle stays usable and keeps the state it had): a block begun and
+ * not finished; a handle of vk_chain_create_joint / _joint_blocks (its theory workspace is laid out by the route that evaluates
+ * it); a handle with tempering, and vk_chain_set_tempering on a handle with predictive sums (a swap moves states without touching
+ * the accept counters); group < 1 or n_chains % group != 0; vk_chain_predictive on a handle without it.  Device memory that cannot
+ * be had is reported as vk_chain_create reports it (VK_E_HIP); the handle keeps the sums it had. */
+int vk_chain_set_predictive(vk_chain* f, int32_t group);
+int vk_chain_predictive(vk_chain* f, double* pivot_t, double* sum_t, double* sum_tt, double* deviance, int64_t* n, int64_t* n_skipped,
+                        double* held);
+
 /* ---- Hessians of lnL + ln prior at given points of a best-fit handle: Laplace covariances -----------------------------------
  * vk_fit_run returns a point per problem and nothing about its uncertainty.  vk_fit_hessian evaluates, on any handle of the
  * three vk_fit_create calls (before or after vk_fit_run; with the prior of vk_fit_set_prior, if any), one central-difference

@@ -194,6 +194,9 @@ SYMBOLS = {
     "vk_chain_begin_tempered": (C.c_int, [_vp, C.c_int32, _dp, _dp, _dp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
                                           C.POINTER(C.c_int32)]),
     "vk_chain_tempering": (C.c_int, [_vp, _dp, _dp, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    # the posterior-predictive sums of a chain handle: held theory vectors, their sums and the deviance sums
+    "vk_chain_set_predictive": (C.c_int, [_vp, C.c_int32]),
+    "vk_chain_predictive": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _dp]),
     # the Hessian stencil of a best-fit handle and the Laplace covariance from it
     "vk_hessian_rows": (C.c_int64, [C.c_int32]),
     "vk_fit_hessian": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int32)]),

@@ -353,7 +353,7 @@ class CCFFit(CCFModel):
 
     def sample_chains(self, params, n_steps, walkers=8, seed=0, fixed=None, start=None, scatter=None, proposal=None, burn=0,
                       thin=1, keep_chain=True, device=True, move="metropolis", stretch_a=2.0, prior=None, marginals=None, autocorr=None, temper=None,
-                      **kwargs):
+                      predictive=None, **kwargs):
         """``walkers`` independent random-walk Metropolis chains of this fit's lnL, stepped on the GPU (``device=True``: the
         step loop runs on the device, ``vk_chain_begin``) or by the NumPy loop that defines them (``device=False``, over
         :meth:`log_likelihood_batch`): :func:`victor_amd.chains.sample_chains`, which documents the arguments.  Returns a
@@ -368,7 +368,7 @@ class CCFFit(CCFModel):
         from .chains import sample_chains
         return sample_chains(self, params, n_steps, walkers, seed, fixed, start, scatter, proposal, burn, thin, keep_chain, device,
                              kwargs, move=move, stretch_a=stretch_a, prior=prior, marginals=marginals,
-                             autocorr=autocorr, temper=temper)
+                             autocorr=autocorr, temper=temper, predictive=predictive)
 
     def realisations(self, simulation_numbers=None):
         """Every simulation realisation of this fit's data file (or the listed ``simulation_numbers``) against one model:

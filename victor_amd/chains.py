@@ -73,6 +73,14 @@ exchange states (replica exchange; :mod:`victor_amd.tempering` states the step, 
 reproduces them bit for bit through ``vk_chain_begin_tempered``): chain ``c = (r K + k) W + w`` is problem r, rung k, walker w, so
 everything above that groups W chains sees every (r, k) as a problem, and the public fields of ``Chains`` are the cold rung k = 0.
 ``Chains.tempering`` carries every rung's state and the evidence by thermodynamic integration.  Metropolis move only.
+
+**``predictive=``** keeps, per chain, the theory vector at its current position - taken from the launch that decided a step
+whenever the chain's accept count moved - and sums it per problem at every kept step (kept sweep), with chi2 and lnL beside it
+(:mod:`victor_amd.predictive` states the rules): on the device route by two small kernels behind the step kernel
+(``vk_chain_set_predictive``), on the definition route by the NumPy statement over ``fit.theory_vector_batch``.  The sums hold
+products the device may contract, so the routes agree to rounding.  ``Chains.predictive`` reads the posterior mean and scatter of
+the model vector (the band drawn through the data's multipoles), the mean chi-square and the deviance information criterion from
+them, with or without a history.  Single fits only, and not with ``temper=``.
 """
 
 import ctypes as C
@@ -144,11 +152,18 @@ class Chains:
     ``tempering``: a :class:`victor_amd.tempering.Tempering` (None without ``temper=``) - the ladder, every rung's state and
     history, the rungs' mean and variance of lnL, swap acceptances and ``ln_evidence`` -, rebuilt after every :meth:`extend`, which
     continues the ladder (the swap-event count and the swap levels' stream run over the chains' whole life).  Every (R, W, ...)
-    field above is then the cold rung's."""
+    field above is then the cold rung's.
+
+    ``predictive``: a :class:`victor_amd.predictive.Predictive` (None without ``predictive=``) - the posterior mean and scatter of
+    the theory vector and of its multipoles, the mean and variance of chi2 and lnL, ``p_d``, ``p_v`` and ``dic`` -, rebuilt after
+    every :meth:`extend`, which keeps accumulating."""
 
     def __init__(self, names, specs, fixed, R, W, rng, width, burn, thin, keep_chain, evaluator, device_handle, move="metropolis",
-                 stretch_a=2.0, prior=None, binning=None, lags=None, temper=None):
+                 stretch_a=2.0, prior=None, binning=None, lags=None, temper=None, predictive=None):
         self.names = list(names)
+        self._pred = predictive                           # a victor_amd.predictive.PredictiveState, or None
+        self._theory = self._at_mean = self._poles = None    # x (m, d) -> theory vectors (m, N); x (m, d), problems (m,) -> (lnL, chi2); (poles, n_s)
+        self.predictive = None
         self._series = self._lag_c = self.autocorr = None
         self._temper = temper                             # a victor_amd.tempering.TemperState, or None
         self._K = temper.K if temper is not None else 1
@@ -236,6 +251,16 @@ class Chains:
         self._sum2 = np.zeros((C_, d, d))
         self._n_outside = np.zeros(C_, dtype=np.int64)
         self.decision_margin = np.inf
+        if self._pred is not None:
+            self._pred.start(self._theory(self._x), self._n_accept, self._chi2, self._lnl)
+
+    def _hold(self, chains, rows):
+        """Behind a decision: the chains (of ``chains``, which the launch's ``rows`` serve) whose accept count moved take the
+        theory vector of their row (:mod:`victor_amd.predictive`)."""
+        q = self._pred
+        take = q.changed(chains, self._n_accept)
+        if take.any():
+            q.hold(chains[take], self._theory(rows[take]), self._n_accept)
 
     def _account(self, x, lnl, chi2):
         """The end of a step (a sweep): a kept one enters the moment sums and the history."""
@@ -248,6 +273,8 @@ class Chains:
                 self._binning.add(self._h1, self._h2, x, self.W)
             if self._series is not None:
                 self._series.add(x)
+            if self._pred is not None:
+                self._pred.add(chi2, lnl)
             if self.keep_chain:
                 for h, a in zip(self._hist, (x, lnl, chi2)):
                     h.append(a.copy())
@@ -292,6 +319,8 @@ class Chains:
                     lnl[won] = lnl_p[accept]
                     chi2[won] = chi2_p[accept]
                     self._n_accept[won] += 1
+                    if self._pred is not None:
+                        self._hold(mv, rows)
                 self._account(x, lnl, chi2)                              # "kept" is decided after the second half, for all W
             done += len(z)
 
@@ -326,6 +355,8 @@ class Chains:
                 lnl[accept] = lnl_p[accept]
                 chi2[accept] = chi2_p[accept]
                 self._n_accept += accept
+                if self._pred is not None:
+                    self._hold(np.arange(len(x)), rows)
                 self._account(x, lnl, chi2)
             done += len(dz)
 
@@ -426,10 +457,20 @@ class Chains:
             self._check(lib.vk_chain_autocorr(h, N.as_dp(q.pivot), N.as_dp(q.total), N.as_dp(q.head), N.as_dp(q.ring), N.as_dp(q.acc),
                                               C.byref(n)), "vk_chain_autocorr")
             q.n = int(n.value)
+        if self._pred is not None:
+            q = self._pred
+            self._check(lib.vk_chain_predictive(h, N.as_dp(q.pivot_t), N.as_dp(q.sum_t), N.as_dp(q.sum_tt), N.as_dp(q.deviance),
+                                                q.n.ctypes.data_as(i64), q.n_skipped.ctypes.data_as(i64), N.as_dp(q.held)),
+                        "vk_chain_predictive")
         if self._temper is not None:
             q = self._temper
             self._check(lib.vk_chain_tempering(h, N.as_dp(q.pivot_e), N.as_dp(q.e1), N.as_dp(q.e2), q.n_e.ctypes.data_as(i64),
                                                q.n_swap_try.ctypes.data_as(i64), q.n_swap_acc.ctypes.data_as(i64)), "vk_chain_tempering")
+
+    def _set_predictive_device(self):
+        """Ask the handle for the predictive sums (before ``vk_chain_start``): the W chains of a problem pool."""
+        lib, h = self._dev
+        self._check(lib.vk_chain_set_predictive(h, self.W), "vk_chain_set_predictive")
 
     def _set_tempering_device(self):
         """Hand the ladder to the handle (before ``vk_chain_start``)."""
@@ -495,6 +536,13 @@ class Chains:
         if self._series is not None:
             from .autocorr import Autocorr
             self.autocorr = Autocorr(self.names, W, self._series.n, self._lag_c, {k: v[cold] for k, v in self._series.arrays().items()})
+        if self._pred is not None:
+            from .predictive import Predictive
+            lnl_at, chi2_at = np.full(R, np.nan), np.full(R, np.nan)
+            has = np.flatnonzero(np.all(np.isfinite(self.mean), axis=1))
+            if len(has):                                     # one pairs evaluation at the pooled means of the problems that have one
+                lnl_at[has], chi2_at[has] = self._at_mean(self.mean[has], has.astype(np.int32))
+            self.predictive = Predictive(self._pred.arrays(), *self._poles, chi2_at_mean=chi2_at, lnl_at_mean=lnl_at)
         self.rhat = None
         hist = None
         if self.keep_chain:
@@ -526,7 +574,7 @@ def _draw_start(rng, loc, scale, lo, hi, what):
 
 def sample_chains(fit, params, n_steps, walkers=8, seed=0, fixed=None, start=None, scatter=None, proposal=None, burn=0, thin=1,
                   keep_chain=True, device=True, kwargs=None, realisations=None, evaluate=None, move="metropolis", stretch_a=2.0,
-                  prior=None, marginals=None, autocorr=None, temper=None):
+                  prior=None, marginals=None, autocorr=None, temper=None, predictive=None):
     """The work of ``CCFFit.sample_chains`` (``realisations=None``: the fit's data vector, R = 1) and
     ``Realisations.sample_chains`` (R = the realisations); see the module docstring.  With ``evaluate`` - a callable taking a dict
     of ``(C,)`` arrays (sampled and fixed parameters) and returning ``lnL (C,)`` or ``(lnL, chi2)`` - in place of ``fit`` only the
@@ -557,7 +605,10 @@ def sample_chains(fit, params, n_steps, walkers=8, seed=0, fixed=None, start=Non
     explicit ladder (from 1, strictly decreasing, >= 0), ``"swap_every"`` (default 4; 0: never) and ``"scales"``, one factor per
     rung on the proposal widths and on a Laplace proposal's factors (default ``min(1 / sqrt(beta_k), min_j (hi_j - lo_j) / (2
     width_j))``).  R x K x ``walkers`` chains run, at most 65536; every public (R, W, ...) field of the result is the cold rung;
-    ``move="stretch"`` is refused with it.  Every argument is checked before the first device call.  Returns a :class:`Chains`."""
+    ``move="stretch"`` is refused with it.  ``predictive``: None (off) or True for the posterior mean and scatter of the theory
+    vector, the mean chi-square and the deviance information criterion, summed where the chains run
+    (:mod:`victor_amd.predictive`; ``Chains.predictive``); refused (a ``ValueError``) on joint fits, with ``temper`` and with an
+    ``evaluate`` callable.  Every argument is checked before the first device call.  Returns a :class:`Chains`."""
     kwargs = kwargs or {}
     n_steps, walkers, burn, thin = int(n_steps), int(walkers), int(burn), int(thin)
     if n_steps < 0:
@@ -596,6 +647,10 @@ def sample_chains(fit, params, n_steps, walkers=8, seed=0, fixed=None, start=Non
     binning = resolve_marginals(marginals, "sample_chains", names, lo, hi)
     from .autocorr import resolve_autocorr
     lags = resolve_autocorr(autocorr, "sample_chains")
+    from .joint import JointFit
+    from .predictive import PredictiveState, resolve_predictive
+    predictive = resolve_predictive(predictive, "sample_chains", isinstance(fit, JointFit), temper is not None and temper is not False,
+                                    evaluate is None)
     if evaluate is None:
         fit_options = q.fit_options(fit, kwargs)
     R = len(realisations) if realisations is not None else 1
@@ -682,7 +737,13 @@ def sample_chains(fit, params, n_steps, walkers=8, seed=0, fixed=None, start=Non
         lib, h, refresh = q.create("vk_chain_create", fit, realisations, kwargs, fit_options, batch_of(x0), which)
         handle = (lib, h)
     ch = Chains(names, specs, fixed_out, R, W, rng, width, burn, thin, bool(keep_chain), evaluator, handle, move, stretch_a, prior,
-                binning, lags, None if ladder is None else TemperState(ladder, R, W, seed))
+                binning, lags, None if ladder is None else TemperState(ladder, R, W, seed),
+                PredictiveState(R, W, len(fit.s) * len(fit.poles_s)) if predictive else None)
+    if predictive:
+        ch._theory = lambda x: fit.theory_vector_batch(batch_of(x), **kwargs)
+        ch._at_mean = ((lambda x, problems: realisations.log_likelihood_pairs(batch_of(x), problems, **kwargs)) if realisations is not None
+                       else (lambda x, problems: fit.log_likelihood_batch(batch_of(x), **kwargs)))
+        ch._poles = (np.atleast_1d(fit.poles_s), len(fit.s))
     if lap is not None:
         ch._factor = np.repeat(lap.proposal_factors(width), K * W, axis=0)
         if ladder is not None:
@@ -698,6 +759,8 @@ def sample_chains(fit, params, n_steps, walkers=8, seed=0, fixed=None, start=Non
         ch._set_autocorr_device()
     if handle and ladder is not None:
         ch._set_tempering_device()
+    if handle and predictive:
+        ch._set_predictive_device()
     if handle:
         ch._check(handle[0].vk_chain_start(handle[1], N.as_dp(N.f64(x0))), "vk_chain_start")
     else:

@@ -30,6 +30,9 @@
 //   vk_kernel_temper.h   replica exchange on the same handles (vk_chain_begin_tempered): the tempered step kernel, one thread per
 //                        chain, and the swap kernel, one thread per candidate pair of neighbouring rungs, over the transition,
 //                        energy sums and swap of vk_temper_step.h (plain C++, likewise)
+//   vk_kernel_predictive.h the posterior-predictive sums (vk_chain_set_predictive): the hold kernel behind every step kernel, one
+//                        wave per row, which keeps each chain's theory vector, and the predict kernel behind every kept step, one
+//                        thread per (problem, entry), over the rules of vk_predictive.h (plain C++, likewise)
 
 #include <hip/hip_runtime.h>
 
@@ -47,6 +50,7 @@
 #include "vk_kernel_stretch.h"
 #include "vk_kernel_temper.h"
 #include "vk_kernel_autocorr.h"
+#include "vk_kernel_predictive.h"
 #include "vk_kernel_hessian.h"
 
 using namespace vk;
@@ -78,6 +82,7 @@ struct Sampled {
   double *d_base = nullptr, *d_rows = nullptr, *d_th = nullptr;   // each problem's base row; the pending rows, their theory vectors
   int *d_which = nullptr, *d_row_which = nullptr;                 // realisation of each problem, of each pending row
   vkprior::Prior prior{};                  // the Gaussian prior the step kernels add to lnL (vk_fit_set_prior / vk_chain_set_prior)
+  bool keep_theory = false;                // the data-vector route stores the rows' theory vectors in d_th (vk_chain_set_predictive)
   std::string err;
 
   // doubles between two row sets of d_rows (fixed per handle: a best fit's launches shrink, its sets stay where they are)
@@ -295,8 +300,12 @@ static int sampled_ready(Sampled* f, const char* who, const char* noun, bool nam
 static int sampled_evaluate(Sampled* f, long long m, double* d_lnl, double* d_chi) {
   int rc;
   if (f->blocks.empty()) {
+    // (with lnL requested the data-vector route treats d_th as scratch and its fused tail never stores the theory vector:
+    // keep_theory asks for the stores - TheoryArgs::want_theory -, which change no bit of lnL; the realisation route writes d_th)
+    f->ctx->theory_wanted = f->keep_theory && !f->real;
     rc = f->real ? enqueue_realisations(f->ctx, &f->opts, f->d_rows, m, f->d_th, d_lnl, d_chi, f->d_row_which)
                  : vk_eval_batch_device_async(f->ctx, &f->opts, f->d_rows, m, d_lnl, d_chi, f->d_th);
+    f->ctx->theory_wanted = false;
   } else {
     // A joint fit: the launches of the joint entry points, enqueue only.  Stream order: the rows (and their realisation
     // indices) were written on the lead stream; every route first puts each block's stream behind an event of the lead stream
@@ -664,6 +673,24 @@ struct __attribute__((visibility("hidden"))) vk_chain : Sampled {
   TemperArgs temper{};
   void* d_temper = nullptr;
   double* d_logs = nullptr;
+  // the posterior-predictive state of vk_predictive.h, pivot_t | sum_t | sum_tt [R][N] | held [C][N] | dev [R][6] | n, n_skipped
+  // [R] | seen [C]: one allocation of its own, (C + 3 R) N + 6 R doubles and C + 2 R counters, made (and zeroed) by
+  // vk_chain_set_predictive
+  vkpred::Predictive pred{};
+  void* d_pred = nullptr;
+  size_t pred_bytes = 0;
+
+  void predictive_layout(Carve& c, int group) {
+    const size_t n = C, R = n / group, N = ctx->N;
+    c.take(pred.pivot_t, R * N);
+    c.take(pred.sum_t, R * N);
+    c.take(pred.sum_tt, R * N);
+    c.take(pred.held, n * N);
+    c.take(pred.dev, R * vkpred::kDeviance);
+    c.take(pred.n, R);
+    c.take(pred.n_skipped, R);
+    c.take(pred.seen, n);
+  }
 
   void temper_layout(Carve& c, int K) {
     const size_t n = C;
@@ -785,6 +812,47 @@ static void chain_drop_tempering(vk_chain* f) {
   f->d_temper = nullptr;
   f->d_logs = nullptr;
   f->temper = TemperArgs{};
+}
+
+// no predictive sums any more: the handle makes the launches it made before it had any
+static void chain_drop_predictive(vk_chain* f) {
+  if (f->d_pred) {
+    (void)hipSetDevice(f->ctx->device);
+    (void)hipFree(f->d_pred);
+  }
+  f->d_pred = nullptr;
+  f->pred = vkpred::Predictive{};
+  f->pred_bytes = 0;
+  f->keep_theory = false;
+}
+
+// the hold behind the step kernel of a launch of M rows (half == 0: a Metropolis launch), before the next evaluation overwrites d_th
+static int chain_hold(vk_chain* f, int M, int half, int side, bool all) {
+  HoldArgs h{};
+  h.p = f->pred;
+  h.th = f->d_th;
+  h.n_accept = f->d_acc;
+  h.M = M;
+  h.half = half;
+  h.side = side;
+  h.all = all ? 1 : 0;
+  hipLaunchKernelGGL(vk_chain_hold_kernel, dim3((unsigned)M), dim3(kChainBlock), 0, f->ctx->stream, h);
+  VK_SAMPLED_HIP(f, hipGetLastError());
+  return VK_OK;
+}
+
+// the predict kernel behind the hold of a kept step (a kept sweep's second half), or behind the start's hold: the pivots
+static int chain_predict(vk_chain* f, bool start) {
+  PredictArgs q{};
+  q.p = f->pred;
+  q.chi2 = f->d_chi;
+  q.lnl = f->d_lnl;
+  q.R = f->C / f->pred.group;
+  q.start = start ? 1 : 0;
+  const unsigned per = (unsigned)((f->pred.N + kChainBlock - 1) / kChainBlock);
+  hipLaunchKernelGGL(vk_chain_predict_kernel, dim3((unsigned)q.R * per), dim3(kChainBlock), 0, f->ctx->stream, q);
+  VK_SAMPLED_HIP(f, hipGetLastError());
+  return VK_OK;
 }
 
 // fresh energy sums and swap counters, in stream order
@@ -989,12 +1057,83 @@ int vk_chain_autocorr(vk_chain* f, double* pivot, double* total, double* head, d
   return VK_OK;
 }
 
+// The posterior-predictive sums (vk_predictive.h).  Everything the two kernels index with is checked here: the group and the
+// context's N fix the size of the state they address.
+int vk_chain_set_predictive(vk_chain* f, int32_t group) {
+  if (!f) return VK_E_ARG;
+  const std::string me = "vk_chain_set_predictive: ";
+  if (f->in_flight) return refused(f, me + "a block begun with vk_chain_begin is awaiting vk_chain_finish");
+  if (group == 0) {
+    chain_drop_predictive(f);
+    f->err.clear();
+    return VK_OK;
+  }
+  if (!f->blocks.empty())
+    return refused(f, me + "a joint handle (vk_chain_create_joint) is refused: its theory workspace is laid out by the route that "
+                           "evaluates it, not as one vector per row");
+  if (f->temper.K)
+    return refused(f, me + "the handle is tempered (vk_chain_set_tempering): a swap moves states without touching the accept "
+                           "counters the held vectors follow");
+  if (group < 1 || f->C % group)
+    return refused(f, me + std::to_string(f->C) + " chains are not a whole number of groups of " + std::to_string(group));
+  vkpred::Predictive keep = f->pred;
+  Carve count;
+  f->predictive_layout(count, group);
+  f->pred = keep;
+  void* mem = nullptr;
+  if (hipSetDevice(f->ctx->device) != hipSuccess || hipMalloc(&mem, count.bytes) != hipSuccess) {
+    (void)hipGetLastError();               // (the handle keeps the sums it had, as after a refusal)
+    f->err = me + "cannot allocate " + std::to_string(count.bytes) + " bytes of device memory";
+    return VK_E_HIP;
+  }
+  chain_drop_predictive(f);
+  f->d_pred = mem;
+  // (on the handle's stream, idle now: the kernels that add to the sums run there)
+  if (hipMemsetAsync(f->d_pred, 0, count.bytes, f->ctx->stream) != hipSuccess || hipStreamSynchronize(f->ctx->stream) != hipSuccess) {
+    (void)hipGetLastError();
+    chain_drop_predictive(f);
+    f->err = me + "hipMemsetAsync failed";
+    return VK_E_HIP;
+  }
+  Carve carve{static_cast<char*>(f->d_pred)};
+  f->predictive_layout(carve, group);
+  f->pred.on = 1;
+  f->pred.group = group;
+  f->pred.N = f->ctx->N;
+  f->pred_bytes = count.bytes;
+  f->keep_theory = true;
+  f->started = false;                      // the held vectors are taken at the start: chains already running need a new one
+  f->err.clear();
+  return VK_OK;
+}
+
+int vk_chain_predictive(vk_chain* f, double* pivot_t, double* sum_t, double* sum_tt, double* deviance, int64_t* n, int64_t* n_skipped,
+                        double* held) {
+  if (!f) return VK_E_ARG;
+  if (f->in_flight) return refused(f, "vk_chain_predictive: a block begun with vk_chain_begin is awaiting vk_chain_finish");
+  if (!f->pred.on) return refused(f, "vk_chain_predictive: the handle has no predictive sums (vk_chain_set_predictive)");
+  VK_SAMPLED_HIP(f, hipSetDevice(f->ctx->device));
+  const vkpred::Predictive& p = f->pred;
+  const size_t C = f->C, R = C / p.group, N = p.N;
+  auto home = [&](void* dst, const void* src, size_t bytes) { return dst ? hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) : hipSuccess; };
+  VK_SAMPLED_HIP(f, home(pivot_t, p.pivot_t, R * N * sizeof(double)));
+  VK_SAMPLED_HIP(f, home(sum_t, p.sum_t, R * N * sizeof(double)));
+  VK_SAMPLED_HIP(f, home(sum_tt, p.sum_tt, R * N * sizeof(double)));
+  VK_SAMPLED_HIP(f, home(deviance, p.dev, R * vkpred::kDeviance * sizeof(double)));
+  VK_SAMPLED_HIP(f, home(n, p.n, R * sizeof(int64_t)));
+  VK_SAMPLED_HIP(f, home(n_skipped, p.n_skipped, R * sizeof(int64_t)));
+  VK_SAMPLED_HIP(f, home(held, p.held, C * N * sizeof(double)));
+  f->err.clear();
+  return VK_OK;
+}
+
 void vk_chain_destroy(vk_chain* f) {
   if (!f) return;
   if (f->in_flight) (void)hipStreamSynchronize(f->ctx->stream);
   chain_drop_marginals(f);
   chain_drop_autocorr(f);
   chain_drop_tempering(f);
+  chain_drop_predictive(f);
   if (f->d_stretch) {
     (void)hipSetDevice(f->ctx->device);
     (void)hipFree(f->d_stretch);
@@ -1021,11 +1160,14 @@ int vk_chain_start(vk_chain* f, const double* x0) {
     f->ac.n = 0;
   }
   if (f->temper.K) VK_SAMPLED_HIP(f, chain_zero_tempering(f));          // ... and fresh energy sums and swap counters
+  if (f->pred.on) VK_SAMPLED_HIP(f, hipMemsetAsync(f->d_pred, 0, f->pred_bytes, ctx->stream));    // ... and fresh predictive sums
   ChainArgs a = chain_args(f);
   rc = sampled_launch(f, vk_chain_init_kernel, a.C, kChainBlock, a);
   if (rc == VK_OK) rc = sampled_evaluate(f, f->C, f->d_res_lnl, f->d_res_chi);
   a.adopt = 1;
   if (rc == VK_OK) rc = sampled_launch(f, vk_chain_step_kernel, a.C, kChainBlock, a);
+  if (rc == VK_OK && f->pred.on) rc = chain_hold(f, f->C, 0, 0, true);   // every chain holds its start's theory vector ...
+  if (rc == VK_OK && f->pred.on) rc = chain_predict(f, true);            // ... and the pivots are taken from it
   if (rc) return sampled_abort(f, rc);
   VK_SAMPLED_HIP(f, hipStreamSynchronize(ctx->stream));
   f->started = true;
@@ -1068,6 +1210,8 @@ int vk_chain_begin(vk_chain* f, int32_t n_steps, const double* dz, const double*
     if (hist) ++slot;
     rc = sampled_launch(f, vk_chain_step_kernel, a.C, kChainBlock, a);
     if (rc == VK_OK && kept && f->ac.on) rc = chain_series(f);
+    if (rc == VK_OK && f->pred.on) rc = chain_hold(f, f->C, 0, 0, false);      // (every step: accepts happen on steps not kept)
+    if (rc == VK_OK && kept && f->pred.on) rc = chain_predict(f, false);
   }
   if (rc) return sampled_abort(f, rc);
   f->in_flight = n_steps;
@@ -1155,8 +1299,10 @@ int vk_chain_begin_stretch(vk_chain* f, int32_t n_steps, int32_t walkers, const 
       rc = sampled_launch(f, vk_stretch_propose_kernel, a.M, kChainBlock, a);
       if (rc == VK_OK) rc = sampled_evaluate(f, (long long)M, f->d_res_lnl, f->d_res_chi);
       if (rc == VK_OK) rc = sampled_launch(f, vk_stretch_step_kernel, a.M, kChainBlock, a);
+      if (rc == VK_OK && f->pred.on) rc = chain_hold(f, (int)M, half, side, false);
     }
     if (rc == VK_OK && kept && f->ac.on) rc = chain_series(f);     // (behind the second half: all W walkers as the sweep leaves them)
+    if (rc == VK_OK && kept && f->pred.on) rc = chain_predict(f, false);
   }
   if (rc) return sampled_abort(f, rc);
   f->in_flight = n_steps;
@@ -1179,6 +1325,9 @@ int vk_chain_set_tempering(vk_chain* f, int32_t rungs, int32_t walkers, const do
     return VK_OK;
   }
   if (rungs < 1 || walkers < 1) return refused(f, me + "need rungs >= 1 and walkers >= 1 (rungs == 0 clears)");
+  if (f->pred.on)
+    return refused(f, me + "the handle keeps predictive sums (vk_chain_set_predictive), which follow the accept counters: a swap "
+                           "moves states without touching them");
   if (!betas) return refused(f, me + "NULL argument");
   const long long ladder = (long long)rungs * walkers;
   if (ladder > f->C || f->C % ladder)

@@ -522,14 +522,14 @@ class JointFit:
 
     def sample_chains(self, params, n_steps, walkers=8, seed=0, fixed=None, start=None, scatter=None, proposal=None, burn=0,
                       thin=1, keep_chain=True, device=True, move="metropolis", stretch_a=2.0, prior=None, marginals=None, autocorr=None, temper=None,
-                      **kwargs):
+                      predictive=None, **kwargs):
         """``walkers`` Metropolis chains of the joint lnL, stepped on the GPU (``device=True``) or by the NumPy loop over
         :meth:`log_likelihood_batch` that defines them (``device=False``).  Arguments and result as ``CCFFit.sample_chains``
         (:mod:`victor_amd.chains`), ``move="stretch"`` included; the result keeps this joint fit alive."""
         from .chains import sample_chains
         return sample_chains(self, params, n_steps, walkers, seed, fixed, start, scatter, proposal, burn, thin, keep_chain, device,
                              kwargs, move=move, stretch_a=stretch_a, prior=prior, marginals=marginals,
-                             autocorr=autocorr, temper=temper)
+                             autocorr=autocorr, temper=temper, predictive=predictive)
 
     @property
     def n_data(self):
@@ -586,7 +586,7 @@ class JointRealisations:
 
     def sample_chains(self, params, n_steps, walkers=8, seed=0, fixed=None, start=None, scatter=None, proposal=None, burn=0,
                       thin=1, keep_chain=True, device=True, move="metropolis", stretch_a=2.0, prior=None, marginals=None, autocorr=None, temper=None,
-                      **kwargs):
+                      predictive=None, **kwargs):
         """``walkers`` Metropolis chains of EVERY joint realisation in lock step, on the GPU (``device=True``) or by the NumPy
         loop over :meth:`log_likelihood_pairs` that defines them (``device=False``).  Arguments and result as
         ``Realisations.sample_chains`` (``move="stretch"``: one ensemble per joint realisation); ``start`` may be the ``BestFit``
@@ -594,7 +594,7 @@ class JointRealisations:
         from .chains import sample_chains
         return sample_chains(self.joint, params, n_steps, walkers, seed, fixed, start, scatter, proposal, burn, thin, keep_chain,
                              device, kwargs, realisations=self, move=move, stretch_a=stretch_a, prior=prior, marginals=marginals,
-                             autocorr=autocorr, temper=temper)
+                             autocorr=autocorr, temper=temper, predictive=predictive)
 
     def _eval(self, params, kwargs, which=None):
         joint = self.joint

@@ -154,7 +154,7 @@ class Realisations:
 
     def sample_chains(self, params, n_steps, walkers=8, seed=0, fixed=None, start=None, scatter=None, proposal=None, burn=0,
                       thin=1, keep_chain=True, device=True, move="metropolis", stretch_a=2.0, prior=None, marginals=None, autocorr=None, temper=None,
-                      **kwargs):
+                      predictive=None, **kwargs):
         """``walkers`` Metropolis chains of EVERY realisation, all of them in lock step: problem i samples lnL against realisation
         ``numbers[i]``, on the GPU (``device=True``) or by the NumPy loop over :meth:`log_likelihood_pairs` that defines the
         chains (``device=False``).  Arguments and result as ``CCFFit.sample_chains`` (:mod:`victor_amd.chains`); ``start`` may be
@@ -163,7 +163,7 @@ class Realisations:
         from .chains import sample_chains
         return sample_chains(self.fit, params, n_steps, walkers, seed, fixed, start, scatter, proposal, burn, thin, keep_chain,
                              device, kwargs, realisations=self, move=move, stretch_a=stretch_a, prior=prior, marginals=marginals,
-                             autocorr=autocorr, temper=temper)
+                             autocorr=autocorr, temper=temper, predictive=predictive)
 
     def log_likelihood_pairs(self, params, which, **kwargs):
         """(lnL, chi2), each ``(n_points,)``: point p against realisation ``numbers[which[p]]`` only - the form an ensemble of
