@@ -1,7 +1,7 @@
 """Metropolis chains stepped on the GPU (victor_amd/chains.py, vk_chain_begin) against the NumPy loop that defines them
 (device=False: one log_likelihood_pairs / log_likelihood_batch call per step): positions, decisions and log-likelihoods, every
-kept sample against the likelihood and the oracle, determinism and cuts, the moment sums, the prior box, and the
-best_fit -> sample_chains workflow.  No test asserts a posterior mean or width against a number."""
+kept sample against the likelihood and the oracle, determinism and cuts, the moment sums, the prior box, the
+best_fit -> sample_chains workflow, and several optional states (histograms, series, predictive sums, tempering) on one handle.  No test asserts a posterior mean or width against a number."""
 
 import faulthandler
 import os
@@ -218,3 +218,104 @@ def test_best_fit_then_chains(rs, single_fits):
     first = rs.sample_chains(PARAMS, 0, walkers=8, start=bf, seed=1)
     assert same_bytes(first.x, ch.pivot) and np.all(np.isfinite(first.lnl))
     assert np.all(np.isfinite(ch.lnl)) and ch.mean.shape == (16, 4) and np.all(np.isfinite(ch.cov))
+
+
+# ------------------------------------------------------------------ several optional states on one handle ---------------------
+# Each optional state of a handle (histograms, the autocorrelation series, predictive sums, tempering) has a test module of its
+# own; here they share a handle, across a block boundary (64 + 5 steps), kept and unkept steps (burn 3, thin 2) and an extend.
+# Shapes, options and bounds are those of the modules named in the imports: nothing here is a new tolerance.
+@pytest.fixture(scope="module")
+def rs2(rs):
+    """Two realisations: with W = 8, 16 chains."""
+    return rs.fit.realisations([0, 1])
+
+
+def same_series(a, b, what):
+    assert a.autocorr.n == b.autocorr.n, what
+    for k, v in a.autocorr.state.items():
+        assert same_bytes(v, b.autocorr.state[k]), (what, k)
+
+
+@pytest.mark.parametrize("move", ["metropolis", "stretch"])
+def test_marginals_autocorr_and_predictive_share_a_handle(rs2, move):
+    from tests.test_gpu_predictive import LAGS, RUNS, check_history, check_routes
+    from tests.test_gpu_priors import same_run
+    from tests.test_marginals import same_marginals
+    block, kw, option = RUNS[move]
+    kw = dict(kw, burn=3, thin=2, marginals=option, autocorr=LAGS, predictive=True)
+    ref = rs2.sample_chains(block, 69, device=False, **kw).extend(5)
+    dev = rs2.sample_chains(block, 69, **kw).extend(5)
+    assert dev.chain.shape == (36, 2, 8, 3) and dev.n_steps == 74                # steps 3, 5, .. 73: both sides of the block of 64
+    assert np.all((0 < dev.n_accept) & (dev.n_accept < 74))
+    same_run(dev, ref, move)
+    same_marginals(dev.marginals, ref.marginals, move)
+    assert dev.marginals.n.tolist() == [36 * 8] * 2
+    same_series(dev, ref, move)
+    assert dev.autocorr.n == 36
+    bounds = check_history(rs2.fit, dev, f"three states on a handle, {move}, device")
+    check_routes(dev, ref, bounds, f"three states on a handle, {move}")
+
+
+def test_tempering_marginals_and_autocorr_share_a_handle(rs2):
+    from tests.test_gpu_marginals import OPTION
+    from tests.test_gpu_predictive import LAGS
+    from tests.test_gpu_tempering import same_tempered
+    from tests.test_marginals import same_marginals
+    kw = dict(walkers=4, seed=2, burn=3, thin=2, fixed={"epsilon": 1.0}, temper={"betas": [1.0, 0.3], "swap_every": 2},
+              marginals=OPTION, autocorr=LAGS)
+    ref = rs2.sample_chains(PARAMS, 69, device=False, **kw).extend(5)
+    dev = rs2.sample_chains(PARAMS, 69, **kw).extend(5)
+    assert dev.chain.shape == (36, 2, 4, 3)
+    assert ref.tempering.n_swap_try[:, 0].tolist() == [[19] * 4] * 2        # 37 events; two rungs have a pair at even parity only
+    assert 0 < ref.tempering.n_swap_acc.sum() < ref.tempering.n_swap_try.sum()
+    same_tempered(dev, ref, "tempering with histograms and series")
+    same_marginals(dev.marginals, ref.marginals, "tempering with histograms and series")
+    same_series(dev, ref, "tempering with histograms and series")
+
+
+def test_clearing_one_state_leaves_the_others_on_the_handle(rs2):
+    """Through the C ABI: three states set, the autocorrelation cleared again, a second start, one block - the histograms and
+    the predictive sums are those of the block's own history, and the walk is that of a handle that never had any of them."""
+    from types import SimpleNamespace
+    from tests.test_gpu_marginals import HI_R, LO_R, PAIRS_R, read_marginals, set_marginals
+    from tests.test_gpu_predictive import read_predictive, restate, within
+    from tests.test_gpu_stretch import Raw
+    from victor_amd.marginals import Binning
+    rng = np.random.default_rng(4)
+    x0 = np.ascontiguousarray(rs2.sample_chains(PARAMS, 0, walkers=8, seed=2, fixed={"epsilon": 1.0}).pivot.reshape(16, 3))
+    names = ["fsigma8", "beta", "sigma_v"]
+    width = np.array([PARAMS[n]["proposal"] for n in names], dtype=float)
+    dz, lu = width * rng.standard_normal((6, 16, 3)), np.log(rng.random((6, 16)))
+    plain, raw = Raw(rs2, x0, 8), Raw(rs2, x0, 8)
+    try:
+        assert plain.start(x0) == 0, plain.error()
+        assert plain.metropolis(dz, lu, 0) == (0, 6), plain.error()
+        want = plain.finish(6)
+        assert raw.start(x0) == 0, raw.error()
+        assert set_marginals(raw, 8, 16, LO_R, HI_R, PAIRS_R, 4) == 0, raw.error()
+        assert raw.lib.vk_chain_set_autocorr(raw.h, 8, 16) == 0, raw.error()
+        assert raw.lib.vk_chain_set_predictive(raw.h, 8) == 0, raw.error()
+        assert raw.lib.vk_chain_set_autocorr(raw.h, 0, 0) == 0, raw.error()
+        assert raw.start(x0) == 0, raw.error()
+        assert raw.metropolis(dz, lu, 0) == (0, 6), raw.error()
+        got = raw.finish(6)
+        assert got[0] == 0 and all(same_bytes(u, v) for u, v in zip(got[1:], want[1:])), raw.error()
+        assert all(same_bytes(u, v) for u, v in zip(raw.state(), plain.state()))
+        assert raw.lib.vk_chain_autocorr(raw.h, *[None] * 6) == -1 and "has no autocorrelation" in raw.error()
+        q = Binning(names, 16, LO_R, HI_R, PAIRS_R, [("fsigma8", "sigma_v"), ("beta", "sigma_v")], 4)
+        h1, h2 = q.zeros(2)
+        for t in range(6):
+            q.add(h1, h2, got[1][t], 8)
+        d1, d2 = read_marginals(raw, 2, 16, 2, 4)
+        assert np.array_equal(d1, h1) and np.array_equal(d2, h2) and np.all(d1.sum(axis=2) == 6 * 8)
+        state = read_predictive(raw, 2)
+        ch = SimpleNamespace(predictive=SimpleNamespace(state=state), names=names, fixed=raw.fixed, chain=got[1].reshape(6, 2, 8, 3),
+                             lnl_chain=got[2].reshape(6, 2, 8), chi2_chain=got[3].reshape(6, 2, 8))
+        rules = restate(rs2.fit, ch)
+        assert state["n"].tolist() == [48] * 2 and np.array_equal(state["n"], rules["n"]) and not state["n_skipped"].any()
+        within(state["sum_t"], rules["sum_t"], rules["b_t"], "one state cleared: sum_t against the history")
+        within(state["sum_tt"], rules["sum_tt"], rules["b_tt"], "one state cleared: sum_tt against the history")
+        within(state["deviance"][:, 2:], rules["dev"], rules["b_dev"], "one state cleared: deviance sums against the history")
+    finally:
+        plain.close()
+        raw.close()

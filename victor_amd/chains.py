@@ -325,15 +325,17 @@ class Chains:
             done += len(z)
 
     def _run_host(self, n_steps):
+        """Metropolis steps.  Under replica exchange (:mod:`victor_amd.tempering`) the decision is the tempered one at each chain's
+        beta, a kept step enters the energy sums, and a swap event may follow the step."""
         if self.move == "stretch":
             return self._run_host_stretch(n_steps)
-        if self._temper is not None:
-            return self._run_host_tempered(n_steps)
+        from .tempering import gain as tempered_gain
+        q, prior = self._temper, self._prior
         lo, hi = self._lo, self._hi
         x, lnl, chi2 = self._x, self._lnl, self._chi2
         done = 0
         while done < n_steps:
-            dz, logu = self._piece(n_steps - done)
+            dz, logu, *logs = self._piece(n_steps - done)            # (logs: the swap levels of a tempered block)
             for t in range(len(dz)):
                 prop = x + dz[t]
                 inside = ((prop >= lo) & (prop <= hi)).all(axis=1)
@@ -341,11 +343,15 @@ class Chains:
                 lnl_p, chi2_p = self._evaluate(rows)
                 lnl_p = np.where(inside, lnl_p, -np.inf)
                 with np.errstate(invalid="ignore"):
-                    if self._prior is None:
+                    lp = () if prior is None else (prior.lnprior(prop), prior.lnprior(x))
+                    if q is not None:                                # (beta lnL' + lp') - (beta lnL + lp)
+                        gain = tempered_gain(q.beta, lnl_p, lnl, *lp)
+                    elif prior is None:
                         gain = lnl_p - lnl
                     else:                                            # (lnL' + lp') - (lnL + lp)
-                        gain = (lnl_p + self._prior.lnprior(prop)) - (lnl + self._prior.lnprior(x))
-                    accept = logu[t] < gain                          # NaN (both -inf, or a NaN lnL): False
+                        gain = (lnl_p + lp[0]) - (lnl + lp[1])
+                    # NaN (both -inf, 0 * inf, a NaN lnL): False; outside the box the gain is -inf or NaN, `inside` changes nothing
+                    accept = inside & (logu[t] < gain)
                     margin = np.abs(gain - logu[t])
                 margin = margin[np.isfinite(margin)]
                 if margin.size:
@@ -357,45 +363,12 @@ class Chains:
                 self._n_accept += accept
                 if self._pred is not None:
                     self._hold(np.arange(len(x)), rows)
-                self._account(x, lnl, chi2)
-            done += len(dz)
-
-    def _run_host_tempered(self, n_steps):
-        """The loop of ``_run_host`` under replica exchange (:mod:`victor_amd.tempering`): the tempered decision at each chain's
-        beta, the energy sums of a kept step, and the swap event that follows a step."""
-        from .tempering import gain as tempered_gain
-        q = self._temper
-        lo, hi = self._lo, self._hi
-        x, lnl, chi2 = self._x, self._lnl, self._chi2
-        done = 0
-        while done < n_steps:
-            dz, logu, logs = self._piece(n_steps - done)
-            for t in range(len(dz)):
-                prop = x + dz[t]
-                inside = ((prop >= lo) & (prop <= hi)).all(axis=1)
-                rows = np.where(inside[:, None], prop, x)            # outside: the current position, result discarded
-                lnl_p, chi2_p = self._evaluate(rows)
-                lnl_p = np.where(inside, lnl_p, -np.inf)
-                with np.errstate(invalid="ignore"):
-                    if self._prior is None:
-                        gain = tempered_gain(q.beta, lnl_p, lnl)
-                    else:                                            # (beta lnL' + lp') - (beta lnL + lp)
-                        gain = tempered_gain(q.beta, lnl_p, lnl, self._prior.lnprior(prop), self._prior.lnprior(x))
-                    accept = inside & (logu[t] < gain)               # NaN (0 * inf, inf - inf, a NaN lnL): False
-                    margin = np.abs(gain - logu[t])
-                margin = margin[np.isfinite(margin)]
-                if margin.size:
-                    self.decision_margin = min(self.decision_margin, float(margin.min()))
-                self._n_outside += ~inside
-                x[accept] = prop[accept]
-                lnl[accept] = lnl_p[accept]
-                chi2[accept] = chi2_p[accept]
-                self._n_accept += accept
                 step = self.n_steps
-                if self._kept(step):
+                if q is not None and self._kept(step):
                     q.energy_add(lnl)
                 self._account(x, lnl, chi2)                          # (before the swap: a kept step is what the decision left)
-                q.swap(step, x, lnl, chi2, logs[t])
+                if q is not None:
+                    q.swap(step, x, lnl, chi2, logs[0][t])
             done += len(dz)
 
     # ------------------------------------------------------------------ the device route ---------------------------------
@@ -443,52 +416,49 @@ class Chains:
     def _read_device(self):
         lib, h = self._dev
         C_, d = self._RK * self.W, len(self.names)
-        i64 = C.POINTER(C.c_int64)
+        dp = N.as_dp
+
+        def i64(a):
+            return a.ctypes.data_as(C.POINTER(C.c_int64))
         self._x, self._lnl, self._chi2 = np.empty((C_, d)), np.empty(C_), np.empty(C_)
         self._n_accept, self._n_kept = np.empty(C_, dtype=np.int64), np.empty(C_, dtype=np.int64)
         self._pivot, self._sum1, self._sum2 = np.empty((C_, d)), np.empty((C_, d)), np.empty((C_, d, d))
-        self._check(lib.vk_chain_state(h, N.as_dp(self._x), N.as_dp(self._lnl), N.as_dp(self._chi2),
-                                       self._n_accept.ctypes.data_as(i64), None, self._n_kept.ctypes.data_as(i64),
-                                       N.as_dp(self._pivot), N.as_dp(self._sum1), N.as_dp(self._sum2)), "vk_chain_state")
+        self._check(lib.vk_chain_state(h, dp(self._x), dp(self._lnl), dp(self._chi2), i64(self._n_accept), None, i64(self._n_kept),
+                                       dp(self._pivot), dp(self._sum1), dp(self._sum2)), "vk_chain_state")
         if self._binning is not None:
-            self._check(lib.vk_chain_marginals(h, self._h1.ctypes.data_as(i64), self._h2.ctypes.data_as(i64)), "vk_chain_marginals")
+            self._check(lib.vk_chain_marginals(h, i64(self._h1), i64(self._h2)), "vk_chain_marginals")
         if self._series is not None:
             q, n = self._series, C.c_int64(0)
-            self._check(lib.vk_chain_autocorr(h, N.as_dp(q.pivot), N.as_dp(q.total), N.as_dp(q.head), N.as_dp(q.ring), N.as_dp(q.acc),
-                                              C.byref(n)), "vk_chain_autocorr")
+            self._check(lib.vk_chain_autocorr(h, dp(q.pivot), dp(q.total), dp(q.head), dp(q.ring), dp(q.acc), C.byref(n)), "vk_chain_autocorr")
             q.n = int(n.value)
         if self._pred is not None:
             q = self._pred
-            self._check(lib.vk_chain_predictive(h, N.as_dp(q.pivot_t), N.as_dp(q.sum_t), N.as_dp(q.sum_tt), N.as_dp(q.deviance),
-                                                q.n.ctypes.data_as(i64), q.n_skipped.ctypes.data_as(i64), N.as_dp(q.held)),
-                        "vk_chain_predictive")
+            self._check(lib.vk_chain_predictive(h, dp(q.pivot_t), dp(q.sum_t), dp(q.sum_tt), dp(q.deviance), i64(q.n), i64(q.n_skipped),
+                                                dp(q.held)), "vk_chain_predictive")
         if self._temper is not None:
             q = self._temper
-            self._check(lib.vk_chain_tempering(h, N.as_dp(q.pivot_e), N.as_dp(q.e1), N.as_dp(q.e2), q.n_e.ctypes.data_as(i64),
-                                               q.n_swap_try.ctypes.data_as(i64), q.n_swap_acc.ctypes.data_as(i64)), "vk_chain_tempering")
+            self._check(lib.vk_chain_tempering(h, dp(q.pivot_e), dp(q.e1), dp(q.e2), i64(q.n_e), i64(q.n_swap_try), i64(q.n_swap_acc)),
+                        "vk_chain_tempering")
 
-    def _set_predictive_device(self):
-        """Ask the handle for the predictive sums (before ``vk_chain_start``): the W chains of a problem pool."""
+    def _attach_device(self, set_prior, x0):
+        """Hand the handle what the chains were asked for - the prior (``set_prior``: the call that does it), the binning, the
+        series' shape, the ladder, the predictive sums: the W chains of a problem pool - and start the chains at ``x0``.  (The
+        handle is this object's from here on: a refusal destroys it with the object.)"""
         lib, h = self._dev
-        self._check(lib.vk_chain_set_predictive(h, self.W), "vk_chain_set_predictive")
-
-    def _set_tempering_device(self):
-        """Hand the ladder to the handle (before ``vk_chain_start``)."""
-        lib, h = self._dev
-        self._check(lib.vk_chain_set_tempering(h, self._K, self.W, N.as_dp(self._temper.ladder.betas)), "vk_chain_set_tempering")
-
-    def _set_marginals_device(self):
-        """Hand the binning to the handle (before ``vk_chain_start``): the W chains of a problem pool."""
-        lib, h = self._dev
-        q = self._binning
-        pairs = q.pairs.ctypes.data_as(C.POINTER(C.c_int32)) if len(q.pairs) else None
-        self._check(lib.vk_chain_set_marginals(h, self.W, q.n_bins, N.as_dp(q.a), N.as_dp(q.b), len(q.pairs), pairs, q.n_bins2),
-                    "vk_chain_set_marginals")
-
-    def _set_autocorr_device(self):
-        """Hand the series' shape to the handle (before ``vk_chain_start``): the W chains of a problem make one series."""
-        lib, h = self._dev
-        self._check(lib.vk_chain_set_autocorr(h, self.W, self._series.L), "vk_chain_set_autocorr")
+        if self._prior is not None:
+            set_prior("vk_chain_set_prior", lib, h, self._prior)
+        if self._binning is not None:
+            q = self._binning
+            pairs = q.pairs.ctypes.data_as(C.POINTER(C.c_int32)) if len(q.pairs) else None
+            self._check(lib.vk_chain_set_marginals(h, self.W, q.n_bins, N.as_dp(q.a), N.as_dp(q.b), len(q.pairs), pairs, q.n_bins2),
+                        "vk_chain_set_marginals")
+        if self._series is not None:
+            self._check(lib.vk_chain_set_autocorr(h, self.W, self._series.L), "vk_chain_set_autocorr")
+        if self._temper is not None:
+            self._check(lib.vk_chain_set_tempering(h, self._K, self.W, N.as_dp(self._temper.ladder.betas)), "vk_chain_set_tempering")
+        if self._pred is not None:
+            self._check(lib.vk_chain_set_predictive(h, self.W), "vk_chain_set_predictive")
+        self._check(lib.vk_chain_start(h, N.as_dp(N.f64(x0))), "vk_chain_start")
 
     def __del__(self):
         dev = getattr(self, "_dev", None)
@@ -751,18 +721,7 @@ def sample_chains(fit, params, n_steps, walkers=8, seed=0, fixed=None, start=Non
     if handle:
         ch._refresh = refresh                                # (keeps the realisations and the contexts the handle runs on)
         ch._fit = fit                                        # (a joint fit owns the covariance handles the chains read)
-    if handle and prior is not None:
-        q.set_prior("vk_chain_set_prior", lib, h, prior)  # (the handle is the Chains' from here on: a refusal destroys it with ch)
-    if handle and binning is not None:
-        ch._set_marginals_device()
-    if handle and lags is not None:
-        ch._set_autocorr_device()
-    if handle and ladder is not None:
-        ch._set_tempering_device()
-    if handle and predictive:
-        ch._set_predictive_device()
-    if handle:
-        ch._check(handle[0].vk_chain_start(handle[1], N.as_dp(N.f64(x0))), "vk_chain_start")
+        ch._attach_device(q.set_prior, x0)
     else:
         ch._start_host(x0)
     return ch.extend(n_steps)

@@ -11,6 +11,12 @@
 // to all of them (vk_row_select.h); a handle of the other create calls has one row set and makes the launches it always made.
 // The same object serves every flavour of the library.
 //
+// Host code, top to bottom: `Sampled` and what both kinds of handle share - Carve / carve_alloc lay every allocation out,
+// sampled_create, sampled_ready, sampled_evaluate, sampled_launch makes every launch of the unit and sampled_home every download -;
+// best fits and their Hessians; chains, whose optional state (marginals, autocorrelation, tempering, predictive sums, the stretch
+// buffers) a DevBlock each owns, with the refusals the chain entry points share and the check, the history slot of a step and
+// the ending of the three begin calls stated once.
+//
 // Device code lives in the headers next to this file:
 //   vk_sampled_row.h     a parameter row from a base row and the sampled values
 //   vk_kernel_fit.h      the best-fit search (vk_fit_run): start simplex, step and re-layout kernels, one thread per problem, over
@@ -39,6 +45,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 #include <string>
 #include <vector>
@@ -114,6 +121,25 @@ struct Carve {
     bytes += count * sizeof(T);
   }
 };
+
+// Count a layout with a Carve, allocate that many bytes on `device`, hand the layout's pointers out over them.  False: nothing
+// is allocated (`bytes` says what was asked for).
+template <class Layout>
+static bool carve_alloc(int device, void*& mem, size_t& bytes, Layout&& layout) {
+  Carve count;
+  layout(count);
+  bytes = count.bytes;
+  mem = nullptr;
+  if (hipSetDevice(device) != hipSuccess || hipMalloc(&mem, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    mem = nullptr;
+    return false;
+  }
+  Carve carve{static_cast<char*>(mem)};
+  layout(carve);
+  return true;
+}
+static std::string cannot_allocate(size_t bytes) { return "cannot allocate " + std::to_string(bytes) + " bytes of device memory"; }
 
 // a HIP call on behalf of a handle: the error text goes to the handle (vk_fit_last_error / vk_chain_last_error)
 #define VK_SAMPLED_HIP(f, call)                                                        \
@@ -222,15 +248,11 @@ static H* sampled_create(const char* who, const char* noun, vk_ctx* const* ctxs,
   f->real = which != nullptr;
   f->max_which = max_which;
   f->shape(n, lo, hi);
-  Carve count;
-  f->layout(count);
-  if (hipSetDevice(ctx->device) != hipSuccess || hipMalloc(&f->d_mem, count.bytes) != hipSuccess) {
-    (void)hipGetLastError();
+  size_t bytes = 0;
+  if (!carve_alloc(ctx->device, f->d_mem, bytes, [&](Carve& c) { f->layout(c); })) {
     delete f;
-    return bail(me + "cannot allocate " + std::to_string(count.bytes) + " bytes of device memory");
+    return bail(me + cannot_allocate(bytes));
   }
-  Carve mem{static_cast<char*>(f->d_mem)};
-  f->layout(mem);
   bool ok = hipMemcpy(f->d_base, base_rows, (size_t)f->sets * n * VK_NPAR * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
   if (ok && which) ok = hipMemcpy(f->d_which, which, (size_t)n * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
   if (!ok) {
@@ -239,6 +261,12 @@ static H* sampled_create(const char* who, const char* noun, vk_ctx* const* ctxs,
     return bail(me + "upload failed");
   }
   return f;
+}
+
+// the _blocks create calls, whose param_block is not optional
+static bool no_param_block(const char* who, const int32_t* param_block, char* err, size_t errlen) {
+  if (!param_block && err && errlen) snprintf(err, errlen, "%s: NULL argument", who);
+  return !param_block;
 }
 
 // a call refused before anything was enqueued: the text goes to the handle
@@ -328,11 +356,27 @@ static int sampled_evaluate(Sampled* f, long long m, double* d_lnl, double* d_ch
   return rc;
 }
 
-// a kernel of one thread per problem behind it
+// a kernel of `threads` threads (one per problem; of a kernel of one block per item, items x block) on the handle's stream
 template <class Args>
-static int sampled_launch(Sampled* f, void (*kern)(Args), int threads, int block, const Args& a) {
+static int sampled_launch(Sampled* f, void (*kern)(Args), long long threads, int block, const Args& a) {
   hipLaunchKernelGGL(kern, dim3((unsigned)((threads + block - 1) / block)), dim3(block), 0, f->ctx->stream, a);
   VK_SAMPLED_HIP(f, hipGetLastError());
+  return VK_OK;
+}
+
+// Device arrays copied home, each if the caller gave it a destination: plain copies, complete on return, or (on_stream) enqueued
+// on the handle's stream for the caller to wait for.
+struct Home {
+  void* dst;
+  const void* src;
+  size_t bytes;
+};
+static int sampled_home(Sampled* f, std::initializer_list<Home> arrays, bool on_stream = false) {
+  for (const Home& a : arrays) {
+    if (!a.dst || !a.bytes) continue;
+    if (on_stream) VK_SAMPLED_HIP(f, hipMemcpyAsync(a.dst, a.src, a.bytes, hipMemcpyDeviceToHost, f->ctx->stream));
+    else VK_SAMPLED_HIP(f, hipMemcpy(a.dst, a.src, a.bytes, hipMemcpyDeviceToHost));
+  }
   return VK_OK;
 }
 
@@ -456,10 +500,7 @@ vk_fit* vk_fit_create_joint_blocks(vk_ctx* const* ctxs, int32_t n_ctx, vk_joint_
                                    int32_t n_problems, int32_t n_params, const int32_t* columns, const int32_t* param_block,
                                    const double* lo, const double* hi, const double* base_rows, double alpha, const int32_t* which,
                                    char* err, size_t errlen) {
-  if (!param_block) {
-    if (err && errlen) snprintf(err, errlen, "vk_fit_create_joint_blocks: NULL argument");
-    return nullptr;
-  }
+  if (no_param_block("vk_fit_create_joint_blocks", param_block, err, errlen)) return nullptr;
   return sampled_create<vk_fit>("vk_fit_create_joint_blocks", "problem", ctxs, n_ctx, true, cov, opts, n_problems, n_params, columns,
                                 param_block, lo, hi, base_rows, alpha, which, err, errlen);
 }
@@ -581,18 +622,12 @@ static int hessian_run(vk_fit* f, const HessMem& m, const double* x, const doubl
     VK_SAMPLED_HIP(f, hipMemcpyAsync(m.values + g0, f->d_lnl, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     VK_SAMPLED_HIP(f, hipMemcpyAsync(m.chis + g0, f->d_chi, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
   }
-  hipLaunchKernelGGL(vk_hess_assemble_kernel, dim3((unsigned)R), dim3(kHessBlock), 0, ctx->stream, q);
-  VK_SAMPLED_HIP(f, hipGetLastError());
-  auto home = [&](void* dst, const void* src, size_t bytes) {
-    return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess;
-  };
-  VK_SAMPLED_HIP(f, home(values, m.values, R * M * sizeof(double)));
-  VK_SAMPLED_HIP(f, home(a, m.a, R * d * d * sizeof(double)));
-  VK_SAMPLED_HIP(f, home(hess, m.hess, R * d * d * sizeof(double)));
-  VK_SAMPLED_HIP(f, home(cov, m.cov, R * d * d * sizeof(double)));
-  VK_SAMPLED_HIP(f, home(lnpost, m.lnpost, R * sizeof(double)));
-  VK_SAMPLED_HIP(f, home(chi2, m.chi2, R * sizeof(double)));
-  VK_SAMPLED_HIP(f, home(status, m.status, R * sizeof(int)));
+  int rc = sampled_launch(f, vk_hess_assemble_kernel, (long long)R * kHessBlock, kHessBlock, q);      // one wave per problem
+  const size_t one = R * sizeof(double), mat = one * d * d;
+  if (rc == VK_OK)
+    rc = sampled_home(f, {{values, m.values, one * M}, {a, m.a, mat}, {hess, m.hess, mat}, {cov, m.cov, mat}, {lnpost, m.lnpost, one},
+                          {chi2, m.chi2, one}, {status, m.status, R * sizeof(int)}}, true);
+  if (rc) return rc;
   VK_SAMPLED_HIP(f, hipStreamSynchronize(ctx->stream));
   return VK_OK;
 }
@@ -619,16 +654,12 @@ int vk_fit_hessian(vk_fit* f, const double* x, const double* h, double* values, 
     }
   VK_SAMPLED_HIP(f, hipSetDevice(f->ctx->device));
   HessMem m;
-  Carve count;
-  m.layout(count, R, d, (size_t)vkhess::n_points(f->P));
   void* mem = nullptr;
-  if (hipMalloc(&mem, count.bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    f->err = "vk_fit_hessian: cannot allocate " + std::to_string(count.bytes) + " bytes of device memory";
+  size_t bytes = 0;
+  if (!carve_alloc(f->ctx->device, mem, bytes, [&](Carve& c) { m.layout(c, R, d, (size_t)vkhess::n_points(f->P)); })) {
+    f->err = "vk_fit_hessian: " + cannot_allocate(bytes);
     return VK_E_HIP;
   }
-  Carve carve{static_cast<char*>(mem)};
-  m.layout(carve, R, d, (size_t)vkhess::n_points(f->P));
   rc = hessian_run(f, m, x, h, values, a, hess, cov, lnpost, chi2, status);
   if (rc != VK_OK) rc = sampled_abort(f, rc);
   (void)hipFree(mem);
@@ -643,6 +674,40 @@ int vk_fit_hessian(vk_fit* f, const double* x, const double* h, double* values, 
 // and the step kernel behind it, which decides and writes the next rows.  No host synchronisation and no graph inside a block of
 // up to 64 steps: vk_chain_begin uploads the block's random numbers and enqueues all of it, vk_chain_finish waits and brings the
 // block's kept steps home, and the host draws the next block's numbers in between.
+
+// Device memory a chain handle owns beside its one allocation, for state that is asked for after the create call (hidden, as
+// the handles: no symbol of its leaves the library).
+struct __attribute__((visibility("hidden"))) DevBlock {
+  void* p = nullptr;
+  size_t bytes = 0;
+  // Allocate what `layout` counts and hand its pointers out; zeroed on the handle's stream (idle now: the kernels that write
+  // the block run there) and waited for.  On failure nothing is held and the handle has the text, under the caller's name.
+  template <class Layout>
+  int make(Sampled* f, const std::string& me, Layout&& layout) {
+    if (!carve_alloc(f->ctx->device, p, bytes, layout)) {
+      f->err = me + cannot_allocate(bytes);
+      bytes = 0;
+      return VK_E_HIP;
+    }
+    if (zero(f) != hipSuccess || hipStreamSynchronize(f->ctx->stream) != hipSuccess) {
+      (void)hipGetLastError();
+      drop(f);
+      f->err = me + "hipMemsetAsync failed";
+      return VK_E_HIP;
+    }
+    return VK_OK;
+  }
+  hipError_t zero(Sampled* f) const { return hipMemsetAsync(p, 0, bytes, f->ctx->stream); }      // in stream order
+  void drop(Sampled* f) {
+    if (p) {
+      (void)hipSetDevice(f->ctx->device);
+      (void)hipFree(p);
+    }
+    p = nullptr;
+    bytes = 0;
+  }
+};
+
 struct __attribute__((visibility("hidden"))) vk_chain : Sampled {
   int C = 0, T = 0;                        // chains, entries of a packed second-moment triangle
   vkchain::Box box{};
@@ -653,57 +718,71 @@ struct __attribute__((visibility("hidden"))) vk_chain : Sampled {
   double *d_x0 = nullptr, *d_res_lnl = nullptr, *d_res_chi = nullptr;
   double *d_dz = nullptr, *d_logu = nullptr, *d_hx = nullptr, *d_hl = nullptr, *d_hc = nullptr;
   long long *d_acc = nullptr, *d_steps = nullptr, *d_kept = nullptr;
-  // a stretch block's numbers [64][2][C / 2] and the proposals of a half-step [P][C / 2]: one allocation of its own, made by the
-  // first vk_chain_begin_stretch
-  void* d_stretch = nullptr;
+  std::vector<int> h_which;                // the chains' realisation indices, read back for chain_one_realisation
+  // What a handle may hold beside its one allocation: a DevBlock each, and the words the kernels take (whose pointers lie in it).
+  // a stretch block's numbers [64][2][C / 2] and the proposals of a half-step [P][C / 2], made by the first vk_chain_begin_stretch
+  DevBlock stretch;
   double *d_sz = nullptr, *d_slz = nullptr, *d_slogu = nullptr, *d_prop = nullptr;
   int* d_partner = nullptr;
-  // the marginal histograms h1 | h2 of vk_marginals.h: one allocation of its own, made (and zeroed) by vk_chain_set_marginals
+  // the marginal histograms h1 | h2 of vk_marginals.h (vk_chain_set_marginals)
+  DevBlock marg_mem;
   vkmarg::Marginals marg{};
-  void* d_marg = nullptr;
-  size_t marg_n1 = 0, marg_n2 = 0;         // counts of h1, of h2
-  // the series state pivot | total | head | ring | acc of vk_autocorr.h: one allocation of its own, made (and zeroed) by
-  // vk_chain_set_autocorr; ac.n counts the kept steps enqueued since vk_chain_start
+  // the series state pivot | total | head | ring | acc of vk_autocorr.h (vk_chain_set_autocorr); ac.n counts the kept steps
+  // enqueued since vk_chain_start
+  DevBlock ac_mem;
   vkac::Autocorr ac{};
-  void* d_ac = nullptr;
-  size_t ac_series = 0;                    // C / group problems x P parameters
-  std::vector<int> h_which;                // the chains' realisation indices, read back for vk_chain_begin_stretch's check
   // replica exchange (vk_kernel_temper.h): betas [K] | pivot_e, e1, e2 [C] | a block of swap levels [64][C] | n_e, n_swap_try,
-  // n_swap_acc [C] - one allocation of its own, made (and zeroed) by vk_chain_set_tempering; temper.K == 0: none
+  // n_swap_acc [C] (vk_chain_set_tempering); temper.K == 0: none
+  DevBlock temper_mem;
   TemperArgs temper{};
-  void* d_temper = nullptr;
   double* d_logs = nullptr;
   // the posterior-predictive state of vk_predictive.h, pivot_t | sum_t | sum_tt [R][N] | held [C][N] | dev [R][6] | n, n_skipped
-  // [R] | seen [C]: one allocation of its own, (C + 3 R) N + 6 R doubles and C + 2 R counters, made (and zeroed) by
-  // vk_chain_set_predictive
+  // [R] | seen [C]: (C + 3 R) N + 6 R doubles and C + 2 R counters (vk_chain_set_predictive)
+  DevBlock pred_mem;
   vkpred::Predictive pred{};
-  void* d_pred = nullptr;
-  size_t pred_bytes = 0;
 
-  void predictive_layout(Carve& c, int group) {
-    const size_t n = C, R = n / group, N = ctx->N;
-    c.take(pred.pivot_t, R * N);
-    c.take(pred.sum_t, R * N);
-    c.take(pred.sum_tt, R * N);
-    c.take(pred.held, n * N);
-    c.take(pred.dev, R * vkpred::kDeviance);
-    c.take(pred.n, R);
-    c.take(pred.n_skipped, R);
-    c.take(pred.seen, n);
+  size_t series() const { return (size_t)(C / ac.group) * P; }          // C / group problems x P parameters
+
+  // the layouts of those blocks, from the words' own counts (m.group, m.n_bins, ...)
+  void marginals_layout(Carve& c, vkmarg::Marginals& m) const {
+    const size_t problems = (size_t)(C / m.group);
+    c.take(m.h1, problems * P * ((size_t)m.n_bins + 2));
+    c.take(m.h2, problems * m.n_pairs * ((size_t)m.n_bins2 * m.n_bins2));
   }
 
-  void temper_layout(Carve& c, int K) {
+  void autocorr_layout(Carve& c, vkac::Autocorr& a) const {
+    const size_t n = (size_t)(C / a.group) * P, lags = n * (size_t)a.max_lag;
+    c.take(a.pivot, n);
+    c.take(a.total, n);
+    c.take(a.head, lags);
+    c.take(a.ring, lags);
+    c.take(a.acc, lags);
+  }
+
+  void predictive_layout(Carve& c, vkpred::Predictive& p) const {
+    const size_t n = C, R = n / p.group, N = p.N;
+    c.take(p.pivot_t, R * N);
+    c.take(p.sum_t, R * N);
+    c.take(p.sum_tt, R * N);
+    c.take(p.held, n * N);
+    c.take(p.dev, R * vkpred::kDeviance);
+    c.take(p.n, R);
+    c.take(p.n_skipped, R);
+    c.take(p.seen, n);
+  }
+
+  void temper_layout(Carve& c, TemperArgs& t, double*& logs, int K) const {
     const size_t n = C;
     double* betas = nullptr;
     c.take(betas, (size_t)K);
-    temper.betas = betas;
-    c.take(temper.pivot_e, n);               // (pivot_e .. e2 and n_e .. n_swap_acc are contiguous: zeroed in two calls)
-    c.take(temper.e1, n);
-    c.take(temper.e2, n);
-    c.take(d_logs, (size_t)vkchain::kBlock * n);
-    c.take(temper.n_e, n);
-    c.take(temper.n_swap_try, n);
-    c.take(temper.n_swap_acc, n);
+    t.betas = betas;
+    c.take(t.pivot_e, n);                    // (pivot_e .. e2 and n_e .. n_swap_acc are contiguous: zeroed in two calls)
+    c.take(t.e1, n);
+    c.take(t.e2, n);
+    c.take(logs, (size_t)vkchain::kBlock * n);
+    c.take(t.n_e, n);
+    c.take(t.n_swap_try, n);
+    c.take(t.n_swap_acc, n);
   }
 
   void stretch_layout(Carve& c) {
@@ -781,52 +860,49 @@ static ChainArgs chain_args(const vk_chain* f) {
   return a;
 }
 
-// no histograms any more: the handle makes the launches it made before it had any
-static void chain_drop_marginals(vk_chain* f) {
-  if (f->d_marg) {
-    (void)hipSetDevice(f->ctx->device);
-    (void)hipFree(f->d_marg);
-  }
-  f->d_marg = nullptr;
-  f->marg = vkmarg::Marginals{};
-  f->marg_n1 = f->marg_n2 = 0;
+// What a setter's clearing form does, and a setter that replaces state first: no such state any more - the words the kernels
+// take read "off", and the handle makes the launches it made before it had any.
+template <class Words>
+static int chain_drop(vk_chain* f, DevBlock& mem, Words& words) {
+  mem.drop(f);
+  words = Words{};
+  f->err.clear();
+  return VK_OK;
 }
 
-// no series any more: the handle makes the launches it made before it had any
-static void chain_drop_autocorr(vk_chain* f) {
-  if (f->d_ac) {
-    (void)hipSetDevice(f->ctx->device);
-    (void)hipFree(f->d_ac);
-  }
-  f->d_ac = nullptr;
-  f->ac = vkac::Autocorr{};
-  f->ac_series = 0;
+// what a getter ends with: the arrays the caller asked for, complete on return
+static int chain_home(vk_chain* f, std::initializer_list<Home> arrays) {
+  VK_SAMPLED_HIP(f, hipSetDevice(f->ctx->device));
+  const int rc = sampled_home(f, arrays);
+  if (rc == VK_OK) f->err.clear();
+  return rc;
 }
 
-// no tempering any more: the handle makes the launches it made before it had any
-static void chain_drop_tempering(vk_chain* f) {
-  if (f->d_temper) {
-    (void)hipSetDevice(f->ctx->device);
-    (void)hipFree(f->d_temper);
-  }
-  f->d_temper = nullptr;
-  f->d_logs = nullptr;
-  f->temper = TemperArgs{};
+// the refusals several entry points share (`me`: "vk_chain_...: ")
+static int refused_in_flight(vk_chain* f, const std::string& me) {
+  return refused(f, me + "a block begun with vk_chain_begin is awaiting vk_chain_finish");
+}
+static int refused_groups(vk_chain* f, const std::string& me, const std::string& groups) {
+  return refused(f, me + std::to_string(f->C) + " chains are not a whole number of " + groups);
 }
 
-// no predictive sums any more: the handle makes the launches it made before it had any
-static void chain_drop_predictive(vk_chain* f) {
-  if (f->d_pred) {
-    (void)hipSetDevice(f->ctx->device);
-    (void)hipFree(f->d_pred);
+// The chains of a group (`size` consecutive ones) move along or exchange each other's positions, so they share a data vector:
+// one realisation per group, that of its first chain (`first`: what the texts call it).  The indices are read back once.
+static int chain_one_realisation(vk_chain* f, const std::string& me, int size, const char* first) {
+  if (!f->real) return VK_OK;
+  if (f->h_which.empty()) {
+    std::vector<int> which(f->C);
+    VK_SAMPLED_HIP(f, hipMemcpy(which.data(), f->d_which, (size_t)f->C * sizeof(int), hipMemcpyDeviceToHost));
+    f->h_which.swap(which);
   }
-  f->d_pred = nullptr;
-  f->pred = vkpred::Predictive{};
-  f->pred_bytes = 0;
-  f->keep_theory = false;
+  for (int c = 0; c < f->C; ++c)
+    if (f->h_which[c] != f->h_which[c - c % size])
+      return refused(f, me + "chain " + std::to_string(c) + " is not of the realisation of " + first);
+  return VK_OK;
 }
 
-// the hold behind the step kernel of a launch of M rows (half == 0: a Metropolis launch), before the next evaluation overwrites d_th
+// the hold behind the step kernel of a launch of M rows (half == 0: a Metropolis launch), before the next evaluation overwrites
+// d_th: one wave per row
 static int chain_hold(vk_chain* f, int M, int half, int side, bool all) {
   HoldArgs h{};
   h.p = f->pred;
@@ -836,9 +912,7 @@ static int chain_hold(vk_chain* f, int M, int half, int side, bool all) {
   h.half = half;
   h.side = side;
   h.all = all ? 1 : 0;
-  hipLaunchKernelGGL(vk_chain_hold_kernel, dim3((unsigned)M), dim3(kChainBlock), 0, f->ctx->stream, h);
-  VK_SAMPLED_HIP(f, hipGetLastError());
-  return VK_OK;
+  return sampled_launch(f, vk_chain_hold_kernel, (long long)M * kChainBlock, kChainBlock, h);
 }
 
 // the predict kernel behind the hold of a kept step (a kept sweep's second half), or behind the start's hold: the pivots
@@ -849,10 +923,8 @@ static int chain_predict(vk_chain* f, bool start) {
   q.lnl = f->d_lnl;
   q.R = f->C / f->pred.group;
   q.start = start ? 1 : 0;
-  const unsigned per = (unsigned)((f->pred.N + kChainBlock - 1) / kChainBlock);
-  hipLaunchKernelGGL(vk_chain_predict_kernel, dim3((unsigned)q.R * per), dim3(kChainBlock), 0, f->ctx->stream, q);
-  VK_SAMPLED_HIP(f, hipGetLastError());
-  return VK_OK;
+  const long long per = (f->pred.N + kChainBlock - 1) / kChainBlock;       // blocks of a problem
+  return sampled_launch(f, vk_chain_predict_kernel, q.R * per * kChainBlock, kChainBlock, q);
 }
 
 // fresh energy sums and swap counters, in stream order
@@ -870,9 +942,51 @@ static int chain_series(vk_chain* f) {
   s.x = f->d_x;
   s.C = f->C;
   s.d = f->P;
-  hipLaunchKernelGGL(vk_chain_series_kernel, dim3((unsigned)f->ac_series), dim3(kChainBlock), 0, f->ctx->stream, s);
-  VK_SAMPLED_HIP(f, hipGetLastError());
-  f->ac.n += 1;
+  const int rc = sampled_launch(f, vk_chain_series_kernel, (long long)f->series() * kChainBlock, kChainBlock, s);
+  if (rc == VK_OK) f->ac.n += 1;
+  return rc;
+}
+
+// ---- what vk_chain_begin, vk_chain_begin_stretch and vk_chain_begin_tempered share (`who`: the entry point, a block of `noun`) --
+// the refusals between an entry point's NULL arguments (`null_arg`) and its own checks
+static int begin_check(vk_chain* f, const char* who, const char* noun, bool null_arg, int32_t n_steps, int64_t first_step,
+                       int64_t burn, int64_t thin) {
+  const std::string me = std::string(who) + ": ";
+  if (null_arg) return refused(f, me + "NULL argument");
+  if (!f->started) return refused(f, me + "the chains have no start (vk_chain_start)");
+  if (f->in_flight) return refused(f, me + "the previous block has not been finished (vk_chain_finish)");
+  if (n_steps < 1 || n_steps > vkchain::kBlock) return refused(f, me + "need 1 <= " + noun + " <= 64 in a block");
+  if (first_step < 0 || burn < 0 || thin < 1) return refused(f, me + "need first_step >= 0, burn >= 0, thin >= 1");
+  return VK_OK;
+}
+
+// ... and behind them: may the handle use its context now?
+static int begin_ready(vk_chain* f, const char* who) {
+  const int rc = sampled_ready(f, who, "chain", true);
+  if (rc) return rc;
+  VK_SAMPLED_HIP(f, hipSetDevice(f->ctx->device));
+  return VK_OK;
+}
+
+// a step's (a sweep's) place in the pattern: is it kept, and the history slot of `a` it then fills, the block's slot-th
+static bool begin_slot(const vk_chain* f, ChainArgs& a, int64_t step, int64_t burn, int64_t thin, bool want_history, int& slot) {
+  const bool kept = vkchain::is_kept(step, burn, thin), hist = kept && want_history;
+  const size_t C = f->C;
+  a.kept = kept ? 1 : 0;
+  a.hist_x = hist ? f->d_hx + (size_t)slot * C * f->P : nullptr;
+  a.hist_lnl = hist ? f->d_hl + (size_t)slot * C : nullptr;
+  a.hist_chi2 = hist ? f->d_hc + (size_t)slot * C : nullptr;
+  if (hist) ++slot;
+  return kept;
+}
+
+// everything is enqueued, or rc says what failed (the handle holds its text)
+static int begin_done(vk_chain* f, int rc, int32_t n_steps, int slot, int32_t* n_kept) {
+  if (rc) return sampled_abort(f, rc);
+  f->in_flight = n_steps;
+  f->block_kept = slot;
+  if (n_kept) *n_kept = slot;
+  f->err.clear();
   return VK_OK;
 }
 
@@ -896,10 +1010,7 @@ vk_chain* vk_chain_create_joint_blocks(vk_ctx* const* ctxs, int32_t n_ctx, vk_jo
                                        int32_t n_chains, int32_t n_params, const int32_t* columns, const int32_t* param_block,
                                        const double* lo, const double* hi, const double* base_rows, double alpha,
                                        const int32_t* which, char* err, size_t errlen) {
-  if (!param_block) {
-    if (err && errlen) snprintf(err, errlen, "vk_chain_create_joint_blocks: NULL argument");
-    return nullptr;
-  }
+  if (no_param_block("vk_chain_create_joint_blocks", param_block, err, errlen)) return nullptr;
   return sampled_create<vk_chain>("vk_chain_create_joint_blocks", "chain", ctxs, n_ctx, true, cov, opts, n_chains, n_params, columns,
                                   param_block, lo, hi, base_rows, alpha, which, err, errlen);
 }
@@ -908,7 +1019,7 @@ const char* vk_chain_last_error(const vk_chain* f) { return f ? f->err.c_str() :
 
 int vk_chain_set_prior(vk_chain* f, const double* mu, const double* pp_packed) {
   if (!f) return VK_E_ARG;
-  if (f->in_flight) return refused(f, "vk_chain_set_prior: a block begun with vk_chain_begin is awaiting vk_chain_finish");
+  if (f->in_flight) return refused_in_flight(f, "vk_chain_set_prior: ");
   return sampled_set_prior(f, "vk_chain_set_prior", mu, pp_packed);
 }
 
@@ -918,16 +1029,11 @@ int vk_chain_set_marginals(vk_chain* f, int32_t group, int32_t n_bins, const dou
                            const int32_t* pairs, int32_t n_bins2) {
   if (!f) return VK_E_ARG;
   const std::string me = "vk_chain_set_marginals: ";
-  if (f->in_flight) return refused(f, me + "a block begun with vk_chain_begin is awaiting vk_chain_finish");
-  if (n_bins == 0 && !lo && !hi) {
-    chain_drop_marginals(f);
-    f->err.clear();
-    return VK_OK;
-  }
+  if (f->in_flight) return refused_in_flight(f, me);
+  if (n_bins == 0 && !lo && !hi) return chain_drop(f, f->marg_mem, f->marg);
   if (n_bins < 1 || n_bins > vkmarg::kMaxBins) return refused(f, me + "need 1 <= n_bins <= 1024 (0 with NULL ranges clears)");
   if (!lo || !hi) return refused(f, me + "NULL argument");
-  if (group < 1 || f->C % group)
-    return refused(f, me + std::to_string(f->C) + " chains are not a whole number of groups of " + std::to_string(group));
+  if (group < 1 || f->C % group) return refused_groups(f, me, "groups of " + std::to_string(group));
   if (n_pairs < 0 || n_pairs > vkmarg::kMaxPairs) return refused(f, me + "need 0 <= n_pairs <= 45");
   if (n_pairs > 0 && !pairs) return refused(f, me + "NULL argument");
   if (n_pairs > 0 && (n_bins2 < 1 || n_bins2 > vkmarg::kMaxBins2)) return refused(f, me + "need 1 <= n_bins2 <= 128");
@@ -956,41 +1062,20 @@ int vk_chain_set_marginals(vk_chain* f, int32_t group, int32_t n_bins, const dou
     m.inv[j] = vkmarg::inverse_width(m.n_bins, lo[j], hi[j]);
     m.inv2[j] = vkmarg::inverse_width(m.n_bins2, lo[j], hi[j]);
   }
-  chain_drop_marginals(f);
-  const size_t problems = (size_t)(f->C / group);
-  const size_t n1 = problems * f->P * ((size_t)n_bins + 2), n2 = problems * n_pairs * ((size_t)m.n_bins2 * m.n_bins2);
-  const size_t bytes = (n1 + n2) * sizeof(unsigned long long);
-  if (hipSetDevice(f->ctx->device) != hipSuccess || hipMalloc(&f->d_marg, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    f->d_marg = nullptr;
-    f->err = me + "cannot allocate " + std::to_string(bytes) + " bytes of device memory";
-    return VK_E_HIP;
-  }
-  // (on the handle's stream, idle now: the step kernels that count run there)
-  if (hipMemsetAsync(f->d_marg, 0, bytes, f->ctx->stream) != hipSuccess || hipStreamSynchronize(f->ctx->stream) != hipSuccess) {
-    (void)hipGetLastError();
-    chain_drop_marginals(f);
-    f->err = me + "hipMemsetAsync failed";
-    return VK_E_HIP;
-  }
-  m.h1 = static_cast<unsigned long long*>(f->d_marg);
-  m.h2 = m.h1 + n1;
+  chain_drop(f, f->marg_mem, f->marg);     // (a failed allocation leaves the handle without marginals)
+  const int rc = f->marg_mem.make(f, me, [&](Carve& c) { f->marginals_layout(c, m); });
+  if (rc) return rc;
   f->marg = m;
-  f->marg_n1 = n1;
-  f->marg_n2 = n2;
   f->err.clear();
   return VK_OK;
 }
 
 int vk_chain_marginals(vk_chain* f, int64_t* h1, int64_t* h2) {
   if (!f) return VK_E_ARG;
-  if (f->in_flight) return refused(f, "vk_chain_marginals: a block begun with vk_chain_begin is awaiting vk_chain_finish");
+  if (f->in_flight) return refused_in_flight(f, "vk_chain_marginals: ");
   if (!f->marg.on) return refused(f, "vk_chain_marginals: the handle has no marginals (vk_chain_set_marginals)");
-  VK_SAMPLED_HIP(f, hipSetDevice(f->ctx->device));
-  if (h1 && f->marg_n1) VK_SAMPLED_HIP(f, hipMemcpy(h1, f->marg.h1, f->marg_n1 * sizeof(int64_t), hipMemcpyDeviceToHost));
-  if (h2 && f->marg_n2) VK_SAMPLED_HIP(f, hipMemcpy(h2, f->marg.h2, f->marg_n2 * sizeof(int64_t), hipMemcpyDeviceToHost));
-  f->err.clear();
-  return VK_OK;
+  const size_t first = (size_t)(f->marg.h2 - f->marg.h1) * sizeof(int64_t);         // h1 | h2 fill the block
+  return chain_home(f, {{h1, f->marg.h1, first}, {h2, f->marg.h2, f->marg_mem.bytes - first}});
 }
 
 // The running autocorrelation of the ensemble series (vk_autocorr.h).  Everything the series kernel indexes with is checked
@@ -998,63 +1083,32 @@ int vk_chain_marginals(vk_chain* f, int64_t* h1, int64_t* h2) {
 int vk_chain_set_autocorr(vk_chain* f, int32_t group, int32_t max_lag) {
   if (!f) return VK_E_ARG;
   const std::string me = "vk_chain_set_autocorr: ";
-  if (f->in_flight) return refused(f, me + "a block begun with vk_chain_begin is awaiting vk_chain_finish");
-  if (max_lag == 0) {
-    chain_drop_autocorr(f);
-    f->err.clear();
-    return VK_OK;
-  }
+  if (f->in_flight) return refused_in_flight(f, me);
+  if (max_lag == 0) return chain_drop(f, f->ac_mem, f->ac);
   if (max_lag < 1 || max_lag > vkac::kMaxLag) return refused(f, me + "need 1 <= max_lag <= 1024 (0 clears)");
-  if (group < 1 || f->C % group)
-    return refused(f, me + std::to_string(f->C) + " chains are not a whole number of groups of " + std::to_string(group));
-  const size_t series = (size_t)(f->C / group) * f->P;
-  const size_t bytes = vkac::state_doubles(series, max_lag) * sizeof(double);
-  void* mem = nullptr;
-  if (hipSetDevice(f->ctx->device) != hipSuccess || hipMalloc(&mem, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    chain_drop_autocorr(f);
-    f->err = me + "cannot allocate " + std::to_string(bytes) + " bytes of device memory";
-    return VK_E_HIP;
-  }
-  chain_drop_autocorr(f);
-  f->d_ac = mem;
-  // (on the handle's stream, idle now: the series kernel runs there)
-  if (hipMemsetAsync(f->d_ac, 0, bytes, f->ctx->stream) != hipSuccess || hipStreamSynchronize(f->ctx->stream) != hipSuccess) {
-    (void)hipGetLastError();
-    chain_drop_autocorr(f);
-    f->err = me + "hipMemsetAsync failed";
-    return VK_E_HIP;
-  }
+  if (group < 1 || f->C % group) return refused_groups(f, me, "groups of " + std::to_string(group));
   vkac::Autocorr a{};
   a.on = 1;
   a.group = group;
   a.max_lag = max_lag;
   a.n = 0;
-  a.pivot = static_cast<double*>(f->d_ac);
-  a.total = a.pivot + series;
-  a.head = a.total + series;
-  a.ring = a.head + series * (size_t)max_lag;
-  a.acc = a.ring + series * (size_t)max_lag;
+  chain_drop(f, f->ac_mem, f->ac);         // (a failed allocation leaves the handle without autocorrelation)
+  const int rc = f->ac_mem.make(f, me, [&](Carve& c) { f->autocorr_layout(c, a); });
+  if (rc) return rc;
   f->ac = a;
-  f->ac_series = series;
   f->err.clear();
   return VK_OK;
 }
 
 int vk_chain_autocorr(vk_chain* f, double* pivot, double* total, double* head, double* ring, double* acc, int64_t* n) {
   if (!f) return VK_E_ARG;
-  if (f->in_flight) return refused(f, "vk_chain_autocorr: a block begun with vk_chain_begin is awaiting vk_chain_finish");
+  if (f->in_flight) return refused_in_flight(f, "vk_chain_autocorr: ");
   if (!f->ac.on) return refused(f, "vk_chain_autocorr: the handle has no autocorrelation (vk_chain_set_autocorr)");
-  VK_SAMPLED_HIP(f, hipSetDevice(f->ctx->device));
-  const size_t one = f->ac_series * sizeof(double), lags = one * (size_t)f->ac.max_lag;
-  if (pivot) VK_SAMPLED_HIP(f, hipMemcpy(pivot, f->ac.pivot, one, hipMemcpyDeviceToHost));
-  if (total) VK_SAMPLED_HIP(f, hipMemcpy(total, f->ac.total, one, hipMemcpyDeviceToHost));
-  if (head) VK_SAMPLED_HIP(f, hipMemcpy(head, f->ac.head, lags, hipMemcpyDeviceToHost));
-  if (ring) VK_SAMPLED_HIP(f, hipMemcpy(ring, f->ac.ring, lags, hipMemcpyDeviceToHost));
-  if (acc) VK_SAMPLED_HIP(f, hipMemcpy(acc, f->ac.acc, lags, hipMemcpyDeviceToHost));
-  if (n) *n = (int64_t)f->ac.n;
-  f->err.clear();
-  return VK_OK;
+  const size_t one = f->series() * sizeof(double), lags = one * (size_t)f->ac.max_lag;
+  const vkac::Autocorr& a = f->ac;
+  const int rc = chain_home(f, {{pivot, a.pivot, one}, {total, a.total, one}, {head, a.head, lags}, {ring, a.ring, lags}, {acc, a.acc, lags}});
+  if (rc == VK_OK && n) *n = (int64_t)a.n;
+  return rc;
 }
 
 // The posterior-predictive sums (vk_predictive.h).  Everything the two kernels index with is checked here: the group and the
@@ -1062,11 +1116,10 @@ int vk_chain_autocorr(vk_chain* f, double* pivot, double* total, double* head, d
 int vk_chain_set_predictive(vk_chain* f, int32_t group) {
   if (!f) return VK_E_ARG;
   const std::string me = "vk_chain_set_predictive: ";
-  if (f->in_flight) return refused(f, me + "a block begun with vk_chain_begin is awaiting vk_chain_finish");
+  if (f->in_flight) return refused_in_flight(f, me);
   if (group == 0) {
-    chain_drop_predictive(f);
-    f->err.clear();
-    return VK_OK;
+    f->keep_theory = false;
+    return chain_drop(f, f->pred_mem, f->pred);
   }
   if (!f->blocks.empty())
     return refused(f, me + "a joint handle (vk_chain_create_joint) is refused: its theory workspace is laid out by the route that "
@@ -1074,33 +1127,17 @@ int vk_chain_set_predictive(vk_chain* f, int32_t group) {
   if (f->temper.K)
     return refused(f, me + "the handle is tempered (vk_chain_set_tempering): a swap moves states without touching the accept "
                            "counters the held vectors follow");
-  if (group < 1 || f->C % group)
-    return refused(f, me + std::to_string(f->C) + " chains are not a whole number of groups of " + std::to_string(group));
-  vkpred::Predictive keep = f->pred;
-  Carve count;
-  f->predictive_layout(count, group);
-  f->pred = keep;
-  void* mem = nullptr;
-  if (hipSetDevice(f->ctx->device) != hipSuccess || hipMalloc(&mem, count.bytes) != hipSuccess) {
-    (void)hipGetLastError();               // (the handle keeps the sums it had, as after a refusal)
-    f->err = me + "cannot allocate " + std::to_string(count.bytes) + " bytes of device memory";
-    return VK_E_HIP;
-  }
-  chain_drop_predictive(f);
-  f->d_pred = mem;
-  // (on the handle's stream, idle now: the kernels that add to the sums run there)
-  if (hipMemsetAsync(f->d_pred, 0, count.bytes, f->ctx->stream) != hipSuccess || hipStreamSynchronize(f->ctx->stream) != hipSuccess) {
-    (void)hipGetLastError();
-    chain_drop_predictive(f);
-    f->err = me + "hipMemsetAsync failed";
-    return VK_E_HIP;
-  }
-  Carve carve{static_cast<char*>(f->d_pred)};
-  f->predictive_layout(carve, group);
-  f->pred.on = 1;
-  f->pred.group = group;
-  f->pred.N = f->ctx->N;
-  f->pred_bytes = count.bytes;
+  if (group < 1 || f->C % group) return refused_groups(f, me, "groups of " + std::to_string(group));
+  vkpred::Predictive p{};
+  p.on = 1;
+  p.group = group;
+  p.N = f->ctx->N;
+  DevBlock mem;
+  const int rc = mem.make(f, me, [&](Carve& c) { f->predictive_layout(c, p); });
+  if (rc) return rc;                       // (the handle keeps the sums it had, as after a refusal)
+  f->pred_mem.drop(f);
+  f->pred_mem = mem;
+  f->pred = p;
   f->keep_theory = true;
   f->started = false;                      // the held vectors are taken at the start: chains already running need a new one
   f->err.clear();
@@ -1110,34 +1147,19 @@ int vk_chain_set_predictive(vk_chain* f, int32_t group) {
 int vk_chain_predictive(vk_chain* f, double* pivot_t, double* sum_t, double* sum_tt, double* deviance, int64_t* n, int64_t* n_skipped,
                         double* held) {
   if (!f) return VK_E_ARG;
-  if (f->in_flight) return refused(f, "vk_chain_predictive: a block begun with vk_chain_begin is awaiting vk_chain_finish");
+  if (f->in_flight) return refused_in_flight(f, "vk_chain_predictive: ");
   if (!f->pred.on) return refused(f, "vk_chain_predictive: the handle has no predictive sums (vk_chain_set_predictive)");
-  VK_SAMPLED_HIP(f, hipSetDevice(f->ctx->device));
   const vkpred::Predictive& p = f->pred;
-  const size_t C = f->C, R = C / p.group, N = p.N;
-  auto home = [&](void* dst, const void* src, size_t bytes) { return dst ? hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) : hipSuccess; };
-  VK_SAMPLED_HIP(f, home(pivot_t, p.pivot_t, R * N * sizeof(double)));
-  VK_SAMPLED_HIP(f, home(sum_t, p.sum_t, R * N * sizeof(double)));
-  VK_SAMPLED_HIP(f, home(sum_tt, p.sum_tt, R * N * sizeof(double)));
-  VK_SAMPLED_HIP(f, home(deviance, p.dev, R * vkpred::kDeviance * sizeof(double)));
-  VK_SAMPLED_HIP(f, home(n, p.n, R * sizeof(int64_t)));
-  VK_SAMPLED_HIP(f, home(n_skipped, p.n_skipped, R * sizeof(int64_t)));
-  VK_SAMPLED_HIP(f, home(held, p.held, C * N * sizeof(double)));
-  f->err.clear();
-  return VK_OK;
+  const size_t R = (size_t)f->C / p.group, one = R * sizeof(double), vec = one * p.N;
+  return chain_home(f, {{pivot_t, p.pivot_t, vec}, {sum_t, p.sum_t, vec}, {sum_tt, p.sum_tt, vec}, {deviance, p.dev, one * vkpred::kDeviance},
+                        {n, p.n, R * sizeof(int64_t)}, {n_skipped, p.n_skipped, R * sizeof(int64_t)},
+                        {held, p.held, (size_t)f->C * p.N * sizeof(double)}});
 }
 
 void vk_chain_destroy(vk_chain* f) {
   if (!f) return;
   if (f->in_flight) (void)hipStreamSynchronize(f->ctx->stream);
-  chain_drop_marginals(f);
-  chain_drop_autocorr(f);
-  chain_drop_tempering(f);
-  chain_drop_predictive(f);
-  if (f->d_stretch) {
-    (void)hipSetDevice(f->ctx->device);
-    (void)hipFree(f->d_stretch);
-  }
+  for (DevBlock* mem : {&f->marg_mem, &f->ac_mem, &f->temper_mem, &f->pred_mem, &f->stretch}) mem->drop(f);
   sampled_destroy(f);
 }
 
@@ -1145,7 +1167,7 @@ int vk_chain_start(vk_chain* f, const double* x0) {
   if (!f) return VK_E_ARG;
   vk_ctx* ctx = f->ctx;
   if (!x0) return refused(f, "vk_chain_start: NULL argument");
-  if (f->in_flight) return refused(f, "vk_chain_start: a block begun with vk_chain_begin is awaiting vk_chain_finish");
+  if (f->in_flight) return refused_in_flight(f, "vk_chain_start: ");
   int rc = sampled_ready(f, "vk_chain_start", "chain", true);
   if (rc) return rc;
   for (int c = 0; c < f->C; ++c)
@@ -1153,14 +1175,11 @@ int vk_chain_start(vk_chain* f, const double* x0) {
       return refused(f, "vk_chain_start: the start of chain " + std::to_string(c) + " is outside the box");
   VK_SAMPLED_HIP(f, hipSetDevice(ctx->device));
   VK_SAMPLED_HIP(f, hipMemcpy(f->d_x0, x0, (size_t)f->C * f->P * sizeof(double), hipMemcpyHostToDevice));
-  if (f->marg.on)                          // fresh chains: fresh histograms, as the counters and the moment sums (in stream order)
-    VK_SAMPLED_HIP(f, hipMemsetAsync(f->d_marg, 0, (f->marg_n1 + f->marg_n2) * sizeof(unsigned long long), ctx->stream));
-  if (f->ac.on) {                          // ... and fresh series
-    VK_SAMPLED_HIP(f, hipMemsetAsync(f->d_ac, 0, vkac::state_doubles(f->ac_series, f->ac.max_lag) * sizeof(double), ctx->stream));
-    f->ac.n = 0;
-  }
+  // fresh chains: fresh histograms, series and predictive sums, as the counters and the moment sums (in stream order) ...
+  for (DevBlock* mem : {&f->marg_mem, &f->ac_mem, &f->pred_mem})
+    if (mem->p) VK_SAMPLED_HIP(f, mem->zero(f));
+  f->ac.n = 0;
   if (f->temper.K) VK_SAMPLED_HIP(f, chain_zero_tempering(f));          // ... and fresh energy sums and swap counters
-  if (f->pred.on) VK_SAMPLED_HIP(f, hipMemsetAsync(f->d_pred, 0, f->pred_bytes, ctx->stream));    // ... and fresh predictive sums
   ChainArgs a = chain_args(f);
   rc = sampled_launch(f, vk_chain_init_kernel, a.C, kChainBlock, a);
   if (rc == VK_OK) rc = sampled_evaluate(f, f->C, f->d_res_lnl, f->d_res_chi);
@@ -1178,16 +1197,10 @@ int vk_chain_start(vk_chain* f, const double* x0) {
 int vk_chain_begin(vk_chain* f, int32_t n_steps, const double* dz, const double* logu, int64_t first_step, int64_t burn, int64_t thin,
                    int32_t want_history, int32_t* n_kept) {
   if (!f) return VK_E_ARG;
-  vk_ctx* ctx = f->ctx;
-  if (!dz || !logu) return refused(f, "vk_chain_begin: NULL argument");
-  if (!f->started) return refused(f, "vk_chain_begin: the chains have no start (vk_chain_start)");
-  if (f->in_flight) return refused(f, "vk_chain_begin: the previous block has not been finished (vk_chain_finish)");
-  if (n_steps < 1 || n_steps > vkchain::kBlock) return refused(f, "vk_chain_begin: need 1 <= steps <= 64 in a block");
-  if (first_step < 0 || burn < 0 || thin < 1) return refused(f, "vk_chain_begin: need first_step >= 0, burn >= 0, thin >= 1");
-  int rc = sampled_ready(f, "vk_chain_begin", "chain", true);
+  int rc = begin_check(f, "vk_chain_begin", "steps", !dz || !logu, n_steps, first_step, burn, thin);
+  if (rc == VK_OK) rc = begin_ready(f, "vk_chain_begin");
   if (rc) return rc;
   const size_t C = f->C, P = f->P;
-  VK_SAMPLED_HIP(f, hipSetDevice(ctx->device));
   // the stream is idle (the block before was finished): plain copies, complete on return
   VK_SAMPLED_HIP(f, hipMemcpy(f->d_dz, dz, (size_t)n_steps * C * P * sizeof(double), hipMemcpyHostToDevice));
   VK_SAMPLED_HIP(f, hipMemcpy(f->d_logu, logu, (size_t)n_steps * C * sizeof(double), hipMemcpyHostToDevice));
@@ -1198,27 +1211,16 @@ int vk_chain_begin(vk_chain* f, int32_t n_steps, const double* dz, const double*
   for (int t = 0; t < n_steps && rc == VK_OK; ++t) {
     rc = sampled_evaluate(f, f->C, f->d_res_lnl, f->d_res_chi);
     if (rc) break;
-    const bool kept = vkchain::is_kept(first_step + t, burn, thin);
+    const bool kept = begin_slot(f, a, first_step + t, burn, thin, want_history != 0, slot);
     a.dz = f->d_dz + (size_t)t * C * P;
     a.logu = f->d_logu + (size_t)t * C;
     a.dz_next = t + 1 < n_steps ? a.dz + C * P : nullptr;
-    a.kept = kept ? 1 : 0;
-    const bool hist = kept && want_history;
-    a.hist_x = hist ? f->d_hx + (size_t)slot * C * P : nullptr;
-    a.hist_lnl = hist ? f->d_hl + (size_t)slot * C : nullptr;
-    a.hist_chi2 = hist ? f->d_hc + (size_t)slot * C : nullptr;
-    if (hist) ++slot;
     rc = sampled_launch(f, vk_chain_step_kernel, a.C, kChainBlock, a);
     if (rc == VK_OK && kept && f->ac.on) rc = chain_series(f);
     if (rc == VK_OK && f->pred.on) rc = chain_hold(f, f->C, 0, 0, false);      // (every step: accepts happen on steps not kept)
     if (rc == VK_OK && kept && f->pred.on) rc = chain_predict(f, false);
   }
-  if (rc) return sampled_abort(f, rc);
-  f->in_flight = n_steps;
-  f->block_kept = slot;
-  if (n_kept) *n_kept = slot;
-  f->err.clear();
-  return VK_OK;
+  return begin_done(f, rc, n_steps, slot, n_kept);
 }
 
 // A block of stretch-move sweeps on the chains of a handle read as C / walkers ensembles (vk_kernel_stretch.h).  Per half-step:
@@ -1229,45 +1231,24 @@ int vk_chain_begin_stretch(vk_chain* f, int32_t n_steps, int32_t walkers, const 
                            const int32_t* partner, int64_t first_step, int64_t burn, int64_t thin, int32_t want_history,
                            int32_t* n_kept) {
   if (!f) return VK_E_ARG;
-  vk_ctx* ctx = f->ctx;
-  const char* me = "vk_chain_begin_stretch: ";
-  if (!z || !lz || !logu || !partner) return refused(f, std::string(me) + "NULL argument");
-  if (!f->started) return refused(f, std::string(me) + "the chains have no start (vk_chain_start)");
-  if (f->in_flight) return refused(f, std::string(me) + "the previous block has not been finished (vk_chain_finish)");
-  if (n_steps < 1 || n_steps > vkchain::kBlock) return refused(f, std::string(me) + "need 1 <= sweeps <= 64 in a block");
-  if (first_step < 0 || burn < 0 || thin < 1) return refused(f, std::string(me) + "need first_step >= 0, burn >= 0, thin >= 1");
-  if (walkers < 2 || walkers % 2) return refused(f, std::string(me) + "an ensemble needs an even number of walkers, at least 2");
-  if (f->C % walkers)
-    return refused(f, std::string(me) + std::to_string(f->C) + " chains are not a whole number of ensembles of " + std::to_string(walkers));
+  const std::string me = "vk_chain_begin_stretch: ";
+  int rc = begin_check(f, "vk_chain_begin_stretch", "sweeps", !z || !lz || !logu || !partner, n_steps, first_step, burn, thin);
+  if (rc) return rc;
+  if (walkers < 2 || walkers % 2) return refused(f, me + "an ensemble needs an even number of walkers, at least 2");
+  if (f->C % walkers) return refused_groups(f, me, "ensembles of " + std::to_string(walkers));
   const int half = walkers / 2;
   const size_t M = (size_t)f->C / 2, n = (size_t)n_steps * 2 * M;
   for (size_t i = 0; i < n; ++i)
     if (partner[i] < 0 || partner[i] >= half)
-      return refused(f, std::string(me) + "partner index " + std::to_string(partner[i]) + " (entry " + std::to_string(i) +
-                            ") is outside 0.." + std::to_string(half - 1));
-  int rc = sampled_ready(f, "vk_chain_begin_stretch", "chain", true);
+      return refused(f, me + "partner index " + std::to_string(partner[i]) + " (entry " + std::to_string(i) + ") is outside 0.." +
+                            std::to_string(half - 1));
+  rc = begin_ready(f, "vk_chain_begin_stretch");
+  if (rc == VK_OK) rc = chain_one_realisation(f, me, walkers, "its ensemble's first walker");     // (partners share a data vector)
   if (rc) return rc;
-  VK_SAMPLED_HIP(f, hipSetDevice(ctx->device));
-  if (f->real) {                           // partners share their walker's data vector: one realisation per ensemble
-    if (f->h_which.empty()) {
-      f->h_which.resize(f->C);
-      VK_SAMPLED_HIP(f, hipMemcpy(f->h_which.data(), f->d_which, (size_t)f->C * sizeof(int), hipMemcpyDeviceToHost));
-    }
-    for (int c = 0; c < f->C; ++c)
-      if (f->h_which[c] != f->h_which[c - c % walkers])
-        return refused(f, std::string(me) + "chain " + std::to_string(c) + " is not of the realisation of its ensemble's first walker");
-  }
-  if (!f->d_stretch) {
-    Carve count;
-    f->stretch_layout(count);
-    if (hipMalloc(&f->d_stretch, count.bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      f->d_stretch = nullptr;
-      f->err = std::string(me) + "cannot allocate " + std::to_string(count.bytes) + " bytes of device memory";
-      return VK_E_HIP;
-    }
-    Carve mem{static_cast<char*>(f->d_stretch)};
-    f->stretch_layout(mem);
+  // (the buffers are written before they are read: not zeroed)
+  if (!f->stretch.p && !carve_alloc(f->ctx->device, f->stretch.p, f->stretch.bytes, [&](Carve& c) { f->stretch_layout(c); })) {
+    f->err = me + cannot_allocate(f->stretch.bytes);
+    return VK_E_HIP;
   }
   // the stream is idle (the block before was finished): plain copies, complete on return
   VK_SAMPLED_HIP(f, hipMemcpy(f->d_sz, z, n * sizeof(double), hipMemcpyHostToDevice));
@@ -1279,16 +1260,9 @@ int vk_chain_begin_stretch(vk_chain* f, int32_t n_steps, int32_t walkers, const 
   a.half = half;
   a.M = (int)M;
   a.prop = f->d_prop;
-  const size_t CP = (size_t)f->C * f->P;
   int slot = 0;
   for (int t = 0; t < n_steps && rc == VK_OK; ++t) {
-    const bool kept = vkchain::is_kept(first_step + t, burn, thin);
-    const bool hist = kept && want_history;
-    a.c.kept = kept ? 1 : 0;
-    a.c.hist_x = hist ? f->d_hx + (size_t)slot * CP : nullptr;
-    a.c.hist_lnl = hist ? f->d_hl + (size_t)slot * f->C : nullptr;
-    a.c.hist_chi2 = hist ? f->d_hc + (size_t)slot * f->C : nullptr;
-    if (hist) ++slot;
+    const bool kept = begin_slot(f, a.c, first_step + t, burn, thin, want_history != 0, slot);
     for (int side = 0; side < 2 && rc == VK_OK; ++side) {
       const size_t at = ((size_t)t * 2 + side) * M;
       a.side = side;
@@ -1304,12 +1278,7 @@ int vk_chain_begin_stretch(vk_chain* f, int32_t n_steps, int32_t walkers, const 
     if (rc == VK_OK && kept && f->ac.on) rc = chain_series(f);     // (behind the second half: all W walkers as the sweep leaves them)
     if (rc == VK_OK && kept && f->pred.on) rc = chain_predict(f, false);
   }
-  if (rc) return sampled_abort(f, rc);
-  f->in_flight = n_steps;
-  f->block_kept = slot;
-  if (n_kept) *n_kept = slot;
-  f->err.clear();
-  return VK_OK;
+  return begin_done(f, rc, n_steps, slot, n_kept);
 }
 
 // Replica exchange on the chains of a handle read as C / (rungs walkers) problems of `rungs` temperatures and `walkers` ladders
@@ -1318,11 +1287,10 @@ int vk_chain_begin_stretch(vk_chain* f, int32_t n_steps, int32_t walkers, const 
 int vk_chain_set_tempering(vk_chain* f, int32_t rungs, int32_t walkers, const double* betas) {
   if (!f) return VK_E_ARG;
   const std::string me = "vk_chain_set_tempering: ";
-  if (f->in_flight) return refused(f, me + "a block begun with vk_chain_begin is awaiting vk_chain_finish");
+  if (f->in_flight) return refused_in_flight(f, me);
   if (rungs == 0) {
-    chain_drop_tempering(f);
-    f->err.clear();
-    return VK_OK;
+    f->d_logs = nullptr;
+    return chain_drop(f, f->temper_mem, f->temper);
   }
   if (rungs < 1 || walkers < 1) return refused(f, me + "need rungs >= 1 and walkers >= 1 (rungs == 0 clears)");
   if (f->pred.on)
@@ -1331,8 +1299,7 @@ int vk_chain_set_tempering(vk_chain* f, int32_t rungs, int32_t walkers, const do
   if (!betas) return refused(f, me + "NULL argument");
   const long long ladder = (long long)rungs * walkers;
   if (ladder > f->C || f->C % ladder)
-    return refused(f, me + std::to_string(f->C) + " chains are not a whole number of problems of " + std::to_string(rungs) +
-                          " rungs x " + std::to_string(walkers) + " walkers");
+    return refused_groups(f, me, "problems of " + std::to_string(rungs) + " rungs x " + std::to_string(walkers) + " walkers");
   for (int k = 0; k < rungs; ++k)
     if (!__builtin_isfinite(betas[k]) || betas[k] < 0.0)
       return refused(f, me + "the inverse temperature of rung " + std::to_string(k) + " is not finite and >= 0");
@@ -1340,55 +1307,36 @@ int vk_chain_set_tempering(vk_chain* f, int32_t rungs, int32_t walkers, const do
   for (int k = 1; k < rungs; ++k)
     if (!(betas[k] < betas[k - 1])) return refused(f, me + "the inverse temperatures must decrease strictly from rung to rung");
   VK_SAMPLED_HIP(f, hipSetDevice(f->ctx->device));
-  if (f->real) {                           // the rungs of a ladder exchange positions: one realisation per problem
-    if (f->h_which.empty()) {
-      f->h_which.resize(f->C);
-      VK_SAMPLED_HIP(f, hipMemcpy(f->h_which.data(), f->d_which, (size_t)f->C * sizeof(int), hipMemcpyDeviceToHost));
-    }
-    for (int c = 0; c < f->C; ++c)
-      if (f->h_which[c] != f->h_which[c - c % (int)ladder])
-        return refused(f, me + "chain " + std::to_string(c) + " is not of the realisation of its problem's first chain");
-  }
-  chain_drop_tempering(f);
-  Carve count;
-  f->temper_layout(count, rungs);
-  if (hipMalloc(&f->d_temper, count.bytes) != hipSuccess) {
+  int rc = chain_one_realisation(f, me, (int)ladder, "its problem's first chain");      // (the rungs of a ladder exchange positions)
+  if (rc) return rc;
+  f->d_logs = nullptr;
+  chain_drop(f, f->temper_mem, f->temper);   // (a failed allocation leaves the handle without tempering)
+  TemperArgs t{};
+  double* logs = nullptr;
+  rc = f->temper_mem.make(f, me, [&](Carve& c) { f->temper_layout(c, t, logs, rungs); });
+  if (rc) return rc;
+  if (hipMemcpy(const_cast<double*>(t.betas), betas, (size_t)rungs * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
     (void)hipGetLastError();
-    f->d_temper = nullptr;
-    f->temper = TemperArgs{};
-    f->err = me + "cannot allocate " + std::to_string(count.bytes) + " bytes of device memory";
-    return VK_E_HIP;
-  }
-  Carve mem{static_cast<char*>(f->d_temper)};
-  f->temper_layout(mem, rungs);
-  // (on the handle's stream, idle now: the kernels that add to the sums run there)
-  if (hipMemcpy(const_cast<double*>(f->temper.betas), betas, (size_t)rungs * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-      chain_zero_tempering(f) != hipSuccess || hipStreamSynchronize(f->ctx->stream) != hipSuccess) {
-    (void)hipGetLastError();
-    chain_drop_tempering(f);
+    f->temper_mem.drop(f);
     f->err = me + "upload failed";
     return VK_E_HIP;
   }
-  f->temper.K = rungs;
-  f->temper.W = walkers;
+  t.K = rungs;
+  t.W = walkers;
+  f->temper = t;
+  f->d_logs = logs;
   f->err.clear();
   return VK_OK;
 }
 
 int vk_chain_tempering(vk_chain* f, double* pivot_e, double* e1, double* e2, int64_t* n_e, int64_t* n_swap_try, int64_t* n_swap_acc) {
   if (!f) return VK_E_ARG;
-  if (f->in_flight) return refused(f, "vk_chain_tempering: a block begun with vk_chain_begin is awaiting vk_chain_finish");
+  if (f->in_flight) return refused_in_flight(f, "vk_chain_tempering: ");
   if (!f->temper.K) return refused(f, "vk_chain_tempering: the handle has no tempering (vk_chain_set_tempering)");
-  VK_SAMPLED_HIP(f, hipSetDevice(f->ctx->device));
-  const size_t n = f->C;
-  if (pivot_e) VK_SAMPLED_HIP(f, hipMemcpy(pivot_e, f->temper.pivot_e, n * sizeof(double), hipMemcpyDeviceToHost));
-  if (e1) VK_SAMPLED_HIP(f, hipMemcpy(e1, f->temper.e1, n * sizeof(double), hipMemcpyDeviceToHost));
-  if (e2) VK_SAMPLED_HIP(f, hipMemcpy(e2, f->temper.e2, n * sizeof(double), hipMemcpyDeviceToHost));
-  if (n_e) VK_SAMPLED_HIP(f, hipMemcpy(n_e, f->temper.n_e, n * sizeof(int64_t), hipMemcpyDeviceToHost));
-  if (n_swap_try) VK_SAMPLED_HIP(f, hipMemcpy(n_swap_try, f->temper.n_swap_try, n * sizeof(int64_t), hipMemcpyDeviceToHost));
-  if (n_swap_acc) VK_SAMPLED_HIP(f, hipMemcpy(n_swap_acc, f->temper.n_swap_acc, n * sizeof(int64_t), hipMemcpyDeviceToHost));
-  f->err.clear();
-  return VK_OK;
+  const TemperArgs& t = f->temper;
+  const size_t one = (size_t)f->C * sizeof(double);                      // (sums and counters alike: [C] words of 8 bytes)
+  return chain_home(f, {{pivot_e, t.pivot_e, one}, {e1, t.e1, one}, {e2, t.e2, one}, {n_e, t.n_e, one}, {n_swap_try, t.n_swap_try, one},
+                        {n_swap_acc, t.n_swap_acc, one}});
 }
 
 // A block of tempered steps (vk_kernel_temper.h).  Per step: the evaluation of the C rows and the tempered step kernel, which
@@ -1398,19 +1346,14 @@ int vk_chain_tempering(vk_chain* f, double* pivot_e, double* e1, double* e2, int
 int vk_chain_begin_tempered(vk_chain* f, int32_t n_steps, const double* dz, const double* logu, const double* logs, int64_t swap_every,
                             int64_t first_step, int64_t burn, int64_t thin, int32_t want_history, int32_t* n_kept) {
   if (!f) return VK_E_ARG;
-  vk_ctx* ctx = f->ctx;
-  const std::string me = "vk_chain_begin_tempered: ";
-  if (!f->temper.K) return refused(f, me + "the handle has no tempering (vk_chain_set_tempering)");
-  if (!dz || !logu || (swap_every > 0 && !logs)) return refused(f, me + "NULL argument");
-  if (!f->started) return refused(f, me + "the chains have no start (vk_chain_start)");
-  if (f->in_flight) return refused(f, me + "the previous block has not been finished (vk_chain_finish)");
-  if (n_steps < 1 || n_steps > vkchain::kBlock) return refused(f, me + "need 1 <= steps <= 64 in a block");
-  if (first_step < 0 || burn < 0 || thin < 1) return refused(f, me + "need first_step >= 0, burn >= 0, thin >= 1");
-  if (swap_every < 0) return refused(f, me + "need swap_every >= 0 (0: never)");
-  int rc = sampled_ready(f, "vk_chain_begin_tempered", "chain", true);
+  const char* who = "vk_chain_begin_tempered";
+  if (!f->temper.K) return refused(f, std::string(who) + ": the handle has no tempering (vk_chain_set_tempering)");
+  int rc = begin_check(f, who, "steps", !dz || !logu || (swap_every > 0 && !logs), n_steps, first_step, burn, thin);
+  if (rc) return rc;
+  if (swap_every < 0) return refused(f, std::string(who) + ": need swap_every >= 0 (0: never)");
+  rc = begin_ready(f, who);
   if (rc) return rc;
   const size_t C = f->C, P = f->P;
-  VK_SAMPLED_HIP(f, hipSetDevice(ctx->device));
   // the stream is idle (the block before was finished): plain copies, complete on return
   VK_SAMPLED_HIP(f, hipMemcpy(f->d_dz, dz, (size_t)n_steps * C * P * sizeof(double), hipMemcpyHostToDevice));
   VK_SAMPLED_HIP(f, hipMemcpy(f->d_logu, logu, (size_t)n_steps * C * sizeof(double), hipMemcpyHostToDevice));
@@ -1433,7 +1376,7 @@ int vk_chain_begin_tempered(vk_chain* f, int32_t n_steps, const double* dz, cons
   for (int t = 0; t < n_steps && rc == VK_OK; ++t) {
     rc = sampled_evaluate(f, f->C, f->d_res_lnl, f->d_res_chi);
     if (rc) break;
-    const bool kept = vkchain::is_kept(first_step + t, burn, thin);
+    const bool kept = begin_slot(f, a, first_step + t, burn, thin, want_history != 0, slot);
     // a swap event with no pair (one rung; two rungs at odd parity) is no event: the step kernel keeps writing the next rows
     const int parity = vktemper::is_swap(first_step + t, swap_every) ? vktemper::swap_parity(first_step + t, swap_every) : 0;
     const int pairs = vktemper::is_swap(first_step + t, swap_every) ? vktemper::pairs_of(f->temper.K, parity) : 0;
@@ -1441,12 +1384,6 @@ int vk_chain_begin_tempered(vk_chain* f, int32_t n_steps, const double* dz, cons
     a.logu = f->d_logu + (size_t)t * C;
     const double* next = t + 1 < n_steps ? a.dz + C * P : nullptr;
     a.dz_next = pairs ? nullptr : next;
-    a.kept = kept ? 1 : 0;
-    const bool hist = kept && want_history;
-    a.hist_x = hist ? f->d_hx + (size_t)slot * C * P : nullptr;
-    a.hist_lnl = hist ? f->d_hl + (size_t)slot * C : nullptr;
-    a.hist_chi2 = hist ? f->d_hc + (size_t)slot * C : nullptr;
-    if (hist) ++slot;
     rc = sampled_launch(f, vk_chain_step_tempered_kernel, a.C, kChainBlock, g);
     if (rc == VK_OK && kept && f->ac.on) rc = chain_series(f);      // (the positions the sums have just taken: before the swap)
     if (rc == VK_OK && pairs) {
@@ -1462,12 +1399,7 @@ int vk_chain_begin_tempered(vk_chain* f, int32_t n_steps, const double* dz, cons
       }
     }
   }
-  if (rc) return sampled_abort(f, rc);
-  f->in_flight = n_steps;
-  f->block_kept = slot;
-  if (n_kept) *n_kept = slot;
-  f->err.clear();
-  return VK_OK;
+  return begin_done(f, rc, n_steps, slot, n_kept);
 }
 
 int vk_chain_finish(vk_chain* f, double* x, double* lnl, double* chi2) {
