@@ -1,6 +1,8 @@
 """Best fits (victor_amd/fitting.py, vk_fit_run) without a GPU: the simplex transition of victor_amd/csrc/vk_fit_simplex.h compiled
 on its own under g++ and driven on analytic functions, checked launch by launch against a one-point-at-a-time NumPy restatement
-of the same rules; and the refusals of CCFFit.best_fit / Realisations.best_fit, raised before any device call."""
+of the same rules, and bit for bit - phase, live[] and pt[] of every slot of every launch - against the slot-for-slot mirror the
+GPU tests hold the device search to (tests/fit_definition.py) at d = 1, 2, 3, 4 and 10; and the refusals of CCFFit.best_fit /
+Realisations.best_fit, raised before any device call."""
 
 import math
 import os
@@ -42,7 +44,36 @@ def _halfinf(x):
     return -((x[0] - 0.3) * (x[0] - 0.3) + 2.0 * ((x[1] + 0.4) * (x[1] + 0.4)))
 
 
+# The rotated quadratic in every d: coordinates rotated pairwise by the angle whose cosine and sine are PQ_C, PQ_S (decimal
+# literals, read alike by both compilers), a last odd coordinate unrotated; minimum at PQ_M (outside [-1, 1] in x_0).
+PQ_C, PQ_S = 0.955336489125606, 0.29552020666133955
+PQ_M = (1.5, -0.2, 0.4, 0.1, -0.3, 0.25, 0.6, -0.45, 0.05, 0.35)
+PQ_W = (1.0, 3.0, 0.5, 2.0, 1.5, 0.75, 2.5, 1.25, 4.0, 0.6)
+
+
+def _pairquad(x):
+    d = len(x)
+    y = [x[i] - PQ_M[i] for i in range(d)]
+    z = list(y)
+    for i in range(0, d - 1, 2):
+        z[i] = PQ_C * y[i] - PQ_S * y[i + 1]
+        z[i + 1] = PQ_S * y[i] + PQ_C * y[i + 1]
+    f = 0.0
+    for i in range(d):
+        f = f + PQ_W[i] * (z[i] * z[i])
+    return -f
+
+
+def _pairhole(x):
+    # the same with x_0 < 0 failing: -inf where the last coordinate is positive, NaN elsewhere
+    if x[0] < 0.0:
+        return -INF if x[len(x) - 1] > 0.0 else math.nan
+    return _pairquad(x)
+
+
 LNL = {
+    "pairquad": _pairquad,
+    "pairhole": _pairhole,
     "rosen": lambda x: -(100.0 * ((x[1] - x[0] * x[0]) * (x[1] - x[0] * x[0])) + (1.0 - x[0]) * (1.0 - x[0])),
     "rotquad": _rotquad,
     "halfinf": _halfinf,
@@ -58,7 +89,27 @@ DRIVER = r"""
 #include "vk_fit_simplex.h"
 
 static const double THETA = 0.3;
+static const double PQ_C = 0.955336489125606, PQ_S = 0.29552020666133955;
+static const double PQ_M[10] = {1.5, -0.2, 0.4, 0.1, -0.3, 0.25, 0.6, -0.45, 0.05, 0.35};
+static const double PQ_W[10] = {1.0, 3.0, 0.5, 2.0, 1.5, 0.75, 2.5, 1.25, 4.0, 0.6};
+static int D = 0;
+static double pairquad(const double* x) {
+  double y[10], z[10];
+  for (int i = 0; i < D; ++i) z[i] = y[i] = x[i] - PQ_M[i];
+  for (int i = 0; i + 1 < D; i += 2) {
+    z[i] = PQ_C * y[i] - PQ_S * y[i + 1];
+    z[i + 1] = PQ_S * y[i] + PQ_C * y[i + 1];
+  }
+  double f = 0.0;
+  for (int i = 0; i < D; ++i) f = f + PQ_W[i] * (z[i] * z[i]);
+  return -f;
+}
 static double lnl_of(const char* fn, const double* x) {
+  if (!strcmp(fn, "pairquad")) return pairquad(x);
+  if (!strcmp(fn, "pairhole")) {
+    if (x[0] < 0.0) return x[D - 1] > 0.0 ? -HUGE_VAL : std::nan("");
+    return pairquad(x);
+  }
   if (!strcmp(fn, "rosen")) {
     const double a = x[1] - x[0] * x[0];
     return -(100.0 * (a * a) + (1.0 - x[0]) * (1.0 - x[0]));
@@ -81,11 +132,11 @@ static double lnl_of(const char* fn, const double* x) {
   return -HUGE_VAL;
 }
 
-// usage: driver fn d max_iter restarts ftol  then d values each of lo, hi, x0, step, xtol
+// usage: driver fn d max_iter restarts ftol  then d values each of lo, hi, x0, step, xtol, then the file the launches go to
 int main(int argc, char** argv) {
   const char* fn = argv[1];
   vkfit::Params q{};
-  q.d = atoi(argv[2]);
+  q.d = D = atoi(argv[2]);
   q.S = vkfit::slots(q.d);
   q.max_iter = atoi(argv[3]);
   q.restarts = atoi(argv[4]);
@@ -99,8 +150,14 @@ int main(int argc, char** argv) {
   for (int j = 0; j < q.d; ++j) q.xtol[j] = strtod(argv[a++], nullptr);
   static vkfit::State s;
   vkfit::start(s, q, x0);
+  FILE* launches = fopen(argv[a], "w");          // per launch: phase, live[0..S), pt[0..S)[0..d) as hexadecimal floats
   while (s.phase != vkfit::kDone) {
     double lnl[vkfit::kMaxS], chi[vkfit::kMaxS];
+    fprintf(launches, "%d", s.phase);
+    for (int i = 0; i < q.S; ++i) fprintf(launches, " %d", s.live[i]);
+    for (int i = 0; i < q.S; ++i)
+      for (int j = 0; j < q.d; ++j) fprintf(launches, " %a", s.pt[i][j]);
+    fprintf(launches, "\n");
     for (int i = 0; i < q.S; ++i) {
       lnl[i] = lnl_of(fn, s.pt[i]);
       chi[i] = -2.0 * lnl[i];
@@ -109,7 +166,10 @@ int main(int argc, char** argv) {
   }
   printf("\n%d %d %lld %.17g %.17g", s.status, s.iter, (long long)s.n_evals, -s.f[0], s.chi[0]);
   for (int j = 0; j < q.d; ++j) printf(" %.17g", s.v[0][j]);
+  printf("\n%a %a", -s.f[0], s.chi[0]);
+  for (int j = 0; j < q.d; ++j) printf(" %a", s.v[0][j]);
   printf("\n");
+  fclose(launches);
   return 0;
 }
 """
@@ -130,11 +190,20 @@ def driver(tmp_path_factory):
         args = [str(exe), fn, str(len(x0)), str(max_iter), str(restarts), repr(float(ftol))]
         for arr in (lo, hi, x0, step, xtol):
             args += [repr(float(v)) for v in arr]
+        args.append(str(d / "launches.txt"))
         out = subprocess.run(args, check=True, capture_output=True, text=True).stdout.split("\n")
         decisions = [int(t) for t in out[0].split()]
         tail = out[1].split()
+        S = max(4, len(x0) + 1)
+        launches = []
+        for line in (d / "launches.txt").read_text().splitlines():
+            t = line.split()
+            launches.append((int(t[0]), tuple(int(v) for v in t[1:1 + S]),
+                             np.array([float.fromhex(v) for v in t[1 + S:]]).reshape(S, len(x0))))
+        exact = [float.fromhex(t) for t in out[2].split()]
         return {"decisions": decisions, "status": int(tail[0]), "iter": int(tail[1]), "n_evals": int(tail[2]),
-                "lnl": float(tail[3]), "chi2": float(tail[4]), "x": np.array([float(t) for t in tail[5:]])}
+                "lnl": float(tail[3]), "chi2": float(tail[4]), "x": np.array([float(t) for t in tail[5:]]),
+                "launches": launches, "exact": {"lnl": exact[0], "chi2": exact[1], "x": np.array(exact[2:])}}
     return run
 
 
@@ -304,6 +373,86 @@ def test_start_simplex_falls_back_and_clamps(driver):
     for x0, step in (([0.95, -0.95], [0.1, 0.1]), ([0.5, 0.2], [3.0, 3.0])):
         case = dict(fn="vee", lo=[-1, -1], hi=[1, 1], x0=x0, step=step, xtol=[1e-9, 1e-9], ftol=1e-14)
         same(driver(**case), restated(**case))
+
+
+# ------------------------------------------------------------------ the slot-for-slot mirror (tests/fit_definition.py) -------
+def mirrored(fn, lo, hi, x0, step, xtol, ftol=1e-8, max_iter=1000, restarts=0):
+    """The same run through tests/fit_definition.run: one problem, the analytic function as its evaluation."""
+    from tests import fit_definition as FD
+
+    def evaluate(x, problem):
+        lnl = np.array([LNL[fn]([float(t) for t in row]) for row in x])
+        return lnl, -2.0 * lnl
+    return FD.run(evaluate, [x0], lo, hi, step, xtol, ftol, max_iter, restarts, trace=True)
+
+
+def bits(a):
+    return np.asarray(a, dtype=np.float64).tobytes()
+
+
+def same_as_mirror(got, m, what):
+    """Decisions, the slot layout of every launch, and the result: equality, not a tolerance."""
+    assert got["decisions"] == m.decisions[0], (what, got["decisions"], m.decisions[0])
+    assert (got["status"], got["iter"], got["n_evals"]) == (int(m.status[0]), int(m.n_iter[0]), int(m.n_evals[0])), what
+    assert len(got["launches"]) == len(m.trace[0]) == got["iter"], what
+    for i, ((phase, live, pt), (m_phase, m_live, m_pt)) in enumerate(zip(got["launches"], m.trace[0])):
+        assert phase == m_phase and live == m_live, (what, "launch", i, phase, m_phase, live, m_live)
+        assert bits(pt) == bits(m_pt), (what, "launch", i, pt, m_pt)
+    e = got["exact"]
+    assert bits(e["x"]) == bits(m.x[0]), (what, e["x"], m.x[0])
+    assert bits(e["lnl"]) == bits(m.lnl[0]) and bits(e["chi2"]) == bits(m.chi2[0]), (what, e, m.lnl, m.chi2)
+
+
+def box(d, half=1.0):
+    return dict(lo=[-half] * d, hi=[half] * d)
+
+
+MIRROR_CASES = [
+    # the rotated quadratic in d = 1, 2, 3, 4, 10: its minimum lies outside the box in x_0, which cuts candidates off
+    *[dict(fn="pairquad", **box(d), x0=[0.0] * d, step=[0.2] * d, xtol=[1e-7] * d, ftol=1e-12, max_iter=400 * d, restarts=r)
+      for d in (1, 2, 3, 4, 10) for r in (0, 2)],
+    # x_0 < 0 fails: -inf where the last coordinate is positive, NaN elsewhere; starts that straddle the edge
+    *[dict(fn="pairhole", **box(d), x0=[0.05] + [0.3] * (d - 1), step=[0.5] * d, xtol=[1e-8] * d, ftol=1e-13, max_iter=400 * d, restarts=r)
+      for d in (1, 2, 3, 4, 10) for r in (0, 2)],
+    dict(fn="pairhole", **box(10), x0=[-0.5] + [0.3] * 9, step=[0.8] * 10, xtol=[1e-8] * 10, ftol=1e-13, max_iter=60),
+    # no finite start vertex: every vertex in the failing half (d = 10), and a function that fails everywhere (d = 3)
+    dict(fn="pairhole", **box(10), x0=[-0.9] + [0.3] * 9, step=[0.05] * 10, xtol=[1e-8] * 10, restarts=2),
+    dict(fn="none", lo=[0, 0, 0], hi=[1, 1, 1], x0=[0.5, 0.5, 0.5], step=[0.1] * 3, xtol=[1e-6] * 3),
+    # the cases of the tests above
+    dict(fn="rosen", lo=[-2, -2], hi=[2, 2], x0=[-1.2, 1.0], step=[0.1, 0.1], xtol=[1e-8, 1e-8], ftol=1e-14, restarts=1),
+    dict(fn="rosen", lo=[-2, -2], hi=[2, 2], x0=[-1.2, 1.0], step=[0.1, 0.1], xtol=[1e-8, 1e-8], max_iter=7),
+    dict(fn="halfinf", lo=[-1, -1], hi=[1, 1], x0=[0.05, 0.9], step=[0.5, 0.5], xtol=[1e-9, 1e-9], ftol=1e-14, restarts=1),
+    dict(fn="halfinf", lo=[-1, -1], hi=[1, 1], x0=[0.3, 0.3], step=[0.8, 0.8], xtol=[1e-10, 1e-10], ftol=1e-14, restarts=2),
+    dict(fn="halfinf", lo=[-1, -1], hi=[1, 1], x0=[-0.5, 0.5], step=[0.8, 0.8], xtol=[1e-10, 1e-10], ftol=1e-14),
+    dict(fn="vee", lo=[-1, -1], hi=[1, 1], x0=[0.95, -0.95], step=[0.1, 0.1], xtol=[1e-9, 1e-9], ftol=1e-14),
+    dict(fn="vee", lo=[-1, -1], hi=[1, 1], x0=[0.5, 0.2], step=[3.0, 3.0], xtol=[1e-9, 1e-9], ftol=1e-14),
+]
+
+
+def test_the_mirror_is_the_header_bit_for_bit(driver):
+    """tests/fit_definition.py against vk_fit_simplex.h under g++, launch by launch: phase, live[] and pt[] of every slot, the
+    decisions, and the final x, f, chi2, iter, n_evals - all by equality.  Every Decision occurs."""
+    seen, dead, shrink_cut = set(), 0, 0
+    for case in MIRROR_CASES:
+        got, m = driver(**case), mirrored(**case)
+        what = (case["fn"], len(case["x0"]), case.get("restarts", 0), case.get("max_iter", 1000))
+        same_as_mirror(got, m, what)
+        same(got, restated(**case))
+        seen |= set(got["decisions"])
+        dead += int(m.n_dead_candidates[0])
+        # the same run cut at its first shrink: the limit ends it inside the candidate launch that asked for the shrink
+        if SHRUNK in got["decisions"]:
+            cut = dict(case, max_iter=got["decisions"].index(SHRUNK) + 1)
+            got_cut, m_cut = driver(**cut), mirrored(**cut)
+            same_as_mirror(got_cut, m_cut, what + ("cut at its first shrink",))
+            assert got_cut["decisions"] == got["decisions"][:cut["max_iter"] - 1] + [MAX_ITER] and got_cut["status"] == ST_MAX_ITER
+            assert got_cut["launches"][-1][0] == 1                     # (kCand: the shrink launch was never laid out)
+            shrink_cut += 1
+    print("decisions seen:", sorted(seen), "dead candidate slots:", dead, "runs cut inside a shrink:", shrink_cut)
+    assert seen == set(range(10)), sorted(seen)
+    assert dead > 0 and shrink_cut > 0
+    d10 = [c for c in MIRROR_CASES if len(c["x0"]) == 10]
+    assert len(d10) >= 4
 
 
 # ------------------------------------------------------------------ refusals (no GPU) -------

@@ -147,6 +147,22 @@ def test_refusals_come_before_any_device_call(joints):
             call()
 
 
+def test_an_eleventh_sampled_value_is_refused_before_any_device_call(joints):
+    """kMaxP = 10 sizes the kernels' by-value arguments: three blocks with fsigma8, sigma_v and bias of their own plus beta and
+    epsilon are eleven sampled values, and ten of them (epsilon fixed) pass the check and go on to the device."""
+    from victor_amd import InputError
+    from victor_amd.joint import per_block
+    eleven = per_block(dict(PARAMS, bias={"prior": {"min": 1.0, "max": 3.0}, "ref": {"loc": 2.0, "scale": 0.1}, "proposal": 0.05}),
+                       ["fsigma8", "sigma_v", "bias"], 3)
+    joint = joints["cov"]
+    with pytest.raises(InputError, match="at most 10 sampled parameters"):
+        joint.sample_chains(eleven, 5)
+    with pytest.raises(InputError, match="at most 10 sampled parameters"):
+        joint.sample_chains(eleven, 5, move="stretch", walkers=24)
+    with pytest.raises(AssertionError, match="reached the device"):
+        joint.sample_chains(eleven, 5, fixed={"epsilon": 1.0})
+
+
 def test_block_rows_are_each_blocks_own_rows(joints):
     """The row of block q is ``fits[q]._fit_rows`` of the dictionary resolved for it - scalars broadcast over a batch."""
     from victor_amd import _native as N
