@@ -1,0 +1,186 @@
+"""The launch shapes the device step loops are tested at (tests/test_gpu_launch_shapes.py; DESIGN.md section 7b, "Launch shapes
+under test") and the thresholds of the sources those shapes were chosen against.  No GPU, no library: ``thresholds()`` reads the
+numbers out of the sources by regular expression, ``TABLE`` holds one row per case with the property that makes it the smallest
+shape that reaches what it is about, and ``tests/test_launch_shapes.py`` checks every property against the numbers as they
+stand - when somebody moves a threshold, that test fails and names the row to revisit.  The GPU cases take their shapes from
+``TABLE``: nothing is stated twice.
+
+A row: ``R`` problems x ``K`` rungs (1 without tempering) x ``W`` walkers, the move and the route.  ``chains(row)`` is R K W,
+``rows(row)`` the rows of one evaluation launch inside the loop - R K W for the Metropolis moves, half of it for the stretch move,
+whose half-steps move half of every ensemble - and ``steps(row)`` the step count: 2 BLOCK + 2 up to 600 chains, BLOCK + 2 above
+(one block edge plus two)."""
+
+import os
+import re
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "victor_amd", "csrc")
+MANY_CHAINS = 600        # up to here two blocks of steps and two more, above one block and two
+
+
+def _read(*path):
+    with open(os.path.join(ROOT, *path)) as fh:
+        return fh.read()
+
+
+def _one(pattern, text, what):
+    m = re.search(pattern, text)
+    assert m, f"{what}: the pattern {pattern!r} no longer matches its source"
+    return m
+
+
+def thresholds():
+    """name -> int, read from the sources."""
+    hip = _read("victor_amd", "csrc", "victor_hip.hip")
+    chains = _read("victor_amd", "chains.py")
+    t = {}
+    t["kChainBlock"] = int(_one(r"constexpr int kChainBlock = (\d+);", _read("victor_amd", "csrc", "vk_kernel_chain.h"), "kChainBlock").group(1))
+    t["kPartialPoints"] = int(_one(r"constexpr long long kPartialPoints = (\d+);", _read("victor_amd", "csrc", "vk_host.h"), "kPartialPoints").group(1))
+    m = _one(r"const long long kFuseMaxDefault = (\d+), kFuseBlendedMin = (\d+);", hip, "kFuseMaxDefault / kFuseBlendedMin")
+    t["kFuseMaxDefault"], t["kFuseBlendedMin"] = int(m.group(1)), int(m.group(2))
+    # the rule the two constants enter: fused up to the one, and from the other on under a covariance gridded in beta
+    _one(r"a\.n <= kFuseMaxDefault \|\| \(like && like->n_beta_c > 0 && a\.n >= kFuseBlendedMin\)", hip, "the fuse rule")
+    t["cells_min"] = int(_one(r"const long long cells_min = (\d+);", hip, "cells_min").group(1))
+    _one(r"n_dec >= cells_min", hip, "the point-major / cells rule")
+    # cells per range by row count, streaming model: below band1 rows cpi0, below band2 cpi1, from there on cpi2 ...
+    m = _one(r": \(n_dec < (\d+) \? (\d+) : \(n_dec < (\d+) \? (\d+) : (\d+)\)\);", hip, "the range bands")
+    t["band1"], t["cpi0"], t["band2"], t["cpi1"], t["cpi2"] = (int(g) for g in m.groups())
+    # ... and only up to kPartialPoints rows: above, one workgroup per point
+    _one(r"\} else if \(a\.n <= kPartialPoints\) \{", hip, "the partial-sum limit of the ranges")
+    _one(r"constexpr int kJointSortChunk = kBlock;", _read("victor_amd", "csrc", "vk_kernel_joint.h"), "kJointSortChunk")
+    t["kJointSortChunk"] = int(_one(r"constexpr int kBlock = (\d+);", _read("victor_amd", "csrc", "vk_common.h"), "kBlock").group(1))
+    t["kZeroCopyMaxDefault"] = int(_one(r"constexpr int64_t kZeroCopyMaxDefault = (\d+);", hip, "kZeroCopyMaxDefault").group(1))
+    t["MAX_CHAINS"] = int(_one(r"(?m)^MAX_CHAINS = (\d+)$", chains, "MAX_CHAINS").group(1))
+    _one(r"(?m)^BLOCK = EnsembleMetropolis\.BLOCK$", chains, "BLOCK of chains.py")
+    t["BLOCK"] = int(_one(r"(?m)^    BLOCK = (\d+)", _read("victor_amd", "sampler.py"), "EnsembleMetropolis.BLOCK").group(1))
+    t["VK_NPAR"] = int(_one(r"#define VK_NPAR (\d+)", _read("include", "victor_hip.h"), "VK_NPAR").group(1))
+    return t
+
+
+# ------------------------------------------------------------------ what a launch of m rows is, by the numbers -------------------
+def cells_range(m, t):
+    """Cells per range of the theory launch for m rows: 0 for the point-major kernel, -1 for one workgroup per point."""
+    if m < t["cells_min"]:
+        return 0
+    if m > t["kPartialPoints"]:
+        return -1
+    return t["cpi0"] if m < t["band1"] else t["cpi1"] if m < t["band2"] else t["cpi2"]
+
+
+def fused(m, t, gridded=True):
+    """The data-vector route's chi-square inside the theory kernel (the BOSS fit's covariance is gridded in beta)."""
+    return m <= t["kFuseMaxDefault"] or (gridded and m >= t["kFuseBlendedMin"])
+
+
+def workgroups(n, t):
+    return -(-n // t["kChainBlock"])
+
+
+def pairs_of(K, parity):
+    """vktemper::pairs_of (vk_temper_step.h; tests/test_tempering.py holds the header to the NumPy definition)."""
+    return (K - parity) // 2 if K - parity > 0 else 0
+
+
+def chains(row):
+    return row["R"] * row.get("K", 1) * row["W"]
+
+
+def rows(row):
+    return chains(row) // 2 if row["move"] == "stretch" else chains(row)
+
+
+def steps(row, t=None):
+    block = 64 if t is None else t["BLOCK"]
+    return 2 * block + 2 if chains(row) <= MANY_CHAINS else block + 2
+
+
+def swap_threads(row):
+    """Threads of the swap launches of the two parities."""
+    return [row["R"] * pairs_of(row["K"], parity) * row["W"] for parity in (0, 1)]
+
+
+# ------------------------------------------------------------------ the table -------------------------------------------------------
+# ``reaches``: (text, check) pairs; check(row, t) is the property in the numbers of the sources.
+def _past(n_groups):
+    return lambda r, t: workgroups(rows(r), t) >= n_groups
+
+
+def _range_is(key):
+    return lambda r, t: cells_range(rows(r), t) == (t[key] if isinstance(key, str) else key)
+
+
+def _straddles(r, t):
+    """An ensemble whose movers lie on both sides of the first workgroup edge, wholly inside the launch."""
+    half, edge = r["W"] // 2, t["kChainBlock"]
+    e = edge // half
+    return edge % half != 0 and e * half < edge < (e + 1) * half <= rows(r) and e < r["R"]
+
+
+LADDER4 = {"betas": [1.0, 0.5, 0.1, 0.0], "swap_every": 3}
+LADDER3 = {"betas": [1.0, 0.3, 0.0], "swap_every": 4}
+LADDER5 = {"betas": [1.0, 0.5, 0.2, 0.05, 0.0], "swap_every": 3}
+
+TABLE = {
+    "M1": dict(move="metropolis", route="mocks", R=5, W=26, reaches=[
+        ("three workgroups, the last with two lanes", lambda r, t: workgroups(rows(r), t) == 3 and rows(r) - 2 * t["kChainBlock"] == 2),
+        ("ranges of the middle band", _range_is("cpi1"))]),
+    "M2": dict(move="metropolis", route="mocks", R=70, W=8, reaches=[
+        ("more problems than mocks", lambda r, t: r["R"] > 16),
+        ("ranges of the upper band", _range_is("cpi2")),
+        ("the smallest W x R above the band", lambda r, t: rows(r) >= t["band2"] and rows(r) <= t["kPartialPoints"])]),
+    "M3": dict(move="metropolis", route="mocks", R=5, W=410, reaches=[
+        ("one workgroup per point: just past kPartialPoints", lambda r, t: r["R"] * (r["W"] - 1) <= t["kPartialPoints"] < rows(r))]),
+    "M4": dict(move="metropolis", route="data", R=1, W=(130, 512, 513, 2048, 2049, 8192), reaches=[
+        ("130 rows: fused, ranges of the middle band", lambda r, t: fused(130, t) and cells_range(130, t) == t["cpi1"]),
+        ("both sides of the fuse limit", lambda r, t: 512 <= t["kFuseMaxDefault"] < 513 and fused(512, t) and not fused(513, t)),
+        ("both sides of the partial-sum limit, unfused", lambda r, t: 2048 <= t["kPartialPoints"] < 2049 and not fused(2048, t) and not fused(2049, t)
+         and cells_range(2048, t) == t["cpi2"] and cells_range(2049, t) == -1),
+        ("fused again under the gridded covariance", lambda r, t: 8191 < t["kFuseBlendedMin"] <= 8192 and fused(8192, t) and not fused(8192, t, gridded=False)),
+        ("8192 rows leave the host entry point's in-place path", lambda r, t: t["kZeroCopyMaxDefault"] < 8192)]),
+    "S1": dict(move="stretch", route="mocks", R=13, W=10, reaches=[
+        ("two workgroups of movers", lambda r, t: rows(r) > t["kChainBlock"] and workgroups(rows(r), t) == 2),
+        ("an ensemble straddles the workgroup edge", _straddles)]),
+    "S2": dict(move="stretch", route="mocks", R=5, W=52, reaches=[
+        ("ranges of the middle band in the half-launches", _range_is("cpi1")),
+        ("three workgroups", _past(3))]),
+    "S3": dict(move="stretch", route="data", R=1, W=1026, reaches=[
+        ("a chi-square launch of its own between propose and step", lambda r, t: rows(r) == t["kFuseMaxDefault"] + 1 and not fused(rows(r), t))]),
+    "T1": dict(move="tempered", route="mocks", R=3, K=4, W=11, temper=LADDER4, reaches=[
+        ("the step kernel past two workgroups", _past(3)),
+        ("a swap launch past one workgroup, one within", lambda r, t: swap_threads(r) == [66, 33] and swap_threads(r)[0] > t["kChainBlock"] > swap_threads(r)[1]),
+        ("W divides neither the workgroup nor the pair groups' edge", lambda r, t: t["kChainBlock"] % r["W"] != 0
+         and t["kChainBlock"] % (r["W"] * pairs_of(r["K"], 0)) != 0)]),
+    "T2": dict(move="tempered", route="mocks", R=3, K=3, W=23, temper=LADDER3, reaches=[
+        ("odd K, both swap launches past one workgroup", lambda r, t: r["K"] % 2 == 1 and min(swap_threads(r)) > t["kChainBlock"]),
+        ("a swap behind the last step of a block", lambda r, t: t["BLOCK"] % r["temper"]["swap_every"] == 0)]),
+    "T3": dict(move="tempered", route="data", R=1, K=5, W=105, temper=LADDER5, reaches=[
+        ("an unfused evaluation between step and swap", lambda r, t: not fused(rows(r), t)),
+        ("swap launches past three workgroups", lambda r, t: swap_threads(r) == [210, 210] and workgroups(210, t) > 3)]),
+    "O1": dict(move=("metropolis", "stretch"), route="mocks", R=2, W=260, reaches=[
+        ("lane_partial over five strides, the last partial", lambda r, t: workgroups(r["W"], t) == 5 and r["W"] % t["kChainBlock"] != 0),
+        ("more chains of one problem than a workgroup count into its bins", lambda r, t: r["W"] > 4 * t["kChainBlock"]),
+        ("hold and predict at more than eight workgroups of rows", lambda r, t: workgroups(r["R"] * r["W"], t) > 8)]),
+    "J1": dict(move=("metropolis", "stretch"), route="dsplit_cov mocks", R=3, W=44, reaches=[
+        ("the blocks' streams forked and joined per step past one workgroup", lambda r, t: workgroups(r["R"] * r["W"], t) == 3
+         and r["R"] * r["W"] // 2 > t["kChainBlock"])]),
+    "J2": dict(move="metropolis", route="dsplit_cov data", R=1, W=520, reaches=[
+        ("the joint chi-square kernel past two sort chunks of rows, ranges of the upper band", lambda r, t: rows(r) > 2 * t["kJointSortChunk"]
+         and cells_range(rows(r), t) == t["cpi2"])]),
+    "J3": dict(move="metropolis", route="dsplit_diag mocks", R=3, W=44, reaches=[
+        ("vk_joint_sum_kernel past one workgroup of rows", _past(3))]),
+    "J4": dict(move="metropolis", route="boss_grid mocks", R=4, W=130, reaches=[
+        ("the counting sort over three workgroups", lambda r, t: -(-rows(r) // t["kJointSortChunk"]) == 3)]),
+    "J5": dict(move="metropolis", route="five blocks, ten parameters", R=3, W=44, reaches=[
+        ("sampled_row's row-set loop at a stride of 132 rows", lambda r, t: rows(r) * t["VK_NPAR"] == 132 * t["VK_NPAR"] and _past(3)(r, t))]),
+}
+
+# What stays untested: everything above 8192 chains - in particular the 16384 chains DESIGN.md section 7b times and the
+# MAX_CHAINS = 65536 the product accepts.
+LARGEST_TESTED = 8192
+
+
+def variants(row):
+    """The (move, W) combinations of a row."""
+    moves = row["move"] if isinstance(row["move"], tuple) else (row["move"],)
+    widths = row["W"] if isinstance(row["W"], tuple) else (row["W"],)
+    return [dict(row, move=m, W=w) for m in moves for w in widths]

@@ -138,6 +138,35 @@ def test_b_seventy_problems_with_their_own_starts(fit):
     same_fit(dev, ref, "(b) 70 problems")
 
 
+def test_b_520_problems_shrink_through_every_regime_of_the_evaluator(fit):
+    """(b') 520 problems (``np.arange(520) % 16``), d = 3, S = 4, each from a start of its own: the first launches hold 2080
+    rows, just past ``kPartialPoints`` - one workgroup per point -, and as problems finish the compacted launches pass through
+    the ranges of 1024, 512 and 256 cells down to the point-major kernel below 20 rows (tests/launch_shapes.py reads the
+    thresholds from the sources).  No other case starts from that height, and here the regime changes from one compaction to the
+    next.  Tolerances of 1e-3 of the proposal widths and 1e-4 in lnL without a restart keep the mirror's Python loop to a few
+    seconds at d = 3; chosen, like the starts, with the mirror alone, whose launches are held to every regime before the device
+    runs."""
+    from tests import launch_shapes as LS
+    t = LS.thresholds()
+    R = 520
+    rs = fit.realisations(np.arange(R) % 16)
+    rng = np.random.default_rng(5)
+    x0 = LO3 + (HI3 - LO3) * (0.3 + 0.4 * rng.random((R, 3)))
+    kw = dict(fixed=EPS_FIXED, start={n: x0[:, j] for j, n in enumerate(NAMES3)}, restarts=0, ftol=1e-4,
+              xtol={n: 1e-3 * PARAMS[n]["proposal"] for n in NAMES3})
+    ref = FD.best_fit(rs, PARAMS, **kw)
+    figures(ref, "(b') 520 problems")
+    regimes = sorted({LS.cells_range(m, t) for m in ref.launches})
+    print("(b') launches by regime (-1: a workgroup per point, 0: point-major, else cells per range):",
+          {g: sum(LS.cells_range(m, t) == g for m in ref.launches) for g in regimes})
+    assert ref.launches[0] == 4 * R and t["kPartialPoints"] < 4 * R <= t["kPartialPoints"] + 32
+    assert regimes == sorted([-1, 0, t["cpi0"], t["cpi1"], t["cpi2"]]), regimes
+    assert ref.compactions >= 4, ref.n_active
+    dev = rs.best_fit(PARAMS, **kw)
+    assert dev.names == ref.names == NAMES3 and dev.x.shape == (R, 3)
+    same_fit(dev, ref, "(b') 520 problems")
+
+
 def test_c_data_vector_profile_and_one_problem(data_fit):
     """(c) The fit's own data vector: a profile over eight fixed values of fsigma8 (per-problem base rows, no realisation
     index; d = 2, launches of 32 rows and fewer) and one problem on its own (d = 3: launches of four rows, below the

@@ -1,0 +1,56 @@
+"""The shape table of tests/launch_shapes.py against the sources, without a GPU: every row still reaches what it was chosen
+for at the thresholds as they stand in victor_hip.hip, vk_host.h, the kernel headers and chains.py, every row is a case of
+tests/test_gpu_launch_shapes.py, and no shape exceeds what ``sample_chains`` accepts.  A failure names the row to revisit."""
+
+import pytest
+
+from tests import launch_shapes as LS
+
+
+@pytest.fixture(scope="module")
+def t():
+    return LS.thresholds()
+
+
+def test_the_thresholds_are_found_and_in_order(t):
+    print(t)
+    assert t["kChainBlock"] == 64 == t["BLOCK"], "one wave per workgroup and blocks of 64 steps: every shape of the table assumes both"
+    assert 0 < t["cells_min"] < t["band1"] < t["band2"] <= t["kPartialPoints"]
+    assert 0 < t["cpi0"] < t["cpi1"] < t["cpi2"]
+    assert t["kFuseMaxDefault"] < t["kPartialPoints"] < t["kFuseBlendedMin"] <= LS.LARGEST_TESTED < t["MAX_CHAINS"]
+    assert t["kZeroCopyMaxDefault"] < LS.LARGEST_TESTED
+
+
+@pytest.mark.parametrize("case", sorted(LS.TABLE))
+def test_a_row_reaches_what_it_is_about(t, case):
+    row = LS.TABLE[case]
+    for v in LS.variants(row):
+        assert 0 < LS.chains(v) <= t["MAX_CHAINS"], (case, LS.chains(v))
+        assert LS.chains(v) <= LS.LARGEST_TESTED, (case, "LARGEST_TESTED and the paragraph of DESIGN.md section 7b no longer say what is tested")
+        assert LS.steps(v, t) == (2 * t["BLOCK"] + 2 if LS.chains(v) <= LS.MANY_CHAINS else t["BLOCK"] + 2)
+        if v["move"] == "stretch":
+            assert v["W"] % 2 == 0 and LS.rows(v) == v["R"] * (v["W"] // 2)
+        for text, check in row["reaches"]:
+            assert check(v, t), f"row {case} ({v['move']}, R = {v['R']}, W = {v['W']}) no longer reaches: {text} - revisit its shape"
+
+
+def test_the_table_is_the_smallest_on_its_thresholds(t):
+    """One below the shape, the property is gone: the sizes are the smallest that cross each threshold."""
+    assert LS.cells_range(t["band1"] - 1, t) == t["cpi0"] and LS.cells_range(t["band1"], t) == t["cpi1"]
+    assert LS.cells_range(t["band2"] - 1, t) == t["cpi1"] and LS.cells_range(t["band2"], t) == t["cpi2"]
+    assert LS.cells_range(t["cells_min"] - 1, t) == 0 and LS.cells_range(t["cells_min"], t) == t["cpi0"]
+    s1 = LS.TABLE["S1"]
+    assert LS.rows(dict(s1, R=s1["R"] - 1)) <= t["kChainBlock"]                   # twelve ensembles of ten: 60 movers, one workgroup
+    t1 = LS.TABLE["T1"]
+    assert max(LS.swap_threads(dict(t1, W=t1["W"] - 1))) <= t["kChainBlock"]      # W = 10: 60 pairs at most
+
+
+def test_every_row_is_a_gpu_case():
+    """The GPU file's parametrisation is built from the table: every row, every variant."""
+    import tests.test_gpu_launch_shapes as G
+    ids = [i for ids in G.IDS.values() for i in ids]
+    assert len(ids) == len(set(ids))
+    for case, row in LS.TABLE.items():
+        mine = [i for i in ids if i.split("-")[0] == case]
+        assert len(mine) >= len(LS.variants(row)), (case, mine)
+    assert {i.split("-")[0] for i in ids} == set(LS.TABLE)
