@@ -698,6 +698,45 @@ int64_t vk_hessian_rows(int32_t n_params);
 int vk_fit_hessian(vk_fit* f, const double* x, const double* h, double* values, double* a, double* hess, double* cov,
                    double* lnpost, double* chi2, int32_t* status);
 
+/* ---- Fisher matrices from model-vector Jacobians at given points of a best-fit handle: forecasts ----------------------------
+ * vk_fit_hessian differentiates lnL twice against a data vector.  vk_fit_fisher answers the question asked before the data
+ * exist: on any handle of the three vk_fit_create calls it evaluates one central-difference stencil of THEORY VECTORS per
+ * problem - M = vk_fisher_rows(n_params) = 2 n_params + 1 rows, the first 2 n_params + 1 points of the Hessian's stencil -
+ * around the point x_p with the steps h_p, and forms F = J^T P J with J = d(theory vector)/d(theta) and P the precision the
+ * handle's chi-square uses at the centre's beta (vk_fisher.h states every order and rounding; victor_amd/fisher.py restates it
+ * in NumPy, bit for bit).  No data vector and no realisation is read: a handle made against realisations only supplies
+ * n_problems.
+ *   vector      N entries: the context's; of a joint handle the blocks' vectors concatenated in block order
+ *   D           D_ak = t_a(x + h_k e_k) - t_a(x - h_k e_k); the division by 2 h is folded into the scaling of the matrices
+ *   P           a fixed covariance: its slice; a beta-gridded one: slice lo where the bracket's weight t is 0, else
+ *               (1 - t) P_lo + t P_last, at the beta of the centre's row (a joint covariance: block 0's row; a block-diagonal
+ *               joint fit: block-diagonal, each block bracketed at the beta of its own row)
+ *   S           S_jk = sum_a D_aj (sum_b P_ab D_bk)
+ *   scale       c = -2 dlnL/dchi2 at chi2 = 0 of the handle's likelihood form: gaussian 1, hartlap (nm - N - 2) / (nm - 1),
+ *               sellentin nm / (nm - 1), percival m / (nm - 1) - exact where data = model
+ *   fisher, a, cov   fisher_jk = (c / 4) S_jk / (h_j h_k): the likelihood's information;  A_jk = (c / 4) S_jk + Lambda_jk h_j h_k
+ *               with Lambda the precision of the prior of vk_fit_set_prior (absent without one);  cov_jk = (h_j h_k) B_jk with
+ *               B = A^-1 through the Cholesky factor of A
+ *   status      the codes of vk_fit_hessian, in this precedence: VK_HESS_AT_BOUND (the stencil leaves the box or x is outside
+ *               it: every row of the problem is formed at x; fisher, a, cov NaN), VK_HESS_NOT_FINITE (an entry of the M vectors
+ *               is not finite; fisher, a, cov NaN), VK_HESS_NOT_POSDEF (a Cholesky pivot fails > 0 - a parameter the theory does
+ *               not depend on gives S_jj = 0 exactly -: fisher and a given, cov NaN), VK_HESS_OK
+ *   x, h        [n_problems][n_params]: the points and per-problem steps (> 0)
+ *   vectors     [n_problems][M][N] the theory vector of every stencil row, or NULL: not downloaded
+ *   fisher, a, cov   [n_problems][n_params][n_params], symmetric;  scale: one double;  status [n_problems].  Any output may be NULL.
+ * The R M rows are evaluated theory-only, in chunks of the handle's largest launch (n_problems S rows, S = max(4, n_params + 1);
+ * chunk boundaries inside problems), into an allocation of the call, [R M][N]; a joint handle makes one theory launch per block
+ * and chunk on the block's stream, ordered against the lead's as the joint entry points order theirs.  One assemble kernel, a
+ * workgroup per problem, holds 2 N n_params doubles in LDS: N n_params <= 10026, more is refused.  Synchronous; the call owns
+ * the contexts as vk_fit_run does.  On error the code is returned, vk_fit_last_error gives the text and nothing stays in
+ * flight.  Refused (VK_E_ARG): what vk_fit_hessian refuses (of the context, a NULL x or h, a point that is not finite, a step
+ * that is not finite or <= 0), a vector too long for the LDS, and a block-diagonal joint handle whose blocks would take
+ * different scales (hartlap / percival with blocks of different lengths).  A handle that never calls it makes the launches it
+ * made before and returns the bytes it returned; the call changes nothing on the handle or its contexts. */
+int64_t vk_fisher_rows(int32_t n_params);
+int vk_fit_fisher(vk_fit* f, const double* x, const double* h, double* vectors, double* fisher, double* a, double* cov, double* scale,
+                  int32_t* status);
+
 /* Theory multipoles on a caller-supplied s grid: out[n][n_ell][n_s] with the caller's own
  * projection weights w_ell[n_ell][n_mu] on mu[n_mu] (host buffers). */
 int vk_theory_batch(vk_ctx* ctx, const vk_eval_opts* opts, const double* params, int64_t n,

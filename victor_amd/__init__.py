@@ -13,8 +13,9 @@ from .chains import Chains
 from .joint import JointFit, JointRealisations
 from .priors import GaussianPrior
 from .laplace import Laplace
+from .fisher import Fisher
 from .realisations import Realisations
 from .utils import InputError
 
 __version__ = "0.1.0"
-__all__ = ["CCFModel", "CCFFit", "BackgroundCosmology", "BestFit", "Chains", "GaussianPrior", "InputError", "JointFit", "JointRealisations", "Laplace", "Realisations", "utils", "__version__"]
+__all__ = ["CCFModel", "CCFFit", "BackgroundCosmology", "BestFit", "Chains", "Fisher", "GaussianPrior", "InputError", "JointFit", "JointRealisations", "Laplace", "Realisations", "utils", "__version__"]

@@ -200,6 +200,9 @@ SYMBOLS = {
     # the Hessian stencil of a best-fit handle and the Laplace covariance from it
     "vk_hessian_rows": (C.c_int64, [C.c_int32]),
     "vk_fit_hessian": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int32)]),
+    # the Jacobian stencil of a best-fit handle's theory vectors and the Fisher matrix from it
+    "vk_fisher_rows": (C.c_int64, [C.c_int32]),
+    "vk_fit_fisher": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int32)]),
     "vk_serve_mailboxes": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, _optp, _vp, C.c_int32, _vp, C.c_double, C.c_int32,
                            C.c_double, C.POINTER(vk_serve_stats)]),
     "vk_timing_enable": (C.c_int, [_vp, C.c_int]),

@@ -351,6 +351,16 @@ class CCFFit(CCFModel):
         from .laplace import laplace
         return laplace(self, params, at, step, fixed, prior, shrink, refine, keep_values, kwargs)
 
+    def fisher(self, params, at, step=None, fixed=None, prior=None, shrink=8, keep_vectors=False, **kwargs):
+        """The Fisher forecast at given points: ``F = J^T P J`` from the central-difference Jacobian of the theory vector over
+        the sampled parameters, ``2 d + 1`` theory evaluations per problem on the GPU (``vk_fit_fisher``), its inverse as the
+        covariance this model, binning and covariance allow, and a status per problem (:mod:`victor_amd.fisher`).  No data
+        vector is read.  ``at``, ``step``, ``fixed``, ``prior``, ``shrink``, ``kwargs`` as :meth:`laplace`; ``keep_vectors``:
+        return the stencil's theory vectors and the Jacobian.  Returns a :class:`victor_amd.fisher.Fisher`.  Runs on this
+        fit's own context (never through the broker)."""
+        from .fisher import fisher
+        return fisher(self, params, at, step, fixed, prior, shrink, keep_vectors, kwargs)
+
     def sample_chains(self, params, n_steps, walkers=8, seed=0, fixed=None, start=None, scatter=None, proposal=None, burn=0,
                       thin=1, keep_chain=True, device=True, move="metropolis", stretch_a=2.0, prior=None, marginals=None, autocorr=None, temper=None,
                       predictive=None, **kwargs):

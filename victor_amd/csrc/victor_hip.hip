@@ -1711,6 +1711,10 @@ vkh::JointRealWs vkh::joint_real_carve(const vk_joint_cov* h, double* d_ws, long
 
 int vkh::joint_cov_n_beta(const vk_joint_cov* h) { return h ? h->n_beta : 0; }
 
+vkh::JointCovView vkh::joint_cov_view(const vk_joint_cov* h) {
+  return JointCovView{h->n_beta > 0 ? h->d_beta : nullptr, h->d_prec, h->NT, h->NTp, h->n_beta};
+}
+
 int vkh::enqueue_joint_cov_realisations(vk_joint_cov* h, vk_ctx* const* ctxs, int n_ctx, const vk_eval_opts* opts, const double* d_par,
                                         long long par_stride, long long m, const int32_t* d_which, double* d_lnl, double* d_chi,
                                         const JointRealWs& w) {

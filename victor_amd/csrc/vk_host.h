@@ -211,6 +211,13 @@ int enqueue_joint_sum_realisations(vk_ctx* const* ctxs, int n_ctx, const vk_eval
                                    double* d_ws);
 // slices of the handle's beta grid (0: one fixed covariance, or no handle)
 int joint_cov_n_beta(const vk_joint_cov* h);
+// the handle's precision tables on the device, for vk_fit_fisher: the beta grid [n_beta] (NULL: one fixed covariance) and the
+// slices [max(n_beta, 1)][NTp][NTp], zero-padded, row stride NTp
+struct JointCovView {
+  const double *beta, *prec;
+  int NT, NTp, n_beta;
+};
+JointCovView joint_cov_view(const vk_joint_cov* h);
 
 // sizeof(vk_ctx) and the offset of its last member as each host-compiled unit sees them (vk_create compares them with its own)
 size_t ctx_layout_walk(size_t* last_offset);

@@ -13,7 +13,7 @@
 //
 // Host code, top to bottom: `Sampled` and what both kinds of handle share - Carve / carve_alloc lay every allocation out,
 // sampled_create, sampled_ready, sampled_evaluate, sampled_launch makes every launch of the unit and sampled_home every download -;
-// best fits and their Hessians; chains, whose optional state (marginals, autocorrelation, tempering, predictive sums, the stretch
+// best fits, their Hessians and Fisher matrices; chains, whose optional state (marginals, autocorrelation, tempering, predictive sums, the stretch
 // buffers) a DevBlock each owns, with the refusals the chain entry points share and the check, the history slot of a step and
 // the ending of the three begin calls stated once.
 //
@@ -33,6 +33,9 @@
 //   vk_kernel_hessian.h  the central-difference stencil of vk_fit_hessian on a best-fit handle: a rows kernel, one thread per
 //                        stencil row, and an assemble kernel, one wave per problem, over the statistic of vk_hessian.h (plain
 //                        C++, likewise)
+//   vk_kernel_fisher.h   the Jacobian stencil of vk_fit_fisher on the same handles: a rows kernel, one thread per stencil row, and
+//                        an assemble kernel, one workgroup per problem, which forms J^T P J from the rows' theory vectors over the
+//                        statistic of vk_fisher.h (plain C++, likewise)
 //   vk_kernel_temper.h   replica exchange on the same handles (vk_chain_begin_tempered): the tempered step kernel, one thread per
 //                        chain, and the swap kernel, one thread per candidate pair of neighbouring rungs, over the transition,
 //                        energy sums and swap of vk_temper_step.h (plain C++, likewise)
@@ -59,6 +62,7 @@
 #include "vk_kernel_autocorr.h"
 #include "vk_kernel_predictive.h"
 #include "vk_kernel_hessian.h"
+#include "vk_kernel_fisher.h"
 
 using namespace vk;
 using vkh::check_joint;
@@ -664,6 +668,214 @@ int vk_fit_hessian(vk_fit* f, const double* x, const double* h, double* values, 
   if (rc != VK_OK) rc = sampled_abort(f, rc);
   (void)hipFree(mem);
   if (rc == VK_OK) f->err.clear();
+  return rc;
+}
+
+}  // extern "C"
+
+// ---- Fisher matrices at given points: one Jacobian stencil of theory vectors per problem (include/victor_hip.h, vk_kernel_fisher.h)
+// The R M stencil rows, M = 2 d + 1, go through in chunks of rows_max consecutive global rows as the Hessian's do (M may be
+// smaller than a problem's S rows - d = 1 - or larger; chunk boundaries fall inside problems): a rows kernel, then a THEORY-ONLY
+// evaluation (vk_eval_batch_device_async without lnl / chi2: no data vector and no realisation is read, the handle's pending
+// results and workspace stay untouched) straight into the call's own [R M][N] allocation at the chunk's offset.  A joint fit
+// makes one such evaluation per block context into that block's [R M][N_q] part, on the block's own stream between the two
+// event hand-overs the joint entry points use: every block stream waits for the lead's (the rows are written there), the lead
+// waits for every block's before it writes the next chunk's rows or assembles.  One assemble kernel follows on the lead stream.
+// Nothing of the handle or its contexts is toggled: a handle that never calls this makes the launches it made before.
+struct FisherMem {
+  double *x = nullptr, *h = nullptr, *vec = nullptr, *fisher = nullptr, *a = nullptr, *cov = nullptr;
+  int* status = nullptr;
+  void layout(Carve& c, size_t R, size_t d, size_t M, size_t N) {
+    c.take(x, R * d);
+    c.take(h, R * d);
+    c.take(vec, R * M * N);
+    c.take(fisher, R * d * d);
+    c.take(a, R * d * d);
+    c.take(cov, R * d * d);
+    c.take(status, R);
+  }
+};
+
+// the entries of the handle's theory vector (a joint fit: of its blocks' vectors, concatenated)
+static int fisher_entries(const vk_fit* f) {
+  if (f->blocks.empty()) return f->ctx->N;
+  int n = 0;
+  for (const vk_ctx* c : f->blocks) n += c->N;
+  return n;
+}
+
+// c of vk_fisher.h for the handle's likelihood form; false: the blocks of a block-diagonal joint fit disagree about it
+static bool fisher_scale(const vk_fit* f, double* c) {
+  const vk_eval_opts& o = f->opts;
+  if (f->blocks.empty() || f->cov) {
+    *c = vkfisher::form_scale(o.like_form, o.nmocks, o.nparams, (double)fisher_entries(f));
+    return true;
+  }
+  *c = vkfisher::form_scale(o.like_form, o.nmocks, o.nparams, (double)f->blocks[0]->N);
+  for (const vk_ctx* b : f->blocks)
+    if (vkfisher::form_scale(o.like_form, o.nmocks, o.nparams, (double)b->N) != *c) return false;
+  return true;
+}
+
+static int fisher_run(vk_fit* f, const FisherMem& m, double c, const double* x, const double* h, double* vectors, double* fisher,
+                      double* a, double* cov, int32_t* status) {
+  vk_ctx* ctx = f->ctx;
+  const size_t R = f->R, d = f->P, M = (size_t)vkfisher::n_rows(f->P), N = (size_t)fisher_entries(f);
+  const int nb = (int)f->blocks.size();
+  VK_SAMPLED_HIP(f, hipMemcpyAsync(m.x, x, R * d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  VK_SAMPLED_HIP(f, hipMemcpyAsync(m.h, h, R * d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  FisherArgs q{};
+  q.d = (int)d;
+  q.M = (int)M;
+  q.R = (int)R;
+  q.N = (int)N;
+  for (size_t j = 0; j < d; ++j) {
+    q.lo[j] = f->lo[j];
+    q.hi[j] = f->hi[j];
+  }
+  q.x = m.x;
+  q.h = m.h;
+  q.base = f->d_base;
+  q.rows = f->d_rows;
+  for (int j = 0; j < vkhess::kMaxP; ++j) q.col[j] = f->col[j];
+  q.alpha = f->alpha;
+  q.blocks = f->row_sets(R);
+  q.prior = f->prior;
+  q.c = c;
+  q.fisher = m.fisher;
+  q.a = m.a;
+  q.cov = m.cov;
+  q.status = m.status;
+  // the segments: block b's vectors at vec + R M off_b, against the precision its entries meet
+  q.n_seg = nb ? nb : 1;
+  int off = 0;
+  for (int b = 0; b < q.n_seg; ++b) {
+    const vk_ctx* bc = nb ? f->blocks[b] : ctx;
+    FisherSeg& s = q.seg[b];
+    s.theory = m.vec + R * M * (size_t)off;
+    s.N = bc->N;
+    s.off = off;
+    if (f->cov) {                                  // one covariance across the blocks: its padded slices, beta of block 0's rows
+      const vkh::JointCovView v = vkh::joint_cov_view(f->cov);
+      s.prec = v.prec;
+      s.beta_c = v.beta;
+      s.n_beta_c = v.n_beta;
+      s.ld = v.NTp;
+      s.slice = (long long)v.NTp * v.NTp;
+      s.prow0 = off;
+      s.poff = 0;
+      s.pn = v.NT;
+      s.set = 0;
+    } else {
+      s.prec = bc->d_prec;
+      s.beta_c = bc->n_beta_c > 0 ? bc->d_beta_c : nullptr;
+      s.n_beta_c = bc->n_beta_c;
+      s.ld = bc->N;
+      s.slice = (long long)bc->N * bc->N;
+      s.prow0 = 0;
+      s.poff = off;
+      s.pn = bc->N;
+      s.set = f->sets > 1 ? b : 0;
+    }
+    off += bc->N;
+  }
+  const long long total = (long long)(R * M), chunk = (long long)f->rows_max, ps = f->par_stride();
+  for (int b = 1; b < nb; ++b)
+    if (!f->blocks[b]->ev_joint) VK_SAMPLED_HIP(f, hipEventCreateWithFlags(&f->blocks[b]->ev_joint, hipEventDisableTiming));
+  if (nb && !ctx->ev_joint) VK_SAMPLED_HIP(f, hipEventCreateWithFlags(&ctx->ev_joint, hipEventDisableTiming));
+  for (long long g0 = 0; g0 < total; g0 += chunk) {
+    const long long n = std::min(chunk, total - g0);
+    q.g0 = g0;
+    q.n = n;
+    int rc = sampled_launch(f, vk_fisher_rows_kernel, n, kFisherRowsBlock, q);
+    if (rc) return rc;
+    if (!nb) {
+      rc = vk_eval_batch_device_async(ctx, &f->opts, f->d_rows, n, nullptr, nullptr, m.vec + (size_t)g0 * N);
+      if (rc) f->err = ctx->err;
+      if (rc) return rc;
+      continue;
+    }
+    VK_SAMPLED_HIP(f, hipEventRecord(ctx->ev_joint, ctx->stream));
+    for (int b = 0; b < nb; ++b) {
+      vk_ctx* bc = f->blocks[b];
+      if (b > 0) VK_SAMPLED_HIP(f, hipStreamWaitEvent(bc->stream, ctx->ev_joint, 0));
+      rc = vk_eval_batch_device_async(bc, &f->opts, f->d_rows + b * ps, n, nullptr, nullptr,
+                                      const_cast<double*>(q.seg[b].theory) + (size_t)g0 * bc->N);
+      if (rc) f->err = bc->err;
+      if (rc) return rc;
+    }
+    for (int b = 1; b < nb; ++b) {
+      VK_SAMPLED_HIP(f, hipEventRecord(f->blocks[b]->ev_joint, f->blocks[b]->stream));
+      VK_SAMPLED_HIP(f, hipStreamWaitEvent(ctx->stream, f->blocks[b]->ev_joint, 0));
+    }
+  }
+  const size_t lds = fisher_lds_doubles((int)N, (int)d) * sizeof(double);
+  if (lds > 64 * 1024) {                           // (the per-kernel opt-in of launch_on_stream, victor_hip.hip: sticky, asked for once)
+    int& granted = ctx->lds_opt_in[reinterpret_cast<const void*>(vk_fisher_assemble_kernel)];
+    if ((int)lds > granted) {
+      VK_SAMPLED_HIP(f, hipFuncSetAttribute(reinterpret_cast<const void*>(vk_fisher_assemble_kernel),
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      granted = (int)lds;
+    }
+  }
+  hipLaunchKernelGGL(vk_fisher_assemble_kernel, dim3((unsigned)R), dim3(kFisherBlock), lds, ctx->stream, q);   // a workgroup per problem
+  VK_SAMPLED_HIP(f, hipGetLastError());
+  const size_t mat = R * d * d * sizeof(double);
+  int rc = sampled_home(f, {{fisher, m.fisher, mat}, {a, m.a, mat}, {cov, m.cov, mat}, {status, m.status, R * sizeof(int)}}, true);
+  if (rc) return rc;
+  // the vectors, [R][M][N]: a joint fit's blocks side by side in every row
+  if (vectors)
+    for (int b = 0; b < q.n_seg; ++b)
+      VK_SAMPLED_HIP(f, hipMemcpy2DAsync(vectors + q.seg[b].off, N * sizeof(double), q.seg[b].theory, (size_t)q.seg[b].N * sizeof(double),
+                                         (size_t)q.seg[b].N * sizeof(double), R * M, hipMemcpyDeviceToHost, ctx->stream));
+  VK_SAMPLED_HIP(f, hipStreamSynchronize(ctx->stream));
+  return VK_OK;
+}
+
+extern "C" {
+
+int64_t vk_fisher_rows(int32_t n_params) {
+  return n_params >= 1 && n_params <= kSampledMaxP ? (int64_t)vkfisher::n_rows(n_params) : 0;
+}
+
+int vk_fit_fisher(vk_fit* f, const double* x, const double* h, double* vectors, double* fisher, double* a, double* cov, double* scale,
+                  int32_t* status) {
+  if (!f) return VK_E_ARG;
+  if (!x || !h) return refused(f, "vk_fit_fisher: NULL argument");
+  int rc = sampled_ready(f, "vk_fit_fisher", "problem", false);
+  if (rc) return rc;
+  const size_t R = f->R, d = f->P;
+  for (size_t p = 0; p < R; ++p)
+    for (size_t j = 0; j < d; ++j) {
+      if (!__builtin_isfinite(x[p * d + j]))
+        return refused(f, "vk_fit_fisher: the point of problem " + std::to_string(p) + " is not finite in parameter " + std::to_string(j));
+      if (!(h[p * d + j] > 0) || !__builtin_isfinite(h[p * d + j]))
+        return refused(f, "vk_fit_fisher: problem " + std::to_string(p) + ", parameter " + std::to_string(j) + " needs a finite step > 0");
+    }
+  const int N = fisher_entries(f);
+  if (fisher_lds_doubles(N, (int)d) > (size_t)kFisherLdsDoubles)
+    return refused(f, "vk_fit_fisher: a theory vector of " + std::to_string(N) + " entries with " + std::to_string(d) +
+                          " parameters needs more than 160 KiB of LDS (entries x parameters <= " +
+                          std::to_string((kFisherLdsDoubles - 3 * vkhess::kMaxP * vkhess::kMaxP) / 2) + ")");
+  double c = 1.0;
+  if (!fisher_scale(f, &c))
+    return refused(f, "vk_fit_fisher: the blocks of a block-diagonal joint fit have different lengths, and this likelihood form "
+                      "scales each block's chi-square by a factor of its own: there is no one scale");
+  VK_SAMPLED_HIP(f, hipSetDevice(f->ctx->device));
+  FisherMem m;
+  void* mem = nullptr;
+  size_t bytes = 0;
+  if (!carve_alloc(f->ctx->device, mem, bytes, [&](Carve& cv) { m.layout(cv, R, d, (size_t)vkfisher::n_rows(f->P), (size_t)N); })) {
+    f->err = "vk_fit_fisher: " + cannot_allocate(bytes);
+    return VK_E_HIP;
+  }
+  rc = fisher_run(f, m, c, x, h, vectors, fisher, a, cov, status);
+  if (rc != VK_OK) rc = sampled_abort(f, rc);
+  (void)hipFree(mem);
+  if (rc == VK_OK) {
+    if (scale) *scale = c;
+    f->err.clear();
+  }
   return rc;
 }
 

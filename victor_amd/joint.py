@@ -520,6 +520,13 @@ class JointFit:
         from .laplace import laplace
         return laplace(self, params, at, step, fixed, prior, shrink, refine, keep_values, kwargs)
 
+    def fisher(self, params, at, step=None, fixed=None, prior=None, shrink=8, keep_vectors=False, **kwargs):
+        """The Fisher forecast of the joint vector at given points (``CCFFit.fisher``): the blocks' theory vectors
+        concatenated, under the joint covariance or block-diagonal, ``"name@q"`` parameters included (at most 10 sampled
+        values in all).  Arguments and result as ``CCFFit.fisher``."""
+        from .fisher import fisher
+        return fisher(self, params, at, step, fixed, prior, shrink, keep_vectors, kwargs)
+
     def sample_chains(self, params, n_steps, walkers=8, seed=0, fixed=None, start=None, scatter=None, proposal=None, burn=0,
                       thin=1, keep_chain=True, device=True, move="metropolis", stretch_a=2.0, prior=None, marginals=None, autocorr=None, temper=None,
                       predictive=None, **kwargs):
@@ -583,6 +590,12 @@ class JointRealisations:
         the GPU.  Arguments and result as ``JointFit.laplace``; ``fixed`` values must be scalars."""
         from .laplace import laplace
         return laplace(self.joint, params, at, step, fixed, prior, shrink, refine, keep_values, kwargs, realisations=self)
+
+    def fisher(self, params, at, step=None, fixed=None, prior=None, shrink=8, keep_vectors=False, **kwargs):
+        """The Fisher forecast (``JointFit.fisher``) at every joint realisation's own point, all of them in one call on the
+        GPU; the realisations only supply the number of problems.  ``fixed`` values must be scalars."""
+        from .fisher import fisher
+        return fisher(self.joint, params, at, step, fixed, prior, shrink, keep_vectors, kwargs, realisations=self)
 
     def sample_chains(self, params, n_steps, walkers=8, seed=0, fixed=None, start=None, scatter=None, proposal=None, burn=0,
                       thin=1, keep_chain=True, device=True, move="metropolis", stretch_a=2.0, prior=None, marginals=None, autocorr=None, temper=None,

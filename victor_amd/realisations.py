@@ -152,6 +152,14 @@ class Realisations:
         from .laplace import laplace
         return laplace(self.fit, params, at, step, fixed, prior, shrink, refine, keep_values, kwargs, realisations=self)
 
+    def fisher(self, params, at, step=None, fixed=None, prior=None, shrink=8, keep_vectors=False, **kwargs):
+        """The Fisher forecast (``CCFFit.fisher``) at EVERY realisation's own point (``at``: typically the ``BestFit`` of
+        :meth:`best_fit`), one problem per realisation in one call on the GPU.  The realisations only supply the number of
+        problems: the forecast reads no data.  Arguments and result as ``CCFFit.fisher``; ``fixed`` values must be scalars
+        here."""
+        from .fisher import fisher
+        return fisher(self.fit, params, at, step, fixed, prior, shrink, keep_vectors, kwargs, realisations=self)
+
     def sample_chains(self, params, n_steps, walkers=8, seed=0, fixed=None, start=None, scatter=None, proposal=None, burn=0,
                       thin=1, keep_chain=True, device=True, move="metropolis", stretch_a=2.0, prior=None, marginals=None, autocorr=None, temper=None,
                       predictive=None, **kwargs):
