@@ -38,11 +38,12 @@ def fisher_bound(D, P, h, scale, dt):
     return 0.25 * abs(float(scale)) * dS / np.outer(h, h)
 
 
-def dense_precision(blocks, r, N, R):
-    """The (N, N) precision of problem ``r`` of R from a list of :class:`victor_amd.fisher.Block`."""
+def dense_precision(blocks, r, N, R, slices=None):
+    """The (N, N) precision of problem ``r`` of R from a list of :class:`victor_amd.fisher.Block` (``slices``: the blocks'
+    ``precision(R)``, formed once by a caller that loops over the problems)."""
     P = np.zeros((N, N))
-    for b in blocks:
-        P[b.off:b.off + b.n, b.off:b.off + b.n] = b.precision(R)[r]
+    for i, b in enumerate(blocks):
+        P[b.off:b.off + b.n, b.off:b.off + b.n] = (b.precision(R) if slices is None else slices[i])[r]
     return P
 
 
@@ -52,8 +53,9 @@ def assert_same_fisher(got, want, D, blocks, h, scale, dt, what=""):
     got, want = np.asarray(got, dtype=float), np.asarray(want, dtype=float)
     assert got.shape == want.shape, (what, got.shape, want.shape)
     worst = 0.0
+    slices = [b.precision(len(got)) for b in blocks]
     for r in range(len(got)):
-        bound = fisher_bound(D[r], dense_precision(blocks, r, D.shape[1], len(got)), h[r], scale, dt)
+        bound = fisher_bound(D[r], dense_precision(blocks, r, D.shape[1], len(got), slices), h[r], scale, dt)
         diff = np.abs(got[r] - want[r])
         assert np.all(np.isfinite(diff)), (what, r, "not finite")
         margin = float(np.max(diff / bound))

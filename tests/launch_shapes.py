@@ -8,7 +8,11 @@ stand - when somebody moves a threshold, that test fails and names the row to re
 A row: ``R`` problems x ``K`` rungs (1 without tempering) x ``W`` walkers, the move and the route.  ``chains(row)`` is R K W,
 ``rows(row)`` the rows of one evaluation launch inside the loop - R K W for the Metropolis moves, half of it for the stretch move,
 whose half-steps move half of every ensemble - and ``steps(row)`` the step count: 2 BLOCK + 2 up to 600 chains, BLOCK + 2 above
-(one block edge plus two)."""
+(one block edge plus two).
+
+``STENCILS``, further down, is the same for the two stencil calls - ``laplace`` (vk_fit_hessian) and ``fisher`` (vk_fit_fisher);
+tests/test_gpu_stencil_shapes.py; DESIGN.md section 7a, "Launch shapes under test" - whose R M rows go through in chunks of R S
+rows: ``slots``, ``points``, ``chunks``."""
 
 import os
 import re
@@ -54,6 +58,22 @@ def thresholds():
     _one(r"(?m)^BLOCK = EnsembleMetropolis\.BLOCK$", chains, "BLOCK of chains.py")
     t["BLOCK"] = int(_one(r"(?m)^    BLOCK = (\d+)", _read("victor_amd", "sampler.py"), "EnsembleMetropolis.BLOCK").group(1))
     t["VK_NPAR"] = int(_one(r"#define VK_NPAR (\d+)", _read("include", "victor_hip.h"), "VK_NPAR").group(1))
+    # the stencil calls (vk_fit_hessian, vk_fit_fisher): their kernels' workgroups and the LDS ceiling of the Fisher assemble kernel
+    t["kHessBlock"] = int(_one(r"constexpr int kHessBlock = (\d+);", _read("victor_amd", "csrc", "vk_kernel_hessian.h"), "kHessBlock").group(1))
+    fisher = _read("victor_amd", "csrc", "vk_kernel_fisher.h")
+    for name in ("kFisherRowsBlock", "kFisherBlock", "kFisherMaxSeg"):
+        t[name] = int(_one(r"constexpr int %s = (\d+);" % name, fisher, name).group(1))
+    m = _one(r"constexpr int kFisherLdsDoubles = (\d+) - (\d+);", fisher, "kFisherLdsDoubles")
+    t["kFisherLdsDoubles"] = int(m.group(1)) - int(m.group(2))
+    # the rules the constants enter: the doubles a workgroup asks for, the slots of a problem in the handle's largest launch, and
+    # the chunks both stencil loops cut their R M rows into
+    _one(r"fisher_lds_doubles\(int N, int d\) \{ return 2 \* \(size_t\)N \* d \+ 3 \* vkhess::kMaxP \* vkhess::kMaxP; \}", fisher, "fisher_lds_doubles")
+    t["kMaxP"] = int(_one(r"constexpr int kMaxP = (\d+);", _read("victor_amd", "csrc", "vk_hessian.h"), "vkhess::kMaxP").group(1))
+    _one(r"inline int slots\(int d\) \{ return d \+ 1 > 4 \? d \+ 1 : 4; \}", _read("victor_amd", "csrc", "vk_fit_simplex.h"), "vkfit::slots")
+    sampled = _read("victor_amd", "csrc", "vk_sampled.hip")
+    _one(r"rows_max = \(size_t\)R \* S;", sampled, "rows_max of a vk_fit handle")
+    assert len(re.findall(r"const long long total = \(long long\)\(R \* M\), chunk = \(long long\)f->rows_max", sampled)) == 2, \
+        "the chunk loops of hessian_run and fisher_run no longer match their pattern"
     return t
 
 
@@ -184,3 +204,128 @@ def variants(row):
     moves = row["move"] if isinstance(row["move"], tuple) else (row["move"],)
     widths = row["W"] if isinstance(row["W"], tuple) else (row["W"],)
     return [dict(row, move=m, W=w) for m in moves for w in widths]
+
+
+# ------------------------------------------------------------------ the stencil calls: laplace and fisher -------------------------
+# vk_fit_hessian and vk_fit_fisher cut the R M stencil rows of a call into chunks of rows_max = R S rows (S the slots of a
+# problem in the search's launches), each chunk an evaluation launch of its own: the full chunks have R S rows, the last one
+# the remainder - which may lie in another regime of the evaluator than the chunks before it.  A row of ``STENCILS``: the
+# ``call`` ("laplace", "fisher" or both), the ``route``, d sampled parameters and R problems (one or several), and ``reaches``
+# as in ``TABLE``.  A row that claims to be the smallest on its threshold names the property in ``smallest``: it holds at the
+# row's largest R and not one problem below.
+def slots(d):
+    """vkfit::slots (vk_fit_simplex.h)."""
+    return max(4, d + 1)
+
+
+def points(call, d):
+    """Stencil points per problem: vkhess::n_points, vkfisher::n_rows."""
+    return {"laplace": 2 * d * d + 1, "fisher": 2 * d + 1}[call]
+
+
+def chunks(row):
+    """The chunk lengths of the R M rows of a call, in launch order."""
+    total, chunk = row["R"] * points(row["call"], row["d"]), row["R"] * slots(row["d"])
+    return [min(chunk, total - g0) for g0 in range(0, total, chunk)]
+
+
+def fisher_lds_doubles(n_entries, d, t):
+    """fisher_lds_doubles of vk_kernel_fisher.h: the dynamic LDS of the Fisher assemble kernel, in doubles."""
+    return 2 * n_entries * d + 3 * t["kMaxP"] * t["kMaxP"]
+
+
+def _full(r):
+    return chunks(r)[:-1]
+
+
+def _last(r):
+    return chunks(r)[-1]
+
+
+def _all_full(check):
+    return lambda r, t: len(_full(r)) > 0 and all(check(m, t) for m in _full(r))
+
+
+def _is(*lengths):
+    """The chunks are exactly these."""
+    return lambda r, t: chunks(r) == list(lengths)
+
+
+BOSS_N, DSPLIT_N = 60, 120          # entries of the BOSS theory vector (30 s bins, two poles) and of a density-split block's
+
+STENCILS = {
+    "H1": dict(call="laplace", route="data", d=3, R=5, reaches=[
+        ("the first chunk exactly at cells_min", lambda r, t: chunks(r)[0] == t["cells_min"] and cells_range(chunks(r)[0], t) == t["cpi0"]),
+        ("the last chunk on the point-major kernel", lambda r, t: cells_range(_last(r), t) == 0)],
+        smallest=lambda r, t: cells_range(chunks(r)[0], t) != 0),
+    "H2": dict(call="laplace", route="data", d=3, R=32, reaches=[
+        ("four chunks of 128 and one of 96", _is(128, 128, 128, 128, 96)),
+        ("full chunks in the middle band, the last in the lower band", lambda r, t: _all_full(lambda m, t: cells_range(m, t) == t["cpi1"])(r, t)
+         and cells_range(_last(r), t) == t["cpi0"]),
+        ("every chunk fused", lambda r, t: all(fused(m, t) for m in chunks(r)))]),
+    "H3": dict(call="laplace", route="data", d=3, R=(128, 129), reaches=[
+        ("R = 128: every chunk fused, the full ones at the fuse limit", lambda r, t: r["R"] != 128 or (chunks(r)[0] == t["kFuseMaxDefault"]
+         and all(fused(m, t) for m in chunks(r)))),
+        ("R = 129: the full chunks unfused, the last chunk fused", lambda r, t: r["R"] != 129 or (_all_full(lambda m, t: not fused(m, t))(r, t)
+         and fused(_last(r), t)))],
+        smallest=lambda r, t: not fused(chunks(r)[0], t)),
+    "H4": dict(call="laplace", route="data", d=3, R=513, reaches=[
+        ("full chunks one workgroup per point", _all_full(lambda m, t: cells_range(m, t) == -1)),
+        ("the last chunk back on partial sums", lambda r, t: cells_range(_last(r), t) == t["cpi2"]),
+        ("every chunk unfused", lambda r, t: not any(fused(m, t) for m in chunks(r)))],
+        smallest=lambda r, t: cells_range(chunks(r)[0], t) == -1),
+    "H5": dict(call="laplace", route="data", d=3, R=2048, reaches=[
+        ("full chunks fused again under the gridded covariance", _all_full(lambda m, t: m >= t["kFuseBlendedMin"] and fused(m, t) and not fused(m, t, gridded=False))),
+        ("the last chunk unfused, one workgroup per point", lambda r, t: not fused(_last(r), t) and cells_range(_last(r), t) == -1),
+        ("2048 workgroups of the assemble kernel, 32 full workgroups of the rows kernel per chunk", lambda r, t: r["R"] == 2048
+         and chunks(r)[0] % t["kHessBlock"] == 0)],
+        smallest=lambda r, t: fused(chunks(r)[0], t)),
+    "H6": dict(call="laplace", route="data", d=1, R=513, reaches=[
+        ("M < S: one chunk, shorter than the buffer", lambda r, t: points("laplace", r["d"]) < slots(r["d"]) and len(chunks(r)) == 1),
+        ("the chunk on partial sums, the buffer's length one workgroup per point", lambda r, t: cells_range(chunks(r)[0], t) == t["cpi2"]
+         and cells_range(r["R"] * slots(r["d"]), t) == -1)]),
+    "H7": dict(call="laplace", route="mocks", d=3, R=513, reaches=[
+        ("the pairs-mode realisation kernel at one workgroup per point, then on partial sums", lambda r, t: cells_range(chunks(r)[0], t) == -1
+         and cells_range(_last(r), t) == t["cpi2"]),
+        ("row_which over 33 workgroups of the rows kernel", lambda r, t: -(-chunks(r)[0] // t["kHessBlock"]) == 33)]),
+    "F1": dict(call="fisher", route="data", d=3, R=(4, 5), reaches=[
+        ("R = 4: point-major", lambda r, t: r["R"] != 4 or all(cells_range(m, t) == 0 for m in chunks(r))),
+        ("R = 5: the first chunk exactly at cells_min", lambda r, t: r["R"] != 5 or (chunks(r)[0] == t["cells_min"] and cells_range(_last(r), t) == 0))],
+        smallest=lambda r, t: cells_range(chunks(r)[0], t) != 0),
+    "F2": dict(call="fisher", route="data", d=3, R=32, reaches=[
+        ("middle and lower band", lambda r, t: chunks(r) == [128, 96] and cells_range(128, t) == t["cpi1"] and cells_range(96, t) == t["cpi0"])]),
+    "F3": dict(call="fisher", route="data", d=3, R=64, reaches=[
+        ("upper and middle band", lambda r, t: chunks(r) == [256, 192] and cells_range(256, t) == t["cpi2"] and cells_range(192, t) == t["cpi1"])]),
+    "F4": dict(call="fisher", route="data", d=3, R=513, reaches=[
+        ("one workgroup per point, then partial sums", lambda r, t: chunks(r) == [2052, 1539] and cells_range(2052, t) == -1
+         and cells_range(1539, t) == t["cpi2"]),
+        ("the second chunk written at an offset of 2052 N doubles, past one workgroup of the rows kernel", lambda r, t: chunks(r)[0] * BOSS_N == 123120
+         and chunks(r)[0] > t["kFisherRowsBlock"])],
+        smallest=lambda r, t: cells_range(chunks(r)[0], t) == -1),
+    "J6": dict(call=("laplace", "fisher"), route=("five_cov", "five_diag"), d=2, R=130, reaches=[
+        ("520 rows per chunk: more than two sort chunks of the joint chi-square kernels, past the fuse limit", lambda r, t: chunks(r)[0] == 520
+         and chunks(r)[0] > 2 * t["kJointSortChunk"] and chunks(r)[0] > t["kFuseMaxDefault"]),
+        ("a shorter last chunk", lambda r, t: 0 < _last(r) < chunks(r)[0])]),
+    "J7": dict(call="laplace", route="boss_grid", d=3, R=130, reaches=[
+        ("the counting sort over three chunks", lambda r, t: -(-chunks(r)[0] // t["kJointSortChunk"]) == 3 and chunks(r)[0] == 520)]),
+    "J8": dict(call=("laplace", "fisher"), route="five_cov", d=10, R=24, reaches=[
+        ("264 rows per chunk; M = 201 for laplace", lambda r, t: chunks(r)[0] == 264 and (r["call"] != "laplace" or points("laplace", r["d"]) == 201)),
+        ("96 KiB of LDS in 24 workgroups of the Fisher assemble kernel", lambda r, t: r["call"] != "fisher"
+         or (64 * 1024 < 8 * fisher_lds_doubles(5 * DSPLIT_N, r["d"], t) <= 8 * t["kFisherLdsDoubles"] and r["R"] == 24))]),
+}
+SMALLEST = ("H1", "H3", "H4", "H5", "F1", "F4")
+
+# The LDS ceiling of the Fisher assemble kernel (tests/test_gpu_stencil_shapes.py, section 4): block-diagonal joint fits of
+# fixed-covariance BOSS blocks of BOSS_N entries each - the largest N d the library accepts in 16 of its 32 segments, and the
+# first it refuses.
+CEILING = dict(accepted=dict(blocks=16, d=10, R=2), refused=dict(blocks=17, d=10, R=2), below=dict(blocks=17, d=9, R=2))
+
+# What stays untested: the stencil calls above 8192 rows per chunk, and ``refine`` passes at these sizes.
+LARGEST_STENCIL_CHUNK = 8192
+
+
+def stencil_variants(row):
+    """The (call, route, R) combinations of a stencil row."""
+    def each(v):
+        return v if isinstance(v, tuple) else (v,)
+    return [dict(row, call=c, route=p, R=n) for c in each(row["call"]) for p in each(row["route"]) for n in each(row["R"])]

@@ -45,15 +45,18 @@ def time_limit():
 
 class NoiseFree:
     """86 noise-free realisations of the fixed-covariance stack: 16 at random points of the inner 60 % of the box, then 70 that
-    differ in sigma_v alone (the other parameters at ``common``)."""
+    differ in sigma_v alone (the other parameters at ``common``).  With ``truth`` (n, 4): a stack of those truths instead."""
 
-    def __init__(self, tmp):
+    def __init__(self, tmp, truth=None):
         import victor_amd
         self.base = victor_amd.CCFFit(*stack_options(fixed=True))
-        rng = np.random.default_rng(5)
-        self.truth = LO + (HI - LO) * (0.2 + 0.6 * rng.random((86, 4)))
-        self.common = self.truth[16].copy()
-        self.truth[16:, [0, 1, 3]] = self.common[[0, 1, 3]]
+        if truth is None:
+            rng = np.random.default_rng(5)
+            self.truth = LO + (HI - LO) * (0.2 + 0.6 * rng.random((86, 4)))
+            self.common = self.truth[16].copy()
+            self.truth[16:, [0, 1, 3]] = self.common[[0, 1, 3]]
+        else:
+            self.truth, self.common = np.array(truth, dtype=float), None
         t = self.base.theory_vector_batch({n: self.truth[:, j] for j, n in enumerate(NAMES)})
         n_s = len(self.base.s)
         s = np.load(os.path.join(REAL, "stack_fixed.npy"), allow_pickle=True).item()

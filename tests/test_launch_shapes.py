@@ -1,6 +1,8 @@
 """The shape table of tests/launch_shapes.py against the sources, without a GPU: every row still reaches what it was chosen
 for at the thresholds as they stand in victor_hip.hip, vk_host.h, the kernel headers and chains.py, every row is a case of
-tests/test_gpu_launch_shapes.py, and no shape exceeds what ``sample_chains`` accepts.  A failure names the row to revisit."""
+tests/test_gpu_launch_shapes.py, and no shape exceeds what ``sample_chains`` accepts.  The same for ``STENCILS``, the shapes of the
+two stencil calls (tests/test_gpu_stencil_shapes.py), and for the cases at the LDS ceiling of the Fisher assemble kernel.  A
+failure names the row to revisit."""
 
 import pytest
 
@@ -54,3 +56,57 @@ def test_every_row_is_a_gpu_case():
         mine = [i for i in ids if i.split("-")[0] == case]
         assert len(mine) >= len(LS.variants(row)), (case, mine)
     assert {i.split("-")[0] for i in ids} == set(LS.TABLE)
+
+
+# ------------------------------------------------------------------ the stencil calls ------------------------------------------------
+def test_the_stencil_thresholds_are_found_and_in_order(t):
+    assert t["kHessBlock"] == 64 == t["kFisherRowsBlock"], "one wave per workgroup of both rows kernels: every stencil row assumes it"
+    assert t["kFisherMaxSeg"] <= t["kFisherBlock"] and t["kMaxP"] == 10
+    assert 64 * 1024 < 8 * t["kFisherLdsDoubles"] <= 160 * 1024
+    assert LS.slots(1) == LS.slots(3) == 4 and LS.slots(4) == 5 and LS.slots(10) == 11
+    assert LS.points("laplace", 3) == 19 and LS.points("fisher", 3) == 7 and LS.points("laplace", 10) == 201 and LS.points("fisher", 10) == 21
+    assert LS.chunks(dict(call="laplace", d=4, R=16)) == [80] * 6 + [48]          # (the shapes tests/test_gpu_hessian.py states)
+    assert LS.chunks(dict(call="fisher", d=4, R=16)) == [80, 64] and LS.chunks(dict(call="fisher", d=1, R=70)) == [210]
+
+
+@pytest.mark.parametrize("case", sorted(LS.STENCILS))
+def test_a_stencil_row_reaches_what_it_is_about(t, case):
+    row = LS.STENCILS[case]
+    for v in LS.stencil_variants(row):
+        lengths = LS.chunks(v)
+        assert sum(lengths) == v["R"] * LS.points(v["call"], v["d"]) and max(lengths) == lengths[0] <= v["R"] * LS.slots(v["d"])
+        assert max(lengths) <= LS.LARGEST_STENCIL_CHUNK, (case, "LARGEST_STENCIL_CHUNK and the paragraph of DESIGN.md section 7a no longer say what is tested")
+        assert 1 <= v["d"] <= t["kMaxP"]
+        for text, check in row["reaches"]:
+            assert check(v, t), f"stencil row {case} ({v['call']}, {v['route']}, R = {v['R']}, d = {v['d']}) no longer reaches: {text} - revisit its shape"
+
+
+@pytest.mark.parametrize("case", LS.SMALLEST)
+def test_a_stencil_row_is_the_smallest_on_its_threshold(t, case):
+    """One problem fewer, and the property is gone."""
+    row = LS.STENCILS[case]
+    v = max(LS.stencil_variants(row), key=lambda v: v["R"])
+    assert row["smallest"](v, t), f"stencil row {case} at R = {v['R']} no longer has the property it is the smallest for - revisit its shape"
+    assert not row["smallest"](dict(v, R=v["R"] - 1), t), f"stencil row {case}: R = {v['R'] - 1} has the property too - revisit its shape"
+
+
+def test_the_lds_ceiling_cases_sit_on_the_limit(t):
+    """The accepted case is the largest N d in whole BOSS blocks at d = 10, the refused one the next, and d = 9 fits again."""
+    c = LS.CEILING
+    def doubles(k):
+        return LS.fisher_lds_doubles(c[k]["blocks"] * LS.BOSS_N, c[k]["d"], t)
+    assert doubles("accepted") <= t["kFisherLdsDoubles"] < doubles("refused"), "the LDS ceiling moved: revisit CEILING"
+    assert doubles("below") <= t["kFisherLdsDoubles"]
+    assert c["refused"]["blocks"] == c["accepted"]["blocks"] + 1 == c["below"]["blocks"] and c["refused"]["blocks"] <= t["kFisherMaxSeg"]
+    assert 8 * doubles("accepted") > 150 * 1024 and c["accepted"]["blocks"] > 5
+
+
+def test_every_stencil_row_is_a_gpu_case():
+    """The GPU file's parametrisation is built from the table: every row, every variant."""
+    import tests.test_gpu_stencil_shapes as G
+    ids = [i for ids in G.IDS.values() for i in ids]
+    assert len(ids) == len(set(ids))
+    for case, row in LS.STENCILS.items():
+        mine = [i for i in ids if i.split("-")[0] == case]
+        assert len(mine) == len(LS.stencil_variants(row)), (case, mine)
+    assert {i.split("-")[0] for i in ids} == set(LS.STENCILS)
