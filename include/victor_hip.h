@@ -15,6 +15,8 @@
  *   vk_xi_smu_batch      CCFModel.theory_xi           victor/ccf_model.py:538-789
  *   vk_eval_realisations CCFFit.log_likelihood against every simulation realisation of the
  *                        data file (simulation_number, victor/ccf_fit.py:59-61,93-100)
+ *   vk_set_model_realisations  ... each with the model of its own real-space CCF
+ *                        (realspace_ccf.simulation_number, victor/ccf_model.py:127-162)
  *   vk_joint_cov_eval_realisations  the same for a joint fit under one covariance: realisation m
  *                        of every block's own file (victor/ccf_fit.py:59-61,93-100,325-483)
  *   vk_fit_create_joint, vk_chain_create_joint   a host optimiser / cobaya (victor/likelihoods/
@@ -391,6 +393,27 @@ void vk_epsilon_to_ap(const double* eps, int64_t n, double alpha, double* aperp,
 int vk_set_realisations(vk_ctx* ctx, const double* data, int32_t n_real);
 int vk_eval_realisations(vk_ctx* ctx, const vk_eval_opts* opts, const double* params, int64_t n, const int32_t* which,
                          double* lnl, double* chi2);
+
+/* ---- every realisation with its own real-space CCF: xi^r table sets selected per row ------------------------------------
+ * The reference picks the real-space multipoles xi^r_l(r) - with reconstruction xi^r_l(beta, r) - of ONE simulation out of a
+ * stacked model file, the one `realspace_ccf.simulation_number` names (victor/ccf_model.py:127-162), as it picks the data vector;
+ * a mock test fits mock m's redshift-space multipoles with the model built from mock m's own real-space CCF.
+ * vk_set_model_realisations: n_sets table sets back to back, each with exactly the layout and length of vk_tables.xi.coef,
+ *   vk_tables.uni_xi and vk_tables.uni_xic of the context (set m of xi_coef at xi_coef + m * length, and so on).  A pointer whose
+ *   array the context was created without (a context without unified tables reads neither uni_xi nor uni_xic) may be NULL; the
+ *   others must be given.  Copied to the device, resident until replaced or vk_destroy; n_sets = 0 releases them, after which
+ *   the context does exactly what it did before.  VK_E_ARG: n_sets < 0; a needed pointer is NULL; velocity tables that depend on
+ *   the real-space CCF (vk_tables.vr_beta_dep, or matter_model linear_bias, whose profile is derived from xi^r_0) - those would
+ *   need sets of their own.
+ * While sets are resident: the pairs mode of vk_eval_realisations (which != NULL) and every fit, chain, stretch, tempered,
+ *   Hessian, Fisher and predictive launch of a handle created with `which` evaluate row i from table set which[i] - everything
+ *   else of the arithmetic is unchanged, so a row's bits are those of a context created from set which[i]'s tables at the same
+ *   batch size.  These launches need n_sets == n_real (VK_E_ARG otherwise).  Cross mode (which == NULL) of vk_eval_realisations
+ *   is refused with VK_E_ARG - a point no longer has one theory vector; expand it into pairs.  Every entry point without
+ *   realisation indices (vk_eval_batch*, vk_theory_batch, vk_xi_smu_batch, the walkers, the mailbox server, handles created with
+ *   which == NULL) keeps using the context's own tables, bit for bit.  Joint evaluations (vk_joint_*, joint handles) over a
+ *   context with sets resident are refused with VK_E_ARG. */
+int vk_set_model_realisations(vk_ctx* ctx, const double* xi_coef, const double* uni_xi, const double* uni_xic, int32_t n_sets);
 
 /* ---- best-fit points: bounded Nelder-Mead on the device, one simplex per problem ----------------------------------------
  * The reference has no optimiser: a user maximises CCFFit.log_likelihood (victor/ccf_fit.py:356-483) with a host optimiser,

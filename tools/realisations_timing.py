@@ -1,9 +1,10 @@
 """BOSS at batch 4096 against M simulation realisations (vk_eval_realisations): wall time, the theory / chi-square split of the
 library's event timing (vk_timing_*), the matrix-core kernel against its vector-ALU twin (VICTOR_HIP_REAL_VALU, same tiling,
 alternated), and the same work as M separate CCFFit objects at M = 64.  Writes realisations_<M>.txt and
-realisations_separate_fits.txt into the output directory.
+realisations_separate_fits.txt into the output directory.  With --paired instead: 65536 rows in pairs mode over 1024 mocks,
+realisations(paired_model=True) against the shared model, BOSS and the fixed-table config 3 (paired_main).
 
-    python tools/realisations_timing.py OUT_DIR [--commit SHA]
+    python tools/realisations_timing.py OUT_DIR [--commit SHA] [--paired]
 """
 import os
 import sys
@@ -108,5 +109,97 @@ def main():
         fh.write(text)
 
 
+# ---- --paired: what it costs to give every mock the model of its own real-space CCF (realisations(paired_model=True)) ---------
+PAIRED_MOCKS, PAIRED_ROWS = 1024, 65536
+
+
+def paired_fixtures(tmp):
+    """name -> (model, data) of a fit over PAIRED_MOCKS mocks: the BOSS stack tiled by the rule of write_stack (beta-dependent
+    tables) and the synthetic config 3 (fixed tables), each against a model file whose real-space multipoles have one
+    realisation per mock (base x (1 + 0.03 sin(0.7 m + r / 20)), realisation 0 the base)."""
+    m = np.arange(PAIRED_MOCKS)
+
+    def factor(r):
+        f = 1.0 + 0.03 * np.sin(0.7 * m[:, None] + np.asarray(r)[None, :] / 20.0)
+        f[0] = 1.0
+        return f
+    out = {}
+    base = np.load(os.path.join(cases.GOLDEN, "boss", "model.npy"), allow_pickle=True).item()
+    f = factor(base["r"])[:, None, :]
+    mpath = os.path.join(tmp, "boss_model_stack.npy")
+    np.save(mpath, dict(base, monopole=base["monopole"][None] * f, quadrupole=base["quadrupole"][None] * f), allow_pickle=True)
+    dpath = os.path.join(tmp, "boss_data_stack.npy")
+    write_stack(dpath, PAIRED_MOCKS)
+    model, data = options(dpath)
+    model["input_model_data_file"] = mpath
+    model["realspace_ccf"]["simulation_number"] = 0
+    out["BOSS (n_beta_r = 31)"] = (model, data)
+    base = np.load(os.path.join(cases.GOLDEN, "synth", "model.npy"), allow_pickle=True).item()
+    f = factor(base["r"])
+    keys = ("monopole", "quadrupole", "hexadecapole")
+    mpath = os.path.join(tmp, "synth_model_stack.npy")
+    np.save(mpath, dict(base, **{k: base[k][None] * f for k in keys}), allow_pickle=True)
+    d = np.load(os.path.join(cases.GOLDEN, "synth", "data3.npy"), allow_pickle=True).item()
+    scale = (1.0 + (m // 16) / 100.0)[:, None]
+    dpath = os.path.join(tmp, "synth_data_stack.npy")
+    np.save(dpath, dict(d, **{k: d[k][None] * scale for k in keys}), allow_pickle=True)
+    model, data = cases.synth_options(3)
+    model["input_model_data_file"] = mpath
+    model["realspace_ccf"]["simulation_number"] = 0
+    data["redshift_space_ccf"].update(data_file=dpath, simulation_number=0)
+    out["config 3 (fixed tables)"] = (model, data)
+    return out
+
+
+def paired_main():
+    """PAIRED_ROWS rows in pairs mode over PAIRED_MOCKS mocks, paired_model=True against False: wall time per call, median of
+    five and their spread, the two legs alternating in one process after a warm-up of each.  Each leg has a fit - an engine - of
+    its own, so the warm-ups carry the uploads and a timed call is the evaluation alone.  Writes paired_realisations.txt."""
+    import victor_amd
+    from victor_amd import engine
+    out = sys.argv[1]
+    commit = sys.argv[sys.argv.index("--commit") + 1] if "--commit" in sys.argv else "unknown"
+    os.makedirs(out, exist_ok=True)
+    tmp = tempfile.mkdtemp()
+    which = ((7 * np.arange(PAIRED_ROWS)) % PAIRED_MOCKS).astype(np.int32)
+    lines = [f"commit {commit}", f"{PAIRED_ROWS} rows in pairs mode over {PAIRED_MOCKS} mocks; wall ms per call, median of 5 [min .. max]"]
+    for name, (model, data) in paired_fixtures(tmp).items():
+        fits = [victor_amd.CCFFit(model, data), victor_amd.CCFFit(model, data)]      # an engine per leg: no re-upload between calls
+        hp = cases.halton_params(PAIRED_ROWS, with_beta=not fits[0].fixed_data)
+        t0 = time.perf_counter()
+        legs = {"shared": fits[0].realisations(), "paired": fits[1].realisations(paired_model=True)}
+        sets = legs["paired"].model_sets()
+        t_sets = time.perf_counter() - t0
+        t, keep = engine.build_tables(fits[0], fits[0])
+        n = engine.table_array_lengths(t)
+        per_set = 8 * (n["xi.coef"] + n["uni_xi"] + n["uni_xic"])
+        del keep
+        walls = {k: [] for k in legs}
+        values = {}
+        for k, rs in legs.items():                                  # warm-up: code objects, uploads, scratch
+            t0 = time.perf_counter()
+            values[k] = rs.log_likelihood_pairs(hp, which)
+            lines.append(f"{name}: first call {k} {1e3 * (time.perf_counter() - t0):.1f} ms")
+        for _ in range(5):
+            for k, rs in legs.items():
+                t0 = time.perf_counter()
+                rs.log_likelihood_pairs(hp, which)
+                walls[k].append(1e3 * (time.perf_counter() - t0))
+        # (mock 0's tables are the fit's own: the same bits there)
+        same = np.array_equal(values["paired"][1][which == 0], values["shared"][1][which == 0])
+        lines.append(f"{name}: table set {per_set} bytes, {PAIRED_MOCKS} sets {per_set * PAIRED_MOCKS / 1e6:.1f} MB "
+                     f"(stacked on the host in {t_sets:.1f} s: {sum(s.nbytes for s in sets if s is not None) / 1e6:.1f} MB); "
+                     f"rows of mock 0 equal in both legs: {same}; rows that differ: {int(np.sum(values['paired'][1] != values['shared'][1]))} of {PAIRED_ROWS}")
+        for k, w in walls.items():
+            lines.append(f"{name}: {k:6s} {np.median(w):9.2f} [{min(w):.2f} .. {max(w):.2f}]")
+        lines.append(f"{name}: paired / shared {np.median(walls['paired']) / np.median(walls['shared']):.4f}")
+        for f in fits:
+            f._engine = None
+    text = "\n".join(lines) + "\n"
+    print(text, flush=True)
+    with open(os.path.join(out, "paired_realisations.txt"), "w") as fh:
+        fh.write(text)
+
+
 if __name__ == "__main__":
-    main()
+    paired_main() if "--paired" in sys.argv else main()

@@ -380,11 +380,13 @@ class CCFFit(CCFModel):
                              kwargs, move=move, stretch_a=stretch_a, prior=prior, marginals=marginals,
                              autocorr=autocorr, temper=temper, predictive=predictive)
 
-    def realisations(self, simulation_numbers=None):
+    def realisations(self, simulation_numbers=None, paired_model=False):
         """Every simulation realisation of this fit's data file (or the listed ``simulation_numbers``) against one model:
-        :class:`victor_amd.realisations.Realisations`.  The fit must have been built with an integer ``simulation_number``."""
+        :class:`victor_amd.realisations.Realisations`.  The fit must have been built with an integer ``simulation_number``.
+        ``paired_model=True``: realisation m against the model built from realisation m of the real-space CCF stack of the
+        model file (``realspace_ccf.simulation_number``, an integer as well)."""
         from .realisations import Realisations
-        return Realisations(self, simulation_numbers)
+        return Realisations(self, simulation_numbers, paired_model)
 
     def theory_vector_batch(self, params, **kwargs):
         """Theory vectors (n, N) on the data's own s grid and multipoles."""

@@ -49,6 +49,7 @@ class CCFModel:
         input_data = utils.read_input_file(input_fn, self.extensions)
 
         self._load_realspace_ccf(model["realspace_ccf"], input_data)
+        self._real_source = (input_fn, dict(model["realspace_ccf"]))   # what realisations(paired_model=True) reads the stack from
         self.matter_model = model["matter_ccf"].get("model", "linear_bias")
         self.realspace_ccf_from_data = model["realspace_ccf"].get("from_data", False)
         self.template_sigma8 = model["matter_ccf"].get("template_sigma8", None)

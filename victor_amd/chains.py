@@ -696,6 +696,9 @@ def sample_chains(fit, params, n_steps, walkers=8, seed=0, fixed=None, start=Non
             lnl = np.asarray(out, dtype=float)
             return lnl, -2.0 * lnl
     elif not device:
+        if predictive and getattr(realisations, "paired_model", False):
+            raise InputError("sample_chains: predictive= on the definition route (device=False) takes its theory vectors from the "
+                             "fit's own tables; with realisations(paired_model=True) use the device route")
         if realisations is not None:
             def evaluator(x, rows_which=None):
                 return realisations.log_likelihood_pairs(batch_of(x), which if rows_which is None else rows_which, **kwargs)

@@ -401,6 +401,21 @@ int launch_xi_generic(vk_ctx* ctx, TheoryArgs a, int nlr) {
   return launch_xi_smu(ctx, a, nlr, grid, lds);
 }
 
+// What the fast kernels read is 1 + xi^r as a polynomial in (2 mu_r)^2 (vk_kernel_fast.h: uni_point): the "+1" of
+// ccf_model.py:690 goes into the constant coefficient of the l = 0 set (for beta polynomials: the beta-constant one), and
+// the sets of mu_r^2 and mu_r^4 are divided by 4 and 16 - exact rescalings, done on the host copies of vk_tables.uni_xi (uxi)
+// and vk_tables.uni_xic (uxc) so that vk_tables keeps its meaning
+void uni_xi_kernel_form(double* uxi, double* uxc, int n_ell_r, int n_beta_r, int uni_n) {
+  const size_t per_l = n_beta_r > 0 ? (size_t)(n_beta_r - 1) * uni_n * 16 : (size_t)uni_n * 4;
+  const size_t step = n_beta_r > 0 ? 16 : 4;          // doubles per (interval): [4 powers of tau] x [4 powers of d beta] or [4]
+  for (double* x0 : {uxi, uxc})
+    for (size_t e = 0; e < per_l; e += step) x0[e] += 1.0;
+  for (int l = 1; l < n_ell_r; ++l) {
+    const double f = l == 1 ? 0.25 : 0.0625;
+    for (size_t e = 0; e < per_l; ++e) uxc[(size_t)l * per_l + e] *= f;
+  }
+}
+
 // fills the grid-independent part of TheoryArgs
 int theory_args(vk_ctx* ctx, const vk_eval_opts* o, TheoryArgs* a, int* nlr) {
   a->n_beta_r = ctx->n_beta_r;
@@ -601,7 +616,7 @@ int launch_theory(vk_ctx* ctx, TheoryArgs a, int nlr, const LikeArgs* like, bool
   // config 3 2.58 / 2.66 / 2.66 against 2.23 / 2.58 / 2.65) and kept as the yardstick of tools/ and of the mapping tests:
   // VICTOR_HIP_MAPPING=lanes selects it.  The product library does not contain it (round 5).
   {
-    const bool lanes_ok = fast && a.n_beta_r == 0 && !a.empirical && !a.from_data && !disp && !kais && !sva;   // per-point tables need a workgroup per point
+    const bool lanes_ok = fast && a.n_beta_r == 0 && !a.empirical && !a.from_data && !disp && !kais && !sva && !a.set_which;   // per-point tables need a workgroup per point
     const long long waves = ((a.n + 63) >> 6) * (long long)a.n_s;
     const long long blocks_l = (waves + kWaves - 1) / kWaves;
     const size_t lds_l = (size_t)make_lanes_plan(a.n_mu, a.n_x, a.uni_n, nlr, a.uni_lut_n).total * sizeof(double);
@@ -1057,6 +1072,7 @@ vk_ctx* vk_create(const vk_tables* t, int device, char* err, size_t errlen) {
   const size_t xi_coef_n = t->n_beta_r > 0 ? (size_t)t->n_ell_r * (t->n_beta_r - 1) * t->xi.n_int * 16
                                            : (size_t)t->n_ell_r * t->xi.n_int * 4;
   const size_t o_xik = up.add(t->xi.knots, t->xi.n_int + 1), o_xic = up.add(t->xi.coef, xi_coef_n);
+  ctx->xi_coef_doubles = xi_coef_n;
   const size_t vr_coef_n = t->vr_beta_dep ? (size_t)2 * (t->n_beta_r - 1) * t->vr.n_int * 16 : (size_t)kVrVars * t->vr.n_int * 4;
   const size_t o_vrk = up.add(t->vr.knots, t->vr.n_int + 1), o_vrc = up.add(t->vr.coef, vr_coef_n);
   const bool have_vr_emp = t->vr_beta_dep && t->vr_emp;
@@ -1099,19 +1115,9 @@ vk_ctx* vk_create(const vk_tables* t, int device, char* err, size_t errlen) {
     // What the fast kernels read is 1 + xi^r as a polynomial in (2 mu_r)^2 (vk_kernel_fast.h: uni_point): the "+1" of
     // ccf_model.py:690 goes into the constant coefficient of the l = 0 set (for beta polynomials: the beta-constant one), and
     // the sets of mu_r^2 and mu_r^4 are divided by 4 and 16 - exact rescalings, done here so that vk_tables keeps its meaning
-    {
-      const size_t per_l = t->n_beta_r > 0 ? (size_t)(t->n_beta_r - 1) * t->uni_n * 16 : (size_t)t->uni_n * 4;
-      const size_t step = t->n_beta_r > 0 ? 16 : 4;          // doubles per (interval): [4 powers of tau] x [4 powers of d beta] or [4]
-      for (size_t o : {o_uxi, o_uxc}) {
-        double* x0 = up.host.data() + o;
-        for (size_t e = 0; e < per_l; e += step) x0[e] += 1.0;
-      }
-      double* xc = up.host.data() + o_uxc;
-      for (int l = 1; l < t->n_ell_r; ++l) {
-        const double f = l == 1 ? 0.25 : 0.0625;
-        for (size_t e = 0; e < per_l; ++e) xc[(size_t)l * per_l + e] *= f;
-      }
-    }
+    // (uni_xi_kernel_form, shared with the table sets of vk_set_model_realisations)
+    uni_xi_kernel_form(up.host.data() + o_uxi, up.host.data() + o_uxc, t->n_ell_r, t->n_beta_r, t->uni_n);
+    ctx->uni_xi_doubles = t->n_beta_r > 0 ? (size_t)t->n_ell_r * (t->n_beta_r - 1) * t->uni_n * 16 : (size_t)t->n_ell_r * t->uni_n * 4;
     if (t->vr_beta_dep && t->uni_vb) o_uvb = up.add(t->uni_vb, (size_t)(t->n_beta_r - 1) * t->uni_n * 16);
     if (!t->vr_beta_dep && t->uni_v2) o_uv2 = up.add(t->uni_v2, (size_t)t->uni_n * 4);
     if (!t->vr_beta_dep && t->uni_da) o_uda = up.add(t->uni_da, (size_t)t->uni_n * 4);
@@ -1286,6 +1292,7 @@ void vk_destroy(vk_ctx* ctx) {
   for (auto& kv : ctx->images) (void)hipFree(kv.second);
   if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
   if (ctx->d_real) (void)hipFree(ctx->d_real);
+  if (ctx->d_sets) (void)hipFree(ctx->d_sets);
   for (auto& evt : ctx->ev)
     if (evt) (void)hipEventDestroy(evt);
   if (ctx->ev_joint) (void)hipEventDestroy(ctx->ev_joint);
@@ -1397,6 +1404,14 @@ int vk_eval_batch_device_async(vk_ctx* ctx, const vk_eval_opts* opts, const doub
     a.params = d_params + off * VK_NPAR;
     a.n = m;
     a.out = d_theory_ws + off * ctx->N;
+    if (ctx->row_set) {                       // enqueue_realisations, pairs mode, table sets resident: row i from set row_set[i]
+      a.set_which = ctx->row_set + off;
+      a.set_xi_coef = ctx->d_set_xi_coef;
+      a.set_uni_xi = ctx->d_set_uni_xi;
+      a.set_uni_xic = ctx->d_set_uni_xic;
+      a.set_coef_stride = ctx->set_coef_stride;
+      a.set_uni_stride = ctx->set_uni_stride;
+    }
     LikeArgs la;
     if (want_like)
       fill_like_args(ctx, opts, a.params, a.out, m, d_lnl ? d_lnl + off : nullptr, d_chi2 ? d_chi2 + off : nullptr, &la);
@@ -1445,6 +1460,9 @@ static int check_blocks(vk_ctx* lead, const vk_joint_cov* h, vk_ctx* const* ctxs
     if (!c->d_data) return fail(lead, VK_E_ARG, "joint fit: context %d was created without a data vector", q);
     if (h && c->N != h->block_n[q])
       return fail(lead, VK_E_ARG, "joint covariance: block %d has %d entries, its context %d", q, h->block_n[q], c->N);
+    if (c->n_sets > 0)
+      return fail(lead, VK_E_ARG, "joint fit: context %d holds model realisations (vk_set_model_realisations), which joint "
+                                  "evaluations do not support", q);
     if (!need_real) continue;
     if (c->begun_n != 0)
       return fail(lead, VK_E_ARG, "a batch begun with vk_eval_batch_begin is awaiting vk_eval_batch_finish on context %d", q);
@@ -1636,15 +1654,28 @@ int vkh::check_real_lds(vk_ctx* ctx) {
 // Enqueue on ctx's stream: the theory vectors of m device rows d_par into the workspace d_th, then the realisation chi-square
 // kernel behind them - every point against every realisation (d_which NULL: outputs [m][n_real]) or point i against realisation
 // d_which[i] (pairs mode, indices in device memory: outputs [m]).  The caller has checked the LDS limit (check_real_lds) and the
-// indices.  Shared by vk_eval_realisations and the best fits and chains of vk_sampled.hip.
+// indices.  Shared by vk_eval_realisations and the best fits and chains of vk_sampled.hip.  With xi^r table sets resident
+// (vk_set_model_realisations) the theory launch evaluates row i from set d_which[i]: pairs mode only, n_sets == n_real.
 int vkh::enqueue_realisations(vk_ctx* ctx, const vk_eval_opts* opts, const double* d_par, long long m, double* d_th, double* d_lnl,
                               double* d_chi, const int32_t* d_which) {
+  // xi^r table sets resident (vk_set_model_realisations): row i is evaluated from set d_which[i], so there is no cross mode and
+  // the sets are the realisations'
+  if (ctx->n_sets > 0) {
+    if (!d_which)
+      return fail(ctx, VK_E_ARG, "model realisations are set on this context (vk_set_model_realisations): a point has one theory "
+                                 "vector per realisation, evaluate pairs (which) instead of every point against every realisation");
+    if (ctx->n_sets != ctx->n_real)
+      return fail(ctx, VK_E_ARG, "%d model realisations (vk_set_model_realisations) against %d realisations of the data "
+                                 "(vk_set_realisations): the counts must agree", ctx->n_sets, ctx->n_real);
+  }
   const bool timed = ctx->timing;
   if (timed) {
     harvest_timing(ctx);
     VK_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
   }
+  ctx->row_set = ctx->n_sets > 0 ? d_which : nullptr;
   int rc = vk_eval_batch_device_async(ctx, opts, d_par, m, nullptr, nullptr, d_th);     // theory vectors only, into the workspace
+  ctx->row_set = nullptr;
   if (rc) return rc;
   if (timed) VK_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
   RealArgs ra{};
@@ -2317,12 +2348,72 @@ int vk_set_realisations(vk_ctx* ctx, const double* data, int32_t n_real) {
   return VK_OK;
 }
 
+// ---- xi^r table sets, one per realisation (include/victor_hip.h; the kernels: rebuild_point_tables, build_beta_tables) --------
+int vk_set_model_realisations(vk_ctx* ctx, const double* xi_coef, const double* uni_xi, const double* uni_xic, int32_t n_sets) {
+  if (!ctx) return VK_E_ARG;
+  if (n_sets < 0) return fail(ctx, VK_E_ARG, "vk_set_model_realisations: n_sets = %d is negative", n_sets);
+  const bool uni = ctx->d_uni_xi != nullptr;             // unified tables on the device: the kernels that own a point per workgroup read them
+  if (n_sets > 0) {
+    if (ctx->vr_beta_dep || ctx->matter_lb)
+      return fail(ctx, VK_E_ARG, "vk_set_model_realisations: the velocity tables of this context depend on the real-space CCF (%s) "
+                                 "and would need sets of their own", ctx->vr_beta_dep ? "vr_beta_dep" : "matter_model linear_bias");
+    if (!xi_coef) return fail(ctx, VK_E_ARG, "vk_set_model_realisations: xi_coef is NULL");
+    if (uni && (!uni_xi || !uni_xic))
+      return fail(ctx, VK_E_ARG, "vk_set_model_realisations: %s is NULL on a context with unified tables", uni_xi ? "uni_xic" : "uni_xi");
+  }
+  VK_HIP(ctx, hipSetDevice(ctx->device));
+  VK_HIP(ctx, hipStreamSynchronize(ctx->stream));        // (nothing in flight may still read the old sets)
+  if (ctx->d_sets) (void)hipFree(ctx->d_sets);
+  ctx->d_sets = nullptr;
+  ctx->d_set_xi_coef = ctx->d_set_uni_xi = ctx->d_set_uni_xic = nullptr;
+  ctx->n_sets = 0;
+  ctx->set_coef_stride = ctx->set_uni_stride = 0;
+  if (n_sets == 0) return VK_OK;
+  const size_t nc = ctx->xi_coef_doubles, nu = uni ? ctx->uni_xi_doubles : 0;
+  std::vector<double> host;
+  try {
+    host.resize((size_t)n_sets * (nc + 2 * nu));
+  } catch (const std::bad_alloc&) {
+    return fail(ctx, VK_E_NOMEM, "vk_set_model_realisations: no host memory for %d sets", n_sets);
+  }
+  double* h_coef = host.data();
+  double* h_uxi = h_coef + (size_t)n_sets * nc;
+  double* h_uxc = h_uxi + (size_t)n_sets * nu;
+  memcpy(h_coef, xi_coef, (size_t)n_sets * nc * sizeof(double));
+  if (nu) {
+    memcpy(h_uxi, uni_xi, (size_t)n_sets * nu * sizeof(double));
+    memcpy(h_uxc, uni_xic, (size_t)n_sets * nu * sizeof(double));
+    for (int m = 0; m < n_sets; ++m)                      // the form the kernels read, as vk_create makes it of the context's own tables
+      uni_xi_kernel_form(h_uxi + (size_t)m * nu, h_uxc + (size_t)m * nu, ctx->n_ell_r, ctx->n_beta_r, ctx->uni_n);
+  }
+  VK_HIP(ctx, hipMalloc((void**)&ctx->d_sets, host.size() * sizeof(double)));
+  const hipError_t e = hipMemcpy(ctx->d_sets, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)hipFree(ctx->d_sets);
+    ctx->d_sets = nullptr;
+    return fail(ctx, VK_E_HIP, "vk_set_model_realisations: upload failed: %s", hipGetErrorString(e));
+  }
+  ctx->d_set_xi_coef = ctx->d_sets;
+  ctx->d_set_uni_xi = nu ? ctx->d_sets + (size_t)n_sets * nc : nullptr;
+  ctx->d_set_uni_xic = nu ? ctx->d_sets + (size_t)n_sets * (nc + nu) : nullptr;
+  ctx->set_coef_stride = (long long)nc;
+  ctx->set_uni_stride = (long long)nu;
+  ctx->n_sets = n_sets;
+  return VK_OK;
+}
+
 int vk_eval_realisations(vk_ctx* ctx, const vk_eval_opts* opts, const double* params, int64_t n, const int32_t* which,
                          double* lnl, double* chi2) {
   if (!ctx) return VK_E_ARG;
   sync_knobs(ctx);
   int rc = check_opts(ctx, opts);
   if (rc) return rc;
+  if (ctx->n_sets > 0 && !which)
+    return fail(ctx, VK_E_ARG, "model realisations are set on this context (vk_set_model_realisations): a point has one theory "
+                               "vector per realisation, evaluate pairs (which) instead of every point against every realisation");
+  if (ctx->n_sets > 0 && ctx->n_sets != ctx->n_real)
+    return fail(ctx, VK_E_ARG, "%d model realisations (vk_set_model_realisations) against %d realisations of the data "
+                               "(vk_set_realisations): the counts must agree", ctx->n_sets, ctx->n_real);
   if (n < 0 || (n > 0 && !params)) return fail(ctx, VK_E_ARG, "params is NULL");
   if (ctx->begun_n != 0) return fail(ctx, VK_E_ARG, "a batch begun with vk_eval_batch_begin is awaiting vk_eval_batch_finish on this context");
   if (ctx->n_real <= 0 || !ctx->d_real) return fail(ctx, VK_E_ARG, "no realisations are set on this context (vk_set_realisations)");

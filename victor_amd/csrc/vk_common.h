@@ -148,6 +148,15 @@ struct TheoryArgs {
   // 0 with `fuse`: nobody reads `out` - the chi-square is taken from LDS in the same workgroup - and the kernels that hold a
   // point's whole vector in LDS (cells) do not write it to HBM at all (BOSS, 65536 points: 31.5 MB per launch that nobody read).
   int want_theory;
+  // ---- xi^r table sets selected per row (vk_set_model_realisations; ccf_model.py:127-162 once per simulation_number) ----------
+  // set_which NULL: off, the tables above.  Else point i reads its xi^r coefficients from set set_which[i]: xi.coef at
+  // set_xi_coef + set * set_coef_stride (generic kernel), uni_xi / uni_xic at set_uni_xi / set_uni_xic + set * set_uni_stride (the
+  // kernels that own a point per workgroup).  The index is the point's, so every workgroup that shares a point selects the same set.
+  const int* set_which;   // [n], device
+  const double* set_xi_coef;
+  const double* set_uni_xi;
+  const double* set_uni_xic;
+  long long set_coef_stride, set_uni_stride;   // doubles
 #ifdef VK_PHASES
   long long* stamps;      // profiling build only (make phases): [workgroup][16] wall_clock64() marks of the point-major kernel
 #endif

@@ -118,6 +118,13 @@ struct vk_ctx {
   double* d_real = nullptr;
   int n_real = 0;
   long long real_block = 0;
+  // xi^r table sets, one per realisation (vk_set_model_realisations): one allocation, n_sets copies each of xi.coef | uni_xi | uni_xic
+  double* d_sets = nullptr;
+  const double *d_set_xi_coef = nullptr, *d_set_uni_xi = nullptr, *d_set_uni_xic = nullptr;
+  int n_sets = 0;
+  long long set_coef_stride = 0, set_uni_stride = 0;   // doubles between two sets of xi.coef; of uni_xi and of uni_xic
+  size_t xi_coef_doubles = 0, uni_xi_doubles = 0;       // lengths of vk_tables.xi.coef and of uni_xi / uni_xic as vk_create uploaded them (0: not there)
+  const int32_t* row_set = nullptr;    // set around the theory launch of enqueue_realisations in pairs mode: the rows' set indices (device)
   // timing
   bool timing = false;
   hipEvent_t ev[3] = {nullptr, nullptr, nullptr};

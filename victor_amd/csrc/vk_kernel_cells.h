@@ -287,7 +287,7 @@ __global__ __launch_bounds__(kBlock, (MODE == kModeStreaming && !SVA) || MODE ==
     // the V cubics carry the point's factor: AVk (streaming), -Gk (dispersion, see disp_value), none (kaiser / euclid_special)
     constexpr int PV = MODE == kModeKaiser ? 0 : 1;
     __syncthreads();      // every wave is done with the previous item's records and accumulators
-    rebuild_point_tables<NLR, PV>(a, lds, pl.betar, pl.v1, row[VK_P_BETA], ps.av, mode_is_dispersion(MODE) ? -fp.Gk : fp.AVk,
+    rebuild_point_tables<NLR, PV>(a, lds, pl.betar, pl.v1, point, row[VK_P_BETA], ps.av, mode_is_dispersion(MODE) ? -fp.Gk : fp.AVk,
                                   mode_has_da(MODE) ? lds + pl.da : nullptr);
     if (mode_has_da(MODE) && a.empirical && !a.vr_beta_dep) rebuild_da_emp(a, lds + pl.da, ps.av);
     for (int e = lane; e < kMaxEll * slots; e += 64) l_acc[e * kWaves + wave] = 0.0;

@@ -195,9 +195,10 @@ __device__ __forceinline__ double poly6(const double* __restrict__ c, double db)
 }
 
 // `da`: LDS table of the dispersion model's v_r' (NULL in the streaming modes); `av`: the point's empirical_corr amplitude.
+// `xsrc`: the point's xi^r coefficients - the context's uni_xi / uni_xic, or those of the point's table set (rebuild_point_tables)
 template <int NLR>
-__device__ __forceinline__ void rebuild_uni_xi(const TheoryArgs& a, double* recs, const double* bg, double beta, double vs = 1.0,
-                                               double av = 0.0, double* da = nullptr) {
+__device__ __forceinline__ void rebuild_uni_xi(const TheoryArgs& a, double* recs, const double* xsrc, const double* bg, double beta,
+                                               double vs = 1.0, double av = 0.0, double* da = nullptr) {
   constexpr int stride = uni_stride(NLR);
   const int tid = late_tid();        // fresh per work item: nothing derived from it is carried through the integrand loops
   // PCHIP piece: last i in [1, n-2] with beta >= bg[i], else 0 - a count over the lanes for grids of up to 64 nodes
@@ -211,7 +212,7 @@ __device__ __forceinline__ void rebuild_uni_xi(const TheoryArgs& a, double* recs
   const double db = beta - bg[kb];
   const int per_l = a.uni_n * 4;
   const size_t stride_l = (size_t)(a.n_beta_r - 1) * per_l * 4;
-  const double* src = ((NLR > 1) ? a.uni_xic : a.uni_xi) + (size_t)kb * per_l * 4;
+  const double* src = xsrc + (size_t)kb * per_l * 4;
   const int total = NLR * per_l;
   // four entries per thread per pass, their eight 16-byte coefficient loads in flight together
   for (int base = tid; base < total; base += 4 * kBlock) {
@@ -256,6 +257,34 @@ __device__ __forceinline__ void rebuild_uni_xi(const TheoryArgs& a, double* recs
   }
 }
 
+// Fixed xi^r tables of a point's own table set (TheoryArgs::set_which, n_beta_r == 0): the xi^r part of the records, which the
+// staged image holds for the context's own tables, is overwritten from `src` ([NLR][uni_n][4], the layout stage_uni_records
+// reads).  Four 16-byte loads per thread per pass, all in flight before the first store; the pad slots and the sentinel records
+// of the union-grid form are not touched.
+template <int NLR>
+__device__ __forceinline__ void copy_uni_xi(const TheoryArgs& a, double* recs, const double* __restrict__ src) {
+  constexpr int stride = uni_stride(NLR);
+  const int tid = late_tid();
+  const int per_l = a.uni_n * 4;
+  const int total = NLR * a.uni_n * 2;                       // pairs of doubles
+  for (int base = tid; base < total; base += 4 * kBlock) {
+    vk_d2 c[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) c[k] = *reinterpret_cast<const vk_d2*>(src + 2 * (size_t)min(base + k * kBlock, total - 1));
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int e = 2 * (base + k * kBlock);
+      if (e < 2 * total) {
+        const int l = (NLR > 2 && e >= 2 * per_l) ? 2 : ((NLR > 1 && e >= per_l) ? 1 : 0);
+        const int iq = e - l * per_l;
+        double* dst = recs + (iq >> 2) * stride + 8 + 4 * l + (iq & 3);
+        dst[0] = c[k].x;
+        dst[1] = c[k].y;
+      }
+    }
+  }
+}
+
 // empirical_corr (ccf_model.py:451-455): v_r carries the factor (1 + Av delta), i.e. V = V1 + av V2 with the per-point
 // av; the kernels that own a point per workgroup rewrite the V half of the records for it
 template <int NLR>
@@ -275,12 +304,21 @@ __device__ __forceinline__ void scale_uni_v(int uni_n, double* recs, const doubl
 
 // Per-item tables of the kernels that own a point per workgroup.  PV: fold AVk into the V cubics (streaming modes).
 // `da`: the dispersion modes' LDS table of v_r' (NULL in the streaming modes) - rebuilt here when the velocity profile depends on beta.
+// `point`: the work item's point (wave-uniform) - with table sets resident (TheoryArgs::set_which) its xi^r records come from its
+// own set: the beta rebuild reads there, and fixed tables, which the staged image holds for the context's own set, are copied over.
 template <int NLR, int PV>
-__device__ __forceinline__ void rebuild_point_tables(const TheoryArgs& a, double* lds, int betar_off, int v1_off, double beta,
-                                                     double av, double AVk, double* da = nullptr) {
+__device__ __forceinline__ void rebuild_point_tables(const TheoryArgs& a, double* lds, int betar_off, int v1_off, long long point,
+                                                     double beta, double av, double AVk, double* da = nullptr) {
   const double vs = PV ? AVk : 1.0;
   double* recs = lds + recs_off<0>();                        // the kernels that own a point per workgroup use the plain exp table
-  if (a.n_beta_r > 0) rebuild_uni_xi<NLR>(a, recs, lds + betar_off, beta, vs, av, a.vr_beta_dep ? da : nullptr);
+  const double* xsrc = (NLR > 1) ? a.uni_xic : a.uni_xi;     // anisotropic sum: the mu_r^2-power regrouping
+  if (a.set_which) {
+    // one index per point, the same in every workgroup that shares the point: a scalar load, the offset kept in scalar registers
+    const int set = __builtin_amdgcn_readfirstlane(a.set_which[point]);
+    xsrc = ((NLR > 1) ? a.set_uni_xic : a.set_uni_xi) + (size_t)set * (size_t)a.set_uni_stride;
+    if (a.n_beta_r == 0) copy_uni_xi<NLR>(a, recs, xsrc);
+  }
+  if (a.n_beta_r > 0) rebuild_uni_xi<NLR>(a, recs, xsrc, lds + betar_off, beta, vs, av, a.vr_beta_dep ? da : nullptr);
   if (a.empirical && !a.vr_beta_dep) rebuild_uni_v_emp<NLR>(a, recs, av, vs);
   else if (PV && !a.vr_beta_dep) scale_uni_v<NLR>(a.uni_n, recs, lds + v1_off, vs);
 }
@@ -810,7 +848,7 @@ __global__ __launch_bounds__(kBlock, MODE == kModeStreaming && !SVA ? 3 : 2) voi
     constexpr int PV = 1;      // the V cubics carry the point's factor: AVk (streaming) or -Gk (dispersion, see disp_value)
     if (PV || a.n_beta_r > 0 || a.empirical) {
       __syncthreads();  // previous item's readers are done with the per-point records
-      rebuild_point_tables<NLR, PV>(a, lds, pl.betar, pl.v1, row[VK_P_BETA], ps.av, mode_is_dispersion(MODE) ? -fp.Gk : fp.AVk,
+      rebuild_point_tables<NLR, PV>(a, lds, pl.betar, pl.v1, point, row[VK_P_BETA], ps.av, mode_is_dispersion(MODE) ? -fp.Gk : fp.AVk,
                                     mode_is_dispersion(MODE) ? lds + pl.da : nullptr);
       if (mode_is_dispersion(MODE) && a.empirical && !a.vr_beta_dep) rebuild_da_emp(a, lds + pl.da, ps.av);
       __syncthreads();

@@ -60,6 +60,8 @@ struct FisherArgs {
   long long g0, n;          // the chunk: global rows g0 .. g0 + n - 1 land in pending rows 0 .. n - 1
   const double* base;       // [R][VK_NPAR] per row set
   double* rows;             // [rows_max][VK_NPAR] per row set
+  int* row_which;           // [rows_max], or NULL: the rows' realisations, for a context whose xi^r tables are selected per row
+  const int* which;         // [R], or NULL     (vk_set_model_realisations) - the forecast itself reads no data
   int col[vkhess::kMaxP];
   double alpha;
   vkrow::Blocks blocks;
@@ -88,6 +90,7 @@ __global__ void __launch_bounds__(kFisherRowsBlock) vk_fisher_rows_kernel(Fisher
   const vkhess::Point pt = fisher_at_bound(a, p) ? vkhess::decode(a.d, 0) : vkhess::decode(a.d, m);
   const double *x = a.x + p * a.d, *h = a.h + p * a.d;
   sampled_row(a.blocks, a.base, p, a.rows, (size_t)i, a.col, a.d, a.alpha, [&](int j) { return vkhess::coord(pt, j, x[j], h[j]); });
+  if (a.row_which) a.row_which[i] = a.which[p];
 }
 
 __global__ void __launch_bounds__(kFisherBlock) vk_fisher_assemble_kernel(FisherArgs a) {

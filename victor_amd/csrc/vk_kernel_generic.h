@@ -217,8 +217,9 @@ __device__ void stage_tables(const TheoryArgs& a, const LdsPlan& pl, double* lds
 
 // per-point xi^r tables when the real-space input depends on the reconstruction beta:
 // coef[l][i][q] = sum_p T[l][k][i][q][p] (beta - beta_k)^p   (PCHIP piece k; extrapolates with end pieces)
+// `xi_coef`: the context's xi.coef, or that of the point's own table set (point_xi_tables)
 __device__ void build_beta_tables(const TheoryArgs& a, const LdsPlan& pl, double* lds, int n_ell_r_used,
-                                  double beta) {
+                                  double beta, const double* xi_coef) {
   const double* bg = lds + pl.betar;
   int k = 0;
   for (int i = 1; i < a.n_beta_r - 1; ++i) k = (beta >= bg[i]) ? i : k;
@@ -228,7 +229,7 @@ __device__ void build_beta_tables(const TheoryArgs& a, const LdsPlan& pl, double
   for (int e = threadIdx.x; e < n_ell_r_used * per_l; e += kBlock) {
     const int l = e / per_l;
     const int iq = e - l * per_l;
-    const double* c = a.xi.coef + l * stride_l + ((size_t)k * per_l + iq) * 4;
+    const double* c = xi_coef + l * stride_l + ((size_t)k * per_l + iq) * 4;
     lds[pl.xic + e] = fma(fma(fma(c[3], db, c[2]), db, c[1]), db, c[0]);
   }
   if (a.vr_beta_dep) {   // V1 and Da follow xi^r_0(beta) (linear_bias with reconstruction)
@@ -250,6 +251,33 @@ __device__ void build_beta_tables(const TheoryArgs& a, const LdsPlan& pl, double
 #pragma unroll
         for (int p = 5; p >= 0; --p) v = fma(v, db, c[p]);
         lds[pl.vrc + 2 * per_v + e] = v;
+      }
+    }
+  }
+}
+
+// The xi^r tables of a point's own table set (TheoryArgs::set_which != NULL; ccf_model.py:127-162 once per simulation_number):
+// the coefficients build_beta_tables reads when they depend on beta; fixed tables - the staged copy is the context's own set -
+// are copied over here, 16-byte loads, four in flight per thread.
+__device__ void point_xi_tables(const TheoryArgs& a, const LdsPlan& pl, double* lds, int n_ell_r_used, double beta, long long point) {
+  const int set = __builtin_amdgcn_readfirstlane(a.set_which[point]);       // wave-uniform: the offset stays in scalar registers
+  const double* xi_coef = a.set_xi_coef + (size_t)set * (size_t)a.set_coef_stride;
+  if (a.n_beta_r > 0) {
+    build_beta_tables(a, pl, lds, n_ell_r_used, beta, xi_coef);
+    return;
+  }
+  typedef double d2 __attribute__((ext_vector_type(2)));
+  const int total = n_ell_r_used * a.xi.n_int * 2;                          // pairs of doubles
+  for (int base = threadIdx.x; base < total; base += 4 * kBlock) {
+    d2 c[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) c[k] = *reinterpret_cast<const d2*>(xi_coef + 2 * (size_t)min(base + k * kBlock, total - 1));
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int e = base + k * kBlock;
+      if (e < total) {
+        lds[pl.xic + 2 * e] = c[k].x;
+        lds[pl.xic + 2 * e + 1] = c[k].y;
       }
     }
   }
@@ -298,9 +326,13 @@ __global__ __launch_bounds__(kBlock) void vk_theory_kernel(TheoryArgs a) {
     const int g = (int)(item - point * groups);
     const double* row = param_row(a, point);
     const PointScalars ps = point_scalars(a, row);
-    if (a.n_beta_r > 0) {
+    if (a.set_which) {
+      __syncthreads();
+      point_xi_tables(a, pl, lds, NLR, row[VK_P_BETA], point);
+      __syncthreads();
+    } else if (a.n_beta_r > 0) {
       __syncthreads();  // previous item's readers are done with the per-point table
-      build_beta_tables(a, pl, lds, NLR, row[VK_P_BETA]);
+      build_beta_tables(a, pl, lds, NLR, row[VK_P_BETA], a.xi.coef);
       __syncthreads();
     }
     for (int rd = 0; rd < rounds; ++rd) {
@@ -379,7 +411,7 @@ __global__ __launch_bounds__(kBlock) void vk_xi_smu_kernel(TheoryArgs a) {
     const PointScalars ps = point_scalars(a, row);
     if (a.n_beta_r > 0) {
       __syncthreads();
-      build_beta_tables(a, pl, lds, NLR, row[VK_P_BETA]);
+      build_beta_tables(a, pl, lds, NLR, row[VK_P_BETA], a.xi.coef);
       __syncthreads();
     }
     for (int rd = 0; rd < rounds; ++rd) {

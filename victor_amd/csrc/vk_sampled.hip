@@ -737,6 +737,16 @@ static int fisher_run(vk_fit* f, const FisherMem& m, double c, const double* x, 
   q.h = m.h;
   q.base = f->d_base;
   q.rows = f->d_rows;
+  // xi^r table sets resident on the context (vk_set_model_realisations) and a handle over realisations: problem p's stencil is
+  // evaluated from table set which[p] - the rows kernel writes the rows' indices, the theory launch selects by them
+  const bool paired = f->real && !nb && ctx->n_sets > 0;
+  if (paired && ctx->n_sets != ctx->n_real) {
+    f->err = "the context holds " + std::to_string(ctx->n_sets) + " model realisations (vk_set_model_realisations) and " +
+             std::to_string(ctx->n_real) + " realisations of the data: the counts must agree";
+    return VK_E_ARG;
+  }
+  q.row_which = paired ? f->d_row_which : nullptr;
+  q.which = paired ? f->d_which : nullptr;
   for (int j = 0; j < vkhess::kMaxP; ++j) q.col[j] = f->col[j];
   q.alpha = f->alpha;
   q.blocks = f->row_sets(R);
@@ -790,7 +800,9 @@ static int fisher_run(vk_fit* f, const FisherMem& m, double c, const double* x, 
     int rc = sampled_launch(f, vk_fisher_rows_kernel, n, kFisherRowsBlock, q);
     if (rc) return rc;
     if (!nb) {
+      ctx->row_set = paired ? f->d_row_which : nullptr;
       rc = vk_eval_batch_device_async(ctx, &f->opts, f->d_rows, n, nullptr, nullptr, m.vec + (size_t)g0 * N);
+      ctx->row_set = nullptr;
       if (rc) f->err = ctx->err;
       if (rc) return rc;
       continue;

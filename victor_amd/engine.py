@@ -441,6 +441,17 @@ class Engine:
         blocks = N.f64(blocks)
         self._check(self._lib.vk_set_realisations(self._ctx, N.as_dp(blocks), len(blocks)))
 
+    def set_model_realisations(self, xi_coef, uni_xi, uni_xic):
+        """Upload one xi^r table set per realisation: ``xi_coef[i]``, ``uni_xi[i]``, ``uni_xic[i]`` in the layout of
+        ``vk_tables.xi.coef`` / ``uni_xi`` / ``uni_xic`` (``uni_*``: ``None`` for tables without the unified grid); the pairs
+        mode of :meth:`eval_realisations` and the handles created with realisation indices then evaluate row i from set
+        ``which[i]``.  ``xi_coef=None`` releases the sets."""
+        if xi_coef is None:
+            self._check(self._lib.vk_set_model_realisations(self._ctx, None, None, None, 0))
+            return
+        arrs = [None if a is None else N.f64(a).reshape(len(xi_coef), -1) for a in (xi_coef, uni_xi, uni_xic)]
+        self._check(self._lib.vk_set_model_realisations(self._ctx, *[None if a is None else N.as_dp(a) for a in arrs], len(xi_coef)))
+
     def eval_realisations(self, opts, rows, n_real, which=None):
         """(lnl, chi2) of every row against every uploaded realisation, each ``(n, n_real)``; with ``which`` (one realisation
         index per row) only those pairs, each ``(n,)``."""

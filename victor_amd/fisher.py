@@ -368,7 +368,13 @@ def fisher(fit, params, at, step=None, fixed=None, prior=None, shrink=8, keep_ve
     def result(out_fisher, a, cov, status, c, model, vectors):
         return Fisher(names, x, h, fixed_out, out_fisher, a, cov, status, c, model, q.lo, q.hi, lam, vectors if keep_vectors else None)
 
+    # realisations(paired_model=True): the vectors depend on the problem's table set, which only the device route selects - the
+    # centres come back with the stencil instead of through the fit's public route
+    paired = getattr(realisations, "paired_model", False)
     if not device:
+        if paired and evaluate is None:
+            raise InputError("fisher: the definition route (device=False) takes its theory vectors from the fit's own tables; with "
+                             "realisations(paired_model=True) use the device route")
         pts = stencil_points(x, h, q.lo, q.hi).reshape(R * M, d)
         which = np.repeat(np.arange(R), M)
         if evaluate is not None:
@@ -394,7 +400,7 @@ def fisher(fit, params, at, step=None, fixed=None, prior=None, shrink=8, keep_ve
         out_fisher, a, cov = np.empty((R, d, d)), np.empty((R, d, d)), np.empty((R, d, d))
         status, c = np.empty(R, dtype=np.int32), C.c_double(0.0)
         vectors = None
-        if keep_vectors:
+        if keep_vectors or paired:
             n_entries = fit.n_data if hasattr(fit, "fits") else _n_data(fit)
             vectors = np.empty((R, M, n_entries))
         rc = lib.vk_fit_fisher(handle, N.as_dp(N.f64(x)), N.as_dp(N.f64(h)), None if vectors is None else N.as_dp(vectors),

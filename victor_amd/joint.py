@@ -542,9 +542,13 @@ class JointFit:
     def n_data(self):
         return sum(len(f.s) * len(f.poles_s) for f in self.fits)
 
-    def realisations(self, simulation_numbers=None):
+    def realisations(self, simulation_numbers=None, paired_model=False):
         """Every simulation realisation of the blocks' data files (or the listed ``simulation_numbers``) against this joint fit:
-        :class:`JointRealisations`.  Every block's fit must have been built with an integer ``simulation_number``."""
+        :class:`JointRealisations`.  Every block's fit must have been built with an integer ``simulation_number``.
+        ``paired_model=True`` (``CCFFit.realisations``: every mock with the model of its own real-space CCF) is refused."""
+        if paired_model:
+            raise InputError("JointFit.realisations: paired_model=True is not supported for joint fits (each block would need the "
+                             "table sets of its own real-space CCF stack); use CCFFit.realisations(paired_model=True) per block")
         return JointRealisations(self, simulation_numbers)
 
 

@@ -9,8 +9,17 @@ theory vector is computed once on the GPU and compared with every realisation's 
 
 Value contract: entry ``[p, m]`` equals ``CCFFit(model, data with simulation_number=numbers[m]).log_likelihood(point p)`` to
 rounding (the chi-square is summed in another order), ``(-inf, inf)`` exactly where that call returns it.
+
+``paired_model=True``: every realisation with the model of ITS OWN real-space CCF.  The reference picks one simulation out of a
+stacked model file as it does out of the data file (``realspace_ccf.simulation_number``, reference: ``ccf_model.py:127-162``);
+a mock test fits mock m's redshift-space multipoles with the model built from mock m's real-space multipoles.  The object then
+compiles the xi^r tables of every listed simulation (:func:`victor_amd.engine.build_tables`), checks that nothing else of the
+model's tables depends on the simulation, and keeps the sets on the device next to the data blocks
+(``vk_set_model_realisations``): every route evaluates row i from table set ``which[i]``, and the contract reads ``CCFFit(model
+with realspace_ccf.simulation_number=numbers[m], data with simulation_number=numbers[m])``.  The streaming model only.
 """
 
+import copy
 import weakref
 
 import numpy as np
@@ -19,6 +28,9 @@ from . import _native as N
 from . import utils
 from .engine import data_table
 from .utils import InputError
+
+
+PAIR_CHUNK = 65536        # pairs per device call of a paired object's cross mode (Realisations._eval_rows)
 
 
 def check_which(rows, which, n_real):
@@ -40,7 +52,10 @@ class Realisations:
     """Realisations ``numbers`` of ``fit``'s data file (``CCFFit.realisations``).  ``blocks[i]`` is realisation ``numbers[i]``
     in the layout of ``vk_tables.data``; it is uploaded once per engine the object evaluates on."""
 
-    def __init__(self, fit, simulation_numbers=None):
+    def __init__(self, fit, simulation_numbers=None, paired_model=False):
+        from .joint import JointFit
+        if paired_model and isinstance(fit, JointFit):
+            raise InputError("paired_model=True is not supported for joint fits")
         data_fn, ccf = fit._data_source
         if not isinstance(ccf.get("simulation_number", None), int):
             raise InputError("realisations() needs a fit constructed with an integer simulation_number "
@@ -73,6 +88,107 @@ class Realisations:
         beta = None if fit.fixed_data else fit.beta_ccf
         self.blocks = np.ascontiguousarray(np.stack(
             [data_table(np.array([a[m] for a in stacks]), fit.fixed_data, beta).ravel() for m in self.numbers]))
+        self.paired_model = bool(paired_model)
+        self._sets = {}           # (engine key, Simpson rule) -> (xi.coef, uni_xi, uni_xic) of every listed simulation, stacked
+        self._sets_of = {}        # id(engine) -> the entry of _sets it evaluates with
+        if self.paired_model:
+            self._real_input = self._read_real_stack(n_sims, data_fn)
+
+    # ------------------------------------------------------------------ paired model: table sets -------
+    def _read_real_stack(self, n_sims, data_fn):
+        """The model file's contents, after checking that its real-space CCF keys hold one realisation per realisation of the
+        data file (both formats of ``CCFModel._load_realspace_ccf``)."""
+        fit = self.fit
+        model_fn, rc = fit._real_source
+        if not isinstance(rc.get("simulation_number", None), int):
+            raise InputError("realisations(paired_model=True) needs a model constructed with an integer simulation_number "
+                             "(realspace_ccf.simulation_number)")
+        input_data = utils.read_input_file(model_fn, fit.extensions)
+        keys = np.atleast_1d(rc["ccf_keys"])
+        if rc.get("format", "multipoles") == "multipoles":
+            stack_keys = keys[1:]
+            want = fit.r.shape if fit.fixed_real_input else (len(fit.beta), len(fit.r))
+        else:
+            stack_keys = keys[2:]
+            n_mu = len(np.asarray(input_data[keys[1]]))
+            want = (len(fit.r), n_mu) if fit.fixed_real_input else (len(fit.beta), len(fit.r), n_mu)
+        for key in stack_keys:
+            a = np.asarray(input_data[key])
+            if a.ndim != len(want) + 1:
+                raise InputError(f"{key} in {model_fn} has no realisation axis (shape {a.shape})")
+            if a.shape[1:] != want:
+                raise InputError(f"Shape of a realisation of {key} in {model_fn} is {a.shape[1:]}, expected {want}")
+            if a.shape[0] != n_sims:
+                raise InputError(f"{key} in {model_fn} holds {a.shape[0]} realisations, the data file {data_fn} holds {n_sims}")
+        return input_data
+
+    def _model_of(self, number):
+        """The fit with the real-space CCF of simulation ``number`` in place of its own: what ``CCFModel`` reads when it is
+        built with that ``realspace_ccf.simulation_number`` (same loader), everything else shared."""
+        clone = copy.copy(self.fit)
+        clone._engine = None
+        _, rc = self.fit._real_source
+        clone._load_realspace_ccf(dict(rc, simulation_number=int(number)), self._real_input)
+        return clone
+
+    def model_sets(self, matter_model=None, simpson_even=None):
+        """``(xi_coef, uni_xi, uni_xic)``: the three xi^r arrays of ``vk_tables`` for every listed simulation, stacked in the
+        order of ``numbers`` (``uni_*``: ``None`` for tables without the unified grid).  Every other model-side array must equal
+        the fit's own bit for bit - a velocity profile derived from xi^r (``linear_bias``) or another ``r`` grid would need sets
+        of their own - else ``InputError`` names the first one that differs."""
+        from . import tables as T
+        from .engine import build_tables, table_array_lengths
+        fit = self.fit
+        matter_model = matter_model or fit._engine_key(fit.model)
+        rule = T.simpson_even_rule(simpson_even if simpson_even is not None else fit.model["simpson_even"])
+        key = (matter_model, rule)
+        if key in self._sets:
+            return self._sets[key]
+        if not self.paired_model:
+            raise InputError("model_sets() needs realisations(paired_model=True)")
+        mine = ("xi.coef", "uni_xi", "uni_xic")
+        data_side = ("beta_d", "data", "beta_c", "prec", "logdet", "eig")
+
+        def arrays(t):
+            out = {}
+            for name, n in table_array_lengths(t).items():
+                obj = t
+                for part in name.split("."):
+                    obj = getattr(obj, part)
+                if name in data_side:
+                    continue
+                out[name] = np.ctypeslib.as_array(obj, shape=(n,)).copy() if (n and obj) else None
+            return out
+
+        def scalars(t):
+            return [(n, getattr(t, n)) for n, ct in t._fields_ if isinstance(getattr(t, n), (int, float))] + \
+                   [(f"{p}.{n}", getattr(getattr(t, p), n)) for p in ("xi", "vr", "sv") for n in ("n_int", "lead", "inv_h")]
+
+        t0, keep0 = build_tables(fit, None, matter_model, rule)
+        ref, ref_s = arrays(t0), scalars(t0)
+        del keep0
+        stacks = {n: [] for n in mine}
+        for number in self.numbers:
+            t, keep = build_tables(self._model_of(number), None, matter_model, rule)
+            got, got_s = arrays(t), scalars(t)
+            del keep
+            for (n, a), (_, b) in zip(ref_s, got_s):
+                if a != b:
+                    raise InputError(f"paired_model: vk_tables.{n} of simulation {int(number)} differs from the fit's own "
+                                     f"({b} against {a}); only the real-space CCF may depend on the simulation")
+            for n, a in ref.items():
+                b = got[n]
+                if n in mine:
+                    if (a is None) != (b is None) or (a is not None and a.shape != b.shape):
+                        raise InputError(f"paired_model: vk_tables.{n} of simulation {int(number)} has another length than the fit's own")
+                    stacks[n].append(b)
+                elif (a is None) != (b is None) or (a is not None and a.tobytes() != b.tobytes()):
+                    raise InputError(f"paired_model: vk_tables.{n} of simulation {int(number)} differs from the fit's own; only the "
+                                     "real-space CCF may depend on the simulation (a velocity profile derived from it, as with "
+                                     "matter_ccf.model linear_bias, or another r grid would need table sets of their own)")
+        sets = tuple(None if stacks[n][0] is None else np.ascontiguousarray(np.stack(stacks[n])) for n in mine)
+        self._sets[key] = sets
+        return sets
 
     def __len__(self):
         return len(self.numbers)
@@ -83,15 +199,29 @@ class Realisations:
         model = fit._merged(kwargs)
         fit._check_supported(model)
         fit_options = fit._merged_fit(kwargs)
+        sets = None
+        if self.paired_model:
+            if model["rsd_model"] != "streaming":
+                raise InputError(f"realisations(paired_model=True) supports rsd_model 'streaming' only, not '{model['rsd_model']}'")
+            sets = self.model_sets(fit._engine_key(model), model["simpson_even"])     # (refusals before any device call)
         eng = fit._get_engine(fit._engine_key(model), model["simpson_even"])
+        if sets is not None:
+            self._sets_of[id(eng)] = sets
         self._upload(eng)
         return model, fit_options, eng, eng.make_opts(model, fit_options)
 
     def _upload(self, eng):
-        """Make this object's realisations the ones set on ``eng`` (uploaded only when another object's, or none, are there)."""
+        """Make this object's realisations the ones set on ``eng`` (uploaded only when another object's, or none, are there):
+        the data blocks and, paired, the xi^r table sets; an object without them clears the sets another one left."""
         owner = getattr(eng, "_real_owner", None)
         if owner is None or owner() is not self:
             eng.set_realisations(self.blocks)
+            if self.paired_model:
+                eng.set_model_realisations(*self._sets_of[id(eng)])
+                eng._model_sets = True
+            elif getattr(eng, "_model_sets", False):
+                eng.set_model_realisations(None, None, None)
+                eng._model_sets = False
             eng._real_owner = weakref.ref(self)
 
     def _eval(self, params, kwargs, which=None):
@@ -99,7 +229,24 @@ class Realisations:
         rows, which = check_which(self.fit._fit_rows(params, model), which, len(self))
         if fit_options["beta_interpolation"] == "likelihood" and not self.fit.fixed_data:
             return self._likelihood_interp(eng, opts, rows, which)
-        return eng.eval_realisations(opts, rows, len(self), which)
+        return self._eval_rows(eng, opts, rows, which)
+
+    def _eval_rows(self, eng, opts, rows, which):
+        """``Engine.eval_realisations``; paired, cross mode (``which=None``) expands to pairs on the host - a point has one
+        theory vector per realisation: rows repeated ``n_real`` times, ``which`` tiled, in chunks of whole points, reshaped to
+        ``(n_points, n_real)``."""
+        if not self.paired_model or which is not None:
+            return eng.eval_realisations(opts, rows, len(self), which)
+        R = len(self)
+        rows = np.asarray(rows, dtype=np.float64).reshape(-1, N.VK_NPAR)
+        lnl, chi2 = np.empty((len(rows), R)), np.empty((len(rows), R))
+        per = max(1, PAIR_CHUNK // R)
+        for lo in range(0, len(rows), per):
+            part = rows[lo:lo + per]
+            l, c = eng.eval_realisations(opts, np.repeat(part, R, axis=0), R, np.tile(np.arange(R, dtype=np.int32), len(part)))
+            lnl[lo:lo + per] = l.reshape(len(part), R)
+            chi2[lo:lo + per] = c.reshape(len(part), R)
+        return lnl, chi2
 
     def _likelihood_interp(self, eng, opts, rows, which):
         """beta_interpolation='likelihood' (reference: ccf_fit.py:383-440): both bracketing grid betas against every
@@ -112,7 +259,7 @@ class Realisations:
         both = np.concatenate([rows, rows])
         both[: len(rows), N.P_BETA] = g[lo]
         both[len(rows):, N.P_BETA] = g[hi]
-        lnl, chi2 = eng.eval_realisations(opts, both, len(self), None if which is None else np.concatenate([which, which]))
+        lnl, chi2 = self._eval_rows(eng, opts, both, None if which is None else np.concatenate([which, which]))
         n = len(rows)
         if which is None:
             t = t[:, None]
