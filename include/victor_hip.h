@@ -760,6 +760,66 @@ int64_t vk_fisher_rows(int32_t n_params);
 int vk_fit_fisher(vk_fit* f, const double* x, const double* h, double* vectors, double* fisher, double* a, double* cov, double* scale,
                   int32_t* status);
 
+/* ---- Grid posteriors: marginals, profile likelihoods and the evidence of every problem over one shared grid -----------------
+ * The fits have two to four sampled parameters: a grid gives exact marginals, profiles and the evidence where chains, histograms,
+ * Laplace and thermodynamic integration estimate them.  The reference has nothing of the kind (a user would loop
+ * CCFFit.log_likelihood, victor/ccf_fit.py:356-483, over the nodes on the host).  A grid handle evaluates that lnL at the nodes of
+ * a regular grid over d sampled parameters - against the context's data vector (one problem) or against EVERY realisation set on
+ * the context (vk_set_realisations: R = n_real problems, each grid point's theory vector computed once for all of them, the cross
+ * mode of vk_eval_realisations) - and reduces the values where they are produced; (G, R) values never travel to the host.
+ * victor_amd/grid.py states the definition in NumPy, vk_grid.h the index rules and the step, DESIGN.md section 7c the mapping.
+ *   columns[j]  row column (VK_P_*) of axis j, or VK_WALK_EPSILON, each once, 1 <= n_axes <= 10 (as vk_fit_create)
+ *   bins[j]     nodes of axis j, 1 .. 1024; G = prod bins[j] <= 2^40.  Flat index g is ROW-MAJOR: the last axis varies fastest
+ *   nodes       the node values of all axes, concatenated (sum bins[j] doubles, finite).  The caller's arrays are the definition:
+ *               the device looks nodes up and never recomputes one
+ *   eps_pow     [bins of the epsilon axis] the caller's own eps^(-2/3) of every node of an epsilon axis (NULL without one): the
+ *               row kernel forms apar = alpha eps_pow, aperp = eps apar from it, so a device row equals the row the host forms
+ *               (vk_epsilon_to_ap, CCFFit._fit_rows) BIT FOR BIT WITH EPSILON AS AN AXIS - unlike the best fits and chains above,
+ *               whose rows use the device's pow.  A node whose eps_pow is NaN (eps < 0) gives a row that fails: lnL = -inf
+ *   base_row    [VK_NPAR] the fixed parameters and defaults;  alpha as vk_fit_create
+ *   every_realisation   0: the context's data vector, R = 1;  else every realisation set on the context, R = n_real (a context
+ *               with model realisations, vk_set_model_realisations, is refused: a point has one theory vector there per realisation)
+ *   pairs       [n_pairs][2] axis pairs (a < b) for the two-dimensional products, at most 45, each axis of a pair at most 128 bins
+ *   chunk       grid points per launch, 1 .. 65536: the handle's one device allocation holds rows, workspace and two [chunk][R]
+ *               arrays
+ * lnpost[g][r] = lnL[g][r], plus ln prior at the point under vk_grid_set_prior (mu, pp_packed as vk_fit_set_prior; one rounded
+ * addition); a value that is not finite counts as -inf.  The chunks [c chunk, min((c + 1) chunk, G)) go in order; per chunk and
+ * problem, with M the running maximum (-inf at the start):
+ *   M' = max(M, max_g lnpost[g]); arg_max moves on a strict increase only, to the smallest such g; M' = -inf: nothing else happens
+ *   M' > M: total, m1, m2 of the problem are multiplied by exp(M - M') (exp(-inf) = 0), then M = M'
+ *   every accumulator adds exp(lnpost[g] - M) for its g of the chunk, ONE AT A TIME IN INCREASING g from its own value - no
+ *   pairwise or tree sums, no floating-point atomics -; p1, p2 take the maximum of lnpost; n_finite counts
+ * so maxima, arg max and counts do not depend on the chunk, sums depend on it through rounding only, and for a given chunk the
+ * bytes depend neither on how vk_grid_run calls cut the run nor on anything timed.
+ * vk_grid_run(h, first, count) enqueues the whole chunks of flat indices [first, min(first + count, G)) on the context's stream -
+ *   per chunk a rows kernel, the evaluation (the launches vk_eval_batch / vk_eval_realisations make for as many rows), and the
+ *   max, weight and accumulate kernels, no host synchronisation between chunks - and waits once at its end.  first is a multiple
+ *   of chunk: 0 starts a new run (the accumulators are reset), otherwise where the last call ended; count is whole chunks or
+ *   reaches G.  Resumable: a long grid reports progress between calls.
+ * vk_grid_rows(h, first, count, rows) forms the rows of flat indices first .. first + count - 1 (count <= chunk) as vk_grid_run
+ *   forms them and copies them home, [count][VK_NPAR]; nothing is evaluated.
+ * vk_grid_result, after a run has reached G, per problem r: ln_max [R] the largest lnpost (-inf: no node was finite), arg_max [R]
+ *   the smallest flat index attaining it (-1), total [R] = sum_g exp(lnpost_g - ln_max), n_finite [R], m1 / p1 [R][sum bins] the
+ *   weight sum and the lnpost maximum over the cells of every node of every axis (axis j at sum_{i<j} bins[i]), m2 / p2
+ *   [R][sum_pairs bins_a bins_b] the same per pair, [ka][kb];  prior_ln_max, prior_total: under a prior the same two numbers of
+ *   lnpost = ln prior alone - the Gaussian's own midpoint sum over the grid, accumulated by the same kernels as one more problem -
+ *   else 0.  Any output may be NULL.
+ * Synchronous calls that own the context while they run.  On error the code is returned, vk_grid_last_error gives the text and
+ * nothing stays in flight.  Refused (VK_E_ARG): what vk_fit_run refuses of the context, another number of realisations on the
+ * context than at vk_grid_create, a first that is not where the run stands, a result before the run is complete;
+ * vk_grid_set_prior moves the run back to its start. */
+typedef struct vk_grid vk_grid;
+vk_grid* vk_grid_create(vk_ctx* ctx, const vk_eval_opts* opts, int32_t n_axes, const int32_t* columns, const int32_t* bins,
+                        const double* nodes, const double* eps_pow, const double* base_row, double alpha,
+                        int32_t every_realisation, int32_t n_pairs, const int32_t* pairs, int32_t chunk, char* err, size_t errlen);
+int vk_grid_set_prior(vk_grid* h, const double* mu, const double* pp_packed);
+int vk_grid_run(vk_grid* h, int64_t first, int64_t count);
+int vk_grid_rows(vk_grid* h, int64_t first, int32_t count, double* rows);
+int vk_grid_result(vk_grid* h, double* ln_max, int64_t* arg_max, double* total, int64_t* n_finite, double* m1, double* p1,
+                   double* m2, double* p2, double* prior_ln_max, double* prior_total);
+const char* vk_grid_last_error(const vk_grid* h);
+void vk_grid_destroy(vk_grid* h);
+
 /* Theory multipoles on a caller-supplied s grid: out[n][n_ell][n_s] with the caller's own
  * projection weights w_ell[n_ell][n_mu] on mu[n_mu] (host buffers). */
 int vk_theory_batch(vk_ctx* ctx, const vk_eval_opts* opts, const double* params, int64_t n,

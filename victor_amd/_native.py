@@ -204,6 +204,15 @@ SYMBOLS = {
     # the Jacobian stencil of a best-fit handle's theory vectors and the Fisher matrix from it
     "vk_fisher_rows": (C.c_int64, [C.c_int32]),
     "vk_fit_fisher": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int32)]),
+    # grid posteriors: marginals, profiles and the evidence of every problem over one shared grid
+    "vk_grid_create": (_vp, [_vp, _optp, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp, _dp, _dp, C.c_double, C.c_int32,
+                             C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_char_p, C.c_size_t]),
+    "vk_grid_set_prior": (C.c_int, [_vp, _dp, _dp]),
+    "vk_grid_run": (C.c_int, [_vp, C.c_int64, C.c_int64]),
+    "vk_grid_rows": (C.c_int, [_vp, C.c_int64, C.c_int32, _dp]),
+    "vk_grid_result": (C.c_int, [_vp, _dp, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_int64), _dp, _dp, _dp, _dp, _dp, _dp]),
+    "vk_grid_last_error": (C.c_char_p, [_vp]),
+    "vk_grid_destroy": (None, [_vp]),
     "vk_serve_mailboxes": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, _optp, _vp, C.c_int32, _vp, C.c_double, C.c_int32,
                            C.c_double, C.POINTER(vk_serve_stats)]),
     "vk_timing_enable": (C.c_int, [_vp, C.c_int]),

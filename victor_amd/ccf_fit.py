@@ -380,6 +380,15 @@ class CCFFit(CCFModel):
                              kwargs, move=move, stretch_a=stretch_a, prior=prior, marginals=marginals,
                              autocorr=autocorr, temper=temper, predictive=predictive)
 
+    def grid_posterior(self, params, bins=32, ranges=None, fixed=None, prior=None, pairs=None, chunk=None, device=True, **kwargs):
+        """The posterior of this fit's data vector on a regular grid of the sampled parameters of a cobaya ``params`` block:
+        exact marginals, profile likelihoods and the evidence, reduced on the GPU where the likelihoods are produced
+        (``vk_grid_run``) or by the NumPy loop that defines them (``device=False``, over :meth:`log_likelihood_batch`):
+        :func:`victor_amd.grid.grid_posterior`, which documents the arguments.  Returns a
+        :class:`victor_amd.grid.GridPosterior` with R = 1.  Runs on this fit's own context (never through the broker)."""
+        from .grid import grid_posterior
+        return grid_posterior(self, params, bins, ranges, fixed, prior, pairs, chunk, device, kwargs)
+
     def realisations(self, simulation_numbers=None, paired_model=False):
         """Every simulation realisation of this fit's data file (or the listed ``simulation_numbers``) against one model:
         :class:`victor_amd.realisations.Realisations`.  The fit must have been built with an integer ``simulation_number``.

@@ -42,6 +42,8 @@
 //   vk_kernel_predictive.h the posterior-predictive sums (vk_chain_set_predictive): the hold kernel behind every step kernel, one
 //                        wave per row, which keeps each chain's theory vector, and the predict kernel behind every kept step, one
 //                        thread per (problem, entry), over the rules of vk_predictive.h (plain C++, likewise)
+//   vk_kernel_grid.h     grid posteriors (vk_grid_run; the last section of this file): rows, max, weight and accumulate kernels of
+//                        a chunk of grid points, over the index rules and the step of vk_grid.h (plain C++, likewise)
 
 #include <hip/hip_runtime.h>
 
@@ -63,6 +65,7 @@
 #include "vk_kernel_predictive.h"
 #include "vk_kernel_hessian.h"
 #include "vk_kernel_fisher.h"
+#include "vk_kernel_grid.h"
 
 using namespace vk;
 using vkh::check_joint;
@@ -170,11 +173,13 @@ static void sampled_destroy(H* f) {
 // leaves the library).  joint: ctxs are the n_ctx blocks of a joint fit, lead first, under cov (NULL: block-diagonal); otherwise
 // ctxs is the one context.  param_block (the _blocks forms; NULL otherwise): the block each sampled parameter belongs to, or -1;
 // base_rows then holds a set of n rows per block.
-template <class H>
+// prepare(f) runs on the new handle before shape(): a handle whose layout needs more than the count and the box (a grid's bins,
+// pairs and chunk) takes it there.
+template <class H, class Prepare>
 static H* sampled_create(const char* who, const char* noun, vk_ctx* const* ctxs, int n_ctx, bool joint, vk_joint_cov* cov,
                          const vk_eval_opts* opts, int32_t n, int32_t n_params, const int32_t* columns, const int32_t* param_block,
                          const double* lo, const double* hi, const double* base_rows, double alpha, const int32_t* which, char* err,
-                         size_t errlen) {
+                         size_t errlen, Prepare prepare) {
   auto bail = [&](const std::string& msg) -> H* {
     if (err && errlen) {
       strncpy(err, msg.c_str(), errlen - 1);
@@ -251,6 +256,7 @@ static H* sampled_create(const char* who, const char* noun, vk_ctx* const* ctxs,
   f->alpha = alpha;
   f->real = which != nullptr;
   f->max_which = max_which;
+  prepare(f);
   f->shape(n, lo, hi);
   size_t bytes = 0;
   if (!carve_alloc(ctx->device, f->d_mem, bytes, [&](Carve& c) { f->layout(c); })) {
@@ -265,6 +271,15 @@ static H* sampled_create(const char* who, const char* noun, vk_ctx* const* ctxs,
     return bail(me + "upload failed");
   }
   return f;
+}
+
+template <class H>
+static H* sampled_create(const char* who, const char* noun, vk_ctx* const* ctxs, int n_ctx, bool joint, vk_joint_cov* cov,
+                         const vk_eval_opts* opts, int32_t n, int32_t n_params, const int32_t* columns, const int32_t* param_block,
+                         const double* lo, const double* hi, const double* base_rows, double alpha, const int32_t* which, char* err,
+                         size_t errlen) {
+  return sampled_create<H>(who, noun, ctxs, n_ctx, joint, cov, opts, n, n_params, columns, param_block, lo, hi, base_rows, alpha,
+                           which, err, errlen, [](H*) {});
 }
 
 // the _blocks create calls, whose param_block is not optional
@@ -1685,6 +1700,277 @@ int vk_chain_state(vk_chain* f, double* x, double* lnl, double* chi2, int64_t* n
     if (n_steps) n_steps[c] = n[C + c];
     if (n_kept) n_kept[c] = n[2 * C + c];
   }
+  f->err.clear();
+  return VK_OK;
+}
+
+}  // extern "C"
+
+// ---- grid posteriors: marginals, profiles and the evidence of every problem over one shared grid (include/victor_hip.h, -------
+// vk_kernel_grid.h; the definition: victor_amd/grid.py, the index rules and the step: vk_grid.h) -------------------------------
+// A grid handle is a Sampled with ONE base row whose pending rows are a chunk of the grid: per chunk a rows kernel, sampled_evaluate
+// (the data-vector route with lnL, or enqueue_realisations in cross mode - d_row_which stays NULL, every row against every
+// realisation, [n][R]), then the max, weight and accumulate kernels, all on the context's stream with no host synchronisation
+// between chunks; vk_grid_run waits once at its end.  One allocation holds rows, workspace, the chunk's values and the accumulators.
+struct __attribute__((visibility("hidden"))) vk_grid : Sampled {
+  vkgrid::Shape g{};
+  int R = 1, chunk = 0, n1 = 0, n2 = 0, n_pairs = 0, n_eps = 0;
+  int axis_off[vkgrid::kMaxP] = {}, pair[vkgrid::kMaxPairs][2] = {}, pair_off[vkgrid::kMaxPairs] = {};
+  long long done = 0;                      // flat indices [0, done) are in the accumulators
+  vkgrid::Running* d_run = nullptr;        // [R + 1]: the problems', the prior's own
+  double *d_nodes = nullptr, *d_eps = nullptr, *d_lnprior = nullptr, *d_lnl = nullptr, *d_chi = nullptr, *d_wp = nullptr;
+  double *d_total = nullptr, *d_m1 = nullptr, *d_p1 = nullptr, *d_m2 = nullptr, *d_p2 = nullptr;
+
+  void shape(int, const double*, const double*) { rows_max = (size_t)chunk; }
+  void layout(Carve& c) {
+    const size_t n = (size_t)chunk, r = (size_t)R;
+    c.take(d_run, r + 1);
+    c.take(d_base, VK_NPAR);
+    c.take(d_rows, n * VK_NPAR);
+    c.take(d_nodes, (size_t)n1);
+    c.take(d_eps, (size_t)std::max(n_eps, 1));
+    c.take(d_lnprior, n);
+    c.take(d_lnl, n * r);
+    c.take(d_chi, n * r);                  // the evaluation's chi-squares, then the chunk's weights (vk_grid_weight_kernel)
+    c.take(d_wp, n);
+    c.take(d_th, workspace_doubles());
+    c.take(d_total, r + 1);
+    c.take(d_m1, r * n1);
+    c.take(d_p1, r * n1);
+    c.take(d_m2, r * n2);
+    c.take(d_p2, r * n2);
+  }
+  int Rp() const { return prior.on ? R + 1 : R; }
+  long long cells() const { return 1 + (long long)n1 + n2; }
+};
+
+static GridArgs grid_args(const vk_grid* f) {
+  GridArgs a{};
+  a.shape = f->g;
+  a.R = f->R;
+  a.Rp = f->Rp();
+  a.nodes = f->d_nodes;
+  a.eps_pow = f->n_eps ? f->d_eps : nullptr;
+  a.base = f->d_base;
+  a.rows = f->d_rows;
+  for (int j = 0; j < vkgrid::kMaxP; ++j) {
+    a.col[j] = f->col[j];
+    a.axis_off[j] = f->axis_off[j];
+  }
+  a.alpha = f->alpha;
+  a.prior = f->prior;
+  a.lnprior = f->d_lnprior;
+  a.lnl = f->d_lnl;
+  a.w = f->d_chi;
+  a.wp = f->d_wp;
+  a.run = f->d_run;
+  a.total = f->d_total;
+  a.m1 = f->d_m1;
+  a.p1 = f->d_p1;
+  a.m2 = f->d_m2;
+  a.p2 = f->d_p2;
+  a.n1 = f->n1;
+  a.n2 = f->n2;
+  a.n_pairs = f->n_pairs;
+  a.pr = 1;
+  while (a.pr < 64 && a.pr < a.Rp) a.pr *= 2;
+  for (int q = 0; q < f->n_pairs; ++q) {
+    a.pair[q][0] = f->pair[q][0];
+    a.pair[q][1] = f->pair[q][1];
+    a.pair_off[q] = f->pair_off[q];
+  }
+  return a;
+}
+
+// may the handle run now: the context, and of the realisation route that the set on the context is the one it was made for
+static int grid_ready(vk_grid* f, const char* who) {
+  int rc = sampled_ready(f, who, "grid", true);
+  if (rc) return rc;
+  if (f->real && f->ctx->n_real != f->R)
+    return refused(f, std::string(who) + ": the context holds " + std::to_string(f->ctx->n_real) + " realisations, the grid was made for " +
+                          std::to_string(f->R));
+  if (f->real && f->ctx->n_sets > 0)
+    return refused(f, std::string(who) + ": model realisations are set on the context (vk_set_model_realisations): a point has one "
+                          "theory vector per realisation, and a grid evaluates every point once");
+  return VK_OK;
+}
+
+// the launches of flat indices [first, end), chunk by chunk
+static int grid_chunks(vk_grid* f, long long first, long long end) {
+  GridArgs a = grid_args(f);
+  int rc = VK_OK;
+  if (first == 0) {
+    const long long most = std::max<long long>({a.Rp, (long long)a.R * a.n1, (long long)a.R * a.n2});
+    rc = sampled_launch(f, vk_grid_init_kernel, most, kGridBlock, a);
+  }
+  for (long long g0 = first; g0 < end && rc == VK_OK; g0 += f->chunk) {
+    a.g0 = g0;
+    a.n = (int)std::min<long long>(f->chunk, end - g0);
+    rc = sampled_launch(f, vk_grid_rows_kernel, a.n, kGridBlock, a);
+    if (rc == VK_OK) rc = sampled_evaluate(f, a.n, f->d_lnl, f->d_chi);
+    if (rc == VK_OK) rc = sampled_launch(f, vk_grid_max_kernel, (long long)((a.Rp + a.pr - 1) / a.pr) * kGridBlock, kGridBlock, a);
+    if (rc == VK_OK) rc = sampled_launch(f, vk_grid_weight_kernel, (long long)a.n * a.Rp, kGridBlock, a);
+    if (rc == VK_OK) rc = sampled_launch(f, vk_grid_accumulate_kernel, f->cells() * a.Rp, kGridBlock, a);
+  }
+  if (rc) return rc;
+  VK_SAMPLED_HIP(f, hipStreamSynchronize(f->ctx->stream));
+  return VK_OK;
+}
+
+extern "C" {
+
+vk_grid* vk_grid_create(vk_ctx* ctx, const vk_eval_opts* opts, int32_t n_axes, const int32_t* columns, const int32_t* bins,
+                        const double* nodes, const double* eps_pow, const double* base_row, double alpha, int32_t every_realisation,
+                        int32_t n_pairs, const int32_t* pairs, int32_t chunk, char* err, size_t errlen) {
+  auto bail = [&](const std::string& msg) -> vk_grid* {
+    if (err && errlen) snprintf(err, errlen, "vk_grid_create: %s", msg.c_str());
+    return nullptr;
+  };
+  if (!ctx || !opts || !columns || !bins || !nodes || !base_row || (n_pairs > 0 && !pairs)) return bail("NULL argument");
+  if (n_axes < 1 || n_axes > vkgrid::kMaxP) return bail("need 1 <= axes <= 10");
+  if (chunk < 1 || chunk > vkgrid::kMaxChunk) return bail("need 1 <= chunk <= 65536");
+  if (n_pairs < 0 || n_pairs > vkgrid::kMaxPairs) return bail("need 0 <= pairs <= 45");
+  long long G = 1, n1 = 0;
+  int eps_axis = -1;
+  for (int j = 0; j < n_axes; ++j) {
+    if (bins[j] < 1 || bins[j] > vkgrid::kMaxBins) return bail("axis " + std::to_string(j) + " needs 1 <= bins <= 1024");
+    G *= bins[j];                          // (at most 2^40 x 2^10 before the check: 64 bits hold it)
+    if (G > vkgrid::kMaxPoints) return bail("the grid has more than 2^40 points");
+    for (int k = 0; k < bins[j]; ++k)
+      if (!__builtin_isfinite(nodes[n1 + k])) return bail("node " + std::to_string(k) + " of axis " + std::to_string(j) + " is not finite");
+    n1 += bins[j];
+    if (columns[j] == VK_WALK_EPSILON) eps_axis = j;
+  }
+  if (eps_axis >= 0 && !eps_pow) return bail("an epsilon axis needs eps_pow, the host's eps^(-2/3) of every node");
+  long long n2 = 0;
+  for (int q = 0; q < n_pairs; ++q) {
+    const int ja = pairs[2 * q], jb = pairs[2 * q + 1];
+    if (ja < 0 || jb >= n_axes || ja >= jb) return bail("pair " + std::to_string(q) + " needs two axes 0 <= a < b < axes");
+    if (bins[ja] > vkgrid::kMaxBins2 || bins[jb] > vkgrid::kMaxBins2) return bail("an axis of a pair has at most 128 bins");
+    n2 += (long long)bins[ja] * bins[jb];
+  }
+  int R = 1;
+  if (every_realisation) {
+    if (ctx->n_real <= 0 || !ctx->d_real) return bail("no realisations are set on the context (vk_set_realisations)");
+    if (ctx->n_sets > 0)
+      return bail("model realisations are set on the context (vk_set_model_realisations): a point has one theory vector per "
+                  "realisation, and a grid evaluates every point once");
+    if (check_real_lds(ctx) != VK_OK) return bail(ctx->err);
+    R = ctx->n_real;
+  }
+  if ((1 + n1 + n2) * (long long)(R + 1) > (1LL << 31) * (kGridBlock / 2))
+    return bail("too many accumulators for one launch (cells x problems)");
+  const double inf = __builtin_inf();
+  double lo[vkgrid::kMaxP], hi[vkgrid::kMaxP];                 // (a grid has nodes, not a box)
+  for (int j = 0; j < vkgrid::kMaxP; ++j) lo[j] = -inf, hi[j] = inf;
+  vk_grid* f = sampled_create<vk_grid>("vk_grid_create", "grid", &ctx, 1, false, nullptr, opts, 1, n_axes, columns, nullptr, lo, hi,
+                                       base_row, alpha, nullptr, err, errlen, [&](vk_grid* h) {
+    h->g = vkgrid::make_shape(n_axes, bins);
+    h->R = R;
+    h->real = every_realisation != 0;
+    h->max_which = h->real ? R - 1 : -1;
+    h->chunk = chunk;
+    h->n1 = (int)n1;
+    h->n2 = (int)n2;
+    h->n_pairs = n_pairs;
+    h->n_eps = eps_axis >= 0 ? bins[eps_axis] : 0;
+    int off = 0;
+    for (int j = 0; j < n_axes; ++j) {
+      h->axis_off[j] = off;
+      off += bins[j];
+    }
+    off = 0;
+    for (int q = 0; q < n_pairs; ++q) {
+      h->pair[q][0] = pairs[2 * q];
+      h->pair[q][1] = pairs[2 * q + 1];
+      h->pair_off[q] = off;
+      off += bins[pairs[2 * q]] * bins[pairs[2 * q + 1]];
+    }
+  });
+  if (!f) return nullptr;
+  bool ok = hipMemcpy(f->d_nodes, nodes, (size_t)n1 * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+  if (ok && f->n_eps) ok = hipMemcpy(f->d_eps, eps_pow, (size_t)f->n_eps * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    sampled_destroy(f);
+    return bail("upload failed");
+  }
+  return f;
+}
+
+const char* vk_grid_last_error(const vk_grid* f) { return f ? f->err.c_str() : ""; }
+
+int vk_grid_set_prior(vk_grid* f, const double* mu, const double* pp_packed) {
+  if (!f) return VK_E_ARG;
+  const int rc = sampled_set_prior(f, "vk_grid_set_prior", mu, pp_packed);      // (vk_grid_run is synchronous: nothing is in flight)
+  if (rc == VK_OK) f->done = 0;            // the accumulators hold another posterior: the next run starts at 0
+  return rc;
+}
+
+void vk_grid_destroy(vk_grid* f) {
+  if (f) sampled_destroy(f);
+}
+
+int vk_grid_run(vk_grid* f, int64_t first, int64_t count) {
+  if (!f) return VK_E_ARG;
+  int rc = grid_ready(f, "vk_grid_run");
+  if (rc) return rc;
+  const long long G = f->g.G;
+  if (first < 0 || first >= G || count < 1) return refused(f, "vk_grid_run: need 0 <= first < points and count >= 1");
+  if (first % f->chunk) return refused(f, "vk_grid_run: first must be a multiple of the chunk (" + std::to_string(f->chunk) + ")");
+  if (first != 0 && first != f->done)
+    return refused(f, "vk_grid_run: the chunks go in order: first must be 0 (a new run) or " + std::to_string(f->done) +
+                          " (where the last call ended)");
+  const long long end = count > G - first ? G : first + count;
+  if (end != G && count % f->chunk) return refused(f, "vk_grid_run: count must be whole chunks, or reach the end of the grid");
+  VK_SAMPLED_HIP(f, hipSetDevice(f->ctx->device));
+  f->done = 0;
+  rc = grid_chunks(f, first, end);
+  if (rc != VK_OK) return sampled_abort(f, rc);
+  f->done = end;
+  f->err.clear();
+  return VK_OK;
+}
+
+int vk_grid_rows(vk_grid* f, int64_t first, int32_t count, double* rows) {
+  if (!f) return VK_E_ARG;
+  if (!rows) return refused(f, "vk_grid_rows: NULL argument");
+  int rc = grid_ready(f, "vk_grid_rows");
+  if (rc) return rc;
+  if (first < 0 || count < 1 || count > f->chunk || first > f->g.G - count)
+    return refused(f, "vk_grid_rows: need 1 <= count <= chunk and 0 <= first <= points - count");
+  VK_SAMPLED_HIP(f, hipSetDevice(f->ctx->device));
+  GridArgs a = grid_args(f);
+  a.g0 = first;
+  a.n = count;
+  rc = sampled_launch(f, vk_grid_rows_kernel, a.n, kGridBlock, a);
+  if (rc == VK_OK) rc = sampled_home(f, {{rows, f->d_rows, (size_t)count * VK_NPAR * sizeof(double)}}, true);
+  if (rc != VK_OK) return sampled_abort(f, rc);
+  VK_SAMPLED_HIP(f, hipStreamSynchronize(f->ctx->stream));
+  f->err.clear();
+  return VK_OK;
+}
+
+int vk_grid_result(vk_grid* f, double* ln_max, int64_t* arg_max, double* total, int64_t* n_finite, double* m1, double* p1, double* m2,
+                   double* p2, double* prior_ln_max, double* prior_total) {
+  if (!f) return VK_E_ARG;
+  if (f->done != f->g.G) return refused(f, "vk_grid_result: the run has reached " + std::to_string(f->done) + " of " + std::to_string(f->g.G) + " points");
+  const size_t R = (size_t)f->R, Rp = (size_t)f->Rp();
+  VK_SAMPLED_HIP(f, hipSetDevice(f->ctx->device));
+  std::vector<vkgrid::Running> run(Rp);
+  std::vector<double> tot(Rp);
+  const size_t one = R * sizeof(double);
+  int rc = sampled_home(f, {{run.data(), f->d_run, Rp * sizeof(vkgrid::Running)}, {tot.data(), f->d_total, Rp * sizeof(double)},
+                            {m1, f->d_m1, one * f->n1}, {p1, f->d_p1, one * f->n1}, {m2, f->d_m2, one * f->n2}, {p2, f->d_p2, one * f->n2}});
+  if (rc) return rc;
+  for (size_t r = 0; r < R; ++r) {
+    if (ln_max) ln_max[r] = run[r].m;
+    if (arg_max) arg_max[r] = run[r].arg;
+    if (total) total[r] = tot[r];
+    if (n_finite) n_finite[r] = run[r].n_finite;
+  }
+  if (prior_ln_max) *prior_ln_max = f->prior.on ? run[R].m : 0.0;
+  if (prior_total) *prior_total = f->prior.on ? tot[R] : 0.0;
   f->err.clear();
   return VK_OK;
 }

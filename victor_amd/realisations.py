@@ -320,6 +320,15 @@ class Realisations:
                              device, kwargs, realisations=self, move=move, stretch_a=stretch_a, prior=prior, marginals=marginals,
                              autocorr=autocorr, temper=temper, predictive=predictive)
 
+    def grid_posterior(self, params, bins=32, ranges=None, fixed=None, prior=None, pairs=None, chunk=None, device=True, **kwargs):
+        """The posterior of EVERY realisation on one shared grid (R = ``len(self)`` problems): a grid point's theory vector is
+        computed once and compared with all realisations, and marginals, profiles and the evidence are reduced on the GPU
+        (``device=True``) or by the NumPy loop over :meth:`log_likelihood` that defines them (``device=False``).  Arguments and
+        result as ``CCFFit.grid_posterior`` (:mod:`victor_amd.grid`).  Refused with ``paired_model=True``: a point then has one
+        theory vector per realisation."""
+        from .grid import grid_posterior
+        return grid_posterior(self.fit, params, bins, ranges, fixed, prior, pairs, chunk, device, kwargs, realisations=self)
+
     def log_likelihood_pairs(self, params, which, **kwargs):
         """(lnL, chi2), each ``(n_points,)``: point p against realisation ``numbers[which[p]]`` only - the form an ensemble of
         independent per-mock chains needs.  The same bits as the matching entries of :meth:`log_likelihood`."""
