@@ -820,6 +820,42 @@ int vk_grid_result(vk_grid* h, double* ln_max, int64_t* arg_max, double* total, 
 const char* vk_grid_last_error(const vk_grid* h);
 void vk_grid_destroy(vk_grid* h);
 
+/* ---- nested sampling: the evidence and a posterior sample of the data vector or of every realisation ---------------------------
+ * R problems of L live points each inside the box [lo, hi]; per iteration the K lowest live points of every problem die and K
+ * walkers, each started at a surviving live point, take S constrained random-walk steps and replace them.  The handle is one of
+ * R K rows: row r K + k of EVERY launch it makes is walker k of problem r (base_rows, which: one entry per row, as
+ * vk_chain_create; the K rows of a problem name one realisation).  victor_amd/nested.py states the loop in NumPy - that is the
+ * definition, reproduced bit for bit with epsilon fixed -, vk_nested_step.h the rules, DESIGN.md section 7d the mapping.
+ *   n_rows      R K, at most 65536;  n_live L, 2 .. 4096;  batch K, a divisor of L with K <= L / 2;  steps S, 1 .. 1024
+ *   scale       the proposal of a step is  y_j + (scale range_j) dz_j,  range_j = max - min of parameter j over the problem's L
+ *               live points at the start of the iteration; each product and the sum rounded on its own
+ *   n_params, columns, lo, hi, base_rows, alpha, which (and ctxs, cov, param_block of the joint forms): as vk_chain_create
+ * vk_nested_start(h, x0): x0 [R][L][d], inside the box.  L / K launches evaluate the points: row r K + k of pass p is live point
+ *   p K + k of problem r.  A NaN lnL is stored as -inf.  Fresh counters.  Synchronous.
+ * vk_nested_begin(h, n_iter, pick, dz, first_iter, keep_dead) enqueues 1 <= n_iter <= 8 iterations, first_iter the number of
+ *   iterations finished since the start: pick [n_iter][R K] in [0, 1), dz [n_iter][S][R K][d].  Per iteration and problem: the K
+ *   live points smallest in (lnL, index) are dead points 0 .. K - 1 in that order (ties go to the smaller index), L* the lnL of
+ *   the last; walker k starts at survivor min(floor(pick (L - K)), L - K - 1) of the L - K others in increasing index; a step is
+ *   accepted when its proposal lies inside the box and lnL' > L* (strict; a NaN rejects), a proposal outside the box is
+ *   evaluated at the walker's position and discarded; after step S walker k takes the slot of dead point k.  No host
+ *   synchronisation inside the block.
+ * vk_nested_finish(h, dead_lnl, dead_chi2, dead_x, live_lnl) waits and copies home the block's dead record [n_iter][R][K]
+ *   (dead_x [n_iter][R][K][d]: what keep_dead asked for, else unspecified) and the live lnL [R][L] behind it.  Any may be NULL.
+ * vk_nested_state(h, x, lnl, chi2, n_accept, n_steps, n_stuck): the live points [R][L][d], [R][L] and per problem [R] the
+ *   accepted steps, the steps and the walkers that never moved in their iteration (they leave a duplicate).  Any may be NULL.
+ * On error the code is returned, vk_nested_last_error gives the text and nothing stays in flight.  Refused (VK_E_ARG): what
+ * vk_chain_begin refuses of the context, a block out of order, a start outside the box, a second begin before the finish. */
+typedef struct vk_nested vk_nested;
+vk_nested* vk_nested_create(vk_ctx* ctx, const vk_eval_opts* opts, int32_t n_rows, int32_t n_live, int32_t batch, int32_t steps,
+                            double scale, int32_t n_params, const int32_t* columns, const double* lo, const double* hi,
+                            const double* base_rows, double alpha, const int32_t* which, char* err, size_t errlen);
+int vk_nested_start(vk_nested* h, const double* x0);
+int vk_nested_begin(vk_nested* h, int32_t n_iter, const double* pick, const double* dz, int64_t first_iter, int32_t keep_dead);
+int vk_nested_finish(vk_nested* h, double* dead_lnl, double* dead_chi2, double* dead_x, double* live_lnl);
+int vk_nested_state(vk_nested* h, double* x, double* lnl, double* chi2, int64_t* n_accept, int64_t* n_steps, int64_t* n_stuck);
+const char* vk_nested_last_error(const vk_nested* h);
+void vk_nested_destroy(vk_nested* h);
+
 /* Theory multipoles on a caller-supplied s grid: out[n][n_ell][n_s] with the caller's own
  * projection weights w_ell[n_ell][n_mu] on mu[n_mu] (host buffers). */
 int vk_theory_batch(vk_ctx* ctx, const vk_eval_opts* opts, const double* params, int64_t n,
@@ -978,6 +1014,18 @@ vk_chain* vk_chain_create_joint_blocks(vk_ctx* const* ctxs, int32_t n_ctx, vk_jo
                                        int32_t n_chains, int32_t n_params, const int32_t* columns, const int32_t* param_block,
                                        const double* lo, const double* hi, const double* base_rows, double alpha,
                                        const int32_t* which, char* err, size_t errlen);
+/* Nested sampling (vk_nested_create above) of a joint fit: the same handle over the joint entry points, one row for all blocks
+ * or (_blocks) a row per block; which[i]: joint realisation of row i.  Arguments as vk_chain_create_joint /
+ * vk_chain_create_joint_blocks with the shape of vk_nested_create behind n_rows. */
+vk_nested* vk_nested_create_joint(vk_ctx* const* ctxs, int32_t n_ctx, vk_joint_cov* cov, const vk_eval_opts* opts, int32_t n_rows,
+                                  int32_t n_live, int32_t batch, int32_t steps, double scale, int32_t n_params,
+                                  const int32_t* columns, const double* lo, const double* hi, const double* base_rows,
+                                  double alpha, const int32_t* which, char* err, size_t errlen);
+vk_nested* vk_nested_create_joint_blocks(vk_ctx* const* ctxs, int32_t n_ctx, vk_joint_cov* cov, const vk_eval_opts* opts,
+                                         int32_t n_rows, int32_t n_live, int32_t batch, int32_t steps, double scale,
+                                         int32_t n_params, const int32_t* columns, const int32_t* param_block, const double* lo,
+                                         const double* hi, const double* base_rows, double alpha, const int32_t* which, char* err,
+                                         size_t errlen);
 
 /* ---- many one-point callers sharing one GPU: mailboxes in shared memory -----------------------------------------------
  * The reference is sampled by cobaya, which asks for ONE likelihood per call (victor/likelihoods/CCFLikelihood.py:32-39); more

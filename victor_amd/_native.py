@@ -213,6 +213,21 @@ SYMBOLS = {
     "vk_grid_result": (C.c_int, [_vp, _dp, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_int64), _dp, _dp, _dp, _dp, _dp, _dp]),
     "vk_grid_last_error": (C.c_char_p, [_vp]),
     "vk_grid_destroy": (None, [_vp]),
+    # nested sampling: R problems of L live points, K replaced per iteration by S constrained steps
+    "vk_nested_create": (_vp, [_vp, _optp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.POINTER(C.c_int32),
+                               _dp, _dp, _dp, C.c_double, C.POINTER(C.c_int32), C.c_char_p, C.c_size_t]),
+    "vk_nested_create_joint": (_vp, [C.POINTER(C.c_void_p), C.c_int32, _vp, _optp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                     C.c_double, C.c_int32, C.POINTER(C.c_int32), _dp, _dp, _dp, C.c_double, C.POINTER(C.c_int32),
+                                     C.c_char_p, C.c_size_t]),
+    "vk_nested_create_joint_blocks": (_vp, [C.POINTER(C.c_void_p), C.c_int32, _vp, _optp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                            C.c_double, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp, _dp, _dp,
+                                            C.c_double, C.POINTER(C.c_int32), C.c_char_p, C.c_size_t]),
+    "vk_nested_start": (C.c_int, [_vp, _dp]),
+    "vk_nested_begin": (C.c_int, [_vp, C.c_int32, _dp, _dp, C.c_int64, C.c_int32]),
+    "vk_nested_finish": (C.c_int, [_vp, _dp, _dp, _dp, _dp]),
+    "vk_nested_state": (C.c_int, [_vp, _dp, _dp, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "vk_nested_last_error": (C.c_char_p, [_vp]),
+    "vk_nested_destroy": (None, [_vp]),
     "vk_serve_mailboxes": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, _optp, _vp, C.c_int32, _vp, C.c_double, C.c_int32,
                            C.c_double, C.POINTER(vk_serve_stats)]),
     "vk_timing_enable": (C.c_int, [_vp, C.c_int]),

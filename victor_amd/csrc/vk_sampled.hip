@@ -42,8 +42,11 @@
 //   vk_kernel_predictive.h the posterior-predictive sums (vk_chain_set_predictive): the hold kernel behind every step kernel, one
 //                        wave per row, which keeps each chain's theory vector, and the predict kernel behind every kept step, one
 //                        thread per (problem, entry), over the rules of vk_predictive.h (plain C++, likewise)
-//   vk_kernel_grid.h     grid posteriors (vk_grid_run; the last section of this file): rows, max, weight and accumulate kernels of
+//   vk_kernel_grid.h     grid posteriors (vk_grid_run; the section before the last of this file): rows, max, weight and accumulate kernels of
 //                        a chunk of grid points, over the index rules and the step of vk_grid.h (plain C++, likewise)
+//   vk_kernel_nested.h   nested sampling (vk_nested_begin; the last section of this file): the select kernel, one workgroup per
+//                        problem, and the step and commit kernels, one thread per replacement walker, over the order, the pick,
+//                        the constrained step and the commit of vk_nested_step.h (plain C++, likewise)
 
 #include <hip/hip_runtime.h>
 
@@ -66,6 +69,7 @@
 #include "vk_kernel_hessian.h"
 #include "vk_kernel_fisher.h"
 #include "vk_kernel_grid.h"
+#include "vk_kernel_nested.h"
 
 using namespace vk;
 using vkh::check_joint;
@@ -1971,6 +1975,290 @@ int vk_grid_result(vk_grid* f, double* ln_max, int64_t* arg_max, double* total, 
   }
   if (prior_ln_max) *prior_ln_max = f->prior.on ? run[R].m : 0.0;
   if (prior_total) *prior_total = f->prior.on ? tot[R] : 0.0;
+  f->err.clear();
+  return VK_OK;
+}
+
+}  // extern "C"
+
+// ---- nested sampling: R problems of L live points, K replaced per iteration by S constrained steps (include/victor_hip.h, --------
+// vk_kernel_nested.h; the definition: victor_amd/nested.py, the rules: vk_nested_step.h) ----------------------------------------
+// A nested handle is a Sampled of R K rows: row r K + k is walker k of problem r in every launch it makes.  An iteration enqueues
+// the select kernel, S times (sampled_evaluate, the step kernel) and the commit kernel on the context's stream; a block of up
+// to 8 iterations runs without host synchronisation between vk_nested_begin, which uploads the block's random numbers, and
+// vk_nested_finish, which waits and brings the block's dead record and the live lnL home.
+struct __attribute__((visibility("hidden"))) vk_nested : Sampled {
+  int R = 0, L = 0, K = 0, S = 0, RK = 0;
+  double scale = 0.0;
+  vkchain::Box box{};
+  bool started = false;
+  int in_flight = 0;                       // iterations of the block begun and not finished
+  long long done = 0;                      // iterations finished since vk_nested_start
+  double *d_lx = nullptr, *d_llnl = nullptr, *d_lchi = nullptr, *d_wx = nullptr, *d_wlnl = nullptr, *d_wchi = nullptr;
+  double *d_lstar = nullptr, *d_range = nullptr, *d_x0 = nullptr, *d_res_lnl = nullptr, *d_res_chi = nullptr;
+  double *d_pick = nullptr, *d_dz = nullptr, *d_dlnl = nullptr, *d_dchi = nullptr, *d_dx = nullptr;
+  long long *d_acc = nullptr, *d_steps = nullptr, *d_stuck = nullptr;
+  int *d_wslot = nullptr, *d_wmoved = nullptr;
+
+  void shape(int n, const double* lo, const double* hi) {
+    RK = n;
+    R = n / K;
+    rows_max = (size_t)n;
+    box.d = P;
+    for (int j = 0; j < P; ++j) {
+      box.lo[j] = lo[j];
+      box.hi[j] = hi[j];
+    }
+  }
+  // live points | walkers | L*, ranges | base, start, rows, results, theory workspace | one block of random numbers | one block of
+  // dead record | counters | indices
+  void layout(Carve& c) {
+    const size_t n = RK, live = (size_t)R * L, block = (size_t)vknest::kBlock * n;
+    c.take(d_lx, live * P);
+    c.take(d_llnl, live);
+    c.take(d_lchi, live);
+    c.take(d_wx, n * P);
+    c.take(d_wlnl, n);
+    c.take(d_wchi, n);
+    c.take(d_lstar, (size_t)R);
+    c.take(d_range, (size_t)R * P);
+    c.take(d_base, sets * n * VK_NPAR);
+    c.take(d_x0, live * P);
+    c.take(d_rows, sets * n * VK_NPAR);
+    c.take(d_res_lnl, n);
+    c.take(d_res_chi, n);
+    c.take(d_th, workspace_doubles());
+    c.take(d_pick, block);
+    c.take(d_dz, block * S * P);
+    c.take(d_dlnl, block);
+    c.take(d_dchi, block);
+    c.take(d_dx, block * P);
+    c.take(d_acc, n);
+    c.take(d_steps, n);
+    c.take(d_stuck, n);
+    c.take(d_which, n);
+    c.take(d_row_which, n);
+    c.take(d_wslot, n);
+    c.take(d_wmoved, n);
+  }
+};
+
+static NestedArgs nested_args(const vk_nested* f) {
+  NestedArgs a{};
+  a.box = f->box;
+  a.R = f->R;
+  a.L = f->L;
+  a.K = f->K;
+  a.scale = f->scale;
+  a.lx = f->d_lx;
+  a.llnl = f->d_llnl;
+  a.lchi = f->d_lchi;
+  a.wx = f->d_wx;
+  a.wlnl = f->d_wlnl;
+  a.wchi = f->d_wchi;
+  a.wslot = f->d_wslot;
+  a.wmoved = f->d_wmoved;
+  a.n_accept = f->d_acc;
+  a.n_steps = f->d_steps;
+  a.n_stuck = f->d_stuck;
+  a.lstar = f->d_lstar;
+  a.range = f->d_range;
+  a.base = f->d_base;
+  a.which = f->real ? f->d_which : nullptr;
+  a.rows = f->d_rows;
+  a.row_which = f->real ? f->d_row_which : nullptr;
+  a.res_lnl = f->d_res_lnl;
+  a.res_chi2 = f->d_res_chi;
+  a.x0 = f->d_x0;
+  for (int j = 0; j < vknest::kMaxP; ++j) a.col[j] = f->col[j];
+  a.alpha = f->alpha;
+  a.blocks = f->row_sets((size_t)f->RK);
+  return a;
+}
+
+// vk_nested_create and its joint forms: the shape is checked before the shared create call, which lays the handle out from it
+template <class Make>
+static vk_nested* nested_create(const char* who, int32_t n_rows, int32_t n_live, int32_t batch, int32_t steps, double scale, char* err,
+                                size_t errlen, Make make) {
+  auto bail = [&](const std::string& msg) -> vk_nested* {
+    if (err && errlen) snprintf(err, errlen, "%s: %s", who, msg.c_str());
+    return nullptr;
+  };
+  if (n_live < 2 || n_live > vknest::kMaxLive) return bail("need 2 <= live points <= 4096");
+  if (batch < 1 || n_live % batch || batch > n_live / 2)
+    return bail("the batch must divide the live points and be at most half of them");
+  if (steps < 1 || steps > 1024) return bail("need 1 <= steps <= 1024");
+  if (!(scale > 0) || !__builtin_isfinite(scale)) return bail("need a finite scale > 0");
+  if (n_rows < 1 || n_rows > kSampledMax) return bail("need 1 <= rows <= 65536");
+  if (n_rows % batch) return bail(std::to_string(n_rows) + " rows are not a whole number of problems of " + std::to_string(batch));
+  return make([=](vk_nested* h) {
+    h->L = n_live;
+    h->K = batch;
+    h->S = steps;
+    h->scale = scale;
+  });
+}
+
+extern "C" {
+
+vk_nested* vk_nested_create(vk_ctx* ctx, const vk_eval_opts* opts, int32_t n_rows, int32_t n_live, int32_t batch, int32_t steps,
+                            double scale, int32_t n_params, const int32_t* columns, const double* lo, const double* hi,
+                            const double* base_rows, double alpha, const int32_t* which, char* err, size_t errlen) {
+  return nested_create("vk_nested_create", n_rows, n_live, batch, steps, scale, err, errlen, [&](auto prepare) {
+    return sampled_create<vk_nested>("vk_nested_create", "row", &ctx, 1, false, nullptr, opts, n_rows, n_params, columns, nullptr, lo,
+                                     hi, base_rows, alpha, which, err, errlen, prepare);
+  });
+}
+
+vk_nested* vk_nested_create_joint(vk_ctx* const* ctxs, int32_t n_ctx, vk_joint_cov* cov, const vk_eval_opts* opts, int32_t n_rows,
+                                  int32_t n_live, int32_t batch, int32_t steps, double scale, int32_t n_params,
+                                  const int32_t* columns, const double* lo, const double* hi, const double* base_rows, double alpha,
+                                  const int32_t* which, char* err, size_t errlen) {
+  return nested_create("vk_nested_create_joint", n_rows, n_live, batch, steps, scale, err, errlen, [&](auto prepare) {
+    return sampled_create<vk_nested>("vk_nested_create_joint", "row", ctxs, n_ctx, true, cov, opts, n_rows, n_params, columns, nullptr,
+                                     lo, hi, base_rows, alpha, which, err, errlen, prepare);
+  });
+}
+
+vk_nested* vk_nested_create_joint_blocks(vk_ctx* const* ctxs, int32_t n_ctx, vk_joint_cov* cov, const vk_eval_opts* opts,
+                                         int32_t n_rows, int32_t n_live, int32_t batch, int32_t steps, double scale,
+                                         int32_t n_params, const int32_t* columns, const int32_t* param_block, const double* lo,
+                                         const double* hi, const double* base_rows, double alpha, const int32_t* which, char* err,
+                                         size_t errlen) {
+  if (no_param_block("vk_nested_create_joint_blocks", param_block, err, errlen)) return nullptr;
+  return nested_create("vk_nested_create_joint_blocks", n_rows, n_live, batch, steps, scale, err, errlen, [&](auto prepare) {
+    return sampled_create<vk_nested>("vk_nested_create_joint_blocks", "row", ctxs, n_ctx, true, cov, opts, n_rows, n_params, columns,
+                                     param_block, lo, hi, base_rows, alpha, which, err, errlen, prepare);
+  });
+}
+
+const char* vk_nested_last_error(const vk_nested* f) { return f ? f->err.c_str() : ""; }
+
+void vk_nested_destroy(vk_nested* f) {
+  if (!f) return;
+  if (f->in_flight) (void)hipStreamSynchronize(f->ctx->stream);
+  sampled_destroy(f);
+}
+
+// x0 [R][L][d]: the live points, inside the box.  L / K launches of R K rows each evaluate them: row r K + k of pass p is live
+// point p K + k of problem r.
+int vk_nested_start(vk_nested* f, const double* x0) {
+  if (!f) return VK_E_ARG;
+  if (!x0) return refused(f, "vk_nested_start: NULL argument");
+  if (f->in_flight) return refused(f, "vk_nested_start: a block begun with vk_nested_begin is awaiting vk_nested_finish");
+  int rc = sampled_ready(f, "vk_nested_start", "row", true);
+  if (rc) return rc;
+  const size_t live = (size_t)f->R * f->L;
+  for (size_t i = 0; i < live; ++i)
+    if (!vkchain::in_box(f->box, x0 + i * f->P))
+      return refused(f, "vk_nested_start: live point " + std::to_string(i % f->L) + " of problem " + std::to_string(i / f->L) +
+                            " is outside the box");
+  VK_SAMPLED_HIP(f, hipSetDevice(f->ctx->device));
+  VK_SAMPLED_HIP(f, hipMemcpy(f->d_x0, x0, live * f->P * sizeof(double), hipMemcpyHostToDevice));
+  f->started = false;
+  NestedArgs a = nested_args(f);
+  for (int p = 0; p < f->L / f->K && rc == VK_OK; ++p) {
+    a.pass = p;
+    rc = sampled_launch(f, vk_nested_load_kernel, f->RK, kNestedBlock, a);
+    if (rc == VK_OK) rc = sampled_evaluate(f, f->RK, f->d_res_lnl, f->d_res_chi);
+    if (rc == VK_OK) rc = sampled_launch(f, vk_nested_adopt_kernel, f->RK, kNestedBlock, a);
+  }
+  if (rc) return sampled_abort(f, rc);
+  VK_SAMPLED_HIP(f, hipStreamSynchronize(f->ctx->stream));
+  f->started = true;
+  f->done = 0;
+  f->err.clear();
+  return VK_OK;
+}
+
+// pick [n_iter][R K], dz [n_iter][S][R K][d]: the block's random numbers; first_iter: the life-long index of its first iteration
+int vk_nested_begin(vk_nested* f, int32_t n_iter, const double* pick, const double* dz, int64_t first_iter, int32_t keep_dead) {
+  if (!f) return VK_E_ARG;
+  const std::string me = "vk_nested_begin: ";
+  if (!pick || !dz) return refused(f, me + "NULL argument");
+  if (!f->started) return refused(f, me + "the live points have no start (vk_nested_start)");
+  if (f->in_flight) return refused(f, me + "the previous block has not been finished (vk_nested_finish)");
+  if (n_iter < 1 || n_iter > vknest::kBlock) return refused(f, me + "need 1 <= iterations <= 8 in a block");
+  if (first_iter != f->done)
+    return refused(f, me + "the iterations go in order: first_iter must be " + std::to_string(f->done) + " (where the last block ended)");
+  int rc = sampled_ready(f, "vk_nested_begin", "row", true);
+  if (rc) return rc;
+  VK_SAMPLED_HIP(f, hipSetDevice(f->ctx->device));
+  const size_t n = f->RK, P = f->P, S = f->S;
+  // the stream is idle (the block before was finished): plain copies, complete on return
+  VK_SAMPLED_HIP(f, hipMemcpy(f->d_pick, pick, (size_t)n_iter * n * sizeof(double), hipMemcpyHostToDevice));
+  VK_SAMPLED_HIP(f, hipMemcpy(f->d_dz, dz, (size_t)n_iter * S * n * P * sizeof(double), hipMemcpyHostToDevice));
+  NestedArgs a = nested_args(f);
+  for (int t = 0; t < n_iter && rc == VK_OK; ++t) {
+    const double* dz_t = f->d_dz + (size_t)t * S * n * P;
+    a.pick = f->d_pick + (size_t)t * n;
+    a.dz = dz_t;
+    a.dz_next = nullptr;
+    a.dead_lnl = f->d_dlnl + (size_t)t * n;
+    a.dead_chi2 = f->d_dchi + (size_t)t * n;
+    a.dead_x = keep_dead ? f->d_dx + (size_t)t * n * P : nullptr;
+    rc = sampled_launch(f, vk_nested_select_kernel, (long long)f->R * kNestedSelect, kNestedSelect, a);
+    for (size_t s = 0; s < S && rc == VK_OK; ++s) {
+      rc = sampled_evaluate(f, f->RK, f->d_res_lnl, f->d_res_chi);
+      if (rc) break;
+      a.dz = dz_t + s * n * P;
+      a.dz_next = s + 1 < S ? a.dz + n * P : nullptr;
+      rc = sampled_launch(f, vk_nested_step_kernel, f->RK, kNestedBlock, a);
+    }
+    if (rc == VK_OK) rc = sampled_launch(f, vk_nested_commit_kernel, f->RK, kNestedBlock, a);
+  }
+  if (rc) return sampled_abort(f, rc);
+  f->in_flight = n_iter;
+  f->err.clear();
+  return VK_OK;
+}
+
+// dead_lnl, dead_chi2 [n_iter][R][K] and dead_x [n_iter][R][K][d] (NULL: not wanted) of the block, live_lnl [R][L] behind it
+int vk_nested_finish(vk_nested* f, double* dead_lnl, double* dead_chi2, double* dead_x, double* live_lnl) {
+  if (!f) return VK_E_ARG;
+  if (!f->in_flight) return refused(f, "vk_nested_finish: nothing was begun");
+  const size_t n = (size_t)f->in_flight * f->RK, one = sizeof(double);
+  int rc = hipSetDevice(f->ctx->device) == hipSuccess ? VK_OK : VK_E_HIP;
+  if (rc == VK_OK)
+    rc = sampled_home(f, {{dead_lnl, f->d_dlnl, n * one}, {dead_chi2, f->d_dchi, n * one}, {dead_x, f->d_dx, n * f->P * one},
+                          {live_lnl, f->d_llnl, (size_t)f->R * f->L * one}}, true);
+  hipError_t e = hipStreamSynchronize(f->ctx->stream);
+  f->done += f->in_flight;
+  f->in_flight = 0;
+  if (rc != VK_OK || e != hipSuccess) {
+    (void)hipGetLastError();
+    if (rc == VK_OK) f->err = std::string("vk_nested_finish: ") + hipGetErrorString(e);
+    return VK_E_HIP;
+  }
+  f->err.clear();
+  return VK_OK;
+}
+
+// x [R][L][d], lnl, chi2 [R][L]: the live points; n_accept, n_steps, n_stuck [R]: per problem, summed over its walkers
+int vk_nested_state(vk_nested* f, double* x, double* lnl, double* chi2, int64_t* n_accept, int64_t* n_steps, int64_t* n_stuck) {
+  if (!f) return VK_E_ARG;
+  if (!f->started || f->in_flight)
+    return refused(f, f->started ? "vk_nested_state: a block begun with vk_nested_begin is awaiting vk_nested_finish"
+                                 : "vk_nested_state: the live points have no start (vk_nested_start)");
+  const size_t live = (size_t)f->R * f->L, P = f->P, n = f->RK;
+  VK_SAMPLED_HIP(f, hipSetDevice(f->ctx->device));
+  std::vector<double> h(x ? live * P : 0);
+  std::vector<long long> cnt(3 * n);                       // n_accept | n_steps | n_stuck are contiguous
+  int rc = sampled_home(f, {{h.data(), f->d_lx, h.size() * sizeof(double)}, {lnl, f->d_llnl, live * sizeof(double)},
+                            {chi2, f->d_lchi, live * sizeof(double)}, {cnt.data(), f->d_acc, cnt.size() * sizeof(long long)}});
+  if (rc) return rc;
+  if (x)
+    for (size_t i = 0; i < live; ++i)
+      for (size_t j = 0; j < P; ++j) x[i * P + j] = h[j * live + i];
+  int64_t* out[3] = {n_accept, n_steps, n_stuck};
+  for (int q = 0; q < 3; ++q) {
+    if (!out[q]) continue;
+    for (int r = 0; r < f->R; ++r) {
+      long long sum = 0;
+      for (int k = 0; k < f->K; ++k) sum += cnt[(size_t)q * n + (size_t)r * f->K + k];
+      out[q][r] = sum;
+    }
+  }
   f->err.clear();
   return VK_OK;
 }

@@ -172,15 +172,16 @@ class _Sampled:
                              f"[{self.lo[j]}, {self.hi[j]}]")
         return x0
 
-    def create(self, entry, fit, realisations, kwargs, fit_options, batch, which):
-        """``(lib, handle, refresh)`` of ``entry`` (``vk_fit_create`` / ``vk_chain_create``): one problem per row of ``batch``
+    def create(self, entry, fit, realisations, kwargs, fit_options, batch, which, shape=()):
+        """``(lib, handle, refresh)`` of ``entry`` (``vk_fit_create`` / ``vk_chain_create``; ``vk_nested_create`` with its ``shape``
+        arguments, which follow the row count): one problem per row of ``batch``
         (the sampled and fixed values its rows start from), against the fit's data vector or realisation ``which[i]``.
         ``refresh`` (None against the data vector) makes ``realisations`` the ones set on the handle's context(s) again - another
         object's may have been set since.  A :class:`victor_amd.joint.JointFit` builds its own handle, of ``entry + "_joint"``
         (``JointFit._sampled_create``)."""
         from .joint import JointFit
         if isinstance(fit, JointFit):
-            return fit._sampled_create(entry + "_joint", self, realisations, kwargs, batch, which)
+            return fit._sampled_create(entry + "_joint", self, realisations, kwargs, batch, which, shape)
         model = fit._merged(kwargs)
         fit._check_supported(model)
         rows = np.ascontiguousarray(fit._fit_rows(batch, model), dtype=np.float64)
@@ -196,7 +197,7 @@ class _Sampled:
                 realisations._upload(eng)
         i32 = C.POINTER(C.c_int32)
         err = C.create_string_buffer(512)
-        h = getattr(eng._lib, entry)(eng._ctx, C.byref(opts), len(rows), len(cols), cols.ctypes.data_as(i32), N.as_dp(N.f64(self.lo)),
+        h = getattr(eng._lib, entry)(eng._ctx, C.byref(opts), len(rows), *shape, len(cols), cols.ctypes.data_as(i32), N.as_dp(N.f64(self.lo)),
                                      N.as_dp(N.f64(self.hi)), N.as_dp(rows), float(self.fixed_all.get("alpha", 1)),
                                      None if realisations is None else which.ctypes.data_as(i32), err, len(err))
         if not h:

@@ -451,7 +451,7 @@ class JointFit:
         return float(lnl[0]), float(chi2[0])
 
     # ------------------------------------------------------------------ best fits and chains (fitting.py, chains.py)
-    def _sampled_create(self, entry, q, realisations, kwargs, batch, which):
+    def _sampled_create(self, entry, q, realisations, kwargs, batch, which, shape=()):
         """``(lib, handle, refresh)`` of ``vk_fit_create_joint`` / ``vk_chain_create_joint`` (``entry``; with ``@`` names among the
         sampled or fixed parameters their ``_blocks`` forms, a row per block) for the sampled
         parameters ``q`` (the contract of ``fitting._Sampled.create``): one problem per row of ``batch``, against the joint data
@@ -494,7 +494,7 @@ class JointFit:
         ctxs = (C.c_void_p * len(engines))(*[e._ctx for e in engines])
         i32 = C.POINTER(C.c_int32)
         err = C.create_string_buffer(512)
-        h = getattr(lead._lib, entry)(ctxs, len(engines), handle, C.byref(opts), n_rows, len(cols), cols.ctypes.data_as(i32),
+        h = getattr(lead._lib, entry)(ctxs, len(engines), handle, C.byref(opts), n_rows, *shape, len(cols), cols.ctypes.data_as(i32),
                                       *extra, N.as_dp(N.f64(q.lo)), N.as_dp(N.f64(q.hi)), N.as_dp(rows),
                                       float(q.fixed_all.get("alpha", 1)),
                                       None if realisations is None else which.ctypes.data_as(i32), err, len(err))
@@ -537,6 +537,15 @@ class JointFit:
         return sample_chains(self, params, n_steps, walkers, seed, fixed, start, scatter, proposal, burn, thin, keep_chain, device,
                              kwargs, move=move, stretch_a=stretch_a, prior=prior, marginals=marginals,
                              autocorr=autocorr, temper=temper, predictive=predictive)
+
+    def nested_sampling(self, params, n_live=256, batch=32, steps=16, scale=None, seed=0, fixed=None, tol=1e-3, max_iter=None, n_iter=None,
+                        keep_dead=True, device=True, evaluate=None, **kwargs):
+        """Nested sampling of the joint lnL - one parameter vector for all blocks, or with ``"name@q"`` entries a value per
+        block, at most 10 sampled values in all -, block-diagonal or under the joint covariance.  Arguments and result as
+        ``CCFFit.nested_sampling`` (:mod:`victor_amd.nested`); the result keeps this joint fit alive."""
+        from .nested import nested_sampling
+        return nested_sampling(self, params, n_live, batch, steps, scale, seed, fixed, tol, max_iter, n_iter, keep_dead, device,
+                               evaluate, kwargs)
 
     @property
     def n_data(self):
@@ -612,6 +621,14 @@ class JointRealisations:
         return sample_chains(self.joint, params, n_steps, walkers, seed, fixed, start, scatter, proposal, burn, thin, keep_chain,
                              device, kwargs, realisations=self, move=move, stretch_a=stretch_a, prior=prior, marginals=marginals,
                              autocorr=autocorr, temper=temper, predictive=predictive)
+
+    def nested_sampling(self, params, n_live=256, batch=32, steps=16, scale=None, seed=0, fixed=None, tol=1e-3, max_iter=None, n_iter=None,
+                        keep_dead=True, device=True, evaluate=None, **kwargs):
+        """Nested sampling of EVERY joint realisation in lock step: one evidence and one posterior sample per joint mock.
+        Arguments and result as ``Realisations.nested_sampling``."""
+        from .nested import nested_sampling
+        return nested_sampling(self.joint, params, n_live, batch, steps, scale, seed, fixed, tol, max_iter, n_iter, keep_dead, device,
+                               evaluate, kwargs, realisations=self)
 
     def _eval(self, params, kwargs, which=None):
         joint = self.joint

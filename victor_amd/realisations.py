@@ -329,6 +329,16 @@ class Realisations:
         from .grid import grid_posterior
         return grid_posterior(self.fit, params, bins, ranges, fixed, prior, pairs, chunk, device, kwargs, realisations=self)
 
+    def nested_sampling(self, params, n_live=256, batch=32, steps=16, scale=None, seed=0, fixed=None, tol=1e-3, max_iter=None, n_iter=None,
+                        keep_dead=True, device=True, evaluate=None, **kwargs):
+        """Nested sampling of EVERY realisation, all of them in lock step (R = ``len(self)`` problems, one evidence and one
+        posterior sample per mock): on the GPU (``device=True``) or by the NumPy loop over :meth:`log_likelihood_pairs` that
+        defines the runs (``device=False``).  ``paired_model=True`` is honoured: a row is evaluated with the model of its own
+        mock.  Arguments and result as ``CCFFit.nested_sampling`` (:mod:`victor_amd.nested`)."""
+        from .nested import nested_sampling
+        return nested_sampling(self.fit, params, n_live, batch, steps, scale, seed, fixed, tol, max_iter, n_iter, keep_dead, device,
+                               evaluate, kwargs, realisations=self)
+
     def log_likelihood_pairs(self, params, which, **kwargs):
         """(lnL, chi2), each ``(n_points,)``: point p against realisation ``numbers[which[p]]`` only - the form an ensemble of
         independent per-mock chains needs.  The same bits as the matching entries of :meth:`log_likelihood`."""
