@@ -820,6 +820,54 @@ int vk_grid_result(vk_grid* h, double* ln_max, int64_t* arg_max, double* total, 
 const char* vk_grid_last_error(const vk_grid* h);
 void vk_grid_destroy(vk_grid* h);
 
+/* ---- Importance-sampled posteriors: the evidence, the effective sample size, moments and marginal histograms of every problem --
+ * from ONE shared sample.  G points drawn once from a proposal that covers every problem's posterior are evaluated once - against
+ * the context's data vector (one problem) or against EVERY realisation set on the context (R = n_real problems, the cross mode of
+ * vk_eval_realisations) - and reduced where the values are produced; (G, R) values never travel to the host.  The reduction is
+ * the grid's step (vk_grid_run above) generalised from lattice nodes to scattered points: what the lattice gave for free - the
+ * cells' run patterns, nodes looked up by index, no proposal density - the caller states.  victor_amd/importance.py states the
+ * definition in NumPy, vk_importance.h the accumulator index rules, the list walk and the terms, DESIGN.md section 7e the mapping.
+ *   columns[j]  row column (VK_P_*) of axis j, or VK_WALK_EPSILON, each once, 1 <= n_axes <= 10 (as vk_fit_create)
+ *   n_points    G, 1 .. 2^24: the points kept, in the order they were drawn
+ *   x, y        [G][n_axes] the points and their centred coordinates y = x - centre the moments use (finite)
+ *   eps_pow     [G] the caller's own eps^(-2/3) of every point when epsilon is sampled (NULL otherwise): a device row equals the
+ *               row the host forms (CCFFit._fit_rows) bit for bit, as with vk_grid_create
+ *   lno         [G] ln prior(x_g) - ln q(x_g), added to lnL once;  lno_prior [G] or NULL: lnpost of the prior's own problem,
+ *               which rides along as problem R and keeps a total alone
+ *   n_bins[j]   bins of axis j's histogram, 1 .. 1024: n_bins[j] + 2 cells (below the range, the bins, above it)
+ *   pair_bins[q]  bins per axis of pair q's two-dimensional histogram, 1 .. 128: pair_bins[q]^2 cells; at most 45 pairs
+ *   lists       [n_axes + n_pairs][G]: per list (the axes, then the pairs) and chunk c the chunk's segment starts at c chunk; it
+ *               names the chunk's points (g - c chunk) cell by cell, increasing inside a cell.  A point outside either range of a
+ *               pair is in none of the pair's cells
+ *   offsets     [chunks][cells + lists]: per chunk, list after list, one offset more than the list has cells: cell k of the list
+ *               holds entries off[k] .. off[k + 1] - 1 of the chunk's segment.  vk_is_create checks every index a kernel will
+ *               form: offsets that start at 0, never decrease and end inside the chunk's points, entries inside the chunk that
+ *               increase inside a cell
+ *   base_row, alpha, every_realisation, chunk: as vk_grid_create
+ * lnpost[g][r] = lnL[g][r] + lno[g], one rounded addition; a value that is not finite counts as -inf.  The chunks go in order and
+ * per chunk and problem the step is vk_grid_run's - the running maximum M, arg_max on a strict increase to the smallest g, every
+ * accumulator multiplied by exp(M - M') when M rises (the sum of squares twice, each product rounded), w = exp(lnpost - M) - with
+ * the additions ONE AT A TIME IN INCREASING g:  total += w;  sq += w w;  s1[j] += w y_j;  s2[j][k] += (w y_j) y_k, j <= k;  every
+ * histogram and pair cell += w over its list.  No pairwise or tree sums, no floating-point atomics: maxima, arg max and counts do
+ * not depend on the chunk, sums depend on it through rounding only, and two runs give the same bytes.
+ * vk_is_run(h, first, count), vk_is_rows(h, first, count, rows): as vk_grid_run and vk_grid_rows, over points for flat indices.
+ * vk_is_result, after a run has reached G, per problem r: ln_max, arg_max, n_finite, total, sq [R]; s1 [R][d]; s2
+ *   [R][d (d + 1) / 2], the packed upper triangle row by row; h1 [R][sum (n_bins[j] + 2)], axis after axis; h2
+ *   [R][sum pair_bins[q]^2];  prior_ln_max, prior_total: the two numbers of the prior's own problem, else 0.  Any may be NULL.
+ * Synchronous calls that own the context while they run.  On error the code is returned, vk_is_last_error gives the text,
+ * nothing stays in flight and the handle stays usable.  Refused (VK_E_ARG): what vk_grid_run refuses. */
+typedef struct vk_is vk_is;
+vk_is* vk_is_create(vk_ctx* ctx, const vk_eval_opts* opts, int32_t n_axes, const int32_t* columns, int64_t n_points, const double* x,
+                    const double* y, const double* eps_pow, const double* lno, const double* lno_prior, const int32_t* n_bins,
+                    int32_t n_pairs, const int32_t* pair_bins, const int32_t* lists, const int32_t* offsets, const double* base_row,
+                    double alpha, int32_t every_realisation, int32_t chunk, char* err, size_t errlen);
+int vk_is_run(vk_is* h, int64_t first, int64_t count);
+int vk_is_rows(vk_is* h, int64_t first, int32_t count, double* rows);
+int vk_is_result(vk_is* h, double* ln_max, int64_t* arg_max, int64_t* n_finite, double* total, double* sq, double* s1, double* s2,
+                 double* h1, double* h2, double* prior_ln_max, double* prior_total);
+const char* vk_is_last_error(const vk_is* h);
+void vk_is_destroy(vk_is* h);
+
 /* ---- nested sampling: the evidence and a posterior sample of the data vector or of every realisation ---------------------------
  * R problems of L live points each inside the box [lo, hi]; per iteration the K lowest live points of every problem die and K
  * walkers, each started at a surviving live point, take S constrained random-walk steps and replace them.  The handle is one of

@@ -213,6 +213,15 @@ SYMBOLS = {
     "vk_grid_result": (C.c_int, [_vp, _dp, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_int64), _dp, _dp, _dp, _dp, _dp, _dp]),
     "vk_grid_last_error": (C.c_char_p, [_vp]),
     "vk_grid_destroy": (None, [_vp]),
+    # importance-sampled posteriors: every problem's evidence, ESS, moments and histograms from one shared sample
+    "vk_is_create": (_vp, [_vp, _optp, C.c_int32, C.POINTER(C.c_int32), C.c_int64, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int32),
+                           C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp, C.c_double, C.c_int32,
+                           C.c_int32, C.c_char_p, C.c_size_t]),
+    "vk_is_run": (C.c_int, [_vp, C.c_int64, C.c_int64]),
+    "vk_is_rows": (C.c_int, [_vp, C.c_int64, C.c_int32, _dp]),
+    "vk_is_result": (C.c_int, [_vp, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "vk_is_last_error": (C.c_char_p, [_vp]),
+    "vk_is_destroy": (None, [_vp]),
     # nested sampling: R problems of L live points, K replaced per iteration by S constrained steps
     "vk_nested_create": (_vp, [_vp, _optp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.POINTER(C.c_int32),
                                _dp, _dp, _dp, C.c_double, C.POINTER(C.c_int32), C.c_char_p, C.c_size_t]),

@@ -389,6 +389,19 @@ class CCFFit(CCFModel):
         from .grid import grid_posterior
         return grid_posterior(self, params, bins, ranges, fixed, prior, pairs, chunk, device, kwargs)
 
+    def importance_posterior(self, params, q=None, n=16384, seed=0, fixed=None, prior=None, bins=64, ranges=None, pairs=None, chunk=None,
+                             min_ess=50.0, device=True, evaluate=None, sample=None, ln_proposal=None, **kwargs):
+        """The posterior of this fit's data vector from an importance sample of the proposal ``q`` (a
+        :class:`victor_amd.importance.GaussianProposal`; or the caller's own ``sample`` and ``ln_proposal``): the evidence with
+        its error, the effective sample size, the mean and covariance and marginal histograms, under the box of a cobaya
+        ``params`` block and an optional Gaussian ``prior``, in any dimension up to 10 - reduced on the GPU where the likelihoods
+        are produced (``vk_is_run``) or by the NumPy loop that defines them (``device=False``, over
+        :meth:`log_likelihood_batch`): :func:`victor_amd.importance.importance_posterior`, which documents the arguments.
+        Returns a :class:`victor_amd.importance.ImportancePosterior` with R = 1.  Runs on this fit's own context."""
+        from .importance import importance_posterior
+        return importance_posterior(self, params, q, n, seed, fixed, prior, bins, ranges, pairs, chunk, min_ess, device, evaluate,
+                                    sample, ln_proposal, kwargs)
+
     def nested_sampling(self, params, n_live=256, batch=32, steps=16, scale=None, seed=0, fixed=None, tol=1e-3, max_iter=None, n_iter=None,
                         keep_dead=True, device=True, evaluate=None, **kwargs):
         """Nested sampling of the fit's data vector over the uniform box of a cobaya ``params`` block: the evidence under the

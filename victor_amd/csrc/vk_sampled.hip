@@ -42,8 +42,11 @@
 //   vk_kernel_predictive.h the posterior-predictive sums (vk_chain_set_predictive): the hold kernel behind every step kernel, one
 //                        wave per row, which keeps each chain's theory vector, and the predict kernel behind every kept step, one
 //                        thread per (problem, entry), over the rules of vk_predictive.h (plain C++, likewise)
-//   vk_kernel_grid.h     grid posteriors (vk_grid_run; the section before the last of this file): rows, max, weight and accumulate kernels of
+//   vk_kernel_grid.h     grid posteriors (vk_grid_run; the third section from the end of this file): rows, max, weight and accumulate kernels of
 //                        a chunk of grid points, over the index rules and the step of vk_grid.h (plain C++, likewise)
+//   vk_kernel_importance.h importance-sampled posteriors (vk_is_run; the section behind the grid's): rows, max, weight and accumulate
+//                        kernels of a chunk of an uploaded sample, over the index rules, the list walk and the terms of
+//                        vk_importance.h (plain C++, likewise)
 //   vk_kernel_nested.h   nested sampling (vk_nested_begin; the last section of this file): the select kernel, one workgroup per
 //                        problem, and the step and commit kernels, one thread per replacement walker, over the order, the pick,
 //                        the constrained step and the commit of vk_nested_step.h (plain C++, likewise)
@@ -69,6 +72,7 @@
 #include "vk_kernel_hessian.h"
 #include "vk_kernel_fisher.h"
 #include "vk_kernel_grid.h"
+#include "vk_kernel_importance.h"
 #include "vk_kernel_nested.h"
 
 using namespace vk;
@@ -1975,6 +1979,295 @@ int vk_grid_result(vk_grid* f, double* ln_max, int64_t* arg_max, double* total, 
   }
   if (prior_ln_max) *prior_ln_max = f->prior.on ? run[R].m : 0.0;
   if (prior_total) *prior_total = f->prior.on ? tot[R] : 0.0;
+  f->err.clear();
+  return VK_OK;
+}
+
+}  // extern "C"
+
+// ---- importance-sampled posteriors: the evidence, effective sample size, moments and marginal histograms of every problem from --
+// one shared sample (include/victor_hip.h, vk_kernel_importance.h; the definition: victor_amd/importance.py, the index rules, the
+// list walk and the terms: vk_importance.h) --------------------------------------------------------------------------------------
+// An importance handle is a Sampled with ONE base row whose pending rows are a chunk of the uploaded sample: per chunk a rows
+// kernel, sampled_evaluate (the data-vector route with lnL, or enqueue_realisations in cross mode, [n][R]), then the max, weight
+// and accumulate kernels, all on the context's stream with no host synchronisation between chunks; vk_is_run waits once at its
+// end.  One allocation holds the sample, its lists and offsets, rows, workspace, the chunk's values and the accumulators.
+struct __attribute__((visibility("hidden"))) vk_is : Sampled {
+  int R = 1, chunk = 0, n_lists = 0, n_cells = 0, n_acc = 0, n1 = 0, n2 = 0;
+  bool eps = false, own = false;           // epsilon is sampled; the prior's own problem rides along
+  long long G = 0, n_chunks = 0;
+  int cell_off[vkis::kMaxLists + 1] = {};
+  long long done = 0;                      // points [0, done) are in the accumulators
+  vkgrid::Running* d_run = nullptr;        // [R + 1]: the problems', the prior's own
+  double *d_x = nullptr, *d_y = nullptr, *d_eps = nullptr, *d_lno = nullptr, *d_lnop = nullptr, *d_lnl = nullptr, *d_chi = nullptr;
+  double *d_wp = nullptr, *d_acc = nullptr;
+  int *d_list = nullptr, *d_off = nullptr;
+
+  void shape(int, const double*, const double*) { rows_max = (size_t)chunk; }
+  long long offsets_per_chunk() const { return (long long)n_cells + n_lists; }
+  void layout(Carve& c) {
+    const size_t n = (size_t)chunk, r = (size_t)R, g = (size_t)G;
+    c.take(d_run, r + 1);
+    c.take(d_base, VK_NPAR);
+    c.take(d_rows, n * VK_NPAR);
+    c.take(d_x, g * P);
+    c.take(d_y, g * P);
+    c.take(d_eps, eps ? g : 1);
+    c.take(d_lno, g);
+    c.take(d_lnop, own ? g : 1);
+    c.take(d_lnl, n * r);
+    c.take(d_chi, n * r);                  // the evaluation's chi-squares, then the chunk's weights (vk_is_weight_kernel)
+    c.take(d_wp, n);
+    c.take(d_th, workspace_doubles());
+    c.take(d_acc, (size_t)n_acc * (r + 1));
+    c.take(d_list, (size_t)n_lists * g);
+    c.take(d_off, (size_t)(n_chunks * offsets_per_chunk()));
+  }
+  int Rp() const { return own ? R + 1 : R; }
+};
+
+static IsArgs is_args(const vk_is* f) {
+  IsArgs a{};
+  a.d = f->P;
+  a.R = f->R;
+  a.Rp = f->Rp();
+  a.G = f->G;
+  a.x = f->d_x;
+  a.eps_pow = f->eps ? f->d_eps : nullptr;
+  a.base = f->d_base;
+  a.rows = f->d_rows;
+  for (int j = 0; j < vkis::kMaxP; ++j) a.col[j] = f->col[j];
+  a.alpha = f->alpha;
+  a.y = f->d_y;
+  a.lno = f->d_lno;
+  a.lnop = f->own ? f->d_lnop : nullptr;
+  a.lnl = f->d_lnl;
+  a.w = f->d_chi;
+  a.wp = f->d_wp;
+  a.run = f->d_run;
+  a.acc = f->d_acc;
+  a.n_acc = f->n_acc;
+  a.whole = vkis::whole(f->P);
+  a.n_lists = f->n_lists;
+  a.pr = 1;
+  while (a.pr < 64 && a.pr < a.Rp) a.pr *= 2;
+  a.list = f->d_list;
+  for (int l = 0; l <= f->n_lists; ++l) a.cell_off[l] = f->cell_off[l];
+  return a;
+}
+
+// may the handle run now: the context, and of the realisation route that the set on the context is the one it was made for
+static int is_ready(vk_is* f, const char* who) {
+  int rc = sampled_ready(f, who, "sample", true);
+  if (rc) return rc;
+  if (f->real && f->ctx->n_real != f->R)
+    return refused(f, std::string(who) + ": the context holds " + std::to_string(f->ctx->n_real) + " realisations, the sample was made for " +
+                          std::to_string(f->R));
+  if (f->real && f->ctx->n_sets > 0)
+    return refused(f, std::string(who) + ": model realisations are set on the context (vk_set_model_realisations): a point has one "
+                          "theory vector per realisation, and a shared sample evaluates every point once");
+  return VK_OK;
+}
+
+// the launches of points [first, end), chunk by chunk
+static int is_chunks(vk_is* f, long long first, long long end) {
+  IsArgs a = is_args(f);
+  int rc = VK_OK;
+  if (first == 0) rc = sampled_launch(f, vk_is_init_kernel, (long long)a.n_acc * a.Rp, kIsBlock, a);
+  for (long long g0 = first; g0 < end && rc == VK_OK; g0 += f->chunk) {
+    a.g0 = g0;
+    a.n = (int)std::min<long long>(f->chunk, end - g0);
+    a.off = f->d_off + (g0 / f->chunk) * f->offsets_per_chunk();
+    rc = sampled_launch(f, vk_is_rows_kernel, a.n, kIsBlock, a);
+    if (rc == VK_OK) rc = sampled_evaluate(f, a.n, f->d_lnl, f->d_chi);
+    if (rc == VK_OK) rc = sampled_launch(f, vk_is_max_kernel, (long long)((a.Rp + a.pr - 1) / a.pr) * kIsBlock, kIsBlock, a);
+    if (rc == VK_OK) rc = sampled_launch(f, vk_is_weight_kernel, (long long)a.n * a.Rp, kIsBlock, a);
+    if (rc == VK_OK) rc = sampled_launch(f, vk_is_accumulate_kernel, (long long)a.n_acc * a.Rp, kIsBlock, a);
+  }
+  if (rc) return rc;
+  VK_SAMPLED_HIP(f, hipStreamSynchronize(f->ctx->stream));
+  return VK_OK;
+}
+
+extern "C" {
+
+vk_is* vk_is_create(vk_ctx* ctx, const vk_eval_opts* opts, int32_t n_axes, const int32_t* columns, int64_t n_points, const double* x,
+                    const double* y, const double* eps_pow, const double* lno, const double* lno_prior, const int32_t* n_bins,
+                    int32_t n_pairs, const int32_t* pair_bins, const int32_t* lists, const int32_t* offsets, const double* base_row,
+                    double alpha, int32_t every_realisation, int32_t chunk, char* err, size_t errlen) {
+  auto bail = [&](const std::string& msg) -> vk_is* {
+    if (err && errlen) snprintf(err, errlen, "vk_is_create: %s", msg.c_str());
+    return nullptr;
+  };
+  if (!ctx || !opts || !columns || !x || !y || !lno || !n_bins || !lists || !offsets || !base_row || (n_pairs > 0 && !pair_bins))
+    return bail("NULL argument");
+  if (n_axes < 1 || n_axes > vkis::kMaxP) return bail("need 1 <= axes <= 10");
+  if (n_points < 1 || n_points > vkis::kMaxPoints) return bail("need 1 <= points <= 2^24");
+  if (chunk < 1 || chunk > vkis::kMaxChunk) return bail("need 1 <= chunk <= 65536");
+  if (n_pairs < 0 || n_pairs > vkis::kMaxPairs) return bail("need 0 <= pairs <= 45");
+  const long long G = n_points, n_chunks = (G + chunk - 1) / chunk;
+  const int n_lists = n_axes + n_pairs;
+  int cell_off[vkis::kMaxLists + 1] = {};
+  long long cells = 0, n1 = 0;
+  bool eps = false;
+  for (int j = 0; j < n_axes; ++j) {
+    if (n_bins[j] < 1 || n_bins[j] > vkis::kMaxBins) return bail("axis " + std::to_string(j) + " needs 1 <= bins <= 1024");
+    cell_off[j] = (int)cells;
+    cells += n_bins[j] + 2;                // below, the bins, above
+    if (columns[j] == VK_WALK_EPSILON) eps = true;
+  }
+  n1 = cells;
+  for (int q = 0; q < n_pairs; ++q) {
+    if (pair_bins[q] < 1 || pair_bins[q] > vkis::kMaxBins2) return bail("pair " + std::to_string(q) + " needs 1 <= bins <= 128 per axis");
+    cell_off[n_axes + q] = (int)cells;
+    cells += (long long)pair_bins[q] * pair_bins[q];
+  }
+  cell_off[n_lists] = (int)cells;
+  if (eps && !eps_pow) return bail("a sampled epsilon needs eps_pow, the host's eps^(-2/3) of every point");
+  const long long per_chunk = cells + n_lists;
+  if (n_chunks * per_chunk > vkis::kMaxOffsets) return bail("too many cell offsets (chunks x cells): at most 2^27, take a larger chunk or fewer cells");
+  for (long long g = 0; g < G; ++g) {
+    for (int j = 0; j < n_axes; ++j)
+      if (!__builtin_isfinite(x[g * n_axes + j]) || !__builtin_isfinite(y[g * n_axes + j]))
+        return bail("point " + std::to_string(g) + " is not finite in axis " + std::to_string(j));
+    if (__builtin_isnan(lno[g]) || (lno_prior && __builtin_isnan(lno_prior[g]))) return bail("lno of point " + std::to_string(g) + " is NaN");
+  }
+  // every index a kernel forms: a list entry inside its chunk, a cell's end inside the chunk's count, offsets that never decrease
+  for (long long c = 0; c < n_chunks; ++c) {
+    const long long g0 = c * chunk;
+    const int n = (int)std::min<long long>(chunk, G - g0);
+    for (int l = 0; l < n_lists; ++l) {
+      long long where = 0;
+      const int bad = vkis::check_list(lists + (size_t)l * G + g0, offsets + c * per_chunk + cell_off[l] + l, cell_off[l + 1] - cell_off[l], n, &where);
+      if (bad == 1)
+        return bail("offset " + std::to_string(where) + " of list " + std::to_string(l) + " in chunk " + std::to_string(c) +
+                    " is wrong: the offsets start at 0, never decrease and end inside the chunk's " + std::to_string(n) + " points");
+      if (bad == 2)
+        return bail("entry " + std::to_string(where) + " of list " + std::to_string(l) + " in chunk " + std::to_string(c) +
+                    " is outside its chunk of " + std::to_string(n) + " points, or not after the entry before it in its cell");
+    }
+  }
+  int R = 1;
+  if (every_realisation) {
+    if (ctx->n_real <= 0 || !ctx->d_real) return bail("no realisations are set on the context (vk_set_realisations)");
+    if (ctx->n_sets > 0)
+      return bail("model realisations are set on the context (vk_set_model_realisations): a point has one theory vector per "
+                  "realisation, and a shared sample evaluates every point once");
+    if (check_real_lds(ctx) != VK_OK) return bail(ctx->err);
+    R = ctx->n_real;
+  }
+  const long long n_acc = vkis::whole(n_axes) + cells;
+  if (n_acc * (long long)(R + 1) > (1LL << 31) * (kIsBlock / 2)) return bail("too many accumulators for one launch (accumulators x problems)");
+  const double inf = __builtin_inf();
+  double lo[vkis::kMaxP], hi[vkis::kMaxP];                     // (a sample has points, not a box)
+  for (int j = 0; j < vkis::kMaxP; ++j) lo[j] = -inf, hi[j] = inf;
+  vk_is* f = sampled_create<vk_is>("vk_is_create", "sample", &ctx, 1, false, nullptr, opts, 1, n_axes, columns, nullptr, lo, hi, base_row,
+                                   alpha, nullptr, err, errlen, [&](vk_is* h) {
+    h->R = R;
+    h->real = every_realisation != 0;
+    h->max_which = h->real ? R - 1 : -1;
+    h->chunk = chunk;
+    h->G = G;
+    h->n_chunks = n_chunks;
+    h->n_lists = n_lists;
+    h->n_cells = (int)cells;
+    h->n1 = (int)n1;
+    h->n2 = (int)(cells - n1);
+    h->n_acc = (int)n_acc;
+    h->eps = eps;
+    h->own = lno_prior != nullptr;
+    for (int l = 0; l <= n_lists; ++l) h->cell_off[l] = cell_off[l];
+  });
+  if (!f) return nullptr;
+  auto up = [&](void* dst, const void* src, size_t bytes) { return hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess; };
+  const size_t g = (size_t)G;
+  bool ok = up(f->d_x, x, g * n_axes * sizeof(double)) && up(f->d_y, y, g * n_axes * sizeof(double)) && up(f->d_lno, lno, g * sizeof(double));
+  if (ok && eps) ok = up(f->d_eps, eps_pow, g * sizeof(double));
+  if (ok && lno_prior) ok = up(f->d_lnop, lno_prior, g * sizeof(double));
+  if (ok) ok = up(f->d_list, lists, (size_t)n_lists * g * sizeof(int)) && up(f->d_off, offsets, (size_t)(n_chunks * per_chunk) * sizeof(int));
+  if (!ok) {
+    (void)hipGetLastError();
+    sampled_destroy(f);
+    return bail("upload failed");
+  }
+  return f;
+}
+
+const char* vk_is_last_error(const vk_is* f) { return f ? f->err.c_str() : ""; }
+
+void vk_is_destroy(vk_is* f) {
+  if (f) sampled_destroy(f);
+}
+
+int vk_is_run(vk_is* f, int64_t first, int64_t count) {
+  if (!f) return VK_E_ARG;
+  int rc = is_ready(f, "vk_is_run");
+  if (rc) return rc;
+  const long long G = f->G;
+  if (first < 0 || first >= G || count < 1) return refused(f, "vk_is_run: need 0 <= first < points and count >= 1");
+  if (first % f->chunk) return refused(f, "vk_is_run: first must be a multiple of the chunk (" + std::to_string(f->chunk) + ")");
+  if (first != 0 && first != f->done)
+    return refused(f, "vk_is_run: the chunks go in order: first must be 0 (a new run) or " + std::to_string(f->done) +
+                          " (where the last call ended)");
+  const long long end = count > G - first ? G : first + count;
+  if (end != G && count % f->chunk) return refused(f, "vk_is_run: count must be whole chunks, or reach the end of the sample");
+  VK_SAMPLED_HIP(f, hipSetDevice(f->ctx->device));
+  f->done = 0;
+  rc = is_chunks(f, first, end);
+  if (rc != VK_OK) return sampled_abort(f, rc);
+  f->done = end;
+  f->err.clear();
+  return VK_OK;
+}
+
+int vk_is_rows(vk_is* f, int64_t first, int32_t count, double* rows) {
+  if (!f) return VK_E_ARG;
+  if (!rows) return refused(f, "vk_is_rows: NULL argument");
+  int rc = is_ready(f, "vk_is_rows");
+  if (rc) return rc;
+  if (first < 0 || count < 1 || count > f->chunk || first > f->G - count)
+    return refused(f, "vk_is_rows: need 1 <= count <= chunk and 0 <= first <= points - count");
+  VK_SAMPLED_HIP(f, hipSetDevice(f->ctx->device));
+  IsArgs a = is_args(f);
+  a.g0 = first;
+  a.n = count;
+  rc = sampled_launch(f, vk_is_rows_kernel, a.n, kIsBlock, a);
+  if (rc == VK_OK) rc = sampled_home(f, {{rows, f->d_rows, (size_t)count * VK_NPAR * sizeof(double)}}, true);
+  if (rc != VK_OK) return sampled_abort(f, rc);
+  VK_SAMPLED_HIP(f, hipStreamSynchronize(f->ctx->stream));
+  f->err.clear();
+  return VK_OK;
+}
+
+int vk_is_result(vk_is* f, double* ln_max, int64_t* arg_max, int64_t* n_finite, double* total, double* sq, double* s1, double* s2,
+                 double* h1, double* h2, double* prior_ln_max, double* prior_total) {
+  if (!f) return VK_E_ARG;
+  if (f->done != f->G) return refused(f, "vk_is_result: the run has reached " + std::to_string(f->done) + " of " + std::to_string(f->G) + " points");
+  const size_t R = (size_t)f->R, Rp = (size_t)f->Rp(), A = (size_t)f->n_acc;
+  const int d = f->P, T = d * (d + 1) / 2, W = vkis::whole(d);
+  VK_SAMPLED_HIP(f, hipSetDevice(f->ctx->device));
+  std::vector<vkgrid::Running> run(Rp);
+  std::vector<double> acc(A * Rp);
+  int rc = sampled_home(f, {{run.data(), f->d_run, Rp * sizeof(vkgrid::Running)}, {acc.data(), f->d_acc, A * Rp * sizeof(double)}});
+  if (rc) return rc;
+  auto at = [&](size_t a, size_t r) { return acc[a * Rp + r]; };
+  for (size_t r = 0; r < R; ++r) {
+    if (ln_max) ln_max[r] = run[r].m;
+    if (arg_max) arg_max[r] = run[r].arg;
+    if (n_finite) n_finite[r] = run[r].n_finite;
+    if (total) total[r] = at(vkis::kTotal, r);
+    if (sq) sq[r] = at(vkis::kSq, r);
+    if (s1)
+      for (int j = 0; j < d; ++j) s1[r * d + j] = at(vkis::first(j), r);
+    if (s2)
+      for (int t = 0; t < T; ++t) s2[r * T + t] = at(vkis::kFirst + d + t, r);
+    if (h1)
+      for (int c = 0; c < f->n1; ++c) h1[r * f->n1 + c] = at(W + c, r);
+    if (h2)
+      for (int c = 0; c < f->n2; ++c) h2[r * f->n2 + c] = at(W + f->n1 + c, r);
+  }
+  if (prior_ln_max) *prior_ln_max = f->own ? run[R].m : 0.0;
+  if (prior_total) *prior_total = f->own ? at(vkis::kTotal, R) : 0.0;
   f->err.clear();
   return VK_OK;
 }

@@ -1,0 +1,675 @@
+"""Importance-sampled posteriors: ``CCFFit.importance_posterior`` and ``Realisations.importance_posterior`` - the evidence, the
+effective sample size, the moments and the marginal histograms of the data vector (R = 1) or of EVERY realisation (R =
+``len(rs)``) from ONE shared sample of a proposal that covers every problem's posterior, reduced where the likelihoods are
+produced (``vk_is_run``, ``include/victor_hip.h``).
+
+A point's theory vector is computed once and compared with every realisation (the cross mode of ``Realisations.log_likelihood``),
+so R mocks cost G theory evaluations - the grid's economy (:mod:`victor_amd.grid`) without its limit of two to four axes and
+without its nodes where the posterior is empty.  Gaussian priors work in any dimension a handle allows (d <= 10); there is no
+burn-in and no R-hat, and the effective sample size says directly how good the proposal - a Laplace covariance, say - is for
+each mock.
+
+**The definition** (:func:`run_definition` / :func:`step_definition`; ``device=False`` runs it over ``log_likelihood_batch`` /
+``Realisations.log_likelihood`` or an ``evaluate`` callable, ``device=True`` reproduces it in kernels).
+
+1. *The sample.*  ``z = default_rng([seed, 0]).standard_normal((n, d))`` and ``x = mean + z @ L.T``, ``L`` the Cholesky factor of
+   the proposal covariance; with ``dof`` every row of ``z`` is first scaled by ``sqrt(dof / chi2)``, ``chi2 = default_rng([seed,
+   1]).chisquare(dof, n)`` (a multivariate Student-t).  ``ln q`` is the closed form of the UNTRUNCATED density, in float64 on the
+   host.  Points outside the prior box are dropped on the host, in order: ``n_drawn`` counts all of them, ``n_inside = G`` is what
+   remains, and flat index g runs over the kept points.  No truncation constant of q is needed: a dropped point has weight 0 and
+   still counts in ``n_drawn``.
+2. *Host-side arrays, shared by every problem.*  ``lno[g] = ln prior(x_g) - ln q(x_g)``, with ``ln prior`` the resolved Gaussian
+   prior's value (:mod:`victor_amd.priors`: no normalisation constant) or ``-sum_j log(hi_j - lo_j)`` without a prior; ``y = x -
+   mean_q``, the centred coordinates the moments use; with epsilon sampled libm's ``eps^(-2/3)`` per point, so that device rows
+   equal ``CCFFit._fit_rows`` rows bit for bit; the slot of every point in every 1-D histogram (``bins + 2`` slots: below the
+   range, the bins, above it) and its cell in every pair's histogram, by :func:`victor_amd.marginals.slots` / ``cells`` - one
+   binning rule, ranges default to the box, a pair has ``min(bins_a, bins_b, 128)`` bins per axis and holds the points inside
+   both ranges; and per chunk and axis or pair the chunk's points LISTED BY CELL in increasing g, with the cells' offsets
+   (:class:`Lists`).
+3. *The step.*  The chunks ``[c chunk, min((c + 1) chunk, G))`` go through in order.  Per chunk and problem r the step is the
+   grid's, with the same rounding rules (no fused multiply-add): ``lnpost = lnl + lno[g]``, one addition, a value that is not
+   finite counts as -inf; the running maximum M, ``arg_max`` moving on a strict increase to the smallest g; when M rises every
+   accumulator is multiplied by ``f = exp(M - M')`` - the sum of squares by f twice, each product rounded -; ``w = exp(lnpost -
+   M)``; then the additions run ONE AT A TIME IN INCREASING g: ``total += w``, ``sq += w w``, ``s1[j] += w y_j``, ``s2[j][k] +=
+   (w y_j) y_k`` for j <= k, and each histogram slot and pair cell ``+= w`` over its list.  So maxima, arg max and counts do
+   not depend on ``chunk``, sums depend on it through rounding only, and two runs give the same bytes.
+4. *The prior's own problem.*  Under a prior ``lnpost = lno[g]`` (its total only) rides along as problem R, as in the grid: it
+   normalises the prior over the box, by the same sample.  ``ln_evidence = (ln_max + log total) - (prior_ln_max + log
+   prior_total)`` with a prior, ``ln_max + log total - log n_drawn`` without one.
+5. *The read-out* (:class:`ImportancePosterior`, host, both routes alike).  ``ess = total^2 / sq``; ``max_weight_share = 1 /
+   total`` (the largest weight is 1); ``ln_evidence_error = sqrt(sq / total^2 - 1 / n_drawn)``; mean and covariance from ``s1``,
+   ``s2`` and the centre; histograms through the reader of :mod:`victor_amd.marginals`; ``outside_mass`` from the below and above
+   slots; ``status``: ``OK``, ``LOW_ESS`` (``ess < min_ess``), ``NO_FINITE`` (no point was finite: evidence -inf, no NaN in any
+   sum).
+"""
+
+import ctypes as C
+import math
+
+import numpy as np
+
+from . import _native as N
+from .fitting import _Sampled
+from .grid import MAX_CHUNK, default_chunk
+from .marginals import Marginals, cells, slots
+from .priors import tri
+from .utils import InputError
+
+MAX_AXES = 10
+MAX_BINS = 1024          # vkis::kMaxBins
+MAX_BINS2 = 128          # ... of an axis of a pair
+MAX_PAIRS = 45
+MAX_POINTS = 1 << 24     # vkis::kMaxPoints
+MAX_OFFSETS = 1 << 27    # vkis::kMaxOffsets
+
+
+class GaussianProposal:
+    """The shared proposal: a multivariate normal over ``names`` with ``mean`` (d,) and ``cov`` (d, d), or with ``dof=k`` the
+    multivariate Student-t of k degrees of freedom with that location and scale matrix (heavier tails)."""
+
+    def __init__(self, names, mean, cov, dof=None):
+        if isinstance(names, str):
+            names = [names]
+        self.names = [str(n) for n in names]
+        d = len(self.names)
+        if d < 1 or len(set(self.names)) != d:
+            raise InputError("GaussianProposal: names must be different parameters, at least one")
+        self.mean = np.atleast_1d(np.asarray(mean, dtype=np.float64))
+        self.cov = np.atleast_2d(np.asarray(cov, dtype=np.float64))
+        if self.mean.shape != (d,) or not np.all(np.isfinite(self.mean)):
+            raise InputError(f"GaussianProposal: mean must hold {d} finite values, one per name")
+        if self.cov.shape != (d, d) or not np.all(np.isfinite(self.cov)) or not np.allclose(self.cov, self.cov.T, rtol=1e-12, atol=0.0):
+            raise InputError(f"GaussianProposal: cov must be a finite symmetric ({d}, {d}) matrix")
+        self.cov = 0.5 * (self.cov + self.cov.T)
+        try:
+            self.chol = np.linalg.cholesky(self.cov)
+        except np.linalg.LinAlgError:
+            raise InputError("GaussianProposal: cov is not positive definite") from None
+        if dof is not None and (isinstance(dof, bool) or not np.isfinite(dof) or not dof > 0):
+            raise InputError(f"GaussianProposal: dof must be None or a number > 0, not {dof!r}")
+        self.dof = None if dof is None else float(dof)
+
+    def __repr__(self):
+        return f"GaussianProposal({self.names}, mean={self.mean.tolist()}, dof={self.dof})"
+
+    @classmethod
+    def from_fits(cls, bf, lap=None, inflate=2.0, dof=None):
+        """The proposal pooled over the converged problems of a :class:`victor_amd.fitting.BestFit`: the mean of their best fits,
+        and for covariance their scatter (if more than one) plus the mean of ``lap.cov`` over the same problems (a
+        :class:`victor_amd.laplace.Laplace`, if given; its problems without a finite covariance are left out), times ``inflate``."""
+        ok = np.asarray(bf.status) == bf.CONVERGED
+        if not np.any(ok):
+            raise InputError("GaussianProposal.from_fits: no problem of the best fit converged")
+        if not np.isfinite(inflate) or not inflate > 0:
+            raise InputError(f"GaussianProposal.from_fits: inflate must be > 0, not {inflate!r}")
+        x = np.asarray(bf.x, dtype=np.float64)[ok]
+        d = x.shape[1]
+        cov = np.zeros((d, d))
+        if len(x) > 1:
+            cov = cov + np.atleast_2d(np.cov(x, rowvar=False))
+        if lap is not None:
+            if list(lap.names) != list(bf.names) or len(lap.cov) != len(bf.x):
+                raise InputError("GaussianProposal.from_fits: lap must be the Laplace of the same best fit")
+            c = np.asarray(lap.cov, dtype=np.float64)[ok]
+            c = c[np.all(np.isfinite(c), axis=(1, 2))]
+            if not len(c):
+                raise InputError("GaussianProposal.from_fits: no converged problem has a finite Laplace covariance")
+            cov = cov + c.mean(axis=0)
+        if not np.any(cov):
+            raise InputError("GaussianProposal.from_fits: one problem and no lap: nothing gives a covariance")
+        return cls(bf.names, x.mean(axis=0), float(inflate) * cov, dof)
+
+    def ordered(self, who, names):
+        """``(mean, chol)`` in the order of the sampled ``names``: the proposal names exactly them."""
+        if set(self.names) != set(names):
+            raise InputError(f"{who}: the proposal names {self.names}, the sampled parameters are {list(names)}")
+        at = [self.names.index(n) for n in names]
+        cov = self.cov[np.ix_(at, at)]
+        return self.mean[at], np.linalg.cholesky(cov)
+
+    @staticmethod
+    def draw(mean, chol, dof, n, seed):
+        """(n, d) points: rule 1 of the module docstring."""
+        z = np.random.default_rng([seed, 0]).standard_normal((n, len(mean)))
+        if dof is not None:
+            chi2 = np.random.default_rng([seed, 1]).chisquare(dof, n)
+            z = z * np.sqrt(dof / chi2)[:, None]
+        return mean + z @ chol.T
+
+    @staticmethod
+    def ln_density(x, mean, chol, dof):
+        """(n,) ln q of the untruncated density at ``x`` (n, d)."""
+        d = len(mean)
+        z = np.linalg.solve(chol, (np.asarray(x, dtype=np.float64) - mean).T)
+        q = np.sum(z * z, axis=0)
+        ln_det = float(np.sum(np.log(np.diag(chol))))
+        if dof is None:
+            return -0.5 * q - ln_det - 0.5 * d * math.log(2.0 * math.pi)
+        return (math.lgamma(0.5 * (dof + d)) - math.lgamma(0.5 * dof) - 0.5 * d * math.log(dof * math.pi) - ln_det
+                - 0.5 * (dof + d) * np.log1p(q / dof))
+
+
+class Layout:
+    """The histograms of a call: ``names``; ``n_bins`` (d,); ``a``, ``b`` the ranges and ``lo``, ``hi`` the prior box; ``edges[j]``;
+    ``pairs`` the (ja < jb) index pairs, ``pair_names`` as the caller wrote them and ``pair_bins`` their bins per axis;
+    ``cell_off`` (d + n_pairs + 1,): the first cell of every list - the axes (``n_bins + 2`` cells each), then the pairs."""
+
+    def __init__(self, names, n_bins, a, b, lo, hi, pairs, pair_names):
+        self.names, self.n_bins = list(names), [int(n) for n in n_bins]
+        self.a, self.b, self.lo, self.hi = (np.asarray(v, dtype=np.float64) for v in (a, b, lo, hi))
+        self.edges = [np.linspace(self.a[j], self.b[j], n + 1) for j, n in enumerate(self.n_bins)]
+        self.pairs, self.pair_names = list(pairs), list(pair_names)
+        self.pair_bins = [min(self.n_bins[i], self.n_bins[j], MAX_BINS2) for i, j in self.pairs]
+        counts = [n + 2 for n in self.n_bins] + [m * m for m in self.pair_bins]
+        self.cell_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+
+    @property
+    def d(self):
+        return len(self.names)
+
+    @property
+    def n_lists(self):
+        return self.d + len(self.pairs)
+
+    @property
+    def n1(self):
+        return int(self.cell_off[self.d])
+
+    @property
+    def n2(self):
+        return int(self.cell_off[-1] - self.cell_off[self.d])
+
+    def cells_of(self, x):
+        """(n_lists, n) the cell of every point of ``x`` (n, d) in every list: the slot 0 .. bins + 1 of an axis, the cell of a
+        pair or -1 outside either of its ranges."""
+        out = np.empty((self.n_lists, len(x)), dtype=np.int64)
+        for j in range(self.d):
+            out[j] = slots(x[:, j], self.a[j], self.b[j], self.n_bins[j])
+        for q, (ja, jb) in enumerate(self.pairs):
+            out[self.d + q] = cells(x[:, ja], self.a[ja], self.b[ja], x[:, jb], self.a[jb], self.b[jb], self.pair_bins[q])
+        return out
+
+
+def resolve_layout(who, names, lo, hi, bins, ranges, pairs):
+    """The :class:`Layout` of the arguments ``bins``, ``ranges``, ``pairs`` against the sampled ``names`` with box ``lo``, ``hi``;
+    every refusal an ``InputError``."""
+    names = list(names)
+    given = dict(bins) if isinstance(bins, dict) else {n: bins for n in names}
+    if set(given) != set(names):
+        raise InputError(f"{who}: bins names {sorted(set(given) ^ set(names))}: a dict gives every sampled parameter, and only those, "
+                         f"a count ({names})")
+    n_bins = []
+    for n in names:
+        v = given[n]
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or int(v) != v or not 1 <= int(v) <= MAX_BINS:
+            raise InputError(f"{who}: bins of {n} must be an integer in 1 .. {MAX_BINS}, not {v!r}")
+        n_bins.append(int(v))
+    a, b = np.array(lo, dtype=np.float64), np.array(hi, dtype=np.float64)
+    for n, r in dict(ranges or {}).items():
+        if n not in names:
+            raise InputError(f"{who}: ranges names {n}, which is not sampled ({names})")
+        j = names.index(n)
+        try:
+            ra, rb = float(r[0]), float(r[1])
+        except (TypeError, ValueError, IndexError):
+            raise InputError(f"{who}: the range of {n} must be a pair (a, b)") from None
+        if not (np.isfinite(ra) and np.isfinite(rb) and ra < rb):
+            raise InputError(f"{who}: the range of {n} needs finite a < b, not ({ra}, {rb})")
+        if ra < lo[j] or rb > hi[j]:
+            raise InputError(f"{who}: the range of {n} ({ra}, {rb}) leaves its prior box [{lo[j]}, {hi[j]}]")
+        a[j], b[j] = ra, rb
+    index, pair_names = [], []
+    for p in pairs or []:
+        try:
+            n1, n2 = p
+        except (TypeError, ValueError):
+            raise InputError(f"{who}: pairs must be a list of name pairs") from None
+        if n1 not in names or n2 not in names or n1 == n2:
+            raise InputError(f"{who}: the pair ({n1}, {n2}) must name two different sampled parameters ({names})")
+        j, k = sorted((names.index(n1), names.index(n2)))
+        if (j, k) in index:
+            raise InputError(f"{who}: the pair ({n1}, {n2}) is given twice")
+        index.append((j, k))
+        pair_names.append((n1, n2))
+    if len(index) > MAX_PAIRS:
+        raise InputError(f"{who}: at most {MAX_PAIRS} pairs, not {len(index)}")
+    return Layout(names, n_bins, a, b, lo, hi, index, pair_names)
+
+
+class Sample:
+    """The kept points of a call and what every problem shares: ``x`` (G, d); ``centre`` (d,) and ``y = x - centre``; ``lno``
+    (G,); ``lnop`` (G,) the prior's own lnpost, or None without a prior; ``n_drawn``; ``G = n_inside``."""
+
+    def __init__(self, x, centre, lnq, n_drawn, lo, hi, prior):
+        self.x = np.ascontiguousarray(x, dtype=np.float64)
+        self.centre = np.asarray(centre, dtype=np.float64)
+        self.y = np.ascontiguousarray(self.x - self.centre)
+        self.n_drawn, self.G = int(n_drawn), len(self.x)
+        lnq = np.asarray(lnq, dtype=np.float64)
+        if prior is not None:
+            self.lno = prior.lnprior(self.x) - lnq
+            self.lnop = self.lno
+        else:
+            self.lno = -np.sum(np.log(np.asarray(hi, dtype=np.float64) - np.asarray(lo, dtype=np.float64))) - lnq
+            self.lnop = None
+        self.lno = np.ascontiguousarray(self.lno)
+
+
+class Lists:
+    """Rule 2's lists: ``entries`` (n_lists, G) int32 - list l's segment of chunk c starts at ``c chunk`` and names the chunk's
+    points (g - c chunk) cell by cell, in increasing g inside a cell - and ``offsets`` (n_chunks, cells + n_lists) int32: per
+    chunk, list after list, one offset more than the list has cells."""
+
+    def __init__(self, layout, x, chunk):
+        G = len(x)
+        self.chunk, self.n_chunks = int(chunk), -(-G // int(chunk))
+        per = int(layout.cell_off[-1]) + layout.n_lists
+        if self.n_chunks * per > MAX_OFFSETS:
+            raise InputError(f"importance_posterior: {self.n_chunks} chunks x {per} cell offsets are more than 2^27: take a larger "
+                             "chunk or fewer bins and pairs")
+        self.entries = np.zeros((layout.n_lists, G), dtype=np.int32)
+        self.offsets = np.zeros((self.n_chunks, per), dtype=np.int32)
+        where = layout.cells_of(x)
+        for c in range(self.n_chunks):
+            g0 = c * self.chunk
+            for l in range(layout.n_lists):
+                s = where[l, g0:g0 + self.chunk]
+                inside = np.flatnonzero(s >= 0)
+                order = inside[np.argsort(s[inside], kind="stable")]             # by cell, increasing g inside a cell
+                self.entries[l, g0:g0 + len(order)] = order
+                K = int(layout.cell_off[l + 1] - layout.cell_off[l])
+                at = int(layout.cell_off[l]) + l
+                self.offsets[c, at + 1:at + K + 1] = np.cumsum(np.bincount(s[inside], minlength=K))
+
+    def members(self, layout, c, l):
+        """``(entries of the chunk's segment, offsets of list l's cells)``."""
+        at = int(layout.cell_off[l]) + l
+        K = int(layout.cell_off[l + 1] - layout.cell_off[l])
+        g0 = c * self.chunk
+        return self.entries[l, g0:g0 + self.chunk], self.offsets[c, at:at + K + 1]
+
+
+class Sums:
+    """What a run returns per problem (the arrays of ``vk_is_result``): ``ln_max``, ``arg_max``, ``n_finite``, ``total``, ``sq``
+    (R,); ``s1`` (R, d); ``s2`` (R, d (d + 1) / 2), the packed upper triangle; ``h1`` (R, sum (bins_j + 2)); ``h2`` (R, sum
+    m_q^2)."""
+
+    def __init__(self, layout, R):
+        d = layout.d
+        self.ln_max = np.full(R, -np.inf)
+        self.arg_max = np.full(R, -1, dtype=np.int64)
+        self.n_finite = np.zeros(R, dtype=np.int64)
+        self.total, self.sq = np.zeros(R), np.zeros(R)
+        self.s1, self.s2 = np.zeros((R, d)), np.zeros((R, d * (d + 1) // 2))
+        self.h1, self.h2 = np.zeros((R, layout.n1)), np.zeros((R, layout.n2))
+
+
+def _add_in_order(acc, terms):
+    """``acc`` (R,) plus the rows of ``terms`` (n, R), one addition at a time in the rows' order (``np.add.accumulate`` is that
+    loop)."""
+    if not len(terms):
+        return acc
+    return np.add.accumulate(np.concatenate([acc[None, :], terms], axis=0), axis=0)[-1]
+
+
+def step_definition(layout, lists, c, y, acc, g0, lnpost, total_only=False):
+    """Rule 3 of the module docstring for chunk ``c``: ``lnpost`` (n, R) of the points ``g0 .. g0 + n - 1``, whose centred
+    coordinates are ``y`` (n, d), into the :class:`Sums` ``acc``, in place."""
+    lnpost = np.asarray(lnpost, dtype=np.float64)
+    lnpost = np.where(np.isfinite(lnpost), lnpost, -np.inf)
+    acc.n_finite += np.count_nonzero(lnpost > -np.inf, axis=0)
+    cmax = lnpost.max(axis=0)
+    carg = g0 + np.argmax(lnpost, axis=0)                        # (the first of equal maxima)
+    up = cmax > acc.ln_max
+    with np.errstate(invalid="ignore"):
+        f = np.where(up, np.exp(acc.ln_max - cmax), 1.0)
+    acc.arg_max = np.where(up, carg, acc.arg_max)
+    acc.ln_max = np.where(up, cmax, acc.ln_max)
+    acc.total = acc.total * f                                    # (a factor of 1.0 changes no bit)
+    acc.sq = (acc.sq * f) * f
+    acc.s1, acc.s2, acc.h1, acc.h2 = acc.s1 * f[:, None], acc.s2 * f[:, None], acc.h1 * f[:, None], acc.h2 * f[:, None]
+    live = acc.ln_max > -np.inf
+    if not np.any(live):
+        return
+    with np.errstate(invalid="ignore"):
+        w = np.where(live, np.exp(lnpost - acc.ln_max), 0.0)
+    acc.total = _add_in_order(acc.total, w)
+    if total_only:
+        return
+    d = layout.d
+    acc.sq = _add_in_order(acc.sq, w * w)
+    for j in range(d):
+        wy = w * y[:, j, None]
+        acc.s1[:, j] = _add_in_order(acc.s1[:, j], wy)
+        for k in range(j, d):
+            acc.s2[:, tri(d, j, k)] = _add_in_order(acc.s2[:, tri(d, j, k)], wy * y[:, k, None])
+    for l in range(layout.n_lists):
+        entries, off = lists.members(layout, c, l)
+        h, base = (acc.h1, int(layout.cell_off[l])) if l < d else (acc.h2, int(layout.cell_off[l]) - layout.n1)
+        for k in np.flatnonzero(np.diff(off)):
+            h[:, base + k] = _add_in_order(h[:, base + k], w[entries[off[k]:off[k + 1]]])
+
+
+def run_definition(layout, sample, lists, R, values):
+    """The definition: ``values(x)`` gives lnL ``(n, R)`` (or ``(n,)``: R = 1) at the points ``x`` (n, d) of a chunk; ``R`` None:
+    whatever the first chunk returns.  Returns ``(Sums, the prior's own Sums or None)``."""
+    acc = None
+    pacc = Sums(layout, 1) if sample.lnop is not None else None
+    chunk = lists.chunk
+    for c in range(lists.n_chunks):
+        g0 = c * chunk
+        x, y, lno = sample.x[g0:g0 + chunk], sample.y[g0:g0 + chunk], sample.lno[g0:g0 + chunk]
+        lnl = np.asarray(values(x), dtype=np.float64)
+        lnl = lnl.reshape(len(x), -1 if R is None else R)
+        if acc is None:
+            R = lnl.shape[1]
+            acc = Sums(layout, R)
+        if pacc is not None:
+            step_definition(layout, lists, c, y, pacc, g0, sample.lnop[g0:g0 + chunk, None], total_only=True)
+        step_definition(layout, lists, c, y, acc, g0, lnl + lno[:, None])
+    return acc, pacc
+
+
+class ImportancePosterior:
+    """The posterior of R problems from one shared sample.
+
+    ``names``; ``n_problems``; ``n_drawn``, ``n_inside`` (the points kept: inside the prior box) and ``n_finite`` (R,);
+    ``chunk``, ``n_chunks`` (what the sums' rounding depends on); ``ln_max`` (R,) the largest lnpost = lnL + ln prior - ln q and
+    ``best[name]`` (R,) the point attaining it (the first such point, ``arg_max``); ``ln_evidence`` (R,) under the block's
+    normalised uniform prior, or under the Gaussian prior normalised over the box by the same sample, and
+    ``ln_evidence_error`` (R,) its standard error, ``sqrt(1 / ess - 1 / n_drawn)`` - under a prior that of the numerator alone:
+    ``prior_error`` is the same figure of the prior's own normalisation, which the same sample estimates (the proposal has to
+    cover the prior inside the box as it covers the posterior), and the two do not add in any fixed way (they are correlated); ``ess`` (R,) the effective sample size
+    ``total^2 / sq`` and ``max_weight_share`` (R,) the largest normalised weight; ``mean`` (R, d), ``cov`` (R, d, d), ``sigma``
+    (R, d); ``outside_mass`` (R, d, 2) the posterior mass below and above every range; ``status`` (R,): ``OK``, ``LOW_ESS``
+    (``ess < min_ess``: the proposal misses this problem's posterior) or ``NO_FINITE`` (no kept point had a finite lnpost:
+    ``ln_evidence`` -inf, ``ess`` 0, the sums zeros, the moments and ``best`` NaN).  ``raw``: the :class:`Sums`."""
+
+    OK, LOW_ESS, NO_FINITE = 0, 1, 2
+
+    def __init__(self, layout, sample, lists, acc, pacc, min_ess):
+        self._layout, self._sample, self._lists, self.raw = layout, sample, lists, acc
+        self.names = list(layout.names)
+        self.edges = dict(zip(self.names, layout.edges))
+        self.n_problems = R = len(acc.ln_max)
+        self.n_drawn, self.n_inside = sample.n_drawn, sample.G
+        self.chunk, self.n_chunks = lists.chunk, lists.n_chunks
+        self.ln_max, self.arg_max, self.n_finite = acc.ln_max, acc.arg_max, acc.n_finite
+        self.min_ess = float(min_ess)
+        ok = self._ok = acc.n_finite > 0
+        total = self._total = np.where(ok, acc.total, 1.0)       # (never divided by zero)
+        d = layout.d
+        with np.errstate(divide="ignore"):
+            ln_sum = np.where(ok, acc.ln_max, 0.0) + np.log(total)
+        if pacc is None:
+            self.ln_evidence = ln_sum - np.log(float(self.n_drawn))
+        else:
+            self.prior_ln_max, self.prior_total = float(pacc.ln_max[0]), float(pacc.total[0])
+            self.ln_evidence = ln_sum - (self.prior_ln_max + np.log(self.prior_total))
+            b = np.exp(sample.lnop - sample.lnop.max())
+            self.prior_error = float(np.sqrt(max(np.sum(b * b) / np.sum(b) ** 2 - 1.0 / self.n_drawn, 0.0)))
+        self.ln_evidence = np.where(ok, self.ln_evidence, -np.inf)
+        sq = np.where(ok, acc.sq, 1.0)
+        self.ess = np.where(ok, total * total / sq, 0.0)
+        self.max_weight_share = np.where(ok, 1.0 / total, 0.0)
+        self.ln_evidence_error = np.where(ok, np.sqrt(np.maximum(sq / (total * total) - 1.0 / self.n_drawn, 0.0)), np.inf)
+        m = acc.s1 / total[:, None]
+        self.mean = np.where(ok[:, None], sample.centre[None, :] + m, np.nan)
+        self.cov = np.empty((R, d, d))
+        for j in range(d):
+            for k in range(j, d):
+                self.cov[:, j, k] = self.cov[:, k, j] = acc.s2[:, tri(d, j, k)] / total - m[:, j] * m[:, k]
+        self.cov[~ok] = np.nan
+        with np.errstate(invalid="ignore"):
+            self.sigma = np.sqrt(np.diagonal(self.cov, axis1=1, axis2=2))
+        at = np.where(ok, acc.arg_max, 0)
+        self.best = {n: np.where(ok, sample.x[at, j], np.nan) for j, n in enumerate(self.names)}
+        self.outside_mass = np.stack([np.stack([self._h1(j)[:, 0], self._h1(j)[:, -1]], axis=1) for j in range(d)], axis=1) / total[:, None, None]
+        self.status = np.where(ok, np.where(self.ess < self.min_ess, self.LOW_ESS, self.OK), self.NO_FINITE).astype(np.int32)
+        self._reader = None
+
+    def __len__(self):
+        return self.n_problems
+
+    def _axis(self, name):
+        if name not in self.names:
+            raise InputError(f"ImportancePosterior: {name} is not a sampled parameter ({self.names})")
+        return self.names.index(name)
+
+    def _h1(self, j):
+        return self.raw.h1[:, self._layout.cell_off[j]:self._layout.cell_off[j + 1]]
+
+    def marginal(self, name):
+        """(R, bins) the marginal posterior density of ``name`` over its range's bins: its integral is the mass inside the range."""
+        j = self._axis(name)
+        return self._h1(j)[:, 1:-1] / (self._total[:, None] * np.diff(self.edges[name])[None, :])
+
+    def marginal2d(self, a, b):
+        """(R, m, m) the joint marginal density of a requested pair, axis 1 along ``a``; ``edges2d(a, b)`` gives its edges."""
+        q, swap = self._pair(a, b, "marginal2d")
+        L = self._layout
+        ja, jb = L.pairs[q]
+        m = L.pair_bins[q]
+        at = L.cell_off[L.d + q] - L.n1
+        h = self.raw.h2[:, at:at + m * m].reshape(-1, m, m)
+        area = ((L.b[ja] - L.a[ja]) / m) * ((L.b[jb] - L.a[jb]) / m)
+        out = h / (self._total[:, None, None] * area)
+        return np.swapaxes(out, 1, 2) if swap else out
+
+    def edges2d(self, a, b):
+        """The two edge arrays (m + 1,) of a requested pair's cells, in the order ``a``, ``b``."""
+        q, _ = self._pair(a, b, "edges2d")
+        L = self._layout
+        return tuple(np.linspace(L.a[j], L.b[j], L.pair_bins[q] + 1) for j in (self._axis(a), self._axis(b)))
+
+    def _pair(self, a, b, what):
+        j, k = self._axis(a), self._axis(b)
+        key = tuple(sorted((j, k)))
+        if j == k or key not in self._layout.pairs:
+            raise InputError(f"ImportancePosterior.{what}: the pair ({a}, {b}) was not requested (pairs={self._layout.pair_names})")
+        return self._layout.pairs.index(key), j > k
+
+    def _marginals(self, name):
+        """The 1-D histograms as the reader of :mod:`victor_amd.marginals` takes them - weights for counts - with ``n`` the
+        running sum of ``name``'s own slots (the axes' sums differ by rounding)."""
+        if self._reader is None:
+            m = object.__new__(Marginals)
+            m.names = list(self.names)
+            m.counts = {n: self._h1(j)[:, 1:-1] for j, n in enumerate(self.names)}
+            m.below = {n: self._h1(j)[:, 0] for j, n in enumerate(self.names)}
+            m.above = {n: self._h1(j)[:, -1] for j, n in enumerate(self.names)}
+            m.edges = dict(self.edges)
+            self._reader = m
+        self._reader.n = np.cumsum(self._h1(self._axis(name)), axis=1)[:, -1]
+        return self._reader
+
+    def quantile(self, name, q):
+        """(R,) the q-quantile of ``name``, read from its histogram as ``Marginals.quantile`` reads one (linear inside a bin; NaN
+        in the mass outside the range, or without a finite point)."""
+        return self._marginals(name).quantile(name, q)
+
+    def interval(self, name, level=0.68):
+        """The equal-tailed interval of ``name``: two (R,) arrays."""
+        return self._marginals(name).interval(name, level)
+
+    def median(self, name):
+        return self.quantile(name, 0.5)
+
+
+def importance_posterior(fit, params, proposal=None, n=16384, seed=0, fixed=None, prior=None, bins=64, ranges=None, pairs=None,
+                         chunk=None, min_ess=50.0, device=True, evaluate=None, sample=None, ln_proposal=None, kwargs=None,
+                         realisations=None):
+    """The work of ``CCFFit.importance_posterior`` (``realisations=None``: the fit's data vector, R = 1) and
+    ``Realisations.importance_posterior`` (R = the realisations, one shared sample); see the module docstring.  With ``evaluate``
+    - a callable taking a dict of ``(n,)`` arrays (sampled and fixed parameters) and returning lnL ``(n,)`` or ``(n, R)`` - in
+    place of ``fit`` only the definition route (``device=False``) is possible and no GPU is needed.
+
+    ``params``: the cobaya block, as ``best_fit`` takes it (``fixed`` values must be scalars); ``proposal``: a
+    :class:`GaussianProposal` naming exactly the sampled parameters, drawn ``n`` times with ``seed``; or ``sample`` (G, d) with
+    ``ln_proposal`` (G,): the caller's own points, columns in sampled order, and ln of their normalised density; ``prior``: a
+    :class:`victor_amd.priors.GaussianPrior` or a list of them; ``bins``: an int or a dict name -> int, 1 .. 1024; ``ranges``:
+    name -> (a, b) inside the prior box (default the box); ``pairs``: name pairs for the 2-D histograms; ``chunk``: points per
+    launch, at most 65536 (default :func:`victor_amd.grid.default_chunk`); ``min_ess``: below it a problem is ``LOW_ESS``;
+    ``device=False``: the NumPy definition.  Every argument is checked before the first device call.  Returns an
+    :class:`ImportancePosterior`."""
+    who = "importance_posterior"
+    kwargs = kwargs or {}
+    if evaluate is not None and device:
+        raise InputError(f"{who}: an evaluate callable runs the definition route only (device=False)")
+    if evaluate is None and fit is None:
+        raise InputError(f"{who}: a fit or an evaluate callable is needed")
+    from .joint import JointFit
+    if isinstance(fit, JointFit):
+        raise InputError(f"{who}: joint fits have no importance posterior")
+    q = _Sampled(who, "sampled", params, fixed)
+    names, fixed_all = q.names, q.fixed_all
+    d = len(names)
+    per_block = sorted(n for n in list(names) + list(fixed_all) if "@" in n)
+    if per_block:
+        raise InputError(f"{who}: per-block parameters ('name@block': {per_block}) have no importance posterior")
+    if d > MAX_AXES:
+        raise InputError(f"{who}: at most {MAX_AXES} sampled parameters ({d} are sampled)")
+    if evaluate is None:
+        q.check_columns(fit)
+        q.check_alpha()
+    arrays = sorted(k for k, v in fixed_all.items() if np.ndim(v) > 0)
+    if arrays:
+        raise InputError(f"{who}: fixed values must be scalars ({arrays} are not)")
+    layout = resolve_layout(who, names, q.lo, q.hi, bins, ranges, pairs)
+    prior = q.prior(prior, fit)
+    if realisations is not None and getattr(realisations, "paired_model", False):
+        raise InputError(f"{who}: realisations(paired_model=True) have no cross mode (a point has one theory vector per "
+                         "realisation): a shared sample evaluates every point once")
+    if evaluate is None:
+        fit_options = q.fit_options(fit, kwargs)
+    if not np.isfinite(min_ess) or min_ess < 0:
+        raise InputError(f"{who}: min_ess must be a number >= 0, not {min_ess!r}")
+
+    # ---- rule 1: the sample
+    if sample is not None or ln_proposal is not None:
+        if sample is None or ln_proposal is None or proposal is not None:
+            raise InputError(f"{who}: sample and ln_proposal come together, in place of the proposal")
+        x = np.asarray(sample, dtype=np.float64)
+        lnq = np.asarray(ln_proposal, dtype=np.float64)
+        if x.ndim != 2 or x.shape[1] != d or lnq.shape != (len(x),) or not len(x):
+            raise InputError(f"{who}: sample must be (G, {d}) in the order {names} and ln_proposal (G,)")
+        if not np.all(np.isfinite(x)) or not np.all(np.isfinite(lnq)):
+            raise InputError(f"{who}: sample and ln_proposal must be finite")
+        centre = None
+    else:
+        if not isinstance(proposal, GaussianProposal):
+            raise InputError(f"{who}: a GaussianProposal is needed (or sample= and ln_proposal=)")
+        if isinstance(n, bool) or int(n) != n or not 1 <= int(n) <= MAX_POINTS:
+            raise InputError(f"{who}: n must be an integer in 1 .. 2^24, not {n!r}")
+        if isinstance(seed, bool) or int(seed) != seed or int(seed) < 0:
+            raise InputError(f"{who}: seed must be an integer >= 0, not {seed!r}")
+        centre, chol = proposal.ordered(who, names)
+        x = GaussianProposal.draw(centre, chol, proposal.dof, int(n), int(seed))
+        lnq = GaussianProposal.ln_density(x, centre, chol, proposal.dof)
+    if len(x) > MAX_POINTS:
+        raise InputError(f"{who}: at most 2^24 points, not {len(x)}")
+    inside = np.all((x >= q.lo) & (x <= q.hi), axis=1)
+    if not np.any(inside):
+        raise InputError(f"{who}: no point of the sample lies inside the prior box ({len(x)} drawn)")
+    kept = x[inside]
+    smp = Sample(kept, kept.mean(axis=0) if centre is None else centre, lnq[inside], len(x), q.lo, q.hi, prior)
+
+    R = len(realisations) if realisations is not None else 1
+    if chunk is None:
+        chunk = default_chunk(R, smp.G)
+    if isinstance(chunk, bool) or int(chunk) != chunk or not 1 <= int(chunk) <= MAX_CHUNK:
+        raise InputError(f"{who}: chunk must be an integer in 1 .. {MAX_CHUNK}, not {chunk!r}")
+    chunk = int(chunk)
+    lists = Lists(layout, smp.x, chunk)                           # rule 2
+    fixed_out = {k: float(v) for k, v in fixed_all.items()}
+
+    def batch_of(x):
+        batch = dict(fixed_out)
+        batch.update({n: np.ascontiguousarray(x[:, j]) for j, n in enumerate(names)})
+        return batch
+
+    if not device:
+        if evaluate is not None:
+            R = None                                             # (as many problems as the callable returns columns)
+
+            def values(x):
+                return evaluate(batch_of(x))
+        elif realisations is not None:
+            def values(x):
+                return realisations.log_likelihood(batch_of(x), **kwargs)[0]
+        else:
+            def values(x):
+                return fit.log_likelihood_batch(batch_of(x), **kwargs)[0]
+        acc, pacc = run_definition(layout, smp, lists, R, values)
+        return ImportancePosterior(layout, smp, lists, acc, pacc, min_ess)
+
+    # ---- device
+    lib, h, refresh = create_handle(q, fit, realisations, kwargs, fit_options, layout, smp, lists, fixed_out)
+    try:
+        if refresh is not None:
+            refresh()
+        _check(lib, h, lib.vk_is_run(h, 0, smp.G), "vk_is_run")
+        acc, pacc = read_result(lib, h, layout, R, smp.lnop is not None)
+    finally:
+        lib.vk_is_destroy(h)
+    return ImportancePosterior(layout, smp, lists, acc, pacc, min_ess)
+
+
+def _check(lib, h, rc, entry):
+    if rc != 0:
+        msg = (lib.vk_is_last_error(h) or b"").decode() or f"{entry} failed ({rc})"
+        raise (InputError if rc == -1 else N.NativeError)(msg)
+
+
+def create_handle(q, fit, realisations, kwargs, fit_options, layout, smp, lists, fixed_out):
+    """``(lib, handle, refresh)`` of ``vk_is_create`` for the sample: the base row from the fixed values (the sampled columns are
+    overwritten per point), the sample's arrays, and per point the host's own ``eps^(-2/3)`` (``vk_epsilon_to_ap``: libm's pow)."""
+    model = fit._merged(kwargs)
+    fit._check_supported(model)
+    batch = dict(fixed_out)
+    batch.update({n: np.array([smp.x[0, j]]) for j, n in enumerate(layout.names)})
+    base = np.ascontiguousarray(fit._fit_rows(batch, model), dtype=np.float64)
+    cols = np.array([N.ROW_COLUMNS.get(n, N.VK_WALK_EPSILON) for n in layout.names], dtype=np.int32)
+    refresh = None
+    if realisations is None:
+        eng = fit._get_engine(fit._engine_key(model), model["simpson_even"])
+        opts = eng.make_opts(model, fit_options)
+    else:
+        _, _, eng, opts = realisations._plan(kwargs)
+
+        def refresh():
+            realisations._upload(eng)
+    eps_pow = None
+    if "epsilon" in layout.names:
+        with np.errstate(invalid="ignore"):
+            eps_pow = N.f64(N.epsilon_to_ap(N.f64(smp.x[:, layout.names.index("epsilon")]), 1.0)[1])
+    i32 = C.POINTER(C.c_int32)
+    n_bins = np.array(layout.n_bins, dtype=np.int32)
+    pair_bins = np.array(layout.pair_bins, dtype=np.int32)
+    err = C.create_string_buffer(512)
+    h = eng._lib.vk_is_create(eng._ctx, C.byref(opts), layout.d, cols.ctypes.data_as(i32), smp.G, N.as_dp(smp.x), N.as_dp(smp.y),
+                              None if eps_pow is None else N.as_dp(eps_pow), N.as_dp(smp.lno),
+                              None if smp.lnop is None else N.as_dp(smp.lnop), n_bins.ctypes.data_as(i32), len(pair_bins),
+                              pair_bins.ctypes.data_as(i32) if len(pair_bins) else None, lists.entries.ctypes.data_as(i32),
+                              lists.offsets.ctypes.data_as(i32), N.as_dp(base), float(fixed_out.get("alpha", 1)),
+                              0 if realisations is None else 1, lists.chunk, err, len(err))
+    if not h:
+        msg = err.value.decode()
+        raise (N.NativeError if "device memory" in msg else InputError)(msg)
+    return eng._lib, h, refresh
+
+
+def read_result(lib, h, layout, R, with_prior):
+    """``(Sums, the prior's own Sums or None)`` of a completed run (``vk_is_result``)."""
+    acc = Sums(layout, R)
+    i64 = C.POINTER(C.c_int64)
+    pm, pt = C.c_double(0.0), C.c_double(0.0)
+    rc = lib.vk_is_result(h, N.as_dp(acc.ln_max), acc.arg_max.ctypes.data_as(i64), acc.n_finite.ctypes.data_as(i64), N.as_dp(acc.total),
+                          N.as_dp(acc.sq), N.as_dp(acc.s1), N.as_dp(acc.s2), N.as_dp(acc.h1), N.as_dp(acc.h2),
+                          C.cast(C.byref(pm), C.POINTER(C.c_double)), C.cast(C.byref(pt), C.POINTER(C.c_double)))
+    _check(lib, h, rc, "vk_is_result")
+    pacc = None
+    if with_prior:
+        pacc = Sums(layout, 1)
+        pacc.ln_max[0], pacc.total[0] = pm.value, pt.value
+    return acc, pacc

@@ -329,6 +329,18 @@ class Realisations:
         from .grid import grid_posterior
         return grid_posterior(self.fit, params, bins, ranges, fixed, prior, pairs, chunk, device, kwargs, realisations=self)
 
+    def importance_posterior(self, params, q=None, n=16384, seed=0, fixed=None, prior=None, bins=64, ranges=None, pairs=None, chunk=None,
+                             min_ess=50.0, device=True, evaluate=None, sample=None, ln_proposal=None, **kwargs):
+        """The posterior of EVERY realisation from ONE shared importance sample (R = ``len(self)`` problems): a point's theory
+        vector is computed once and compared with all realisations, and the evidence, the effective sample size, the moments
+        and the marginal histograms of each are reduced on the GPU (``device=True``) or by the NumPy loop over
+        :meth:`log_likelihood` that defines them (``device=False``).  Arguments and result as ``CCFFit.importance_posterior``
+        (:mod:`victor_amd.importance`).  Refused with ``paired_model=True``: a point then has one theory vector per
+        realisation."""
+        from .importance import importance_posterior
+        return importance_posterior(self.fit, params, q, n, seed, fixed, prior, bins, ranges, pairs, chunk, min_ess, device, evaluate,
+                                    sample, ln_proposal, kwargs, realisations=self)
+
     def nested_sampling(self, params, n_live=256, batch=32, steps=16, scale=None, seed=0, fixed=None, tol=1e-3, max_iter=None, n_iter=None,
                         keep_dead=True, device=True, evaluate=None, **kwargs):
         """Nested sampling of EVERY realisation, all of them in lock step (R = ``len(self)`` problems, one evidence and one
