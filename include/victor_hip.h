@@ -1074,6 +1074,29 @@ vk_nested* vk_nested_create_joint_blocks(vk_ctx* const* ctxs, int32_t n_ctx, vk_
                                          int32_t n_params, const int32_t* columns, const int32_t* param_block, const double* lo,
                                          const double* hi, const double* base_rows, double alpha, const int32_t* which, char* err,
                                          size_t errlen);
+/* Importance-sampled posteriors (vk_is_create above) of a joint fit: the same handle over the joint entry points, block-diagonal
+ * (cov NULL) or under the covariance handle, fixed or gridded in beta.  Arguments as vk_is_create behind ctxs, n_ctx and cov;
+ * every_realisation: problem r is JOINT realisation r - realisation r of every block - and every point's theory vectors are
+ * computed once per block and compared with all of them (the cross mode of vk_joint_cov_eval_realisations; block-diagonal each
+ * block's cross-mode chi-squares, summed in block order by the rule of vk_joint_eval_device_async: start at 0, add block after
+ * block, a sum that is not finite becomes (-inf, +inf)).  The _blocks form keeps a row per block as vk_fit_create_joint_blocks
+ * does: param_block [n_axes] and base_rows [n_ctx][VK_NPAR]; vk_is_rows then returns [n_ctx][count][VK_NPAR].  vk_is_run, _rows,
+ * _result, _last_error and _destroy serve these handles as they serve vk_is_create's.
+ * Refused in addition to what vk_is_create and vk_fit_create_joint[_blocks] refuse: with every_realisation, blocks that hold
+ * different numbers of realisations or none, a block with model realisations (vk_set_model_realisations: no cross mode), a block
+ * whose realisation kernel lacks LDS - at create time and again at every run -; VK_WALK_EPSILON per block (eps_pow holds one
+ * power per point). */
+vk_is* vk_is_create_joint(vk_ctx* const* ctxs, int32_t n_ctx, vk_joint_cov* cov, const vk_eval_opts* opts, int32_t n_axes,
+                          const int32_t* columns, int64_t n_points, const double* x, const double* y, const double* eps_pow,
+                          const double* lno, const double* lno_prior, const int32_t* n_bins, int32_t n_pairs, const int32_t* pair_bins,
+                          const int32_t* lists, const int32_t* offsets, const double* base_row, double alpha, int32_t every_realisation,
+                          int32_t chunk, char* err, size_t errlen);
+vk_is* vk_is_create_joint_blocks(vk_ctx* const* ctxs, int32_t n_ctx, vk_joint_cov* cov, const vk_eval_opts* opts, int32_t n_axes,
+                                 const int32_t* columns, const int32_t* param_block, int64_t n_points, const double* x, const double* y,
+                                 const double* eps_pow, const double* lno, const double* lno_prior, const int32_t* n_bins,
+                                 int32_t n_pairs, const int32_t* pair_bins, const int32_t* lists, const int32_t* offsets,
+                                 const double* base_rows, double alpha, int32_t every_realisation, int32_t chunk, char* err,
+                                 size_t errlen);
 
 /* ---- many one-point callers sharing one GPU: mailboxes in shared memory -----------------------------------------------
  * The reference is sampled by cobaya, which asks for ONE likelihood per call (victor/likelihoods/CCFLikelihood.py:32-39); more

@@ -217,6 +217,14 @@ SYMBOLS = {
     "vk_is_create": (_vp, [_vp, _optp, C.c_int32, C.POINTER(C.c_int32), C.c_int64, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int32),
                            C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp, C.c_double, C.c_int32,
                            C.c_int32, C.c_char_p, C.c_size_t]),
+    # ... of a joint fit: the contexts, their number and the covariance handle in front; _blocks: param_block behind the columns
+    "vk_is_create_joint": (_vp, [C.POINTER(C.c_void_p), C.c_int32, _vp, _optp, C.c_int32, C.POINTER(C.c_int32), C.c_int64, _dp, _dp,
+                                 _dp, _dp, _dp, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                 C.POINTER(C.c_int32), _dp, C.c_double, C.c_int32, C.c_int32, C.c_char_p, C.c_size_t]),
+    "vk_is_create_joint_blocks": (_vp, [C.POINTER(C.c_void_p), C.c_int32, _vp, _optp, C.c_int32, C.POINTER(C.c_int32),
+                                        C.POINTER(C.c_int32), C.c_int64, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int32), C.c_int32,
+                                        C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp, C.c_double,
+                                        C.c_int32, C.c_int32, C.c_char_p, C.c_size_t]),
     "vk_is_run": (C.c_int, [_vp, C.c_int64, C.c_int64]),
     "vk_is_rows": (C.c_int, [_vp, C.c_int64, C.c_int32, _dp]),
     "vk_is_result": (C.c_int, [_vp, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),

@@ -1722,8 +1722,10 @@ int vkh::check_joint(const vk_joint_cov* h, vk_ctx* const* ctxs, int n_ctx, bool
 
 // real, under a covariance: theory [m][NT] | -1/2 log det [m] | ints: sign test [m], the slice sort's lo, rank, perm [m] and
 // histograms [chunks + 1][n_beta]
-size_t vkh::joint_workspace_doubles(const vk_joint_cov* h, vk_ctx* const* ctxs, int n_ctx, long long m, bool real) {
-  if (!h) return vk_joint_workspace_doubles(ctxs, n_ctx, m);       // real or not: per block lnl | chi2 | theory
+size_t vkh::joint_workspace_doubles(const vk_joint_cov* h, vk_ctx* const* ctxs, int n_ctx, long long m, bool real, long long cross) {
+  // block-diagonal, real or not: per block lnl | chi2 | theory, n_ctx m (N_max + 2); in cross mode a row has `cross` values of
+  // each, n_ctx m (N_max + 2 cross)
+  if (!h) return vk_joint_workspace_doubles(ctxs, n_ctx, m) + (real && cross > 1 ? (size_t)n_ctx * (size_t)m * 2 * (size_t)(cross - 1) : 0);
   if (!real) return vk_joint_cov_workspace_doubles(h, m);
   const size_t chunks = (size_t)(m + kJointSortChunk - 1) / kJointSortChunk;
   const size_t ints = (size_t)m * 4 + (chunks + 1) * h->n_beta;
@@ -1783,15 +1785,19 @@ int vkh::enqueue_joint_sum_realisations(vk_ctx* const* ctxs, int n_ctx, const vk
   VK_HIP(lead, hipSetDevice(lead->device));
   int n_max = 0;
   for (int q = 0; q < n_ctx; ++q) n_max = std::max(n_max, ctxs[q]->N);
-  const long long block_stride = m * (n_max + 2);               // per block: lnl[m] | chi2[m] | theory workspace [m][N]
+  // values of a block's lnl and of its chi2: one per row (pairs mode) or per (row, realisation) (cross mode; check_joint has
+  // made n_real the same on every block)
+  const long long nv = d_which ? m : m * lead->n_real;
+  const long long block_stride = 2 * nv + m * n_max;            // per block: lnl[nv] | chi2[nv] | theory workspace [m][N]
   int rc = fan_out_with(ctxs, n_ctx, [&](int q, vk_ctx* c) {
     double* blk = d_ws + q * block_stride;
-    return enqueue_realisations(c, opts, d_par + q * par_stride, m, blk + 2 * m, blk, blk + m, d_which);
+    return enqueue_realisations(c, opts, d_par + q * par_stride, m, blk + 2 * nv, blk, blk + nv, d_which);
   });
   if (rc) return rc;
   const hipError_t e = join_block_streams(ctxs, n_ctx);
   if (e != hipSuccess) return fail(lead, VK_E_HIP, "joint fit: enqueue failed: %s", hipGetErrorString(e));
-  hipLaunchKernelGGL(vk_joint_sum_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, lead->stream, d_ws, m, n_ctx, block_stride,
+  // (the sum kernel reads block q's lnl at q block_stride + i and its chi2 n entries on: n = nv serves both modes)
+  hipLaunchKernelGGL(vk_joint_sum_kernel, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, lead->stream, d_ws, nv, n_ctx, block_stride,
                      d_lnl, d_chi);
   VK_HIP(lead, hipGetLastError());
   return VK_OK;

@@ -192,8 +192,10 @@ int enqueue_realisations(vk_ctx* ctx, const vk_eval_opts* opts, const double* d_
 // check_joint: may these contexts (lead first) be evaluated together - under the covariance handle h, or block-diagonal (h NULL);
 // need_real: against their realisations (pairs mode).  The text of a refusal is the lead's vk_last_error.
 int check_joint(const vk_joint_cov* h, vk_ctx* const* ctxs, int n_ctx, bool need_real);
-// doubles of workspace the joint evaluation of up to m rows needs (data: the public workspace sizes; real: the layouts below)
-size_t joint_workspace_doubles(const vk_joint_cov* h, vk_ctx* const* ctxs, int n_ctx, long long m, bool real);
+// doubles of workspace the joint evaluation of up to m rows needs (data: the public workspace sizes; real: the layouts below).
+// cross > 0: the rows go against every one of `cross` realisations (cross mode) - block-diagonal each block then keeps m * cross
+// values of lnl and of chi2 in front of its theory vectors; under a covariance the outputs are the caller's and nothing changes.
+size_t joint_workspace_doubles(const vk_joint_cov* h, vk_ctx* const* ctxs, int n_ctx, long long m, bool real, long long cross = 0);
 // the device arrays of one joint-covariance launch against realisations: theory vectors [m][NT] (block q at m * off_q), -1/2 log
 // det [m], the sign test's word [m], the slice sort's lo | rank | perm [sort_stride] and histograms
 struct JointRealWs {
@@ -211,8 +213,10 @@ JointRealWs joint_real_carve(const vk_joint_cov* h, double* d_ws, long long m_ma
 int enqueue_joint_cov_realisations(vk_joint_cov* h, vk_ctx* const* ctxs, int n_ctx, const vk_eval_opts* opts, const double* d_par,
                                    long long par_stride, long long m, const int32_t* d_which, double* d_lnl, double* d_chi,
                                    const JointRealWs& w);
-// Block-diagonal, pairs mode: every block's enqueue_realisations on its own stream behind the lead's, into block q's part of d_ws
-// (lnl [m] | chi2 [m] | theory [m][N_max], the layout of vk_joint_eval_device_async), then the block-order sum on the lead stream.
+// Block-diagonal: every block's enqueue_realisations on its own stream behind the lead's, into block q's part of d_ws, then the
+// block-order sum (vk_joint_sum_kernel's rule) on the lead stream.  Pairs mode (d_which: device indices, outputs [m]): a block's
+// part is lnl [m] | chi2 [m] | theory [m][N_max], the layout of vk_joint_eval_device_async.  Cross mode (d_which NULL, outputs
+// [m][R], R the blocks' common n_real): lnl [m R] | chi2 [m R] | theory [m][N_max], and the sum runs over m R entries.
 int enqueue_joint_sum_realisations(vk_ctx* const* ctxs, int n_ctx, const vk_eval_opts* opts, const double* d_par,
                                    long long par_stride, long long m, const int32_t* d_which, double* d_lnl, double* d_chi,
                                    double* d_ws);

@@ -5,8 +5,11 @@
 //
 // A chunk of n consecutive points g0 .. g0 + n - 1 of the uploaded sample goes through five launches on the context's stream:
 //   vk_is_rows_kernel      one thread per point: reads x[g][.] and the host's eps^(-2/3) of the point and forms the parameter row
-//                          through vkrow::form_rows - the row is CCFFit._fit_rows' bit for bit, epsilon sampled or not
+//                          through vkrow::form_rows - the row is CCFFit._fit_rows' bit for bit, epsilon sampled or not; of a
+//                          joint handle with per-block axes a row per block (JointFit._block_rows' bit for bit): an axis goes to
+//                          its own block's row, or to every block's
 //   (the evaluation)       sampled_evaluate: lnL of the rows, [n] against the data vector or [n][R] against every realisation
+//                          (of a joint fit: every joint realisation, under its covariance or block-diagonal)
 //   vk_is_max_kernel       per problem the chunk's maximum of lnpost = lnL + lno[g], first arg max and finite count - the shape of
 //                          vk_grid_max_kernel: up to 64 problems of a workgroup (problem the fastest-varying lane: the loads of a
 //                          row of [n][R] coalesce) times 256 / 64 slices of the chunk, merged through LDS with vkgrid::merge
@@ -41,8 +44,9 @@ struct IsArgs {
   // rows kernel
   const double* x;                   // [G][d]
   const double* eps_pow;             // [G]: the host's eps^(-2/3) per point (NULL: epsilon is not sampled)
-  const double* base;                // [VK_NPAR]
-  double* rows;                      // [chunk][VK_NPAR]
+  const double* base;                // [VK_NPAR]; of a handle with a row per block (vk_is_create_joint_blocks) one base row per set
+  double* rows;                      // [chunk][VK_NPAR]; ... a set per block, blocks.row_stride apart
+  vkrow::Blocks blocks;              // the row sets and the set every axis is written to (one set: every axis to it)
   int col[vkis::kMaxP];
   double alpha;
   // values
@@ -83,8 +87,9 @@ __global__ void __launch_bounds__(kIsBlock) vk_is_rows_kernel(IsArgs a) {
   const long long g = a.g0 + i;
   const double* x = a.x + g * a.d;
   const double* eps_pow = a.eps_pow;
-  vkrow::form_rows(vkrow::one_set(), a.base, 0, a.rows, (long long)i, a.col, a.d, a.alpha, [=](int j) { return x[j]; },
-                   [=](double) { return eps_pow[g]; });               // (called for a sampled epsilon only)
+  // (block q's row at rows + q row_stride from its own base row; with one set the stores are those of vkrow::one_set())
+  vkrow::form_rows(a.blocks, a.base, 0, a.rows, (long long)i, a.col, a.d, a.alpha, [=](int j) { return x[j]; },
+                   [=](double) { return eps_pow[g]; });               // (called for a sampled epsilon only: shared by all blocks)
 }
 
 __global__ void __launch_bounds__(kIsBlock) vk_is_max_kernel(IsArgs a) {

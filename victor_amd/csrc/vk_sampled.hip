@@ -100,6 +100,7 @@ struct Sampled {
   double alpha = 1.0;
   bool real = false;
   int max_which = -1;
+  long long cross = 0;                     // > 0: every pending row goes against all `cross` realisations (an importance handle)
   void* d_mem = nullptr;                   // one allocation holding every device array of the handle
   double *d_base = nullptr, *d_rows = nullptr, *d_th = nullptr;   // each problem's base row; the pending rows, their theory vectors
   int *d_which = nullptr, *d_row_which = nullptr;                 // realisation of each problem, of each pending row
@@ -119,9 +120,12 @@ struct Sampled {
   }
 
   // doubles of d_th: the theory vectors of rows_max rows; of a joint fit, the workspace of its evaluation of that many rows
-  // (whose head is the rows' theory vectors, block by block)
+  // (whose head is the rows' theory vectors, block by block).  Block-diagonal that is B rows_max (N_max + 2) in pairs mode - per
+  // block lnl | chi2 | theory - and B rows_max (N_max + 2 cross) in cross mode, where a row has `cross` values of lnl and of chi2;
+  // under a covariance the outputs are the handle's own arrays in either mode (vkh::joint_workspace_doubles).
   size_t workspace_doubles() const {
-    return blocks.empty() ? rows_max * ctx->N : vkh::joint_workspace_doubles(cov, blocks.data(), (int)blocks.size(), (long long)rows_max, real);
+    return blocks.empty() ? rows_max * ctx->N
+                          : vkh::joint_workspace_doubles(cov, blocks.data(), (int)blocks.size(), (long long)rows_max, real, cross);
   }
 };
 
@@ -351,7 +355,8 @@ static int sampled_ready(Sampled* f, const char* who, const char* noun, bool nam
 }
 
 // the evaluation of the first m pending rows into d_lnl / d_chi, on the context's stream: the fit's own data vector with lnL /
-// chi2 in the theory launch (the fused tail applies), realisations in pairs mode
+// chi2 in the theory launch (the fused tail applies), realisations in pairs mode - or, of a handle that keeps no d_row_which (an
+// importance handle), in cross mode: every row against every realisation, outputs [m][n_real], single fit and joint fit alike
 static int sampled_evaluate(Sampled* f, long long m, double* d_lnl, double* d_chi) {
   int rc;
   if (f->blocks.empty()) {
@@ -1992,6 +1997,9 @@ int vk_grid_result(vk_grid* f, double* ln_max, int64_t* arg_max, double* total, 
 // kernel, sampled_evaluate (the data-vector route with lnL, or enqueue_realisations in cross mode, [n][R]), then the max, weight
 // and accumulate kernels, all on the context's stream with no host synchronisation between chunks; vk_is_run waits once at its
 // end.  One allocation holds the sample, its lists and offsets, rows, workspace, the chunk's values and the accumulators.
+// Of a joint fit (vk_is_create_joint): the same handle over the blocks' contexts - sampled_evaluate's joint routes, against the
+// joint data vector or every joint realisation (cross mode) - with one base row and one set of pending rows, or
+// (vk_is_create_joint_blocks) one of each per block.
 struct __attribute__((visibility("hidden"))) vk_is : Sampled {
   int R = 1, chunk = 0, n_lists = 0, n_cells = 0, n_acc = 0, n1 = 0, n2 = 0;
   bool eps = false, own = false;           // epsilon is sampled; the prior's own problem rides along
@@ -2008,8 +2016,8 @@ struct __attribute__((visibility("hidden"))) vk_is : Sampled {
   void layout(Carve& c) {
     const size_t n = (size_t)chunk, r = (size_t)R, g = (size_t)G;
     c.take(d_run, r + 1);
-    c.take(d_base, VK_NPAR);
-    c.take(d_rows, n * VK_NPAR);
+    c.take(d_base, (size_t)sets * VK_NPAR);          // (a base row and a set of pending rows per block: vk_is_create_joint_blocks)
+    c.take(d_rows, (size_t)sets * n * VK_NPAR);
     c.take(d_x, g * P);
     c.take(d_y, g * P);
     c.take(d_eps, eps ? g : 1);
@@ -2036,6 +2044,7 @@ static IsArgs is_args(const vk_is* f) {
   a.eps_pow = f->eps ? f->d_eps : nullptr;
   a.base = f->d_base;
   a.rows = f->d_rows;
+  a.blocks = f->row_sets(1);
   for (int j = 0; j < vkis::kMaxP; ++j) a.col[j] = f->col[j];
   a.alpha = f->alpha;
   a.y = f->d_y;
@@ -2056,16 +2065,23 @@ static IsArgs is_args(const vk_is* f) {
   return a;
 }
 
-// may the handle run now: the context, and of the realisation route that the set on the context is the one it was made for
+// may the handle run now: the context, and of the realisation route that the set on the context is the one it was made for - of
+// a joint handle every block's context (sampled_ready has been through check_joint: the counts agree between the blocks, no
+// block holds model realisations, the realisation kernels have their LDS)
 static int is_ready(vk_is* f, const char* who) {
   int rc = sampled_ready(f, who, "sample", true);
-  if (rc) return rc;
-  if (f->real && f->ctx->n_real != f->R)
-    return refused(f, std::string(who) + ": the context holds " + std::to_string(f->ctx->n_real) + " realisations, the sample was made for " +
-                          std::to_string(f->R));
-  if (f->real && f->ctx->n_sets > 0)
-    return refused(f, std::string(who) + ": model realisations are set on the context (vk_set_model_realisations): a point has one "
-                          "theory vector per realisation, and a shared sample evaluates every point once");
+  if (rc || !f->real) return rc;
+  const size_t nb = f->blocks.empty() ? 1 : f->blocks.size();
+  for (size_t q = 0; q < nb; ++q) {
+    const vk_ctx* c = f->blocks.empty() ? f->ctx : f->blocks[q];
+    const std::string ctx_q = f->blocks.empty() ? "the context" : "context " + std::to_string(q);
+    if (c->n_real != f->R)
+      return refused(f, std::string(who) + ": " + ctx_q + " holds " + std::to_string(c->n_real) + " realisations, the sample was made for " +
+                            std::to_string(f->R));
+    if (c->n_sets > 0)
+      return refused(f, std::string(who) + ": model realisations are set on " + ctx_q + " (vk_set_model_realisations): a point has one "
+                            "theory vector per realisation, and a shared sample evaluates every point once");
+  }
   return VK_OK;
 }
 
@@ -2089,18 +2105,26 @@ static int is_chunks(vk_is* f, long long first, long long end) {
   return VK_OK;
 }
 
-extern "C" {
-
-vk_is* vk_is_create(vk_ctx* ctx, const vk_eval_opts* opts, int32_t n_axes, const int32_t* columns, int64_t n_points, const double* x,
-                    const double* y, const double* eps_pow, const double* lno, const double* lno_prior, const int32_t* n_bins,
-                    int32_t n_pairs, const int32_t* pair_bins, const int32_t* lists, const int32_t* offsets, const double* base_row,
-                    double alpha, int32_t every_realisation, int32_t chunk, char* err, size_t errlen) {
+// vk_is_create and its _joint forms (`who`): the one place where a sample's shape, bins, offsets, lists and values are checked,
+// the handle is made (sampled_create) and the sample goes up.  joint: ctxs are the n_ctx blocks of a joint fit, lead first, under
+// cov (NULL: block-diagonal); otherwise ctxs is the one context.  param_block (the _blocks form; NULL otherwise): the block each
+// axis belongs to, or -1; base_rows then holds one row per block.
+static vk_is* is_create(const char* who, vk_ctx* const* ctxs, int n_ctx, bool joint, vk_joint_cov* cov, const vk_eval_opts* opts,
+                        int32_t n_axes, const int32_t* columns, const int32_t* param_block, int64_t n_points, const double* x,
+                        const double* y, const double* eps_pow, const double* lno, const double* lno_prior, const int32_t* n_bins,
+                        int32_t n_pairs, const int32_t* pair_bins, const int32_t* lists, const int32_t* offsets, const double* base_rows,
+                        double alpha, int32_t every_realisation, int32_t chunk, char* err, size_t errlen) {
   auto bail = [&](const std::string& msg) -> vk_is* {
-    if (err && errlen) snprintf(err, errlen, "vk_is_create: %s", msg.c_str());
+    if (err && errlen) snprintf(err, errlen, "%s: %s", who, msg.c_str());
     return nullptr;
   };
-  if (!ctx || !opts || !columns || !x || !y || !lno || !n_bins || !lists || !offsets || !base_row || (n_pairs > 0 && !pair_bins))
+  if (!ctxs || (!joint && !ctxs[0]) || !opts || !columns || !x || !y || !lno || !n_bins || !lists || !offsets || !base_rows ||
+      (n_pairs > 0 && !pair_bins))
     return bail("NULL argument");
+  if (n_ctx < 1 || n_ctx > 32) return bail("need 1 <= contexts <= 32");
+  for (int q = 0; q < n_ctx; ++q)
+    if (!ctxs[q]) return bail("context " + std::to_string(q) + " is NULL");
+  vk_ctx* ctx = ctxs[0];
   if (n_axes < 1 || n_axes > vkis::kMaxP) return bail("need 1 <= axes <= 10");
   if (n_points < 1 || n_points > vkis::kMaxPoints) return bail("need 1 <= points <= 2^24");
   if (chunk < 1 || chunk > vkis::kMaxChunk) return bail("need 1 <= chunk <= 65536");
@@ -2114,7 +2138,11 @@ vk_is* vk_is_create(vk_ctx* ctx, const vk_eval_opts* opts, int32_t n_axes, const
     if (n_bins[j] < 1 || n_bins[j] > vkis::kMaxBins) return bail("axis " + std::to_string(j) + " needs 1 <= bins <= 1024");
     cell_off[j] = (int)cells;
     cells += n_bins[j] + 2;                // below, the bins, above
-    if (columns[j] == VK_WALK_EPSILON) eps = true;
+    if (columns[j] == VK_WALK_EPSILON) {
+      eps = true;
+      // (eps_pow holds one power per point: two blocks' epsilons of a point would read the same one)
+      if (param_block && param_block[j] >= 0) return bail("epsilon cannot be sampled per block (eps_pow holds one eps^(-2/3) per point)");
+    }
   }
   n1 = cells;
   for (int q = 0; q < n_pairs; ++q) {
@@ -2148,7 +2176,12 @@ vk_is* vk_is_create(vk_ctx* ctx, const vk_eval_opts* opts, int32_t n_axes, const
     }
   }
   int R = 1;
-  if (every_realisation) {
+  if (every_realisation && joint) {
+    // every block: realisations set, the same number of them as the lead's, no model realisations (no cross mode), the LDS the
+    // realisation kernels need
+    if (check_joint(cov, ctxs, n_ctx, true) != VK_OK) return bail(ctx->err);
+    R = ctx->n_real;
+  } else if (every_realisation) {
     if (ctx->n_real <= 0 || !ctx->d_real) return bail("no realisations are set on the context (vk_set_realisations)");
     if (ctx->n_sets > 0)
       return bail("model realisations are set on the context (vk_set_model_realisations): a point has one theory vector per "
@@ -2161,10 +2194,11 @@ vk_is* vk_is_create(vk_ctx* ctx, const vk_eval_opts* opts, int32_t n_axes, const
   const double inf = __builtin_inf();
   double lo[vkis::kMaxP], hi[vkis::kMaxP];                     // (a sample has points, not a box)
   for (int j = 0; j < vkis::kMaxP; ++j) lo[j] = -inf, hi[j] = inf;
-  vk_is* f = sampled_create<vk_is>("vk_is_create", "sample", &ctx, 1, false, nullptr, opts, 1, n_axes, columns, nullptr, lo, hi, base_row,
+  vk_is* f = sampled_create<vk_is>(who, "sample", ctxs, n_ctx, joint, cov, opts, 1, n_axes, columns, param_block, lo, hi, base_rows,
                                    alpha, nullptr, err, errlen, [&](vk_is* h) {
     h->R = R;
     h->real = every_realisation != 0;
+    h->cross = h->real ? R : 0;
     h->max_which = h->real ? R - 1 : -1;
     h->chunk = chunk;
     h->G = G;
@@ -2191,6 +2225,36 @@ vk_is* vk_is_create(vk_ctx* ctx, const vk_eval_opts* opts, int32_t n_axes, const
     return bail("upload failed");
   }
   return f;
+}
+
+extern "C" {
+
+vk_is* vk_is_create(vk_ctx* ctx, const vk_eval_opts* opts, int32_t n_axes, const int32_t* columns, int64_t n_points, const double* x,
+                    const double* y, const double* eps_pow, const double* lno, const double* lno_prior, const int32_t* n_bins,
+                    int32_t n_pairs, const int32_t* pair_bins, const int32_t* lists, const int32_t* offsets, const double* base_row,
+                    double alpha, int32_t every_realisation, int32_t chunk, char* err, size_t errlen) {
+  return is_create("vk_is_create", &ctx, 1, false, nullptr, opts, n_axes, columns, nullptr, n_points, x, y, eps_pow, lno, lno_prior, n_bins,
+                   n_pairs, pair_bins, lists, offsets, base_row, alpha, every_realisation, chunk, err, errlen);
+}
+
+vk_is* vk_is_create_joint(vk_ctx* const* ctxs, int32_t n_ctx, vk_joint_cov* cov, const vk_eval_opts* opts, int32_t n_axes,
+                          const int32_t* columns, int64_t n_points, const double* x, const double* y, const double* eps_pow,
+                          const double* lno, const double* lno_prior, const int32_t* n_bins, int32_t n_pairs, const int32_t* pair_bins,
+                          const int32_t* lists, const int32_t* offsets, const double* base_row, double alpha, int32_t every_realisation,
+                          int32_t chunk, char* err, size_t errlen) {
+  return is_create("vk_is_create_joint", ctxs, n_ctx, true, cov, opts, n_axes, columns, nullptr, n_points, x, y, eps_pow, lno, lno_prior,
+                   n_bins, n_pairs, pair_bins, lists, offsets, base_row, alpha, every_realisation, chunk, err, errlen);
+}
+
+vk_is* vk_is_create_joint_blocks(vk_ctx* const* ctxs, int32_t n_ctx, vk_joint_cov* cov, const vk_eval_opts* opts, int32_t n_axes,
+                                 const int32_t* columns, const int32_t* param_block, int64_t n_points, const double* x, const double* y,
+                                 const double* eps_pow, const double* lno, const double* lno_prior, const int32_t* n_bins,
+                                 int32_t n_pairs, const int32_t* pair_bins, const int32_t* lists, const int32_t* offsets,
+                                 const double* base_rows, double alpha, int32_t every_realisation, int32_t chunk, char* err,
+                                 size_t errlen) {
+  if (no_param_block("vk_is_create_joint_blocks", param_block, err, errlen)) return nullptr;
+  return is_create("vk_is_create_joint_blocks", ctxs, n_ctx, true, cov, opts, n_axes, columns, param_block, n_points, x, y, eps_pow, lno,
+                   lno_prior, n_bins, n_pairs, pair_bins, lists, offsets, base_rows, alpha, every_realisation, chunk, err, errlen);
 }
 
 const char* vk_is_last_error(const vk_is* f) { return f ? f->err.c_str() : ""; }
@@ -2232,7 +2296,10 @@ int vk_is_rows(vk_is* f, int64_t first, int32_t count, double* rows) {
   a.g0 = first;
   a.n = count;
   rc = sampled_launch(f, vk_is_rows_kernel, a.n, kIsBlock, a);
-  if (rc == VK_OK) rc = sampled_home(f, {{rows, f->d_rows, (size_t)count * VK_NPAR * sizeof(double)}}, true);
+  // rows [sets][count][VK_NPAR]: one set, or (vk_is_create_joint_blocks) block q's rows from its set at d_rows + q par_stride
+  const size_t set_doubles = (size_t)count * VK_NPAR;
+  for (int q = 0; q < f->sets && rc == VK_OK; ++q)
+    rc = sampled_home(f, {{rows + q * set_doubles, f->d_rows + q * f->par_stride(), set_doubles * sizeof(double)}}, true);
   if (rc != VK_OK) return sampled_abort(f, rc);
   VK_SAMPLED_HIP(f, hipStreamSynchronize(f->ctx->stream));
   f->err.clear();

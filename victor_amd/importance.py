@@ -1,7 +1,9 @@
 """Importance-sampled posteriors: ``CCFFit.importance_posterior`` and ``Realisations.importance_posterior`` - the evidence, the
 effective sample size, the moments and the marginal histograms of the data vector (R = 1) or of EVERY realisation (R =
 ``len(rs)``) from ONE shared sample of a proposal that covers every problem's posterior, reduced where the likelihoods are
-produced (``vk_is_run``, ``include/victor_hip.h``).
+produced (``vk_is_run``, ``include/victor_hip.h``).  Joint fits: ``JointRealisations.importance_posterior``
+(every joint realisation, ``vk_is_create_joint``; with ``"name@q"`` parameters ``vk_is_create_joint_blocks``) and, for the joint
+data vector, :func:`importance_posterior` itself with the ``JointFit`` for ``fit``.
 
 A point's theory vector is computed once and compared with every realisation (the cross mode of ``Realisations.log_likelihood``),
 so R mocks cost G theory evaluations - the grid's economy (:mod:`victor_amd.grid`) without its limit of two to four axes and
@@ -52,7 +54,7 @@ from . import _native as N
 from .fitting import _Sampled
 from .grid import MAX_CHUNK, default_chunk
 from .marginals import Marginals, cells, slots
-from .priors import tri
+from .priors import resolve_prior, tri
 from .utils import InputError
 
 MAX_AXES = 10
@@ -498,11 +500,21 @@ class ImportancePosterior:
 
 def importance_posterior(fit, params, proposal=None, n=16384, seed=0, fixed=None, prior=None, bins=64, ranges=None, pairs=None,
                          chunk=None, min_ess=50.0, device=True, evaluate=None, sample=None, ln_proposal=None, kwargs=None,
-                         realisations=None):
+                         realisations=None, n_blocks=None):
     """The work of ``CCFFit.importance_posterior`` (``realisations=None``: the fit's data vector, R = 1) and
     ``Realisations.importance_posterior`` (R = the realisations, one shared sample); see the module docstring.  With ``evaluate``
     - a callable taking a dict of ``(n,)`` arrays (sampled and fixed parameters) and returning lnL ``(n,)`` or ``(n, R)`` - in
     place of ``fit`` only the definition route (``device=False``) is possible and no GPU is needed.
+
+    Joint fits: ``fit`` may be a :class:`victor_amd.joint.JointFit` - with ``realisations`` a ``JointRealisations`` this is the
+    work of ``JointRealisations.importance_posterior`` (problem i: joint realisation i), without them the posterior of the JOINT
+    DATA VECTOR (R = 1).  This function is the only way to the latter: ``JointFit`` has no ``importance_posterior`` method, by
+    design (call ``victor_amd.importance.importance_posterior(joint, params, ...)``).  ``"name@q"`` parameters
+    (:func:`victor_amd.joint.per_block`) may then be sampled or fixed under the rules of the other joint loops; a sampled
+    ``epsilon@q`` is refused (a point carries one host ``eps^(-2/3)``), a fixed one is fine.  Without a joint fit a per-block
+    name has nothing to refer to and is refused - except with ``evaluate=`` and ``n_blocks=B`` (``device=False``), the
+    definition route for per-block parameters: the ``@`` names are then checked against B blocks and the callable receives the
+    batch with the ``@`` names as keys.
 
     ``params``: the cobaya block, as ``best_fit`` takes it (``fixed`` values must be scalars); ``proposal``: a
     :class:`GaussianProposal` naming exactly the sampled parameters, drawn ``n`` times with ``seed``; or ``sample`` (G, d) with
@@ -518,15 +530,29 @@ def importance_posterior(fit, params, proposal=None, n=16384, seed=0, fixed=None
         raise InputError(f"{who}: an evaluate callable runs the definition route only (device=False)")
     if evaluate is None and fit is None:
         raise InputError(f"{who}: a fit or an evaluate callable is needed")
-    from .joint import JointFit
-    if isinstance(fit, JointFit):
-        raise InputError(f"{who}: joint fits have no importance posterior")
+    from .joint import JointFit, check_block_names, split_name
+    joint = fit if isinstance(fit, JointFit) else None
+    if n_blocks is not None:
+        if fit is not None or evaluate is None:
+            raise InputError(f"{who}: n_blocks goes with an evaluate callable in place of a fit (a joint fit knows its blocks)")
+        if isinstance(n_blocks, bool) or not isinstance(n_blocks, (int, np.integer)) or n_blocks < 1:
+            raise InputError(f"{who}: n_blocks must be an integer >= 1, not {n_blocks!r}")
     q = _Sampled(who, "sampled", params, fixed)
     names, fixed_all = q.names, q.fixed_all
     d = len(names)
     per_block = sorted(n for n in list(names) + list(fixed_all) if "@" in n)
-    if per_block:
-        raise InputError(f"{who}: per-block parameters ('name@block': {per_block}) have no importance posterior")
+    if per_block and joint is None:
+        # a per-block name needs blocks to refer to: a joint fit's, or the caller's word for them beside an evaluate callable
+        if n_blocks is None:
+            raise InputError(f"{who}: per-block parameters ('name@block': {per_block}) need a joint fit to refer to (or, beside "
+                             "an evaluate callable, n_blocks)")
+        check_block_names(per_block, int(n_blocks), who=who)
+    if joint is not None and evaluate is not None:
+        joint._check_block_names(per_block, who)
+    eps_own = sorted(n for n in names if "@" in n and split_name(n)[0] == "epsilon")
+    if eps_own:
+        raise InputError(f"{who}: epsilon cannot be sampled per block ({eps_own}): a point of the sample carries one eps^(-2/3); "
+                         "fix the per-block epsilons, or sample one epsilon for all blocks")
     if d > MAX_AXES:
         raise InputError(f"{who}: at most {MAX_AXES} sampled parameters ({d} are sampled)")
     if evaluate is None:
@@ -536,12 +562,14 @@ def importance_posterior(fit, params, proposal=None, n=16384, seed=0, fixed=None
     if arrays:
         raise InputError(f"{who}: fixed values must be scalars ({arrays} are not)")
     layout = resolve_layout(who, names, q.lo, q.hi, bins, ranges, pairs)
-    prior = q.prior(prior, fit)
+    prior = resolve_prior(prior, who, names, q.lo, q.hi, fixed_all, joint is not None or n_blocks is not None)
     if realisations is not None and getattr(realisations, "paired_model", False):
         raise InputError(f"{who}: realisations(paired_model=True) have no cross mode (a point has one theory vector per "
                          "realisation): a shared sample evaluates every point once")
     if evaluate is None:
         fit_options = q.fit_options(fit, kwargs)
+    if joint is not None and evaluate is None and len({f._device for f in joint.fits}) != 1:
+        raise InputError(f"{who}: every block of a joint fit must live on the same device")
     if not np.isfinite(min_ess) or min_ess < 0:
         raise InputError(f"{who}: min_ess must be a number >= 0, not {min_ess!r}")
 
@@ -623,40 +651,56 @@ def _check(lib, h, rc, entry):
 
 def create_handle(q, fit, realisations, kwargs, fit_options, layout, smp, lists, fixed_out):
     """``(lib, handle, refresh)`` of ``vk_is_create`` for the sample: the base row from the fixed values (the sampled columns are
-    overwritten per point), the sample's arrays, and per point the host's own ``eps^(-2/3)`` (``vk_epsilon_to_ap``: libm's pow)."""
-    model = fit._merged(kwargs)
-    fit._check_supported(model)
+    overwritten per point), the sample's arrays, and per point the host's own ``eps^(-2/3)`` (``vk_epsilon_to_ap``: libm's pow).
+    Of a :class:`victor_amd.joint.JointFit`: ``vk_is_create_joint`` over the engines, option block, covariance handle and
+    realisation upload every joint device loop uses (``JointFit._sampled_plan`` / ``_sampled_rows`` / ``_sampled_device``); with
+    ``@`` names among the sampled or fixed parameters its ``_blocks`` form, a base row per block."""
+    from .joint import JointFit
     batch = dict(fixed_out)
     batch.update({n: np.array([smp.x[0, j]]) for j, n in enumerate(layout.names)})
-    base = np.ascontiguousarray(fit._fit_rows(batch, model), dtype=np.float64)
-    cols = np.array([N.ROW_COLUMNS.get(n, N.VK_WALK_EPSILON) for n in layout.names], dtype=np.int32)
-    refresh = None
-    if realisations is None:
-        eng = fit._get_engine(fit._engine_key(model), model["simpson_even"])
-        opts = eng.make_opts(model, fit_options)
+    i32 = C.POINTER(C.c_int32)
+    extra = ()
+    if isinstance(fit, JointFit):
+        engines, opts, kw = fit._sampled_plan(q.who, kwargs)
+        base, cols, param_block, _ = fit._sampled_rows(layout.names, batch, kw)
+        entry = "vk_is_create_joint"
+        if param_block is not None:
+            extra = (param_block.ctypes.data_as(i32),)
+            entry += "_blocks"
+        lib, ctxs, cov, refresh = fit._sampled_device(engines, realisations)
+        head = (ctxs, len(engines), cov, C.byref(opts))
     else:
-        _, _, eng, opts = realisations._plan(kwargs)
+        model = fit._merged(kwargs)
+        fit._check_supported(model)
+        base = np.ascontiguousarray(fit._fit_rows(batch, model), dtype=np.float64)
+        cols = np.array([N.ROW_COLUMNS.get(n, N.VK_WALK_EPSILON) for n in layout.names], dtype=np.int32)
+        refresh = None
+        if realisations is None:
+            eng = fit._get_engine(fit._engine_key(model), model["simpson_even"])
+            opts = eng.make_opts(model, fit_options)
+        else:
+            _, _, eng, opts = realisations._plan(kwargs)
 
-        def refresh():
-            realisations._upload(eng)
+            def refresh():
+                realisations._upload(eng)
+        lib, entry, head = eng._lib, "vk_is_create", (eng._ctx, C.byref(opts))
     eps_pow = None
     if "epsilon" in layout.names:
         with np.errstate(invalid="ignore"):
             eps_pow = N.f64(N.epsilon_to_ap(N.f64(smp.x[:, layout.names.index("epsilon")]), 1.0)[1])
-    i32 = C.POINTER(C.c_int32)
     n_bins = np.array(layout.n_bins, dtype=np.int32)
     pair_bins = np.array(layout.pair_bins, dtype=np.int32)
     err = C.create_string_buffer(512)
-    h = eng._lib.vk_is_create(eng._ctx, C.byref(opts), layout.d, cols.ctypes.data_as(i32), smp.G, N.as_dp(smp.x), N.as_dp(smp.y),
-                              None if eps_pow is None else N.as_dp(eps_pow), N.as_dp(smp.lno),
-                              None if smp.lnop is None else N.as_dp(smp.lnop), n_bins.ctypes.data_as(i32), len(pair_bins),
-                              pair_bins.ctypes.data_as(i32) if len(pair_bins) else None, lists.entries.ctypes.data_as(i32),
-                              lists.offsets.ctypes.data_as(i32), N.as_dp(base), float(fixed_out.get("alpha", 1)),
-                              0 if realisations is None else 1, lists.chunk, err, len(err))
+    h = getattr(lib, entry)(*head, layout.d, cols.ctypes.data_as(i32), *extra, smp.G, N.as_dp(smp.x), N.as_dp(smp.y),
+                            None if eps_pow is None else N.as_dp(eps_pow), N.as_dp(smp.lno),
+                            None if smp.lnop is None else N.as_dp(smp.lnop), n_bins.ctypes.data_as(i32), len(pair_bins),
+                            pair_bins.ctypes.data_as(i32) if len(pair_bins) else None, lists.entries.ctypes.data_as(i32),
+                            lists.offsets.ctypes.data_as(i32), N.as_dp(base), float(fixed_out.get("alpha", 1)),
+                            0 if realisations is None else 1, lists.chunk, err, len(err))
     if not h:
         msg = err.value.decode()
         raise (N.NativeError if "device memory" in msg else InputError)(msg)
-    return eng._lib, h, refresh
+    return lib, h, refresh
 
 
 def read_result(lib, h, layout, R, with_prior):

@@ -457,33 +457,58 @@ class JointFit:
         parameters ``q`` (the contract of ``fitting._Sampled.create``): one problem per row of ``batch``, against the joint data
         vector or joint realisation ``which[i]`` of ``realisations``.  The rows are the lead fit's, as
         :meth:`log_likelihood_batch` forms them."""
+        engines, opts, kwargs = self._sampled_plan(q.who, kwargs)
+        rows, cols, param_block, n_rows = self._sampled_rows(q.names, batch, kwargs)
+        i32 = C.POINTER(C.c_int32)
+        extra = ()
+        if param_block is not None:
+            extra = (param_block.ctypes.data_as(i32),)
+            entry += "_blocks"
+        lib, ctxs, handle, refresh = self._sampled_device(engines, realisations)
+        err = C.create_string_buffer(512)
+        h = getattr(lib, entry)(ctxs, len(engines), handle, C.byref(opts), n_rows, *shape, len(cols), cols.ctypes.data_as(i32),
+                                *extra, N.as_dp(N.f64(q.lo)), N.as_dp(N.f64(q.hi)), N.as_dp(rows),
+                                float(q.fixed_all.get("alpha", 1)),
+                                None if realisations is None else which.ctypes.data_as(i32), err, len(err))
+        if not h:
+            msg = err.value.decode()
+            raise (N.NativeError if "device memory" in msg else InputError)(msg)
+        return lib, h, refresh
+
+    # what every handle over the joint lnL shares (the device loops above; ``vk_is_create_joint``: importance.create_handle)
+    def _sampled_plan(self, who, kwargs):
+        """``(engines, opts, kwargs)`` of a device loop over the joint lnL: the blocks' engines, lead first, their one option
+        block, and ``kwargs`` as the blocks' own row builders take them (under a joint covariance without its ``likelihood``).
+        Refused: blocks on different devices, and blocks that cannot share one option block."""
         if len({f._device for f in self.fits}) != 1:
-            raise InputError(f"{q.who}: every block of a joint fit must live on the same device")
+            raise InputError(f"{who}: every block of a joint fit must live on the same device")
         if self.covariance is not None:
             engines, opts = self._plan_cov(kwargs)
-            kwargs = {k: v for k, v in kwargs.items() if k != "likelihood"}
-        else:
-            plan = self._plan(kwargs)
-            if plan is None:
-                raise InputError(f"{q.who}: the blocks of a block-diagonal joint fit must share one option block (their model, "
-                                 "fit options and their data's beta dependence) and one device")
-            engines, opts = plan
-        blocks = has_block_names(batch)
-        extra = ()
-        if blocks:
-            # a row set per block: block b's base rows from the values resolved for it, each sampled value to its own block
+            return engines, opts, {k: v for k, v in kwargs.items() if k != "likelihood"}
+        plan = self._plan(kwargs)
+        if plan is None:
+            raise InputError(f"{who}: the blocks of a block-diagonal joint fit must share one option block (their model, "
+                             "fit options and their data's beta dependence) and one device")
+        return plan[0], plan[1], kwargs
+
+    def _sampled_rows(self, names, batch, kwargs):
+        """``(rows, cols, param_block, n_rows)`` of the sampled ``names`` and the rows of ``batch``: with ``@`` names anywhere in
+        the batch a row set per block, ``rows`` ``(B n_rows, VK_NPAR)`` - block b's base rows from the values resolved for it,
+        each sampled value to its own block (``param_block``, -1: every block) -; otherwise the lead fit's rows and None."""
+        if has_block_names(batch):
             rows = self._block_rows(batch, kwargs).reshape(-1, N.VK_NPAR)
-            split = [split_name(n) for n in q.names]
+            split = [split_name(n) for n in names]
             cols = np.array([N.ROW_COLUMNS.get(base, N.VK_WALK_EPSILON) for base, _ in split], dtype=np.int32)
             param_block = np.array([-1 if b is None else b for _, b in split], dtype=np.int32)
-            extra = (param_block.ctypes.data_as(C.POINTER(C.c_int32)),)
-            entry += "_blocks"
-            n_rows = len(rows) // len(self.fits)
-        else:
-            fit = self.fits[0]
-            rows = np.ascontiguousarray(fit._fit_rows(batch, fit._merged(kwargs)), dtype=np.float64)
-            cols = np.array([N.ROW_COLUMNS.get(n, N.VK_WALK_EPSILON) for n in q.names], dtype=np.int32)
-            n_rows = len(rows)
+            return rows, cols, param_block, len(rows) // len(self.fits)
+        fit = self.fits[0]
+        rows = np.ascontiguousarray(fit._fit_rows(batch, fit._merged(kwargs)), dtype=np.float64)
+        cols = np.array([N.ROW_COLUMNS.get(n, N.VK_WALK_EPSILON) for n in names], dtype=np.int32)
+        return rows, cols, None, len(rows)
+
+    def _sampled_device(self, engines, realisations):
+        """``(lib, ctxs, covariance handle or None, refresh)`` for a create call: ``refresh`` (None against the data vector)
+        makes ``realisations`` the ones set on every block's engine again, and has been called once."""
         refresh = None
         if realisations is not None:
             def refresh(realisations=realisations, engines=list(engines)):
@@ -492,16 +517,7 @@ class JointFit:
         lead = engines[0]
         handle = self._joint_handle(lead) if self.covariance is not None else None
         ctxs = (C.c_void_p * len(engines))(*[e._ctx for e in engines])
-        i32 = C.POINTER(C.c_int32)
-        err = C.create_string_buffer(512)
-        h = getattr(lead._lib, entry)(ctxs, len(engines), handle, C.byref(opts), n_rows, *shape, len(cols), cols.ctypes.data_as(i32),
-                                      *extra, N.as_dp(N.f64(q.lo)), N.as_dp(N.f64(q.hi)), N.as_dp(rows),
-                                      float(q.fixed_all.get("alpha", 1)),
-                                      None if realisations is None else which.ctypes.data_as(i32), err, len(err))
-        if not h:
-            msg = err.value.decode()
-            raise (N.NativeError if "device memory" in msg else InputError)(msg)
-        return lead._lib, h, refresh
+        return lead._lib, ctxs, handle, refresh
 
     def best_fit(self, params, fixed=None, start=None, step=None, xtol=None, ftol=1e-6, max_iter=None, restarts=1, prior=None,
                  covariance=None, **kwargs):
@@ -629,6 +645,20 @@ class JointRealisations:
         from .nested import nested_sampling
         return nested_sampling(self.joint, params, n_live, batch, steps, scale, seed, fixed, tol, max_iter, n_iter, keep_dead, device,
                                evaluate, kwargs, realisations=self)
+
+    def importance_posterior(self, params, proposal=None, n=16384, seed=0, fixed=None, prior=None, bins=64, ranges=None, pairs=None,
+                             chunk=None, min_ess=50.0, device=True, evaluate=None, sample=None, ln_proposal=None, **kwargs):
+        """The posterior of EVERY joint realisation from ONE shared importance sample (problem i: realisation ``numbers[i]`` of
+        every block): a point's theory vectors are computed once per block and compared with all joint realisations, under the
+        joint covariance (fixed or gridded in beta) or block-diagonal, and the evidence, the effective sample size, the moments
+        and the marginal histograms of each are reduced on the GPU (``device=True``, ``vk_is_create_joint``) or by the NumPy
+        loop over :meth:`log_likelihood` that defines them (``device=False``).  ``"name@q"`` parameters (:func:`per_block`) may be
+        sampled or fixed - a sampled ``epsilon@q`` is refused - and a ``prior`` may name them.  Arguments and result as
+        ``Realisations.importance_posterior`` (:mod:`victor_amd.importance`).  The joint data vector itself (R = 1) goes through
+        ``victor_amd.importance.importance_posterior(joint, params, ...)``."""
+        from .importance import importance_posterior
+        return importance_posterior(self.joint, params, proposal, n, seed, fixed, prior, bins, ranges, pairs, chunk, min_ess, device,
+                                    evaluate, sample, ln_proposal, kwargs, realisations=self)
 
     def _eval(self, params, kwargs, which=None):
         joint = self.joint
