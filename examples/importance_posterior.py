@@ -9,9 +9,15 @@
   ``nested_sampling``, as pulls in units of the two errors combined;
 * ``--joint``: the same three steps for the five-quantile density-split fit under one covariance with a ``sigma_v`` per
   quantile (d = 7): ``JointRealisations.importance_posterior`` for the mock stack (``--stack`` mocks per block), and for
-  R = 1 the joint data vector through ``victor_amd.importance.importance_posterior(joint, ...)``.
+  R = 1 the joint data vector through ``victor_amd.importance.importance_posterior(joint, ...)``;
+* ``--predictive``: the same call with ``predictive=True`` - the posterior band of the model multipoles and the DIC of the first
+  mocks, from the theory vectors the sample already computed; with ``--timing`` three routes alternate instead of two: the
+  device route without and with ``predictive``, and the definition route with it (``device=False, predictive=True``: what a
+  user could assemble before from ``theory_vector_batch`` and NumPy) up to ``--definition-max`` problems, beyond it once
+  (``--definition-once-max``: beyond that not at all).
 
-    python examples/importance_posterior.py [--joint] [--timing] [--evidence] [--sizes 1,16,1024] [--samples 5] [--out FILE]
+    python examples/importance_posterior.py [--joint] [--timing] [--evidence] [--predictive] [--sizes 1,16,1024] [--samples 5]
+                                            [--out FILE]
 
 Needs a GPU and the test fixtures of the repository (tests/golden)."""
 
@@ -27,10 +33,48 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def timed(obj, params, q, device, n):
+def timed(obj, params, q, device, n, predictive=None):
     t = time.perf_counter()
-    ip = obj.importance_posterior(params, q, n=n, seed=0, device=device)
+    ip = obj.importance_posterior(params, q, n=n, seed=0, device=device, predictive=predictive)
     return time.perf_counter() - t, ip
+
+
+def show_predictive(ip, first=3):
+    """The band of the first multipole's first bins and the DIC of the first mocks."""
+    p = ip.predictive
+    poles = p.multipoles if p.multipoles is not None else p.multipoles_of(0)
+    ell = sorted(poles)[0]
+    mean, std = poles[ell]
+    for r in range(min(first, len(ip))):
+        band = ", ".join(f"{m:+.4f} +- {s:.4f}" for m, s in zip(mean[r, :4], std[r, :4]))
+        print(f"mock {r}: ell = {ell} band, first bins: {band}")
+        print(f"        <chi2> {p.mean_chi2[r]:.2f}, chi2 at the mean {p.chi2_at_mean[r]:.2f}, p_D {p.p_d[r]:.2f}, p_V {p.p_v[r]:.2f}, "
+              f"DIC {p.dic[r]:.2f}")
+    return {"mean_chi2": p.mean_chi2.tolist(), "chi2_at_mean": p.chi2_at_mean.tolist(), "p_d": p.p_d.tolist(), "p_v": p.p_v.tolist(),
+            "dic": p.dic.tolist()}
+
+
+def three_routes(run, R, args):
+    """``--timing --predictive``: device off / device on / definition on, alternating after a warm-up of each; the definition
+    beyond ``--definition-max`` problems runs once, un-warmed (it takes minutes there), and beyond ``--definition-once-max`` not at
+    all."""
+    many = R <= args.definition_max
+    off, on, ref = [], [], []
+    run(True, None)
+    run(True, True)
+    if many:
+        run(False, True)
+    for i in range(args.samples):
+        off.append(run(True, None)[0])
+        on.append(run(True, True)[0])
+        if many or (i == 0 and R <= args.definition_once_max):
+            ref.append(run(False, True)[0])
+    med = {k: float(np.median(v)) if v else float("nan") for k, v in (("off", off), ("on", on), ("definition", ref))}
+    print(f"R={R}: device {med['off']:.3f} s ({min(off):.3f} .. {max(off):.3f}), with predictive {med['on']:.3f} s ({min(on):.3f} .. "
+          f"{max(on):.3f}), added {1e3 * (med['on'] - med['off']):.1f} ms; definition with predictive {med['definition']:.2f} s "
+          f"({len(ref)} run{'s' if len(ref) > 1 else ''}), ratio {med['definition'] / med['on']:.1f}", flush=True)
+    return {"device_off_s": med["off"], "device_on_s": med["on"], "definition_on_s": med["definition"], "device_off_all": off,
+            "device_on_all": on, "definition_on_all": ref}
 
 
 def joint_main(args):
@@ -51,12 +95,12 @@ def joint_main(args):
     jr = joint.realisations()
     res = {"n": args.n, "stack": args.stack}
 
-    def run(obj, device):
+    def run(obj, device, predictive=None):
         t = time.perf_counter()
         if obj is joint:       # the joint data vector (R = 1): JointFit has no method of this name, the module function is the way
-            ip = importance_posterior(joint, params, q, n=args.n, seed=0, fixed=fixed, device=device)
+            ip = importance_posterior(joint, params, q, n=args.n, seed=0, fixed=fixed, device=device, predictive=predictive)
         else:
-            ip = obj.importance_posterior(params, q, n=args.n, seed=0, fixed=fixed, device=device)
+            ip = obj.importance_posterior(params, q, n=args.n, seed=0, fixed=fixed, device=device, predictive=predictive)
         return time.perf_counter() - t, ip
 
     t = time.perf_counter()
@@ -73,11 +117,16 @@ def joint_main(args):
     print("ESS per mock", np.round(ip.ess).astype(int).tolist())
     print("ln_evidence", np.round(ip.ln_evidence, 3).tolist())
     print("error      ", np.round(ip.ln_evidence_error, 4).tolist(), flush=True)
+    if args.predictive:
+        res["predictive"] = show_predictive(run(jr, True, True)[1])
 
     if args.timing:
         res["timing"] = {}
         for R in (int(v) for v in args.sizes.split(",")):
             obj = joint if R == 1 else jr if R == args.stack else joint.realisations(list(np.arange(R) % args.stack))
+            if args.predictive:
+                res["timing"][f"R={R}"] = three_routes(lambda device, predictive, obj=obj: run(obj, device, predictive), R, args)
+                continue
             dev, ref = [], []
             run(obj, True)                                       # a warm-up of each route
             run(obj, False)
@@ -112,6 +161,9 @@ def main():
     ap.add_argument("--sizes", default="1,16,1024", help="problem counts of --timing")
     ap.add_argument("--samples", type=int, default=5)
     ap.add_argument("--n", type=int, default=65536, help="draws")
+    ap.add_argument("--predictive", action="store_true", help="the posterior band and the DIC; with --timing its cost")
+    ap.add_argument("--definition-max", type=int, default=16, help="problems up to which --timing --predictive repeats the definition route")
+    ap.add_argument("--definition-once-max", type=int, default=1024, help="... and up to which it runs it at least once")
     args = ap.parse_args()
     if args.joint:
         return joint_main(args)
@@ -144,11 +196,16 @@ def main():
     for j, n in enumerate(ip.names):
         lo, hi = ip.interval(n, 0.68)
         print(f"{n:8s} mock 0: mean {ip.mean[0, j]:.4f} sigma {ip.sigma[0, j]:.4f} median {ip.median(n)[0]:.4f} 68% [{lo[0]:.4f}, {hi[0]:.4f}]")
+    if args.predictive:
+        res["predictive"] = show_predictive(timed(rs, params, q, True, args.n, True)[1])
 
     if args.timing:
         res["timing"] = {}
         for R in (int(v) for v in args.sizes.split(",")):
             obj = data_fit if R == 1 else rs if R == 16 else stack.realisations(list(np.arange(R) % 16))
+            if args.predictive:
+                res["timing"][f"R={R}"] = three_routes(lambda device, predictive, obj=obj: timed(obj, params, q, device, args.n, predictive), R, args)
+                continue
             dev, ref = [], []
             timed(obj, params, q, True, args.n)                   # a warm-up of each route
             timed(obj, params, q, False, args.n)

@@ -867,6 +867,26 @@ int vk_is_result(vk_is* h, double* ln_max, int64_t* arg_max, int64_t* n_finite, 
                  double* h1, double* h2, double* prior_ln_max, double* prior_total);
 const char* vk_is_last_error(const vk_is* h);
 void vk_is_destroy(vk_is* h);
+/* Posterior-predictive sums of the sample (victor_amd/csrc/vk_is_predict.h; the definition: victor_amd/importance.py): per problem
+ * the weighted first and second sums of the points' THEORY VECTORS and of their chi2 and lnL, taken from what every chunk leaves
+ * on the device - one more launch per chunk (of a joint handle one per block), no further theory evaluation.
+ * vk_is_set_predictive(h, on): before the first vk_is_run (a completed run's results are dropped: the next run starts at point
+ *   0); on != 0 allocates the state beside the handle's allocation - (1 + 2 R) N + 6 R + chunk R doubles, N the entries of a
+ *   theory vector, of a joint handle the sum of the blocks' - and makes the evaluation keep the points' vectors, which changes no
+ *   bit of lnL, of chi2 or of anything vk_is_result returns; on == 0 releases it, and the handle allocates and launches what it
+ *   did before.  Refused: a run under way; a block whose theory vector has more than 2^17 entries.
+ * The rules, per chunk: pivot_t = the theory vector of point 0 where finite, else 0 (one vector for all problems; of a joint
+ *   handle the blocks' vectors in block order); pivot_chi2[r], pivot_lnl[r] = chi2 and lnL of point 0 for problem r where finite,
+ *   else 0.  Every sum is multiplied ONCE by the chunk's factor exp(M - M'); then every point with w > 0 adds, with v = T - pivot_t,
+ *   a = chi2 - pivot_chi2[r], b = lnl - pivot_lnl[r]:  w v and (w v) v per entry;  w a, (w a) a, w b, (w b) b.  A point of weight 0
+ *   adds nothing.  Each difference and product is rounded on its own; the additions run in a fixed order of the kernel's (four
+ *   slices of the chunk, combined in slice order), so two runs give the same bytes, and the sums agree with the definition's
+ *   (increasing g) to rounding.  The prior's own problem keeps no such sums.
+ * vk_is_predictive, after a run has reached G: pivot_t [N]; sum_t, sum_tt [N][R] - entry k of problem r at k R + r -; pivots
+ *   [2][R]: pivot_chi2 | pivot_lnl; deviance [4][R]: sum w a | sum (w a) a | sum w b | sum (w b) b.  Any may be NULL.  The sums are
+ *   in units of the weights of vk_is_result: divide by total[r]. */
+int vk_is_set_predictive(vk_is* h, int32_t on);
+int vk_is_predictive(vk_is* h, double* pivot_t, double* sum_t, double* sum_tt, double* pivots, double* deviance);
 
 /* ---- nested sampling: the evidence and a posterior sample of the data vector or of every realisation ---------------------------
  * R problems of L live points each inside the box [lo, hi]; per iteration the K lowest live points of every problem die and K

@@ -1742,6 +1742,18 @@ vkh::JointRealWs vkh::joint_real_carve(const vk_joint_cov* h, double* d_ws, long
   return w;
 }
 
+const double* vkh::joint_theory_segment(const vk_joint_cov* h, vk_ctx* const* ctxs, int n_ctx, int q, long long m, bool real,
+                                        long long cross, const double* d_ws) {
+  int n_max = 0, off = 0;
+  for (int b = 0; b < n_ctx; ++b) {
+    n_max = std::max(n_max, ctxs[b]->N);
+    if (b < q) off += ctxs[b]->N;
+  }
+  if (h) return d_ws + (size_t)m * off;                             // joint_args: th + n off_q, data vectors and realisations alike
+  const long long nv = real ? m * std::max<long long>(cross, 1) : m;   // values of lnl and of chi2 in front of a block's vectors
+  return d_ws + (size_t)q * (size_t)(2 * nv + m * n_max) + (size_t)(2 * nv);
+}
+
 int vkh::joint_cov_n_beta(const vk_joint_cov* h) { return h ? h->n_beta : 0; }
 
 vkh::JointCovView vkh::joint_cov_view(const vk_joint_cov* h) {

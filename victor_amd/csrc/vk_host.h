@@ -220,6 +220,13 @@ int enqueue_joint_cov_realisations(vk_joint_cov* h, vk_ctx* const* ctxs, int n_c
 int enqueue_joint_sum_realisations(vk_ctx* const* ctxs, int n_ctx, const vk_eval_opts* opts, const double* d_par,
                                    long long par_stride, long long m, const int32_t* d_which, double* d_lnl, double* d_chi,
                                    double* d_ws);
+// Where block q's theory vectors [m][N_q] lie in the workspace d_ws after a joint evaluation of m rows by any of the four routes
+// of vk_sampled.hip's sampled_evaluate (h: under a covariance; real: against realisations, in cross mode with `cross` of them) -
+// the layouts of joint_args, vk_joint_eval_blocks_device_async and enqueue_joint_sum_realisations, stated once more for the
+// readers of a chunk's vectors (vk_is_set_predictive).  Block-diagonal against the data vectors the blocks' fused tails store
+// their vectors only with vk_ctx::theory_wanted set at the enqueue.
+const double* joint_theory_segment(const vk_joint_cov* h, vk_ctx* const* ctxs, int n_ctx, int q, long long m, bool real, long long cross,
+                                   const double* d_ws);
 // slices of the handle's beta grid (0: one fixed covariance, or no handle)
 int joint_cov_n_beta(const vk_joint_cov* h);
 // the handle's precision tables on the device, for vk_fit_fisher: the beta grid [n_beta] (NULL: one fixed covariance) and the

@@ -47,6 +47,9 @@
 //   vk_kernel_importance.h importance-sampled posteriors (vk_is_run; the section behind the grid's): rows, max, weight and accumulate
 //                        kernels of a chunk of an uploaded sample, over the index rules, the list walk and the terms of
 //                        vk_importance.h (plain C++, likewise)
+//   vk_kernel_is_predict.h the posterior-predictive sums of an importance handle (vk_is_set_predictive): the product kernel behind
+//                        every chunk's accumulate kernel, weights x theory vectors, over the tile and index rules and the terms
+//                        of vk_is_predict.h (plain C++, likewise)
 //   vk_kernel_nested.h   nested sampling (vk_nested_begin; the last section of this file): the select kernel, one workgroup per
 //                        problem, and the step and commit kernels, one thread per replacement walker, over the order, the pick,
 //                        the constrained step and the commit of vk_nested_step.h (plain C++, likewise)
@@ -73,6 +76,7 @@
 #include "vk_kernel_fisher.h"
 #include "vk_kernel_grid.h"
 #include "vk_kernel_importance.h"
+#include "vk_kernel_is_predict.h"
 #include "vk_kernel_nested.h"
 
 using namespace vk;
@@ -375,9 +379,13 @@ static int sampled_evaluate(Sampled* f, long long m, double* d_lnl, double* d_ch
     vk_ctx* const* cs = f->blocks.data();
     const int nb = (int)f->blocks.size();
     const long long ps = f->par_stride();  // block q's rows: d_rows + q * ps (0: one row set)
-    if (!f->real)
+    if (!f->real) {
+      // (block-diagonal, each block's launch carries its own lnL: as above, keep_theory asks the fused tails for the stores)
+      for (int q = 0; q < nb; ++q) cs[q]->theory_wanted = f->keep_theory && !f->cov;
       rc = f->cov ? vk_joint_cov_eval_blocks_device_async(f->cov, cs, nb, &f->opts, f->d_rows, ps, m, d_lnl, d_chi, f->d_th)
                   : vk_joint_eval_blocks_device_async(cs, nb, &f->opts, f->d_rows, ps, m, d_lnl, d_chi, f->d_th);
+      for (int q = 0; q < nb; ++q) cs[q]->theory_wanted = false;
+    }
     else if (f->cov)
       rc = vkh::enqueue_joint_cov_realisations(f->cov, cs, nb, &f->opts, f->d_rows, ps, m, f->d_row_which, d_lnl, d_chi,
                                                vkh::joint_real_carve(f->cov, f->d_th, (long long)f->rows_max));
@@ -2010,6 +2018,21 @@ struct __attribute__((visibility("hidden"))) vk_is : Sampled {
   double *d_x = nullptr, *d_y = nullptr, *d_eps = nullptr, *d_lno = nullptr, *d_lnop = nullptr, *d_lnl = nullptr, *d_chi = nullptr;
   double *d_wp = nullptr, *d_acc = nullptr;
   int *d_list = nullptr, *d_off = nullptr;
+  // the posterior-predictive state of vk_is_predict.h, beside the one allocation (vk_is_set_predictive; pred_N == 0: none):
+  // pivot_t [N] | pt, ptt [N][R] | pivots [2][R] | dev [4][R] | the chunk's weights [chunk][R], which then leave d_chi alone
+  DevBlock pred_mem;
+  int pred_N = 0;                          // entries of a theory vector (of a joint handle: of the joint vector)
+  double *p_pivot_t = nullptr, *p_pt = nullptr, *p_ptt = nullptr, *p_pivots = nullptr, *p_dev = nullptr, *p_w = nullptr;
+
+  void predictive_layout(Carve& c, size_t N) {
+    const size_t r = (size_t)R;
+    c.take(p_pivot_t, N);
+    c.take(p_pt, N * r);
+    c.take(p_ptt, N * r);
+    c.take(p_pivots, 2 * r);
+    c.take(p_dev, (size_t)vkisp::kDeviance * r);
+    c.take(p_w, (size_t)chunk * r);
+  }
 
   void shape(int, const double*, const double*) { rows_max = (size_t)chunk; }
   long long offsets_per_chunk() const { return (long long)n_cells + n_lists; }
@@ -2051,7 +2074,7 @@ static IsArgs is_args(const vk_is* f) {
   a.lno = f->d_lno;
   a.lnop = f->own ? f->d_lnop : nullptr;
   a.lnl = f->d_lnl;
-  a.w = f->d_chi;
+  a.w = f->pred_N ? f->p_w : f->d_chi;    // (with predictive sums the chi-squares survive to vk_is_predict_kernel)
   a.wp = f->d_wp;
   a.run = f->d_run;
   a.acc = f->d_acc;
@@ -2085,6 +2108,39 @@ static int is_ready(vk_is* f, const char* who) {
   return VK_OK;
 }
 
+// The predictive sums of the chunk just accumulated (n rows from kept point g0): one launch of vk_is_predict_kernel - of a joint
+// handle one per block segment, which the block's vectors were left in by the route that evaluated the chunk
+// (vkh::joint_theory_segment).  On the lead stream, which every route has put behind the blocks' streams.
+static int is_predict(vk_is* f, long long g0, int n) {
+  IsPredictArgs q{};
+  q.n = n;
+  q.R = f->R;
+  q.pr = vkisp::problems_per_wave(f->R);
+  q.first = g0 == 0 ? 1 : 0;
+  q.w = f->p_w;
+  q.chi2 = f->d_chi;
+  q.lnl = f->d_lnl;
+  q.run = f->d_run;
+  q.pivots = f->p_pivots;
+  q.dev = f->p_dev;
+  const int nb = (int)f->blocks.size();
+  size_t off = 0;
+  for (int b = 0; b < (nb ? nb : 1); ++b) {
+    q.N = nb ? f->blocks[b]->N : f->ctx->N;
+    q.th = nb ? vkh::joint_theory_segment(f->cov, f->blocks.data(), nb, b, n, f->real, f->cross, f->d_th) : f->d_th;
+    q.deviance = b == 0 ? 1 : 0;
+    q.pivot_t = f->p_pivot_t + off;
+    q.pt = f->p_pt + off * (size_t)f->R;
+    q.ptt = f->p_ptt + off * (size_t)f->R;
+    const dim3 grid((unsigned)vkisp::problem_tiles(q.R, q.pr), (unsigned)(vkisp::entry_tiles(q.N, q.pr) + q.deviance));
+    if (q.pr == vkisp::kWave) hipLaunchKernelGGL(vk_is_predict_kernel<true>, grid, dim3(vkisp::kBlock), 0, f->ctx->stream, q);
+    else hipLaunchKernelGGL(vk_is_predict_kernel<false>, grid, dim3(vkisp::kBlock), 0, f->ctx->stream, q);
+    VK_SAMPLED_HIP(f, hipGetLastError());
+    off += (size_t)q.N;
+  }
+  return VK_OK;
+}
+
 // the launches of points [first, end), chunk by chunk
 static int is_chunks(vk_is* f, long long first, long long end) {
   IsArgs a = is_args(f);
@@ -2099,6 +2155,7 @@ static int is_chunks(vk_is* f, long long first, long long end) {
     if (rc == VK_OK) rc = sampled_launch(f, vk_is_max_kernel, (long long)((a.Rp + a.pr - 1) / a.pr) * kIsBlock, kIsBlock, a);
     if (rc == VK_OK) rc = sampled_launch(f, vk_is_weight_kernel, (long long)a.n * a.Rp, kIsBlock, a);
     if (rc == VK_OK) rc = sampled_launch(f, vk_is_accumulate_kernel, (long long)a.n_acc * a.Rp, kIsBlock, a);
+    if (rc == VK_OK && f->pred_N) rc = is_predict(f, g0, a.n);
   }
   if (rc) return rc;
   VK_SAMPLED_HIP(f, hipStreamSynchronize(f->ctx->stream));
@@ -2260,7 +2317,47 @@ vk_is* vk_is_create_joint_blocks(vk_ctx* const* ctxs, int32_t n_ctx, vk_joint_co
 const char* vk_is_last_error(const vk_is* f) { return f ? f->err.c_str() : ""; }
 
 void vk_is_destroy(vk_is* f) {
-  if (f) sampled_destroy(f);
+  if (!f) return;
+  f->pred_mem.drop(f);
+  sampled_destroy(f);
+}
+
+// The posterior-predictive sums (vk_is_predict.h).  Everything vk_is_predict_kernel indexes with is fixed here: R, the chunk and
+// the entries of the theory vectors - of a joint handle the blocks' N, in block order - size the state it addresses.
+int vk_is_set_predictive(vk_is* f, int32_t on) {
+  if (!f) return VK_E_ARG;
+  const std::string me = "vk_is_set_predictive: ";
+  if (f->done != 0 && f->done != f->G) return refused(f, me + "a run is under way (call it before the first vk_is_run)");
+  f->pred_mem.drop(f);
+  f->pred_N = 0;
+  f->keep_theory = false;
+  f->done = 0;                             // (the sums belong to a whole run: the next one starts at point 0)
+  f->err.clear();
+  if (!on) return VK_OK;
+  long long N = 0;
+  if (f->blocks.empty()) N = f->ctx->N;
+  for (const vk_ctx* b : f->blocks) N += b->N;
+  for (size_t b = 0; b < (f->blocks.empty() ? 1 : f->blocks.size()); ++b)
+    if ((f->blocks.empty() ? f->ctx : f->blocks[b])->N > vkisp::kMaxEntries)
+      return refused(f, me + "a theory vector of more than 2^17 entries");
+  VK_SAMPLED_HIP(f, hipSetDevice(f->ctx->device));
+  const int rc = f->pred_mem.make(f, me, [&](Carve& c) { f->predictive_layout(c, (size_t)N); });
+  if (rc) return rc;
+  f->pred_N = (int)N;
+  f->keep_theory = true;
+  return VK_OK;
+}
+
+int vk_is_predictive(vk_is* f, double* pivot_t, double* sum_t, double* sum_tt, double* pivots, double* deviance) {
+  if (!f) return VK_E_ARG;
+  if (!f->pred_N) return refused(f, "vk_is_predictive: the handle has no predictive sums (vk_is_set_predictive)");
+  if (f->done != f->G) return refused(f, "vk_is_predictive: the run has reached " + std::to_string(f->done) + " of " + std::to_string(f->G) + " points");
+  VK_SAMPLED_HIP(f, hipSetDevice(f->ctx->device));
+  const size_t one = (size_t)f->R * sizeof(double), vec = (size_t)f->pred_N * sizeof(double);
+  const int rc = sampled_home(f, {{pivot_t, f->p_pivot_t, vec}, {sum_t, f->p_pt, vec * f->R}, {sum_tt, f->p_ptt, vec * f->R},
+                                  {pivots, f->p_pivots, 2 * one}, {deviance, f->p_dev, vkisp::kDeviance * one}});
+  if (rc == VK_OK) f->err.clear();
+  return rc;
 }
 
 int vk_is_run(vk_is* f, int64_t first, int64_t count) {

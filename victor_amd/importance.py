@@ -43,6 +43,24 @@ each mock.
    ``s2`` and the centre; histograms through the reader of :mod:`victor_amd.marginals`; ``outside_mass`` from the below and above
    slots; ``status``: ``OK``, ``LOW_ESS`` (``ess < min_ess``), ``NO_FINITE`` (no point was finite: evidence -inf, no NaN in any
    sum).
+6. *Predictive* (``predictive=True``; :class:`SamplePredictive`, ``ip.predictive``): the posterior mean and scatter of the THEORY
+   VECTOR of every problem - the band drawn through the data multipoles - and the moments of its deviance, from the weights
+   the step already forms and the theory vectors the evaluation already computes: no further theory evaluation, and R mocks
+   share the G vectors.  T[g] is the theory vector of kept point g, N entries; of a joint fit the blocks' vectors concatenated
+   in block order.  *Pivots*: ``pivot_t = T[0]`` where its entries are finite, else 0 - one vector for all problems -;
+   ``pivot_chi2[r] = chi2[0][r]`` and ``pivot_lnl[r] = lnl[0][r]`` where finite, else 0.  *Per chunk*, after the step's own
+   rescale and with its weights: every predictive accumulator is multiplied by the chunk's factor f ONCE (each term is linear
+   in w); then every point with ``w > 0`` adds, with ``v = T - pivot_t``, ``a = chi2 - pivot_chi2[r]`` and ``b = lnl -
+   pivot_lnl[r]``, the terms ``w v`` and ``(w v) v`` to ``pt[r]`` and ``ptt[r]`` (N entries each) and ``w a``, ``(w a) a``, ``w
+   b``, ``(w b) b`` to the four deviance sums ``dev[r]`` - each difference and product rounded on its own.  A point with ``w ==
+   0`` adds nothing, so no NaN of a failed point can enter a sum.  The prior's own problem keeps no such sums.  The definition
+   adds in increasing g; the device adds in a fixed order of its own (``victor_amd/csrc/vk_is_predict.h``), so the two routes
+   agree to rounding and each gives the same bytes twice.  The definition route takes its vectors from the batched theory call
+   on the rows the likelihood call forms (``theory_vector_batch``; per block and concatenated for a joint fit -
+   :func:`victor_amd.fisher.host_vectors`) and chi2 from the call that gives it lnL.  *The read-out*, in ``np.longdouble``:
+   ``mean = pivot + pt / total``, ``var = ptt / total - (pt / total)^2`` (weighted, no ddof: as ``cov``); D = -2 lnL carries no
+   prior term, the weights do; ``p_d = mean_D - D(mean position)``, ``p_v = var_D / 2``, ``dic = mean_D + p_d``, with the
+   likelihood at ``ip.mean[r]`` from one pairs call after the run.  A ``NO_FINITE`` problem reads NaN throughout.
 """
 
 import ctypes as C
@@ -294,10 +312,15 @@ class Lists:
 class Sums:
     """What a run returns per problem (the arrays of ``vk_is_result``): ``ln_max``, ``arg_max``, ``n_finite``, ``total``, ``sq``
     (R,); ``s1`` (R, d); ``s2`` (R, d (d + 1) / 2), the packed upper triangle; ``h1`` (R, sum (bins_j + 2)); ``h2`` (R, sum
-    m_q^2)."""
+    m_q^2).  With ``n_theory=N`` (rule 6; the arrays of ``vk_is_predictive``) also ``pivot_t`` (N,), ``pt``, ``ptt`` (R, N),
+    ``pivots`` (2, R): pivot_chi2, pivot_lnl, and ``dev`` (4, R): sum w a, (w a) a, w b, (w b) b; without it no such attribute."""
 
-    def __init__(self, layout, R):
+    def __init__(self, layout, R, n_theory=None):
         d = layout.d
+        if n_theory is not None:
+            self.pivot_t = np.zeros(n_theory)
+            self.pt, self.ptt = np.zeros((R, n_theory)), np.zeros((R, n_theory))
+            self.pivots, self.dev = np.zeros((2, R)), np.zeros((4, R))
         self.ln_max = np.full(R, -np.inf)
         self.arg_max = np.full(R, -1, dtype=np.int64)
         self.n_finite = np.zeros(R, dtype=np.int64)
@@ -314,9 +337,48 @@ def _add_in_order(acc, terms):
     return np.add.accumulate(np.concatenate([acc[None, :], terms], axis=0), axis=0)[-1]
 
 
-def step_definition(layout, lists, c, y, acc, g0, lnpost, total_only=False):
+def _pivot(v):
+    v = np.asarray(v, dtype=np.float64)
+    return np.where(np.isfinite(v), v, 0.0)
+
+
+def _predictive_step(acc, g0, f, w, theory, chi2, lnl):
+    """Rule 6 for one chunk: the factors ``f`` (R,) and weights ``w`` (n, R; None: nothing is live yet) of the step just made,
+    the points' theory vectors (n, N), chi2 and lnL (n, R)."""
+    theory, chi2, lnl = (np.asarray(v, dtype=np.float64) for v in (theory, chi2, lnl))
+    if g0 == 0:
+        acc.pivot_t = _pivot(theory[0])
+        acc.pivots = np.stack([_pivot(chi2[0]), _pivot(lnl[0])])
+    acc.pt, acc.ptt, acc.dev = acc.pt * f[:, None], acc.ptt * f[:, None], acc.dev * f[None, :]
+    if w is None:
+        return
+    on = w > 0
+
+    off = ~on
+
+    def in_order(acc, terms):                                    # _add_in_order on an array of the caller's own: no copy
+        terms[0] += acc
+        return np.add.accumulate(terms, axis=0, out=terms)[-1].copy()
+
+    def add(s1, s2, values, pivot):
+        with np.errstate(invalid="ignore", over="ignore"):
+            v = values - pivot
+            wv = w * v
+            wv[off] = 0.0                                        # (a point of weight 0 adds nothing, whatever it holds)
+            wvv = wv * v
+            wvv[off] = 0.0
+        return in_order(s1, wv), in_order(s2, wvv)
+
+    for k in range(theory.shape[1]):
+        acc.pt[:, k], acc.ptt[:, k] = add(acc.pt[:, k], acc.ptt[:, k], theory[:, k, None], acc.pivot_t[k])
+    acc.dev[0], acc.dev[1] = add(acc.dev[0], acc.dev[1], chi2, acc.pivots[0][None, :])
+    acc.dev[2], acc.dev[3] = add(acc.dev[2], acc.dev[3], lnl, acc.pivots[1][None, :])
+
+
+def step_definition(layout, lists, c, y, acc, g0, lnpost, total_only=False, predictive=None):
     """Rule 3 of the module docstring for chunk ``c``: ``lnpost`` (n, R) of the points ``g0 .. g0 + n - 1``, whose centred
-    coordinates are ``y`` (n, d), into the :class:`Sums` ``acc``, in place."""
+    coordinates are ``y`` (n, d), into the :class:`Sums` ``acc``, in place.  ``predictive``: ``(theory (n, N), chi2 (n, R), lnl
+    (n, R))`` of the chunk's points, for rule 6 (``acc`` was made with ``n_theory=N``)."""
     lnpost = np.asarray(lnpost, dtype=np.float64)
     lnpost = np.where(np.isfinite(lnpost), lnpost, -np.inf)
     acc.n_finite += np.count_nonzero(lnpost > -np.inf, axis=0)
@@ -332,9 +394,13 @@ def step_definition(layout, lists, c, y, acc, g0, lnpost, total_only=False):
     acc.s1, acc.s2, acc.h1, acc.h2 = acc.s1 * f[:, None], acc.s2 * f[:, None], acc.h1 * f[:, None], acc.h2 * f[:, None]
     live = acc.ln_max > -np.inf
     if not np.any(live):
+        if predictive is not None:
+            _predictive_step(acc, g0, f, None, *predictive)
         return
     with np.errstate(invalid="ignore"):
         w = np.where(live, np.exp(lnpost - acc.ln_max), 0.0)
+    if predictive is not None:
+        _predictive_step(acc, g0, f, w, *predictive)
     acc.total = _add_in_order(acc.total, w)
     if total_only:
         return
@@ -352,24 +418,89 @@ def step_definition(layout, lists, c, y, acc, g0, lnpost, total_only=False):
             h[:, base + k] = _add_in_order(h[:, base + k], w[entries[off[k]:off[k + 1]]])
 
 
-def run_definition(layout, sample, lists, R, values):
+def run_definition(layout, sample, lists, R, values, theory=None):
     """The definition: ``values(x)`` gives lnL ``(n, R)`` (or ``(n,)``: R = 1) at the points ``x`` (n, d) of a chunk; ``R`` None:
-    whatever the first chunk returns.  Returns ``(Sums, the prior's own Sums or None)``."""
+    whatever the first chunk returns.  Returns ``(Sums, the prior's own Sums or None)``.  With ``theory`` - ``theory(x)`` gives
+    the points' theory vectors (n, N) - rule 6 runs along, and ``values(x)`` gives ``(lnL, chi2)``, both (n, R)."""
     acc = None
     pacc = Sums(layout, 1) if sample.lnop is not None else None
     chunk = lists.chunk
     for c in range(lists.n_chunks):
         g0 = c * chunk
         x, y, lno = sample.x[g0:g0 + chunk], sample.y[g0:g0 + chunk], sample.lno[g0:g0 + chunk]
-        lnl = np.asarray(values(x), dtype=np.float64)
+        pred = None
+        if theory is None:
+            lnl = np.asarray(values(x), dtype=np.float64)
+        else:
+            lnl, chi2 = (np.asarray(v, dtype=np.float64) for v in values(x))
         lnl = lnl.reshape(len(x), -1 if R is None else R)
+        if theory is not None:
+            vectors = np.asarray(theory(x), dtype=np.float64).reshape(len(x), -1)
+            pred = (vectors, chi2.reshape(lnl.shape), lnl)
         if acc is None:
             R = lnl.shape[1]
-            acc = Sums(layout, R)
+            acc = Sums(layout, R, None if pred is None else vectors.shape[1])
         if pacc is not None:
             step_definition(layout, lists, c, y, pacc, g0, sample.lnop[g0:g0 + chunk, None], total_only=True)
-        step_definition(layout, lists, c, y, acc, g0, lnl + lno[:, None])
+        step_definition(layout, lists, c, y, acc, g0, lnl + lno[:, None], predictive=pred)
     return acc, pacc
+
+
+class SamplePredictive:
+    """What ``ImportancePosterior.predictive`` holds (rule 6 of the module docstring), read the way ``Chains.predictive`` is.
+    Per problem: ``mean``, ``std`` (R, N) the posterior mean and scatter (weighted, no ddof) of the theory vector, N the joint
+    length for a joint fit; ``multipoles``: ``{ell: (mean (R, n_s), std (R, n_s))}`` in the fit's ``poles_s`` / ``s`` order - of
+    a joint fit ``multipoles_of(q)`` gives block q's, and ``blocks`` the slices of the joint vector -; ``mean_chi2``,
+    ``var_chi2``, ``mean_lnl``, ``var_lnl`` (R,); ``chi2_at_mean``, ``lnl_at_mean`` (R,): the likelihood of problem r at
+    ``ip.mean[r]``; with D = -2 lnL (no prior term; the weights include the prior) ``p_d = mean_D - D(mean position)``, ``p_v =
+    var_D / 2`` and ``dic = mean_D + p_d``; ``state``: the raw arrays ``pivot_t`` (N,), ``sum_t``, ``sum_tt`` (R, N), ``pivots``
+    (2, R), ``deviance`` (4, R) and ``total`` (R,) as the route that ran the sample returns them.  A ``NO_FINITE`` problem reads
+    NaN throughout."""
+
+    def __init__(self, acc, ok, blocks, poles, chi2_at_mean=None, lnl_at_mean=None):
+        ld = np.longdouble
+        R = len(acc.total)
+        ok = np.asarray(ok, dtype=bool)
+        self.state = {"pivot_t": np.array(acc.pivot_t), "sum_t": np.array(acc.pt), "sum_tt": np.array(acc.ptt),
+                      "pivots": np.array(acc.pivots), "deviance": np.array(acc.dev), "total": np.array(acc.total)}
+        total = np.where(ok, acc.total, 1.0).astype(ld)
+
+        def moments(pivot, s1, s2, t):
+            m = np.asarray(s1, dtype=ld) / t
+            var = np.asarray(s2, dtype=ld) / t - m * m
+            return (np.asarray(pivot, dtype=ld) + m).astype(np.float64), var.astype(np.float64)
+
+        def masked(v):
+            v = np.array(v, dtype=np.float64)
+            v[~ok] = np.nan
+            return v
+
+        mean, var = moments(acc.pivot_t[None, :], acc.pt, acc.ptt, total[:, None])
+        self.mean = masked(mean)
+        self.std = masked(np.sqrt(np.maximum(var, 0.0)))         # (a variance below zero is rounding about a constant entry)
+        mean_chi2, var_chi2 = moments(acc.pivots[0], acc.dev[0], acc.dev[1], total)
+        mean_lnl, var_lnl = moments(acc.pivots[1], acc.dev[2], acc.dev[3], total)
+        self.mean_chi2, self.var_chi2, self.mean_lnl, self.var_lnl = (masked(v) for v in (mean_chi2, var_chi2, mean_lnl, var_lnl))
+        self.chi2_at_mean = masked(np.full(R, np.nan) if chi2_at_mean is None else chi2_at_mean)
+        self.lnl_at_mean = masked(np.full(R, np.nan) if lnl_at_mean is None else lnl_at_mean)
+        mean_d = -2.0 * self.mean_lnl
+        self.p_d = mean_d - (-2.0 * self.lnl_at_mean)
+        self.p_v = (4.0 * self.var_lnl) / 2.0
+        self.dic = mean_d + self.p_d
+        self.blocks = list(blocks)
+        self._poles = list(poles)
+        self.multipoles = self.multipoles_of(0) if len(self.blocks) == 1 else None
+
+    def multipoles_of(self, q):
+        """``{ell: (mean (R, n_s), std (R, n_s))}`` of block ``q`` of a joint fit (block 0: a single fit's)."""
+        if not 0 <= int(q) < len(self.blocks):
+            raise InputError(f"SamplePredictive.multipoles_of: block {q!r} is outside 0 .. {len(self.blocks) - 1}")
+        at, (poles, n_s) = self.blocks[int(q)].start, self._poles[int(q)]
+        out = {}
+        for i, ell in enumerate(np.atleast_1d(poles)):
+            cut = slice(at + i * n_s, at + (i + 1) * n_s)
+            out[int(ell)] = (self.mean[:, cut], self.std[:, cut])
+        return out
 
 
 class ImportancePosterior:
@@ -385,7 +516,8 @@ class ImportancePosterior:
     ``total^2 / sq`` and ``max_weight_share`` (R,) the largest normalised weight; ``mean`` (R, d), ``cov`` (R, d, d), ``sigma``
     (R, d); ``outside_mass`` (R, d, 2) the posterior mass below and above every range; ``status`` (R,): ``OK``, ``LOW_ESS``
     (``ess < min_ess``: the proposal misses this problem's posterior) or ``NO_FINITE`` (no kept point had a finite lnpost:
-    ``ln_evidence`` -inf, ``ess`` 0, the sums zeros, the moments and ``best`` NaN).  ``raw``: the :class:`Sums`."""
+    ``ln_evidence`` -inf, ``ess`` 0, the sums zeros, the moments and ``best`` NaN).  ``raw``: the :class:`Sums`.  ``predictive``: a
+    :class:`SamplePredictive` with ``predictive=True`` - the band of the theory vector and the DIC per problem -, else None."""
 
     OK, LOW_ESS, NO_FINITE = 0, 1, 2
 
@@ -429,6 +561,7 @@ class ImportancePosterior:
         self.outside_mass = np.stack([np.stack([self._h1(j)[:, 0], self._h1(j)[:, -1]], axis=1) for j in range(d)], axis=1) / total[:, None, None]
         self.status = np.where(ok, np.where(self.ess < self.min_ess, self.LOW_ESS, self.OK), self.NO_FINITE).astype(np.int32)
         self._reader = None
+        self.predictive = None                                   # a SamplePredictive with predictive=True (rule 6)
 
     def __len__(self):
         return self.n_problems
@@ -500,7 +633,7 @@ class ImportancePosterior:
 
 def importance_posterior(fit, params, proposal=None, n=16384, seed=0, fixed=None, prior=None, bins=64, ranges=None, pairs=None,
                          chunk=None, min_ess=50.0, device=True, evaluate=None, sample=None, ln_proposal=None, kwargs=None,
-                         realisations=None, n_blocks=None):
+                         realisations=None, n_blocks=None, predictive=None):
     """The work of ``CCFFit.importance_posterior`` (``realisations=None``: the fit's data vector, R = 1) and
     ``Realisations.importance_posterior`` (R = the realisations, one shared sample); see the module docstring.  With ``evaluate``
     - a callable taking a dict of ``(n,)`` arrays (sampled and fixed parameters) and returning lnL ``(n,)`` or ``(n, R)`` - in
@@ -522,10 +655,16 @@ def importance_posterior(fit, params, proposal=None, n=16384, seed=0, fixed=None
     :class:`victor_amd.priors.GaussianPrior` or a list of them; ``bins``: an int or a dict name -> int, 1 .. 1024; ``ranges``:
     name -> (a, b) inside the prior box (default the box); ``pairs``: name pairs for the 2-D histograms; ``chunk``: points per
     launch, at most 65536 (default :func:`victor_amd.grid.default_chunk`); ``min_ess``: below it a problem is ``LOW_ESS``;
-    ``device=False``: the NumPy definition.  Every argument is checked before the first device call.  Returns an
+    ``device=False``: the NumPy definition.  ``predictive``: None (off) or True for the posterior mean and scatter of the theory
+    vector, the moments of chi2 and lnL and ``p_d``, ``p_v``, ``dic`` of every problem (``ip.predictive``, a
+    :class:`SamplePredictive`; rule 6 of the module docstring) - joint fits, covariances and ``@`` parameters included; refused
+    (a :class:`victor_amd.predictive.PredictiveError`) for any other value, with an ``evaluate`` callable in place of a fit, and
+    with ``paired_model`` realisations.  Every argument is checked before the first device call.  Returns an
     :class:`ImportancePosterior`."""
     who = "importance_posterior"
     kwargs = kwargs or {}
+    from .predictive import PredictiveError, resolve_sample_predictive
+    predictive = resolve_sample_predictive(predictive, who, has_fit=evaluate is None and fit is not None)
     if evaluate is not None and device:
         raise InputError(f"{who}: an evaluate callable runs the definition route only (device=False)")
     if evaluate is None and fit is None:
@@ -564,8 +703,9 @@ def importance_posterior(fit, params, proposal=None, n=16384, seed=0, fixed=None
     layout = resolve_layout(who, names, q.lo, q.hi, bins, ranges, pairs)
     prior = resolve_prior(prior, who, names, q.lo, q.hi, fixed_all, joint is not None or n_blocks is not None)
     if realisations is not None and getattr(realisations, "paired_model", False):
-        raise InputError(f"{who}: realisations(paired_model=True) have no cross mode (a point has one theory vector per "
-                         "realisation): a shared sample evaluates every point once")
+        raise (PredictiveError if predictive else InputError)(
+            f"{who}: realisations(paired_model=True) have no cross mode (a point has one theory vector per "
+            "realisation): a shared sample evaluates every point once")
     if evaluate is None:
         fit_options = q.fit_options(fit, kwargs)
     if joint is not None and evaluate is None and len({f._device for f in joint.fits}) != 1:
@@ -616,7 +756,15 @@ def importance_posterior(fit, params, proposal=None, n=16384, seed=0, fixed=None
         batch.update({n: np.ascontiguousarray(x[:, j]) for j, n in enumerate(names)})
         return batch
 
+    def finish(acc, pacc):
+        ip = ImportancePosterior(layout, smp, lists, acc, pacc, min_ess)
+        if predictive:
+            ip.predictive = read_predictive(ip, fit, realisations, batch_of, kwargs)
+        return ip
+
     if not device:
+        both = (lambda v: v) if predictive else (lambda v: v[0])  # (rule 6 takes chi2 from the call that gives lnL)
+        theory = None
         if evaluate is not None:
             R = None                                             # (as many problems as the callable returns columns)
 
@@ -624,23 +772,60 @@ def importance_posterior(fit, params, proposal=None, n=16384, seed=0, fixed=None
                 return evaluate(batch_of(x))
         elif realisations is not None:
             def values(x):
-                return realisations.log_likelihood(batch_of(x), **kwargs)[0]
+                return both(realisations.log_likelihood(batch_of(x), **kwargs))
         else:
             def values(x):
-                return fit.log_likelihood_batch(batch_of(x), **kwargs)[0]
-        acc, pacc = run_definition(layout, smp, lists, R, values)
-        return ImportancePosterior(layout, smp, lists, acc, pacc, min_ess)
+                return both(fit.log_likelihood_batch(batch_of(x), **kwargs))
+        if predictive:
+            from .fisher import host_vectors
+
+            def theory(x):
+                return host_vectors(fit, batch_of(x), kwargs)
+        return finish(*run_definition(layout, smp, lists, R, values, theory))
 
     # ---- device
     lib, h, refresh = create_handle(q, fit, realisations, kwargs, fit_options, layout, smp, lists, fixed_out)
     try:
         if refresh is not None:
             refresh()
+        if predictive:
+            _check(lib, h, lib.vk_is_set_predictive(h, 1), "vk_is_set_predictive")
         _check(lib, h, lib.vk_is_run(h, 0, smp.G), "vk_is_run")
-        acc, pacc = read_result(lib, h, layout, R, smp.lnop is not None)
+        acc, pacc = read_result(lib, h, layout, R, smp.lnop is not None, theory_entries(fit) if predictive else None)
     finally:
         lib.vk_is_destroy(h)
-    return ImportancePosterior(layout, smp, lists, acc, pacc, min_ess)
+    return finish(acc, pacc)
+
+
+def _blocks_of(fit):
+    from .joint import JointFit
+    return list(fit.fits) if isinstance(fit, JointFit) else [fit]
+
+
+def theory_entries(fit):
+    """N: the entries of a point's theory vector - of a joint fit the blocks' vectors in block order."""
+    return sum(len(f.s) * len(np.atleast_1d(f.poles_s)) for f in _blocks_of(fit))
+
+
+def read_predictive(ip, fit, realisations, batch_of, kwargs):
+    """The :class:`SamplePredictive` of a completed run whose :class:`Sums` carry rule 6's arrays: one pairs call gives the
+    likelihood of problem r at ``ip.mean[r]`` (the problems without a mean read NaN)."""
+    R = ip.n_problems
+    lnl_at, chi2_at = np.full(R, np.nan), np.full(R, np.nan)
+    has = np.flatnonzero(ip._ok & np.all(np.isfinite(ip.mean), axis=1))
+    if len(has):
+        batch = batch_of(ip.mean[has])
+        if realisations is not None:
+            lnl_at[has], chi2_at[has] = realisations.log_likelihood_pairs(batch, has.astype(np.int32), **kwargs)
+        else:
+            lnl_at[has], chi2_at[has] = fit.log_likelihood_batch(batch, **kwargs)
+    blocks, poles, at = [], [], 0
+    for f in _blocks_of(fit):
+        n = len(f.s) * len(np.atleast_1d(f.poles_s))
+        blocks.append(slice(at, at + n))
+        poles.append((np.atleast_1d(f.poles_s), len(f.s)))
+        at += n
+    return SamplePredictive(ip.raw, ip._ok, blocks, poles, chi2_at, lnl_at)
 
 
 def _check(lib, h, rc, entry):
@@ -703,9 +888,15 @@ def create_handle(q, fit, realisations, kwargs, fit_options, layout, smp, lists,
     return lib, h, refresh
 
 
-def read_result(lib, h, layout, R, with_prior):
-    """``(Sums, the prior's own Sums or None)`` of a completed run (``vk_is_result``)."""
-    acc = Sums(layout, R)
+def read_result(lib, h, layout, R, with_prior, n_theory=None):
+    """``(Sums, the prior's own Sums or None)`` of a completed run (``vk_is_result``; with ``n_theory`` rule 6's arrays through
+    ``vk_is_predictive``, whose ``[N][R]`` sums are turned to (R, N))."""
+    acc = Sums(layout, R, n_theory)
+    if n_theory is not None:
+        pt, ptt = np.empty((n_theory, R)), np.empty((n_theory, R))
+        _check(lib, h, lib.vk_is_predictive(h, N.as_dp(acc.pivot_t), N.as_dp(pt), N.as_dp(ptt), N.as_dp(acc.pivots), N.as_dp(acc.dev)),
+               "vk_is_predictive")
+        acc.pt, acc.ptt = np.ascontiguousarray(pt.T), np.ascontiguousarray(ptt.T)
     i64 = C.POINTER(C.c_int64)
     pm, pt = C.c_double(0.0), C.c_double(0.0)
     rc = lib.vk_is_result(h, N.as_dp(acc.ln_max), acc.arg_max.ctypes.data_as(i64), acc.n_finite.ctypes.data_as(i64), N.as_dp(acc.total),

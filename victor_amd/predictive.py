@@ -58,6 +58,19 @@ def resolve_predictive(predictive, who, joint=False, tempered=False, has_fit=Tru
     return True
 
 
+def resolve_sample_predictive(predictive, who, has_fit=True):
+    """The ``predictive=`` of ``importance_posterior`` (:mod:`victor_amd.importance`): True for True, False for None.  A shared
+    sample holds a weight per (point, problem) and every point's theory vector, so joint fits are served; what is refused - a
+    :class:`PredictiveError`, before any evaluation and any device call - is any other value and a call without a fit."""
+    if predictive is None:
+        return False
+    if predictive is not True:
+        raise PredictiveError(f"{who}: predictive must be None or True, not {predictive!r}")
+    if not has_fit:
+        raise PredictiveError(f"{who}: predictive needs a fit (an evaluate callable returns no theory vectors)")
+    return True
+
+
 def stretch_chains(M, half, side):
     """The chain each of the M rows of half-step ``side`` serves: row i is member i % half of the moving half of ensemble
     i // half."""
