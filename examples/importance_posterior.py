@@ -14,10 +14,13 @@
   mocks, from the theory vectors the sample already computed; with ``--timing`` three routes alternate instead of two: the
   device route without and with ``predictive``, and the definition route with it (``device=False, predictive=True``: what a
   user could assemble before from ``theory_vector_batch`` and NumPy) up to ``--definition-max`` problems, beyond it once
-  (``--definition-once-max``: beyond that not at all).
+  (``--definition-once-max``: beyond that not at all);
+* ``--tail``: the same call with ``tail=True`` - per mock the Pareto shape k of its largest weights against the threshold, and
+  the raw against the smoothed ``ln_evidence`` in units of ``ln_evidence_error``; with ``--timing`` the same three routes with
+  ``tail`` for ``predictive``: the device route without and with it, and the definition route with it.
 
-    python examples/importance_posterior.py [--joint] [--timing] [--evidence] [--predictive] [--sizes 1,16,1024] [--samples 5]
-                                            [--out FILE]
+    python examples/importance_posterior.py [--joint] [--timing] [--evidence] [--predictive] [--tail] [--sizes 1,16,1024]
+                                            [--samples 5] [--out FILE]
 
 Needs a GPU and the test fixtures of the repository (tests/golden)."""
 
@@ -33,10 +36,25 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def timed(obj, params, q, device, n, predictive=None):
+def timed(obj, params, q, device, n, predictive=None, tail=None):
     t = time.perf_counter()
-    ip = obj.importance_posterior(params, q, n=n, seed=0, device=device, predictive=predictive)
+    ip = obj.importance_posterior(params, q, n=n, seed=0, device=device, predictive=predictive, tail=tail)
     return time.perf_counter() - t, ip
+
+
+def show_tail(ip):
+    """Per mock the Pareto shape of the largest weights and the raw against the smoothed evidence."""
+    t = ip.tail
+    pull = (ip.ln_evidence - t.ln_evidence) / ip.ln_evidence_error
+    names = {t.OK: "OK", t.HIGH_K: "HIGH_K", t.SHORT: "SHORT", t.NO_FINITE: "NO_FINITE"}
+    print(f"tail of {t.size} weights per mock, k threshold {t.k_threshold:.3f}")
+    for r in range(len(ip)):
+        print(f"mock {r:3d}: k {t.k[r]:+.3f} {names[int(t.status[r])]:7s} ESS {ip.ess[r]:8.0f} -> {t.ess[r]:8.0f}  ln_evidence {ip.ln_evidence[r]:.4f} -> "
+              f"{t.ln_evidence[r]:.4f}  (raw - smoothed) / error {pull[r]:+.3f}")
+    return {"size": t.size, "k_threshold": t.k_threshold, "k": t.k.tolist(), "scale": t.scale.tolist(), "status": t.status.tolist(),
+            "ess_raw": ip.ess.tolist(), "ess": t.ess.tolist(), "ln_evidence_raw": ip.ln_evidence.tolist(), "ln_evidence": t.ln_evidence.tolist(),
+            "ln_evidence_error_raw": ip.ln_evidence_error.tolist(), "ln_evidence_error": t.ln_evidence_error.tolist(),
+            "raw_minus_smoothed_over_error": pull.tolist()}
 
 
 def show_predictive(ip, first=3):
@@ -54,10 +72,10 @@ def show_predictive(ip, first=3):
             "dic": p.dic.tolist()}
 
 
-def three_routes(run, R, args):
-    """``--timing --predictive``: device off / device on / definition on, alternating after a warm-up of each; the definition
-    beyond ``--definition-max`` problems runs once, un-warmed (it takes minutes there), and beyond ``--definition-once-max`` not at
-    all."""
+def three_routes(run, R, args, what="predictive"):
+    """``--timing --predictive`` (or ``--tail``: ``what``): device off / device on / definition on, alternating after a warm-up of
+    each; the definition beyond ``--definition-max`` problems runs once, un-warmed (it takes minutes there), and beyond
+    ``--definition-once-max`` not at all."""
     many = R <= args.definition_max
     off, on, ref = [], [], []
     run(True, None)
@@ -70,8 +88,8 @@ def three_routes(run, R, args):
         if many or (i == 0 and R <= args.definition_once_max):
             ref.append(run(False, True)[0])
     med = {k: float(np.median(v)) if v else float("nan") for k, v in (("off", off), ("on", on), ("definition", ref))}
-    print(f"R={R}: device {med['off']:.3f} s ({min(off):.3f} .. {max(off):.3f}), with predictive {med['on']:.3f} s ({min(on):.3f} .. "
-          f"{max(on):.3f}), added {1e3 * (med['on'] - med['off']):.1f} ms; definition with predictive {med['definition']:.2f} s "
+    print(f"R={R}: device {med['off']:.3f} s ({min(off):.3f} .. {max(off):.3f}), with {what} {med['on']:.3f} s ({min(on):.3f} .. "
+          f"{max(on):.3f}), added {1e3 * (med['on'] - med['off']):.1f} ms; definition with {what} {med['definition']:.2f} s "
           f"({len(ref)} run{'s' if len(ref) > 1 else ''}), ratio {med['definition'] / med['on']:.1f}", flush=True)
     return {"device_off_s": med["off"], "device_on_s": med["on"], "definition_on_s": med["definition"], "device_off_all": off,
             "device_on_all": on, "definition_on_all": ref}
@@ -162,10 +180,13 @@ def main():
     ap.add_argument("--samples", type=int, default=5)
     ap.add_argument("--n", type=int, default=65536, help="draws")
     ap.add_argument("--predictive", action="store_true", help="the posterior band and the DIC; with --timing its cost")
+    ap.add_argument("--tail", action="store_true", help="the Pareto shape of the largest weights and the smoothed evidence; with --timing its cost")
     ap.add_argument("--definition-max", type=int, default=16, help="problems up to which --timing --predictive repeats the definition route")
     ap.add_argument("--definition-once-max", type=int, default=1024, help="... and up to which it runs it at least once")
     args = ap.parse_args()
     if args.joint:
+        if args.tail:
+            ap.error("--tail goes with the single fit (the keyword itself works for joint fits: tail=True)")
         return joint_main(args)
     import victor_amd
     from tests import cases
@@ -198,11 +219,16 @@ def main():
         print(f"{n:8s} mock 0: mean {ip.mean[0, j]:.4f} sigma {ip.sigma[0, j]:.4f} median {ip.median(n)[0]:.4f} 68% [{lo[0]:.4f}, {hi[0]:.4f}]")
     if args.predictive:
         res["predictive"] = show_predictive(timed(rs, params, q, True, args.n, True)[1])
+    if args.tail:
+        res["tail"] = show_tail(timed(rs, params, q, True, args.n, tail=True)[1])
 
     if args.timing:
         res["timing"] = {}
         for R in (int(v) for v in args.sizes.split(",")):
             obj = data_fit if R == 1 else rs if R == 16 else stack.realisations(list(np.arange(R) % 16))
+            if args.tail:
+                res["timing"][f"R={R}"] = three_routes(lambda device, tail, obj=obj: timed(obj, params, q, device, args.n, tail=tail), R, args, "tail")
+                continue
             if args.predictive:
                 res["timing"][f"R={R}"] = three_routes(lambda device, predictive, obj=obj: timed(obj, params, q, device, args.n, predictive), R, args)
                 continue

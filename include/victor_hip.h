@@ -887,6 +887,22 @@ void vk_is_destroy(vk_is* h);
  *   in units of the weights of vk_is_result: divide by total[r]. */
 int vk_is_set_predictive(vk_is* h, int32_t on);
 int vk_is_predictive(vk_is* h, double* pivot_t, double* sum_t, double* sum_tt, double* pivots, double* deviance);
+/* The tail of the sample (victor_amd/csrc/vk_is_tail.h; the definition: victor_amd/importance.py, rule 7): per problem the K
+ * largest finite lnpost[g][r] of the WHOLE sample with their points g - what a Pareto fit to the largest weights and the smoothed
+ * estimates built on it need (PSIS), selected while the chunks stream by: two more launches per chunk behind the max kernel, no
+ * host synchronisation, and (G, R) values still never travel.  lnpost is the value above (one addition; not finite: never held).
+ * The order is total - the larger lnpost first, between equal values the smaller g first - so the held entries and their order
+ * are unique: they depend neither on the chunk nor on anything timed, and two runs give the same bytes.  The prior's own problem
+ * keeps no tail.
+ * vk_is_set_tail(h, K): before the first vk_is_run (a completed run's results are dropped: the next run starts at point 0);
+ *   2 <= K <= min(4096, G) allocates the state beside the handle's allocation - per problem 2 K + 1 doubles and 2 K + chunk +
+ *   258 32-bit words - and changes no bit of anything vk_is_result or vk_is_predictive returns; K == 0 releases it, and
+ *   the handle allocates and launches what it did before.  Refused: a run under way; any other K.
+ * vk_is_tail, after a run has reached G: count [R] = min(K, n_finite[r]); lnpost [R][K] the held values in order, -inf behind
+ *   the count; index [R][K] their points, -1 behind the count.  Any may be NULL.  Refused: a handle without the state, a run
+ *   that is not complete. */
+int vk_is_set_tail(vk_is* h, int32_t K);
+int vk_is_tail(vk_is* h, double* lnpost, int64_t* index, int64_t* count);
 
 /* ---- nested sampling: the evidence and a posterior sample of the data vector or of every realisation ---------------------------
  * R problems of L live points each inside the box [lo, hi]; per iteration the K lowest live points of every problem die and K

@@ -232,6 +232,8 @@ SYMBOLS = {
     "vk_is_destroy": (None, [_vp]),
     "vk_is_set_predictive": (C.c_int, [_vp, C.c_int32]),
     "vk_is_predictive": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp]),
+    "vk_is_set_tail": (C.c_int, [_vp, C.c_int32]),
+    "vk_is_tail": (C.c_int, [_vp, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     # nested sampling: R problems of L live points, K replaced per iteration by S constrained steps
     "vk_nested_create": (_vp, [_vp, _optp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.POINTER(C.c_int32),
                                _dp, _dp, _dp, C.c_double, C.POINTER(C.c_int32), C.c_char_p, C.c_size_t]),

@@ -398,12 +398,14 @@ class CCFFit(CCFModel):
         are produced (``vk_is_run``) or by the NumPy loop that defines them (``device=False``, over
         :meth:`log_likelihood_batch`): :func:`victor_amd.importance.importance_posterior`, which documents the arguments.
         ``predictive=True`` (a keyword): the posterior mean and scatter of the theory vector and the DIC from the same sample
-        (``ip.predictive``).  Returns a :class:`victor_amd.importance.ImportancePosterior` with R = 1.  Runs on this fit's own
-        context."""
+        (``ip.predictive``); ``tail=True`` or ``tail={"size": M}`` (a keyword): the Pareto shape of the largest weights and the
+        smoothed estimates (``ip.tail``).  Returns a :class:`victor_amd.importance.ImportancePosterior` with R = 1.  Runs on
+        this fit's own context."""
         from .importance import importance_posterior
         predictive = kwargs.pop("predictive", None)             # (a keyword of its own, not a model or fit option)
+        tail = kwargs.pop("tail", None)                         # (likewise)
         return importance_posterior(self, params, q, n, seed, fixed, prior, bins, ranges, pairs, chunk, min_ess, device, evaluate,
-                                    sample, ln_proposal, kwargs, predictive=predictive)
+                                    sample, ln_proposal, kwargs, predictive=predictive, tail=tail)
 
     def nested_sampling(self, params, n_live=256, batch=32, steps=16, scale=None, seed=0, fixed=None, tol=1e-3, max_iter=None, n_iter=None,
                         keep_dead=True, device=True, evaluate=None, **kwargs):

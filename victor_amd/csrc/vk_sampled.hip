@@ -50,6 +50,10 @@
 //   vk_kernel_is_predict.h the posterior-predictive sums of an importance handle (vk_is_set_predictive): the product kernel behind
 //                        every chunk's accumulate kernel, weights x theory vectors, over the tile and index rules and the terms
 //                        of vk_is_predict.h (plain C++, likewise)
+//   vk_kernel_is_tail.h  the tail of an importance handle (vk_is_set_tail): behind every chunk's max kernel the filter kernel, a
+//                        thread per (slice of the chunk, problem), and the merge kernel, one workgroup per problem, which keep
+//                        each problem's K largest lnpost and their points, over the order, the slices and the merge positions of
+//                        vk_is_tail.h (plain C++, likewise)
 //   vk_kernel_nested.h   nested sampling (vk_nested_begin; the last section of this file): the select kernel, one workgroup per
 //                        problem, and the step and commit kernels, one thread per replacement walker, over the order, the pick,
 //                        the constrained step and the commit of vk_nested_step.h (plain C++, likewise)
@@ -77,6 +81,7 @@
 #include "vk_kernel_grid.h"
 #include "vk_kernel_importance.h"
 #include "vk_kernel_is_predict.h"
+#include "vk_kernel_is_tail.h"
 #include "vk_kernel_nested.h"
 
 using namespace vk;
@@ -2024,6 +2029,27 @@ struct __attribute__((visibility("hidden"))) vk_is : Sampled {
   int pred_N = 0;                          // entries of a theory vector (of a joint handle: of the joint vector)
   double *p_pivot_t = nullptr, *p_pt = nullptr, *p_ptt = nullptr, *p_pivots = nullptr, *p_dev = nullptr, *p_w = nullptr;
 
+  // the tail state of vk_is_tail.h, beside the one allocation (vk_is_set_tail; tail_K == 0: none): threshold [R] | the held
+  // values, two buffers [R][K] | their points, two buffers [R][K] | the chunk's candidate rows [R][chunk] | the slices' candidate
+  // counts [kMaxSlices][R] | count, side [R]
+  DevBlock tail_mem;
+  int tail_K = 0;                          // entries held per problem
+  double *t_threshold = nullptr, *t_val[2] = {nullptr, nullptr};
+  int *t_idx[2] = {nullptr, nullptr}, *t_cand = nullptr, *t_count = nullptr, *t_side = nullptr, *t_n_cand = nullptr;
+
+  void tail_layout(Carve& c, size_t K) {
+    const size_t r = (size_t)R;
+    c.take(t_threshold, r);
+    c.take(t_val[0], r * K);
+    c.take(t_val[1], r * K);
+    c.take(t_idx[0], r * K);
+    c.take(t_idx[1], r * K);
+    c.take(t_cand, r * (size_t)chunk);
+    c.take(t_n_cand, r * (size_t)vkist::kMaxSlices);
+    c.take(t_count, r);
+    c.take(t_side, r);
+  }
+
   void predictive_layout(Carve& c, size_t N) {
     const size_t r = (size_t)R;
     c.take(p_pivot_t, N);
@@ -2141,11 +2167,43 @@ static int is_predict(vk_is* f, long long g0, int n) {
   return VK_OK;
 }
 
+// the tail's words for the chunk of `a` (vk_is_set_tail has sized what they point to for R, K and the handle's chunk)
+static IsTailArgs is_tail_args(const vk_is* f, const IsArgs& a) {
+  IsTailArgs q{};
+  q.n = a.n;
+  q.R = f->R;
+  q.K = f->tail_K;
+  q.cap = f->chunk;
+  q.pr = vkist::problems_per_block(f->R);
+  q.gy = vkist::row_blocks(a.n, q.pr);
+  q.g0 = a.g0;
+  q.lnl = f->d_lnl;
+  q.lno = f->d_lno;
+  q.threshold = f->t_threshold;
+  q.count = f->t_count;
+  q.side = f->t_side;
+  q.n_cand = f->t_n_cand;
+  q.cand = f->t_cand;
+  for (int s = 0; s < 2; ++s) q.val[s] = f->t_val[s], q.idx[s] = f->t_idx[s];
+  return q;
+}
+
+// The tail of the chunk just evaluated: the filter kernel over [n][R] - tiles of pr problems times gy blocks of rows -, then a
+// merge workgroup per problem.
+static int is_tail_chunk(vk_is* f, const IsArgs& a) {
+  const IsTailArgs q = is_tail_args(f, a);
+  const dim3 grid((unsigned)((q.R + q.pr - 1) / q.pr), (unsigned)q.gy);
+  hipLaunchKernelGGL(vk_is_tail_filter_kernel, grid, dim3(vkist::kBlock), 0, f->ctx->stream, q);
+  VK_SAMPLED_HIP(f, hipGetLastError());
+  return sampled_launch(f, vk_is_tail_merge_kernel, (long long)q.R * vkist::kBlock, vkist::kBlock, q);
+}
+
 // the launches of points [first, end), chunk by chunk
 static int is_chunks(vk_is* f, long long first, long long end) {
   IsArgs a = is_args(f);
   int rc = VK_OK;
   if (first == 0) rc = sampled_launch(f, vk_is_init_kernel, (long long)a.n_acc * a.Rp, kIsBlock, a);
+  if (first == 0 && rc == VK_OK && f->tail_K) rc = sampled_launch(f, vk_is_tail_init_kernel, f->R, vkist::kBlock, is_tail_args(f, a));
   for (long long g0 = first; g0 < end && rc == VK_OK; g0 += f->chunk) {
     a.g0 = g0;
     a.n = (int)std::min<long long>(f->chunk, end - g0);
@@ -2153,6 +2211,7 @@ static int is_chunks(vk_is* f, long long first, long long end) {
     rc = sampled_launch(f, vk_is_rows_kernel, a.n, kIsBlock, a);
     if (rc == VK_OK) rc = sampled_evaluate(f, a.n, f->d_lnl, f->d_chi);
     if (rc == VK_OK) rc = sampled_launch(f, vk_is_max_kernel, (long long)((a.Rp + a.pr - 1) / a.pr) * kIsBlock, kIsBlock, a);
+    if (rc == VK_OK && f->tail_K) rc = is_tail_chunk(f, a);
     if (rc == VK_OK) rc = sampled_launch(f, vk_is_weight_kernel, (long long)a.n * a.Rp, kIsBlock, a);
     if (rc == VK_OK) rc = sampled_launch(f, vk_is_accumulate_kernel, (long long)a.n_acc * a.Rp, kIsBlock, a);
     if (rc == VK_OK && f->pred_N) rc = is_predict(f, g0, a.n);
@@ -2319,6 +2378,7 @@ const char* vk_is_last_error(const vk_is* f) { return f ? f->err.c_str() : ""; }
 void vk_is_destroy(vk_is* f) {
   if (!f) return;
   f->pred_mem.drop(f);
+  f->tail_mem.drop(f);
   sampled_destroy(f);
 }
 
@@ -2358,6 +2418,53 @@ int vk_is_predictive(vk_is* f, double* pivot_t, double* sum_t, double* sum_tt, d
                                   {pivots, f->p_pivots, 2 * one}, {deviance, f->p_dev, vkisp::kDeviance * one}});
   if (rc == VK_OK) f->err.clear();
   return rc;
+}
+
+// The tail (vk_is_tail.h).  Everything the tail kernels index with is fixed here and by the launch: R and the chunk - the
+// candidate slots of a problem, which no chunk can exceed - and K size the state they address.
+int vk_is_set_tail(vk_is* f, int32_t K) {
+  if (!f) return VK_E_ARG;
+  const std::string me = "vk_is_set_tail: ";
+  if (f->done != 0 && f->done != f->G) return refused(f, me + "a run is under way (call it before the first vk_is_run)");
+  if (K != 0 && (K < 2 || K > vkist::kMaxK || K > f->G))
+    return refused(f, me + "need 2 <= K <= min(4096, points) entries per problem, or 0 for none (K = " + std::to_string(K) + ", " +
+                          std::to_string(f->G) + " points)");
+  f->tail_mem.drop(f);
+  f->tail_K = 0;
+  f->done = 0;                             // (the tail belongs to a whole run: the next one starts at point 0)
+  f->err.clear();
+  if (!K) return VK_OK;
+  VK_SAMPLED_HIP(f, hipSetDevice(f->ctx->device));
+  const int rc = f->tail_mem.make(f, me, [&](Carve& c) { f->tail_layout(c, (size_t)K); });
+  if (rc) return rc;
+  f->tail_K = K;
+  return VK_OK;
+}
+
+int vk_is_tail(vk_is* f, double* lnpost, int64_t* index, int64_t* count) {
+  if (!f) return VK_E_ARG;
+  if (!f->tail_K) return refused(f, "vk_is_tail: the handle keeps no tail (vk_is_set_tail)");
+  if (f->done != f->G) return refused(f, "vk_is_tail: the run has reached " + std::to_string(f->done) + " of " + std::to_string(f->G) + " points");
+  VK_SAMPLED_HIP(f, hipSetDevice(f->ctx->device));
+  const size_t R = (size_t)f->R, K = (size_t)f->tail_K;
+  std::vector<double> val[2];
+  std::vector<int> idx[2], held(R), side(R);
+  for (int s = 0; s < 2; ++s) val[s].resize(R * K), idx[s].resize(R * K);
+  const int rc = sampled_home(f, {{val[0].data(), f->t_val[0], R * K * sizeof(double)}, {val[1].data(), f->t_val[1], R * K * sizeof(double)},
+                                  {idx[0].data(), f->t_idx[0], R * K * sizeof(int)}, {idx[1].data(), f->t_idx[1], R * K * sizeof(int)},
+                                  {held.data(), f->t_count, R * sizeof(int)}, {side.data(), f->t_side, R * sizeof(int)}});
+  if (rc) return rc;
+  for (size_t r = 0; r < R; ++r) {
+    const size_t n = (size_t)std::min<long long>(std::max(held[r], 0), (long long)K);
+    const int s = side[r] & 1;
+    if (count) count[r] = (int64_t)n;
+    for (size_t k = 0; k < K; ++k) {
+      if (lnpost) lnpost[r * K + k] = k < n ? val[s][r * K + k] : -__builtin_inf();
+      if (index) index[r * K + k] = k < n ? (int64_t)idx[s][r * K + k] : -1;
+    }
+  }
+  f->err.clear();
+  return VK_OK;
 }
 
 int vk_is_run(vk_is* f, int64_t first, int64_t count) {

@@ -61,6 +61,27 @@ each mock.
    ``mean = pivot + pt / total``, ``var = ptt / total - (pt / total)^2`` (weighted, no ddof: as ``cov``); D = -2 lnL carries no
    prior term, the weights do; ``p_d = mean_D - D(mean position)``, ``p_v = var_D / 2``, ``dic = mean_D + p_d``, with the
    likelihood at ``ip.mean[r]`` from one pairs call after the run.  A ``NO_FINITE`` problem reads NaN throughout.
+7. *The tail* (``tail=True`` or ``tail={"size": M}``; :class:`SampleTail`, ``ip.tail``): a generalised Pareto fit to every
+   problem's M largest weights - its shape k says whether ``ess`` and ``ln_evidence_error``, which are the weights' second
+   moment estimated from the same sample, can be believed - and the Pareto-smoothed estimates (PSIS: Vehtari, Simpson, Gelman,
+   Yao, Gabry).  The default is ``M = min(floor(0.2 G), ceil(3 sqrt(G)), 4095)``; ``1 <= M <= min(G - 1, 4095)``.
+   *Selection* (:class:`Held`; on the device ``vk_is_set_tail`` / ``vk_is_tail``, ``victor_amd/csrc/vk_is_tail.h``): with ``K =
+   M + 1`` problem r holds the K largest finite ``lnpost[g][r]`` of the WHOLE sample with their g - rule 3's value: one
+   addition, and a value that is not finite is never held.  The order is total: the larger lnpost first, between equal values
+   the smaller g first; so the held set and its order are unique, do not depend on ``chunk``, and both routes give the same
+   bytes.  ``count[r] = min(K, n_finite[r])``; the prior's own problem keeps no tail.
+   *The read-out* (host, both routes alike; the corrected sums in ``np.longdouble``).  The cutoff is the LAST held entry and the
+   tail the held entries whose lnpost is strictly above its value.  ``count < K``: ``SHORT``; no finite point: ``NO_FINITE``; a
+   tail of fewer than 5 entries: ``k = inf`` - in each of the three the smoothed figures equal the raw ones.  Otherwise, with
+   ``w = exp(lnpost - ln_max[r])`` (the largest is 1) and the cutoff's weight u, the excesses ``w - u`` in ascending order go
+   to :func:`gpd_fit`, the Zhang-Stephens empirical-Bayes fit as PSIS uses it, regularised ``k = (n k + 5) / (n + 10)``; the
+   tail's i-th smallest weight (i = 1 .. n) becomes ``min(u + scale expm1(-k log1p(-p_i)) / k, 1)``, ``p_i = (i - 0.5) / n``
+   (``k = 0``: the limit ``-scale log1p(-p_i)``), the smoothed values assigned to the tail's points in their order by weight;
+   and each of ``total``, ``sq``, ``s1``, ``s2`` of ``ip.raw`` is corrected by ``sum_tail (w'^p - w^p) (1, y_j, y_j y_k)``, p = 1
+   (p = 2 for ``sq``), y of the held indices.  ``ess``, ``ln_evidence``, ``ln_evidence_error``, ``mean`` and ``cov`` follow from
+   the corrected sums by rule 5's formulas (under a prior with the same prior normalisation), ``max_weight_share`` is the
+   largest smoothed weight over the corrected total.  Histograms are not corrected.  ``k_threshold = min(1 - 1 / log10(n_drawn),
+   0.7)``; ``HIGH_K``: ``k > k_threshold``.
 """
 
 import ctypes as C
@@ -375,12 +396,40 @@ def _predictive_step(acc, g0, f, w, theory, chi2, lnl):
     acc.dev[2], acc.dev[3] = add(acc.dev[2], acc.dev[3], lnl, acc.pivots[1][None, :])
 
 
-def step_definition(layout, lists, c, y, acc, g0, lnpost, total_only=False, predictive=None):
+class Held:
+    """Rule 7's selection: per problem the ``K`` largest finite lnpost seen so far and their points - ``lnpost`` (R, K), padded
+    with -inf, ``index`` (R, K) int64, padded with -1, ``count`` (R,) - in the total order (larger lnpost first, between equal
+    values the smaller g first)."""
+
+    def __init__(self, R, K):
+        self.K = int(K)
+        self.lnpost = np.full((R, self.K), -np.inf)
+        self.index = np.full((R, self.K), -1, dtype=np.int64)
+        self.count = np.zeros(R, dtype=np.int64)
+
+    def step(self, g0, lnpost):
+        """The chunk's ``lnpost`` (n, R; not finite: -inf) of the points ``g0 .. g0 + n - 1`` joins the held entries.  The held
+        entries are in order and belong to earlier points, the chunk's come in increasing g: a stable sort by value keeps
+        equal values in increasing g."""
+        n, R = lnpost.shape
+        v = np.concatenate([self.lnpost, lnpost.T], axis=1)
+        g = np.concatenate([self.index, np.broadcast_to(g0 + np.arange(n, dtype=np.int64), (R, n))], axis=1)
+        order = np.argsort(-v, axis=1, kind="stable")[:, :self.K]
+        self.lnpost = np.take_along_axis(v, order, axis=1)
+        self.index = np.take_along_axis(g, order, axis=1)
+        self.index[self.lnpost == -np.inf] = -1
+        self.count = np.count_nonzero(self.lnpost > -np.inf, axis=1).astype(np.int64)
+
+
+def step_definition(layout, lists, c, y, acc, g0, lnpost, total_only=False, predictive=None, tail=None):
     """Rule 3 of the module docstring for chunk ``c``: ``lnpost`` (n, R) of the points ``g0 .. g0 + n - 1``, whose centred
     coordinates are ``y`` (n, d), into the :class:`Sums` ``acc``, in place.  ``predictive``: ``(theory (n, N), chi2 (n, R), lnl
-    (n, R))`` of the chunk's points, for rule 6 (``acc`` was made with ``n_theory=N``)."""
+    (n, R))`` of the chunk's points, for rule 6 (``acc`` was made with ``n_theory=N``).  ``tail``: the :class:`Held` of rule 7,
+    which takes the chunk's values as the step reads them."""
     lnpost = np.asarray(lnpost, dtype=np.float64)
     lnpost = np.where(np.isfinite(lnpost), lnpost, -np.inf)
+    if tail is not None:
+        tail.step(g0, lnpost)
     acc.n_finite += np.count_nonzero(lnpost > -np.inf, axis=0)
     cmax = lnpost.max(axis=0)
     carg = g0 + np.argmax(lnpost, axis=0)                        # (the first of equal maxima)
@@ -418,10 +467,11 @@ def step_definition(layout, lists, c, y, acc, g0, lnpost, total_only=False, pred
             h[:, base + k] = _add_in_order(h[:, base + k], w[entries[off[k]:off[k + 1]]])
 
 
-def run_definition(layout, sample, lists, R, values, theory=None):
+def run_definition(layout, sample, lists, R, values, theory=None, tail=None):
     """The definition: ``values(x)`` gives lnL ``(n, R)`` (or ``(n,)``: R = 1) at the points ``x`` (n, d) of a chunk; ``R`` None:
     whatever the first chunk returns.  Returns ``(Sums, the prior's own Sums or None)``.  With ``theory`` - ``theory(x)`` gives
-    the points' theory vectors (n, N) - rule 6 runs along, and ``values(x)`` gives ``(lnL, chi2)``, both (n, R)."""
+    the points' theory vectors (n, N) - rule 6 runs along, and ``values(x)`` gives ``(lnL, chi2)``, both (n, R).  With ``tail=K``
+    rule 7's selection runs along: the Sums carry the :class:`Held` as ``tail``."""
     acc = None
     pacc = Sums(layout, 1) if sample.lnop is not None else None
     chunk = lists.chunk
@@ -440,9 +490,11 @@ def run_definition(layout, sample, lists, R, values, theory=None):
         if acc is None:
             R = lnl.shape[1]
             acc = Sums(layout, R, None if pred is None else vectors.shape[1])
+            if tail is not None:
+                acc.tail = Held(R, tail)
         if pacc is not None:
             step_definition(layout, lists, c, y, pacc, g0, sample.lnop[g0:g0 + chunk, None], total_only=True)
-        step_definition(layout, lists, c, y, acc, g0, lnl + lno[:, None], predictive=pred)
+        step_definition(layout, lists, c, y, acc, g0, lnl + lno[:, None], predictive=pred, tail=getattr(acc, "tail", None))
     return acc, pacc
 
 
@@ -503,6 +555,173 @@ class SamplePredictive:
         return out
 
 
+MAX_TAIL = 4095          # vkist::kMaxK - 1: the tail without its cutoff
+MIN_TAIL_FIT = 5         # entries a generalised Pareto fit needs
+
+
+def default_tail_size(G):
+    """Rule 7's default M for G kept points: ``min(floor(0.2 G), ceil(3 sqrt(G)), 4095)``."""
+    return int(min(math.floor(0.2 * G), math.ceil(3.0 * math.sqrt(G)), MAX_TAIL))
+
+
+def resolve_tail(tail, who, G):
+    """The argument ``tail`` against G kept points: None (off) or the tail size M; every refusal an ``InputError``."""
+    if tail is None:
+        return None
+    top = min(G - 1, MAX_TAIL)
+    if tail is True:
+        M = default_tail_size(G)
+        if M < 1:
+            raise InputError(f"{who}: tail=True needs at least 5 kept points ({G} are kept): the default tail is a fifth of them")
+        return M
+    if not isinstance(tail, dict) or set(tail) != {"size"}:
+        raise InputError(f"{who}: tail must be None, True or {{'size': M}}, not {tail!r}")
+    M = tail["size"]
+    if isinstance(M, bool) or not isinstance(M, (int, np.integer)) or not 1 <= int(M) <= top:
+        raise InputError(f"{who}: the tail size must be an integer in 1 .. min(G - 1, {MAX_TAIL}) = {top}, not {M!r}")
+    return int(M)
+
+
+def gpd_fit(x):
+    """``(k, scale)`` of the generalised Pareto distribution fitted to the n ascending excesses ``x`` (> 0 at the top): the
+    Zhang-Stephens empirical-Bayes fit as PSIS uses it (rule 7), with the regularisation ``k = (n k + 5) / (n + 10)``.  ``x``
+    (B, n) fits B samples of one length at once and returns two (B,) arrays - the same arithmetic per sample.  A sample whose
+    largest or lower-quartile excess is not positive has no fit: ``(inf, nan)``."""
+    x = np.asarray(x, dtype=np.float64)
+    one = x.ndim == 1
+    x = np.ascontiguousarray(np.atleast_2d(x))
+    B, n = x.shape
+    k_out, scale_out = np.full(B, np.inf), np.full(B, np.nan)
+    if n >= 1:
+        quartile = x[:, int(math.floor(n / 4.0 + 0.5)) - 1]
+        fit = (quartile > 0) & np.isfinite(x[:, -1])
+        if np.any(fit):
+            xs, quartile = x[fit], quartile[fit]
+            m = 30 + int(math.floor(math.sqrt(n)))
+            i = np.arange(1, m + 1, dtype=np.float64)
+            b = 1.0 / xs[:, -1, None] + (1.0 - np.sqrt(m / (i - 0.5)))[None, :] / (3.0 * quartile[:, None])       # (F, m)
+            k = np.mean(np.log1p(-b[:, :, None] * xs[:, None, :]), axis=2)
+            L = n * (np.log(-b / k) - k - 1.0)
+            with np.errstate(over="ignore"):                     # (a candidate far below the best: weight 0)
+                weight = 1.0 / np.sum(np.exp(L[:, None, :] - L[:, :, None]), axis=2)
+            weight = np.where(weight >= 10.0 * np.finfo(np.float64).eps, weight, 0.0)                             # dropped
+            weight = weight / weight.sum(axis=1, keepdims=True)
+            b_post = np.sum(b * weight, axis=1)
+            k_post = np.mean(np.log1p(-b_post[:, None] * xs), axis=1)
+            scale_out[fit] = -k_post / b_post
+            k_out[fit] = (n * k_post + 5.0) / (n + 10.0)
+    return (float(k_out[0]), float(scale_out[0])) if one else (k_out, scale_out)
+
+
+def gpd_quantile(p, k, scale):
+    """The quantile function of the generalised Pareto distribution of shape ``k`` and scale ``scale`` (location 0) at ``p``:
+    ``scale expm1(-k log1p(-p)) / k``, at ``k = 0`` its limit ``-scale log1p(-p)``; the three broadcast."""
+    k, scale = np.asarray(k, dtype=np.float64), np.asarray(scale, dtype=np.float64)
+    lp = np.log1p(-np.asarray(p, dtype=np.float64))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        general = scale * np.expm1(-k * lp) / k
+    return np.where(k == 0, -scale * lp, general)
+
+
+def smooth_tail(w, u):
+    """Rule 7 for one problem: ``w`` (n,) the tail's weights in DESCENDING order (the held order), ``u`` the cutoff's weight.
+    Returns ``(k, scale, the smoothed weights in the same order)``; fewer than 5 entries, or no fit: ``k = inf`` and the weights
+    as they are.  ``w`` (B, n) with ``u`` (B,): B problems with tails of one length at once, ``k`` and ``scale`` (B,)."""
+    w = np.asarray(w, dtype=np.float64)
+    one = w.ndim == 1
+    w, u = np.atleast_2d(w), np.atleast_1d(np.asarray(u, dtype=np.float64))
+    B, n = w.shape
+    k, scale, out = np.full(B, np.inf), np.full(B, np.nan), w.copy()
+    if n >= MIN_TAIL_FIT:
+        k_fit, scale_fit = gpd_fit((w - u[:, None])[:, ::-1])
+        good = np.isfinite(k_fit) & np.isfinite(scale_fit)
+        p = (np.arange(1, n + 1, dtype=np.float64) - 0.5) / n
+        smoothed = np.minimum(u[good, None] + gpd_quantile(p[None, :], k_fit[good, None], scale_fit[good, None]), 1.0)
+        out[good] = smoothed[:, ::-1]                            # (ascending: the i-th smallest; handed out in the held order)
+        k[good], scale[good] = k_fit[good], scale_fit[good]
+    return (float(k[0]), float(scale[0]), out[0]) if one else (k, scale, out)
+
+
+class SampleTail:
+    """What ``ImportancePosterior.tail`` holds (rule 7 of the module docstring).  ``size`` M; ``count`` (R,) the entries held
+    (at most M + 1: the tail and its cutoff); ``lnpost`` (R, M + 1) the held values, largest first, padded with -inf, and
+    ``index`` (R, M + 1) int64 their points g, padded with -1; ``n_tail`` (R,) the entries strictly above the cutoff; ``k``,
+    ``scale`` (R,) the fitted generalised Pareto shape and scale (``k = inf``: no fit; NaN without a finite point) and
+    ``k_threshold`` the limit above which ``k`` is flagged; ``weight``, ``smoothed_weight`` (R, M + 1) the held entries' weights
+    ``exp(lnpost - ln_max)`` and what replaces them (0 in the padding; the cutoff and an unfitted tail keep theirs);
+    ``ln_evidence``, ``ln_evidence_error``, ``ess``, ``max_weight_share`` (R,), ``mean`` (R, d), ``cov`` (R, d, d), ``sigma`` (R,
+    d) the smoothed estimates, from ``sums``: the corrected ``total``, ``sq`` (R,), ``s1`` (R, d) and ``s2`` (R, d (d + 1) / 2);
+    ``status`` (R,): ``OK``, ``HIGH_K`` (``k > k_threshold``: the variance of the estimate cannot be trusted), ``SHORT`` (fewer
+    than M + 1 finite points: nothing to fit) or ``NO_FINITE``.  Where nothing is fitted the smoothed figures equal the raw
+    ones."""
+
+    OK, HIGH_K, SHORT, NO_FINITE = 0, 1, 2, 3
+
+    def __init__(self, ip, held, pacc=None):
+        ld = np.longdouble
+        acc, sample = ip.raw, ip._sample
+        R, d = ip.n_problems, len(ip.names)
+        K = held.K
+        self.size = K - 1
+        self.count = np.array(held.count, dtype=np.int64)
+        self.lnpost, self.index = np.array(held.lnpost), np.array(held.index, dtype=np.int64)
+        with np.errstate(divide="ignore"):
+            self.k_threshold = float(min(1.0 - 1.0 / np.log10(float(ip.n_drawn)), 0.7)) if ip.n_drawn > 1 else -np.inf
+        self.k, self.scale = np.full(R, np.inf), np.full(R, np.nan)
+        self.n_tail = np.zeros(R, dtype=np.int64)
+        self.status = np.zeros(R, dtype=np.int32)
+        ok = acc.n_finite > 0
+        with np.errstate(invalid="ignore"):
+            self.weight = np.exp(self.lnpost - np.where(ok, acc.ln_max, 0.0)[:, None])    # (the padding, -inf, reads 0)
+        self.smoothed_weight = self.weight.copy()
+        full = ok & (self.count == K)
+        self.status[~ok], self.k[~ok] = self.NO_FINITE, np.nan
+        self.status[ok & ~full] = self.SHORT
+        self.n_tail[full] = np.count_nonzero(self.lnpost[full] > self.lnpost[full, K - 1:K], axis=1)
+        # the fits: the problems whose tails have one length together, in blocks whose (block, m, n) temporaries stay in cache
+        for n in np.unique(self.n_tail[full]):
+            rows = np.flatnonzero(full & (self.n_tail == n))
+            block = max(1, (1 << 18) // (max(int(n), 1) * (30 + int(math.sqrt(max(int(n), 1))))))
+            for at in range(0, len(rows), block):
+                r = rows[at:at + block]
+                self.k[r], self.scale[r], self.smoothed_weight[r, :n] = smooth_tail(self.weight[r, :n], self.weight[r, K - 1])
+        self.status[full] = np.where(self.k[full] > self.k_threshold, self.HIGH_K, self.OK)
+        top = np.where(ok, self.smoothed_weight[:, 0], 1.0)      # the largest weight after smoothing (unsmoothed: 1)
+        # the corrections, all problems at once: the entries that were not smoothed add exact zeros
+        new, old = self.smoothed_weight.astype(ld), self.weight.astype(ld)
+        dw = new - old                                           # (R, K)
+        y = sample.y[np.maximum(self.index, 0)].astype(ld)       # (R, K, d); the padding reads point 0 with dw = 0
+        total = np.array(acc.total, dtype=ld) + dw.sum(axis=1)
+        sq = np.array(acc.sq, dtype=ld) + (new * new - old * old).sum(axis=1)
+        s1, s2 = np.array(acc.s1, dtype=ld), np.array(acc.s2, dtype=ld)
+        for j in range(d):
+            wy = dw * y[:, :, j]
+            s1[:, j] += wy.sum(axis=1)
+            for j2 in range(j, d):
+                s2[:, tri(d, j, j2)] += (wy * y[:, :, j2]).sum(axis=1)
+        self.sums = {"total": total.astype(np.float64), "sq": sq.astype(np.float64), "s1": s1.astype(np.float64),
+                     "s2": s2.astype(np.float64)}
+        # rule 5's formulas on the corrected sums
+        t = np.where(ok, self.sums["total"], 1.0)
+        q = np.where(ok, self.sums["sq"], 1.0)
+        with np.errstate(divide="ignore"):
+            ln_sum = np.where(ok, acc.ln_max, 0.0) + np.log(t)
+        norm = np.log(float(ip.n_drawn)) if pacc is None else float(pacc.ln_max[0]) + np.log(float(pacc.total[0]))
+        self.ln_evidence = np.where(ok, ln_sum - norm, -np.inf)
+        self.ess = np.where(ok, t * t / q, 0.0)
+        self.max_weight_share = np.where(ok, top / t, 0.0)
+        self.ln_evidence_error = np.where(ok, np.sqrt(np.maximum(q / (t * t) - 1.0 / ip.n_drawn, 0.0)), np.inf)
+        m = self.sums["s1"] / t[:, None]
+        self.mean = np.where(ok[:, None], sample.centre[None, :] + m, np.nan)
+        self.cov = np.empty((R, d, d))
+        for j in range(d):
+            for j2 in range(j, d):
+                self.cov[:, j, j2] = self.cov[:, j2, j] = self.sums["s2"][:, tri(d, j, j2)] / t - m[:, j] * m[:, j2]
+        self.cov[~ok] = np.nan
+        with np.errstate(invalid="ignore"):
+            self.sigma = np.sqrt(np.diagonal(self.cov, axis1=1, axis2=2))
+
+
 class ImportancePosterior:
     """The posterior of R problems from one shared sample.
 
@@ -517,7 +736,9 @@ class ImportancePosterior:
     (R, d); ``outside_mass`` (R, d, 2) the posterior mass below and above every range; ``status`` (R,): ``OK``, ``LOW_ESS``
     (``ess < min_ess``: the proposal misses this problem's posterior) or ``NO_FINITE`` (no kept point had a finite lnpost:
     ``ln_evidence`` -inf, ``ess`` 0, the sums zeros, the moments and ``best`` NaN).  ``raw``: the :class:`Sums`.  ``predictive``: a
-    :class:`SamplePredictive` with ``predictive=True`` - the band of the theory vector and the DIC per problem -, else None."""
+    :class:`SamplePredictive` with ``predictive=True`` - the band of the theory vector and the DIC per problem -, else None.
+    ``tail``: a :class:`SampleTail` with ``tail=True`` or ``tail={"size": M}`` - the Pareto shape of every problem's largest
+    weights and the smoothed estimates -, else None."""
 
     OK, LOW_ESS, NO_FINITE = 0, 1, 2
 
@@ -562,6 +783,7 @@ class ImportancePosterior:
         self.status = np.where(ok, np.where(self.ess < self.min_ess, self.LOW_ESS, self.OK), self.NO_FINITE).astype(np.int32)
         self._reader = None
         self.predictive = None                                   # a SamplePredictive with predictive=True (rule 6)
+        self.tail = None                                         # a SampleTail with tail=True or {"size": M} (rule 7)
 
     def __len__(self):
         return self.n_problems
@@ -633,7 +855,7 @@ class ImportancePosterior:
 
 def importance_posterior(fit, params, proposal=None, n=16384, seed=0, fixed=None, prior=None, bins=64, ranges=None, pairs=None,
                          chunk=None, min_ess=50.0, device=True, evaluate=None, sample=None, ln_proposal=None, kwargs=None,
-                         realisations=None, n_blocks=None, predictive=None):
+                         realisations=None, n_blocks=None, predictive=None, tail=None):
     """The work of ``CCFFit.importance_posterior`` (``realisations=None``: the fit's data vector, R = 1) and
     ``Realisations.importance_posterior`` (R = the realisations, one shared sample); see the module docstring.  With ``evaluate``
     - a callable taking a dict of ``(n,)`` arrays (sampled and fixed parameters) and returning lnL ``(n,)`` or ``(n, R)`` - in
@@ -659,8 +881,10 @@ def importance_posterior(fit, params, proposal=None, n=16384, seed=0, fixed=None
     vector, the moments of chi2 and lnL and ``p_d``, ``p_v``, ``dic`` of every problem (``ip.predictive``, a
     :class:`SamplePredictive`; rule 6 of the module docstring) - joint fits, covariances and ``@`` parameters included; refused
     (a :class:`victor_amd.predictive.PredictiveError`) for any other value, with an ``evaluate`` callable in place of a fit, and
-    with ``paired_model`` realisations.  Every argument is checked before the first device call.  Returns an
-    :class:`ImportancePosterior`."""
+    with ``paired_model`` realisations.  ``tail``: None (off), True or ``{"size": M}`` for the Pareto tail diagnostic and the
+    smoothed estimates of every problem (``ip.tail``, a :class:`SampleTail`; rule 7 of the module docstring) - on either route,
+    with an ``evaluate`` callable, a prior, ``predictive=True`` or the caller's own sample; any other value is refused.  Every
+    argument is checked before the first device call.  Returns an :class:`ImportancePosterior`."""
     who = "importance_posterior"
     kwargs = kwargs or {}
     from .predictive import PredictiveError, resolve_sample_predictive
@@ -742,6 +966,8 @@ def importance_posterior(fit, params, proposal=None, n=16384, seed=0, fixed=None
     kept = x[inside]
     smp = Sample(kept, kept.mean(axis=0) if centre is None else centre, lnq[inside], len(x), q.lo, q.hi, prior)
 
+    tail = resolve_tail(tail, who, smp.G)                         # M, or None
+
     R = len(realisations) if realisations is not None else 1
     if chunk is None:
         chunk = default_chunk(R, smp.G)
@@ -760,6 +986,8 @@ def importance_posterior(fit, params, proposal=None, n=16384, seed=0, fixed=None
         ip = ImportancePosterior(layout, smp, lists, acc, pacc, min_ess)
         if predictive:
             ip.predictive = read_predictive(ip, fit, realisations, batch_of, kwargs)
+        if tail is not None:
+            ip.tail = SampleTail(ip, acc.tail, pacc)
         return ip
 
     if not device:
@@ -781,7 +1009,7 @@ def importance_posterior(fit, params, proposal=None, n=16384, seed=0, fixed=None
 
             def theory(x):
                 return host_vectors(fit, batch_of(x), kwargs)
-        return finish(*run_definition(layout, smp, lists, R, values, theory))
+        return finish(*run_definition(layout, smp, lists, R, values, theory, None if tail is None else tail + 1))
 
     # ---- device
     lib, h, refresh = create_handle(q, fit, realisations, kwargs, fit_options, layout, smp, lists, fixed_out)
@@ -790,8 +1018,11 @@ def importance_posterior(fit, params, proposal=None, n=16384, seed=0, fixed=None
             refresh()
         if predictive:
             _check(lib, h, lib.vk_is_set_predictive(h, 1), "vk_is_set_predictive")
+        if tail is not None:
+            _check(lib, h, lib.vk_is_set_tail(h, tail + 1), "vk_is_set_tail")
         _check(lib, h, lib.vk_is_run(h, 0, smp.G), "vk_is_run")
-        acc, pacc = read_result(lib, h, layout, R, smp.lnop is not None, theory_entries(fit) if predictive else None)
+        acc, pacc = read_result(lib, h, layout, R, smp.lnop is not None, theory_entries(fit) if predictive else None,
+                                None if tail is None else tail + 1)
     finally:
         lib.vk_is_destroy(h)
     return finish(acc, pacc)
@@ -888,10 +1119,15 @@ def create_handle(q, fit, realisations, kwargs, fit_options, layout, smp, lists,
     return lib, h, refresh
 
 
-def read_result(lib, h, layout, R, with_prior, n_theory=None):
+def read_result(lib, h, layout, R, with_prior, n_theory=None, tail=None):
     """``(Sums, the prior's own Sums or None)`` of a completed run (``vk_is_result``; with ``n_theory`` rule 6's arrays through
-    ``vk_is_predictive``, whose ``[N][R]`` sums are turned to (R, N))."""
+    ``vk_is_predictive``, whose ``[N][R]`` sums are turned to (R, N); with ``tail=K`` rule 7's :class:`Held` through
+    ``vk_is_tail``, as the Sums' ``tail``)."""
     acc = Sums(layout, R, n_theory)
+    if tail is not None:
+        acc.tail = held = Held(R, tail)
+        to_i64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
+        _check(lib, h, lib.vk_is_tail(h, N.as_dp(held.lnpost), to_i64(held.index), to_i64(held.count)), "vk_is_tail")
     if n_theory is not None:
         pt, ptt = np.empty((n_theory, R)), np.empty((n_theory, R))
         _check(lib, h, lib.vk_is_predictive(h, N.as_dp(acc.pivot_t), N.as_dp(pt), N.as_dp(ptt), N.as_dp(acc.pivots), N.as_dp(acc.dev)),

@@ -655,12 +655,14 @@ class JointRealisations:
         loop over :meth:`log_likelihood` that defines them (``device=False``).  ``"name@q"`` parameters (:func:`per_block`) may be
         sampled or fixed - a sampled ``epsilon@q`` is refused - and a ``prior`` may name them.  Arguments and result as
         ``Realisations.importance_posterior`` (:mod:`victor_amd.importance`); ``predictive=True`` gives the band of the JOINT
-        vector (``ip.predictive.multipoles_of(q)`` per block) and the DIC.  The joint data vector itself (R = 1) goes through
+        vector (``ip.predictive.multipoles_of(q)`` per block) and the DIC, ``tail=True`` every joint mock's Pareto shape and
+        smoothed estimates (``ip.tail``).  The joint data vector itself (R = 1) goes through
         ``victor_amd.importance.importance_posterior(joint, params, ...)``."""
         from .importance import importance_posterior
         predictive = kwargs.pop("predictive", None)             # (a keyword of its own, not a model or fit option)
+        tail = kwargs.pop("tail", None)                         # (likewise)
         return importance_posterior(self.joint, params, proposal, n, seed, fixed, prior, bins, ranges, pairs, chunk, min_ess, device,
-                                    evaluate, sample, ln_proposal, kwargs, realisations=self, predictive=predictive)
+                                    evaluate, sample, ln_proposal, kwargs, realisations=self, predictive=predictive, tail=tail)
 
     def _eval(self, params, kwargs, which=None):
         joint = self.joint

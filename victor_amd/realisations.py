@@ -336,11 +336,13 @@ class Realisations:
         and the marginal histograms of each are reduced on the GPU (``device=True``) or by the NumPy loop over
         :meth:`log_likelihood` that defines them (``device=False``).  Arguments and result as ``CCFFit.importance_posterior``
         (:mod:`victor_amd.importance`), ``predictive=True`` included: every mock's band and DIC from the G shared theory
-        vectors.  Refused with ``paired_model=True``: a point then has one theory vector per realisation."""
+        vectors, and ``tail=True``: every mock's Pareto shape and smoothed estimates (``ip.tail``).  Refused with
+        ``paired_model=True``: a point then has one theory vector per realisation."""
         from .importance import importance_posterior
         predictive = kwargs.pop("predictive", None)             # (a keyword of its own, not a model or fit option)
+        tail = kwargs.pop("tail", None)                         # (likewise)
         return importance_posterior(self.fit, params, q, n, seed, fixed, prior, bins, ranges, pairs, chunk, min_ess, device, evaluate,
-                                    sample, ln_proposal, kwargs, realisations=self, predictive=predictive)
+                                    sample, ln_proposal, kwargs, realisations=self, predictive=predictive, tail=tail)
 
     def nested_sampling(self, params, n_live=256, batch=32, steps=16, scale=None, seed=0, fixed=None, tol=1e-3, max_iter=None, n_iter=None,
                         keep_dead=True, device=True, evaluate=None, **kwargs):
