@@ -12,8 +12,16 @@ whose half-steps move half of every ensemble - and ``steps(row)`` the step count
 
 ``STENCILS``, further down, is the same for the two stencil calls - ``laplace`` (vk_fit_hessian) and ``fisher`` (vk_fit_fisher);
 tests/test_gpu_stencil_shapes.py; DESIGN.md section 7a, "Launch shapes under test" - whose R M rows go through in chunks of R S
-rows: ``slots``, ``points``, ``chunks``."""
+rows: ``slots``, ``points``, ``chunks``.
 
+``CHUNKS``, at the end, is the same for the chunked pipeline of the grid and importance posteriors (vk_grid_run, vk_is_run;
+tests/test_gpu_chunk_shapes.py; DESIGN.md sections 7c and 7e, "Launch shapes under test"): a row is ``R`` problems, a ``chunk``
+and ``G`` points (for a grid: the product of its ``bins``), so ``chunk_lengths(row)`` launches of the rows, evaluation, max,
+tail, weight, accumulate and predict kernels.  The slice and batch geometry of the tail kernels is stated by plain-Python twins
+of victor_amd/csrc/vk_is_tail.h (``problems_per_block`` ... ``rows_of``), which tests/test_launch_shapes.py holds to the header
+compiled under g++."""
+
+import math
 import os
 import re
 
@@ -74,6 +82,30 @@ def thresholds():
     _one(r"rows_max = \(size_t\)R \* S;", sampled, "rows_max of a vk_fit handle")
     assert len(re.findall(r"const long long total = \(long long\)\(R \* M\), chunk = \(long long\)f->rows_max", sampled)) == 2, \
         "the chunk loops of hessian_run and fisher_run no longer match their pattern"
+    # the chunked pipeline of the grid and importance posteriors (CHUNKS): workgroups and loads in flight of the kernels, the
+    # tail's limits (vkist::, keys "tail.*" where a name is shared), the predict kernel's tile rules (vkisp::), the largest chunk
+    importance, grid = _read("victor_amd", "csrc", "vk_kernel_importance.h"), _read("victor_amd", "csrc", "vk_kernel_grid.h")
+    for name in ("kIsBlock", "kIsAhead", "kIsListAhead"):
+        t[name] = int(_one(r"constexpr int %s = (\d+);" % name, importance, name).group(1))
+    for name in ("kGridBlock", "kGridAhead"):
+        t[name] = int(_one(r"constexpr int %s = (\d+);" % name, grid, name).group(1))
+    tail, predict = _read("victor_amd", "csrc", "vk_is_tail.h"), _read("victor_amd", "csrc", "vk_is_predict.h")
+    for name, key in (("kBlock", "tail.kBlock"), ("kBatch", "kBatch"), ("kMaxSlices", "kMaxSlices"), ("kSliceRows", "kSliceRows"), ("kMaxK", "kMaxK")):
+        t[key] = int(_one(r"constexpr int %s = (\d+);" % name, tail, "vkist::" + name).group(1))
+    for name, key in (("kSlices", "predict.kSlices"), ("kAhead", "predict.kAhead"), ("kTile", "predict.kTile"), ("kWave", "predict.kWave")):
+        t[key] = int(_one(r"constexpr int %s = (\d+);" % name, predict, "vkisp::" + name).group(1))
+    t["MAX_CHUNK"] = int(_one(r"(?m)^MAX_CHUNK = (\d+)$", _read("victor_amd", "grid.py"), "MAX_CHUNK").group(1))
+    # the rules the constants enter: the launches of a chunk, the batch loop of the merge kernel, the slices of the max kernels
+    for kern, block in (("vk_is_rows_kernel, a.n", "kIsBlock"), ("vk_is_weight_kernel, (long long)a.n * a.Rp", "kIsBlock"),
+                        ("vk_grid_rows_kernel, a.n", "kGridBlock"), ("vk_grid_weight_kernel, (long long)a.n * a.Rp", "kGridBlock"),
+                        ("vk_grid_accumulate_kernel, f->cells() * a.Rp", "kGridBlock")):
+        _one(re.escape(f"sampled_launch(f, {kern}, {block}, a)"), sampled, kern.split(",")[0])
+    _one(r"for \(int c0 = 0; c0 < c; c0 \+= kBatch\)", _read("victor_amd", "csrc", "vk_kernel_is_tail.h"), "the merge kernel's batch loop")
+    _one(r"const int pr = a\.pr, slices = kIsBlock / pr;", importance, "the slices of vk_is_max_kernel")
+    _one(r"const int pr = a\.pr, slices = kGridBlock / pr;", grid, "the slices of vk_grid_max_kernel")
+    _one(r"range_ahead<kIsAhead>\(0, a\.n,", importance, "the whole-chunk walk of vk_is_accumulate_kernel")
+    _one(r"for \(; i \+ kGridAhead <= a\.n; i \+= kGridAhead\)", grid, "the total's walk of vk_grid_accumulate_kernel")
+    _one(r"slice_begin\(int n, int s\) \{ return \(int\)\(\(long long\)n \* s / kSlices\); \}", predict, "vkisp::slice_begin")
     return t
 
 
@@ -329,3 +361,201 @@ def stencil_variants(row):
     def each(v):
         return v if isinstance(v, tuple) else (v,)
     return [dict(row, call=c, route=p, R=n) for c in each(row["call"]) for p in each(row["route"]) for n in each(row["R"])]
+
+
+# ------------------------------------------------------------------ the chunked pipeline: grid and importance posteriors ----------
+# vk_is_run and vk_grid_run send G points through in chunks of ``chunk`` rows; per chunk a rows kernel, the evaluation of n rows,
+# a max kernel, with a tail the filter and merge kernels, a weight kernel, an accumulate kernel and, with ``predictive``, the
+# predict kernel.  A row of ``CHUNKS``: ``kind`` ("importance" or "grid"), the ``route``, R problems (``prior``: one more, the
+# prior's own), ``chunk`` and ``G`` (a grid: the product of ``bins``, last axis fastest), the ``tail`` sizes M the row runs at
+# ("all": G - 1, None: the default size), whether it runs with ``predictive``, and ``reaches`` as in ``TABLE``.
+def chunk_lengths(row):
+    """The rows of every chunk of a row, in launch order."""
+    return [min(row["chunk"], row["G"] - g0) for g0 in range(0, row["G"], row["chunk"])]
+
+
+def problems_of_a_workgroup(R):
+    """The power of two >= R, at most 64: ``pr`` of the max kernels, vkisp::problems_per_wave, vkist::problems_per_block."""
+    pr = 1
+    while pr < 64 and pr < R:
+        pr *= 2
+    return pr
+
+
+# the twins of victor_amd/csrc/vk_is_tail.h
+def problems_per_block(R):
+    return problems_of_a_workgroup(R)
+
+
+def slices_per_block(pr, t):
+    return t["tail.kBlock"] // pr
+
+
+def row_blocks(n, pr, t):
+    per = slices_per_block(pr, t)
+    most = t["kMaxSlices"] // per
+    want = (n + per * t["kSliceRows"] - 1) // (per * t["kSliceRows"])
+    return 1 if want < 1 else min(want, most)
+
+
+def block_begin(n, gy, y):
+    return n * y // gy
+
+
+def slice_of(n, pr, gy, s, t):
+    """``(first, end, step)`` of slice s of a chunk of n rows."""
+    per = slices_per_block(pr, t)
+    y, sl = divmod(s, per)
+    return block_begin(n, gy, y) + sl, block_begin(n, gy, y + 1), per
+
+
+def rows_of(c):
+    first, end, step = c
+    return (end - first + step - 1) // step if first < end else 0
+
+
+def tail_shape(n, R, t):
+    """``(pr, gy, S)`` of the filter launch of a chunk of n rows: problems of a workgroup, blocks of rows, slices."""
+    pr = problems_per_block(R)
+    gy = row_blocks(n, pr, t)
+    return pr, gy, gy * slices_per_block(pr, t)
+
+
+def batches(c, t):
+    """The candidates of every batch of a merge of c candidates."""
+    return [min(t["kBatch"], c - c0) for c0 in range(0, c, t["kBatch"])]
+
+
+def tail_entries(row, size):
+    """K, the entries held per problem, of a tail of ``size`` (M + 1; None: the default M of victor_amd.importance)."""
+    G = row["G"]
+    if size is None:
+        m = min(int(0.2 * G), math.ceil(3 * math.sqrt(G)), 4095)                # default_tail_size of victor_amd/importance.py
+    else:
+        m = G - 1 if size == "all" else size
+    return m + 1
+
+
+def max_slice_rows(n, Rp, block):
+    """The most rows a thread of a max kernel sees: the chunk over block / pr slices."""
+    return -(-n // (block // problems_of_a_workgroup(Rp)))
+
+
+def _groups(threads, block):
+    return -(-threads // block)
+
+
+def _chunks_are(*lengths):
+    return lambda r, t: chunk_lengths(r) == list(lengths)
+
+
+def _tail_is(n, pr, gy, S):
+    return lambda r, t: tail_shape(n, r["R"], t) == (pr, gy, S)
+
+
+def _batches_are(n, *sizes):
+    return lambda r, t: batches(n, t) == list(sizes)
+
+
+def _smallest_n_of_a_second_block(r, t):
+    """At pr = 64 the filter launch gets a second block of rows at the smallest n of all pr, and this chunk is past it."""
+    first = {pr: next((n for n in range(1, t["MAX_CHUNK"] + 1) if row_blocks(n, pr, t) > 1), math.inf) for pr in (1, 2, 4, 8, 16, 32, 64)}
+    return problems_per_block(r["R"]) == 64 and first[64] == min(first.values()) == 65 and first[64] <= r["chunk"] < 3 * first[64]
+
+
+def _empty_slices(n, R, t):
+    pr, gy, S = tail_shape(n, R, t)
+    return sum(1 for s in range(S) if rows_of(slice_of(n, pr, gy, s, t)) == 0)
+
+
+def grid_cells(row):
+    """Accumulators of a problem of a grid row: the total, a cell per node of every axis and per node pair of every pair."""
+    bins = row["bins"]
+    return 1 + sum(bins) + sum(bins[a] * bins[b] for a, b in row.get("pairs", ()))
+
+
+def _edges_inside_runs(r, t):
+    """Every chunk edge lies inside a run of every axis but the fastest (whose runs are single indices), and inside a period of
+    every axis: no chunk starts or ends where a run does."""
+    bins, G = r["bins"], r["G"]
+    strides = [math.prod(bins[j + 1:]) for j in range(len(bins))]
+    edges = list(range(r["chunk"], G, r["chunk"]))
+    return len(edges) > 0 and all(e % (s * n) != 0 for e in edges for s, n in zip(strides, bins) if s * n < G) \
+        and all(e % s != 0 for e in edges for s in strides if s > 1)
+
+
+CHUNKS = {
+    "I1": dict(kind="importance", route="synthetic mocks", R=3, chunk=300, G=700, tail=(7, 100), predictive=True, reaches=[
+        ("chunks of 300, 300 and 100", _chunks_are(300, 300, 100)),
+        ("the rows kernel in two workgroups, the last partial", lambda r, t: _groups(300, t["kIsBlock"]) == 2 and 300 % t["kIsBlock"] != 0),
+        ("the weight kernel in four workgroups", lambda r, t: _groups(300 * r["R"], t["kIsBlock"]) == 4),
+        ("max-kernel slices of five rows", lambda r, t: max_slice_rows(300, r["R"], t["kIsBlock"]) == 5),
+        ("range_ahead over 18 full batches and 12 rows", lambda r, t: divmod(300, t["kIsAhead"]) == (18, 12)),
+        ("predict slices of 75 rows: nine kAhead batches and three rows", lambda r, t: 300 // t["predict.kSlices"] == 75
+         and divmod(75, t["predict.kAhead"]) == (9, 3)),
+        ("the evaluator in the upper cells band", lambda r, t: cells_range(300, t) == t["cpi2"]),
+        ("one block of rows in the filter kernel: the tail's geometry is that of the small tests", _tail_is(300, 4, 1, 64))]),
+    "I2": dict(kind="importance", route="synthetic mocks, repeated", R=70, chunk=130, G=300, tail=(20,), predictive=True, reaches=[
+        ("chunks of 130, 130 and 40", _chunks_are(130, 130, 40)),
+        ("pr = 64, three blocks of rows, twelve slices", _tail_is(130, 64, 3, 12)),
+        ("blockIdx.y > 0 where it starts at the smallest n", _smallest_n_of_a_second_block),
+        ("uneven cuts of the blocks: 43 and 86", lambda r, t: [block_begin(130, 3, y) for y in range(4)] == [0, 43, 86, 130]),
+        ("then a chunk with fewer slices than the one before", lambda r, t: tail_shape(40, r["R"], t)[2] < tail_shape(130, r["R"], t)[2]),
+        ("the wide predict kernel over two problem tiles", lambda r, t: problems_of_a_workgroup(r["R"]) == t["predict.kWave"]
+         and _groups(r["R"], t["predict.kWave"]) == 2)]),
+    "I3": dict(kind="importance", route="synthetic mocks", R=3, chunk=1100, G=2300, tail=(300, "all"), predictive=False, reaches=[
+        ("chunks of 1100, 1100 and 100", _chunks_are(1100, 1100, 100)),
+        ("two blocks of rows, 128 slices", _tail_is(1100, 4, 2, 128)),
+        ("1100 candidates: two batches, 1024 and 76", _batches_are(1100, 1024, 76)),
+        ("the evaluator unfused on partial sums", lambda r, t: not fused(1100, t) and cells_range(1100, t) == t["cpi2"]),
+        ("size 300: K = 301 past one workgroup, a threshold after chunk 1", lambda r, t: t["tail.kBlock"] < tail_entries(r, 300) <= r["chunk"]),
+        ("size G - 1: K = 2300 past a batch, never a threshold; chunk 2 merges 1100 into h = 1100 > kBatch", lambda r, t: tail_entries(r, "all") == r["G"]
+         and r["G"] > t["kBatch"] and r["chunk"] > t["kBatch"] and tail_entries(r, "all") <= t["kMaxK"])]),
+    "I4": dict(kind="importance", route="synthetic mocks", R=3, chunk=2049, G=2600, tail=(50,), predictive=True, reaches=[
+        ("chunks of 2049 and 551", _chunks_are(2049, 551)),
+        ("one workgroup per point just past kPartialPoints, the last chunk back on partial sums", lambda r, t: cells_range(2048, t) == t["cpi2"]
+         and cells_range(2049, t) == -1 and cells_range(551, t) == t["cpi2"]),
+        ("three blocks of rows, 192 slices", _tail_is(2049, 4, 3, 192)),
+        ("three batches: 1024, 1024 and 1", _batches_are(2049, 1024, 1024, 1))]),
+    "I5": dict(kind="importance", route="synthetic mocks, repeated", R=70, chunk=4200, G=4250, tail=(20, 4095), predictive=False, reaches=[
+        ("chunks of 4200 and 50", _chunks_are(4200, 50)),
+        ("the blocks of rows clamped at 64: S = 256 = kMaxSlices = kBlock", lambda r, t: tail_shape(4200, r["R"], t) == (64, 64, 256)
+         and -(-4200 // (slices_per_block(64, t) * t["kSliceRows"])) > 64 and t["kMaxSlices"] == t["tail.kBlock"] == 256),
+        ("five batches", lambda r, t: len(batches(4200, t)) == 5),
+        ("the weight kernel past 1000 workgroups", lambda r, t: _groups(4200 * r["R"], t["kIsBlock"]) > 1000),
+        ("size 4095: K = kMaxK", lambda r, t: tail_entries(r, 4095) == t["kMaxK"] <= r["G"])]),
+    "I6": dict(kind="importance", route="BOSS data vector", R=1, chunk=8192, G=8292, tail=(None, 2000), predictive=False, reaches=[
+        ("chunks of 8192 and 100", _chunks_are(8192, 100)),
+        ("pr = 1: 256 slices of 32 rows", lambda r, t: tail_shape(8192, 1, t) == (1, 1, 256)
+         and {rows_of(slice_of(8192, 1, 1, s, t)) for s in range(256)} == {32}),
+        ("exactly eight full batches", lambda r, t: 8192 % t["kBatch"] == 0 and batches(8192, t) == [t["kBatch"]] * 8),
+        ("the evaluator fused again under the gridded covariance, past the in-place path", lambda r, t: fused(8192, t)
+         and not fused(8192, t, gridded=False) and t["kZeroCopyMaxDefault"] < 8192),
+        ("the last chunk with 156 empty slices", lambda r, t: tail_shape(100, 1, t)[2] == 256 and _empty_slices(100, 1, t) == 156),
+        ("the default size holds K = 275", lambda r, t: tail_entries(r, None) == 275)]),
+    "I7": dict(kind="importance", route="dsplit_cov joint mocks", R=3, chunk=530, G=1100, tail=(10,), predictive=True, reaches=[
+        ("chunks of 530, 530 and 40", _chunks_are(530, 530, 40)),
+        ("the joint chi-square kernel past two sort chunks, past the fuse limit", lambda r, t: 530 > 2 * t["kJointSortChunk"]
+         and 530 > t["kFuseMaxDefault"])]),
+    "G1": dict(kind="grid", route="synthetic mocks", R=3, bins=(40, 30), pairs=((0, 1),), chunk=500, G=1200, reaches=[
+        ("chunks of 500, 500 and 200", _chunks_are(500, 500, 200)),
+        ("every chunk cuts runs at both ends", _edges_inside_runs),
+        ("a chunk holds several periods of the fast axis", lambda r, t: min(chunk_lengths(r)) >= 2 * r["bins"][-1]),
+        ("the rows kernel in two workgroups", lambda r, t: _groups(500, t["kGridBlock"]) == 2),
+        ("the total's walk over 15 batches and 20 rows", lambda r, t: divmod(500, t["kGridAhead"]) == (15, 20))]),
+    "G2": dict(kind="grid", route="synthetic mocks, repeated", R=70, bins=(60, 40), pairs=((0, 1),), chunk=2049, G=2400, reaches=[
+        ("chunks of 2049 and 351", _chunks_are(2049, 351)),
+        ("the max kernel over two problem tiles", lambda r, t: _groups(r["R"], problems_of_a_workgroup(r["R"])) == 2),
+        ("the accumulate kernel over tens of thousands of (cell, problem) threads", lambda r, t: grid_cells(r) * r["R"] >= 10000),
+        ("the evaluator one workgroup per point, then on partial sums", lambda r, t: cells_range(2049, t) == -1
+         and cells_range(351, t) == t["cpi2"])]),
+    "G3": dict(kind="grid", route="BOSS data vector", R=1, prior=True, bins=(24, 20, 18), pairs=(), chunk=8192, G=8640, reaches=[
+        ("chunks of 8192 and 448", _chunks_are(8192, 448)),
+        ("the prior's own problem: Rp = 2, lnprior[] at 8192 rows", lambda r, t: r["R"] + int(r["prior"]) == 2),
+        ("the fused-blended evaluator regime", lambda r, t: fused(8192, t) and not fused(8192, t, gridded=False)),
+        ("a chunk edge inside runs of all three axes", _edges_inside_runs)]),
+}
+
+# What stays untested: chunks above 8192 rows, up to the MAX_CHUNK = 65536 the product accepts (the default chunk of a call with
+# few problems), and nested sampling's select kernel above 160 live points.
+LARGEST_CHUNK_TESTED = 8192

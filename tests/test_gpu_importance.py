@@ -58,16 +58,19 @@ def rs(stack):
     return stack.realisations()
 
 
-def sample_of(block, names, seed=5, kept=G23):
+def sample_of(block, names, seed=5, kept=G23, draws=None):
     """``dict(sample=, ln_proposal=)`` of a correlated Gaussian proposal over ``names`` (in the block's sampled order), cut behind
-    its ``kept``-th point inside the box: G = 23 whatever the generator draws, and some points outside the box before it."""
+    its ``kept``-th point inside the box: G = ``kept`` (23 by default) whatever the generator draws, and some points outside the
+    box before it.  ``draws``: the points drawn before the cut, 200 for up to 23 kept points and four per kept point above."""
     from victor_amd import GaussianProposal
     d = len(names)
     cov = np.diag([WIDTH[n] ** 2 for n in names])
     for j in range(1, d):
         cov[0, j] = cov[j, 0] = 0.4 * WIDTH[names[0]] * WIDTH[names[j]]
     q = GaussianProposal(names, [CENTRE[n] for n in names], cov)
-    pts = GaussianProposal.draw(q.mean, q.chol, None, 200, seed)
+    if draws is None:
+        draws = 200 if kept <= G23 else 4 * kept
+    pts = GaussianProposal.draw(q.mean, q.chol, None, draws, seed)
     lo, hi = (np.array([block[n]["prior"][k] for n in names]) for k in ("min", "max"))
     inside = np.all((pts >= lo) & (pts <= hi), axis=1)
     end = int(np.flatnonzero(np.cumsum(inside) == kept)[0]) + 1
@@ -100,13 +103,13 @@ def both_routes(obj, params, what, **kw):
 class Handle:
     """A raw vk_is handle of a call's arguments (victor_amd.importance.create_handle), for what the public route does not expose."""
 
-    def __init__(self, fit, params, names, realisations=None, fixed=None, bins=4, ranges=None, pairs=None, chunk=7, prior=None, spoil=None):
+    def __init__(self, fit, params, names, realisations=None, fixed=None, bins=4, ranges=None, pairs=None, chunk=7, prior=None, spoil=None, kept=G23):
         from victor_amd import importance as I
         from victor_amd.fitting import _Sampled
         q = _Sampled("importance_posterior", "sampled", params, fixed)
         assert q.names == names
         self.layout = I.resolve_layout("test", q.names, q.lo, q.hi, bins, ranges, pairs)
-        s = sample_of(params, names)
+        s = sample_of(params, names, kept=kept)
         inside = np.all((s["sample"] >= q.lo) & (s["sample"] <= q.hi), axis=1)
         kept = s["sample"][inside]
         self.sample = I.Sample(kept, kept.mean(axis=0), s["ln_proposal"][inside], len(inside), q.lo, q.hi, q.prior(prior, fit))

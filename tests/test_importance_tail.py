@@ -147,7 +147,21 @@ DRIVER = r"""
 #include "vk_is_tail.h"
 // tail K chunk batch pr in out: the values of one problem, point after point, go through a threshold filter per chunk - slice by
 // slice, a workgroup of pr problems - and a merge in batches: the steps of vk_kernel_is_tail.h over the rules of the header
+// tail geometry n R: the launch shape of a chunk of n rows for R problems as the rules of the header give it - "pr per gy S", the
+// gy + 1 block cuts, then "first end step rows" of every slice (tests/test_launch_shapes.py holds its Python twins to this)
+static int geometry(int n, int R) {
+  const int pr = vkist::problems_per_block(R), per = vkist::slices_per_block(pr), gy = vkist::row_blocks(n, pr), S = gy * per;
+  printf("%d %d %d %d\n", pr, per, gy, S);
+  for (int y = 0; y <= gy; ++y) printf("%d%c", vkist::block_begin(n, gy, y), y == gy ? '\n' : ' ');
+  for (int s = 0; s < S; ++s) {
+    const vkist::Slice c = vkist::slice_of(n, pr, gy, s);
+    printf("%d %d %d %d\n", c.first, c.end, c.step, vkist::rows_of(c));
+  }
+  return 0;
+}
+
 int main(int argc, char** argv) {
+  if (argc == 4 && argv[1][0] == 'g') return geometry(atoi(argv[2]), atoi(argv[3]));
   if (argc != 7) return 2;
   const int K = atoi(argv[1]), chunk = atoi(argv[2]), batch = atoi(argv[3]), pr = atoi(argv[4]);
   FILE* fi = fopen(argv[5], "rb");
@@ -259,6 +273,14 @@ def tail_driver(tmp_path_factory):
         out = np.fromfile(str(fout), dtype=np.float64)
         h = int(out[0])
         return h, out[1:1 + h], out[1 + h:1 + 2 * h].astype(np.int64)
+
+    def geometry(n, R):
+        """``((pr, per, gy, S), the block cuts, [(first, end, step, rows) of every slice])`` of a chunk of n rows, R problems."""
+        done = subprocess.run([str(exe), "geometry", str(n), str(R)], capture_output=True, text=True)
+        assert done.returncode == 0, (done.returncode, done.stderr[-2000:])
+        lines = [tuple(int(v) for v in line.split()) for line in done.stdout.splitlines()]
+        return lines[0], lines[1], lines[2:]
+    run.geometry = geometry
     return run
 
 

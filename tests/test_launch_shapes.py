@@ -1,12 +1,15 @@
 """The shape table of tests/launch_shapes.py against the sources, without a GPU: every row still reaches what it was chosen
 for at the thresholds as they stand in victor_hip.hip, vk_host.h, the kernel headers and chains.py, every row is a case of
 tests/test_gpu_launch_shapes.py, and no shape exceeds what ``sample_chains`` accepts.  The same for ``STENCILS``, the shapes of the
-two stencil calls (tests/test_gpu_stencil_shapes.py), and for the cases at the LDS ceiling of the Fisher assemble kernel.  A
-failure names the row to revisit."""
+two stencil calls (tests/test_gpu_stencil_shapes.py), and for the cases at the LDS ceiling of the Fisher assemble kernel, and for ``CHUNKS``, the
+shapes of the chunked grid and importance pipeline (tests/test_gpu_chunk_shapes.py), whose tail geometry is stated by Python
+twins of victor_amd/csrc/vk_is_tail.h that are held to the header under g++.  A failure names the row to revisit."""
 
+import numpy as np
 import pytest
 
 from tests import launch_shapes as LS
+from tests.test_importance_tail import tail_driver  # noqa: F401  (a fixture: vk_is_tail.h under g++)
 
 
 @pytest.fixture(scope="module")
@@ -110,3 +113,67 @@ def test_every_stencil_row_is_a_gpu_case():
         mine = [i for i in ids if i.split("-")[0] == case]
         assert len(mine) == len(LS.stencil_variants(row)), (case, mine)
     assert {i.split("-")[0] for i in ids} == set(LS.STENCILS)
+
+
+# ------------------------------------------------------------------ the chunked pipeline: grid and importance posteriors ------------
+def test_the_chunk_thresholds_are_found_and_in_order(t):
+    assert t["kIsBlock"] == t["kGridBlock"] == t["tail.kBlock"] == 256, "workgroups of 256 threads: every row of CHUNKS assumes it"
+    assert t["kMaxSlices"] <= t["tail.kBlock"] and t["kBatch"] % t["tail.kBlock"] == 0 and t["kBatch"] < t["kMaxK"]
+    assert t["predict.kWave"] == 64 and t["predict.kSlices"] * t["predict.kWave"] == 256
+    assert 0 < t["kIsListAhead"] < t["kIsAhead"] < t["kGridAhead"] and t["predict.kAhead"] > 1 and t["predict.kTile"] > 0
+    assert max(max(LS.chunk_lengths(r)) for r in LS.CHUNKS.values()) == LS.LARGEST_CHUNK_TESTED < t["MAX_CHUNK"], \
+        "LARGEST_CHUNK_TESTED and the paragraphs of DESIGN.md sections 7c and 7e no longer say what is tested"
+    assert LS.problems_of_a_workgroup(1) == 1 and LS.problems_of_a_workgroup(3) == 4 and LS.problems_of_a_workgroup(70) == 64
+    # the chunk sizes the GPU suite ran before CHUNKS: one block of rows, one batch, whatever R
+    for n in (7, 20, 23, 40, 48, 60, 64):
+        for R in (1, 3, 16, 70):
+            assert LS.tail_shape(n, R, t)[1] == 1 and len(LS.batches(n, t)) == 1
+
+
+@pytest.mark.parametrize("case", sorted(LS.CHUNKS))
+def test_a_chunk_row_reaches_what_it_is_about(t, case):
+    row = LS.CHUNKS[case]
+    lengths = LS.chunk_lengths(row)
+    assert sum(lengths) == row["G"] and max(lengths) == lengths[0] == row["chunk"] <= t["MAX_CHUNK"] and 0 < lengths[-1] < row["chunk"]
+    assert row["kind"] in ("importance", "grid") and 1 <= row["R"]
+    if row["kind"] == "grid":
+        assert np.prod(row["bins"]) == row["G"]
+    else:
+        for size in row["tail"]:
+            assert 2 <= LS.tail_entries(row, size) <= min(row["G"], t["kMaxK"]), (case, size)
+    for text, check in row["reaches"]:
+        assert check(row, t), f"chunk row {case} (R = {row['R']}, chunk {row['chunk']}, G = {row['G']}) no longer reaches: {text} - revisit its shape"
+
+
+@pytest.mark.parametrize("case", sorted(k for k, r in LS.CHUNKS.items() if r["kind"] == "importance"))
+def test_the_tail_twins_are_the_header(t, tail_driver, case):
+    """``problems_per_block``, ``slices_per_block``, ``row_blocks``, ``block_begin``, ``slice_of`` and ``rows_of`` of
+    tests/launch_shapes.py against victor_amd/csrc/vk_is_tail.h under g++, at every (n, R) of the row."""
+    row = LS.CHUNKS[case]
+    for n in sorted(set(LS.chunk_lengths(row))):
+        (pr, per, gy, S), cuts, slices = tail_driver.geometry(n, row["R"])
+        assert (pr, per) == (LS.problems_per_block(row["R"]), LS.slices_per_block(pr, t)), (case, n)
+        assert (pr, gy, S) == LS.tail_shape(n, row["R"], t) and gy == LS.row_blocks(n, pr, t), (case, n)
+        assert list(cuts) == [LS.block_begin(n, gy, y) for y in range(gy + 1)], (case, n)
+        assert len(slices) == S <= t["kMaxSlices"]
+        seen = np.zeros(n, dtype=int)
+        for s, (first, end, step, rows) in enumerate(slices):
+            mine = LS.slice_of(n, pr, gy, s, t)
+            assert (first, end, step) == mine and rows == LS.rows_of(mine), (case, n, s)
+            seen[first:end:step] += 1
+        assert np.all(seen == 1), (case, n)                          # every row in exactly one slice
+
+
+def test_every_chunk_row_is_a_gpu_case():
+    """The GPU file's parametrisation is built from the table: every row, every tail size, every predictive row."""
+    import tests.test_gpu_chunk_shapes as G
+    ids = [i for ids in G.IDS.values() for i in ids]
+    assert {i.split("-")[0] for i in ids} == set(LS.CHUNKS)
+    for case, row in LS.CHUNKS.items():
+        mine = {name: [i for i in ids_ if i.split("-")[0] == case] for name, ids_ in G.IDS.items()}
+        if row["kind"] == "grid":
+            assert mine["test_grid"] == [f"{case}-grid"], (case, mine)
+            continue
+        assert mine["test_importance"] == [f"{case}-plain"], (case, mine)
+        assert mine["test_tail"][:len(row["tail"])] == [f"{case}-{size}" for size in row["tail"]], (case, mine)
+        assert (mine["test_predictive"] == [f"{case}-predictive"]) == row["predictive"], (case, mine)
