@@ -17,10 +17,13 @@
   (``--definition-once-max``: beyond that not at all);
 * ``--tail``: the same call with ``tail=True`` - per mock the Pareto shape k of its largest weights against the threshold, and
   the raw against the smoothed ``ln_evidence`` in units of ``ln_evidence_error``; with ``--timing`` the same three routes with
-  ``tail`` for ``predictive``: the device route without and with it, and the definition route with it.
+  ``tail`` for ``predictive``: the device route without and with it, and the definition route with it;
+* ``--own``: the two-pass recipe - the shared sample with ``tail=True``, then the mocks it flags (``LOW_ESS``, ``HIGH_K``; with
+  ``--own-all`` every mock) once more from a proposal of their own, ``ProposalSet.from_fits(bf, bf.laplace, inflate=--inflate,
+  dof=--dof).take(flagged)`` with ``--own-n`` points per mock, and the two passes side by side.
 
     python examples/importance_posterior.py [--joint] [--timing] [--evidence] [--predictive] [--tail] [--sizes 1,16,1024]
-                                            [--samples 5] [--out FILE]
+                                            [--samples 5] [--own] [--own-all] [--own-n 4096] [--inflate 2] [--dof K] [--out FILE]
 
 Needs a GPU and the test fixtures of the repository (tests/golden)."""
 
@@ -55,6 +58,32 @@ def show_tail(ip):
             "ess_raw": ip.ess.tolist(), "ess": t.ess.tolist(), "ln_evidence_raw": ip.ln_evidence.tolist(), "ln_evidence": t.ln_evidence.tolist(),
             "ln_evidence_error_raw": ip.ln_evidence_error.tolist(), "ln_evidence_error": t.ln_evidence_error.tolist(),
             "raw_minus_smoothed_over_error": pull.tolist()}
+
+
+def two_passes(stack, rs, params, bf, first, args):
+    """``--own``: the mocks the shared sample ``first`` (``tail=True``) flags, sampled again from their own proposals."""
+    from victor_amd import ProposalSet
+    t = first.tail
+    flagged = np.arange(len(first)) if args.own_all else np.flatnonzero((first.status != first.OK) | (t.status == t.HIGH_K))
+    print(f"shared sample: {len(flagged)} of {len(first)} mocks {'taken' if args.own_all else 'flagged (LOW_ESS or HIGH_K)'}: {flagged.tolist()}")
+    if not len(flagged):
+        return {"flagged": []}
+    qs = ProposalSet.from_fits(bf, bf.laplace, inflate=args.inflate, dof=args.dof)
+    sub = stack.realisations(rs.numbers[flagged])
+    clock = time.perf_counter()
+    again = sub.importance_posterior(params, qs.take(flagged), n=args.own_n, seed=0, tail=True)
+    seconds = time.perf_counter() - clock
+    print(f"second pass: {args.own_n} points per mock from its own proposal (inflate {args.inflate}, dof {args.dof}) in {seconds:.3f} s; "
+          f"pooled instead of own: {np.flatnonzero(qs.pooled[flagged]).tolist()}")
+    for i, r in enumerate(flagged):
+        print(f"mock {r:3d}: ESS {first.ess[r]:8.0f} of {first.n_inside} -> {again.ess[i]:8.0f} of {again.n_inside[i]}  k {t.k[r]:+.3f} -> "
+              f"{again.tail.k[i]:+.3f}  ln_evidence {first.ln_evidence[r]:.4f} +- {first.ln_evidence_error[r]:.4f} -> "
+              f"{again.ln_evidence[i]:.4f} +- {again.ln_evidence_error[i]:.4f}")
+    return {"flagged": flagged.tolist(), "seconds": seconds, "n": args.own_n, "inflate": args.inflate, "dof": args.dof,
+            "pooled": qs.pooled[flagged].tolist(), "n_inside": again.n_inside.tolist(), "ess_shared": first.ess[flagged].tolist(),
+            "ess_own": again.ess.tolist(), "k_shared": t.k[flagged].tolist(), "k_own": again.tail.k.tolist(),
+            "ln_evidence_shared": first.ln_evidence[flagged].tolist(), "ln_evidence_own": again.ln_evidence.tolist(),
+            "ln_evidence_error_own": again.ln_evidence_error.tolist(), "status_own": again.status.tolist()}
 
 
 def show_predictive(ip, first=3):
@@ -181,6 +210,11 @@ def main():
     ap.add_argument("--n", type=int, default=65536, help="draws")
     ap.add_argument("--predictive", action="store_true", help="the posterior band and the DIC; with --timing its cost")
     ap.add_argument("--tail", action="store_true", help="the Pareto shape of the largest weights and the smoothed evidence; with --timing its cost")
+    ap.add_argument("--own", action="store_true", help="the mocks the shared sample flags, once more from a proposal of their own")
+    ap.add_argument("--own-all", action="store_true", help="... every mock, flagged or not")
+    ap.add_argument("--own-n", type=int, default=4096, help="... points per mock")
+    ap.add_argument("--inflate", type=float, default=2.0, help="... the Laplace covariance times this")
+    ap.add_argument("--dof", type=float, default=None, help="... a Student-t of this many degrees of freedom")
     ap.add_argument("--definition-max", type=int, default=16, help="problems up to which --timing --predictive repeats the definition route")
     ap.add_argument("--definition-once-max", type=int, default=1024, help="... and up to which it runs it at least once")
     args = ap.parse_args()
@@ -221,6 +255,8 @@ def main():
         res["predictive"] = show_predictive(timed(rs, params, q, True, args.n, True)[1])
     if args.tail:
         res["tail"] = show_tail(timed(rs, params, q, True, args.n, tail=True)[1])
+    if args.own or args.own_all:
+        res["own"] = two_passes(stack, rs, params, bf, timed(rs, params, q, True, args.n, tail=True)[1], args)
 
     if args.timing:
         res["timing"] = {}

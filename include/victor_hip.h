@@ -903,6 +903,29 @@ int vk_is_predictive(vk_is* h, double* pivot_t, double* sum_t, double* sum_tt, d
  *   that is not complete. */
 int vk_is_set_tail(vk_is* h, int32_t K);
 int vk_is_tail(vk_is* h, double* lnpost, int64_t* index, int64_t* count);
+/* A proposal per problem (victor_amd/csrc/vk_kernel_is_own.h; the definition: victor_amd/importance.py, rule 8): R problems, each
+ * with G points of its OWN - drawn from its own proposal, a best fit with its Laplace covariance, say - and evaluated against
+ * realisation which[r] alone: point g of problem r is row g R + r of a pairs-mode evaluation, so a run costs G R theory
+ * evaluations.  A context with model realisations set (vk_set_model_realisations) is accepted, as vk_nested_create and
+ * vk_chain_create accept it: row g R + r is then evaluated with the model of realisation which[r].
+ * Arguments as vk_is_create, with the problem the fastest-varying index of everything that was one value per point:
+ *   n_points    G, the points of EVERY problem;  n_problems R;  which [R], each in 0 .. n_real - 1
+ *   x, y        [G][R][n_axes];   eps_pow, lno, lno_prior [G][R].  lno may be -inf: a point the caller drew outside the prior
+ *               box, whose x the caller has replaced by a point inside (it is evaluated, weighs nothing and is in no list)
+ *   lists       [R][n_axes + n_pairs][G]: problem r's lists, each as vk_is_create's
+ *   offsets     [chunks][R][cells + lists]: per chunk, problem after problem; chunks x R x (cells + lists) <= 2^27
+ *   chunk       points of every problem per launch: chunk x R <= 65536 rows;  G x R <= 2^24
+ * Every index a kernel will form is checked as vk_is_create checks it, per problem; refused with text in err besides: an index of
+ * which outside the context's realisations; G x R or chunk x R above their limits; model realisations whose number differs from
+ * the data realisations'.  With lno_prior problem r has a prior problem of its own (lnpost = lno_prior[g][r], a total alone).
+ * vk_is_run, _result, _set_tail, _tail, _last_error and _destroy serve the handle as they serve vk_is_create's, per problem r over
+ * its own points; vk_is_rows(first, count) returns count x R rows, row i R + r point first + i of problem r; vk_is_result writes
+ * R values to prior_ln_max and to prior_total; vk_is_set_predictive is refused (VK_E_ARG). */
+vk_is* vk_is_create_own(vk_ctx* ctx, const vk_eval_opts* opts, int32_t n_axes, const int32_t* columns, int64_t n_points,
+                        int32_t n_problems, const int32_t* which, const double* x, const double* y, const double* eps_pow,
+                        const double* lno, const double* lno_prior, const int32_t* n_bins, int32_t n_pairs, const int32_t* pair_bins,
+                        const int32_t* lists, const int32_t* offsets, const double* base_row, double alpha, int32_t chunk, char* err,
+                        size_t errlen);
 
 /* ---- nested sampling: the evidence and a posterior sample of the data vector or of every realisation ---------------------------
  * R problems of L live points each inside the box [lo, hi]; per iteration the K lowest live points of every problem die and K

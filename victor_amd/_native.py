@@ -225,6 +225,10 @@ SYMBOLS = {
                                         C.POINTER(C.c_int32), C.c_int64, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int32), C.c_int32,
                                         C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp, C.c_double,
                                         C.c_int32, C.c_int32, C.c_char_p, C.c_size_t]),
+    # ... with a proposal per problem: n_problems and which behind n_points, no every_realisation
+    "vk_is_create_own": (_vp, [_vp, _optp, C.c_int32, C.POINTER(C.c_int32), C.c_int64, C.c_int32, C.POINTER(C.c_int32), _dp, _dp, _dp,
+                               _dp, _dp, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                               C.POINTER(C.c_int32), _dp, C.c_double, C.c_int32, C.c_char_p, C.c_size_t]),
     "vk_is_run": (C.c_int, [_vp, C.c_int64, C.c_int64]),
     "vk_is_rows": (C.c_int, [_vp, C.c_int64, C.c_int32, _dp]),
     "vk_is_result": (C.c_int, [_vp, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),

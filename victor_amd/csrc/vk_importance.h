@@ -118,6 +118,22 @@ VK_GRID_HD inline void rescale_sq(double& acc, double factor) {
   vkgrid::rescale(acc, factor);
 }
 
+// ---- a proposal per problem (vk_is_create_own; victor_amd/importance.py rule 8) ------------------------------------------------
+// Every problem r has its own n points: what was one value per point g is one per (g, r), the problem the fastest-varying index,
+// so the lanes of a wave - consecutive problems of one point - read consecutive values.
+//   x, y                 [G][R][d]   point (g, r) at (g R + r) d
+//   eps_pow, lno, lnop   [G][R]      value_at(g, r, R); with stride 0 the same call names the shared mode's one value per point
+//   rows, lnL, w         [n][R]      row i R + r of a chunk is point g0 + i of problem r, evaluated against realisation which[r]
+//   lists                [R][n_lists][G]            problem r's list l at own_list(r, l, n_lists, G)
+//   offsets              [n_chunks][R][cells + n_lists]   chunk c, problem r at own_offsets(c, r, R, cells + n_lists)
+// Under a prior problem R + r is problem r's prior problem (prior_of): lnpost = lnop[g][r], a total alone.
+VK_GRID_HD inline long long value_at(long long g, int r, int stride) { return stride ? g * stride + r : g; }
+VK_GRID_HD inline long long own_row(long long i, int r, int R) { return i * R + r; }
+VK_GRID_HD inline long long own_list(int r, int l, int n_lists, long long G) { return ((long long)r * n_lists + l) * G; }
+VK_GRID_HD inline long long own_offsets(long long c, int r, int R, long long per_chunk) { return (c * R + r) * per_chunk; }
+// the problem whose sample (points, y, lists, weights' row) problem r of the Rp = R or 2 R reads, and is it a prior problem
+VK_GRID_HD inline int prior_of(int r, int R) { return r >= R ? r - R : r; }
+
 // One chunk's segment of a list against its offsets, as vk_is_create checks every one before a kernel may index with them: n the
 // chunk's points, cells the list's cells, off[0 .. cells].  0: off[0] = 0, the offsets never decrease, off[cells] <= n, every
 // entry is a point of the chunk and the entries of a cell increase.  1: the offsets are wrong, at offset *where; 2: an entry is,

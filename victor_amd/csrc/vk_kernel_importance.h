@@ -38,7 +38,8 @@ constexpr int kIsListAhead = 4;        // ... a list walk
 static_assert(vkis::kMaxP == vkrow::kMaxP, "a sample's axes are sampled parameters");
 
 struct IsArgs {
-  int d, R, Rp;                      // axes; problems; with the prior's own (R + 1 with a prior, else R)
+  int d, R, Rp;                      // axes; problems; with the prior's own (R + 1 with a prior, else R; a proposal per problem: 2 R)
+  int own;                           // 0: one sample for all problems; R: a proposal per problem (vk_kernel_is_own.h), values [G][R]
   long long G, g0;                   // the sample; the chunk: points g0 .. g0 + n - 1 are rows 0 .. n - 1
   int n;
   // rows kernel
@@ -65,14 +66,17 @@ struct IsArgs {
   int cell_off[vkis::kMaxLists + 1]; // the first cell of every list among the histogram cells, and their number
 };
 
-// lnpost of row i for problem r as every kernel reads it: one addition
+// lnpost of row i for problem r as every kernel reads it: one addition.  lno, lnop and the prior problems' weights are one value
+// per point, or (a.own = R) one per point and problem: vkis::value_at names either
 __device__ __forceinline__ double is_post(const IsArgs& a, int i, int r) {
-  if (r >= a.R) return vkgrid::clean(a.lnop[a.g0 + i]);
+  if (r >= a.R) return vkgrid::clean(a.lnop[vkis::value_at(a.g0 + i, r - a.R, a.own)]);
   double v = a.lnl[(size_t)i * a.R + r];
-  v = v + a.lno[a.g0 + i];
+  v = v + a.lno[vkis::value_at(a.g0 + i, r, a.own)];
   return vkgrid::clean(v);
 }
-__device__ __forceinline__ double is_weight(const IsArgs& a, int i, int r) { return r < a.R ? a.w[(size_t)i * a.R + r] : a.wp[i]; }
+__device__ __forceinline__ double is_weight(const IsArgs& a, int i, int r) {
+  return r < a.R ? a.w[(size_t)i * a.R + r] : a.wp[vkis::value_at(i, r - a.R, a.own)];
+}
 
 // the start of a run: nothing seen
 __global__ void __launch_bounds__(kIsBlock) vk_is_init_kernel(IsArgs a) {
@@ -122,7 +126,7 @@ __global__ void __launch_bounds__(kIsBlock) vk_is_weight_kernel(IsArgs a) {
   const double m = a.run[r].m;
   const double w = m > vkgrid::neg_inf() ? vkgrid::weight(is_post(a, i, r), m, [](double x) { return exp(x); }) : 0.0;
   if (r < a.R) a.w[(size_t)i * a.R + r] = w;
-  else a.wp[i] = w;
+  else a.wp[vkis::value_at(i, r - a.R, a.own)] = w;
 }
 
 __global__ void __launch_bounds__(kIsBlock) vk_is_accumulate_kernel(IsArgs a) {

@@ -29,6 +29,7 @@
 // the unique sorted arrangement of its set: two runs give the same bytes.  The prior's own problem keeps no tail.
 #pragma once
 #include "vk_common.h"
+#include "vk_importance.h"
 #include "vk_is_tail.h"
 
 namespace vk {
@@ -38,7 +39,8 @@ struct IsTailArgs {
   int pr, gy;                        // problems of a filter workgroup; blocks of rows of the chunk (grid.y of the filter launch)
   long long g0;                      // the chunk: points g0 .. g0 + n - 1 are rows 0 .. n - 1
   const double* lnl;                 // [n][R]
-  const double* lno;                 // [G]
+  const double* lno;                 // [G]; a proposal per problem (own = R): [G][R]
+  int own;                           // 0, or R: the stride of vkis::value_at, as IsArgs::own
   double* threshold;                 // [R]: the K-th held value, -inf while fewer are held
   int* count;                        // [R]: entries held
   int* side;                         // [R]: which of the two buffers holds the problem's list
@@ -51,7 +53,7 @@ struct IsTailArgs {
 // lnpost of row i for problem r: vk_kernel_importance.h's is_post, one addition
 __device__ __forceinline__ double is_tail_post(const IsTailArgs& a, int i, int r) {
   double v = a.lnl[(size_t)i * a.R + r];
-  v = v + a.lno[a.g0 + i];
+  v = v + a.lno[vkis::value_at(a.g0 + i, r, a.own)];
   return vkgrid::clean(v);
 }
 

@@ -47,6 +47,8 @@
 //   vk_kernel_importance.h importance-sampled posteriors (vk_is_run; the section behind the grid's): rows, max, weight and accumulate
 //                        kernels of a chunk of an uploaded sample, over the index rules, the list walk and the terms of
 //                        vk_importance.h (plain C++, likewise)
+//   vk_kernel_is_own.h   ... with a proposal per problem (vk_is_create_own): the rows and accumulate kernels over [n][R] rows in
+//                        pairs mode; the max, weight and tail kernels are the shared sample's, with a stride
 //   vk_kernel_is_predict.h the posterior-predictive sums of an importance handle (vk_is_set_predictive): the product kernel behind
 //                        every chunk's accumulate kernel, weights x theory vectors, over the tile and index rules and the terms
 //                        of vk_is_predict.h (plain C++, likewise)
@@ -80,6 +82,7 @@
 #include "vk_kernel_fisher.h"
 #include "vk_kernel_grid.h"
 #include "vk_kernel_importance.h"
+#include "vk_kernel_is_own.h"
 #include "vk_kernel_is_predict.h"
 #include "vk_kernel_is_tail.h"
 #include "vk_kernel_nested.h"
@@ -2016,6 +2019,7 @@ int vk_grid_result(vk_grid* f, double* ln_max, int64_t* arg_max, double* total, 
 struct __attribute__((visibility("hidden"))) vk_is : Sampled {
   int R = 1, chunk = 0, n_lists = 0, n_cells = 0, n_acc = 0, n1 = 0, n2 = 0;
   bool eps = false, own = false;           // epsilon is sampled; the prior's own problem rides along
+  bool each = false;                       // a proposal per problem (vk_is_create_own): R samples of G points, pairs mode
   long long G = 0, n_chunks = 0;
   int cell_off[vkis::kMaxLists + 1] = {};
   long long done = 0;                      // points [0, done) are in the accumulators
@@ -2060,10 +2064,13 @@ struct __attribute__((visibility("hidden"))) vk_is : Sampled {
     c.take(p_w, (size_t)chunk * r);
   }
 
-  void shape(int, const double*, const double*) { rows_max = (size_t)chunk; }
+  void shape(int, const double*, const double*) { rows_max = (size_t)chunk * (each ? (size_t)R : 1); }
   long long offsets_per_chunk() const { return (long long)n_cells + n_lists; }
+  // a proposal per problem: every per-point array holds R values per point ([G][R]...), a chunk has chunk R rows, every problem
+  // has a prior problem of its own (2 R running states and accumulator columns) and the rows carry their realisation
   void layout(Carve& c) {
-    const size_t n = (size_t)chunk, r = (size_t)R, g = (size_t)G;
+    const size_t r = (size_t)R, m = each ? r : 1, n = (size_t)chunk * m, g = (size_t)G * m;
+    if (each) return layout_each(c, r, n, g);
     c.take(d_run, r + 1);
     c.take(d_base, (size_t)sets * VK_NPAR);          // (a base row and a set of pending rows per block: vk_is_create_joint_blocks)
     c.take(d_rows, (size_t)sets * n * VK_NPAR);
@@ -2080,7 +2087,26 @@ struct __attribute__((visibility("hidden"))) vk_is : Sampled {
     c.take(d_list, (size_t)n_lists * g);
     c.take(d_off, (size_t)(n_chunks * offsets_per_chunk()));
   }
-  int Rp() const { return own ? R + 1 : R; }
+  void layout_each(Carve& c, size_t r, size_t n, size_t g) {
+    c.take(d_run, 2 * r);
+    c.take(d_base, VK_NPAR);
+    c.take(d_rows, n * VK_NPAR);
+    c.take(d_x, g * P);
+    c.take(d_y, g * P);
+    c.take(d_eps, eps ? g : 1);
+    c.take(d_lno, g);
+    c.take(d_lnop, own ? g : 1);
+    c.take(d_lnl, n);
+    c.take(d_chi, n);                      // the evaluation's chi-squares, then the chunk's weights [chunk][R]
+    c.take(d_wp, n);                       // ... of the prior problems
+    c.take(d_th, workspace_doubles());
+    c.take(d_acc, (size_t)n_acc * 2 * r);
+    c.take(d_list, (size_t)n_lists * g);
+    c.take(d_off, (size_t)(n_chunks * offsets_per_chunk()) * r);
+    c.take(d_which, r);
+    c.take(d_row_which, n);
+  }
+  int Rp() const { return own ? (each ? 2 * R : R + 1) : R; }
 };
 
 static IsArgs is_args(const vk_is* f) {
@@ -2088,6 +2114,7 @@ static IsArgs is_args(const vk_is* f) {
   a.d = f->P;
   a.R = f->R;
   a.Rp = f->Rp();
+  a.own = f->each ? f->R : 0;
   a.G = f->G;
   a.x = f->d_x;
   a.eps_pow = f->eps ? f->d_eps : nullptr;
@@ -2120,6 +2147,12 @@ static IsArgs is_args(const vk_is* f) {
 static int is_ready(vk_is* f, const char* who) {
   int rc = sampled_ready(f, who, "sample", true);
   if (rc || !f->real) return rc;
+  if (f->each) {                           // pairs mode: the indices were checked (max_which); model realisations count as the data's
+    if (f->ctx->n_sets > 0 && f->ctx->n_sets != f->ctx->n_real)
+      return refused(f, std::string(who) + ": the context holds " + std::to_string(f->ctx->n_sets) + " model realisations and " +
+                            std::to_string(f->ctx->n_real) + " realisations of the data: the counts must agree");
+    return VK_OK;
+  }
   const size_t nb = f->blocks.empty() ? 1 : f->blocks.size();
   for (size_t q = 0; q < nb; ++q) {
     const vk_ctx* c = f->blocks.empty() ? f->ctx : f->blocks[q];
@@ -2179,6 +2212,7 @@ static IsTailArgs is_tail_args(const vk_is* f, const IsArgs& a) {
   q.g0 = a.g0;
   q.lnl = f->d_lnl;
   q.lno = f->d_lno;
+  q.own = a.own;
   q.threshold = f->t_threshold;
   q.count = f->t_count;
   q.side = f->t_side;
@@ -2198,6 +2232,30 @@ static int is_tail_chunk(vk_is* f, const IsArgs& a) {
   return sampled_launch(f, vk_is_tail_merge_kernel, (long long)q.R * vkist::kBlock, vkist::kBlock, q);
 }
 
+// a proposal per problem: the words of vk_kernel_is_own.h for the chunk of `a`
+static IsOwnArgs is_own_args(const vk_is* f, const IsArgs& a) {
+  IsOwnArgs q{};
+  q.is = a;
+  q.which = f->d_which;
+  q.row_which = f->d_row_which;
+  q.per_chunk = f->offsets_per_chunk();
+  return q;
+}
+
+// ... and its chunk: the rows [n][R], their evaluation in pairs mode, then the shared sample's max, tail and weight kernels over
+// the [n][R] values and the accumulate kernel that walks every problem's own lists
+static int is_own_chunk(vk_is* f, const IsArgs& a) {
+  const IsOwnArgs q = is_own_args(f, a);
+  const long long rows = (long long)a.n * a.R;
+  int rc = sampled_launch(f, vk_is_own_rows_kernel, rows, kIsBlock, q);
+  if (rc == VK_OK) rc = sampled_evaluate(f, rows, f->d_lnl, f->d_chi);
+  if (rc == VK_OK) rc = sampled_launch(f, vk_is_max_kernel, (long long)((a.Rp + a.pr - 1) / a.pr) * kIsBlock, kIsBlock, a);
+  if (rc == VK_OK && f->tail_K) rc = is_tail_chunk(f, a);
+  if (rc == VK_OK) rc = sampled_launch(f, vk_is_weight_kernel, (long long)a.n * a.Rp, kIsBlock, a);
+  if (rc == VK_OK) rc = sampled_launch(f, vk_is_own_accumulate_kernel, (long long)a.n_acc * a.Rp, kIsBlock, q);
+  return rc;
+}
+
 // the launches of points [first, end), chunk by chunk
 static int is_chunks(vk_is* f, long long first, long long end) {
   IsArgs a = is_args(f);
@@ -2207,7 +2265,11 @@ static int is_chunks(vk_is* f, long long first, long long end) {
   for (long long g0 = first; g0 < end && rc == VK_OK; g0 += f->chunk) {
     a.g0 = g0;
     a.n = (int)std::min<long long>(f->chunk, end - g0);
-    a.off = f->d_off + (g0 / f->chunk) * f->offsets_per_chunk();
+    a.off = f->d_off + (g0 / f->chunk) * f->offsets_per_chunk() * (f->each ? f->R : 1);   // (vkis::own_offsets(c, 0, R, per chunk))
+    if (f->each) {
+      rc = is_own_chunk(f, a);
+      continue;
+    }
     rc = sampled_launch(f, vk_is_rows_kernel, a.n, kIsBlock, a);
     if (rc == VK_OK) rc = sampled_evaluate(f, a.n, f->d_lnl, f->d_chi);
     if (rc == VK_OK) rc = sampled_launch(f, vk_is_max_kernel, (long long)((a.Rp + a.pr - 1) / a.pr) * kIsBlock, kIsBlock, a);
@@ -2224,12 +2286,15 @@ static int is_chunks(vk_is* f, long long first, long long end) {
 // vk_is_create and its _joint forms (`who`): the one place where a sample's shape, bins, offsets, lists and values are checked,
 // the handle is made (sampled_create) and the sample goes up.  joint: ctxs are the n_ctx blocks of a joint fit, lead first, under
 // cov (NULL: block-diagonal); otherwise ctxs is the one context.  param_block (the _blocks form; NULL otherwise): the block each
-// axis belongs to, or -1; base_rows then holds one row per block.
+// axis belongs to, or -1; base_rows then holds one row per block.  which (vk_is_create_own; NULL otherwise): n_problems
+// realisation indices - every per-point array then holds a value per point and problem, the lists and offsets a set per problem
+// (vk_importance.h), and the handle evaluates in pairs mode.
 static vk_is* is_create(const char* who, vk_ctx* const* ctxs, int n_ctx, bool joint, vk_joint_cov* cov, const vk_eval_opts* opts,
                         int32_t n_axes, const int32_t* columns, const int32_t* param_block, int64_t n_points, const double* x,
                         const double* y, const double* eps_pow, const double* lno, const double* lno_prior, const int32_t* n_bins,
                         int32_t n_pairs, const int32_t* pair_bins, const int32_t* lists, const int32_t* offsets, const double* base_rows,
-                        double alpha, int32_t every_realisation, int32_t chunk, char* err, size_t errlen) {
+                        double alpha, int32_t every_realisation, int32_t chunk, char* err, size_t errlen, int32_t n_problems = 1,
+                        const int32_t* which = nullptr) {
   auto bail = [&](const std::string& msg) -> vk_is* {
     if (err && errlen) snprintf(err, errlen, "%s: %s", who, msg.c_str());
     return nullptr;
@@ -2245,6 +2310,22 @@ static vk_is* is_create(const char* who, vk_ctx* const* ctxs, int n_ctx, bool jo
   if (n_points < 1 || n_points > vkis::kMaxPoints) return bail("need 1 <= points <= 2^24");
   if (chunk < 1 || chunk > vkis::kMaxChunk) return bail("need 1 <= chunk <= 65536");
   if (n_pairs < 0 || n_pairs > vkis::kMaxPairs) return bail("need 0 <= pairs <= 45");
+  const bool each = which != nullptr;
+  const long long RR = each ? n_problems : 1;                  // samples: one, or one per problem
+  if (each) {
+    if (n_problems < 1 || n_problems > vkis::kMaxChunk) return bail("need 1 <= problems <= 65536");
+    if (n_points * RR > vkis::kMaxPoints) return bail("need points x problems <= 2^24");
+    if ((long long)chunk * RR > vkis::kMaxChunk) return bail("need chunk x problems <= 65536 (the rows of one launch)");
+    if (ctx->n_real <= 0 || !ctx->d_real) return bail("no realisations are set on the context (vk_set_realisations)");
+    for (long long r = 0; r < RR; ++r)
+      if (which[r] < 0 || which[r] >= ctx->n_real)
+        return bail("realisation index " + std::to_string(which[r]) + " of problem " + std::to_string(r) + " is outside 0.." +
+                    std::to_string(ctx->n_real - 1));
+    if (ctx->n_sets > 0 && ctx->n_sets != ctx->n_real)
+      return bail(std::to_string(ctx->n_sets) + " model realisations (vk_set_model_realisations) against " + std::to_string(ctx->n_real) +
+                  " realisations of the data (vk_set_realisations): the counts must agree");
+    if (check_real_lds(ctx) != VK_OK) return bail(ctx->err);
+  }
   const long long G = n_points, n_chunks = (G + chunk - 1) / chunk;
   const int n_lists = n_axes + n_pairs;
   int cell_off[vkis::kMaxLists + 1] = {};
@@ -2269,30 +2350,39 @@ static vk_is* is_create(const char* who, vk_ctx* const* ctxs, int n_ctx, bool jo
   cell_off[n_lists] = (int)cells;
   if (eps && !eps_pow) return bail("a sampled epsilon needs eps_pow, the host's eps^(-2/3) of every point");
   const long long per_chunk = cells + n_lists;
-  if (n_chunks * per_chunk > vkis::kMaxOffsets) return bail("too many cell offsets (chunks x cells): at most 2^27, take a larger chunk or fewer cells");
-  for (long long g = 0; g < G; ++g) {
+  if (n_chunks * per_chunk * RR > vkis::kMaxOffsets) return bail("too many cell offsets (chunks x cells): at most 2^27, take a larger chunk or fewer cells");
+  // (with a sample per problem flat index g R + r: point g of problem r)
+  const std::string of_problem = each ? " (point x problems + problem)" : "";
+  for (long long g = 0; g < G * RR; ++g) {
     for (int j = 0; j < n_axes; ++j)
       if (!__builtin_isfinite(x[g * n_axes + j]) || !__builtin_isfinite(y[g * n_axes + j]))
-        return bail("point " + std::to_string(g) + " is not finite in axis " + std::to_string(j));
-    if (__builtin_isnan(lno[g]) || (lno_prior && __builtin_isnan(lno_prior[g]))) return bail("lno of point " + std::to_string(g) + " is NaN");
+        return bail("point " + std::to_string(g) + of_problem + " is not finite in axis " + std::to_string(j));
+    if (__builtin_isnan(lno[g]) || (lno_prior && __builtin_isnan(lno_prior[g])))
+      return bail("lno of point " + std::to_string(g) + of_problem + " is NaN");
   }
   // every index a kernel forms: a list entry inside its chunk, a cell's end inside the chunk's count, offsets that never decrease
   for (long long c = 0; c < n_chunks; ++c) {
     const long long g0 = c * chunk;
     const int n = (int)std::min<long long>(chunk, G - g0);
-    for (int l = 0; l < n_lists; ++l) {
-      long long where = 0;
-      const int bad = vkis::check_list(lists + (size_t)l * G + g0, offsets + c * per_chunk + cell_off[l] + l, cell_off[l + 1] - cell_off[l], n, &where);
-      if (bad == 1)
-        return bail("offset " + std::to_string(where) + " of list " + std::to_string(l) + " in chunk " + std::to_string(c) +
-                    " is wrong: the offsets start at 0, never decrease and end inside the chunk's " + std::to_string(n) + " points");
-      if (bad == 2)
-        return bail("entry " + std::to_string(where) + " of list " + std::to_string(l) + " in chunk " + std::to_string(c) +
-                    " is outside its chunk of " + std::to_string(n) + " points, or not after the entry before it in its cell");
-    }
+    for (int r = 0; r < (int)RR; ++r)
+      for (int l = 0; l < n_lists; ++l) {
+        long long where = 0;
+        const int* seg = each ? lists + vkis::own_list(r, l, n_lists, G) + g0 : lists + (size_t)l * G + g0;
+        const int* off = offsets + (each ? vkis::own_offsets(c, r, (int)RR, per_chunk) : c * per_chunk) + cell_off[l] + l;
+        const int bad = vkis::check_list(seg, off, cell_off[l + 1] - cell_off[l], n, &where);
+        const std::string in = " in chunk " + std::to_string(c) + (each ? " of problem " + std::to_string(r) : "");
+        if (bad == 1)
+          return bail("offset " + std::to_string(where) + " of list " + std::to_string(l) + in +
+                      " is wrong: the offsets start at 0, never decrease and end inside the chunk's " + std::to_string(n) + " points");
+        if (bad == 2)
+          return bail("entry " + std::to_string(where) + " of list " + std::to_string(l) + in +
+                      " is outside its chunk of " + std::to_string(n) + " points, or not after the entry before it in its cell");
+      }
   }
   int R = 1;
-  if (every_realisation && joint) {
+  if (each) {
+    R = n_problems;
+  } else if (every_realisation && joint) {
     // every block: realisations set, the same number of them as the lead's, no model realisations (no cross mode), the LDS the
     // realisation kernels need
     if (check_joint(cov, ctxs, n_ctx, true) != VK_OK) return bail(ctx->err);
@@ -2306,16 +2396,18 @@ static vk_is* is_create(const char* who, vk_ctx* const* ctxs, int n_ctx, bool jo
     R = ctx->n_real;
   }
   const long long n_acc = vkis::whole(n_axes) + cells;
-  if (n_acc * (long long)(R + 1) > (1LL << 31) * (kIsBlock / 2)) return bail("too many accumulators for one launch (accumulators x problems)");
+  if (n_acc * (long long)(each ? 2 * R : R + 1) > (1LL << 31) * (kIsBlock / 2)) return bail("too many accumulators for one launch (accumulators x problems)");
   const double inf = __builtin_inf();
   double lo[vkis::kMaxP], hi[vkis::kMaxP];                     // (a sample has points, not a box)
   for (int j = 0; j < vkis::kMaxP; ++j) lo[j] = -inf, hi[j] = inf;
   vk_is* f = sampled_create<vk_is>(who, "sample", ctxs, n_ctx, joint, cov, opts, 1, n_axes, columns, param_block, lo, hi, base_rows,
                                    alpha, nullptr, err, errlen, [&](vk_is* h) {
     h->R = R;
-    h->real = every_realisation != 0;
-    h->cross = h->real ? R : 0;
+    h->each = each;
+    h->real = each || every_realisation != 0;
+    h->cross = h->real && !each ? R : 0;
     h->max_which = h->real ? R - 1 : -1;
+    if (each) h->max_which = *std::max_element(which, which + R);
     h->chunk = chunk;
     h->G = G;
     h->n_chunks = n_chunks;
@@ -2330,11 +2422,12 @@ static vk_is* is_create(const char* who, vk_ctx* const* ctxs, int n_ctx, bool jo
   });
   if (!f) return nullptr;
   auto up = [&](void* dst, const void* src, size_t bytes) { return hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess; };
-  const size_t g = (size_t)G;
+  const size_t g = (size_t)(G * RR);
   bool ok = up(f->d_x, x, g * n_axes * sizeof(double)) && up(f->d_y, y, g * n_axes * sizeof(double)) && up(f->d_lno, lno, g * sizeof(double));
   if (ok && eps) ok = up(f->d_eps, eps_pow, g * sizeof(double));
   if (ok && lno_prior) ok = up(f->d_lnop, lno_prior, g * sizeof(double));
-  if (ok) ok = up(f->d_list, lists, (size_t)n_lists * g * sizeof(int)) && up(f->d_off, offsets, (size_t)(n_chunks * per_chunk) * sizeof(int));
+  if (ok) ok = up(f->d_list, lists, (size_t)n_lists * g * sizeof(int)) && up(f->d_off, offsets, (size_t)(n_chunks * per_chunk * RR) * sizeof(int));
+  if (ok && each) ok = up(f->d_which, which, (size_t)R * sizeof(int));
   if (!ok) {
     (void)hipGetLastError();
     sampled_destroy(f);
@@ -2351,6 +2444,19 @@ vk_is* vk_is_create(vk_ctx* ctx, const vk_eval_opts* opts, int32_t n_axes, const
                     double alpha, int32_t every_realisation, int32_t chunk, char* err, size_t errlen) {
   return is_create("vk_is_create", &ctx, 1, false, nullptr, opts, n_axes, columns, nullptr, n_points, x, y, eps_pow, lno, lno_prior, n_bins,
                    n_pairs, pair_bins, lists, offsets, base_row, alpha, every_realisation, chunk, err, errlen);
+}
+
+vk_is* vk_is_create_own(vk_ctx* ctx, const vk_eval_opts* opts, int32_t n_axes, const int32_t* columns, int64_t n_points,
+                        int32_t n_problems, const int32_t* which, const double* x, const double* y, const double* eps_pow,
+                        const double* lno, const double* lno_prior, const int32_t* n_bins, int32_t n_pairs, const int32_t* pair_bins,
+                        const int32_t* lists, const int32_t* offsets, const double* base_row, double alpha, int32_t chunk, char* err,
+                        size_t errlen) {
+  if (!which || !ctx) {
+    if (err && errlen) snprintf(err, errlen, "vk_is_create_own: NULL argument");
+    return nullptr;
+  }
+  return is_create("vk_is_create_own", &ctx, 1, false, nullptr, opts, n_axes, columns, nullptr, n_points, x, y, eps_pow, lno, lno_prior,
+                   n_bins, n_pairs, pair_bins, lists, offsets, base_row, alpha, 1, chunk, err, errlen, n_problems, which);
 }
 
 vk_is* vk_is_create_joint(vk_ctx* const* ctxs, int32_t n_ctx, vk_joint_cov* cov, const vk_eval_opts* opts, int32_t n_axes,
@@ -2387,6 +2493,7 @@ void vk_is_destroy(vk_is* f) {
 int vk_is_set_predictive(vk_is* f, int32_t on) {
   if (!f) return VK_E_ARG;
   const std::string me = "vk_is_set_predictive: ";
+  if (f->each) return refused(f, me + "a handle with a proposal per problem (vk_is_create_own) keeps no predictive sums");
   if (f->done != 0 && f->done != f->G) return refused(f, me + "a run is under way (call it before the first vk_is_run)");
   f->pred_mem.drop(f);
   f->pred_N = 0;
@@ -2499,6 +2606,14 @@ int vk_is_rows(vk_is* f, int64_t first, int32_t count, double* rows) {
   IsArgs a = is_args(f);
   a.g0 = first;
   a.n = count;
+  if (f->each) {                           // count x R rows, row i R + r: point first + i of problem r
+    rc = sampled_launch(f, vk_is_own_rows_kernel, (long long)a.n * a.R, kIsBlock, is_own_args(f, a));
+    if (rc == VK_OK) rc = sampled_home(f, {{rows, f->d_rows, (size_t)count * f->R * VK_NPAR * sizeof(double)}}, true);
+    if (rc != VK_OK) return sampled_abort(f, rc);
+    VK_SAMPLED_HIP(f, hipStreamSynchronize(f->ctx->stream));
+    f->err.clear();
+    return VK_OK;
+  }
   rc = sampled_launch(f, vk_is_rows_kernel, a.n, kIsBlock, a);
   // rows [sets][count][VK_NPAR]: one set, or (vk_is_create_joint_blocks) block q's rows from its set at d_rows + q par_stride
   const size_t set_doubles = (size_t)count * VK_NPAR;
@@ -2537,8 +2652,11 @@ int vk_is_result(vk_is* f, double* ln_max, int64_t* arg_max, int64_t* n_finite, 
     if (h2)
       for (int c = 0; c < f->n2; ++c) h2[r * f->n2 + c] = at(W + f->n1 + c, r);
   }
-  if (prior_ln_max) *prior_ln_max = f->own ? run[R].m : 0.0;
-  if (prior_total) *prior_total = f->own ? at(vkis::kTotal, R) : 0.0;
+  // (a proposal per problem: R values each, problem r's prior problem is problem R + r)
+  for (size_t r = 0; r < (f->each ? R : 1); ++r) {
+    if (prior_ln_max) prior_ln_max[r] = f->own ? run[R + r].m : 0.0;
+    if (prior_total) prior_total[r] = f->own ? at(vkis::kTotal, R + r) : 0.0;
+  }
   f->err.clear();
   return VK_OK;
 }

@@ -82,6 +82,25 @@ each mock.
    the corrected sums by rule 5's formulas (under a prior with the same prior normalisation), ``max_weight_share`` is the
    largest smoothed weight over the corrected total.  Histograms are not corrected.  ``k_threshold = min(1 - 1 / log10(n_drawn),
    0.7)``; ``HIGH_K``: ``k > k_threshold``.
+8. *A proposal per problem* (``proposal`` a :class:`ProposalSet`; ``Realisations.importance_posterior`` alone, ``paired_model=True``
+   included; on the device ``vk_is_create_own``, ``victor_amd/csrc/vk_kernel_is_own.h``): where one proposal cannot cover every
+   problem's posterior - a mock flagged ``LOW_ESS`` or ``HIGH_K`` - problem r draws n points of its OWN from a proposal of its own,
+   its best fit and Laplace covariance say (:meth:`ProposalSet.from_fits`), and is evaluated against realisation r alone: n R
+   theory evaluations in pairs mode instead of G.
+   *Common random numbers*: ``z`` (with ``dof`` scaled as in rule 1) is drawn ONCE for all problems, ``x[r] = mean_r + z @
+   L_r.T``, and ``ln q[r][g]`` is rule 1's closed form with problem r's mean and Cholesky factor.
+   *No point is dropped*: index g runs over all n drawn points of every problem and ``n_drawn = n``.  A point of problem r
+   outside the box has ``lno[r][g] = -inf`` (rule 3 counts it as not finite), belongs to no histogram list, and is evaluated at
+   the problem's centre ``mean_r`` in its place - the host substitutes it before anything travels, so no out-of-box row is ever
+   evaluated; ``n_inside[r]`` counts the others.
+   *Problem r's sums* are what rules 3 - 5 and 7 give for a one-problem run over its n points: ``y[r] = x[r] - mean_r``, its own
+   lists (:class:`OwnLists`), ``lnpost = lnL + lno[r][g]`` and, under a prior, its own prior problem ``lnop[r][g] = lno[r][g]``
+   (``prior_ln_max``, ``prior_total`` and ``prior_error`` are (R,) arrays).
+   *Chunks*: a chunk holds ``chunk`` consecutive g of every problem; row ``i R + r`` of its evaluation is point ``g0 + i`` of
+   problem r against realisation r, in one pairs call - ``Realisations.log_likelihood_pairs``, or the ``evaluate`` callable given
+   the batch and, as a second argument, ``which``.  The default chunk is ``max(1, min(n, 65536 // R))``; ``chunk R <= 65536`` and
+   ``n R <= 2^24``.  *The read-out* is rule 5's with the per-problem centre and prior normalisation, ``tail`` rule 7's with ``y``
+   taken from the problem's own sample.  ``predictive=True``, joint fits and a caller's own ``sample`` are refused here.
 """
 
 import ctypes as C
@@ -169,13 +188,18 @@ class GaussianProposal:
         return self.mean[at], np.linalg.cholesky(cov)
 
     @staticmethod
-    def draw(mean, chol, dof, n, seed):
-        """(n, d) points: rule 1 of the module docstring."""
-        z = np.random.default_rng([seed, 0]).standard_normal((n, len(mean)))
+    def standard(d, dof, n, seed):
+        """(n, d) standard normal rows, with ``dof`` scaled to Student-t rows: the random numbers of rule 1."""
+        z = np.random.default_rng([seed, 0]).standard_normal((n, d))
         if dof is not None:
             chi2 = np.random.default_rng([seed, 1]).chisquare(dof, n)
             z = z * np.sqrt(dof / chi2)[:, None]
-        return mean + z @ chol.T
+        return z
+
+    @staticmethod
+    def draw(mean, chol, dof, n, seed):
+        """(n, d) points: rule 1 of the module docstring."""
+        return mean + GaussianProposal.standard(len(mean), dof, n, seed) @ chol.T
 
     @staticmethod
     def ln_density(x, mean, chol, dof):
@@ -188,6 +212,99 @@ class GaussianProposal:
             return -0.5 * q - ln_det - 0.5 * d * math.log(2.0 * math.pi)
         return (math.lgamma(0.5 * (dof + d)) - math.lgamma(0.5 * dof) - 0.5 * d * math.log(dof * math.pi) - ln_det
                 - 0.5 * (dof + d) * np.log1p(q / dof))
+
+
+class ProposalSet:
+    """A proposal PER PROBLEM (rule 8 of the module docstring): over ``names`` problem r draws from the multivariate normal - with
+    ``dof=k`` the multivariate Student-t - of mean ``mean[r]`` (``mean``: (R, d)) and covariance ``cov[r]`` (``cov``: (R, d, d)).
+    ``len(qs)`` is R; ``qs.take(index)`` the sub-set of the listed problems; ``pooled`` (R,) bool: the problems whose proposal
+    :meth:`from_fits` took from the pooled fit instead of their own."""
+
+    def __init__(self, names, mean, cov, dof=None):
+        if isinstance(names, str):
+            names = [names]
+        self.names = [str(n) for n in names]
+        d = len(self.names)
+        if d < 1 or len(set(self.names)) != d:
+            raise InputError("ProposalSet: names must be different parameters, at least one")
+        self.mean = np.array(mean, dtype=np.float64)
+        self.cov = np.array(cov, dtype=np.float64)
+        if self.mean.ndim != 2 or self.mean.shape[1] != d or not len(self.mean):
+            raise InputError(f"ProposalSet: mean must be (R, {d}), one row per problem and one value per name")
+        R = len(self.mean)
+        if self.cov.shape != (R, d, d):
+            raise InputError(f"ProposalSet: cov must be ({R}, {d}, {d}), one matrix per problem")
+        self.chol = np.empty_like(self.cov)
+        for r in range(R):
+            if not np.all(np.isfinite(self.mean[r])):
+                raise InputError(f"ProposalSet: the mean of problem {r} is not finite")
+            if not np.all(np.isfinite(self.cov[r])):
+                raise InputError(f"ProposalSet: the covariance of problem {r} is not finite")
+            if not np.allclose(self.cov[r], self.cov[r].T, rtol=1e-12, atol=0.0):
+                raise InputError(f"ProposalSet: the covariance of problem {r} is not symmetric")
+            self.cov[r] = 0.5 * (self.cov[r] + self.cov[r].T)
+            try:
+                self.chol[r] = np.linalg.cholesky(self.cov[r])
+            except np.linalg.LinAlgError:
+                raise InputError(f"ProposalSet: the covariance of problem {r} is not positive definite") from None
+        if dof is not None and (isinstance(dof, bool) or not np.isfinite(dof) or not dof > 0):
+            raise InputError(f"ProposalSet: dof must be None or a number > 0, not {dof!r}")
+        self.dof = None if dof is None else float(dof)
+        self.pooled = np.zeros(R, dtype=bool)
+
+    def __len__(self):
+        return len(self.mean)
+
+    def __repr__(self):
+        return f"ProposalSet({self.names}, {len(self)} problems, dof={self.dof})"
+
+    def take(self, index):
+        """The proposals of the problems ``index`` (integers, or an (R,) bool mask), in that order: what goes with
+        ``fit.realisations(numbers)`` when only some mocks are proposed again."""
+        index = np.atleast_1d(np.asarray(index))
+        if index.dtype == bool:
+            if index.shape != (len(self),):
+                raise InputError(f"ProposalSet.take: a mask must have one entry per problem ({len(self)})")
+            index = np.flatnonzero(index)
+        if index.ndim != 1 or not len(index) or not np.issubdtype(index.dtype, np.integer):
+            raise InputError("ProposalSet.take: index must be a non-empty list of problem numbers, or a bool mask")
+        if np.any(index < 0) or np.any(index >= len(self)):
+            raise InputError(f"ProposalSet.take: problem numbers must lie in 0 .. {len(self) - 1}")
+        out = ProposalSet(self.names, self.mean[index], self.cov[index], self.dof)
+        out.pooled = self.pooled[index].copy()
+        return out
+
+    @classmethod
+    def from_fits(cls, bf, lap, inflate=2.0, dof=None):
+        """Problem r's own best fit and Laplace covariance: mean ``bf.x[r]``, covariance ``inflate * lap.cov[r]``.  A problem
+        that did not converge, or whose Laplace covariance is not finite and positive definite, takes the pooled proposal
+        ``GaussianProposal.from_fits(bf, lap, inflate, dof)`` instead and is marked in ``pooled``.  Refused, as the pooled
+        proposal is, when no problem converged."""
+        pool = GaussianProposal.from_fits(bf, lap, inflate, dof)
+        if lap is None:
+            raise InputError("ProposalSet.from_fits: lap, the Laplace of the best fit, gives the covariances")
+        x = np.asarray(bf.x, dtype=np.float64)
+        cov = float(inflate) * np.asarray(lap.cov, dtype=np.float64)
+        bad = np.asarray(bf.status) != bf.CONVERGED
+        bad |= ~np.all(np.isfinite(cov), axis=(1, 2)) | ~np.all(np.isfinite(x), axis=1)
+        for r in np.flatnonzero(~bad):
+            try:
+                np.linalg.cholesky(0.5 * (cov[r] + cov[r].T))
+            except np.linalg.LinAlgError:
+                bad[r] = True
+        mean, cov = x.copy(), 0.5 * (cov + np.swapaxes(cov, 1, 2))
+        mean[bad], cov[bad] = pool.mean, pool.cov
+        out = cls(bf.names, mean, cov, dof)
+        out.pooled = bad
+        return out
+
+    def ordered(self, who, names):
+        """``(mean (R, d), chol (R, d, d))`` in the order of the sampled ``names``: the set names exactly them."""
+        if set(self.names) != set(names):
+            raise InputError(f"{who}: the proposals name {self.names}, the sampled parameters are {list(names)}")
+        at = [self.names.index(n) for n in names]
+        cov = self.cov[:, at][:, :, at]
+        return np.ascontiguousarray(self.mean[:, at]), np.linalg.cholesky(cov)
 
 
 class Layout:
@@ -295,6 +412,64 @@ class Sample:
             self.lnop = None
         self.lno = np.ascontiguousarray(self.lno)
 
+    own = False
+
+    @property
+    def n_inside(self):
+        return self.G
+
+    def points(self, at):
+        """(R, d) the points ``at`` (R,), one per problem."""
+        return self.x[at]
+
+    def held_y(self, index):
+        """(R, K, d) the centred coordinates of the held points ``index`` (R, K)."""
+        return self.y[index]
+
+    def prior_error(self):
+        """Rule 5's standard error of the prior's own normalisation."""
+        b = np.exp(self.lnop - self.lnop.max())
+        return float(np.sqrt(max(np.sum(b * b) / np.sum(b) ** 2 - 1.0 / self.n_drawn, 0.0)))
+
+
+class OwnSample:
+    """Rule 8's sample, n points per problem: ``x`` (n, R, d), a point outside the box replaced by its problem's centre;
+    ``centre`` (R, d) and ``y = x - centre``; ``inside`` (n, R) and ``n_inside`` (R,); ``lno`` (n, R), -inf outside the box;
+    ``lnop`` the same array under a prior, else None; ``n_drawn = G = n``."""
+
+    own = True
+
+    def __init__(self, x, centre, lnq, lo, hi, prior):
+        x = np.asarray(x, dtype=np.float64)
+        self.centre = np.ascontiguousarray(centre, dtype=np.float64)
+        self.inside = np.all((x >= lo) & (x <= hi), axis=2)
+        self.n_inside = np.count_nonzero(self.inside, axis=0).astype(np.int64)
+        self.x = np.ascontiguousarray(np.where(self.inside[:, :, None], x, self.centre[None, :, :]))
+        self.y = np.ascontiguousarray(self.x - self.centre[None, :, :])
+        self.n_drawn = self.G = len(x)
+        self.R = x.shape[1]
+        lnq = np.asarray(lnq, dtype=np.float64)
+        if prior is not None:
+            lno = prior.lnprior(self.x) - lnq
+        else:
+            lno = -np.sum(np.log(np.asarray(hi, dtype=np.float64) - np.asarray(lo, dtype=np.float64))) - lnq
+        lno[~self.inside] = -np.inf
+        self.lno = np.ascontiguousarray(lno)
+        self.lnop = self.lno if prior is not None else None
+
+    def points(self, at):
+        return self.x[at, np.arange(self.R)]
+
+    def held_y(self, index):
+        return self.y[index, np.arange(self.R)[:, None]]
+
+    def prior_error(self):
+        top = self.lnop.max(axis=0)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            b = np.exp(self.lnop - np.where(np.isfinite(top), top, 0.0))
+            out = np.sqrt(np.maximum(np.sum(b * b, axis=0) / np.sum(b, axis=0) ** 2 - 1.0 / self.n_drawn, 0.0))
+        return np.where(np.isfinite(top), out, np.inf)
+
 
 class Lists:
     """Rule 2's lists: ``entries`` (n_lists, G) int32 - list l's segment of chunk c starts at ``c chunk`` and names the chunk's
@@ -328,6 +503,52 @@ class Lists:
         K = int(layout.cell_off[l + 1] - layout.cell_off[l])
         g0 = c * self.chunk
         return self.entries[l, g0:g0 + self.chunk], self.offsets[c, at:at + K + 1]
+
+
+class OwnLists:
+    """Rule 2's lists of every problem of an :class:`OwnSample`: ``entries`` (R, n_lists, G) int32 and ``offsets`` (n_chunks, R,
+    cells + n_lists) int32, problem r's as :class:`Lists` holds one sample's; a point outside the box is in no list.  Built over
+    all problems at once: per chunk and list one stable argsort along the point axis.  ``of(r)``: problem r's, as
+    :func:`step_definition` asks for them."""
+
+    def __init__(self, layout, sample, chunk):
+        G, R = sample.G, sample.R
+        self.chunk, self.n_chunks = int(chunk), -(-G // int(chunk))
+        per = int(layout.cell_off[-1]) + layout.n_lists
+        if self.n_chunks * R * per > MAX_OFFSETS:
+            raise InputError(f"importance_posterior: {self.n_chunks} chunks x {R} problems x {per} cell offsets are more than 2^27: "
+                             "take a larger chunk or fewer bins and pairs")
+        self.entries = np.zeros((R, layout.n_lists, G), dtype=np.int32)
+        self.offsets = np.zeros((self.n_chunks, R, per), dtype=np.int32)
+        where = layout.cells_of(sample.x.reshape(G * R, layout.d)).reshape(layout.n_lists, G, R)
+        where[:, ~sample.inside] = -1
+        problem = np.arange(R)[None, :]
+        for c in range(self.n_chunks):
+            g0 = c * self.chunk
+            for l in range(layout.n_lists):
+                K = int(layout.cell_off[l + 1] - layout.cell_off[l])
+                s = where[l, g0:g0 + self.chunk]                             # (n, R)
+                key = np.where(s >= 0, s, K)                                 # (in no cell: behind every cell)
+                order = np.argsort(key, axis=0, kind="stable")               # by cell, increasing g inside a cell
+                listed = np.take_along_axis(key, order, axis=0) < K
+                self.entries[:, l, g0:g0 + len(s)] = np.where(listed, order, 0).T
+                counts = np.bincount((key + problem * (K + 1)).ravel(), minlength=R * (K + 1)).reshape(R, K + 1)[:, :K]
+                at = int(layout.cell_off[l]) + l
+                self.offsets[c, :, at + 1:at + K + 1] = np.cumsum(counts, axis=1)
+
+    def of(self, r):
+        return _ProblemLists(self, r)
+
+
+class _ProblemLists:
+    def __init__(self, lists, r):
+        self.lists, self.r, self.chunk, self.n_chunks = lists, r, lists.chunk, lists.n_chunks
+
+    def members(self, layout, c, l):
+        at = int(layout.cell_off[l]) + l
+        K = int(layout.cell_off[l + 1] - layout.cell_off[l])
+        g0 = c * self.chunk
+        return self.lists.entries[self.r, l, g0:g0 + self.chunk], self.lists.offsets[c, self.r, at:at + K + 1]
 
 
 class Sums:
@@ -496,6 +717,46 @@ def run_definition(layout, sample, lists, R, values, theory=None, tail=None):
             step_definition(layout, lists, c, y, pacc, g0, sample.lnop[g0:g0 + chunk, None], total_only=True)
         step_definition(layout, lists, c, y, acc, g0, lnl + lno[:, None], predictive=pred, tail=getattr(acc, "tail", None))
     return acc, pacc
+
+
+def stack_sums(layout, parts):
+    """The :class:`Sums` of R problems from their one-problem Sums, in order (with their :class:`Held`, if they carry one)."""
+    acc = Sums(layout, len(parts))
+    for name in ("ln_max", "arg_max", "n_finite", "total", "sq", "s1", "s2", "h1", "h2"):
+        setattr(acc, name, np.concatenate([getattr(p, name) for p in parts], axis=0))
+    if hasattr(parts[0], "tail"):
+        acc.tail = held = Held(len(parts), parts[0].tail.K)
+        for name in ("lnpost", "index", "count"):
+            setattr(held, name, np.concatenate([getattr(p.tail, name) for p in parts], axis=0))
+    return acc
+
+
+def run_definition_own(layout, sample, lists, values, tail=None):
+    """Rule 8's definition over an :class:`OwnSample` and its :class:`OwnLists`: ``values(x, which)`` gives lnL ``(m,)`` of the
+    rows ``x`` (m, d) against the realisations ``which`` (m,) - a chunk's rows, row ``i R + r`` point ``g0 + i`` of problem r.
+    Every problem then takes rule 3's step on its own column, points, lists and (under a prior) prior problem.  Returns ``(Sums,
+    the prior problems' Sums or None)``, R problems each; with ``tail=K`` the Sums carry the :class:`Held`."""
+    R, d, chunk = sample.R, layout.d, lists.chunk
+    accs = [Sums(layout, 1) for _ in range(R)]
+    paccs = [Sums(layout, 1) for _ in range(R)] if sample.lnop is not None else None
+    if tail is not None:
+        for a in accs:
+            a.tail = Held(1, tail)
+    for c in range(lists.n_chunks):
+        g0 = c * chunk
+        x = sample.x[g0:g0 + chunk]
+        n = len(x)
+        which = np.tile(np.arange(R, dtype=np.int32), n)
+        lnl = np.asarray(values(x.reshape(n * R, d), which), dtype=np.float64).reshape(n, R)
+        with np.errstate(invalid="ignore"):
+            lnpost = lnl + sample.lno[g0:g0 + chunk]
+        for r in range(R):
+            mine = lists.of(r)
+            y = sample.y[g0:g0 + chunk, r]
+            if paccs is not None:
+                step_definition(layout, mine, c, y, paccs[r], g0, sample.lnop[g0:g0 + chunk, r, None], total_only=True)
+            step_definition(layout, mine, c, y, accs[r], g0, lnpost[:, r, None], tail=getattr(accs[r], "tail", None))
+    return stack_sums(layout, accs), None if paccs is None else stack_sums(layout, paccs)
 
 
 class SamplePredictive:
@@ -690,7 +951,7 @@ class SampleTail:
         # the corrections, all problems at once: the entries that were not smoothed add exact zeros
         new, old = self.smoothed_weight.astype(ld), self.weight.astype(ld)
         dw = new - old                                           # (R, K)
-        y = sample.y[np.maximum(self.index, 0)].astype(ld)       # (R, K, d); the padding reads point 0 with dw = 0
+        y = sample.held_y(np.maximum(self.index, 0)).astype(ld)  # (R, K, d); the padding reads point 0 with dw = 0
         total = np.array(acc.total, dtype=ld) + dw.sum(axis=1)
         sq = np.array(acc.sq, dtype=ld) + (new * new - old * old).sum(axis=1)
         s1, s2 = np.array(acc.s1, dtype=ld), np.array(acc.s2, dtype=ld)
@@ -706,13 +967,19 @@ class SampleTail:
         q = np.where(ok, self.sums["sq"], 1.0)
         with np.errstate(divide="ignore"):
             ln_sum = np.where(ok, acc.ln_max, 0.0) + np.log(t)
-        norm = np.log(float(ip.n_drawn)) if pacc is None else float(pacc.ln_max[0]) + np.log(float(pacc.total[0]))
+        if pacc is None:
+            norm = np.log(float(ip.n_drawn))
+        elif sample.own:                                         # (rule 8: every problem's own prior normalisation)
+            with np.errstate(divide="ignore"):
+                norm = pacc.ln_max + np.log(pacc.total)
+        else:
+            norm = float(pacc.ln_max[0]) + np.log(float(pacc.total[0]))
         self.ln_evidence = np.where(ok, ln_sum - norm, -np.inf)
         self.ess = np.where(ok, t * t / q, 0.0)
         self.max_weight_share = np.where(ok, top / t, 0.0)
         self.ln_evidence_error = np.where(ok, np.sqrt(np.maximum(q / (t * t) - 1.0 / ip.n_drawn, 0.0)), np.inf)
         m = self.sums["s1"] / t[:, None]
-        self.mean = np.where(ok[:, None], sample.centre[None, :] + m, np.nan)
+        self.mean = np.where(ok[:, None], np.atleast_2d(sample.centre) + m, np.nan)
         self.cov = np.empty((R, d, d))
         for j in range(d):
             for j2 in range(j, d):
@@ -738,7 +1005,9 @@ class ImportancePosterior:
     ``ln_evidence`` -inf, ``ess`` 0, the sums zeros, the moments and ``best`` NaN).  ``raw``: the :class:`Sums`.  ``predictive``: a
     :class:`SamplePredictive` with ``predictive=True`` - the band of the theory vector and the DIC per problem -, else None.
     ``tail``: a :class:`SampleTail` with ``tail=True`` or ``tail={"size": M}`` - the Pareto shape of every problem's largest
-    weights and the smoothed estimates -, else None."""
+    weights and the smoothed estimates -, else None.  With a proposal per problem (rule 8): ``proposals`` the
+    :class:`ProposalSet` (else None), ``n_inside`` an (R,) array, and under a prior ``prior_ln_max``, ``prior_total`` and
+    ``prior_error`` (R,) arrays."""
 
     OK, LOW_ESS, NO_FINITE = 0, 1, 2
 
@@ -747,7 +1016,8 @@ class ImportancePosterior:
         self.names = list(layout.names)
         self.edges = dict(zip(self.names, layout.edges))
         self.n_problems = R = len(acc.ln_max)
-        self.n_drawn, self.n_inside = sample.n_drawn, sample.G
+        self.n_drawn, self.n_inside = sample.n_drawn, sample.n_inside
+        self.proposals = None                                    # the ProposalSet of a run with a proposal per problem (rule 8)
         self.chunk, self.n_chunks = lists.chunk, lists.n_chunks
         self.ln_max, self.arg_max, self.n_finite = acc.ln_max, acc.arg_max, acc.n_finite
         self.min_ess = float(min_ess)
@@ -759,17 +1029,20 @@ class ImportancePosterior:
         if pacc is None:
             self.ln_evidence = ln_sum - np.log(float(self.n_drawn))
         else:
-            self.prior_ln_max, self.prior_total = float(pacc.ln_max[0]), float(pacc.total[0])
-            self.ln_evidence = ln_sum - (self.prior_ln_max + np.log(self.prior_total))
-            b = np.exp(sample.lnop - sample.lnop.max())
-            self.prior_error = float(np.sqrt(max(np.sum(b * b) / np.sum(b) ** 2 - 1.0 / self.n_drawn, 0.0)))
+            if sample.own:                                       # (rule 8: (R,) arrays, every problem's own prior problem)
+                self.prior_ln_max, self.prior_total = np.array(pacc.ln_max), np.array(pacc.total)
+            else:
+                self.prior_ln_max, self.prior_total = float(pacc.ln_max[0]), float(pacc.total[0])
+            with np.errstate(divide="ignore"):
+                self.ln_evidence = ln_sum - (self.prior_ln_max + np.log(self.prior_total))
+            self.prior_error = sample.prior_error()
         self.ln_evidence = np.where(ok, self.ln_evidence, -np.inf)
         sq = np.where(ok, acc.sq, 1.0)
         self.ess = np.where(ok, total * total / sq, 0.0)
         self.max_weight_share = np.where(ok, 1.0 / total, 0.0)
         self.ln_evidence_error = np.where(ok, np.sqrt(np.maximum(sq / (total * total) - 1.0 / self.n_drawn, 0.0)), np.inf)
         m = acc.s1 / total[:, None]
-        self.mean = np.where(ok[:, None], sample.centre[None, :] + m, np.nan)
+        self.mean = np.where(ok[:, None], np.atleast_2d(sample.centre) + m, np.nan)
         self.cov = np.empty((R, d, d))
         for j in range(d):
             for k in range(j, d):
@@ -778,7 +1051,8 @@ class ImportancePosterior:
         with np.errstate(invalid="ignore"):
             self.sigma = np.sqrt(np.diagonal(self.cov, axis1=1, axis2=2))
         at = np.where(ok, acc.arg_max, 0)
-        self.best = {n: np.where(ok, sample.x[at, j], np.nan) for j, n in enumerate(self.names)}
+        points = sample.points(at)
+        self.best = {n: np.where(ok, points[:, j], np.nan) for j, n in enumerate(self.names)}
         self.outside_mass = np.stack([np.stack([self._h1(j)[:, 0], self._h1(j)[:, -1]], axis=1) for j in range(d)], axis=1) / total[:, None, None]
         self.status = np.where(ok, np.where(self.ess < self.min_ess, self.LOW_ESS, self.OK), self.NO_FINITE).astype(np.int32)
         self._reader = None
@@ -873,7 +1147,9 @@ def importance_posterior(fit, params, proposal=None, n=16384, seed=0, fixed=None
 
     ``params``: the cobaya block, as ``best_fit`` takes it (``fixed`` values must be scalars); ``proposal``: a
     :class:`GaussianProposal` naming exactly the sampled parameters, drawn ``n`` times with ``seed``; or ``sample`` (G, d) with
-    ``ln_proposal`` (G,): the caller's own points, columns in sampled order, and ln of their normalised density; ``prior``: a
+    ``ln_proposal`` (G,): the caller's own points, columns in sampled order, and ln of their normalised density; or, with
+    ``realisations`` (plain or ``paired_model=True``) or an ``evaluate(batch, which)`` callable, a :class:`ProposalSet` of one
+    proposal per problem, each drawn ``n`` times (rule 8 of the module docstring); ``prior``: a
     :class:`victor_amd.priors.GaussianPrior` or a list of them; ``bins``: an int or a dict name -> int, 1 .. 1024; ``ranges``:
     name -> (a, b) inside the prior box (default the box); ``pairs``: name pairs for the 2-D histograms; ``chunk``: points per
     launch, at most 65536 (default :func:`victor_amd.grid.default_chunk`); ``min_ess``: below it a problem is ``LOW_ESS``;
@@ -895,6 +1171,19 @@ def importance_posterior(fit, params, proposal=None, n=16384, seed=0, fixed=None
         raise InputError(f"{who}: a fit or an evaluate callable is needed")
     from .joint import JointFit, check_block_names, split_name
     joint = fit if isinstance(fit, JointFit) else None
+    own = isinstance(proposal, ProposalSet)                       # rule 8: a proposal per problem
+    if own:
+        if predictive:
+            raise PredictiveError(f"{who}: predictive=True needs one shared sample (a point's theory vector serves every problem); "
+                                  "with a ProposalSet every problem has points of its own")
+        if sample is not None or ln_proposal is not None:
+            raise InputError(f"{who}: sample and ln_proposal come in place of the proposal, not beside a ProposalSet")
+        if joint is not None or n_blocks is not None:
+            raise InputError(f"{who}: a ProposalSet is not supported for joint fits (one proposal for all problems is)")
+        if realisations is None and evaluate is None:
+            raise InputError(f"{who}: a ProposalSet needs realisations (one problem per proposal) or an evaluate callable")
+        if realisations is not None and len(proposal) != len(realisations):
+            raise InputError(f"{who}: the ProposalSet holds {len(proposal)} proposals, there are {len(realisations)} realisations")
     if n_blocks is not None:
         if fit is not None or evaluate is None:
             raise InputError(f"{who}: n_blocks goes with an evaluate callable in place of a fit (a joint fit knows its blocks)")
@@ -926,7 +1215,7 @@ def importance_posterior(fit, params, proposal=None, n=16384, seed=0, fixed=None
         raise InputError(f"{who}: fixed values must be scalars ({arrays} are not)")
     layout = resolve_layout(who, names, q.lo, q.hi, bins, ranges, pairs)
     prior = resolve_prior(prior, who, names, q.lo, q.hi, fixed_all, joint is not None or n_blocks is not None)
-    if realisations is not None and getattr(realisations, "paired_model", False):
+    if realisations is not None and getattr(realisations, "paired_model", False) and not own:
         raise (PredictiveError if predictive else InputError)(
             f"{who}: realisations(paired_model=True) have no cross mode (a point has one theory vector per "
             "realisation): a shared sample evaluates every point once")
@@ -936,6 +1225,10 @@ def importance_posterior(fit, params, proposal=None, n=16384, seed=0, fixed=None
         raise InputError(f"{who}: every block of a joint fit must live on the same device")
     if not np.isfinite(min_ess) or min_ess < 0:
         raise InputError(f"{who}: min_ess must be a number >= 0, not {min_ess!r}")
+
+    if own:
+        return _own_posterior(who, q, fit, realisations, kwargs, layout, prior, proposal, n, seed, chunk, min_ess, device, evaluate, tail,
+                              fixed_all)
 
     # ---- rule 1: the sample
     if sample is not None or ln_proposal is not None:
@@ -1026,6 +1319,112 @@ def importance_posterior(fit, params, proposal=None, n=16384, seed=0, fixed=None
     finally:
         lib.vk_is_destroy(h)
     return finish(acc, pacc)
+
+
+def draw_own(centre, chol, dof, n, seed):
+    """Rule 8.1, common random numbers: ONE ``z`` (n, d) for all problems, ``x[:, r] = centre[r] + z @ chol[r].T`` and its ln q.
+    Returns ``(x (n, R, d), centre, ln q (n, R))``, the first arguments of :class:`OwnSample`."""
+    R, d = centre.shape
+    z = GaussianProposal.standard(d, dof, n, seed)
+    x, lnq = np.empty((n, R, d)), np.empty((n, R))
+    for r in range(R):
+        x[:, r] = centre[r] + z @ chol[r].T
+        lnq[:, r] = GaussianProposal.ln_density(x[:, r], centre[r], chol[r], dof)
+    return x, centre, lnq
+
+
+def _own_posterior(who, q, fit, realisations, kwargs, layout, prior, proposals, n, seed, chunk, min_ess, device, evaluate, tail,
+                   fixed_all):
+    """Rule 8 behind :func:`importance_posterior`, whose checks have run: the sample of every problem from its own proposal,
+    its lists, then the definition (``device=False``) or ``vk_is_create_own``."""
+    names, d, R = layout.names, layout.d, len(proposals)
+    if isinstance(n, bool) or int(n) != n or not 1 <= int(n) <= MAX_POINTS:
+        raise InputError(f"{who}: n must be an integer in 1 .. 2^24, not {n!r}")
+    if isinstance(seed, bool) or int(seed) != seed or int(seed) < 0:
+        raise InputError(f"{who}: seed must be an integer >= 0, not {seed!r}")
+    n = int(n)
+    if n * R > MAX_POINTS:
+        raise InputError(f"{who}: n x problems = {n} x {R} is more than 2^24 points: take fewer points or fewer problems at once")
+    if chunk is None:
+        chunk = max(1, min(n, MAX_CHUNK // R))
+    if isinstance(chunk, bool) or int(chunk) != chunk or not 1 <= int(chunk) <= MAX_CHUNK:
+        raise InputError(f"{who}: chunk must be an integer in 1 .. {MAX_CHUNK}, not {chunk!r}")
+    chunk = int(chunk)
+    if chunk * R > MAX_CHUNK:
+        raise InputError(f"{who}: chunk x problems = {chunk} x {R} is more than {MAX_CHUNK} rows of one launch: take a smaller chunk")
+    centre, chol = proposals.ordered(who, names)
+    outside = np.flatnonzero(np.any((centre < q.lo) | (centre > q.hi), axis=1))
+    if len(outside):
+        raise InputError(f"{who}: the proposal of problem {int(outside[0])} has its mean {centre[outside[0]].tolist()} outside the "
+                         f"prior box of {names}")
+    smp = OwnSample(*draw_own(centre, chol, proposals.dof, n, int(seed)), q.lo, q.hi, prior)
+    tail = resolve_tail(tail, who, n)
+    lists = OwnLists(layout, smp, chunk)
+    fixed_out = {k: float(v) for k, v in fixed_all.items()}
+
+    def batch_of(x):
+        batch = dict(fixed_out)
+        batch.update({name: np.ascontiguousarray(x[:, j]) for j, name in enumerate(names)})
+        return batch
+
+    def finish(acc, pacc):
+        ip = ImportancePosterior(layout, smp, lists, acc, pacc, min_ess)
+        ip.proposals = proposals
+        if tail is not None:
+            ip.tail = SampleTail(ip, acc.tail, pacc)
+        return ip
+
+    K = None if tail is None else tail + 1
+    if not device:
+        if evaluate is not None:
+            def values(x, which):
+                return evaluate(batch_of(x), which)
+        else:
+            def values(x, which):
+                return realisations.log_likelihood_pairs(batch_of(x), which, **kwargs)[0]
+        return finish(*run_definition_own(layout, smp, lists, values, K))
+
+    lib, h = create_own_handle(fit, realisations, kwargs, layout, smp, lists, fixed_out)
+    try:
+        if tail is not None:
+            _check(lib, h, lib.vk_is_set_tail(h, K), "vk_is_set_tail")
+        _check(lib, h, lib.vk_is_run(h, 0, n), "vk_is_run")
+        acc, pacc = read_result(lib, h, layout, R, smp.lnop is not None, None, K, own=True)
+    finally:
+        lib.vk_is_destroy(h)
+    return finish(acc, pacc)
+
+
+def create_own_handle(fit, realisations, kwargs, layout, smp, lists, fixed_out, which=None):
+    """``(lib, handle)`` of ``vk_is_create_own`` for an :class:`OwnSample` and its :class:`OwnLists` on the realisations' engine
+    (``paired_model``: its table sets are uploaded with the data's): the base row from the fixed values, the sample's arrays and
+    per point the host's own ``eps^(-2/3)``, as :func:`create_handle`.  ``which``: the realisation of every problem (default
+    problem r: realisation r)."""
+    names, d, n, R, chunk = layout.names, layout.d, smp.G, smp.R, lists.chunk
+    i32 = C.POINTER(C.c_int32)
+    batch = dict(fixed_out)
+    batch.update({name: np.array([smp.x[0, 0, j]]) for j, name in enumerate(names)})
+    model, _, eng, opts = realisations._plan(kwargs)
+    base = np.ascontiguousarray(fit._fit_rows(batch, model), dtype=np.float64)
+    cols = np.array([N.ROW_COLUMNS.get(name, N.VK_WALK_EPSILON) for name in names], dtype=np.int32)
+    eps_pow = None
+    if "epsilon" in names:
+        with np.errstate(invalid="ignore"):
+            eps_pow = N.f64(N.epsilon_to_ap(N.f64(smp.x[:, :, names.index("epsilon")].ravel()), 1.0)[1])
+    n_bins = np.array(layout.n_bins, dtype=np.int32)
+    pair_bins = np.array(layout.pair_bins, dtype=np.int32)
+    which = np.arange(R, dtype=np.int32) if which is None else np.ascontiguousarray(which, dtype=np.int32)
+    err = C.create_string_buffer(512)
+    lib = eng._lib
+    h = lib.vk_is_create_own(eng._ctx, C.byref(opts), d, cols.ctypes.data_as(i32), n, R, which.ctypes.data_as(i32), N.as_dp(smp.x),
+                             N.as_dp(smp.y), None if eps_pow is None else N.as_dp(eps_pow), N.as_dp(smp.lno),
+                             None if smp.lnop is None else N.as_dp(smp.lnop), n_bins.ctypes.data_as(i32), len(pair_bins),
+                             pair_bins.ctypes.data_as(i32) if len(pair_bins) else None, lists.entries.ctypes.data_as(i32),
+                             lists.offsets.ctypes.data_as(i32), N.as_dp(base), float(fixed_out.get("alpha", 1)), chunk, err, len(err))
+    if not h:
+        msg = err.value.decode()
+        raise (N.NativeError if "device memory" in msg else InputError)(msg)
+    return lib, h
 
 
 def _blocks_of(fit):
@@ -1119,7 +1518,7 @@ def create_handle(q, fit, realisations, kwargs, fit_options, layout, smp, lists,
     return lib, h, refresh
 
 
-def read_result(lib, h, layout, R, with_prior, n_theory=None, tail=None):
+def read_result(lib, h, layout, R, with_prior, n_theory=None, tail=None, own=False):
     """``(Sums, the prior's own Sums or None)`` of a completed run (``vk_is_result``; with ``n_theory`` rule 6's arrays through
     ``vk_is_predictive``, whose ``[N][R]`` sums are turned to (R, N); with ``tail=K`` rule 7's :class:`Held` through
     ``vk_is_tail``, as the Sums' ``tail``)."""
@@ -1134,6 +1533,13 @@ def read_result(lib, h, layout, R, with_prior, n_theory=None, tail=None):
                "vk_is_predictive")
         acc.pt, acc.ptt = np.ascontiguousarray(pt.T), np.ascontiguousarray(ptt.T)
     i64 = C.POINTER(C.c_int64)
+    if own:                                                      # (vk_is_create_own: R values each, a prior problem per problem)
+        pacc = Sums(layout, R)
+        rc = lib.vk_is_result(h, N.as_dp(acc.ln_max), acc.arg_max.ctypes.data_as(i64), acc.n_finite.ctypes.data_as(i64),
+                              N.as_dp(acc.total), N.as_dp(acc.sq), N.as_dp(acc.s1), N.as_dp(acc.s2), N.as_dp(acc.h1), N.as_dp(acc.h2),
+                              N.as_dp(pacc.ln_max), N.as_dp(pacc.total))
+        _check(lib, h, rc, "vk_is_result")
+        return acc, pacc if with_prior else None
     pm, pt = C.c_double(0.0), C.c_double(0.0)
     rc = lib.vk_is_result(h, N.as_dp(acc.ln_max), acc.arg_max.ctypes.data_as(i64), acc.n_finite.ctypes.data_as(i64), N.as_dp(acc.total),
                           N.as_dp(acc.sq), N.as_dp(acc.s1), N.as_dp(acc.s2), N.as_dp(acc.h1), N.as_dp(acc.h2),

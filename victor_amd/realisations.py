@@ -337,7 +337,13 @@ class Realisations:
         :meth:`log_likelihood` that defines them (``device=False``).  Arguments and result as ``CCFFit.importance_posterior``
         (:mod:`victor_amd.importance`), ``predictive=True`` included: every mock's band and DIC from the G shared theory
         vectors, and ``tail=True``: every mock's Pareto shape and smoothed estimates (``ip.tail``).  Refused with
-        ``paired_model=True``: a point then has one theory vector per realisation."""
+        ``paired_model=True``: a point then has one theory vector per realisation.
+
+        ``q`` a :class:`victor_amd.importance.ProposalSet` of ``len(self)`` proposals - every mock's own best fit and Laplace
+        covariance, ``ProposalSet.from_fits(bf, lap)`` - runs every mock over ``n`` points of its OWN instead (rule 8 of
+        :mod:`victor_amd.importance`): ``n`` x R theory evaluations in pairs mode, for the mocks a shared proposal misses
+        (``LOW_ESS``, ``HIGH_K``) and for ``paired_model=True``, which this route serves; ``predictive=True``, ``sample`` and
+        ``ln_proposal`` are refused with it."""
         from .importance import importance_posterior
         predictive = kwargs.pop("predictive", None)             # (a keyword of its own, not a model or fit option)
         tail = kwargs.pop("tail", None)                         # (likewise)
