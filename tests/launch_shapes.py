@@ -14,7 +14,11 @@ whose half-steps move half of every ensemble - and ``steps(row)`` the step count
 tests/test_gpu_stencil_shapes.py; DESIGN.md section 7a, "Launch shapes under test" - whose R M rows go through in chunks of R S
 rows: ``slots``, ``points``, ``chunks``.
 
-``CHUNKS``, at the end, is the same for the chunked pipeline of the grid and importance posteriors (vk_grid_run, vk_is_run;
+``NESTED``, at the end, is the same for nested sampling (vk_nested_start, vk_nested_begin; tests/test_gpu_nested_shapes.py;
+DESIGN.md section 7d, "Launch shapes under test"): a row is ``R`` problems of ``L`` live points and ``K`` walkers, so
+``nested_rows(row)`` rows per launch, ``passes(row)`` start passes and ``select_trips(n, t)`` trips of a select-kernel loop.
+
+``CHUNKS``, before it, is the same for the chunked pipeline of the grid and importance posteriors (vk_grid_run, vk_is_run;
 tests/test_gpu_chunk_shapes.py; DESIGN.md sections 7c and 7e, "Launch shapes under test"): a row is ``R`` problems, a ``chunk``
 and ``G`` points (for a grid: the product of its ``bins``), so ``chunk_lengths(row)`` launches of the rows, evaluation, max,
 tail, weight, accumulate and predict kernels.  The slice and batch geometry of the tail kernels is stated by plain-Python twins
@@ -106,6 +110,34 @@ def thresholds():
     _one(r"range_ahead<kIsAhead>\(0, a\.n,", importance, "the whole-chunk walk of vk_is_accumulate_kernel")
     _one(r"for \(; i \+ kGridAhead <= a\.n; i \+= kGridAhead\)", grid, "the total's walk of vk_grid_accumulate_kernel")
     _one(r"slice_begin\(int n, int s\) \{ return \(int\)\(\(long long\)n \* s / kSlices\); \}", predict, "vkisp::slice_begin")
+    # nested sampling (NESTED): the workgroups of its kernels, the ceiling of the select kernel's LDS arrays, the block of
+    # iterations whose random numbers travel together (key "nested.BLOCK") and what victor_amd/nested.py accepts and defaults to
+    kernel, step, nested = _read("victor_amd", "csrc", "vk_kernel_nested.h"), _read("victor_amd", "csrc", "vk_nested_step.h"), _read("victor_amd", "nested.py")
+    for name in ("kNestedBlock", "kNestedSelect"):
+        t[name] = int(_one(r"constexpr int %s = (\d+);" % name, kernel, name).group(1))
+    t["kMaxLive"] = int(_one(r"constexpr int kMaxLive = (\d+);", step, "vknest::kMaxLive").group(1))
+    t["nested.BLOCK"] = int(_one(r"constexpr int kBlock = (\d+);", step, "vknest::kBlock").group(1))
+    assert t["nested.BLOCK"] == int(_one(r"(?m)^BLOCK = (\d+)$", nested, "BLOCK of nested.py").group(1)), "vknest::kBlock is not victor_amd.nested.BLOCK"
+    t["MAX_LIVE"] = int(_one(r"(?m)^MAX_LIVE = (\d+)$", nested, "MAX_LIVE").group(1))
+    t["MAX_ROWS"] = int(_one(r"(?m)^MAX_ROWS = (\d+)$", nested, "MAX_ROWS").group(1))
+    m = _one(r"(?m)^DEFAULT_LIVE, DEFAULT_BATCH, DEFAULT_STEPS = (\d+), (\d+), (\d+)$", nested, "the defaults of nested.py")
+    t["nested.DEFAULT_LIVE"], t["nested.DEFAULT_BATCH"] = int(m.group(1)), int(m.group(2))
+    # the rules the constants enter: the five strided loops of the select kernel (four over the live points, one over the
+    # walkers), its LDS arrays, the thread of a walker in the four per-walker kernels, the select launch, the refusal
+    assert len(re.findall(r"for \(int i = tid; i < L; i \+= kNestedSelect\)", kernel)) == 4, "the select kernel's loops over the live points"
+    assert len(re.findall(r"for \(int k = tid; k < K; k \+= kNestedSelect\)", kernel)) == 1, "the select kernel's loop over the walkers"
+    _one(r"__shared__ double s_lnl\[vknest::kMaxLive\];", kernel, "s_lnl")
+    _one(r"__shared__ int s_surv\[vknest::kMaxLive\];", kernel, "s_surv")
+    _one(r"__shared__ int s_dead\[vknest::kMaxLive / 2\];", kernel, "s_dead")
+    assert len(re.findall(r"const int c = blockIdx\.x \* kNestedBlock \+ threadIdx\.x;\n  if \(c >= a\.R \* a\.K\) return;", kernel)) == 4, \
+        "the walker of a thread in the load, adopt, step and commit kernels"
+    assert len(re.findall(r"const int r = c / a\.K", kernel)) == 4, "the problem of a walker in the load, adopt, step and commit kernels"
+    _one(re.escape("sampled_launch(f, vk_nested_select_kernel, (long long)f->R * kNestedSelect, kNestedSelect, a)"), sampled, "the select launch")
+    for kern, count in (("load", 1), ("adopt", 1), ("step", 1), ("commit", 1)):
+        assert len(re.findall(re.escape(f"sampled_launch(f, vk_nested_{kern}_kernel, f->RK, kNestedBlock, a)"), sampled)) == count, kern
+    _one(r"n_live < 2 \|\| n_live > vknest::kMaxLive", sampled, "the refusal of more live points than the LDS holds")
+    _one(r"n_live < 2 or n_live > MAX_LIVE", nested, "the refusal of nested.py")
+    _one(r"R \* batch > MAX_ROWS", nested, "the row limit of nested.py")
     return t
 
 
@@ -557,5 +589,111 @@ CHUNKS = {
 }
 
 # What stays untested: chunks above 8192 rows, up to the MAX_CHUNK = 65536 the product accepts (the default chunk of a call with
-# few problems), and nested sampling's select kernel above 160 live points.
+# few problems).
 LARGEST_CHUNK_TESTED = 8192
+
+
+# ------------------------------------------------------------------ nested sampling ---------------------------------------------
+# vk_nested_start and vk_nested_begin launch R K rows at a time - row r K + k walker k of problem r: L / K start passes (load,
+# evaluation, adopt), then per iteration the select kernel (one workgroup of kNestedSelect threads per problem, strided loops
+# over the L live points and the K walkers, LDS arrays of kMaxLive entries), S times (evaluation, step kernel) and the commit
+# kernel; the load, adopt, step and commit kernels have one thread per walker in workgroups of kNestedBlock.  A row of
+# ``NESTED``: the ``route``, R problems, L live points, K walkers (tuples of equal length: one variant per pair), S steps,
+# ``n_iter`` iterations, the ``seed``, and ``reaches`` as in ``TABLE``.
+def nested_rows(row):
+    """The rows of every launch of a run."""
+    return row["R"] * row["K"]
+
+
+def passes(row):
+    """The start passes: launches of load, evaluation and adopt."""
+    return row["L"] // row["K"]
+
+
+def select_trips(n, t):
+    """The trips a loop of the select kernel makes over n entries."""
+    return -(-n // t["kNestedSelect"])
+
+
+def walker_groups(row, t):
+    """The workgroups of the per-walker kernels."""
+    return -(-nested_rows(row) // t["kNestedBlock"])
+
+
+def split_problems(row, t):
+    """The problems whose walkers lie in two workgroups of the per-walker kernels: a workgroup edge inside their K rows."""
+    K, block = row["K"], t["kNestedBlock"]
+    return sum(1 for r in range(row["R"]) if (r * K) // block != (r * K + K - 1) // block)
+
+
+def _lds_full(r, t):
+    """Every LDS array of the select kernel is used to its last entry: s_lnl and s_surv hold L, s_dead holds K."""
+    return r["L"] == t["kMaxLive"] == t["MAX_LIVE"] and 2 * r["K"] == t["kMaxLive"]
+
+
+def _nested_range_is(key):
+    return lambda r, t: cells_range(nested_rows(r), t) == (t[key] if isinstance(key, str) else key)
+
+
+NESTED = {
+    "N1": dict(route="mocks", R=16, L=256, K=32, S=2, n_iter=9, seed=1, reaches=[
+        ("the product's default live points and batch on the 16 golden mocks", lambda r, t: (r["L"], r["K"], r["R"]) == (t["nested.DEFAULT_LIVE"], t["nested.DEFAULT_BATCH"], 16)),
+        ("L == kNestedSelect: one full trip of every loop over the live points", lambda r, t: r["L"] == t["kNestedSelect"] and select_trips(r["L"], t) == 1),
+        ("512 rows: ranges of the upper band", lambda r, t: nested_rows(r) == 512 and _nested_range_is("cpi2")(r, t)),
+        ("nine iterations cross a block of random numbers", lambda r, t: t["nested.BLOCK"] < r["n_iter"] < 2 * t["nested.BLOCK"])]),
+    "N2": dict(route="data", R=1, L=258, K=129, S=2, n_iter=3, seed=2, reaches=[
+        ("a second trip over the live points with two lanes", lambda r, t: r["L"] == t["kNestedSelect"] + 2 and select_trips(r["L"], t) == 2),
+        ("the walkers past two workgroups, one lane in the third", lambda r, t: walker_groups(r, t) == 3 and nested_rows(r) - 2 * t["kNestedBlock"] == 1),
+        ("fused, ranges of the middle band", lambda r, t: fused(nested_rows(r), t) and _nested_range_is("cpi1")(r, t))]),
+    "N3": dict(route="data", R=1, L=(1024, 1026), K=(512, 513), S=2, n_iter=3, seed=3, reaches=[
+        ("both sides of the fuse limit on the data-vector route", lambda r, t: nested_rows(r) - t["kFuseMaxDefault"] in (0, 1)
+         and fused(nested_rows(r), t) == (nested_rows(r) == t["kFuseMaxDefault"]) and fused(512, t) and not fused(513, t)),
+        ("K = 513: a third trip of the walker loop with one lane", lambda r, t: r["K"] != 513 or (r["K"] == 2 * t["kNestedSelect"] + 1 and select_trips(r["K"], t) == 3)),
+        ("K = 512: two full trips of the walker loop, four of the loops over the live points", lambda r, t: r["K"] != 512
+         or (r["K"] == 2 * t["kNestedSelect"] and select_trips(r["L"], t) == 4 and r["L"] % t["kNestedSelect"] == 0)),
+        ("L = 1026: not a multiple of a wave", lambda r, t: r["L"] != 1026 or (r["L"] % 64 == 2 and select_trips(r["L"], t) == 5)),
+        ("ranges of the upper band", _nested_range_is("cpi2"))]),
+    "N4": dict(route="data", R=1, L=4096, K=2048, S=2, n_iter=3, seed=4, reaches=[
+        ("L == kMaxLive, K == kMaxLive / 2: every LDS array full", _lds_full),
+        ("rows exactly at kPartialPoints, unfused on partial sums", lambda r, t: nested_rows(r) == t["kPartialPoints"] and not fused(nested_rows(r), t)
+         and _nested_range_is("cpi2")(r, t)),
+        ("16 trips of the rank loop, 8 of the walker loop", lambda r, t: select_trips(r["L"], t) == 16 and select_trips(r["K"], t) == 8)]),
+    "N5": dict(route="mocks", R=3, L=1366, K=683, S=2, n_iter=3, seed=5, reaches=[
+        ("the smallest R K past kPartialPoints at R = 3: one workgroup per point", lambda r, t: r["R"] * (r["K"] - 1) <= t["kPartialPoints"] < nested_rows(r)
+         and _nested_range_is(-1)(r, t)),
+        ("K is no multiple of a workgroup: every problem edge inside a workgroup of the load, adopt, step and commit kernels",
+         lambda r, t: r["R"] > 1 and t["kNestedBlock"] % r["K"] != 0 and all((q * r["K"]) % t["kNestedBlock"] != 0 for q in range(1, r["R"]))),
+        ("L % 64 == 22: a partial wave in the last trip over the live points", lambda r, t: r["L"] % 64 == 22 and select_trips(r["L"], t) == 6)]),
+    "N6": dict(route="mocks, repeated", R=4, L=4096, K=2048, S=2, n_iter=3, seed=6, reaches=[
+        ("8192 rows: the largest launch under test, one workgroup per point", lambda r, t: nested_rows(r) == 8192 == LARGEST_NESTED_ROWS_TESTED
+         and _nested_range_is(-1)(r, t)),
+        ("four select workgroups, each with every LDS array full", lambda r, t: r["R"] == 4 and _lds_full(r, t)),
+        ("the definition route's log_likelihood_pairs past the in-place host path", lambda r, t: t["kZeroCopyMaxDefault"] < nested_rows(r))]),
+    "N7": dict(route="mocks, repeated", R=300, L=6, K=3, S=2, n_iter=3, seed=7, reaches=[
+        ("more problems than the select kernel has threads, more than mocks", lambda r, t: r["R"] > t["kNestedSelect"] and r["R"] > 16 + 16),
+        ("900 rows: ranges of the upper band", lambda r, t: nested_rows(r) == 900 and _nested_range_is("cpi2")(r, t)),
+        ("K = 3 does not divide a workgroup: ten of the fourteen workgroup edges split a problem", lambda r, t: t["kNestedBlock"] % r["K"] != 0
+         and walker_groups(r, t) == 15 and split_problems(r, t) == 10)]),
+    "N8": dict(route="mocks", R=3, L=320, K=5, S=2, n_iter=3, seed=8, reaches=[
+        ("64 start passes: pass K addressing of load and adopt", lambda r, t: passes(r) == 64),
+        ("L % kNestedSelect == 64: a second trip of one wave", lambda r, t: r["L"] % t["kNestedSelect"] == 64 and select_trips(r["L"], t) == 2),
+        ("15 rows: the point-major kernel", _nested_range_is(0))]),
+    "N9": dict(route="paired models", R=3, L=48, K=24, S=2, n_iter=3, seed=9, reaches=[
+        ("72 rows: row_which written by select and step across a workgroup edge", lambda r, t: nested_rows(r) == 72 > t["kNestedBlock"]
+         and t["kNestedBlock"] % r["K"] != 0 and split_problems(r, t) == 1)]),
+    "N10": dict(route="dsplit_diag joint mocks, sigma_v@q per block", R=5, L=176, K=88, S=2, n_iter=3, seed=10, reaches=[
+        ("R K past kJointSortChunk: sampled_row's row-set loop at a stride of 440 rows", lambda r, t: nested_rows(r) == 440 > t["kJointSortChunk"]),
+        ("problems split across workgroups of the per-walker kernels", lambda r, t: t["kNestedBlock"] % r["K"] != 0 and split_problems(r, t) >= 4)]),
+}
+
+# What stays untested: launches above 8192 rows, up to the MAX_ROWS = 65536 the product accepts - in particular the 32768 rows
+# (R = 1024 at the default batch) DESIGN.md section 7d times - and NO_FINITE / NaN log-likelihoods on the device.
+LARGEST_NESTED_ROWS_TESTED = 8192
+
+
+def nested_variants(row):
+    """The (L, K) combinations of a nested row."""
+    Ls = row["L"] if isinstance(row["L"], tuple) else (row["L"],)
+    Ks = row["K"] if isinstance(row["K"], tuple) else (row["K"],)
+    assert len(Ls) == len(Ks)
+    return [dict(row, L=L, K=K) for L, K in zip(Ls, Ks)]

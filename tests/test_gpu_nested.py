@@ -4,7 +4,11 @@ so the dead record (lnL, chi2, x), the final live points and the counters are co
 the beta-dependent BOSS fit, mocks and the data vector, rows and live points past one wave, more problems than a wave with repeated
 mocks, K = 1, paired models, a joint fit under one covariance and block-diagonal mocks with a dispersion per block; epsilon sampled
 at the margin of tests/test_gpu_chains.py; cuts; every dead point against an independent ``log_likelihood_pairs`` call; and the
-refusals of the C entry points.  The shapes are the smallest that reach every path.  No assertion is on elapsed time."""
+refusals of the C entry points.  The shapes are the smallest that reach every path of the algorithm; the live-point counts and row
+bands the product runs at - the select kernel's loops past one trip, its LDS arrays full, problems across workgroup edges, every
+regime of the evaluation up to 8192 rows, stuck walkers and planted ties - are in tests/test_gpu_nested_shapes.py (the ``NESTED``
+table of tests/launch_shapes.py), which imports ``both``, ``same_run``, ``exercised`` and ``Raw`` from here.  No assertion is on
+elapsed time."""
 
 import ctypes as C
 import faulthandler

@@ -3,7 +3,8 @@ for at the thresholds as they stand in victor_hip.hip, vk_host.h, the kernel hea
 tests/test_gpu_launch_shapes.py, and no shape exceeds what ``sample_chains`` accepts.  The same for ``STENCILS``, the shapes of the
 two stencil calls (tests/test_gpu_stencil_shapes.py), and for the cases at the LDS ceiling of the Fisher assemble kernel, and for ``CHUNKS``, the
 shapes of the chunked grid and importance pipeline (tests/test_gpu_chunk_shapes.py), whose tail geometry is stated by Python
-twins of victor_amd/csrc/vk_is_tail.h that are held to the header under g++.  A failure names the row to revisit."""
+twins of victor_amd/csrc/vk_is_tail.h that are held to the header under g++, and for ``NESTED``, the shapes of nested sampling
+(tests/test_gpu_nested_shapes.py): K | L, K <= L / 2 and R K <= MAX_ROWS in every row.  A failure names the row to revisit."""
 
 import numpy as np
 import pytest
@@ -162,6 +163,52 @@ def test_the_tail_twins_are_the_header(t, tail_driver, case):
             assert (first, end, step) == mine and rows == LS.rows_of(mine), (case, n, s)
             seen[first:end:step] += 1
         assert np.all(seen == 1), (case, n)                          # every row in exactly one slice
+
+
+# ------------------------------------------------------------------ nested sampling -------------------------------------------------
+def test_the_nested_thresholds_are_found_and_in_order(t):
+    assert t["kNestedBlock"] == 64, "one wave per workgroup of the per-walker kernels: every row of NESTED assumes it"
+    assert t["kNestedSelect"] == 256 and t["kNestedSelect"] % 64 == 0 and t["kMaxLive"] % t["kNestedSelect"] == 0
+    assert t["kMaxLive"] == t["MAX_LIVE"] and t["nested.BLOCK"] == 8
+    assert (8 + 4 + 2) * t["kMaxLive"] <= 64 * 1024, "s_lnl, s_surv and s_dead at kMaxLive entries no longer fit 64 KiB of LDS"
+    assert max(LS.nested_rows(v) for r in LS.NESTED.values() for v in LS.nested_variants(r)) == LS.LARGEST_NESTED_ROWS_TESTED < t["MAX_ROWS"], \
+        "LARGEST_NESTED_ROWS_TESTED and the paragraph of DESIGN.md section 7d no longer say what is tested"
+    assert LS.select_trips(1, t) == 1 and LS.select_trips(t["kNestedSelect"], t) == 1 and LS.select_trips(t["kNestedSelect"] + 1, t) == 2
+    # the shapes tests/test_gpu_nested.py runs: every loop of the select kernel in one trip, every problem with R > 1 inside one
+    # workgroup of the per-walker kernels
+    for R, L, K in ((3, 8, 2), (1, 8, 2), (1, 160, 80), (70, 4, 2), (3, 4, 1)):
+        row = dict(R=R, L=L, K=K)
+        assert LS.select_trips(L, t) == LS.select_trips(K, t) == 1 and (R == 1 or LS.split_problems(row, t) == 0), (R, L, K)
+
+
+@pytest.mark.parametrize("case", sorted(LS.NESTED))
+def test_a_nested_row_reaches_what_it_is_about(t, case):
+    row = LS.NESTED[case]
+    assert {"route", "R", "L", "K", "S", "n_iter", "seed", "reaches"} <= set(row)
+    for v in LS.nested_variants(row):
+        R, L, K = v["R"], v["L"], v["K"]
+        assert L % K == 0 and 1 <= K <= L // 2 and 2 <= L <= t["MAX_LIVE"], (case, L, K)
+        assert 1 <= LS.nested_rows(v) <= t["MAX_ROWS"] and LS.nested_rows(v) <= LS.LARGEST_NESTED_ROWS_TESTED, (case, LS.nested_rows(v))
+        assert LS.passes(v) * K == L and v["S"] >= 1 and v["n_iter"] >= 1
+        for text, check in row["reaches"]:
+            assert check(v, t), f"nested row {case} ({v['route']}, R = {R}, L = {L}, K = {K}) no longer reaches: {text} - revisit its shape"
+
+
+def test_the_nested_table_is_the_smallest_on_its_thresholds(t):
+    """One below the shape, the property is gone."""
+    n2, n5 = LS.NESTED["N2"], LS.NESTED["N5"]
+    assert LS.select_trips(n2["L"] - 2, t) == 1 and LS.walker_groups(dict(n2, K=n2["K"] - 1), t) == 2
+    assert LS.cells_range(LS.nested_rows(dict(n5, K=n5["K"] - 1)), t) == t["cpi2"]
+    assert LS.split_problems(dict(LS.NESTED["N9"], R=2), t) == 0
+
+
+def test_every_nested_row_is_a_gpu_case():
+    """The GPU file's parametrisation is built from the table: every row, every variant."""
+    import tests.test_gpu_nested_shapes as G
+    ids = G.IDS["test_a_row"]
+    assert len(ids) == len(set(ids)) and {i.split("-")[0] for i in ids} == set(LS.NESTED)
+    for case, row in LS.NESTED.items():
+        assert [i for i in ids if i.split("-")[0] == case] == [f"{case}-{v['L']}x{v['K']}" for v in LS.nested_variants(row)], case
 
 
 def test_every_chunk_row_is_a_gpu_case():
