@@ -223,8 +223,38 @@ typedef struct vk_eval_opts {
   int32_t from_data;         /* realspace_ccf_from_data: xi^r evaluated at fiducial coordinates, un-rescaled
                                 abscissae (ccf_model.py:618-619,675-679); growth term beta*bias for linear_bias */
   int32_t empirical_corr;    /* velocity multiplied by (1 + Av delta(r)) (ccf_model.py:451-459)          */
-  int32_t reserved;
+  int32_t reserved;          /* flag word: VK_OPT_* below, read by the create calls of the sampled handles alone; 0 otherwise */
 } vk_eval_opts;
+
+/* ---- likelihood-level beta interpolation in the device loops (ccf_fit.py:383-440) ---------------------------------------------
+ * The reference's `beta_interpolation: likelihood` evaluates a point at the two nodes of the data vector's beta grid that
+ * bracket its beta - lo the last node with g < beta, hi the first with g >= beta (ccf_fit.py:386-390; a beta on a node gives
+ * hi = that node and t = 1) - and blends lnL and chi-square linearly with t = (beta - g[lo]) / (g[hi] - g[lo]); an end that is
+ * not finite fails both (ccf_fit.py:402-410).
+ *
+ * VK_OPT_BETA_BLEND in opts->reserved of vk_fit_create / vk_chain_create / vk_nested_create / vk_grid_create / vk_is_create /
+ * vk_is_create_own puts the new handle in that mode: every evaluation of its m pending rows becomes a split kernel (2 m rows:
+ * [0, m) at g[lo], [m, 2 m) at g[hi], realisation indices duplicated), the unchanged evaluation of the 2 m rows - the data
+ * vector, realisations in pairs mode, realisations in cross mode - and a merge kernel that forms (1 - t) lo + t hi with separate
+ * roundings, the host expression's bits.  A row without a bracket (beta <= g[0], beta > g[last], NaN: where the reference
+ * raises IndexError) reports (-inf, +inf), so a sampler rejects it.  g is the context's beta_d, copied once per handle; the
+ * handle's pending-row copies, realisation indices, theory workspace and raw results are sized for twice its largest launch,
+ * inside its one allocation (a create call that cannot allocate says how many bytes it asked for).
+ * Refused by the create call, before any device call (VK_E_ARG words in `err`): the _joint and _joint_blocks forms (a blend per
+ * block under one beta is a design of its own) and a context whose data vector is not gridded in beta.  On a handle in this
+ * mode vk_fit_fisher, vk_chain_set_predictive and vk_is_set_predictive are refused: a blended point has two theory vectors.
+ * The evaluation entry points (vk_eval_batch and its kin) never read the word; the handle clears the flag in its own copy.
+ *
+ * vk_blend_split / vk_blend_merge run the two kernels alone on host buffers (device `device`, synchronous; for tests):
+ *   split: grid [n_grid] increasing, rows [m][VK_NPAR], which [m] or NULL -> rows2 [2 m][VK_NPAR], which2 [2 m] (untouched
+ *          without which), t [m], fail [m].
+ *   merge: t [m], fail [m], raw_lnl / raw_chi [2 m][per_row] -> lnl / chi [m][per_row] (per_row: 1, or n_real in cross mode).
+ * Both return VK_OK, VK_E_ARG (a NULL array, m < 1, n_grid < 2, per_row < 1) or VK_E_HIP. */
+#define VK_OPT_BETA_BLEND 1
+int vk_blend_split(int device, const double* grid, int32_t n_grid, const double* rows, const int32_t* which, int64_t m, double* rows2,
+                   int32_t* which2, double* t, int32_t* fail);
+int vk_blend_merge(int device, const double* t, const int32_t* fail, int64_t m, int64_t per_row, const double* raw_lnl,
+                   const double* raw_chi, double* lnl, double* chi);
 
 typedef struct vk_ctx vk_ctx;
 

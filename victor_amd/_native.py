@@ -23,6 +23,7 @@ VK_WALK_EPSILON = -1
 ROW_COLUMNS = {"fsigma8": P_FSIGMA8, "sigma_v": P_SIGMAV, "beta": P_BETA, "astar": P_ASTAR, "M": P_M, "Q": P_Q, "bias": P_BIAS,
                "Av": P_AV}
 VK_FIT_CONVERGED, VK_FIT_MAX_ITER, VK_FIT_NO_FINITE_START = 0, 1, 2
+VK_OPT_BETA_BLEND = 1     # vk_eval_opts.reserved of a sampled handle's create call: blend lnL / chi2 between the bracketing grid betas
 VK_HESS_OK, VK_HESS_AT_BOUND, VK_HESS_NOT_FINITE, VK_HESS_NOT_POSDEF = 0, 1, 2, 3
 
 _dp = C.POINTER(C.c_double)
@@ -253,6 +254,10 @@ SYMBOLS = {
     "vk_nested_state": (C.c_int, [_vp, _dp, _dp, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "vk_nested_last_error": (C.c_char_p, [_vp]),
     "vk_nested_destroy": (None, [_vp]),
+    # likelihood-level beta interpolation (VK_OPT_BETA_BLEND in vk_eval_opts.reserved at a handle's create call): its two kernels alone
+    "vk_blend_split": (C.c_int, [C.c_int, _dp, C.c_int32, _dp, C.POINTER(C.c_int32), C.c_int64, _dp, C.POINTER(C.c_int32), _dp,
+                                 C.POINTER(C.c_int32)]),
+    "vk_blend_merge": (C.c_int, [C.c_int, _dp, C.POINTER(C.c_int32), C.c_int64, C.c_int64, _dp, _dp, _dp, _dp]),
     "vk_serve_mailboxes": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, _optp, _vp, C.c_int32, _vp, C.c_double, C.c_int32,
                            C.c_double, C.POINTER(vk_serve_stats)]),
     "vk_timing_enable": (C.c_int, [_vp, C.c_int]),

@@ -622,7 +622,7 @@ def sample_chains(fit, params, n_steps, walkers=8, seed=0, fixed=None, start=Non
     predictive = resolve_predictive(predictive, "sample_chains", isinstance(fit, JointFit), temper is not None and temper is not False,
                                     evaluate is None)
     if evaluate is None:
-        fit_options = q.fit_options(fit, kwargs)
+        fit_options = q.fit_options(fit, kwargs, "predictive=" if predictive else None)
     R = len(realisations) if realisations is not None else 1
     W = walkers
     if R * W > MAX_CHAINS:

@@ -59,6 +59,9 @@
 //   vk_kernel_nested.h   nested sampling (vk_nested_begin; the last section of this file): the select kernel, one workgroup per
 //                        problem, and the step and commit kernels, one thread per replacement walker, over the order, the pick,
 //                        the constrained step and the commit of vk_nested_step.h (plain C++, likewise)
+//   vk_kernel_blend.h    likelihood-level beta interpolation on any single-fit handle (VK_OPT_BETA_BLEND; sampled_evaluate_blend):
+//                        the split kernel, one thread per pending row, and the merge kernel, one thread per output, around the
+//                        unchanged evaluation of twice the rows
 
 #include <hip/hip_runtime.h>
 
@@ -86,6 +89,7 @@
 #include "vk_kernel_is_predict.h"
 #include "vk_kernel_is_tail.h"
 #include "vk_kernel_nested.h"
+#include "vk_kernel_blend.h"
 
 using namespace vk;
 using vkh::check_joint;
@@ -118,6 +122,17 @@ struct Sampled {
   int *d_which = nullptr, *d_row_which = nullptr;                 // realisation of each problem, of each pending row
   vkprior::Prior prior{};                  // the Gaussian prior the step kernels add to lnL (vk_fit_set_prior / vk_chain_set_prior)
   bool keep_theory = false;                // the data-vector route stores the rows' theory vectors in d_th (vk_chain_set_predictive)
+  // Likelihood-level beta interpolation (VK_OPT_BETA_BLEND of the create call's opts; vk_kernel_blend.h, a single fit only): the
+  // m pending rows are evaluated as 2 m rows - rows [0, m) at the lower, rows [m, 2 m) at the upper bracketing node of the data
+  // vector's beta grid - and blended.  The doubled launch's arrays live in the handle's one allocation (blend_layout), d_th is
+  // sized for twice rows_max (workspace_doubles); d_rows / d_row_which / the callers' d_lnl and d_chi stay what they were.
+  struct Blend {
+    bool on = false;
+    int n_grid = 0;
+    long long per_row = 1;                 // outputs of a pending row: n_real in cross mode (a handle's prepare sets it), else 1
+    double *grid = nullptr, *rows = nullptr, *t = nullptr, *lnl = nullptr, *chi = nullptr;   // [n_grid], [2 rows_max][VK_NPAR], [rows_max], raw [2 rows_max][per_row] x 2
+    int *which = nullptr, *fail = nullptr;                                                    // [2 rows_max], [rows_max]
+  } blend;
   std::string err;
 
   // doubles between two row sets of d_rows (fixed per handle: a best fit's launches shrink, its sets stay where they are)
@@ -131,12 +146,27 @@ struct Sampled {
     return b;
   }
 
+  // the blend arrays, first in every handle's layout (nothing without the mode); the int arrays take an even count each, so
+  // what follows stays aligned for doubles
+  template <class C>
+  void blend_layout(C& c) {
+    if (!blend.on) return;
+    const size_t n = rows_max, even = (n + 1) & ~(size_t)1;
+    c.take(blend.grid, (size_t)blend.n_grid);
+    c.take(blend.rows, 2 * n * VK_NPAR);
+    c.take(blend.t, n);
+    c.take(blend.lnl, 2 * n * (size_t)blend.per_row);
+    c.take(blend.chi, 2 * n * (size_t)blend.per_row);
+    c.take(blend.which, 2 * n);
+    c.take(blend.fail, even);
+  }
+
   // doubles of d_th: the theory vectors of rows_max rows; of a joint fit, the workspace of its evaluation of that many rows
   // (whose head is the rows' theory vectors, block by block).  Block-diagonal that is B rows_max (N_max + 2) in pairs mode - per
   // block lnl | chi2 | theory - and B rows_max (N_max + 2 cross) in cross mode, where a row has `cross` values of lnl and of chi2;
   // under a covariance the outputs are the handle's own arrays in either mode (vkh::joint_workspace_doubles).
   size_t workspace_doubles() const {
-    return blocks.empty() ? rows_max * ctx->N
+    return blocks.empty() ? rows_max * (blend.on ? 2 : 1) * ctx->N
                           : vkh::joint_workspace_doubles(cov, blocks.data(), (int)blocks.size(), (long long)rows_max, real, cross);
   }
 };
@@ -225,6 +255,13 @@ static H* sampled_create(const char* who, const char* noun, vk_ctx* const* ctxs,
     if (check_opts(ctxs[q], opts) != VK_OK) return bail(ctxs[q]->err);
   }
   if (!joint && !ctx->d_data) return bail(me + "context was created without a data vector");
+  const bool blend = (opts->reserved & VK_OPT_BETA_BLEND) != 0;
+  if (blend && joint)
+    return bail(me + "VK_OPT_BETA_BLEND (beta_interpolation 'likelihood') is refused for a joint fit: a blend per block under one "
+                     "beta is a design of its own");
+  if (blend && ctx->n_beta_d < 2)
+    return bail(me + "VK_OPT_BETA_BLEND (beta_interpolation 'likelihood') needs a data vector gridded in beta: a fixed data vector "
+                     "has no nodes to blend between");
   // a joint fit: one device, data vectors, the handle's lead and block sizes; against realisations, the same number of them on
   // every context and the LDS the realisation kernels need
   if (joint && check_joint(cov, ctxs, n_ctx, which != nullptr) != VK_OK) return bail(me + ctx->err);
@@ -270,6 +307,9 @@ static H* sampled_create(const char* who, const char* noun, vk_ctx* const* ctxs,
   if (joint) f->blocks.assign(ctxs, ctxs + n_ctx);
   f->cov = cov;
   f->opts = *opts;
+  f->opts.reserved &= ~VK_OPT_BETA_BLEND;    // (the handle's mode, not the evaluation's: the entry points it calls see the word without it)
+  f->blend.on = blend;
+  f->blend.n_grid = blend ? ctx->n_beta_d : 0;
   f->P = n_params;
   for (int j = 0; j < kSampledMaxP; ++j) f->pblock[j] = -1;
   for (int j = 0; j < n_params; ++j) {
@@ -289,6 +329,8 @@ static H* sampled_create(const char* who, const char* noun, vk_ctx* const* ctxs,
   }
   bool ok = hipMemcpy(f->d_base, base_rows, (size_t)f->sets * n * VK_NPAR * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
   if (ok && which) ok = hipMemcpy(f->d_which, which, (size_t)n * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
+  if (ok && blend)                         // the handle's own copy of the data vector's beta nodes, once
+    ok = hipMemcpy(f->blend.grid, ctx->d_beta_d, (size_t)f->blend.n_grid * sizeof(double), hipMemcpyDeviceToDevice) == hipSuccess;
   if (!ok) {
     (void)hipGetLastError();
     sampled_destroy(f);
@@ -369,8 +411,10 @@ static int sampled_ready(Sampled* f, const char* who, const char* noun, bool nam
 // the evaluation of the first m pending rows into d_lnl / d_chi, on the context's stream: the fit's own data vector with lnL /
 // chi2 in the theory launch (the fused tail applies), realisations in pairs mode - or, of a handle that keeps no d_row_which (an
 // importance handle), in cross mode: every row against every realisation, outputs [m][n_real], single fit and joint fit alike
+static int sampled_evaluate_blend(Sampled* f, long long m, double* d_lnl, double* d_chi);
 static int sampled_evaluate(Sampled* f, long long m, double* d_lnl, double* d_chi) {
   int rc;
+  if (f->blend.on) return sampled_evaluate_blend(f, m, d_lnl, d_chi);
   if (f->blocks.empty()) {
     // (with lnL requested the data-vector route treats d_th as scratch and its fused tail never stores the theory vector:
     // keep_theory asks for the stores - TheoryArgs::want_theory -, which change no bit of lnL; the realisation route writes d_th)
@@ -410,6 +454,39 @@ static int sampled_launch(Sampled* f, void (*kern)(Args), long long threads, int
   hipLaunchKernelGGL(kern, dim3((unsigned)((threads + block - 1) / block)), dim3(block), 0, f->ctx->stream, a);
   VK_SAMPLED_HIP(f, hipGetLastError());
   return VK_OK;
+}
+
+// sampled_evaluate of a handle in blend mode (a single fit: sampled_create): the split kernel writes the 2 m rows, the evaluation
+// sampled_evaluate makes otherwise runs over them into the raw arrays - the data vector, realisations in pairs mode with the
+// duplicated indices, or in cross mode [2 m][n_real] -, the merge kernel blends into the caller's arrays.  m <= rows_max.
+static int sampled_evaluate_blend(Sampled* f, long long m, double* d_lnl, double* d_chi) {
+  if (m <= 0) return VK_OK;
+  const Sampled::Blend& b = f->blend;
+  const int* row_which = f->real ? f->d_row_which : nullptr;     // (NULL against realisations: cross mode)
+  BlendArgs q{};
+  q.grid = b.grid;
+  q.n_grid = b.n_grid;
+  q.m = m;
+  q.per_row = f->real && !row_which ? b.per_row : 1;
+  q.rows = f->d_rows;
+  q.row_which = row_which;
+  q.rows2 = b.rows;
+  q.which2 = b.which;
+  q.t = b.t;
+  q.fail = b.fail;
+  q.raw_lnl = b.lnl;
+  q.raw_chi = b.chi;
+  q.lnl = d_lnl;
+  q.chi = d_chi;
+  int rc = sampled_launch(f, vk_blend_split_kernel, m, kBlendBlock, q);
+  if (rc) return rc;
+  rc = f->real ? enqueue_realisations(f->ctx, &f->opts, b.rows, 2 * m, f->d_th, b.lnl, b.chi, row_which ? b.which : nullptr)
+               : vk_eval_batch_device_async(f->ctx, &f->opts, b.rows, 2 * m, b.lnl, b.chi, f->d_th);
+  if (rc) {
+    f->err = f->ctx->err;
+    return rc;
+  }
+  return sampled_launch(f, vk_blend_merge_kernel, m * q.per_row, kBlendBlock, q);
 }
 
 // Device arrays copied home, each if the caller gave it a destination: plain copies, complete on return, or (on_stream) enqueued
@@ -461,6 +538,7 @@ struct __attribute__((visibility("hidden"))) vk_fit : Sampled {
   }
   void layout(Carve& c) {
     const size_t n = R, rows = n * S;
+    blend_layout(c);
     c.take(d_state, n);
     c.take(d_base, sets * n * VK_NPAR);
     c.take(d_x0, n * P);
@@ -898,6 +976,9 @@ int vk_fit_fisher(vk_fit* f, const double* x, const double* h, double* vectors, 
                   int32_t* status) {
   if (!f) return VK_E_ARG;
   if (!x || !h) return refused(f, "vk_fit_fisher: NULL argument");
+  if (f->blend.on)
+    return refused(f, "vk_fit_fisher: the handle blends the likelihood between two grid betas (VK_OPT_BETA_BLEND): a point has two "
+                      "theory vectors and no one Jacobian");
   int rc = sampled_ready(f, "vk_fit_fisher", "problem", false);
   if (rc) return rc;
   const size_t R = f->R, d = f->P;
@@ -1075,6 +1156,7 @@ struct __attribute__((visibility("hidden"))) vk_chain : Sampled {
   // state | base, x0, rows, results, theory workspace | one block of random numbers | one block of history | counters | indices
   void layout(Carve& c) {
     const size_t n = C, block = vkchain::kBlock * n;
+    blend_layout(c);
     c.take(d_x, n * P);
     c.take(d_lnl, n);
     c.take(d_chi, n);
@@ -1392,6 +1474,9 @@ int vk_chain_set_predictive(vk_chain* f, int32_t group) {
   if (!f->blocks.empty())
     return refused(f, me + "a joint handle (vk_chain_create_joint) is refused: its theory workspace is laid out by the route that "
                            "evaluates it, not as one vector per row");
+  if (f->blend.on)
+    return refused(f, me + "the handle blends the likelihood between two grid betas (VK_OPT_BETA_BLEND): a point has two theory "
+                           "vectors, and the sums are of one");
   if (f->temper.K)
     return refused(f, me + "the handle is tempered (vk_chain_set_tempering): a swap moves states without touching the accept "
                            "counters the held vectors follow");
@@ -1753,6 +1838,7 @@ struct __attribute__((visibility("hidden"))) vk_grid : Sampled {
   void shape(int, const double*, const double*) { rows_max = (size_t)chunk; }
   void layout(Carve& c) {
     const size_t n = (size_t)chunk, r = (size_t)R;
+    blend_layout(c);
     c.take(d_run, r + 1);
     c.take(d_base, VK_NPAR);
     c.take(d_rows, n * VK_NPAR);
@@ -1897,6 +1983,7 @@ vk_grid* vk_grid_create(vk_ctx* ctx, const vk_eval_opts* opts, int32_t n_axes, c
     h->g = vkgrid::make_shape(n_axes, bins);
     h->R = R;
     h->real = every_realisation != 0;
+    h->blend.per_row = R;                  // (cross mode: every grid point against every realisation)
     h->max_which = h->real ? R - 1 : -1;
     h->chunk = chunk;
     h->n1 = (int)n1;
@@ -2070,6 +2157,7 @@ struct __attribute__((visibility("hidden"))) vk_is : Sampled {
   // has a prior problem of its own (2 R running states and accumulator columns) and the rows carry their realisation
   void layout(Carve& c) {
     const size_t r = (size_t)R, m = each ? r : 1, n = (size_t)chunk * m, g = (size_t)G * m;
+    blend_layout(c);
     if (each) return layout_each(c, r, n, g);
     c.take(d_run, r + 1);
     c.take(d_base, (size_t)sets * VK_NPAR);          // (a base row and a set of pending rows per block: vk_is_create_joint_blocks)
@@ -2406,6 +2494,7 @@ static vk_is* is_create(const char* who, vk_ctx* const* ctxs, int n_ctx, bool jo
     h->each = each;
     h->real = each || every_realisation != 0;
     h->cross = h->real && !each ? R : 0;
+    h->blend.per_row = each ? 1 : R;
     h->max_which = h->real ? R - 1 : -1;
     if (each) h->max_which = *std::max_element(which, which + R);
     h->chunk = chunk;
@@ -2494,6 +2583,9 @@ int vk_is_set_predictive(vk_is* f, int32_t on) {
   if (!f) return VK_E_ARG;
   const std::string me = "vk_is_set_predictive: ";
   if (f->each) return refused(f, me + "a handle with a proposal per problem (vk_is_create_own) keeps no predictive sums");
+  if (on && f->blend.on)
+    return refused(f, me + "the handle blends the likelihood between two grid betas (VK_OPT_BETA_BLEND): a point has two theory "
+                           "vectors, and the sums are of one");
   if (f->done != 0 && f->done != f->G) return refused(f, me + "a run is under way (call it before the first vk_is_run)");
   f->pred_mem.drop(f);
   f->pred_N = 0;
@@ -2696,6 +2788,7 @@ struct __attribute__((visibility("hidden"))) vk_nested : Sampled {
   // dead record | counters | indices
   void layout(Carve& c) {
     const size_t n = RK, live = (size_t)R * L, block = (size_t)vknest::kBlock * n;
+    blend_layout(c);
     c.take(d_lx, live * P);
     c.take(d_llnl, live);
     c.take(d_lchi, live);
@@ -2943,6 +3036,103 @@ int vk_nested_state(vk_nested* f, double* x, double* lnl, double* chi2, int64_t*
   }
   f->err.clear();
   return VK_OK;
+}
+
+}  // extern "C"
+
+// ---- the kernels of vk_kernel_blend.h alone, on host buffers (include/victor_hip.h: vk_blend_split / vk_blend_merge) ----------
+// One allocation per call, the kernels on the device's null stream, the results copied home: what sampled_evaluate_blend
+// launches around its evaluation, with nothing between them.
+namespace {
+struct BlendMem {
+  double *grid = nullptr, *rows = nullptr, *rows2 = nullptr, *t = nullptr, *raw_lnl = nullptr, *raw_chi = nullptr, *lnl = nullptr,
+         *chi = nullptr;
+  int *which = nullptr, *which2 = nullptr, *fail = nullptr;
+};
+
+template <class Layout, class Body>
+int blend_call(int device, Layout&& layout, Body&& body) {
+  void* mem = nullptr;
+  size_t bytes = 0;
+  if (!carve_alloc(device, mem, bytes, layout)) return VK_E_HIP;
+  const bool ok = body();
+  const bool clean = hipDeviceSynchronize() == hipSuccess;
+  (void)hipGetLastError();
+  (void)hipFree(mem);
+  return ok && clean ? VK_OK : VK_E_HIP;
+}
+}  // namespace
+
+extern "C" {
+
+int vk_blend_split(int device, const double* grid, int32_t n_grid, const double* rows, const int32_t* which, int64_t m, double* rows2,
+                   int32_t* which2, double* t, int32_t* fail) {
+  if (!grid || !rows || !rows2 || !t || !fail || (which && !which2) || m < 1 || m > (1LL << 30) || n_grid < 2) return VK_E_ARG;
+  const size_t n = (size_t)m;
+  BlendMem b;
+  return blend_call(device, [&](Carve& c) {
+    c.take(b.grid, (size_t)n_grid);
+    c.take(b.rows, n * VK_NPAR);
+    c.take(b.rows2, 2 * n * VK_NPAR);
+    c.take(b.t, n);
+    c.take(b.which, n);
+    c.take(b.which2, 2 * n);
+    c.take(b.fail, n);
+  }, [&]() {
+    auto up = [](void* dst, const void* src, size_t bytes) { return hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess; };
+    auto home = [](void* dst, const void* src, size_t bytes) { return hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) == hipSuccess; };
+    if (!up(b.grid, grid, (size_t)n_grid * sizeof(double)) || !up(b.rows, rows, n * VK_NPAR * sizeof(double))) return false;
+    if (which && !up(b.which, which, n * sizeof(int))) return false;
+    BlendArgs q{};
+    q.grid = b.grid;
+    q.n_grid = n_grid;
+    q.m = m;
+    q.per_row = 1;
+    q.rows = b.rows;
+    q.row_which = which ? b.which : nullptr;
+    q.rows2 = b.rows2;
+    q.which2 = b.which2;
+    q.t = b.t;
+    q.fail = b.fail;
+    hipLaunchKernelGGL(vk_blend_split_kernel, dim3((unsigned)((m + kBlendBlock - 1) / kBlendBlock)), dim3(kBlendBlock), 0, nullptr, q);
+    if (hipGetLastError() != hipSuccess) return false;
+    return home(rows2, b.rows2, 2 * n * VK_NPAR * sizeof(double)) && home(t, b.t, n * sizeof(double)) &&
+           home(fail, b.fail, n * sizeof(int)) && (!which || home(which2, b.which2, 2 * n * sizeof(int)));
+  });
+}
+
+int vk_blend_merge(int device, const double* t, const int32_t* fail, int64_t m, int64_t per_row, const double* raw_lnl,
+                   const double* raw_chi, double* lnl, double* chi) {
+  if (!t || !fail || !raw_lnl || !raw_chi || !lnl || !chi || m < 1 || per_row < 1 || m > (1LL << 30) / per_row) return VK_E_ARG;
+  const size_t n = (size_t)m, out = n * (size_t)per_row;
+  BlendMem b;
+  return blend_call(device, [&](Carve& c) {
+    c.take(b.t, n);
+    c.take(b.raw_lnl, 2 * out);
+    c.take(b.raw_chi, 2 * out);
+    c.take(b.lnl, out);
+    c.take(b.chi, out);
+    c.take(b.fail, n);
+  }, [&]() {
+    auto up = [](void* dst, const void* src, size_t bytes) { return hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess; };
+    auto home = [](void* dst, const void* src, size_t bytes) { return hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) == hipSuccess; };
+    if (!up(b.t, t, n * sizeof(double)) || !up(b.fail, fail, n * sizeof(int)) || !up(b.raw_lnl, raw_lnl, 2 * out * sizeof(double)) ||
+        !up(b.raw_chi, raw_chi, 2 * out * sizeof(double)))
+      return false;
+    BlendArgs q{};
+    q.m = m;
+    q.per_row = per_row;
+    q.t = b.t;
+    q.fail = b.fail;
+    q.raw_lnl = b.raw_lnl;
+    q.raw_chi = b.raw_chi;
+    q.lnl = b.lnl;
+    q.chi = b.chi;
+    hipLaunchKernelGGL(vk_blend_merge_kernel, dim3((unsigned)(((long long)out + kBlendBlock - 1) / kBlendBlock)), dim3(kBlendBlock), 0,
+                       nullptr, q);
+    if (hipGetLastError() != hipSuccess) return false;
+    return home(lnl, b.lnl, out * sizeof(double)) && home(chi, b.chi, out * sizeof(double));
+  });
 }
 
 }  // extern "C"

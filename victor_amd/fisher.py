@@ -347,7 +347,7 @@ def fisher(fit, params, at, step=None, fixed=None, prior=None, shrink=8, keep_ve
     shrink, _ = check_policy("fisher", shrink, 0)
     keep_vectors = bool(keep_vectors)
     if evaluate is None:
-        fit_options = q.fit_options(fit, kwargs)
+        fit_options = q.fit_options(fit, kwargs, "a Fisher matrix (fisher, keep_vectors)")
         scale = resolve_scale(fit, kwargs)
     else:
         scale = 1.0

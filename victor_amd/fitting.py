@@ -71,6 +71,24 @@ def _per_problem(name, v, R, who=""):
     return a
 
 
+def blends(fit, fit_options):
+    """Does ``fit`` under these fit options blend the likelihood between two grid betas (``beta_interpolation: likelihood`` on a
+    beta-dependent data vector; reference: ``ccf_fit.py:383-440``)?"""
+    return fit_options["beta_interpolation"] == "likelihood" and not fit.fixed_data
+
+
+def blend_opts(fit, fit_options, opts):
+    """``opts`` for the create call of a sampled handle of a single ``fit``: a copy with ``VK_OPT_BETA_BLEND`` set when the fit
+    options ask for the likelihood-level blend - the handle then evaluates every pending row at its two bracketing nodes of
+    ``fit.beta_ccf`` (the context's ``beta_d``) and blends on the device (``include/victor_hip.h``).  The evaluation entry points
+    never see the flag: ``Engine.make_opts`` leaves the word 0, and the host blend of ``log_likelihood_batch`` stays what it is."""
+    if not blends(fit, fit_options):
+        return opts
+    out = N.vk_eval_opts.from_buffer_copy(opts)
+    out.reserved |= N.VK_OPT_BETA_BLEND
+    return out
+
+
 class _Sampled:
     """What ``best_fit`` and ``sample_chains`` (``who``; their parameters are ``verb``: "fitted" / "sampled") share: the sampled
     parameters of a cobaya ``params`` block with their prior box, the checks on them, and the handle of their device loop.  Each
@@ -117,8 +135,13 @@ class _Sampled:
         if any(n.partition("@")[0] == "epsilon" for n in self.names) and np.ndim(self.fixed_all.get("alpha", 1)) > 0:
             raise InputError(f"{self.who}: alpha must be a scalar when epsilon is {self.verb}")
 
-    def fit_options(self, fit, kwargs):
-        """The merged fit options (of a joint fit: its lead block's; every block is checked)."""
+    def fit_options(self, fit, kwargs, vectors=None):
+        """The merged fit options (of a joint fit: its lead block's; every block is checked).  ``beta_interpolation='likelihood'``
+        on a beta-dependent data vector (reference: ``ccf_fit.py:383-440``) is served by a single fit's device loops
+        (``VK_OPT_BETA_BLEND``: :func:`blend_opts`) when it is the fit's own option (its data block / ``fit.fit_options``);
+        refused here, before any device call: a joint fit, a caller that needs the theory vector of a point (``vectors``: its
+        word for what it computes from them) - a blended point has two -, and the option given per call on a fit configured
+        otherwise, which these loops have always refused."""
         from .joint import JointFit
         blocks = fit.fits if isinstance(fit, JointFit) else None
         if blocks is not None and fit.covariance is not None:
@@ -126,9 +149,19 @@ class _Sampled:
         first = None
         for f in blocks if blocks is not None else [fit]:
             fit_options = f._merged_fit(kwargs)
-            if fit_options["beta_interpolation"] == "likelihood" and not f.fixed_data:
-                raise InputError(f"{self.who}: beta_interpolation 'likelihood' on a beta-dependent data vector is not supported "
-                                 "(its blend of two evaluations runs on the host)")
+            if blends(f, fit_options):
+                if blocks is not None:
+                    raise InputError(f"{self.who}: beta_interpolation 'likelihood' on a beta-dependent data vector is not supported "
+                                     "for joint fits (a blend per block under one beta is a design of its own)")
+                if vectors:
+                    raise InputError(f"{self.who}: beta_interpolation 'likelihood' on a beta-dependent data vector is not supported "
+                                     f"with {vectors} (a blended point has two theory vectors, one per bracketing grid beta)")
+                if f.fit_options.get("beta_interpolation") != "likelihood":
+                    # the mode of a loop is the fit's own, as the reference configures it (ccf_fit.py:41-42: read from the data
+                    # block); a per-call override into it stays what it always was in these loops - a refusal
+                    raise InputError(f"{self.who}: beta_interpolation 'likelihood' on a beta-dependent data vector is not supported "
+                                     "as a per-call option here: set it on the fit (`beta_interpolation: likelihood` in its data "
+                                     "block, or fit.fit_options), where the reference configures it")
             first = fit_options if first is None else first
         return first
 
@@ -197,6 +230,7 @@ class _Sampled:
                 realisations._upload(eng)
         i32 = C.POINTER(C.c_int32)
         err = C.create_string_buffer(512)
+        opts = blend_opts(fit, fit_options, opts)
         h = getattr(eng._lib, entry)(eng._ctx, C.byref(opts), len(rows), *shape, len(cols), cols.ctypes.data_as(i32), N.as_dp(N.f64(self.lo)),
                                      N.as_dp(N.f64(self.hi)), N.as_dp(rows), float(self.fixed_all.get("alpha", 1)),
                                      None if realisations is None else which.ctypes.data_as(i32), err, len(err))

@@ -38,7 +38,7 @@ import ctypes as C
 import numpy as np
 
 from . import _native as N
-from .fitting import _Sampled
+from .fitting import _Sampled, blend_opts
 from .utils import InputError
 
 MAX_AXES = 10
@@ -463,6 +463,7 @@ def create_handle(q, fit, realisations, kwargs, fit_options, grid, fixed_out, ch
 
         def refresh():
             realisations._upload(eng)
+    opts = blend_opts(fit, fit_options, opts)
     eps_pow = None
     if "epsilon" in grid.names:
         with np.errstate(invalid="ignore"):

@@ -109,7 +109,7 @@ import math
 import numpy as np
 
 from . import _native as N
-from .fitting import _Sampled
+from .fitting import _Sampled, blend_opts
 from .grid import MAX_CHUNK, default_chunk
 from .marginals import Marginals, cells, slots
 from .priors import resolve_prior, tri
@@ -1220,7 +1220,7 @@ def importance_posterior(fit, params, proposal=None, n=16384, seed=0, fixed=None
             f"{who}: realisations(paired_model=True) have no cross mode (a point has one theory vector per "
             "realisation): a shared sample evaluates every point once")
     if evaluate is None:
-        fit_options = q.fit_options(fit, kwargs)
+        fit_options = q.fit_options(fit, kwargs, "predictive=True" if predictive else None)
     if joint is not None and evaluate is None and len({f._device for f in joint.fits}) != 1:
         raise InputError(f"{who}: every block of a joint fit must live on the same device")
     if not np.isfinite(min_ess) or min_ess < 0:
@@ -1404,7 +1404,8 @@ def create_own_handle(fit, realisations, kwargs, layout, smp, lists, fixed_out, 
     i32 = C.POINTER(C.c_int32)
     batch = dict(fixed_out)
     batch.update({name: np.array([smp.x[0, 0, j]]) for j, name in enumerate(names)})
-    model, _, eng, opts = realisations._plan(kwargs)
+    model, own_options, eng, opts = realisations._plan(kwargs)
+    opts = blend_opts(fit, own_options, opts)
     base = np.ascontiguousarray(fit._fit_rows(batch, model), dtype=np.float64)
     cols = np.array([N.ROW_COLUMNS.get(name, N.VK_WALK_EPSILON) for name in names], dtype=np.int32)
     eps_pow = None
@@ -1498,6 +1499,7 @@ def create_handle(q, fit, realisations, kwargs, fit_options, layout, smp, lists,
 
             def refresh():
                 realisations._upload(eng)
+        opts = blend_opts(fit, fit_options, opts)
         lib, entry, head = eng._lib, "vk_is_create", (eng._ctx, C.byref(opts))
     eps_pow = None
     if "epsilon" in layout.names:
