@@ -8,6 +8,10 @@
 
     python examples/nested_evidence.py [--out FILE] [--skip-large]
 
+``--prior`` runs the same two measurements under a Gaussian prior on sigma_v instead (``prior=``): the device route's wall time
+per iteration with and without the prior, alternating in one process, for R = 1 and R = 16; and beta fixed, d = 3, ``ln_evidence``
+under the prior against ``grid_posterior(bins=32, prior=).ln_evidence`` per mock, seeds 0 - 2.
+
 Needs a GPU and the test fixtures of the repository (tests/golden)."""
 
 import argparse
@@ -34,10 +38,63 @@ def per_iteration(obj, params, device, blocks=5, **kw):
     return out
 
 
+def d3_against_the_grid(rs, params, fixed, prior=None):
+    """beta fixed, d = 3, every mock: nested sampling against the grid, three seeds (the mocks of a run share their start draw, so
+    their errors are correlated within a seed)."""
+    kw = {} if prior is None else {"prior": prior}
+    out, grid = [], None
+    for seed in (0, 1, 2):
+        t = time.perf_counter()
+        ns = rs.nested_sampling(params, fixed=fixed, seed=seed, **kw)
+        t_ns = time.perf_counter() - t
+        if grid is None:
+            lo = np.maximum(ns._lo, (ns.mean - 6 * ns.sigma).min(axis=0))
+            hi = np.minimum(ns._hi, (ns.mean + 6 * ns.sigma).max(axis=0))
+            grid = rs.grid_posterior(params, bins=32, fixed=fixed, ranges={n: (float(a), float(b)) for n, a, b in zip(ns.names, lo, hi)}, **kw)
+        grid_ln_z = grid.ln_evidence
+        if prior is not None:
+            # over a sub-range the grid normalises the prior over that sub-range (its own midpoint sum); the nested evidence is
+            # normalised over the box: the grid's numerator, brought to the box with the closed-form normalisation
+            own = grid.prior_ln_max + np.log(grid.prior_total) + np.sum(np.log(grid._h)) - np.sum(np.log(ns._hi - ns._lo))
+            grid_ln_z = grid.ln_evidence + own - ns.ln_prior_norm
+        diff = ns.ln_evidence - grid_ln_z
+        pull = diff / ns.ln_evidence_error
+        out.append({"seed": seed, "names": ns.names, "n_iter": ns.n_iter, "seconds": t_ns, "status": ns.status_names,
+                    "nested": ns.ln_evidence.tolist(), "error": ns.ln_evidence_error.tolist(),
+                    "grid": np.asarray(grid_ln_z).tolist(), "edge_mass": np.asarray(grid.edge_mass).tolist(),
+                    "pull": pull.tolist(), "information": ns.information.tolist(),
+                    "acceptance": ns.acceptance.tolist(), "n_stuck": ns.n_stuck.tolist()})
+        if prior is not None:
+            out[-1].update(prior_norm=ns.prior_norm, ln_prior_norm=ns.ln_prior_norm, ln_prior_norm_error=ns.ln_prior_norm_error)
+        print("d = 3 against the grid" + (" under the prior" if prior is not None else "") + ", seed", seed, ": pulls", np.round(pull, 2),
+              "mean", pull.mean(), "rms", np.sqrt(np.mean(pull ** 2)), "worst", np.abs(pull).max(), "mean difference", diff.mean(),
+              "mean error", ns.ln_evidence_error.mean(), flush=True)
+    return out
+
+
+def under_a_prior(data_fit, rs, params, res):
+    """``--prior``: what a Gaussian prior on sigma_v costs per iteration, and the evidence under it against the grid's."""
+    from victor_amd.priors import GaussianPrior
+    prior = GaussianPrior("sigma_v", 350.0, sigma=30.0)
+    res["prior"] = {"names": prior.names, "mean": prior.mean.tolist(), "sigma": prior.sigma.tolist()}
+    for name, obj in (("R=1", data_fit), ("R=16", rs)):
+        per_iteration(obj, params, True, blocks=1)
+        per_iteration(obj, params, True, blocks=1, prior=prior)
+        plain, with_prior = [], []
+        for _ in range(5):                                   # alternate: one block of each, five times
+            plain += per_iteration(obj, params, True, blocks=1)
+            with_prior += per_iteration(obj, params, True, blocks=1, prior=prior)
+        res["timing"][name] = {"device_s_per_iteration": float(np.median(plain)), "device_prior_s_per_iteration": float(np.median(with_prior)),
+                               "device_all": plain, "device_prior_all": with_prior}
+        print(name, res["timing"][name], flush=True)
+    res["evidence"]["d3_vs_grid_prior"] = d3_against_the_grid(rs, params, {"beta": 0.4}, prior)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--skip-large", action="store_true", help="leave out R = 1024")
+    ap.add_argument("--prior", action="store_true", help="the measurements under a Gaussian prior on sigma_v instead")
     args = ap.parse_args()
     import victor_amd
     from tests import cases
@@ -47,6 +104,14 @@ def main():
     stack = victor_amd.CCFFit(*stack_options())
     rs = stack.realisations()
     res = {"defaults": {"n_live": 256, "batch": 32, "steps": 16}, "timing": {}, "evidence": {}}
+    if args.prior:
+        under_a_prior(data_fit, rs, params, res)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as fh:
+                json.dump(res, fh, indent=1)
+        print(json.dumps(res["timing"]))
+        return
 
     sizes = [("R=1", data_fit), ("R=16", rs)]
     if not args.skip_large:
@@ -62,27 +127,7 @@ def main():
                                "device_all": dev, "definition_all": ref}
         print(name, res["timing"][name], flush=True)
 
-    # beta fixed, d = 3, every mock: nested sampling against the grid, three seeds (the mocks of a run share their start draw, so
-    # their errors are correlated within a seed)
-    fixed = {"beta": 0.4}
-    res["evidence"]["d3_vs_grid"] = []
-    grid = None
-    for seed in (0, 1, 2):
-        t = time.perf_counter()
-        ns = rs.nested_sampling(params, fixed=fixed, seed=seed)
-        t_ns = time.perf_counter() - t
-        if grid is None:
-            lo = np.maximum(ns._lo, (ns.mean - 6 * ns.sigma).min(axis=0))
-            hi = np.minimum(ns._hi, (ns.mean + 6 * ns.sigma).max(axis=0))
-            grid = rs.grid_posterior(params, bins=32, fixed=fixed, ranges={n: (float(a), float(b)) for n, a, b in zip(ns.names, lo, hi)})
-        pull = (ns.ln_evidence - grid.ln_evidence) / ns.ln_evidence_error
-        res["evidence"]["d3_vs_grid"].append({"seed": seed, "names": ns.names, "n_iter": ns.n_iter, "seconds": t_ns, "status": ns.status_names,
-                                              "nested": ns.ln_evidence.tolist(), "error": ns.ln_evidence_error.tolist(),
-                                              "grid": grid.ln_evidence.tolist(), "edge_mass": np.asarray(grid.edge_mass).tolist(),
-                                              "pull": pull.tolist(), "information": ns.information.tolist(),
-                                              "acceptance": ns.acceptance.tolist(), "n_stuck": ns.n_stuck.tolist()})
-        print("d = 3 against the grid, seed", seed, ": pulls", np.round(pull, 2), "mean", pull.mean(), "rms", np.sqrt(np.mean(pull ** 2)),
-              "mean difference", (ns.ln_evidence - grid.ln_evidence).mean(), flush=True)
+    res["evidence"]["d3_vs_grid"] = d3_against_the_grid(rs, params, {"beta": 0.4})
 
     # d = 4, beta sampled, every mock: against thermodynamic integration
     t = time.perf_counter()

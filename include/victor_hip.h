@@ -993,6 +993,20 @@ int vk_nested_state(vk_nested* h, double* x, double* lnl, double* chi2, int64_t*
 const char* vk_nested_last_error(const vk_nested* h);
 void vk_nested_destroy(vk_nested* h);
 
+/* A Gaussian prior on a nested handle (of any of its three create calls): ln prior = -1/2 (x - mu)^T P (x - mu) of vk_prior.h,
+ * multiplied onto the box.  The run still samples the uniform box; it orders, kills and constrains on lnpost = lnL + ln prior
+ * (one rounded addition): the dead points are the K smallest in (lnpost, index), L* is the lnpost of the last, and a step is
+ * accepted when its proposal lies inside the box and lnL' + lnprior(proposal) > L*.  dead_lnl and live_lnl keep holding lnL.
+ * vk_nprior_set(h, mu, pp): mu [d], pp [d (d + 1) / 2] as vk_chain_set_prior takes them; (NULL, NULL) clears the prior.  The
+ *   live points of a start carry the ln prior they were started under, so an accepted call ends the start: the next call is the
+ *   start of a run, and a begin before it is refused.  Refused (VK_E_ARG, the handle usable and unchanged): a block in flight,
+ *   one pointer NULL, a value that is not finite.
+ * vk_nprior_record(h, n_iter, dead_lnprior, live_lnprior): after the finish of a block of n_iter iterations and before the next
+ *   begin, the block's ln prior record [n_iter][R][K] and the live points' [R][L].  Either may be NULL.  Refused: a handle
+ *   without a prior or without a start, a block in flight, an n_iter that is not the finished block's. */
+int vk_nprior_set(vk_nested* h, const double* mu, const double* pp);
+int vk_nprior_record(vk_nested* h, int32_t n_iter, double* dead_lnprior, double* live_lnprior);
+
 /* Theory multipoles on a caller-supplied s grid: out[n][n_ell][n_s] with the caller's own
  * projection weights w_ell[n_ell][n_mu] on mu[n_mu] (host buffers). */
 int vk_theory_batch(vk_ctx* ctx, const vk_eval_opts* opts, const double* params, int64_t n,

@@ -254,6 +254,9 @@ SYMBOLS = {
     "vk_nested_state": (C.c_int, [_vp, _dp, _dp, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "vk_nested_last_error": (C.c_char_p, [_vp]),
     "vk_nested_destroy": (None, [_vp]),
+    # ... under a Gaussian prior: the prior of a nested handle, and the ln prior of a block's dead record and of the live points
+    "vk_nprior_set": (C.c_int, [_vp, _dp, _dp]),
+    "vk_nprior_record": (C.c_int, [_vp, C.c_int32, _dp, _dp]),
     # likelihood-level beta interpolation (VK_OPT_BETA_BLEND in vk_eval_opts.reserved at a handle's create call): its two kernels alone
     "vk_blend_split": (C.c_int, [C.c_int, _dp, C.c_int32, _dp, C.POINTER(C.c_int32), C.c_int64, _dp, C.POINTER(C.c_int32), _dp,
                                  C.POINTER(C.c_int32)]),

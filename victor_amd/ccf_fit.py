@@ -408,7 +408,7 @@ class CCFFit(CCFModel):
                                     sample, ln_proposal, kwargs, predictive=predictive, tail=tail)
 
     def nested_sampling(self, params, n_live=256, batch=32, steps=16, scale=None, seed=0, fixed=None, tol=1e-3, max_iter=None, n_iter=None,
-                        keep_dead=True, device=True, evaluate=None, **kwargs):
+                        keep_dead=True, device=True, evaluate=None, prior=None, prior_norm="auto", **kwargs):
         """Nested sampling of the fit's data vector over the uniform box of a cobaya ``params`` block: the evidence under the
         normalised prior, in any dimension up to 10, and a weighted posterior sample that depends on no start point - on the GPU
         (``device=True``) or by the NumPy loop that defines the run (``device=False``, over :meth:`log_likelihood_batch`).
@@ -416,7 +416,7 @@ class CCFFit(CCFModel):
         :class:`victor_amd.nested.NestedSampling`."""
         from .nested import nested_sampling
         return nested_sampling(self, params, n_live, batch, steps, scale, seed, fixed, tol, max_iter, n_iter, keep_dead, device,
-                               evaluate, kwargs)
+                               evaluate, kwargs, prior=prior, prior_norm=prior_norm)
 
     def realisations(self, simulation_numbers=None, paired_model=False):
         """Every simulation realisation of this fit's data file (or the listed ``simulation_numbers``) against one model:

@@ -14,9 +14,18 @@
 //   vk_nested_commit_kernel   one thread per walker: the walker into its dead point's slot
 // Between the launches the library evaluates the R K rows (sampled_evaluate).  A thread writes only its own walker, slot or
 // record: no atomics, and every value a kernel indexes with was checked by the host (vk_nested_create) or is a rank < L.
+//
+// Every kernel is a template over its argument struct: NestedArgs (no prior) or NestedPriorArgs, which adds a vkprior::Prior by
+// value (about 0.5 KiB of kernel arguments, read with scalar loads, as the chain kernels read theirs) and the ln prior of the
+// live points, of the walkers and of the dead record.  `if constexpr (Args::kPrior)` keeps the prior's work out of the
+// NestedArgs instantiations altogether: they are the kernels they were.  Under a prior the select kernel's s_lnl holds
+// lnpost = lnL + ln prior (one rounded addition; no further LDS), L* is an lnpost, and the step kernel decides on the sum
+// (the prior forms of vknest::transition / commit).  ln prior is always taken at the point's own sampled values - in a handle
+// that blends in beta, at the point's own beta, never at the split rows' grid beta.
 #pragma once
 #include "vk_common.h"
 #include "vk_nested_step.h"
+#include "vk_prior.h"
 #include "vk_sampled_row.h"
 
 namespace vk {
@@ -26,6 +35,7 @@ constexpr int kNestedSelect = 256;         // ... of the select kernel: four wav
 constexpr int kNestedWaves = kNestedSelect / 64;
 
 struct NestedArgs {
+  static constexpr bool kPrior = false;
   vkchain::Box box;
   int R, L, K;              // problems, live points of each, walkers of each
   double scale;
@@ -61,6 +71,14 @@ struct NestedArgs {
   vkrow::Blocks blocks;
 };
 
+struct NestedPriorArgs : NestedArgs {
+  static constexpr bool kPrior = true;
+  vkprior::Prior prior;
+  double* llp;              // [R L]: ln prior of the live points
+  double* wlp;              // [R K]: ... of the walkers
+  double* dead_lp;          // [R K]: ... of the iteration's dead record
+};
+
 __device__ __forceinline__ vknest::Walker nested_walker(const NestedArgs& a, int c) {
   vknest::Walker w;
   w.stride = (size_t)a.R * a.K;
@@ -71,6 +89,12 @@ __device__ __forceinline__ vknest::Walker nested_walker(const NestedArgs& a, int
   w.n_steps = reinterpret_cast<int64_t*>(a.n_steps + c);
   w.n_stuck = reinterpret_cast<int64_t*>(a.n_stuck + c);
   w.moved = a.wmoved + c;
+  w.lnprior = nullptr;
+  return w;
+}
+__device__ __forceinline__ vknest::Walker nested_walker(const NestedPriorArgs& a, int c) {
+  vknest::Walker w = nested_walker(static_cast<const NestedArgs&>(a), c);
+  w.lnprior = a.wlp + c;
   return w;
 }
 
@@ -86,7 +110,8 @@ __device__ __forceinline__ void nested_emit(const NestedArgs& a, const vknest::W
 }
 
 // the start, pass p: live point p K + k of problem r becomes row r K + k (and, on pass 0, fresh counters)
-__global__ void __launch_bounds__(kNestedBlock) vk_nested_load_kernel(NestedArgs a) {
+template <class Args>
+__global__ void __launch_bounds__(kNestedBlock) vk_nested_load_kernel(Args a) {
   const int c = blockIdx.x * kNestedBlock + threadIdx.x;
   if (c >= a.R * a.K) return;
   const int r = c / a.K, k = c - r * a.K, d = a.box.d;
@@ -103,17 +128,23 @@ __global__ void __launch_bounds__(kNestedBlock) vk_nested_load_kernel(NestedArgs
   }
 }
 
-__global__ void __launch_bounds__(kNestedBlock) vk_nested_adopt_kernel(NestedArgs a) {
+template <class Args>
+__global__ void __launch_bounds__(kNestedBlock) vk_nested_adopt_kernel(Args a) {
   const int c = blockIdx.x * kNestedBlock + threadIdx.x;
   if (c >= a.R * a.K) return;
   const int r = c / a.K, k = c - r * a.K;
   const size_t at = (size_t)r * a.L + (size_t)a.pass * a.K + k;
   a.llnl[at] = vkchain::stored(a.res_lnl[c]);
   a.lchi[at] = a.res_chi2[c];
+  if constexpr (Args::kPrior) {
+    const size_t RL = (size_t)a.R * a.L;
+    a.llp[at] = vkprior::lnprior(a.prior, a.box.d, [&](int j) { return a.lx[j * RL + at]; });
+  }
 }
 
 // one workgroup per problem (blockIdx.x = r)
-__global__ void __launch_bounds__(kNestedSelect) vk_nested_select_kernel(NestedArgs a) {
+template <class Args>
+__global__ void __launch_bounds__(kNestedSelect) vk_nested_select_kernel(Args a) {
   __shared__ double s_lnl[vknest::kMaxLive];
   __shared__ int s_surv[vknest::kMaxLive];                 // the survivors' live indices, increasing
   __shared__ int s_dead[vknest::kMaxLive / 2];             // the live index of dead point k
@@ -122,7 +153,8 @@ __global__ void __launch_bounds__(kNestedSelect) vk_nested_select_kernel(NestedA
   const int r = blockIdx.x, tid = threadIdx.x, L = a.L, K = a.K, d = a.box.d;
   const size_t RL = (size_t)a.R * L, first = (size_t)r * L;
   for (int i = tid; i < L; i += kNestedSelect) {
-    s_lnl[i] = a.llnl[first + i];
+    if constexpr (Args::kPrior) s_lnl[i] = a.llnl[first + i] + a.llp[first + i];      // lnpost: what is ordered and constrained
+    else s_lnl[i] = a.llnl[first + i];
     s_surv[i] = 0;                                         // (every index read below is one of the problem's, whatever lnL holds)
     if (i < K) s_dead[i] = 0;
   }
@@ -178,7 +210,12 @@ __global__ void __launch_bounds__(kNestedSelect) vk_nested_select_kernel(NestedA
   for (int k = tid; k < K; k += kNestedSelect) {
     const int c = r * K + k;
     const int gone = s_dead[k];
-    a.dead_lnl[c] = s_lnl[gone];
+    if constexpr (Args::kPrior) {
+      a.dead_lnl[c] = a.llnl[first + gone];
+      a.dead_lp[c] = a.llp[first + gone];
+    } else {
+      a.dead_lnl[c] = s_lnl[gone];
+    }
     a.dead_chi2[c] = a.lchi[first + gone];
     if (a.dead_x)
       for (int j = 0; j < d; ++j) a.dead_x[(size_t)c * d + j] = a.lx[j * RL + first + gone];
@@ -186,30 +223,41 @@ __global__ void __launch_bounds__(kNestedSelect) vk_nested_select_kernel(NestedA
     if (k == K - 1) a.lstar[r] = s_lnl[gone];
     const int from = s_surv[vknest::pick_of(a.pick[c], L, K)];
     vknest::Walker w = nested_walker(a, c);
-    vknest::start(d, w, [&](int j) { return a.lx[j * RL + first + from]; }, s_lnl[from], a.lchi[first + from]);
+    if constexpr (Args::kPrior) {
+      vknest::start(d, w, [&](int j) { return a.lx[j * RL + first + from]; }, a.llnl[first + from], a.lchi[first + from]);
+      *w.lnprior = a.llp[first + from];
+    } else {
+      vknest::start(d, w, [&](int j) { return a.lx[j * RL + first + from]; }, s_lnl[from], a.lchi[first + from]);
+    }
     nested_emit(a, w, c, [&](int j) { return s_range[j]; }, a.dz + (size_t)c * d);
   }
 }
 
 // one constrained step per walker, then the walker's next row
-__global__ void __launch_bounds__(kNestedBlock) vk_nested_step_kernel(NestedArgs a) {
+template <class Args>
+__global__ void __launch_bounds__(kNestedBlock) vk_nested_step_kernel(Args a) {
   const int c = blockIdx.x * kNestedBlock + threadIdx.x;
   if (c >= a.R * a.K) return;
   const int r = c / a.K, d = a.box.d;
   vknest::Walker w = nested_walker(a, c);
   auto range = [&](int j) { return a.range[(size_t)j * a.R + r]; };
-  vknest::transition(a.box, w, a.scale, range, a.dz + (size_t)c * d, a.lstar[r], a.res_lnl[c], a.res_chi2[c]);
+  if constexpr (Args::kPrior)
+    vknest::transition(a.box, a.prior, w, a.scale, range, a.dz + (size_t)c * d, a.lstar[r], a.res_lnl[c], a.res_chi2[c]);
+  else
+    vknest::transition(a.box, w, a.scale, range, a.dz + (size_t)c * d, a.lstar[r], a.res_lnl[c], a.res_chi2[c]);
   if (a.dz_next) nested_emit(a, w, c, range, a.dz_next + (size_t)c * d);
 }
 
 // the walkers into the slots of their dead points
-__global__ void __launch_bounds__(kNestedBlock) vk_nested_commit_kernel(NestedArgs a) {
+template <class Args>
+__global__ void __launch_bounds__(kNestedBlock) vk_nested_commit_kernel(Args a) {
   const int c = blockIdx.x * kNestedBlock + threadIdx.x;
   if (c >= a.R * a.K) return;
   const int r = c / a.K;
   const size_t at = (size_t)r * a.L + a.wslot[c];
   vknest::Walker w = nested_walker(a, c);
-  vknest::commit(a.box.d, w, a.lx + at, (size_t)a.R * a.L, a.llnl + at, a.lchi + at);
+  if constexpr (Args::kPrior) vknest::commit(a.box.d, w, a.lx + at, (size_t)a.R * a.L, a.llnl + at, a.lchi + at, a.llp + at);
+  else vknest::commit(a.box.d, w, a.lx + at, (size_t)a.R * a.L, a.llnl + at, a.lchi + at);
 }
 
 }  // namespace vk

@@ -21,11 +21,18 @@
 // Bits: the decision arithmetic is two products, one sum and comparisons, the products under `fp contract(off)` (hipcc; the CPU
 // tests build with -ffp-contract=off): hipcc, g++ and NumPy take the same decisions from the same inputs.
 //
+// Under a Gaussian prior (vk_prior.h; the second forms of transition and commit below) the run still samples the uniform box and
+// orders, kills and constrains on lnpost = lnL + ln prior, ONE rounded addition (-inf + finite is -inf): before() and rank_of()
+// are used unchanged on lnpost, L* is the lnpost of dead point K - 1, a walker carries the ln prior of its position beside lnL
+// and chi2, and a step accepts  <=>  inside the box  and  lnL' + lnprior(prop) > L*, ln prior taken at exactly the values
+// proposed() produces and the acceptance stores.
+//
 // Nothing here indexes a local array (ranges and live values are read through callables or strided pointers), so the device
 // code needs no scratch.
 #pragma once
 
 #include "vk_chain_step.h"
+#include "vk_prior.h"
 
 namespace vknest {
 
@@ -45,6 +52,7 @@ struct Walker {
   int64_t* n_steps;
   int64_t* n_stuck;
   int32_t* moved;            // accepted steps of the current iteration
+  double* lnprior;           // ln prior at y (runs under a prior; not read otherwise)
 };
 
 // (la, ia) before (lb, ib) in the total order of live points
@@ -139,12 +147,42 @@ VK_CHAIN_HD inline bool transition(const vkchain::Box& b, Walker& w, double scal
   return accept;
 }
 
+// ... under a prior: the decision is taken on lnL' + ln prior at the proposal, one rounded addition
+template <class Range>
+VK_CHAIN_HD inline bool transition(const vkchain::Box& b, const vkprior::Prior& prior, Walker& w, double scale, Range range,
+                                   const double* dz, double lstar, double lnl_row, double chi2_row) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const bool in = proposal_inside(b, w, scale, range, dz);
+  const double lnl_prop = in ? lnl_row : vkchain::neg_inf();
+  const double lp = vkprior::lnprior(prior, b.d, [&](int j) { return proposed(w.y[j * w.stride], scale, range(j), dz[j]); });
+  const double post = lnl_prop + lp;
+  const bool accept = in && post > lstar;                  // strict; false for a NaN
+  if (accept) {
+    for (int j = 0; j < b.d; ++j) w.y[j * w.stride] = proposed(w.y[j * w.stride], scale, range(j), dz[j]);
+    *w.lnl = lnl_prop;
+    *w.chi2 = chi2_row;
+    *w.lnprior = lp;
+    *w.n_accept += 1;
+    *w.moved += 1;
+  }
+  *w.n_steps += 1;
+  return accept;
+}
+
 // after step S: the walker replaces its dead point.  x: the slot's first element in the live points' storage, live_stride apart
 VK_CHAIN_HD inline void commit(int d, Walker& w, double* x, size_t live_stride, double* lnl, double* chi2) {
   for (int j = 0; j < d; ++j) x[j * live_stride] = w.y[j * w.stride];
   *lnl = *w.lnl;
   *chi2 = *w.chi2;
   if (*w.moved == 0) *w.n_stuck += 1;
+}
+
+// ... under a prior: its ln prior goes into the slot with the rest
+VK_CHAIN_HD inline void commit(int d, Walker& w, double* x, size_t live_stride, double* lnl, double* chi2, double* lnprior) {
+  commit(d, w, x, live_stride, lnl, chi2);
+  *lnprior = *w.lnprior;
 }
 
 }  // namespace vknest

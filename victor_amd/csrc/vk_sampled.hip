@@ -2768,9 +2768,11 @@ struct __attribute__((visibility("hidden"))) vk_nested : Sampled {
   bool started = false;
   int in_flight = 0;                       // iterations of the block begun and not finished
   long long done = 0;                      // iterations finished since vk_nested_start
+  int last_n = 0;                          // iterations of the block finished last (vk_nprior_record)
   double *d_lx = nullptr, *d_llnl = nullptr, *d_lchi = nullptr, *d_wx = nullptr, *d_wlnl = nullptr, *d_wchi = nullptr;
   double *d_lstar = nullptr, *d_range = nullptr, *d_x0 = nullptr, *d_res_lnl = nullptr, *d_res_chi = nullptr;
   double *d_pick = nullptr, *d_dz = nullptr, *d_dlnl = nullptr, *d_dchi = nullptr, *d_dx = nullptr;
+  double *d_llp = nullptr, *d_wlp = nullptr, *d_dlp = nullptr;     // ln prior of the live points, the walkers, a block's dead record
   long long *d_acc = nullptr, *d_steps = nullptr, *d_stuck = nullptr;
   int *d_wslot = nullptr, *d_wmoved = nullptr;
 
@@ -2785,7 +2787,8 @@ struct __attribute__((visibility("hidden"))) vk_nested : Sampled {
     }
   }
   // live points | walkers | L*, ranges | base, start, rows, results, theory workspace | one block of random numbers | one block of
-  // dead record | counters | indices
+  // dead record | ln prior of live points, walkers and the block's dead record (vk_nprior_set may come any time before a start)
+  // | counters | indices
   void layout(Carve& c) {
     const size_t n = RK, live = (size_t)R * L, block = (size_t)vknest::kBlock * n;
     blend_layout(c);
@@ -2808,6 +2811,9 @@ struct __attribute__((visibility("hidden"))) vk_nested : Sampled {
     c.take(d_dlnl, block);
     c.take(d_dchi, block);
     c.take(d_dx, block * P);
+    c.take(d_llp, live);
+    c.take(d_wlp, n);
+    c.take(d_dlp, block);
     c.take(d_acc, n);
     c.take(d_steps, n);
     c.take(d_stuck, n);
@@ -2849,6 +2855,55 @@ static NestedArgs nested_args(const vk_nested* f) {
   a.alpha = f->alpha;
   a.blocks = f->row_sets((size_t)f->RK);
   return a;
+}
+
+static NestedPriorArgs nested_prior_args(const vk_nested* f) {
+  NestedPriorArgs a{};
+  static_cast<NestedArgs&>(a) = nested_args(f);
+  a.prior = f->prior;
+  a.llp = f->d_llp;
+  a.wlp = f->d_wlp;
+  return a;
+}
+
+// the L / K passes of vk_nested_start, enqueued (Args: NestedArgs, or NestedPriorArgs of a handle under a prior)
+template <class Args>
+static int nested_enqueue_start(vk_nested* f, Args a) {
+  int rc = VK_OK;
+  for (int p = 0; p < f->L / f->K && rc == VK_OK; ++p) {
+    a.pass = p;
+    rc = sampled_launch(f, vk_nested_load_kernel, f->RK, kNestedBlock, a);
+    if (rc == VK_OK) rc = sampled_evaluate(f, f->RK, f->d_res_lnl, f->d_res_chi);
+    if (rc == VK_OK) rc = sampled_launch(f, vk_nested_adopt_kernel, f->RK, kNestedBlock, a);
+  }
+  return rc;
+}
+
+// the n_iter iterations of vk_nested_begin, enqueued; dead_lp(a, t): where iteration t's ln prior record goes (a prior's Args)
+template <class Args, class DeadLp>
+static int nested_enqueue_block(vk_nested* f, Args a, int n_iter, int keep_dead, DeadLp dead_lp) {
+  const size_t n = f->RK, P = f->P, S = f->S;
+  int rc = VK_OK;
+  for (int t = 0; t < n_iter && rc == VK_OK; ++t) {
+    const double* dz_t = f->d_dz + (size_t)t * S * n * P;
+    a.pick = f->d_pick + (size_t)t * n;
+    a.dz = dz_t;
+    a.dz_next = nullptr;
+    a.dead_lnl = f->d_dlnl + (size_t)t * n;
+    a.dead_chi2 = f->d_dchi + (size_t)t * n;
+    a.dead_x = keep_dead ? f->d_dx + (size_t)t * n * P : nullptr;
+    dead_lp(a, t);
+    rc = sampled_launch(f, vk_nested_select_kernel, (long long)f->R * kNestedSelect, kNestedSelect, a);
+    for (size_t s = 0; s < S && rc == VK_OK; ++s) {
+      rc = sampled_evaluate(f, f->RK, f->d_res_lnl, f->d_res_chi);
+      if (rc) break;
+      a.dz = dz_t + s * n * P;
+      a.dz_next = s + 1 < S ? a.dz + n * P : nullptr;
+      rc = sampled_launch(f, vk_nested_step_kernel, f->RK, kNestedBlock, a);
+    }
+    if (rc == VK_OK) rc = sampled_launch(f, vk_nested_commit_kernel, f->RK, kNestedBlock, a);
+  }
+  return rc;
 }
 
 // vk_nested_create and its joint forms: the shape is checked before the shared create call, which lays the handle out from it
@@ -2931,17 +2986,12 @@ int vk_nested_start(vk_nested* f, const double* x0) {
   VK_SAMPLED_HIP(f, hipSetDevice(f->ctx->device));
   VK_SAMPLED_HIP(f, hipMemcpy(f->d_x0, x0, live * f->P * sizeof(double), hipMemcpyHostToDevice));
   f->started = false;
-  NestedArgs a = nested_args(f);
-  for (int p = 0; p < f->L / f->K && rc == VK_OK; ++p) {
-    a.pass = p;
-    rc = sampled_launch(f, vk_nested_load_kernel, f->RK, kNestedBlock, a);
-    if (rc == VK_OK) rc = sampled_evaluate(f, f->RK, f->d_res_lnl, f->d_res_chi);
-    if (rc == VK_OK) rc = sampled_launch(f, vk_nested_adopt_kernel, f->RK, kNestedBlock, a);
-  }
+  rc = f->prior.on ? nested_enqueue_start(f, nested_prior_args(f)) : nested_enqueue_start(f, nested_args(f));
   if (rc) return sampled_abort(f, rc);
   VK_SAMPLED_HIP(f, hipStreamSynchronize(f->ctx->stream));
   f->started = true;
   f->done = 0;
+  f->last_n = 0;
   f->err.clear();
   return VK_OK;
 }
@@ -2963,25 +3013,9 @@ int vk_nested_begin(vk_nested* f, int32_t n_iter, const double* pick, const doub
   // the stream is idle (the block before was finished): plain copies, complete on return
   VK_SAMPLED_HIP(f, hipMemcpy(f->d_pick, pick, (size_t)n_iter * n * sizeof(double), hipMemcpyHostToDevice));
   VK_SAMPLED_HIP(f, hipMemcpy(f->d_dz, dz, (size_t)n_iter * S * n * P * sizeof(double), hipMemcpyHostToDevice));
-  NestedArgs a = nested_args(f);
-  for (int t = 0; t < n_iter && rc == VK_OK; ++t) {
-    const double* dz_t = f->d_dz + (size_t)t * S * n * P;
-    a.pick = f->d_pick + (size_t)t * n;
-    a.dz = dz_t;
-    a.dz_next = nullptr;
-    a.dead_lnl = f->d_dlnl + (size_t)t * n;
-    a.dead_chi2 = f->d_dchi + (size_t)t * n;
-    a.dead_x = keep_dead ? f->d_dx + (size_t)t * n * P : nullptr;
-    rc = sampled_launch(f, vk_nested_select_kernel, (long long)f->R * kNestedSelect, kNestedSelect, a);
-    for (size_t s = 0; s < S && rc == VK_OK; ++s) {
-      rc = sampled_evaluate(f, f->RK, f->d_res_lnl, f->d_res_chi);
-      if (rc) break;
-      a.dz = dz_t + s * n * P;
-      a.dz_next = s + 1 < S ? a.dz + n * P : nullptr;
-      rc = sampled_launch(f, vk_nested_step_kernel, f->RK, kNestedBlock, a);
-    }
-    if (rc == VK_OK) rc = sampled_launch(f, vk_nested_commit_kernel, f->RK, kNestedBlock, a);
-  }
+  rc = f->prior.on ? nested_enqueue_block(f, nested_prior_args(f), n_iter, keep_dead,
+                                          [&](NestedPriorArgs& a, int t) { a.dead_lp = f->d_dlp + (size_t)t * n; })
+                   : nested_enqueue_block(f, nested_args(f), n_iter, keep_dead, [](NestedArgs&, int) {});
   if (rc) return sampled_abort(f, rc);
   f->in_flight = n_iter;
   f->err.clear();
@@ -2999,6 +3033,7 @@ int vk_nested_finish(vk_nested* f, double* dead_lnl, double* dead_chi2, double* 
                           {live_lnl, f->d_llnl, (size_t)f->R * f->L * one}}, true);
   hipError_t e = hipStreamSynchronize(f->ctx->stream);
   f->done += f->in_flight;
+  f->last_n = f->in_flight;
   f->in_flight = 0;
   if (rc != VK_OK || e != hipSuccess) {
     (void)hipGetLastError();
@@ -3034,6 +3069,37 @@ int vk_nested_state(vk_nested* f, double* x, double* lnl, double* chi2, int64_t*
       out[q][r] = sum;
     }
   }
+  f->err.clear();
+  return VK_OK;
+}
+
+// A Gaussian prior (vk_prior.h) on a nested handle of any of the three create calls: mu [d], pp [d (d + 1) / 2] as
+// vk_chain_set_prior takes them; NULL, NULL clears it.  The live points of a start carry the ln prior of the prior they were
+// started under, so a change of prior ends the start: the next call is vk_nested_start.
+int vk_nprior_set(vk_nested* f, const double* mu, const double* pp) {
+  if (!f) return VK_E_ARG;
+  if (f->in_flight) return refused(f, "vk_nprior_set: a block begun with vk_nested_begin is awaiting vk_nested_finish");
+  const int rc = sampled_set_prior(f, "vk_nprior_set", mu, pp);
+  if (rc == VK_OK) {
+    f->started = false;
+    f->last_n = 0;
+  }
+  return rc;
+}
+
+// dead_lnprior [n_iter][R][K] of the block finished last (n_iter: its length) and live_lnprior [R][L] behind it; either may be NULL
+int vk_nprior_record(vk_nested* f, int32_t n_iter, double* dead_lnprior, double* live_lnprior) {
+  if (!f) return VK_E_ARG;
+  const std::string me = "vk_nprior_record: ";
+  if (!f->prior.on) return refused(f, me + "the handle has no prior (vk_nprior_set)");
+  if (f->in_flight) return refused(f, me + "a block begun with vk_nested_begin is awaiting vk_nested_finish");
+  if (!f->started) return refused(f, me + "the live points have no start (vk_nested_start)");
+  if (dead_lnprior && n_iter != f->last_n)
+    return refused(f, me + "the block finished last had " + std::to_string(f->last_n) + " iterations, not " + std::to_string(n_iter));
+  VK_SAMPLED_HIP(f, hipSetDevice(f->ctx->device));
+  const int rc = sampled_home(f, {{dead_lnprior, f->d_dlp, (size_t)f->last_n * f->RK * sizeof(double)},
+                                  {live_lnprior, f->d_llp, (size_t)f->R * f->L * sizeof(double)}});
+  if (rc) return rc;
   f->err.clear();
   return VK_OK;
 }

@@ -555,13 +555,13 @@ class JointFit:
                              autocorr=autocorr, temper=temper, predictive=predictive)
 
     def nested_sampling(self, params, n_live=256, batch=32, steps=16, scale=None, seed=0, fixed=None, tol=1e-3, max_iter=None, n_iter=None,
-                        keep_dead=True, device=True, evaluate=None, **kwargs):
+                        keep_dead=True, device=True, evaluate=None, prior=None, prior_norm="auto", **kwargs):
         """Nested sampling of the joint lnL - one parameter vector for all blocks, or with ``"name@q"`` entries a value per
         block, at most 10 sampled values in all -, block-diagonal or under the joint covariance.  Arguments and result as
         ``CCFFit.nested_sampling`` (:mod:`victor_amd.nested`); the result keeps this joint fit alive."""
         from .nested import nested_sampling
         return nested_sampling(self, params, n_live, batch, steps, scale, seed, fixed, tol, max_iter, n_iter, keep_dead, device,
-                               evaluate, kwargs)
+                               evaluate, kwargs, prior=prior, prior_norm=prior_norm)
 
     @property
     def n_data(self):
@@ -639,12 +639,12 @@ class JointRealisations:
                              autocorr=autocorr, temper=temper, predictive=predictive)
 
     def nested_sampling(self, params, n_live=256, batch=32, steps=16, scale=None, seed=0, fixed=None, tol=1e-3, max_iter=None, n_iter=None,
-                        keep_dead=True, device=True, evaluate=None, **kwargs):
+                        keep_dead=True, device=True, evaluate=None, prior=None, prior_norm="auto", **kwargs):
         """Nested sampling of EVERY joint realisation in lock step: one evidence and one posterior sample per joint mock.
         Arguments and result as ``Realisations.nested_sampling``."""
         from .nested import nested_sampling
         return nested_sampling(self.joint, params, n_live, batch, steps, scale, seed, fixed, tol, max_iter, n_iter, keep_dead, device,
-                               evaluate, kwargs, realisations=self)
+                               evaluate, kwargs, realisations=self, prior=prior, prior_norm=prior_norm)
 
     def importance_posterior(self, params, proposal=None, n=16384, seed=0, fixed=None, prior=None, bins=64, ranges=None, pairs=None,
                              chunk=None, min_ess=50.0, device=True, evaluate=None, sample=None, ln_proposal=None, **kwargs):

@@ -37,6 +37,24 @@ pass p is live point ``p K + k`` of problem r.  Every launch of a run has exactl
 ``ln w + lnL``, ``information`` the Kullback-Leibler divergence H of the posterior from the prior, and ``ln_evidence_error =
 sqrt(H / L)`` (Skilling 2006).
 
+**Under a Gaussian prior** (``prior=``, :mod:`victor_amd.priors`) the run samples the uniform box as before - the start points are
+the same bytes - and orders, kills and constrains on ``lnpost = lnL + lnprior``: ``lnprior`` is ``ResolvedPrior.lnprior`` at the
+point's own sampled values and lnpost ONE rounded addition (``-inf + finite`` is ``-inf``; a NaN lnL is stored as -inf first).
+Rule 2: the K live points smallest in (lnpost, index) die and ``L*`` is the lnpost of dead point K - 1; the dead record gains
+``dead_lnprior`` while ``dead_lnl`` and ``dead_chi2`` keep holding lnL and chi2.  Rule 3: a walker takes its survivor's x, lnL,
+chi2 and lnprior.  Rule 4: accept when the proposal is inside the box and ``lnL' + lnprior(prop) > L*`` - strict, a NaN rejects -,
+lnprior taken at exactly the values the proposal arithmetic produces and rule 5 commits.  Rule 5: the walker's lnprior goes into
+the slot with the rest.  The random-number protocol does not change.  In the read-out lnpost takes the place of lnL - terms,
+stop, weights, moments, ``NO_FINITE`` -, the log-sum is ``ln_evidence_unnormalised = ln((1 / V) integral_box L exp(lnprior))``
+and ``information`` is the divergence of the posterior from the UNIFORM BOX, which is what sets the shrinkage error.  The
+prior's normalisation ``ln_prior_norm = ln((1 / V) integral_box exp(lnprior))``, the same for every problem, is the closed form
+of independent priors (``prior_norm="exact"``, error 0; :func:`exact_prior_norm`) or the prior's own problem run through this
+same loop on the host (``"nested"``: R = 1, lnL = 0, the call's ``n_live``, ``batch``, ``steps``, ``scale``, ``tol`` and
+``max_iter``, the generators ``[seed, 3]``, ``[seed, 4]``, ``[seed, 5]`` in the roles of ``[seed, 0 .. 2]``, no theory evaluation;
+:func:`nested_prior_norm`; ``extend`` does not run it again); ``"auto"`` takes the closed form where there is one.  Then
+``ln_evidence = ln_evidence_unnormalised - ln_prior_norm`` and ``ln_evidence_error = sqrt(H / L + ln_prior_norm_error^2)``.
+Without a prior nothing changes, not a byte: the new attributes are None and ``ln_evidence_unnormalised`` is ``ln_evidence``.
+
 **Stop.**  Blocks of at most 8 iterations are enqueued without synchronisation; after each the dead record and the live lnL come
 home.  At every multiple of 8 iterations (over the life of the run) the run ends when every problem has
 ``ln(Z_live / (Z_dead + Z_live)) < ln(tol)``, or at ``max_iter``; ``n_iter=`` runs a fixed count instead.  Nothing depends on how a
@@ -49,6 +67,7 @@ closest one was.
 """
 
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -88,11 +107,20 @@ def log_weights(ln_x, n_live):
     return ln_w, end - np.log(_ld(n_live))
 
 
-def read_out(dead_lnl, live_lnl, n_live, batch, ln_x=None):
+def read_out(dead_lnl, live_lnl, n_live, batch, ln_x=None, dead_lnprior=None, live_lnprior=None):
     """The evidence of R problems from their dead record ``dead_lnl`` (T, R, K) and final live ``live_lnl`` (R, L), in extended
     precision: dict of ``ln_evidence``, ``information``, ``ln_evidence_error`` (R,), ``log_weights`` (R, T K + L: the dead points
     in order, then the live points; normalised, -inf where lnL is), ``ln_z_dead``, ``ln_z_live`` (R,) and ``no_finite`` (R,).
-    ``ln_x`` (T K,) or (R, T K): the shrinkage to use instead of the expected one."""
+    ``ln_x`` (T K,) or (R, T K): the shrinkage to use instead of the expected one.
+
+    With ``dead_lnprior`` (T, R, K) and ``live_lnprior`` (R, L) - a run under a Gaussian prior - lnpost = lnL + ln prior (one
+    rounded float64 addition, the run's own) takes the place of lnL everywhere: ``ln_evidence`` is then the UNNORMALISED
+    ln((1 / V) integral over the box of L exp(ln prior)), ``no_finite`` says that no lnpost was finite, and ``information`` is
+    the Kullback-Leibler divergence of the posterior from the UNIFORM BOX - the prior the run samples and compresses, hence what
+    sets the shrinkage error ``sqrt(H / L)`` -, not from the Gaussian prior."""
+    if dead_lnprior is not None:
+        dead_lnl = np.asarray(dead_lnl, dtype=float) + np.asarray(dead_lnprior, dtype=float)
+        live_lnl = np.asarray(live_lnl, dtype=float) + np.asarray(live_lnprior, dtype=float)
     dead = np.asarray(dead_lnl, dtype=_ld)
     T, R, K = dead.shape
     L = int(n_live)
@@ -130,9 +158,15 @@ class NestedSampling:
     order, then the live points -, ``weights`` (R, n) normalised, ``mean`` (R, d), ``cov`` (R, d, d), ``sigma`` (R, d).
     Diagnostic of the definition route only (None on the device route): ``decision_margin``, the smallest ``|lnL' - L*|`` over the
     decisions taken inside the box with a finite difference and the smallest gap between two unequal neighbours among the K + 1
-    lowest live lnL of an iteration (equal values are copies of one evaluation and stay equal).  :meth:`extend` continues the same runs."""
+    lowest live lnL of an iteration (equal values are copies of one evaluation and stay equal).  :meth:`extend` continues the same runs.
 
-    def __init__(self, names, lo, hi, fixed, R, n_live, batch, steps, scale, seed, tol, keep_dead, evaluator, device_handle, which):
+    Under a prior (None otherwise): ``prior`` (the :class:`victor_amd.priors.ResolvedPrior`), ``dead_lnprior`` (n_iter, R, K),
+    ``lnprior`` (R, L), ``ln_prior_norm``, ``ln_prior_norm_error`` (floats), ``prior_norm`` ("exact" or "nested");
+    ``ln_evidence_unnormalised`` (R,) is the log-sum before the normalisation (without a prior: ``ln_evidence`` itself),
+    ``information`` the divergence from the uniform box, and the margins, the stop and the weights are those of lnL + ln prior."""
+
+    def __init__(self, names, lo, hi, fixed, R, n_live, batch, steps, scale, seed, tol, keep_dead, evaluator, device_handle, which,
+                 prior=None, streams=(0, 1, 2)):
         self.names = list(names)
         self.fixed = fixed
         self._lo, self._hi = np.asarray(lo, dtype=float), np.asarray(hi, dtype=float)
@@ -140,19 +174,23 @@ class NestedSampling:
         self.seed, self.tol, self.keep_dead = seed, float(tol), bool(keep_dead)
         self._evaluate, self._dev, self._which = evaluator, device_handle, which
         self._refresh = self._fit = None
-        self._rng_pick, self._rng_dz = np.random.default_rng([seed, 1]), np.random.default_rng([seed, 2])
+        self.prior = prior                                   # a ResolvedPrior, or None
+        self._streams = tuple(streams)                       # the generators [seed, i] of the start, the picks, the increments
+        self._rng_pick, self._rng_dz = np.random.default_rng([seed, streams[1]]), np.random.default_rng([seed, streams[2]])
         self._block, self._at = None, BLOCK
         self._cut = BLOCK                                    # iterations per call of the device route (tests cut runs differently)
         self.n_iter = 0
         self._dead = ([], [], [])
-        self._live_lnl = None
+        self._dead_lp = []                                   # the dead record's ln prior (under a prior)
+        self._live_lnl = self._live_lp = None
+        self.ln_prior_norm = self.ln_prior_norm_error = self.prior_norm = None
         self.decision_margin = None
         self._trace = None                                   # a list: the definition route appends every iteration's steps to it
 
     # ------------------------------------------------------------------ random numbers ------------------------------------
     def start_points(self):
         """(R, L, d): one draw of the prior for every problem."""
-        u = np.random.default_rng([self.seed, 0]).random((self.n_live, len(self.names)))
+        u = np.random.default_rng([self.seed, self._streams[0]]).random((self.n_live, len(self.names)))
         x = self._lo + u * (self._hi - self._lo)
         x = np.minimum(np.maximum(x, self._lo), self._hi)    # (lo + u (hi - lo) may round past hi by an ulp)
         return np.ascontiguousarray(np.broadcast_to(x, (self.R,) + x.shape))
@@ -184,20 +222,28 @@ class NestedSampling:
         self._n_accept, self._n_steps, self._n_stuck = (np.zeros(R, dtype=np.int64) for _ in range(3))
         self.decision_margin = np.inf
         self._live_lnl = self._lnl
+        if self.prior is not None:
+            self._lnprior = self.prior.lnprior(x0)
+            self._live_lp = self._lnprior
 
     def _iterate_host(self, pick, dz):
         """One iteration of every problem: ``pick`` (R, K), ``dz`` (S, R, K, d).  Returns the dead record (lnl, chi2, x)."""
         R, L, K, S = self.R, self.n_live, self.batch, self.steps
         lo, hi = self._lo, self._hi
         x, lnl, chi2 = self._x, self._lnl, self._chi2
+        prior = self.prior
+        lp = self._lnprior if prior is not None else None
+        key = lnl if prior is None else lnl + lp                                  # lnpost: one rounded addition
         rows_of = np.arange(R)[:, None]
         span = x.max(axis=1) - x.min(axis=1)                                      # (R, d)
-        order = np.argsort(lnl, axis=1, kind="stable")                           # (lnL, index): ties go to the smaller index
+        order = np.argsort(key, axis=1, kind="stable")                           # (lnL, index): ties go to the smaller index
         dead = order[:, :K]
-        lstar = lnl[np.arange(R), dead[:, K - 1]]
+        lstar = key[np.arange(R), dead[:, K - 1]]
         record = (lnl[rows_of, dead].copy(), chi2[rows_of, dead].copy(), x[rows_of, dead].copy())
+        if prior is not None:
+            self._dead_lp.append(lp[rows_of, dead].copy()[None])
         with np.errstate(invalid="ignore"):                                        # how close the order of the dead points was
-            gaps = np.diff(lnl[rows_of, order[:, :K + 1]], axis=1)
+            gaps = np.diff(key[rows_of, order[:, :K + 1]], axis=1)
         gaps = gaps[np.isfinite(gaps) & (gaps > 0)]
         if gaps.size:
             self.decision_margin = min(self.decision_margin, float(gaps.min()))
@@ -205,6 +251,7 @@ class NestedSampling:
         q = np.minimum(np.floor(pick * float(L - K)).astype(np.int64), L - K - 1)
         src = survivors[rows_of, q]
         y, yl, yc = x[rows_of, src].copy(), lnl[rows_of, src].copy(), chi2[rows_of, src].copy()
+        ylp = lp[rows_of, src].copy() if prior is not None else None
         moved = np.zeros((R, K), dtype=np.int64)
         width = (self.scale * span)[:, None, :]
         trace = None if self._trace is None else {"dead": dead.copy(), "lstar": lstar.copy(), "range": span.copy(), "from": src.copy(), "steps": []}
@@ -215,22 +262,31 @@ class NestedSampling:
             lnl_p, chi2_p = self._evaluate(rows.reshape(R * K, -1), self._which)
             lnl_p = np.where(inside, np.asarray(lnl_p, dtype=float).reshape(R, K), -np.inf)
             chi2_p = np.asarray(chi2_p, dtype=float).reshape(R, K)
+            if prior is not None:
+                lp_p = prior.lnprior(prop)                                         # at the proposal, the values an acceptance stores
             with np.errstate(invalid="ignore"):
-                accept = inside & (lnl_p > lstar[:, None])                        # NaN: False
-                margin = np.abs(lnl_p - lstar[:, None])[inside]
+                key_p = lnl_p if prior is None else lnl_p + lp_p
+                accept = inside & (key_p > lstar[:, None])                        # NaN: False
+                margin = np.abs(key_p - lstar[:, None])[inside]
             margin = margin[np.isfinite(margin)]
             if margin.size:
                 self.decision_margin = min(self.decision_margin, float(margin.min()))
             y[accept], yl[accept], yc[accept] = prop[accept], lnl_p[accept], chi2_p[accept]
+            if prior is not None:
+                ylp[accept] = lp_p[accept]
             moved += accept
             if trace is not None:
-                trace["steps"].append((accept.copy(), y.copy(), yl.copy(), yc.copy(), inside.copy()))
+                trace["steps"].append((accept.copy(), y.copy(), yl.copy(), yc.copy(), inside.copy()) + (() if prior is None else (ylp.copy(),)))
         x[rows_of, dead], lnl[rows_of, dead], chi2[rows_of, dead] = y, yl, yc
+        if prior is not None:
+            lp[rows_of, dead] = ylp
         self._n_accept += moved.sum(axis=1)
         self._n_steps += S * K
         self._n_stuck += (moved == 0).sum(axis=1)
         if trace is not None:
             trace.update(x=x.copy(), lnl=lnl.copy(), chi2=chi2.copy())
+            if prior is not None:
+                trace.update(lnprior=lp.copy())
             self._trace.append(trace)
         return record
 
@@ -272,6 +328,11 @@ class NestedSampling:
             for store, a in zip(self._dead, (dl, dc, dx) if self.keep_dead else (dl, dc)):
                 store.append(a)
             self._live_lnl = live
+            if self.prior is not None:
+                dp, live_lp = np.empty((m, R, K)), np.empty((R, L))
+                self._check(lib.vk_nprior_record(h, m, N.as_dp(dp), N.as_dp(live_lp)), "vk_nprior_record")
+                self._dead_lp.append(dp)
+                self._live_lp = live_lp
             self.n_iter += m
             done += m
 
@@ -286,6 +347,10 @@ class NestedSampling:
         self._check(lib.vk_nested_state(h, N.as_dp(self._x), N.as_dp(self._lnl), N.as_dp(self._chi2), i64(self._n_accept),
                                         i64(self._n_steps), i64(self._n_stuck)), "vk_nested_state")
         self._live_lnl = self._lnl
+        if self.prior is not None:
+            self._lnprior = np.empty((R, L))
+            self._check(lib.vk_nprior_record(h, 0, None, N.as_dp(self._lnprior)), "vk_nprior_record")
+            self._live_lp = self._lnprior
 
     def __del__(self):
         dev = getattr(self, "_dev", None)
@@ -307,9 +372,18 @@ class NestedSampling:
             out.append(store[0] if store else np.empty(shapes[i]))
         return out
 
+    def _dead_lnprior(self):
+        """(n_iter, R, K): the dead record's ln prior; None without a prior."""
+        if self.prior is None:
+            return None
+        if len(self._dead_lp) > 1:
+            self._dead_lp[:] = [np.concatenate(self._dead_lp)]
+        return self._dead_lp[0] if self._dead_lp else np.empty((0, self.R, self.batch))
+
     def _remaining(self):
         """``ln(Z_live / (Z_dead + Z_live))`` (R,) of the runs as they stand (NaN for a problem without a finite lnL)."""
-        ro = read_out(self._dead_arrays()[0], self._live_lnl, self.n_live, self.batch)
+        ro = read_out(self._dead_arrays()[0], self._live_lnl, self.n_live, self.batch, dead_lnprior=self._dead_lnprior(),
+                      live_lnprior=self._live_lp)
         with np.errstate(invalid="ignore"):
             return (ro["ln_z_live"] - np.logaddexp(ro["ln_z_dead"], ro["ln_z_live"])).astype(float)
 
@@ -352,8 +426,14 @@ class NestedSampling:
         self.x, self.lnl, self.chi2 = self._x.copy(), self._lnl.copy(), self._chi2.copy()
         self.n_accept, self.n_steps, self.n_stuck = self._n_accept.copy(), self._n_steps.copy(), self._n_stuck.copy()
         self.acceptance = self.n_accept / np.maximum(1, self.n_steps)
-        ro = read_out(self.dead_lnl, self.lnl, L, K)
+        self.dead_lnprior = self._dead_lnprior()
+        self.lnprior = None if self.prior is None else self._lnprior.copy()
+        ro = read_out(self.dead_lnl, self.lnl, L, K, dead_lnprior=self.dead_lnprior, live_lnprior=self.lnprior)
         self.ln_evidence, self.information, self.ln_evidence_error = ro["ln_evidence"], ro["information"], ro["ln_evidence_error"]
+        self.ln_evidence_unnormalised = self.ln_evidence
+        if self.prior is not None:
+            self.ln_evidence = self.ln_evidence_unnormalised - self.ln_prior_norm
+            self.ln_evidence_error = np.sqrt(ro["information"] / L + self.ln_prior_norm_error ** 2)
         with np.errstate(invalid="ignore"):
             self.remaining = (ro["ln_z_live"] - np.logaddexp(ro["ln_z_dead"], ro["ln_z_live"])).astype(float)
             done = self.remaining < np.log(self.tol)
@@ -384,7 +464,10 @@ class NestedSampling:
         live = _ld(self.n_live) - np.tile(np.arange(K), T).astype(_ld)
         for i in range(int(n)):
             ln_t = np.log(rng.random((R, T * K))).astype(_ld) / live
-            out[i] = read_out(self.dead_lnl, self.lnl, self.n_live, K, ln_x=np.cumsum(ln_t, axis=1))["ln_evidence"]
+            out[i] = read_out(self.dead_lnl, self.lnl, self.n_live, K, ln_x=np.cumsum(ln_t, axis=1), dead_lnprior=self.dead_lnprior,
+                              live_lnprior=self.lnprior)["ln_evidence"]
+        if self.prior is not None:
+            out -= self.ln_prior_norm
         return out
 
     def equal_weight_samples(self, n, seed=0):
@@ -401,8 +484,41 @@ class NestedSampling:
         return out
 
 
+def exact_prior_norm(prior, lo, hi):
+    """``ln((1 / V) integral over the box of exp(ln prior))`` of a :class:`victor_amd.priors.ResolvedPrior` whose priors are all
+    independent (``sigma=`` or a diagonal ``cov``): the sum over the named parameters of
+    ``ln(sigma sqrt(pi / 2) [erf((hi - mu) / (sigma sqrt 2)) - erf((lo - mu) / (sigma sqrt 2))] / (hi - lo))``.  None for a
+    correlated prior."""
+    if prior.sigma is None:
+        return None
+    total = 0.0
+    for j in range(prior.d):
+        sg = float(prior.sigma[j])
+        if math.isnan(sg):                                   # (no prior names this parameter: its factor is 1)
+            continue
+        mu, a, b = float(prior.mu[j]), float(lo[j]), float(hi[j])
+        total += math.log(sg * math.sqrt(math.pi / 2.0) * (math.erf((b - mu) / (sg * math.sqrt(2.0))) - math.erf((a - mu) / (sg * math.sqrt(2.0))))
+                          / (b - a))
+    return total
+
+
+def nested_prior_norm(prior, names, lo, hi, n_live, batch, steps, scale, seed, tol, max_iter):
+    """(value, error) of the prior's normalisation over the box by the route's own method: the definition loop on the prior's own
+    problem - R = 1, lnL = 0 - with the generators ``[seed, 3]``, ``[seed, 4]``, ``[seed, 5]`` in the roles of ``[seed, 0 .. 2]``.
+    On the host, without a theory evaluation."""
+    def zero(x, rows_which=None):
+        z = np.zeros(len(x))
+        return z, z.copy()
+    ns = NestedSampling(names, lo, hi, {}, 1, n_live, batch, steps, scale, seed, tol, False, zero, None, None, prior=prior, streams=(3, 4, 5))
+    ns.ln_prior_norm = ns.ln_prior_norm_error = 0.0          # (the prior's own problem: its evidence IS the normalisation)
+    ns._start_host(ns.start_points())
+    ns.run(max_iter)
+    return float(ns.ln_evidence_unnormalised[0]), float(np.sqrt(ns.information[0] / n_live))
+
+
 def nested_sampling(fit, params, n_live=DEFAULT_LIVE, batch=DEFAULT_BATCH, steps=DEFAULT_STEPS, scale=None, seed=0, fixed=None,
-                    tol=1e-3, max_iter=None, n_iter=None, keep_dead=True, device=True, evaluate=None, kwargs=None, realisations=None):
+                    tol=1e-3, max_iter=None, n_iter=None, keep_dead=True, device=True, evaluate=None, kwargs=None, realisations=None,
+                    prior=None, prior_norm="auto"):
     """The work of the ``nested_sampling`` methods (``realisations=None``: the fit's data vector, R = 1); see the module docstring.
     With ``evaluate`` - a callable taking a dict of ``(n,)`` arrays (sampled and fixed parameters) and returning ``lnL (n,)`` or
     ``(lnL, chi2)`` - in place of ``fit`` only the definition route (``device=False``) is possible, R = 1 and no GPU is needed.
@@ -410,11 +526,21 @@ def nested_sampling(fit, params, n_live=DEFAULT_LIVE, batch=DEFAULT_BATCH, steps
     ``params``: the cobaya block, whose uniform priors are the box; ``fixed``: name -> scalar overrides; ``scale``: the step
     width in units of the live range, default ``0.5 / sqrt(d)``; ``tol``, ``max_iter`` (default ``128 n_live / batch``): the stop;
     ``n_iter``: a fixed number of iterations instead; ``keep_dead``: keep the dead points' positions (the posterior sample).
+    ``prior``: a :class:`victor_amd.priors.GaussianPrior` or a list of them, multiplied onto the box (with ``evaluate``: over the
+    block's names); the run then orders, kills and constrains on lnL + ln prior, and the evidence is under the Gaussian
+    normalised over the box.  ``prior_norm``: how that normalisation is had - ``"exact"`` (the closed form of independent
+    priors; refused on a correlated one), ``"nested"`` (the prior's own run of the definition loop, on the host) or ``"auto"``
+    (exact where possible).
     Every argument is checked before the first device call.  Returns a :class:`NestedSampling`."""
+    from .priors import GaussianPrior
     kwargs = dict(kwargs or {})
     who = "nested_sampling"
-    if "prior" in kwargs:
-        raise InputError(f"{who}: prior= is not accepted (the evidence is under the normalised uniform box of the params block)")
+    prior = kwargs.pop("prior", prior)
+    if prior is not None and not isinstance(prior, GaussianPrior) and not (
+            isinstance(prior, (list, tuple)) and len(prior) and all(isinstance(p, GaussianPrior) for p in prior)):
+        raise InputError(f"{who}: prior= is not accepted: it must be a GaussianPrior or a list of them")
+    if prior_norm not in ("auto", "exact", "nested"):
+        raise InputError(f"{who}: prior_norm must be 'auto', 'exact' or 'nested'")
     n_live, batch, steps = int(n_live), int(batch), int(steps)
     if n_live < 2 or n_live > MAX_LIVE:
         raise InputError(f"{who}: need 2 <= n_live <= {MAX_LIVE}")
@@ -450,6 +576,10 @@ def nested_sampling(fit, params, n_live=DEFAULT_LIVE, batch=DEFAULT_BATCH, steps
         raise InputError(f"{who}: scale must be finite and > 0")
     if evaluate is None:
         fit_options = q.fit_options(fit, kwargs)
+    prior = q.prior(list(prior) if isinstance(prior, tuple) else prior, fit)
+    if prior is not None and prior_norm == "exact" and prior.sigma is None:
+        raise InputError(f"{who}: prior_norm='exact' needs independent priors (sigma=, or a diagonal cov); a correlated prior is "
+                         "normalised by prior_norm='nested'")
     R = len(realisations) if realisations is not None else 1
     if R * batch > MAX_ROWS:
         raise InputError(f"{who}: {R} problems x batch {batch} = {R * batch} rows: at most {MAX_ROWS}")
@@ -464,8 +594,14 @@ def nested_sampling(fit, params, n_live=DEFAULT_LIVE, batch=DEFAULT_BATCH, steps
         b.update({n: np.ascontiguousarray(x[:, j]) for j, n in enumerate(names)})
         return b
 
-    ns = NestedSampling(names, lo, hi, fixed_out, R, n_live, batch, steps, scale, seed, tol, keep_dead, None, None, which)
+    ns = NestedSampling(names, lo, hi, fixed_out, R, n_live, batch, steps, scale, seed, tol, keep_dead, None, None, which, prior=prior)
     x0 = ns.start_points()
+    if prior is not None:
+        if prior_norm == "exact" or (prior_norm == "auto" and prior.sigma is not None):
+            ns.prior_norm, ns.ln_prior_norm, ns.ln_prior_norm_error = "exact", exact_prior_norm(prior, lo, hi), 0.0
+        else:
+            ns.prior_norm = "nested"
+            ns.ln_prior_norm, ns.ln_prior_norm_error = nested_prior_norm(prior, names, lo, hi, n_live, batch, steps, scale, seed, tol, max_iter)
     if evaluate is not None:
         def evaluator(x, rows_which=None):
             out = evaluate(batch_of(x))
@@ -486,6 +622,8 @@ def nested_sampling(fit, params, n_live=DEFAULT_LIVE, batch=DEFAULT_BATCH, steps
                                    which, shape=(n_live, batch, steps, scale))
         ns._dev, ns._refresh, ns._fit = (lib, h), refresh, fit
     ns._evaluate = evaluator
+    if ns._dev and prior is not None:
+        ns._check(ns._dev[0].vk_nprior_set(ns._dev[1], N.as_dp(prior.mu), N.as_dp(prior.pp)), "vk_nprior_set")
     if ns._dev:
         ns._check(ns._dev[0].vk_nested_start(ns._dev[1], N.as_dp(N.f64(x0))), "vk_nested_start")
         ns._live_lnl = None

@@ -85,8 +85,9 @@ class ResolvedPrior:
     """The priors of one call against its d sampled parameters: ``mu`` (d,) and ``pp`` (d (d + 1) / 2,), the packed triangle of
     the module docstring - what ``vk_fit_set_prior`` / ``vk_chain_set_prior`` take - and the NumPy statement of ln prior."""
 
-    def __init__(self, names, mu, precision):
+    def __init__(self, names, mu, precision, sigma=None):
         self.names = list(names)
+        self.sigma = sigma                                  # (d,) standard deviations (NaN: no prior) when every prior is independent
         d = self.d = len(self.names)
         self.mu = np.ascontiguousarray(mu, dtype=np.float64)
         self.precision = precision
@@ -127,6 +128,7 @@ def resolve_prior(prior, who, names, lo, hi, fixed=(), joint=True):
         raise InputError(f"{who}: at most {MAX_PARAMS} sampled parameters")
     seen = set()
     mu, precision = np.zeros(d), np.zeros((d, d))
+    sigma = np.full(d, np.nan)                              # ... of independent priors; None once one is correlated
     for p in priors:
         for n in p.names:
             if "@" in n and not joint:
@@ -154,4 +156,11 @@ def resolve_prior(prior, who, names, lo, hi, fixed=(), joint=True):
             raise InputError(f"{who}: the inverse of the prior covariance of {p.names} is not finite")
         mu[at] = mean
         precision[np.ix_(at, at)] = sub
-    return ResolvedPrior(names, mu, precision)
+        if sigma is not None:
+            if p.sigma is not None:
+                sigma[at] = p.sigma[order]
+            elif not np.any(p.cov - np.diag(np.diag(p.cov))):
+                sigma[at] = np.sqrt(np.diag(p.cov))[order]
+            else:
+                sigma = None
+    return ResolvedPrior(names, mu, precision, sigma)

@@ -351,14 +351,14 @@ class Realisations:
                                     sample, ln_proposal, kwargs, realisations=self, predictive=predictive, tail=tail)
 
     def nested_sampling(self, params, n_live=256, batch=32, steps=16, scale=None, seed=0, fixed=None, tol=1e-3, max_iter=None, n_iter=None,
-                        keep_dead=True, device=True, evaluate=None, **kwargs):
+                        keep_dead=True, device=True, evaluate=None, prior=None, prior_norm="auto", **kwargs):
         """Nested sampling of EVERY realisation, all of them in lock step (R = ``len(self)`` problems, one evidence and one
         posterior sample per mock): on the GPU (``device=True``) or by the NumPy loop over :meth:`log_likelihood_pairs` that
         defines the runs (``device=False``).  ``paired_model=True`` is honoured: a row is evaluated with the model of its own
         mock.  Arguments and result as ``CCFFit.nested_sampling`` (:mod:`victor_amd.nested`)."""
         from .nested import nested_sampling
         return nested_sampling(self.fit, params, n_live, batch, steps, scale, seed, fixed, tol, max_iter, n_iter, keep_dead, device,
-                               evaluate, kwargs, realisations=self)
+                               evaluate, kwargs, realisations=self, prior=prior, prior_norm=prior_norm)
 
     def log_likelihood_pairs(self, params, which, **kwargs):
         """(lnL, chi2), each ``(n_points,)``: point p against realisation ``numbers[which[p]]`` only - the form an ensemble of
