@@ -15,6 +15,8 @@
  *   vk_xi_smu_batch      CCFModel.theory_xi           victor/ccf_model.py:538-789
  *   vk_eval_realisations CCFFit.log_likelihood against every simulation realisation of the
  *                        data file (simulation_number, victor/ccf_fit.py:59-61,93-100)
+ *   vk_set_cuts          ... under many scale cuts (s ranges, multipole sets) at once, a use of the reference that
+ *                        slices the data and covariance files by hand, once per cut
  *   vk_set_model_realisations  ... each with the model of its own real-space CCF
  *                        (realspace_ccf.simulation_number, victor/ccf_model.py:127-162)
  *   vk_joint_cov_eval_realisations  the same for a joint fit under one covariance: realisation m
@@ -423,6 +425,31 @@ void vk_epsilon_to_ap(const double* eps, int64_t n, double alpha, double* aperp,
 int vk_set_realisations(vk_ctx* ctx, const double* data, int32_t n_real);
 int vk_eval_realisations(vk_ctx* ctx, const vk_eval_opts* opts, const double* params, int64_t n, const int32_t* which,
                          double* lnl, double* chi2);
+
+/* ---- scale cuts: every realisation under many s ranges and multipole sets, from one theory vector ------------------------
+ * A cut k keeps n_k of the context's N data-vector entries, index_k[0 .. n_k-1] strictly increasing (layout of the data vector:
+ * multipole-major).  Its chi2 is r^T inv(C[idx, idx]) r over the kept entries - the inverse of the SUB-covariance, not a
+ * sub-block of the context's precision -, its log determinant is the sub-covariance's and the likelihood forms (Hartlap,
+ * Percival) count n_k data points.  The theory vector of a point does not depend on the cut.
+ * vk_set_cuts: n_cuts cuts next to the realisations already set (vk_set_realisations comes first).  With S = max(n_beta_c, 1)
+ *   covariance slices:  n_keep [n_cuts];  index [n_cuts][N] (row k: its first n_keep[k] entries are read);  prec [n_cuts][S][N*N]
+ *   (slot (k, j) starts at (k S + j) N N and holds inv(C_j[idx_k, idx_k]) compact, row stride n_keep[k]);  logdet [n_cuts][n_beta_c]
+ *   and eig [n_cuts][n_beta_c][N] (row (k, j): its first n_keep[k] entries) as vk_tables.logdet / eig of the sub-covariances -
+ *   both NULL for a fixed covariance.  Copied to the device; resident until replaced, until n_cuts = 0, until the next
+ *   vk_set_realisations (cuts belong to the realisations they were set next to) or vk_destroy.
+ * While cuts are resident a PROBLEM is the flat index v = k * n_real + m (cut-major): vk_eval_realisations returns [n][n_cuts *
+ *   n_real] in cross mode and takes which[i] = v in pairs mode (the same bits in both modes), and every handle over realisations
+ *   (vk_fit_*, vk_chain_*, vk_nested_*, vk_grid_*, vk_is_*) sees n_cuts * n_real realisations.  Without cuts nothing changes.
+ * VK_E_ARG: no realisations set; model realisations resident (vk_set_model_realisations - a row's table set is its realisation,
+ *   not the flat index; that call is refused in turn while cuts are resident); n_keep outside 1..N; indices not strictly
+ *   increasing within 0..N-1; a needed pointer NULL.  Refused while cuts are resident, each with VK_E_ARG and a text, the handle
+ *   or context staying usable, ON WHAT ADDRESSES REALISATIONS: joint evaluations and joint handles against the blocks'
+ *   realisations, and of a handle created with `which` (or over every realisation) vk_fit_fisher (J^T P J is formed from the full
+ *   precision), vk_chain_set_predictive / vk_is_set_predictive and VK_OPT_BETA_BLEND.  Everything over the context's own data
+ *   vector - vk_eval_batch*, handles created with which == NULL with their Fisher, predictive and blend calls, joint evaluations
+ *   against the data vectors - reads nothing the cuts changed and does what it did before, cuts resident or not. */
+int vk_set_cuts(vk_ctx* ctx, int32_t n_cuts, const int32_t* n_keep, const int32_t* index, const double* prec, const double* logdet,
+                const double* eig);
 
 /* ---- every realisation with its own real-space CCF: xi^r table sets selected per row ------------------------------------
  * The reference picks the real-space multipoles xi^r_l(r) - with reconstruction xi^r_l(beta, r) - of ONE simulation out of a

@@ -2,9 +2,14 @@
 library's event timing (vk_timing_*), the matrix-core kernel against its vector-ALU twin (VICTOR_HIP_REAL_VALU, same tiling,
 alternated), and the same work as M separate CCFFit objects at M = 64.  Writes realisations_<M>.txt and
 realisations_separate_fits.txt into the output directory.  With --paired instead: 65536 rows in pairs mode over 1024 mocks,
-realisations(paired_model=True) against the shared model, BOSS and the fixed-table config 3 (paired_main).
+realisations(paired_model=True) against the shared model, BOSS and the fixed-table config 3 (paired_main).  With --cuts: scale
+cuts in one call against the route without them - 16 mocks, 4096 points, K = 1, 4 and 8 nested s_min cuts:
+``CutRealisations.log_likelihood`` (one theory launch, the cuts kernel) against K sliced ``CCFFit`` objects (data stack and
+covariance sliced into files, as a user does by hand) evaluated one after another through ``Realisations.log_likelihood``; the
+two legs alternate in one process after a warm-up of each, median of --reps timed calls and their spread, and the library's
+event split of the one-call leg (cuts_main).
 
-    python tools/realisations_timing.py OUT_DIR [--commit SHA] [--paired]
+    python tools/realisations_timing.py OUT_DIR [--commit SHA] [--paired | --cuts [--reps 7]]
 """
 import os
 import sys
@@ -201,5 +206,78 @@ def paired_main():
         fh.write(text)
 
 
+# ---- --cuts: K scale cuts in one call against K sliced fits --------------------------------------------------------------------
+CUT_DROPS = {1: [0], 4: [0, 2, 4, 7], 8: [0, 1, 2, 3, 4, 5, 6, 7]}
+
+
+def sliced_fit(tmp, first):
+    """The fit a user builds for ``s >= s[first]``: sliced data stack and covariance files."""
+    import victor_amd
+    stack = np.load(os.path.join(cases.GOLDEN, "realisations", "stack.npy"), allow_pickle=True).item()
+    cov = np.load(os.path.join(cases.GOLDEN, "boss", "cov.npy"), allow_pickle=True).item()
+    keep = np.arange(first, len(stack["s"]))
+    idx = np.concatenate([keep, len(stack["s"]) + keep])
+    data_path, cov_path = os.path.join(tmp, f"stack_{first}.npy"), os.path.join(tmp, f"cov_{first}.npy")
+    np.save(data_path, dict(stack, s=stack["s"][keep], monopole=stack["monopole"][..., keep], quadrupole=stack["quadrupole"][..., keep]),
+            allow_pickle=True)
+    np.save(cov_path, dict(cov, covmat=np.ascontiguousarray(cov["covmat"][:, idx][:, :, idx])), allow_pickle=True)
+    model, data = options(data_path)
+    data["covariance_matrix"]["data_file"] = cov_path
+    return victor_amd.CCFFit(model, data)
+
+
+def cuts_main():
+    """--cuts (see the module docstring).  Writes scale_cuts.txt."""
+    import victor_amd
+    from victor_amd import ScaleCut
+    out = sys.argv[1]
+    commit = sys.argv[sys.argv.index("--commit") + 1] if "--commit" in sys.argv else "unknown"
+    reps = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else 7
+    os.makedirs(out, exist_ok=True)
+    tmp = tempfile.mkdtemp()
+    hp = cases.halton_params(BATCH, with_beta=True)
+    lines = [f"commit {commit}", f"BOSS (N = 60), {BATCH} points x 16 mocks x K nested s_min cuts; wall ms per call, median of {reps} [min .. max]"]
+    for K, drops in CUT_DROPS.items():
+        fit = victor_amd.CCFFit(*options(os.path.join(cases.GOLDEN, "realisations", "stack.npy")))
+        cr = fit.realisations().scale_cuts([ScaleCut(s_min=None if k == 0 else float(fit.s[k])) for k in drops])
+        base = [sliced_fit(tmp, k).realisations() for k in drops]
+        model = fit._merged({})
+        eng = fit._get_engine(fit._engine_key(model), model["simpson_even"])
+
+        def one_call():
+            return cr.log_likelihood(hp)
+
+        def one_by_one():
+            return [rs.log_likelihood(hp) for rs in base]
+        got, want = one_call(), one_by_one()                     # warm-up of each leg
+        worst = max(float(np.nanmax(np.abs(got[1][:, k] / w[1] - 1.0))) for k, w in enumerate(want))
+        walls = {"one call": [], "K fits": []}
+        th, ch = [], []
+        for _ in range(reps):                                    # alternated
+            eng.timing(True)
+            t0 = time.perf_counter()
+            one_call()
+            walls["one call"].append(1e3 * (time.perf_counter() - t0))
+            a, b, _ = eng.read_timing(reset=True)
+            eng.timing(False)
+            th.append(a)
+            ch.append(b)
+            t0 = time.perf_counter()
+            one_by_one()
+            walls["K fits"].append(1e3 * (time.perf_counter() - t0))
+        med = {k: float(np.median(v)) for k, v in walls.items()}
+        lines.append(f"K = {K} (entries kept {[t.n for t in cr.tables]}): largest |chi2 ratio - 1| between the legs {worst:.1e}")
+        for k, v in walls.items():
+            lines.append(f"  {k:9s} {med[k]:9.2f} [{min(v):.2f} .. {max(v):.2f}]")
+        lines.append(f"  one call, device events: theory launch {np.median(th):.3f} ms, cuts kernel {np.median(ch):.3f} ms")
+        lines.append(f"  one call / K fits = {med['one call'] / med['K fits']:.3f}")
+        for f in [fit] + [rs.fit for rs in base]:
+            f._engine = None
+    text = "\n".join(lines) + "\n"
+    print(text, flush=True)
+    with open(os.path.join(out, "scale_cuts.txt"), "w") as fh:
+        fh.write(text)
+
+
 if __name__ == "__main__":
-    paired_main() if "--paired" in sys.argv else main()
+    cuts_main() if "--cuts" in sys.argv else paired_main() if "--paired" in sys.argv else main()

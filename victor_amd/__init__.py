@@ -17,7 +17,8 @@ from .fisher import Fisher
 from .grid import GridPosterior
 from .importance import GaussianProposal, ImportancePosterior, ProposalSet
 from .realisations import Realisations
+from .cuts import CutRealisations, ScaleCut
 from .utils import InputError
 
 __version__ = "0.1.0"
-__all__ = ["CCFModel", "CCFFit", "BackgroundCosmology", "BestFit", "Chains", "Fisher", "GaussianPrior", "GaussianProposal", "GridPosterior", "ImportancePosterior", "InputError", "JointFit", "JointRealisations", "Laplace", "ProposalSet", "Realisations", "utils", "__version__"]
+__all__ = ["CCFModel", "CCFFit", "BackgroundCosmology", "BestFit", "Chains", "Fisher", "GaussianPrior", "GaussianProposal", "GridPosterior", "ImportancePosterior", "InputError", "JointFit", "JointRealisations", "Laplace", "ProposalSet", "Realisations", "CutRealisations", "ScaleCut", "utils", "__version__"]

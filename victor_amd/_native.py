@@ -134,6 +134,7 @@ SYMBOLS = {
     "vk_set_realisations": (C.c_int, [_vp, _dp, C.c_int32]),
     "vk_eval_realisations": (C.c_int, [_vp, _optp, _dp, C.c_int64, C.POINTER(C.c_int32), _dp, _dp]),
     "vk_set_model_realisations": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int32]),
+    "vk_set_cuts": (C.c_int, [_vp, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp, _dp, _dp]),
     "vk_fit_create": (_vp, [_vp, _optp, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _dp, _dp, _dp, C.c_double,
                             C.POINTER(C.c_int32), C.c_char_p, C.c_size_t]),
     "vk_fit_run": (C.c_int, [_vp, _dp, _dp, _dp, C.c_double, C.c_int32, C.c_int32, _dp, _dp, _dp, C.POINTER(C.c_int32),

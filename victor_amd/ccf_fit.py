@@ -426,6 +426,13 @@ class CCFFit(CCFModel):
         from .realisations import Realisations
         return Realisations(self, simulation_numbers, paired_model)
 
+    def scale_cuts(self, cuts):
+        """This fit's data vector under every cut of ``cuts`` (:class:`victor_amd.cuts.ScaleCut`: s ranges, multipole sets,
+        masks) at once: a :class:`victor_amd.cuts.CutRealisations` of ``len(cuts)`` problems (R = 1, no stacked file needed),
+        each with the inverse of its own sub-covariance, its log determinant and its count of data points."""
+        from .cuts import from_fit
+        return from_fit(self, cuts)
+
     def theory_vector_batch(self, params, **kwargs):
         """Theory vectors (n, N) on the data's own s grid and multipoles."""
         model = self._merged(kwargs)

@@ -15,6 +15,7 @@
 //   vk_kernel_cells.h    K1 cells (workgroup = point, lanes over (s, mu) cells, v loop innermost; per-point tables)
 //   vk_kernel_like.h     K2 residual . precision . residual, log det, likelihood form, NaN guard
 //   vk_kernel_real.h     K2 against many realisations of the data vector (vk_eval_realisations): f64 MFMA, one point per workgroup
+//   vk_kernel_real_cuts.h  ... under scale cuts (vk_set_cuts): every (cut, realisation) pair from the one theory vector
 //   vk_kernel_joint.h    K2 of a joint fit under one covariance across its data vectors (vk_joint_cov_eval_device_async): f64 MFMA,
 //                        16 points per workgroup, the precision streamed from L2
 //   vk_kernel_joint_real.h  the same against many realisations of every block (vk_joint_cov_eval_realisations): rows are
@@ -56,6 +57,7 @@
 #endif
 #include "vk_kernel_like.h"
 #include "vk_kernel_real.h"
+#include "vk_kernel_real_cuts.h"
 #include "vk_kernel_joint.h"
 #include "vk_kernel_joint_real.h"
 
@@ -1293,6 +1295,7 @@ void vk_destroy(vk_ctx* ctx) {
   if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
   if (ctx->d_real) (void)hipFree(ctx->d_real);
   if (ctx->d_sets) (void)hipFree(ctx->d_sets);
+  if (ctx->d_cuts) (void)hipFree(ctx->d_cuts);
   for (auto& evt : ctx->ev)
     if (evt) (void)hipEventDestroy(evt);
   if (ctx->ev_joint) (void)hipEventDestroy(ctx->ev_joint);
@@ -1464,6 +1467,10 @@ static int check_blocks(vk_ctx* lead, const vk_joint_cov* h, vk_ctx* const* ctxs
       return fail(lead, VK_E_ARG, "joint fit: context %d holds model realisations (vk_set_model_realisations), which joint "
                                   "evaluations do not support", q);
     if (!need_real) continue;
+    // (against the data vectors a joint evaluation reads nothing the cuts changed and is served as ever)
+    if (c->n_cuts > 0)
+      return fail(lead, VK_E_ARG, "joint fit: context %d holds scale cuts (vk_set_cuts), which joint evaluations against realisations do not support: "
+                                  "a cut of a joint vector needs the joint covariance's own sub-blocks", q);
     if (c->begun_n != 0)
       return fail(lead, VK_E_ARG, "a batch begun with vk_eval_batch_begin is awaiting vk_eval_batch_finish on context %d", q);
     if (c->n_real <= 0 || !c->d_real)
@@ -1684,10 +1691,26 @@ int vkh::enqueue_realisations(vk_ctx* ctx, const vk_eval_opts* opts, const doubl
   ra.block = ctx->real_block;
   ra.n_real = ctx->n_real;
   ra.which = d_which;
-  ctx->last_like = ctx->knobs.real_valu ? "like_real<false>" : "like_real<true>";
   const size_t lds = real_lds_doubles(ctx->N) * sizeof(double);
-  rc = ctx->knobs.real_valu ? launch_on_stream(ctx, vk_like_real_kernel<false>, (int)m, lds, ra)
-                            : launch_on_stream(ctx, vk_like_real_kernel<true>, (int)m, lds, ra);
+  if (ctx->n_cuts > 0) {
+    // scale cuts resident (vk_set_cuts): the same launch shape and LDS, a problem is (cut, realisation)
+    CutArgs ca{};
+    ca.real = ra;
+    ca.n_cuts = ctx->n_cuts;
+    ca.n_slices = std::max(ctx->n_beta_c, 1);
+    ca.n_keep = ctx->d_cut_keep;
+    ca.index = ctx->d_cut_index;
+    ca.prec = ctx->d_cut_prec;
+    ca.logdet = ctx->d_cut_logdet;
+    ca.eig = ctx->d_cut_eig;
+    ctx->last_like = ctx->knobs.real_valu ? "like_real_cuts<false>" : "like_real_cuts<true>";
+    rc = ctx->knobs.real_valu ? launch_on_stream(ctx, vk_cuts_real_kernel<false>, (int)m, lds, ca)
+                              : launch_on_stream(ctx, vk_cuts_real_kernel<true>, (int)m, lds, ca);
+  } else {
+    ctx->last_like = ctx->knobs.real_valu ? "like_real<false>" : "like_real<true>";
+    rc = ctx->knobs.real_valu ? launch_on_stream(ctx, vk_like_real_kernel<false>, (int)m, lds, ra)
+                              : launch_on_stream(ctx, vk_like_real_kernel<true>, (int)m, lds, ra);
+  }
   if (rc) return rc;
   if (timed) {
     VK_HIP(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
@@ -2347,6 +2370,14 @@ int vk_xi_smu_batch(vk_ctx* ctx, const vk_eval_opts* opts, const double* params,
 }
 
 // ---- one parameter batch against many realisations of the data vector (include/victor_hip.h, vk_kernel_real.h) -----------
+static void drop_cuts(vk_ctx* ctx) {
+  if (ctx->d_cuts) (void)hipFree(ctx->d_cuts);
+  ctx->d_cuts = nullptr;
+  ctx->n_cuts = 0;
+  ctx->d_cut_prec = ctx->d_cut_logdet = ctx->d_cut_eig = nullptr;
+  ctx->d_cut_keep = ctx->d_cut_index = nullptr;
+}
+
 int vk_set_realisations(vk_ctx* ctx, const double* data, int32_t n_real) {
   if (!ctx) return VK_E_ARG;
   if (n_real < 0 || (n_real > 0 && !data)) return fail(ctx, VK_E_ARG, "vk_set_realisations: bad arguments");
@@ -2356,6 +2387,7 @@ int vk_set_realisations(vk_ctx* ctx, const double* data, int32_t n_real) {
   if (ctx->d_real) (void)hipFree(ctx->d_real);
   ctx->d_real = nullptr;
   ctx->n_real = 0;
+  drop_cuts(ctx);                                        // (cuts belong to the realisations they were set next to)
   const long long block = ctx->n_beta_d > 0 ? (long long)(ctx->n_beta_d - 1) * ctx->N * 4 : ctx->N;
   ctx->real_block = block;
   if (n_real == 0) return VK_OK;
@@ -2366,12 +2398,78 @@ int vk_set_realisations(vk_ctx* ctx, const double* data, int32_t n_real) {
   return VK_OK;
 }
 
+// ---- scale cuts next to the realisations (include/victor_hip.h, vk_kernel_real_cuts.h) ---------------------------------------
+int vk_set_cuts(vk_ctx* ctx, int32_t n_cuts, const int32_t* n_keep, const int32_t* index, const double* prec, const double* logdet,
+                const double* eig) {
+  if (!ctx) return VK_E_ARG;
+  if (n_cuts < 0) return fail(ctx, VK_E_ARG, "vk_set_cuts: n_cuts = %d is negative", n_cuts);
+  const int N = ctx->N, nb = ctx->n_beta_c, S = std::max(nb, 1);
+  if (n_cuts > 0) {
+    if (ctx->n_real <= 0 || !ctx->d_real)
+      return fail(ctx, VK_E_ARG, "vk_set_cuts: no realisations are set on this context (vk_set_realisations comes first)");
+    if (ctx->n_sets > 0)
+      return fail(ctx, VK_E_ARG, "vk_set_cuts: model realisations are set on this context (vk_set_model_realisations): a row's "
+                                 "table set is its realisation, and under cuts its index names a (cut, realisation) pair");
+    if (!n_keep || !index || !prec || (nb > 0 && (!logdet || !eig))) return fail(ctx, VK_E_ARG, "vk_set_cuts: NULL argument");
+    if ((long long)n_cuts * ctx->n_real > (1LL << 31) - 1)
+      return fail(ctx, VK_E_ARG, "vk_set_cuts: %d cuts x %d realisations do not fit a 32-bit problem index", n_cuts, ctx->n_real);
+    for (int k = 0; k < n_cuts; ++k) {
+      if (n_keep[k] < 1 || n_keep[k] > N)
+        return fail(ctx, VK_E_ARG, "vk_set_cuts: cut %d keeps %d entries, the data vector has %d", k, n_keep[k], N);
+      for (int e = 0; e < n_keep[k]; ++e) {
+        const int32_t i = index[(size_t)k * N + e];
+        if (i < 0 || i >= N || (e > 0 && i <= index[(size_t)k * N + e - 1]))
+          return fail(ctx, VK_E_ARG, "vk_set_cuts: entry %d of cut %d is %d: the indices must increase strictly within 0..%d", e, k,
+                      i, N - 1);
+      }
+    }
+  }
+  VK_HIP(ctx, hipSetDevice(ctx->device));
+  VK_HIP(ctx, hipStreamSynchronize(ctx->stream));        // (nothing in flight may still read the old tables)
+  drop_cuts(ctx);
+  if (n_cuts == 0) return VK_OK;
+  // one allocation: prec [K][S][N N] | logdet [K][nb] | eig [K][nb][N] | ints: n_keep [K], index [K][N] (unused tails zeroed)
+  const size_t n_prec = (size_t)n_cuts * S * N * N, n_ld = (size_t)n_cuts * nb, n_eig = (size_t)n_cuts * nb * N;
+  const size_t n_int = (size_t)n_cuts * (1 + N);
+  std::vector<double> host;
+  try {
+    host.assign(n_prec + n_ld + n_eig + (n_int + 1) / 2, 0.0);
+  } catch (const std::bad_alloc&) {
+    return fail(ctx, VK_E_NOMEM, "vk_set_cuts: no host memory for %d cuts", n_cuts);
+  }
+  memcpy(host.data(), prec, n_prec * sizeof(double));
+  if (nb > 0) {
+    memcpy(host.data() + n_prec, logdet, n_ld * sizeof(double));
+    memcpy(host.data() + n_prec + n_ld, eig, n_eig * sizeof(double));
+  }
+  int32_t* h_int = reinterpret_cast<int32_t*>(host.data() + n_prec + n_ld + n_eig);
+  memcpy(h_int, n_keep, (size_t)n_cuts * sizeof(int32_t));
+  for (int k = 0; k < n_cuts; ++k) memcpy(h_int + n_cuts + (size_t)k * N, index + (size_t)k * N, (size_t)n_keep[k] * sizeof(int32_t));
+  VK_HIP(ctx, hipMalloc((void**)&ctx->d_cuts, host.size() * sizeof(double)));
+  const hipError_t e = hipMemcpy(ctx->d_cuts, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)hipFree(ctx->d_cuts);
+    ctx->d_cuts = nullptr;
+    return fail(ctx, VK_E_HIP, "vk_set_cuts: upload failed: %s", hipGetErrorString(e));
+  }
+  ctx->d_cut_prec = ctx->d_cuts;
+  ctx->d_cut_logdet = nb > 0 ? ctx->d_cuts + n_prec : nullptr;
+  ctx->d_cut_eig = nb > 0 ? ctx->d_cuts + n_prec + n_ld : nullptr;
+  ctx->d_cut_keep = reinterpret_cast<const int32_t*>(ctx->d_cuts + n_prec + n_ld + n_eig);
+  ctx->d_cut_index = ctx->d_cut_keep + n_cuts;
+  ctx->n_cuts = n_cuts;
+  return VK_OK;
+}
+
 // ---- xi^r table sets, one per realisation (include/victor_hip.h; the kernels: rebuild_point_tables, build_beta_tables) --------
 int vk_set_model_realisations(vk_ctx* ctx, const double* xi_coef, const double* uni_xi, const double* uni_xic, int32_t n_sets) {
   if (!ctx) return VK_E_ARG;
   if (n_sets < 0) return fail(ctx, VK_E_ARG, "vk_set_model_realisations: n_sets = %d is negative", n_sets);
   const bool uni = ctx->d_uni_xi != nullptr;             // unified tables on the device: the kernels that own a point per workgroup read them
   if (n_sets > 0) {
+    if (ctx->n_cuts > 0)
+      return fail(ctx, VK_E_ARG, "vk_set_model_realisations: scale cuts are resident on this context (vk_set_cuts): a row's table set "
+                                 "is its realisation, and under cuts its index names a (cut, realisation) pair");
     if (ctx->vr_beta_dep || ctx->matter_lb)
       return fail(ctx, VK_E_ARG, "vk_set_model_realisations: the velocity tables of this context depend on the real-space CCF (%s) "
                                  "and would need sets of their own", ctx->vr_beta_dep ? "vr_beta_dep" : "matter_model linear_bias");
@@ -2435,7 +2533,7 @@ int vk_eval_realisations(vk_ctx* ctx, const vk_eval_opts* opts, const double* pa
   if (n < 0 || (n > 0 && !params)) return fail(ctx, VK_E_ARG, "params is NULL");
   if (ctx->begun_n != 0) return fail(ctx, VK_E_ARG, "a batch begun with vk_eval_batch_begin is awaiting vk_eval_batch_finish on this context");
   if (ctx->n_real <= 0 || !ctx->d_real) return fail(ctx, VK_E_ARG, "no realisations are set on this context (vk_set_realisations)");
-  rc = check_which(ctx, which, n, ctx->n_real);
+  rc = check_which(ctx, which, n, vkh::n_problems(ctx));
   if (rc) return rc;
   if (n == 0) return VK_OK;
   const int N = ctx->N;
@@ -2443,7 +2541,7 @@ int vk_eval_realisations(vk_ctx* ctx, const vk_eval_opts* opts, const double* pa
   if (rc) return rc;
   VK_HIP(ctx, hipSetDevice(ctx->device));
   // a chunk is one theory launch into the workspace and one realisation launch behind it
-  RealChunks ch(which, ctx->n_real, n);
+  RealChunks ch(which, vkh::n_problems(ctx), n);
   const long long m_max = ch.m_max;
   const size_t doubles = (size_t)m_max * (VK_NPAR + N + 2 * ch.per_point) + (size_t)m_max / 2 + 2;
   rc = ensure_scratch(ctx, doubles * sizeof(double));

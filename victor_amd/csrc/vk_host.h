@@ -125,6 +125,11 @@ struct vk_ctx {
   long long set_coef_stride = 0, set_uni_stride = 0;   // doubles between two sets of xi.coef; of uni_xi and of uni_xic
   size_t xi_coef_doubles = 0, uni_xi_doubles = 0;       // lengths of vk_tables.xi.coef and of uni_xi / uni_xic as vk_create uploaded them (0: not there)
   const int32_t* row_set = nullptr;    // set around the theory launch of enqueue_realisations in pairs mode: the rows' set indices (device)
+  // scale cuts (vk_set_cuts): one allocation, the tables of vk_kernel_real_cuts.h's CutArgs; a problem is then (cut, realisation)
+  double* d_cuts = nullptr;
+  int n_cuts = 0;
+  const double *d_cut_prec = nullptr, *d_cut_logdet = nullptr, *d_cut_eig = nullptr;
+  const int32_t *d_cut_keep = nullptr, *d_cut_index = nullptr;
   // timing
   bool timing = false;
   hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
@@ -169,6 +174,9 @@ constexpr int kServeMaxBatch = 32;          // requests one launch of the mailbo
 namespace vkh __attribute__((visibility("hidden"))) {       // (internal: not part of the library's exported symbols)
 
 int fail(vk_ctx* ctx, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
+// The problems a realisation index addresses on this context: its realisations, times the scale cuts resident next to them
+// (vk_set_cuts; flat index cut * n_real + realisation).  What bounds `which` and sizes a cross-mode result.
+static inline int n_problems(const vk_ctx* ctx) { return ctx->n_real * (ctx->n_cuts > 0 ? ctx->n_cuts : 1); }
 int check_opts(vk_ctx* ctx, const vk_eval_opts* o);
 void sync_knobs(vk_ctx* ctx);
 

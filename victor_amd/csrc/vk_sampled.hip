@@ -259,6 +259,9 @@ static H* sampled_create(const char* who, const char* noun, vk_ctx* const* ctxs,
   if (blend && joint)
     return bail(me + "VK_OPT_BETA_BLEND (beta_interpolation 'likelihood') is refused for a joint fit: a blend per block under one "
                      "beta is a design of its own");
+  if (blend && which && ctx->n_cuts > 0)          // (a handle over the data vector reads nothing the cuts changed)
+    return bail(me + "VK_OPT_BETA_BLEND (beta_interpolation 'likelihood') is refused with scale cuts resident on the context "
+                     "(vk_set_cuts)");
   if (blend && ctx->n_beta_d < 2)
     return bail(me + "VK_OPT_BETA_BLEND (beta_interpolation 'likelihood') needs a data vector gridded in beta: a fixed data vector "
                      "has no nodes to blend between");
@@ -296,9 +299,9 @@ static H* sampled_create(const char* who, const char* noun, vk_ctx* const* ctxs,
   int max_which = -1;
   if (which)
     for (int i = 0; i < n; ++i) {
-      if (which[i] < 0 || which[i] >= ctx->n_real)
+      if (which[i] < 0 || which[i] >= vkh::n_problems(ctx))
         return bail(me + "realisation index " + std::to_string(which[i]) + " of " + noun + " " + std::to_string(i) +
-                    " is outside 0.." + std::to_string(ctx->n_real - 1));
+                    " is outside 0.." + std::to_string(vkh::n_problems(ctx) - 1));
       max_which = std::max(max_which, (int)which[i]);
     }
   H* f = new (std::nothrow) H();
@@ -392,16 +395,16 @@ static int sampled_ready(Sampled* f, const char* who, const char* noun, bool nam
       if (f->blocks[q]->begun_n != 0)
         return refuse("a batch begun with vk_eval_batch_begin is awaiting vk_eval_batch_finish on context " + std::to_string(q));
     if (check_joint(f->cov, f->blocks.data(), (int)f->blocks.size(), f->real) != VK_OK) return refuse(ctx->err);
-    if (f->real && f->max_which >= ctx->n_real)
-      return refuse("the contexts hold " + std::to_string(ctx->n_real) + " realisations, a " + noun + " asks for number " +
+    if (f->real && f->max_which >= vkh::n_problems(ctx))
+      return refuse("the contexts hold " + std::to_string(vkh::n_problems(ctx)) + " realisations, a " + noun + " asks for number " +
                     std::to_string(f->max_which));
     return VK_OK;
   }
   if (ctx->begun_n != 0) return refuse("a batch begun with vk_eval_batch_begin is awaiting vk_eval_batch_finish on the context");
   if (f->real) {
     if (ctx->n_real <= 0 || !ctx->d_real) return refuse("no realisations are set on the context (vk_set_realisations)");
-    if (f->max_which >= ctx->n_real)
-      return refuse("the context holds " + std::to_string(ctx->n_real) + " realisations, a " + noun + " asks for number " +
+    if (f->max_which >= vkh::n_problems(ctx))
+      return refuse("the context holds " + std::to_string(vkh::n_problems(ctx)) + " realisations, a " + noun + " asks for number " +
                     std::to_string(f->max_which));
     if (check_real_lds(ctx) != VK_OK) return name_lds ? refuse(ctx->err) : refused(f, ctx->err);
   }
@@ -461,6 +464,11 @@ static int sampled_launch(Sampled* f, void (*kern)(Args), long long threads, int
 // duplicated indices, or in cross mode [2 m][n_real] -, the merge kernel blends into the caller's arrays.  m <= rows_max.
 static int sampled_evaluate_blend(Sampled* f, long long m, double* d_lnl, double* d_chi) {
   if (m <= 0) return VK_OK;
+  if (f->real && f->ctx->n_cuts > 0) {
+    f->err = "the handle blends the likelihood between two grid betas (VK_OPT_BETA_BLEND), which is refused with scale cuts resident "
+             "on the context (vk_set_cuts)";
+    return VK_E_ARG;
+  }
   const Sampled::Blend& b = f->blend;
   const int* row_which = f->real ? f->d_row_which : nullptr;     // (NULL against realisations: cross mode)
   BlendArgs q{};
@@ -979,6 +987,9 @@ int vk_fit_fisher(vk_fit* f, const double* x, const double* h, double* vectors, 
   if (f->blend.on)
     return refused(f, "vk_fit_fisher: the handle blends the likelihood between two grid betas (VK_OPT_BETA_BLEND): a point has two "
                       "theory vectors and no one Jacobian");
+  if (f->real && f->ctx->n_cuts > 0)           // (a handle over the data vector forecasts from the full precision, as ever)
+    return refused(f, "vk_fit_fisher: scale cuts are resident on the context (vk_set_cuts): the forecast forms J^T P J from the "
+                      "context's full precision, not from a cut's");
   int rc = sampled_ready(f, "vk_fit_fisher", "problem", false);
   if (rc) return rc;
   const size_t R = f->R, d = f->P;
@@ -1480,6 +1491,9 @@ int vk_chain_set_predictive(vk_chain* f, int32_t group) {
   if (f->temper.K)
     return refused(f, me + "the handle is tempered (vk_chain_set_tempering): a swap moves states without touching the accept "
                            "counters the held vectors follow");
+  if (f->real && f->ctx->n_cuts > 0)
+    return refused(f, me + "scale cuts are resident on the context (vk_set_cuts): the predictive sums and the DIC are of the full "
+                           "data vector");
   if (group < 1 || f->C % group) return refused_groups(f, me, "groups of " + std::to_string(group));
   vkpred::Predictive p{};
   p.on = 1;
@@ -1901,8 +1915,8 @@ static GridArgs grid_args(const vk_grid* f) {
 static int grid_ready(vk_grid* f, const char* who) {
   int rc = sampled_ready(f, who, "grid", true);
   if (rc) return rc;
-  if (f->real && f->ctx->n_real != f->R)
-    return refused(f, std::string(who) + ": the context holds " + std::to_string(f->ctx->n_real) + " realisations, the grid was made for " +
+  if (f->real && vkh::n_problems(f->ctx) != f->R)
+    return refused(f, std::string(who) + ": the context holds " + std::to_string(vkh::n_problems(f->ctx)) + " realisations, the grid was made for " +
                           std::to_string(f->R));
   if (f->real && f->ctx->n_sets > 0)
     return refused(f, std::string(who) + ": model realisations are set on the context (vk_set_model_realisations): a point has one "
@@ -1971,7 +1985,7 @@ vk_grid* vk_grid_create(vk_ctx* ctx, const vk_eval_opts* opts, int32_t n_axes, c
       return bail("model realisations are set on the context (vk_set_model_realisations): a point has one theory vector per "
                   "realisation, and a grid evaluates every point once");
     if (check_real_lds(ctx) != VK_OK) return bail(ctx->err);
-    R = ctx->n_real;
+    R = vkh::n_problems(ctx);
   }
   if ((1 + n1 + n2) * (long long)(R + 1) > (1LL << 31) * (kGridBlock / 2))
     return bail("too many accumulators for one launch (cells x problems)");
@@ -2245,8 +2259,8 @@ static int is_ready(vk_is* f, const char* who) {
   for (size_t q = 0; q < nb; ++q) {
     const vk_ctx* c = f->blocks.empty() ? f->ctx : f->blocks[q];
     const std::string ctx_q = f->blocks.empty() ? "the context" : "context " + std::to_string(q);
-    if (c->n_real != f->R)
-      return refused(f, std::string(who) + ": " + ctx_q + " holds " + std::to_string(c->n_real) + " realisations, the sample was made for " +
+    if (vkh::n_problems(c) != f->R)
+      return refused(f, std::string(who) + ": " + ctx_q + " holds " + std::to_string(vkh::n_problems(c)) + " realisations, the sample was made for " +
                             std::to_string(f->R));
     if (c->n_sets > 0)
       return refused(f, std::string(who) + ": model realisations are set on " + ctx_q + " (vk_set_model_realisations): a point has one "
@@ -2406,9 +2420,9 @@ static vk_is* is_create(const char* who, vk_ctx* const* ctxs, int n_ctx, bool jo
     if ((long long)chunk * RR > vkis::kMaxChunk) return bail("need chunk x problems <= 65536 (the rows of one launch)");
     if (ctx->n_real <= 0 || !ctx->d_real) return bail("no realisations are set on the context (vk_set_realisations)");
     for (long long r = 0; r < RR; ++r)
-      if (which[r] < 0 || which[r] >= ctx->n_real)
+      if (which[r] < 0 || which[r] >= vkh::n_problems(ctx))
         return bail("realisation index " + std::to_string(which[r]) + " of problem " + std::to_string(r) + " is outside 0.." +
-                    std::to_string(ctx->n_real - 1));
+                    std::to_string(vkh::n_problems(ctx) - 1));
     if (ctx->n_sets > 0 && ctx->n_sets != ctx->n_real)
       return bail(std::to_string(ctx->n_sets) + " model realisations (vk_set_model_realisations) against " + std::to_string(ctx->n_real) +
                   " realisations of the data (vk_set_realisations): the counts must agree");
@@ -2474,14 +2488,14 @@ static vk_is* is_create(const char* who, vk_ctx* const* ctxs, int n_ctx, bool jo
     // every block: realisations set, the same number of them as the lead's, no model realisations (no cross mode), the LDS the
     // realisation kernels need
     if (check_joint(cov, ctxs, n_ctx, true) != VK_OK) return bail(ctx->err);
-    R = ctx->n_real;
+    R = vkh::n_problems(ctx);
   } else if (every_realisation) {
     if (ctx->n_real <= 0 || !ctx->d_real) return bail("no realisations are set on the context (vk_set_realisations)");
     if (ctx->n_sets > 0)
       return bail("model realisations are set on the context (vk_set_model_realisations): a point has one theory vector per "
                   "realisation, and a shared sample evaluates every point once");
     if (check_real_lds(ctx) != VK_OK) return bail(ctx->err);
-    R = ctx->n_real;
+    R = vkh::n_problems(ctx);
   }
   const long long n_acc = vkis::whole(n_axes) + cells;
   if (n_acc * (long long)(each ? 2 * R : R + 1) > (1LL << 31) * (kIsBlock / 2)) return bail("too many accumulators for one launch (accumulators x problems)");
@@ -2587,6 +2601,9 @@ int vk_is_set_predictive(vk_is* f, int32_t on) {
     return refused(f, me + "the handle blends the likelihood between two grid betas (VK_OPT_BETA_BLEND): a point has two theory "
                            "vectors, and the sums are of one");
   if (f->done != 0 && f->done != f->G) return refused(f, me + "a run is under way (call it before the first vk_is_run)");
+  if (on && f->real && f->ctx->n_cuts > 0)
+    return refused(f, me + "scale cuts are resident on the context (vk_set_cuts): the predictive sums and the DIC are of the full "
+                           "data vector");
   f->pred_mem.drop(f);
   f->pred_N = 0;
   f->keep_theory = false;

@@ -441,6 +441,21 @@ class Engine:
         blocks = N.f64(blocks)
         self._check(self._lib.vk_set_realisations(self._ctx, N.as_dp(blocks), len(blocks)))
 
+    def set_cuts(self, n_keep=None, index=None, prec=None, logdet=None, eig=None):
+        """Make scale cuts resident next to the realisations (``vk_set_cuts``; the arrays of
+        :func:`victor_amd.cuts.pack_cut_tables`); without arguments, release them."""
+        i32 = C.POINTER(C.c_int32)
+        if n_keep is None:
+            self._check(self._lib.vk_set_cuts(self._ctx, 0, None, None, None, None, None))
+            return
+        n_keep = np.ascontiguousarray(n_keep, dtype=np.int32)
+        index = np.ascontiguousarray(index, dtype=np.int32)
+        prec = N.f64(prec)
+        logdet = None if logdet is None else N.f64(logdet)
+        eig = None if eig is None else N.f64(eig)
+        self._check(self._lib.vk_set_cuts(self._ctx, len(n_keep), n_keep.ctypes.data_as(i32), index.ctypes.data_as(i32), N.as_dp(prec),
+                                          None if logdet is None else N.as_dp(logdet), None if eig is None else N.as_dp(eig)))
+
     def set_model_realisations(self, xi_coef, uni_xi, uni_xic):
         """Upload one xi^r table set per realisation: ``xi_coef[i]``, ``uni_xi[i]``, ``uni_xic[i]`` in the layout of
         ``vk_tables.xi.coef`` / ``uni_xi`` / ``uni_xic`` (``uni_*``: ``None`` for tables without the unified grid); the pairs

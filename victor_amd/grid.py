@@ -417,7 +417,7 @@ def grid_posterior(fit, params, bins=32, ranges=None, fixed=None, prior=None, pa
                 return evaluate(batch_of(x))
         elif realisations is not None:
             def values(x):
-                return realisations.log_likelihood(batch_of(x), **kwargs)[0]
+                return getattr(realisations, "_cross", realisations.log_likelihood)(batch_of(x), **kwargs)[0]
         else:
             def values(x):
                 return fit.log_likelihood_batch(batch_of(x), **kwargs)[0]

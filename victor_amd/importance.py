@@ -1293,7 +1293,7 @@ def importance_posterior(fit, params, proposal=None, n=16384, seed=0, fixed=None
                 return evaluate(batch_of(x))
         elif realisations is not None:
             def values(x):
-                return both(realisations.log_likelihood(batch_of(x), **kwargs))
+                return both(getattr(realisations, "_cross", realisations.log_likelihood)(batch_of(x), **kwargs))
         else:
             def values(x):
                 return both(fit.log_likelihood_batch(batch_of(x), **kwargs))

@@ -279,6 +279,12 @@ class Realisations:
             return lnl[0], chi2[0]
         return lnl, chi2
 
+    def scale_cuts(self, cuts):
+        """These realisations under every cut of ``cuts`` (:class:`victor_amd.cuts.ScaleCut`) at once: a
+        :class:`victor_amd.cuts.CutRealisations` of ``len(cuts) * len(self)`` problems.  Refused with ``paired_model=True``."""
+        from .cuts import from_realisations
+        return from_realisations(self, cuts)
+
     def chi_squared(self, params, **kwargs):
         """The chi-square half of :meth:`log_likelihood` (data vector interpolated in beta, as ``CCFFit.chi_squared``)."""
         return self.log_likelihood(params, **dict(kwargs, beta_interpolation="datavector"))[1]
